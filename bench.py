@@ -6,10 +6,15 @@ One "step" = every rank traces its batch of independent 500x500 edges to complet
 selection, then the final hyper-parameter fit), inputs (gradient image, inits) resident in HBM.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the configuration); `--full` adds everything else the bench measures or
+checks: `roofline` (per-kernel device times), `cpu_baseline`, `secondary` figures, stage profiles, single-edge latency,
+trace quality vs ground truth and, at N > 1, config 4 as stated.  `--dump-outputs DIR` writes the traces of the last timed
+step as .npy files (same arguments -> same inputs: two builds can be compared output for output).
 """
 import argparse
 import json
@@ -88,6 +93,26 @@ def cpu_baseline(N, img_seed, n_traces, per_curve=True):
                        "scipy L-BFGS-B x13, constructor (gradient KDE) included; best of 1 and 16 BLAS threads" % (n_traces, iters),
                 seconds=dt, host_cores=usable_cpus(), ctor_s_per_trace=ctor,
                 value_ctor_excluded=n_traces / max(1e-9, dt - n_traces * ctor))
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, traces, iters):
+    """--dump-outputs: the arrays GP_Edge_Tracing_Batch.finish / run_loop handed the timed path in its last step -- every
+    edge's trace (pixel (row, column) per grid column) and its iterations -- as float64 .npy files in out_dir.  A batch
+    whose traces exceed DUMP_MAX_BYTES is sampled: a fixed, seeded choice of edges (trace_edges.npy says which)."""
+    tr = np.stack([np.asarray(t_) for t_ in traces]).astype(np.float64)
+    it = np.asarray(iters, dtype=np.float64)
+    edges = np.arange(tr.shape[0])
+    per_edge = tr[0].nbytes + 16
+    if per_edge * len(edges) > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // per_edge
+        edges = np.sort(np.random.default_rng(0).choice(len(edges), size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("traces", tr[edges]), ("iterations", it[edges]), ("trace_edges", edges.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log("outputs of the last timed step: %d of %d edges -> %s" % (len(edges), tr.shape[0], out_dir))
 
 
 def log(msg):
@@ -405,6 +430,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (ctor included, 256 edges, "
                     "distinct images, configs 3 and 5)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the bench measures or checks: "
+                    "per-kernel roofline, CPU baseline, secondary figures, stage profiles, single-edge latency, trace quality, "
+                    "config 4 as stated at N > 1 (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step (rank 0's batch) to DIR/<name>.npy: "
+                         "traces (edges x points x (row, column), float64), iterations (per edge), trace_edges (the edges "
+                         "written: all of them, or a fixed seeded sample above %d MB)" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--headline-only", action="store_true", help="print {value, ms_per_step, hip_hw_queues} after the timed steps and stop "
                     "(the child runs of secondary.hw_queues_runtime_default)")
     args = ap.parse_args()
@@ -532,10 +564,42 @@ def main():
         elapsed = float(tt.item())
     total_traces = E * world * args.steps
     value = total_traces / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, traces, iters)
     if args.headline_only:
         if rank == 0:
             print(json.dumps({"value": value, "ms_per_step": 1e3 * elapsed / args.steps, "steps": args.steps, "warmup": args.warmup,
                               "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "objects_in_flight": len(tracers)}))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    headline = {
+        "metric": "edge-traces/sec on 500x500 synthetic images; GP-iter ms (Cholesky+sample)",
+        "value": value, "unit": "edge-traces/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE config 2 edge (500x500 sinusoidal image, RBF sigma_f=75 l=20, N_samples=1000, "
+                               "delta_x=5, pixel_thresh=5) x %d independent edges per GPU and step (config 4's batch of independent edges, sized to fill the GPU), "
+                               "shared gradient image%s" % (E, ", RCCL broadcast" if world > 1 else ""),
+                   "edges_per_gpu": E, "steps_in_flight_per_gpu": n_in_flight, "image": [N, N],
+                   "seeds": "1 + 997 * ((rank * objects + object) * edges + edge): every (edge, iteration) its own RandomState stream", "iterations_per_trace": iters[:4],
+                   "final_fit": "device-resident: standardisation, 13 starts, L-BFGS-B state machines and the batched LML objective "
+                                "all on the GPU (gpet_final_fit_all); no host workers"},
+        "host": {"cpus_usable": usable_cpus(), "cpus_machine": os.cpu_count(), "lbfgs_workers": 0,
+                 "host_threads": depth + 1, "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "note": "the host only enqueues launches and waits: one driver thread per batch object "
+                 "in flight (its device loop, then its converged fits)"},
+        "time_split_s": {"elapsed": elapsed, "steps_in_flight": n_in_flight, "pipelined": pipeline, "pipeline_depth": depth,
+                         "loop_wall_per_thread": loop_s, "fit_wall_per_thread": fit_s,
+                         "loop_wall_mean": (sum(loop_walls) / len(loop_walls)) if loop_walls else None,
+                         "fit_wall_mean": (sum(fit_walls) / len(fit_walls)) if fit_walls else None,
+                         "note": "wall times of a step's device loop and converged fits while the other objects' steps run beside them"},
+        "bcast_grad_ms": 1e3 * t_b,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
@@ -1011,35 +1075,17 @@ def main():
     if not args.no_cpu_baseline and world == 1:  # (reported at N=1 only)
         cpu = cpu_baseline(N, 3, args.cpu_traces)
 
-    out = {
-        "metric": "edge-traces/sec on 500x500 synthetic images; GP-iter ms (Cholesky+sample)",
-        "value": value, "unit": "edge-traces/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE config 2 edge (500x500 sinusoidal image, RBF sigma_f=75 l=20, N_samples=1000, "
-                               "delta_x=5, pixel_thresh=5) x %d independent edges per GPU and step (config 4's batch of independent edges, sized to fill the GPU), "
-                               "shared gradient image%s" % (E, ", RCCL broadcast" if world > 1 else ""),
-                   "edges_per_gpu": E, "steps_in_flight_per_gpu": n_in_flight, "image": [N, N],
-                   "seeds": "1 + 997 * ((rank * objects + object) * edges + edge): every (edge, iteration) its own RandomState stream", "iterations_per_trace": iters[:4],
-                   "final_fit": "device-resident: standardisation, 13 starts, L-BFGS-B state machines and the batched LML objective "
-                                "all on the GPU (gpet_final_fit_all); no host workers"},
-        "host": {"cpus_usable": usable_cpus(), "cpus_machine": os.cpu_count(), "lbfgs_workers": 0,
-                 "host_threads": depth + 1, "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "note": "the host only enqueues launches and waits: one driver thread per batch object "
-                 "in flight (its device loop, then its converged fits)"},
+    out = dict(headline)
+    out.update({
         "secondary": secondary,
         "gp_iter_ms": {"batch_of_%d" % E: sum(stage_ms[k] for k in STAGES[:4]),
                        "single_edge": sum(one_ms[k] for k in STAGES[:4])},
         "stage_ms_batch": stage_ms, "stage_ms_single_edge": one_ms,
-        "time_split_s": {"elapsed": elapsed, "steps_in_flight": n_in_flight, "pipelined": pipeline, "pipeline_depth": depth,
-                         "loop_wall_per_thread": loop_s, "fit_wall_per_thread": fit_s,
-                         "loop_wall_mean": (sum(loop_walls) / len(loop_walls)) if loop_walls else None,
-                         "fit_wall_mean": (sum(fit_walls) / len(fit_walls)) if fit_walls else None,
-                         "note": "wall times of a step's device loop and converged fits while the other objects' steps run beside them"},
         "single_edge": {"traces_per_s": 1.0 / single_s, "ms_per_trace": 1e3 * single_s,
                         "runs_ms": [round(1e3 * v, 3) for v in single_runs], "note": "median of five traces of one edge"},
-        "trace_mse_vs_truth": mse, "bcast_grad_ms": 1e3 * t_b, "config4_literal_measured": c4_measured,
+        "trace_mse_vs_truth": mse, "config4_literal_measured": c4_measured,
         "roofline": roofline, "cpu_baseline": cpu,
-    }
+    })
     if cpu:
         out["speedup_vs_cpu_port"] = value / cpu["value"]
     print(json.dumps(out))

@@ -144,16 +144,36 @@ def _device_disassembly(tmp_path):
 
 
 def _functions(dis, name_part):
-    out, cur, name = {}, None, None
+    """{symbol: [(address, instruction)]} of the functions whose symbol contains `name_part` (the address is the one in the
+    disassembler's comment: branch targets are resolved against it)."""
+    out, cur = {}, None
     for line in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
         if m:
-            name = m.group(1)
-            cur = out.setdefault(name, []) if name_part in name else None
+            cur = out.setdefault(m.group(1), []) if name_part in m.group(1) else None
             continue
         if cur is not None and line.startswith("\t"):
-            cur.append(re.sub(r"\s+", " ", line.strip().split("//")[0].strip()))
+            m = re.match(r"^\t(.*?)\s*//\s*([0-9A-Fa-f]+):", line)
+            if m:
+                cur.append((int(m.group(2), 16), re.sub(r"\s+", " ", m.group(1).strip())))
     return out
+
+
+def _successors(code, k, index_of):
+    """Indices of the instructions that can execute after code[k]: fall-through and / or the target of a scalar branch
+    (SIMM16 in dwords, relative to the next instruction)."""
+    addr, ins = code[k]
+    op = ins.split(" ")[0]
+    nxt = [k + 1] if k + 1 < len(code) else []
+    if op == "s_endpgm":
+        return []
+    if op == "s_branch" or op.startswith("s_cbranch_"):
+        imm = int(ins.split(" ")[1], 0)
+        imm = imm - 65536 if imm >= 32768 else imm
+        target = index_of[addr + 4 + 4 * imm]
+        return [target] if op == "s_branch" else nxt + [target]
+    assert not op.startswith(("s_setpc", "s_swappc")), ins  # (no indirect jumps in the kernel: every path is followed)
+    return nxt
 
 
 def test_isa_every_wave_drains_its_row_stores_before_a_pair_slot_is_published(tmp_path):
@@ -161,14 +181,44 @@ def test_isa_every_wave_drains_its_row_stores_before_a_pair_slot_is_published(tm
     other three waves wrote (write-through stores, another workgroup on another XCD reads them next) must have COMPLETED by
     then.  A workgroup barrier orders nothing in global memory and the compiler puts no wait in front of it on its own
     (round 4's shipped object had none -- advisor finding): every wave executes s_waitcnt vmcnt(0) between its last row
-    store and the barrier.  Checked in the ISA of both template variants."""
+    store and the barrier.  Checked in the ISA of both template variants, on every control-flow path from a row store to the
+    publishing barrier (the one whose straight-line code goes on to the ticket / slot atomics): the compiler may lay the
+    update loop out after that barrier and branch back to it, so program order alone does not show the paths."""
+    row_store = r"(global_store_dwordx2 \S+ a\[\d+:\d+\], off|flat_store_dwordx2 \S+ a\[\d+:\d+\]) sc1$"
     fns = _functions(_device_disassembly(tmp_path), "k_oj_persist")
     assert len(fns) == 2, list(fns)
-    for name, ins in fns.items():
-        stores = [i for i, s in enumerate(ins) if re.match(r"(global_store_dwordx2 \S+ a\[\d+:\d+\], off|flat_store_dwordx2 \S+ a\[\d+:\d+\]) sc1$", s)]
+    for name, code in fns.items():
+        ins = [s for _, s in code]
+        index_of = {a: k for k, (a, _) in enumerate(code)}
+        stores = [k for k, s in enumerate(ins) if re.match(row_store, s)]
         assert len(stores) >= 16, (name, len(stores))  # the row stores of the update (16 per wave and column batch)
-        last = stores[-1]
-        bar = next(i for i in range(last, len(ins)) if ins[i].startswith("s_barrier"))
-        between = ins[last + 1:bar]
-        assert any(s.startswith("s_waitcnt") and "vmcnt(0)" in s for s in between), (name, between)
-        assert not any(s.startswith(("global_store", "flat_store", "buffer_store")) for s in between), (name, between)
+
+        def publishes(k):
+            for s in ins[k + 1:]:
+                if s.startswith("s_barrier"):
+                    return False
+                if re.match(r"(global|flat)_atomic_add ", s):
+                    return True
+            return False
+        publish = {k for k, s in enumerate(ins) if s.startswith("s_barrier") and publishes(k)}
+        assert publish, name
+        # walk every path from every row store; state = (instruction, a store not yet drained by s_waitcnt vmcnt(0))
+        todo, seen, reached = [(k, True) for k in stores], set(), set()
+        while todo:
+            k, pending = todo.pop()
+            for j in _successors(code, k, index_of):
+                s, p = ins[j], pending
+                if s.startswith("s_waitcnt") and "vmcnt(0)" in s:
+                    p = False
+                elif re.match(row_store, s):
+                    p = True
+                else:
+                    assert not s.startswith(("global_store", "flat_store", "buffer_store")), (name, j, s)
+                if j in publish:
+                    reached.add(j)
+                    assert not p, (name, ins[max(0, j - 8):j + 1])
+                    continue
+                if (j, p) not in seen:
+                    seen.add((j, p))
+                    todo.append((j, p))
+        assert reached, name  # (the walk did reach the publishing barrier)

@@ -106,7 +106,7 @@ def test_host_start_points_are_the_reference_restarts():
 
 
 def test_committed_bench_line_keeps_the_driver_contract():
-    """profiles/rNN_bench_n1.json (the latest round's) is a bench.py output committed with the code: it must carry every
+    """profiles/rNN_bench_n1.json (the latest round's) is a `bench.py --full` output committed with the code: it must carry every
     field of the driver's contract (metric/value/unit/..., roofline{...}, cpu_baseline{...}) with sane types."""
     import json
     import os

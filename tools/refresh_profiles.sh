@@ -9,9 +9,9 @@ R=${2:-r05}
 O=gpurun_out/prof
 rm -rf $O gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_lml_f gpurun_out/pmc_lml_w
 mkdir -p $O
-echo "== bench"; python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
+echo "== bench"; python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json
 echo "== bench under rocprofv3 --kernel-trace --stats"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python3 bench.py > $O/bench_traced.json 2> $O/bench_traced.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_trace -- python3 bench.py --full > $O/bench_traced.json 2> $O/bench_traced.err
 echo "== stages under rocprofv3 --kernel-trace --stats"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stage_trace -- python3 tools/prof_stages.py $E 5 > $O/stages.log 2>&1
 echo "== converged fits alone under rocprofv3 --kernel-trace"
