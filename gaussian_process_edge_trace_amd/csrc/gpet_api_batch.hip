@@ -200,7 +200,7 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
     E.z_ring = (E.z_cols >= Lg && Lg > 128) ? 2 : (B <= 64 ? 16 : 9);
     // small batches are bound by the chain of Jacobi rounds: their rotations are logged and the eigenvectors formed by a
     // second kernel (k_jacobi_wpass); 40 sweeps x (m - 1) rounds x m / 2 pairs x 16 bytes = 2.9 MB per edge at rank 96
-    const int jlog_max_b = option("jlog_max_b");  // (32: the rotation-log form pays while the chain of rounds is the time)
+    const int jlog_max_b = opt(Opt::jlog_max_b);  // (32: the rotation-log form pays while the chain of rounds is the time)
     E.jlog_cap = (B <= jlog_max_b && E.r_cap <= 96) ? 40 : 0;
     E.kernel_type = p.kernel_type;
     E.nu_code = p.kernel_type == GPET_KERNEL_MATERN ? nu_to_code(p.nu) : 2;
@@ -288,23 +288,7 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   HIPCHK(c, hipMalloc(&b->d_minmax, sizeof(unsigned int) * 2 * (size_t)B));
   {
     // (the stream the normals run ahead of the loop on: default priority -- lowest / highest were measured, +-0)
-    // Option side_own_queue: the HIP runtime maps a process's streams onto a pool of GPU_MAX_HW_QUEUES hardware queues, and a
-    // batch whose look-ahead stream lands on the queue of its own loop runs the two IN ORDER -- the loop then stands still for
-    // every 3 ms generator launch (a 32-edge loop 11.8 or 15.9 ms by luck, in a process that has created other contexts
-    // before).  A stream created with a CU mask gets a hardware queue of its own from the runtime: with all CUs enabled it is
-    // an ordinary stream that shares its queue with nobody.
-    bool made = false;
-    if (option("side_own_queue")) {  // (off by default: measured, see the option's description)
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) {
-        const unsigned int words = (unsigned int)((prop.multiProcessorCount + 31) / 32);
-        std::vector<uint32_t> mask(words, 0xFFFFFFFFu);
-        if (prop.multiProcessorCount % 32) mask[words - 1] = (1u << (prop.multiProcessorCount % 32)) - 1u;
-        made = hipExtStreamCreateWithCUMask(&b->side, words, mask.data()) == hipSuccess;
-        if (!made) (void)hipGetLastError();
-      }
-    }
-    if (!made) HIPCHK(c, hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
   }
   {
     int pr_least = 0, pr_greatest = 0;
@@ -346,7 +330,7 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   // structured loop path: eigenbasis of the grid's correlation matrix, once per edge.  Usable when the
   // LDS Jacobi applies (capacity <= 96) and every init x lies on the grid; option "struct_path" = 0 disables it.
   b->structured = false;
-  if (!any_big && option("struct_path")) {
+  if (!any_big && opt(Opt::struct_path)) {
     bool ok = true;
     // without fix_endpoints the pixel selection admits every image column (gpet.py:655-657 only filters when it is
     // set), so the loop can accept observations outside [x_st, x_en] unless the edge spans the whole image: those are
@@ -364,19 +348,17 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
       // a power of two -- so x_st is part of the match; the amplitude is not: the matrix has unit amplitude).  It is computed
       // for the first edge of every such class only (a batch of 1 024 equal edges: one factorisation instead of 1 024, 7.5 ms
       // of the constructor) and the others read that edge's copy, which then stays in L2 for the whole batch (k_struct_H
-      // gathers its rows, k_struct_rows streams it: 288 KB per edge at rank 72, Lg 500).  Option "shared_basis" = 0: every
-      // edge computes and keeps its own.
+      // gathers its rows, k_struct_rows streams it: 288 KB per edge at rank 72, Lg 500).
       std::vector<int> rep_of((size_t)B), reps;
       for (int e = 0; e < B; ++e) {
         const EdgeDev& E = b->h_edges[e];
         int found = -1;
-        if (option("shared_basis"))
-          for (size_t k = reps.size() > 8 ? reps.size() - 8 : 0; k < reps.size() && found < 0; ++k) {  // (batches are homogeneous or nearly so: a short search)
-            const EdgeDev& F = b->h_edges[reps[k]];
-            if (F.Lg == E.Lg && F.x_st == E.x_st && F.kernel_type == E.kernel_type && F.nu_code == E.nu_code && F.nu_gen == E.nu_gen &&
-                F.length_scale == E.length_scale && F.r_cap == E.r_cap)
-              found = reps[k];
-          }
+        for (size_t k = reps.size() > 8 ? reps.size() - 8 : 0; k < reps.size() && found < 0; ++k) {  // (batches are homogeneous or nearly so: a short search)
+          const EdgeDev& F = b->h_edges[reps[k]];
+          if (F.Lg == E.Lg && F.x_st == E.x_st && F.kernel_type == E.kernel_type && F.nu_code == E.nu_code && F.nu_gen == E.nu_gen &&
+              F.length_scale == E.length_scale && F.r_cap == E.r_cap)
+            found = reps[k];
+        }
         if (found < 0) {
           found = e;
           reps.push_back(e);
@@ -761,15 +743,16 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
 
 // the batch's own option table (a copy of the process-wide one taken at gpet_batch_create): returns like gpet_set_option
 int gpet_batch_set_option(gpet_batch* b, const char* name, int value) {
-  if (!b) return -1;
-  int prev = 0, idx = -1;
-  for (int i = 0; i < option_count(); ++i)
-    if (name && strcmp(option_def(i).name, name) == 0) idx = i;
-  if (idx < 0 || option_set_in(&b->opts, name, value, &prev) != 0) return -1;
-  return prev < 0 ? option_def(idx).hi + 1 : prev;
+  const int i = option_find(name);
+  if (!b || i < 0) return -1;
+  const int prev = option_set(&b->opts, i, value);
+  return prev < 0 ? option_def(i).hi + 1 : prev;
 }
 int gpet_batch_get_option(const gpet_batch* b, const char* name, int* value) {
-  return (b && option_get_in(&b->opts, name, value) == 0) ? GPET_OK : GPET_ERR_BAD_ARG;
+  const int i = option_find(name);
+  if (!b || i < 0) return GPET_ERR_BAD_ARG;
+  if (value) *value = option_get(&b->opts, i);
+  return GPET_OK;
 }
 
 int gpet_batch_set_rng(gpet_batch* b, int mode) {
@@ -818,7 +801,7 @@ static int batch_reset(gpet_batch* b, bool next_frame) {
   b->norm_issued = 0;
   HIPCHK(c, hipSetDevice(c->device));
   if (b->bd.r_cap > 96) {  // (any-rank batches keep the last factor rows in a ring)
-    if (next_frame && option("oj_warm")) {  // where every edge's last rows are, before the iteration counters go
+    if (next_frame && opt(Opt::oj_warm)) {  // where every edge's last rows are, before the iteration counters go
       int rc = fetch_all_scalars(b);
       if (rc) return rc;
       std::vector<int> iters((size_t)b->B);

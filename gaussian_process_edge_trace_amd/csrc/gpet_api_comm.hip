@@ -97,7 +97,7 @@ int gpet_comm_create(gpet_ctx* ctx, const void* id128, int world, int rank, gpet
   c->device = ctx->device;
   c->world = world;
   c->rank = rank;
-  if (world > 1 || option("comm_force_rccl")) {  // (a single rank needs no communicator: its collectives are copies)
+  if (world > 1 || opt(Opt::comm_force_rccl)) {  // (a single rank needs no communicator: its collectives are copies)
     Rccl& r = rccl();
     if (!r.why.empty()) {
       delete c;

@@ -4,11 +4,10 @@
 
 // Host waits.  hipStreamSynchronize spins on a CPU core; with one process per GPU and a few driver threads per process
 // (device loop + converged fits in flight) eight ranks would keep 32 threads spinning on a node's cores.  In blocking
-// mode (gpet_set_option("blocking_sync", 1); default: on when WORLD_SIZE > 1, i.e. under torch.distributed.run) a wait
+// mode (option blocking_sync = 1; default: on when WORLD_SIZE > 1, i.e. under torch.distributed.run) a wait
 // is an event created with hipEventBlockingSync: the thread sleeps until the GPU signals.
-static int opt_blocking_sync() {
-  static const int i_ = option_index("blocking_sync");
-  int& v = option_at(i_);
+static int blocking_sync() {
+  const int v = opt(Opt::blocking_sync);
   if (v >= 0) return v;
   static const int by_world = [] {  // (WORLD_SIZE is torch.distributed's variable, not a switch of this library)
     const char* w = getenv("WORLD_SIZE");
@@ -17,7 +16,7 @@ static int opt_blocking_sync() {
   return by_world;
 }
 hipError_t gpet_wait(hipStream_t st) {
-  if (!opt_blocking_sync()) return hipStreamSynchronize(st);
+  if (!blocking_sync()) return hipStreamSynchronize(st);
   static thread_local hipEvent_t ev = nullptr;  // (per host thread: waits from different driver threads do not share it)
   static thread_local int ev_dev = -1;
   int dev = 0;
@@ -76,29 +75,14 @@ int fin_lattice(const double* x, int n, double* hinv) {
   return (int)mr;
 }
 
-// converged fits: every (edge, restart) problem from start to optimum in one workgroup (k_lml16_fit) instead of
-// lock-step rounds over all running problems: -1 = for problem sets resident at once (<= 1024), 0 = never, 1 = always
-// (where the training sets allow it)
-int& opt_fit_persistent() {
-  static const int i_ = option_index("fit_persistent");
-  int& v = option_at(i_);
-  return v;
-}
-
-static int& opt_rng_chunked() {
-  static const int i_ = option_index("rng_chunked");
-  int& v = option_at(i_);  // -1: by launch shape
-  return v;
-}
-
 // One sequential walk per stream: the register-resident generator (four streams per wave, gpet_rng.hip) when the batch is
 // homogeneous and the launch has enough streams to fill the GPU with single waves (2 048 = half of its SIMDs; a wave of
 // four streams takes ~2.5 ms against 0.6 ms for a three-wave workgroup per stream, so small launches keep the old kernel),
 // else one workgroup per stream (k_mt_normals).  The same numbers either way.
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l,
                                      int add_iter, int iter_abs, int n_ahead, int z_store) {
-  const int opt = gpet_opt_rng4();
-  if (b->bd.rng4 && (opt > 0 || (opt < 0 && (long long)B_l * n_ahead >= 2048)))
+  const int o = opt(Opt::rng4);
+  if (b->bd.rng4 && (o > 0 || (o < 0 && (long long)B_l * n_ahead >= 2048)))
     return launch_normals4(st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store, b->bd.Lg, b->bd.S, b->bd.z_cols);
   return launch_normals(st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store);
 }
@@ -115,11 +99,11 @@ int normals_auto(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const
   }
   const int streams = B_l * n_ahead;
   const int nc = mtj_chunks((long long)b->bd.S * b->bd.Lg);
-  const int opt = opt_rng_chunked();
-  const bool force4 = gpet_opt_rng4() > 0 && b->bd.rng4;  // (tests: the register-resident generator on any launch shape)
+  const int o = opt(Opt::rng_chunked);  // -1: by launch shape
+  const bool force4 = opt(Opt::rng4) > 0 && b->bd.rng4;  // (tests: the register-resident generator on any launch shape)
   // (the chunked form works in the batch's ONE jump workspace: a launch that runs beside another chunked launch of the same batch
   //  -- the tail of a small batch's first normals on the fit stream, gpet_trace_iterate -- must take the sequential kernel)
-  const bool chunked = allow_chunked && !force4 && nc >= 2 && (opt > 0 || (opt < 0 && streams <= 32 && nc >= 4));
+  const bool chunked = allow_chunked && !force4 && nc >= 2 && (o > 0 || (o < 0 && streams <= 32 && nc >= 4));
   if (!chunked) {
     HIPCHK(c, launch_normals_seq(b, st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store));
     return GPET_OK;
@@ -148,15 +132,19 @@ extern "C" {
 int gpet_abi_version(void) { return GPET_ABI_VERSION; }
 
 int gpet_set_option(const char* name, int value) {
-  int prev = 0, idx = -1;
-  for (int i = 0; i < option_count(); ++i)
-    if (name && strcmp(option_def(i).name, name) == 0) idx = i;
-  if (idx < 0 || option_set(name, value, &prev) != 0) return -1;
+  const int i = option_find(name);
+  if (i < 0) return -1;
+  const int prev = option_set(nullptr, i, value);
   // ("chosen automatically", -1, is reported as the option's largest value + 1: a negative return means "unknown name")
-  return prev < 0 ? option_def(idx).hi + 1 : prev;
+  return prev < 0 ? option_def(i).hi + 1 : prev;
 }
 
-int gpet_get_option(const char* name, int* value) { return option_get(name, value) == 0 ? GPET_OK : GPET_ERR_BAD_ARG; }
+int gpet_get_option(const char* name, int* value) {
+  const int i = option_find(name);
+  if (i < 0) return GPET_ERR_BAD_ARG;
+  if (value) *value = option_get(nullptr, i);
+  return GPET_OK;
+}
 
 int gpet_option_count(void) { return option_count(); }
 
@@ -164,7 +152,7 @@ int gpet_option_info(int index, const char** name, int* value, int* def, int* lo
   if (index < 0 || index >= option_count()) return GPET_ERR_BAD_ARG;
   const OptionDef& d = option_def(index);
   if (name) *name = d.name;
-  if (value) (void)option_get(d.name, value);
+  if (value) *value = option_get(nullptr, index);
   if (def) *def = d.def;
   if (lo) *lo = d.lo;
   if (hi) *hi = d.hi;

@@ -272,8 +272,10 @@ static int lb_rounds(gpet_batch* b, int P, int n_max, int lag_cap, const LbCfg& 
   // (for problem sets that are resident all at once -- 4 workgroups on each of 256 CUs -- the chain of a problem's ~50
   //  evaluations is what takes the time: 3.2 instead of 4.8 ms for a single edge; bigger sets are throughput-bound and a
   //  workgroup that keeps its registers through the single-threaded state machine costs more than the rounds' launches:
-  //  32 instead of 23 ms of objective time per 13 312 problems)
-  const bool persistent = opt_fit_persistent() > 0 || (opt_fit_persistent() < 0 && P <= 1024);
+  //  32 instead of 23 ms of objective time per 13 312 problems).  Option fit_persistent: -1 = by that rule, 0 = never,
+  //  1 = always (where the training sets allow it)
+  const int fp = opt(Opt::fit_persistent);
+  const bool persistent = fp > 0 || (fp < 0 && P <= 1024);
   if (persistent && lml16_fit_applies(n_max, lag_cap)) {
     // one launch: a workgroup per problem runs objective and state machine until the problem is done (k_lml16_fit)
     HIPCHK(c, hipMemsetAsync(b->lb_count, 0, 4 * sizeof(int), st));

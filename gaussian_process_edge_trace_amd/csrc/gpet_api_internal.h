@@ -110,7 +110,7 @@ struct gpet_batch {
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it
 };
 // first statement of every entry point that works on a batch: its option table for the calling thread
-#define GPET_BATCH_SCOPE(b) OptionScope gpet_opt_scope_((b) ? &(b)->opts : nullptr)
+#define GPET_BATCH_SCOPE(b) OptionScope option_scope_((b) ? &(b)->opts : nullptr)
 
 // ---- helpers defined in gpet_api_ctx.hip ----------------------------------------------------------------------------------
 hipError_t gpet_wait(hipStream_t st);  // host wait on a stream: spinning or sleeping (option blocking_sync)
@@ -133,7 +133,6 @@ struct Carver {  // lays buffers out in one arena (256-byte aligned); with base 
   }
 };
 int fin_lattice(const double* x, int n, double* hinv);
-int& opt_fit_persistent();
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
                               int iter_abs, int n_ahead, int z_store);
 int normals_auto(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter, int iter_abs,
@@ -143,6 +142,6 @@ int fetch_all_scalars(gpet_batch* b);
 int check_device_status(gpet_batch* b);
 // what the loop's generator stores of a sample row: the r0 (rounded to 4) leading normals a structured batch multiplies
 static inline int loop_z_store(const gpet_batch* b) {
-  if (!b->structured || b->bd.r0_max < 1 || option("z_store_full")) return 0;
+  if (!b->structured || b->bd.r0_max < 1) return 0;
   return (b->bd.r0_max + 3) & ~3;
 }

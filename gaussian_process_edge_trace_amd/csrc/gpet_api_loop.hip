@@ -10,7 +10,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(b->d_seeds, base_seeds, sizeof(uint32_t) * b->B, hipMemcpyHostToDevice, c->stream));
   // Normals: the seeds of upcoming iterations are known (gpet.py:839), so the RNG stream runs ahead of the loop on
-  // its own HIP stream, one launch per iteration, `look` iterations ahead (gpet_set_option("rng_lookahead", n), default
+  // its own HIP stream, one launch per iteration, `look` iterations ahead (option rng_lookahead = n, default
   // 1: the draws of iteration k+1 are enqueued when iteration k starts and run next to it), never past the horizon of
   // the iterations enqueued together.  An edge that finishes still gets the draws already enqueued for it, so a deeper
   // look-ahead only wastes generator work (n = 4: 19 % of it; measured loop time of a batch alone: n = 1, 2, 4 within
@@ -19,7 +19,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   // of 179 ms per loop of 1024 edges, 70 instead of 56 ms at 256.  A ring slot is refilled only after the sample GEMM
   // that read it (one ring earlier) has completed.
   const int ring = b->bd.z_ring;
-  int look = gpet_opt_rng_lookahead();
+  int look = opt(Opt::rng_lookahead);  // -1: by batch size
   // Automatic (default): a batch that fills the GPU is throughput-bound in the generator, so one iteration ahead wastes
   // the least; a small batch is LATENCY-bound in it -- a stream is sequential, one workgroup per (edge, iteration),
   // 2.1 ms for the 500 k normals of a 500-column edge against 0.9 ms for the rest of an iteration -- so the streams of
@@ -79,7 +79,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
       // of ALL the iterations of a group in one launch on the loop's own stream (batches above 64 edges: the default -- the
       // launch fills the GPU and runs beside nothing, 157-159 instead of 161-162 ms per step of 1 024 traces); 1 = one
       // iteration per launch on the loop's stream (an experiment: 179 ms)
-      const int rng_inline_opt = option("rng_inline");
+      const int rng_inline_opt = opt(Opt::rng_inline);
       const int rng_inline = rng_inline_opt >= 0 ? rng_inline_opt : (deep ? 0 : 2);
       if (rng_inline == 1) {  // experiment: the normals of this iteration on the loop's own stream, overlapping nothing
         int rcn = normals_auto(b, c->stream, edges_l, B_l, seeds_l, 1, cur, 1, loop_z_store(b));
@@ -100,7 +100,8 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
       //  a 32-edge batch take 2.4 ms, the sequential launch that refills the ring 3 ms -- every refill stalled the loop, and by how
       //  much depended on when the launch got going: 13.5 or 16.7 ms per loop from one run to the next.  At 6 the launch has a
       //  3.6 ms lead.)
-      const int refill_at = option("rng_refill_at") < 0 ? (look > 2 ? look - 2 : look / 2) : option("rng_refill_at");
+      const int refill_opt = opt(Opt::rng_refill_at);
+      const int refill_at = refill_opt < 0 ? (look > 2 ? look - 2 : look / 2) : refill_opt;
       if (!rng_inline && deep && b->norm_issued - cur <= refill_at) {
         // small batch: the streams of the next `n` iterations in ONE launch (blockIdx.x = iteration), side by side.
         // Their ring slots were last read by the sample GEMMs of iterations <= cur - 1 (outstanding + n <= ring).
@@ -115,7 +116,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
         // the sequential launch of the iterations after them runs beside them on the (idle until the converged fits) fit stream.
         int head = 0;
         if (j == 0 && cur == 0 && B_l >= 2 && B_l <= 32 && b->rng_mode == 0) {
-          head = option("rng_head");
+          head = opt(Opt::rng_head);
           if (head < 0) head = 4;
           if (head > n - 1) head = n - 1;
           if (head < 0) head = 0;
@@ -166,7 +167,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
       HIPCHK(c, launch_sample(c->stream, edges_l, B_l, b->bd, rank_max));
       HIPCHK(c, hipEventRecord(b->ev_gemm[cur % 16], c->stream));
       // loop form: the density stays raw and band-limited in HBM; the pixel kernels normalise on the fly
-      const int tail_opt = option("loop_fused_tail");
+      const int tail_opt = opt(Opt::loop_fused_tail);
       if ((tail_opt > 0 || (tail_opt < 0 && b->B <= 64)) && score_tail_applies(b->bd)) {
         HIPCHK(c, launch_score_kde_fused_tail(c->stream, edges_l, B_l, b->bd));  // (small batches: three launches fewer per iteration)
       } else {
@@ -197,7 +198,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
     // of a 6.6 ms single-edge loop on the two.  The observation sets grow at a steady rate (pixel_thresh or a few more per
     // iteration), so the next group is what the slowest running edge still needs at the rate of the group
     // just finished: usually ONE more group that ends on the last iteration.
-    if (b->B <= 64 && option("loop_adaptive_groups")) {
+    if (b->B <= 64) {
       if ((int)b->h_nobs_prev.size() != b->B) b->h_nobs_prev.assign(b->B, 0);
       int need = 1;
       for (int e = 0; e < b->B; ++e) {

@@ -573,11 +573,6 @@ __global__ void __launch_bounds__(64) k_pcx_fin(EdgeDev* edges, int steps, int n
 // products on the f64 matrix cores (k_ojw_gemm: 64 x 64 tiles, K in chunks of 32 through LDS), a blocked Cholesky
 // (k_ojw_chol_*: 64-wide panels), one copy.  Only for rows of full rank (Matern); a non-positive pivot falls back to the
 // pivoted Cholesky, whose launches are no-ops otherwise.  T = A Sigma lives in Gt, M' and L' in G, X in Gt and then G.
-int& gpet_opt_oj_warm() {
-  static const int i_ = option_index("oj_warm");
-  int& v = option_at(i_);
-  return v;
-}
 __device__ __forceinline__ const double* ojw_source(const EdgeDev& E, int warm) {
   const gpet_scalars* sc = E.sc;
   const int k = sc->iter;
@@ -1600,14 +1595,14 @@ __global__ void __launch_bounds__(256) k_oj_rows(EdgeDev* edges) {
 // the warm start's launches (after the pivoted Cholesky's init kernel, before its blocks): no-ops for an edge without
 // usable previous rows
 static void launch_oj_warm(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
-  const int warm = gpet_opt_oj_warm();
+  const int warm = opt(Opt::oj_warm);
   if (!warm || bd.Lg > bd.r_cap) return;
   const int n = bd.Lg, nt = cdiv_h(n, 64);
   hipLaunchKernelGGL(k_ojw_begin, dim3(cdiv_h(n, 4), B), dim3(256), 0, st, d_edges, warm);
   hipLaunchKernelGGL(k_ojw_gemm<0>, dim3(nt, nt, B), dim3(256), 0, st, d_edges, warm);
   hipLaunchKernelGGL(k_ojw_gemm<1>, dim3(nt, nt, B), dim3(256), 0, st, d_edges, warm);
   for (int k0 = 0; k0 < n; k0 += 64) {
-    hipLaunchKernelGGL(k_ojw_chol_diag, dim3(1, B), dim3(256), 0, st, d_edges, k0, (k0 == 0 && option("oj_warm_fail")) ? 1 : 0);
+    hipLaunchKernelGGL(k_ojw_chol_diag, dim3(1, B), dim3(256), 0, st, d_edges, k0, (k0 == 0 && opt(Opt::oj_warm_fail)) ? 1 : 0);
     const int below = cdiv_h(n - k0 - 64, 64);
     if (below > 0) {
       hipLaunchKernelGGL(k_ojw_chol_trsm, dim3(below, B), dim3(256), 0, st, d_edges, k0);
@@ -1628,7 +1623,7 @@ static void launch_oj_warm(hipStream_t st, EdgeDev* d_edges, int B, const BatchD
 // either way, so the prior eigenbasis of the structured loop (whose bits every trace inherits) and edges of up to 1 024
 // columns stay on k_pchol.
 bool pchol_multi_applies(const BatchDims& bd) {
-  const int mode = option("pchol_multi");
+  const int mode = opt(Opt::pchol_multi);
   return bd.Lg > 1024 && bd.r_cap <= 96 && mode != 0 && (mode == 1 || cdiv_h(bd.Lg, PCX_COLS) <= 64);
 }
 hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
@@ -1637,7 +1632,7 @@ hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const Bat
   const int steps = bd.r_cap < bd.Lg ? bd.r_cap : bd.Lg;
   PcxArgs px_args;
   memset(&px_args, 0, sizeof px_args);
-  if (option("pchol_multi") == 1) {
+  if (opt(Opt::pchol_multi) == 1) {
     hipLaunchKernelGGL(k_pcx_init, dim3(nw, B), dim3(256), 0, st, d_edges, nw);
     for (int t = 0; t < steps; ++t) hipLaunchKernelGGL((k_pcx_step<false>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, t, nw);
     hipLaunchKernelGGL(k_pcx_fin, dim3(B), dim3(64), 0, st, d_edges, steps, nw);
@@ -1657,7 +1652,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
   // small batches: the per-edge pointers travel in the kernel arguments (h_edges = host copy of the edge table)
   OjArgs oj_args;
   memset(&oj_args, 0, sizeof oj_args);
-  const bool use_args = h_edges != nullptr && B <= OJ_ARGS_MAXB && option("oj_args");
+  const bool use_args = h_edges != nullptr && B <= OJ_ARGS_MAXB && opt(Opt::oj_args);
   if (use_args)
     for (int e = 0; e < B; ++e) {
       OjEdge& d = oj_args.e[e];
@@ -1689,7 +1684,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
       d.r_cap = h.r_cap;
       d.factor_injected = h.factor_injected;
     }
-  if (nw <= 64 && !option("pcx_one_pivot")) {
+  if (nw <= 64 && !opt(Opt::pcx_one_pivot)) {
     // blocks of up to PCB_NB pivots; rejected candidates cost extra blocks, so the budget is generous (a block that
     // finds the factorisation finished returns at once)
     hipLaunchKernelGGL(k_pcb_init, dim3(nw, B), dim3(64), 0, st, d_edges, nw);
@@ -1709,11 +1704,11 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
     }
     hipLaunchKernelGGL(k_pcx_fin, dim3(B), dim3(64), 0, st, d_edges, steps, nw);
   }
-  const int max_sweeps = gpet_opt_oj_max_sweeps();
+  const int max_sweeps = opt(Opt::oj_max_sweeps);
   // LDS staging costs a workgroup a whole CU (131 KB): worth it while a round's workgroups (pairs x edges) fit the
   // chip's 256 CUs side by side (one edge: 64 pairs; measured 54 vs 61 ms per factor); a bigger batch runs two
   // register-fed workgroups per CU instead (8 edges: 85 vs 106 ms)
-  const bool staged_lds_ok = bd.Lg <= OJ_STAGE_MAX && option("oj_stage");
+  const bool staged_lds_ok = bd.Lg <= OJ_STAGE_MAX && opt(Opt::oj_stage);
   const bool staged = staged_lds_ok && (long long)(nblk / 2) * B <= 256;
   const size_t stage_lds = (size_t)OJ_M * (((bd.Lg + 31) & ~31) + 2) * sizeof(double);
   // k_oj_persist with the panel staged one 512-column half at a time (even widths above 512 columns): 66 KB instead of 131 KB,
@@ -1727,7 +1722,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
     if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess || n_cus < 1) n_cus = 256;
     (void)hipGetLastError();
   }
-  const int half_opt = option("oj_half_stage");
+  const int half_opt = opt(Opt::oj_half_stage);
   const int half_stage = (bd.lg_even && bd.Lg > 512 && (half_opt > 0 || (half_opt < 0 && (long long)(nblk / 2) * B > n_cus))) ? 1 : 0;
   const size_t persist_lds = half_stage ? (size_t)OJ_M * 514 * sizeof(double) : stage_lds;
   if (staged) {
@@ -1740,7 +1735,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
       attr_done[dev] = 1;
     }
   }
-  const double tol2 = pow(10.0, -2.0 * (double)gpet_opt_oj_tol_exp());
+  const double tol2 = pow(10.0, -2.0 * (double)opt(Opt::oj_tol_exp));
   // staged: the rounds and sweeps in ONE launch (k_oj_persist: pair slots by ticket -- no residency requirement, so the
   // grid is sized to what the device holds at once and a workgroup serves several slots per round when the batch has more
   // slots than that; beyond four slots per workgroup and round the round launches' two register-fed workgroups per CU
@@ -1750,7 +1745,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
   static bool persist_attr[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (staged_lds_ok && gpet_opt_oj_persist() && dev >= 0 && dev < 64 && (!persist_cap[dev] || persist_cap_lds[dev] != persist_lds)) {
+  if (staged_lds_ok && opt(Opt::oj_persist) && dev >= 0 && dev < 64 && (!persist_cap[dev] || persist_cap_lds[dev] != persist_lds)) {
     if (!persist_attr[dev]) {
       (void)hipFuncSetAttribute((const void*)k_oj_persist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
       (void)hipFuncSetAttribute((const void*)k_oj_persist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
@@ -1765,7 +1760,7 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
   }
   const int cap = (dev >= 0 && dev < 64 && persist_cap[dev] > 0) ? persist_cap[dev] : 64;
   const long long slots_all = (long long)(nblk / 2) * B;
-  if (staged_lds_ok && gpet_opt_oj_persist() && slots_all <= 4LL * cap) {
+  if (staged_lds_ok && opt(Opt::oj_persist) && slots_all <= 4LL * cap) {
     int wpe = nblk / 2;  // workgroups per edge
     if (slots_all > cap) wpe = cap / B > 0 ? cap / B : 1;
     if (use_args) hipLaunchKernelGGL((k_oj_persist<true>), dim3(wpe, B), dim3(256), persist_lds, st, oj_args, d_edges, nblk, max_sweeps, tol2, half_stage);
@@ -1786,24 +1781,6 @@ hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const Batc
   hipLaunchKernelGGL(k_oj_order, dim3(cdiv_h(steps, 256), B), dim3(256), 0, st, d_edges);
   hipLaunchKernelGGL(k_oj_rows, dim3(steps, B), dim3(256), 0, st, d_edges);
   return hipGetLastError();
-}
-
-int& gpet_opt_oj_tol_exp() {
-  static const int i_ = option_index("oj_tol_exp");
-  int& v = option_at(i_);
-  return v;
-}
-
-int& gpet_opt_oj_persist() {
-  static const int i_ = option_index("oj_persist");
-  int& v = option_at(i_);
-  return v;
-}
-
-int& gpet_opt_oj_max_sweeps() {
-  static const int i_ = option_index("oj_max_sweeps");
-  int& v = option_at(i_);
-  return v;
 }
 
 }  // namespace gpet

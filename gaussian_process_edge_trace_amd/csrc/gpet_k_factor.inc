@@ -454,12 +454,7 @@ __global__ void __launch_bounds__(64 * NT) k_jacobi_prerot(EdgeDev* edges, int w
 // LOGW (small batches, where the chain of rounds IS the time): the eigenvectors are not accumulated here -- 41 KB of LDS
 // stores a round, 1 200-1 600 of its 2 650 cycles -- but the round's rotations (c, s) go to a log in global memory, and
 // k_jacobi_wpass applies them to the rows of W afterwards, one wave per row in registers, on as many CUs as there are rows.
-// RR > 0: the LAST 7 RR components of the eigenvectors (rows of W) are not in LDS but in the registers of the seven worker
-// waves -- wave w rows 2 hl + w, 2 hl + w + 7, ..., lane k the pair k of the seating, exactly k_jacobi_wpass's form and
-// arithmetic (rotate (x, y) by the pair's (c, s), then everybody on the circle moves one seat on by whole-wave DPP shifts).
-// LDS stores bound the round (above) and two thirds of them are W's; the register rows cost vector instructions instead,
-// which the round has to spare: the two resources share W.
-template <int NU, bool LOGW, int RR>  // NU blocks per thread: half (half + 1) / 2 <= 1024 up to m = 88, 1176 at m = 96
+template <int NU, bool LOGW>  // NU blocks per thread: half (half + 1) / 2 <= 1024 up to m = 88, 1176 at m = 96
 __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) k_jacobi_seat(EdgeDev* edges, int scaled_out, int warm) {
   constexpr int NT = JS_NT;
   const EdgeDev E = edges[blockIdx.y];
@@ -477,9 +472,7 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
   double* A0 = s_mem;                                                       // [4][nblk]
   double2* W2 = reinterpret_cast<double2*>(s_mem + 4 * ((nblk + 1) & ~1));  // [hl][m]
   const int tid = threadIdx.x;
-  // component pairs [0, hl) of W in LDS, components [2 hl, m) in registers
-  const int nreg = (LOGW || RR == 0) ? 0 : ((7 * RR < m ? 7 * RR : m) & ~1);
-  const int hl = LOGW ? half : (m - nreg) >> 1;
+  const int hl = half;  // component pairs of W in LDS
   if (nblk > NU * NT) {  // (the launcher picks NU from the batch's capacity)
     if (tid == 0) sc->status = GPET_ERR_RANK_CAP;
     return;
@@ -505,22 +498,6 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
       if (Wp) w0 = make_double2((2 * ip < r && pl < r) ? Wp[(size_t)(2 * ip) * ldg + pl] : w0.x, (2 * ip + 1 < r && pl < r) ? Wp[(size_t)(2 * ip + 1) * ldg + pl] : w0.y);
       W2[e] = w0;
     }
-  // register rows of this wave: component 2 hl + wave + 7 t; lane k = pair k: x = entry of the player in slot 2 k, y = 2 k + 1
-  constexpr int RN = RR > 0 ? RR : 1;
-  double rx[RN], ry[RN];
-  const int rlane = tid & 63, rwave = tid >> 6;
-  const bool r_lane_on = rlane < half, r_lane0 = rlane == 0, r_lane_last = rlane == half - 1;
-  const int r_pe = seat_player(2 * rlane, 0, m1), r_po = seat_player(2 * rlane + 1, 0, m1);
-#pragma unroll
-  for (int t = 0; t < RN; ++t) {
-    const int i = 2 * hl + rwave + 7 * t;
-    rx[t] = (RR > 0 && r_lane_on && r_pe == i) ? 1.0 : 0.0;
-    ry[t] = (RR > 0 && r_lane_on && r_po == i) ? 1.0 : 0.0;
-    if (RR > 0 && Wp && r_lane_on && i < r) {
-      if (r_pe < r) rx[t] = Wp[(size_t)i * ldg + r_pe];
-      if (r_po < r) ry[t] = Wp[(size_t)i * ldg + r_po];
-    }
-  }
   double2* jlog = reinterpret_cast<double2*>(E.jlog);
   // fixed roles: blocks tid, tid + NT, ... with the places of their four entries in the next round's layout
   int ba[NU], bb[NU], dst[NU][4];
@@ -634,8 +611,7 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
           const double cb = rb.x, sb = rb.y;
           if (sb != 0.0) {
             // three component pairs per pass, all loads first: the LDS latency is paid once per pass
-            // (fewer with rows in registers: less of W is here, and the registers are needed there)
-            constexpr int BD = RR >= 6 ? 1 : RR > 0 ? 2 : 3;
+            constexpr int BD = 3;
             for (int ip0 = wg; ip0 < hl; ip0 += BD * ngrp) {
               double2 wp[BD], wq[BD];
 #pragma unroll
@@ -655,20 +631,6 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
                   W2[ip * m + qb] = make_double2(fma(sb, wp[t].x, cb * wq[t].x), fma(sb, wp[t].y, cb * wq[t].y));
                 }
               }
-            }
-          }
-        }
-        if (!LOGW && RR > 0 && tid < WT) {  // the register rows (whole waves: the seat change crosses lanes)
-          const double2 rk = cs[r_lane_on ? rlane : 0];
-          const double c = r_lane_on ? rk.x : 1.0, sn = r_lane_on ? rk.y : 0.0;
-#pragma unroll
-          for (int t = 0; t < RR; ++t) {
-            if (2 * hl + rwave + 7 * t < m) {  // (uniform over the wave)
-              const double xr = fma(c, rx[t], -(sn * ry[t])), yr = fma(sn, rx[t], c * ry[t]);
-              const double xd = wp_lane_from_above(xr, xr);
-              const double yu = wp_lane_from_below(r_lane0 ? xr : yr, yr);
-              rx[t] = r_lane_last ? yr : xd;
-              ry[t] = yu;
             }
           }
         }
@@ -723,26 +685,6 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
       const int i = e / r, j = e - i * r;
       const double th = s_theta[j];
       E.G[(size_t)i * ldg + s_pos[j]] = Wd[((i >> 1) * m + j) * 2 + (i & 1)] * (sc->y_std * sqrt(th > 0.0 ? th : 0.0));
-    }
-  }
-  if (!LOGW && RR > 0 && tid < WT && r_lane_on) {  // the register rows: lane k holds component i of players r_pe and r_po
-#pragma unroll
-    for (int t = 0; t < RR; ++t) {
-      const int i = 2 * hl + rwave + 7 * t;
-      if (i < r) {
-        if (r_pe < r) {
-          E.W[(size_t)i * ldg + r_pe] = rx[t];
-          Wk[(size_t)i * ldg + r_pe] = rx[t];
-          const double th = s_theta[r_pe];
-          if (scaled_out) E.G[(size_t)i * ldg + s_pos[r_pe]] = rx[t] * (sc->y_std * sqrt(th > 0.0 ? th : 0.0));
-        }
-        if (r_po < r) {
-          E.W[(size_t)i * ldg + r_po] = ry[t];
-          Wk[(size_t)i * ldg + r_po] = ry[t];
-          const double th = s_theta[r_po];
-          if (scaled_out) E.G[(size_t)i * ldg + s_pos[r_po]] = ry[t] * (sc->y_std * sqrt(th > 0.0 ? th : 0.0));
-        }
-      }
     }
   }
   if (tid == 0) sc->lml = (double)sweeps;  // diagnostics: Jacobi sweeps of this factorisation
@@ -807,6 +749,11 @@ __device__ __forceinline__ double jac_rot_entry(double b00, double b01, double b
   return fma(xr, t0, yr * t1);
 }
 
+// RR > 0: the LAST 7 RR components of the eigenvectors (rows of W) are not in LDS but in the registers of the seven worker
+// waves -- wave w rows 2 hl + w, 2 hl + w + 7, ..., lane k the pair k of the seating, exactly k_jacobi_wpass's form and
+// arithmetic (rotate (x, y) by the pair's (c, s), then everybody on the circle moves one seat on by whole-wave DPP shifts).
+// LDS stores bound the round and two thirds of them are W's; the register rows cost vector instructions instead, which the
+// round has to spare: the two resources share W.
 template <int NU, bool LOGW, int RR, int NTHR, bool PARAM>
 __device__ __forceinline__ void ja_run(const EdgeDev& E, gpet_scalars* sc, int scaled_out, int warm, double* s_mem, double* s_red, double (*s_cs)[49][6], int* s_pos, double* s_theta);
 template <int NU, bool LOGW, int RR, int NTHR, bool PARAM>  // PARAM: the parameter wave's copy of the body, else the workers'
@@ -852,7 +799,7 @@ __device__ __forceinline__ void ja_run(const EdgeDev& E, gpet_scalars* sc, int s
       if (Wp) w0 = make_double2((2 * ip < r && pl < r) ? Wp[(size_t)(2 * ip) * ldg + pl] : w0.x, (2 * ip + 1 < r && pl < r) ? Wp[(size_t)(2 * ip + 1) * ldg + pl] : w0.y);
       W2[e] = w0;
     }
-  // register rows of the worker waves (RR > 0): component 2 hl + wave + 7 t; lane k = pair k (k_jacobi_seat's form)
+  // register rows of the worker waves (RR > 0): component 2 hl + wave + 7 t; lane k = pair k (k_jacobi_wpass's form)
   constexpr int RN = RR > 0 ? RR : 1;
   double rx[RN], ry[RN];
   const int rlane = tid & 63, rwave = tid >> 6;
@@ -1230,105 +1177,6 @@ __global__ void __launch_bounds__(256) k_jacobi_wpass(EdgeDev* edges, int scaled
     }
   }
   if (!on) return;
-  // lane k holds component i of the eigenvectors of players pe and po
-  if (pe < r) E.W[(size_t)i * ldg + pe] = x, Wk[(size_t)i * ldg + pe] = x;
-  if (po < r) E.W[(size_t)i * ldg + po] = y, Wk[(size_t)i * ldg + po] = y;
-  // (the tag: by the wave of the last row, after its own stores -- the next reader is a later launch)
-  if (i == r - 1 && lane == 0 && E.structured) E.wq_tag[sc->iter & 1] = (sc->iter + 1) + 65536 * r;
-  if (scaled_out) {
-    if (pe < r) {
-      const double th = E.theta[pe];
-      E.G[(size_t)i * ldg + s_pos[pe]] = x * (sc->y_std * sqrt(th > 0.0 ? th : 0.0));
-    }
-    if (po < r) {
-      const double th = E.theta[po];
-      E.G[(size_t)i * ldg + s_pos[po]] = y * (sc->y_std * sqrt(th > 0.0 ? th : 0.0));
-    }
-  }
-}
-
-// The same pass with the log SHARED by the waves of a workgroup (round 6).  k_jacobi_wpass lets every wave stream the whole log
-// (sweeps x (m - 1) rounds x m / 2 pairs x 16 bytes ~ 200 KB) through its CU's vector memory path by itself: 72 waves per edge
-// = 14 MB per edge, and that path (~10 B / clk per CU), not the rotations, was the kernel's time -- 29 us for one edge, 70-95 us
-// for the 32 edges of config 4's per-GPU share.  Here a workgroup of WPL_NW waves (one row of W each) reads every tile of
-// WPL_PF rounds ONCE, into LDS, one tile ahead in registers (a tile is ~2 500 cycles of rotations: more than the 1-2 us a log
-// row written by another CU a moment ago takes to come back), one barrier per tile; the rotations are k_jacobi_wpass's own
-// arithmetic in its order -- the same bits.
-#define WPL_NW 8
-#define WPL_PF 32
-#define WPL_COLS 48
-__global__ void __launch_bounds__(64 * WPL_NW) k_jacobi_wpass_lds(EdgeDev* edges, int scaled_out, int warm) {
-  const EdgeDev E = edges[blockIdx.y];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK || E.factor_injected) return;
-  const int r = sc->rank, ldg = E.r_cap;
-  const int m = (r + 1) & ~1, half = m >> 1, m1 = m - 1;
-  const int tid = threadIdx.x, lane = tid & 63, i = blockIdx.x * WPL_NW + (tid >> 6);
-  typedef double wp_d2 __attribute__((ext_vector_type(2)));
-  __shared__ int s_pos[96];
-  __shared__ __attribute__((aligned(16))) wp_d2 s_log[2][WPL_PF][WPL_COLS];
-  for (int k = tid; k < r; k += 64 * WPL_NW) s_pos[E.order[k]] = k;  // player -> place in descending order
-  if (r < 1 || blockIdx.x * WPL_NW >= r) return;  // (uniform for the workgroup: no barrier is skipped by part of it)
-  const bool live = i < r;
-  const int total = __builtin_amdgcn_readfirstlane((int)sc->lml * m1);
-  const bool on = lane < half;
-  const int pe = seat_player(2 * lane, 0, m1), po = seat_player(2 * lane + 1, 0, m1);
-  double x = (on && pe == i) ? 1.0 : 0.0, y = (on && po == i) ? 1.0 : 0.0;
-  const double* Wp = jac_warm_source(E, sc, warm);  // (warm start: the rotations continue from the previous eigenvectors)
-  if (Wp && on && live) {
-    if (pe < r) x = Wp[(size_t)i * ldg + pe];
-    if (po < r) y = Wp[(size_t)i * ldg + po];
-  }
-  double* Wk = jac_warm_slot(E, sc->iter);
-  const bool lane0 = lane == 0, lane_last = lane == half - 1;
-  // a tile: rounds [PF t, PF t + PF) x pairs [0, half); element e = tid + 512 q -> (round e / COLS, pair e % COLS); loads are
-  // unconditional (rounds beyond the last and pairs beyond `half` read a valid element nobody uses)
-  constexpr int NLD = (WPL_PF * WPL_COLS + 64 * WPL_NW - 1) / (64 * WPL_NW);
-  const GPET_GLOBAL wp_d2* lg = (const GPET_GLOBAL wp_d2*)E.jlog;
-  const int last = total > 0 ? total - 1 : 0;
-  wp_d2 pre[NLD];
-  auto fetch = [&](int t) {
-#pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-      const int e = tid + 64 * WPL_NW * q, u = e / WPL_COLS, k = e - u * WPL_COLS;
-      const int rr = WPL_PF * t + u;
-      pre[q] = lg[(size_t)(rr < last ? rr : last) * half + (k < half ? k : 0)];
-    }
-  };
-  auto put = [&](int b) {
-#pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-      const int e = tid + 64 * WPL_NW * q;
-      if (e < WPL_PF * WPL_COLS) (&s_log[b][0][0])[e] = pre[q];
-    }
-  };
-  const int ntiles = (total + WPL_PF - 1) / WPL_PF;
-  fetch(0);
-  put(0);
-  if (ntiles > 1) fetch(1);
-  __syncthreads();
-  const int lcol = on ? lane : 0;
-  for (int t = 0; t < ntiles; ++t) {
-    const int b = t & 1, r0 = WPL_PF * t;
-    if (t + 1 < ntiles) put(b ^ 1);        // (buffer b ^ 1 was last read in tile t - 1: everybody has passed that tile's barrier)
-    if (t + 2 < ntiles) fetch(t + 2);
-    if (live) {
-#pragma unroll
-      for (int u = 0; u < WPL_PF; ++u) {
-        if (r0 + u < total) {  // (scalar)
-          const wp_d2 cs = s_log[b][u][lcol];
-          const double c = on ? cs.x : 1.0, sn = on ? cs.y : 0.0;
-          const double xr = fma(c, x, -(sn * y)), yr = fma(sn, x, c * y);
-          const double xd = wp_lane_from_above(xr, xr);
-          const double yu = wp_lane_from_below(lane0 ? xr : yr, yr);
-          x = lane_last ? yr : xd;
-          y = yu;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (!on || !live) return;
   // lane k holds component i of the eigenvectors of players pe and po
   if (pe < r) E.W[(size_t)i * ldg + pe] = x, Wk[(size_t)i * ldg + pe] = x;
   if (po < r) E.W[(size_t)i * ldg + po] = y, Wk[(size_t)i * ldg + po] = y;

@@ -248,48 +248,6 @@ hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const B
   return hipGetLastError();
 }
 
-int& gpet_opt_lml_two_tiles_from() {
-  static const int i_ = option_index("lml_two_tiles_from");
-  int& v = option_at(i_);
-  return v;
-}
-
-int& gpet_opt_lml_mfma() {
-  static const int i_ = option_index("lml_mfma");
-  int& v = option_at(i_);
-  return v;
-}
-
-int& gpet_opt_rng_lookahead() {
-  static const int i_ = option_index("rng_lookahead");
-  int& v = option_at(i_);  // -1: by batch size
-  return v;
-}
-
-// LDS Jacobi of ranks <= 96: 1 (default) = rotation parameters one round ahead, one barrier per round (k_jacobi_ahead); 0 = three barriers per round (k_jacobi_seat: the cross-check)
-int& gpet_opt_jacobi_variant() {
-  static const int i_ = option_index("jacobi_variant");
-  int& v = option_at(i_);
-  return v;
-}
-// rotation log + separate eigenvector pass for batches that have a log (gpet_batch_create: up to 16 edges): 1 = on (default)
-int& gpet_opt_jacobi_logw() {
-  static const int i_ = option_index("jacobi_logw");
-  int& v = option_at(i_);
-  return v;
-}
-// warm start of the structured path's eigen-decomposition from the previous iteration's eigenvectors: 1 = on
-int& gpet_opt_jacobi_warm() {
-  static const int i_ = option_index("jacobi_warm");
-  int& v = option_at(i_);
-  return v;
-}
-// rows of the eigenvector matrix kept in the registers of k_jacobi_seat's worker waves: 7 x this many (0, 4, 6 or 8)
-int& gpet_opt_jacobi_wreg() {
-  static const int i_ = option_index("jacobi_wreg");
-  int& v = option_at(i_);
-  return v;
-}
 static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int rank_max, int scaled_out, bool logw, int r_cap) {
   const int mm = (rank_max + 1) & ~1;
   static PerDeviceOnce once;
@@ -297,20 +255,19 @@ static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int ran
     (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-#define GPET_JS_ATTR(NU_, LOGW_, RR_) \
-  (void)hipFuncSetAttribute((const void*)k_jacobi_seat<NU_, LOGW_, RR_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
-    GPET_JS_ATTR(2, true, 0); GPET_JS_ATTR(3, true, 0);
-    GPET_JS_ATTR(2, false, 0); GPET_JS_ATTR(3, false, 0);
-    GPET_JS_ATTR(2, false, 4); GPET_JS_ATTR(2, false, 6); GPET_JS_ATTR(2, false, 8);
+#define GPET_JS_ATTR(NU_, LOGW_) \
+  (void)hipFuncSetAttribute((const void*)k_jacobi_seat<NU_, LOGW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
+    GPET_JS_ATTR(2, true); GPET_JS_ATTR(3, true);
+    GPET_JS_ATTR(2, false); GPET_JS_ATTR(3, false);
 #undef GPET_JS_ATTR
 #define GPET_JA_ATTR(NU_, LOGW_, RR_, NT_) \
   (void)hipFuncSetAttribute((const void*)k_jacobi_ahead<NU_, LOGW_, RR_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
     GPET_JA_ATTR(2, true, 0, JA_NT_LOG); GPET_JA_ATTR(3, true, 0, JA_NT_LOG);
-    GPET_JA_ATTR(2, false, 0, JS_NT); GPET_JA_ATTR(3, false, 0, JS_NT); GPET_JA_ATTR(2, false, 6, JS_NT);
+    GPET_JA_ATTR(3, false, 0, JS_NT); GPET_JA_ATTR(2, false, 6, JS_NT);
 #undef GPET_JA_ATTR
   }
   // warm start (structured loop only: there the matrix of an iteration is a small change of the last one's)
-  const int warm = scaled_out ? gpet_opt_jacobi_warm() : 0;
+  const int warm = scaled_out ? opt(Opt::jacobi_warm) : 0;
   (void)r_cap;
   if (warm) {
     const int nt = (rank_max + 15) >> 4;
@@ -324,7 +281,7 @@ static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int ran
     else GPET_PR_LAUNCH(6);
 #undef GPET_PR_LAUNCH
   }
-  if (gpet_opt_jacobi_variant() != 0) {
+  if (opt(Opt::jacobi_variant) != 0) {
     // parameters one round ahead, one barrier per round (k_jacobi_ahead): the matrix twice in LDS
     const size_t nblk = (size_t)(mm / 2) * (mm / 2 + 1) / 2, nbp = (nblk + 1) & ~(size_t)1;
     const dim3 grid(1, B);
@@ -332,38 +289,28 @@ static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int ran
       const size_t lds = (8 * nbp + 4) * sizeof(double);
       if (nblk <= 2 * (size_t)(JA_NT_LOG - 64)) hipLaunchKernelGGL((k_jacobi_ahead<2, true, 0, JA_NT_LOG>), grid, dim3(JA_NT_LOG), lds, st, d_edges, scaled_out, warm);
       else hipLaunchKernelGGL((k_jacobi_ahead<3, true, 0, JA_NT_LOG>), grid, dim3(JA_NT_LOG), lds, st, d_edges, scaled_out, warm);
-      if (option("wpass_lds")) hipLaunchKernelGGL(k_jacobi_wpass_lds, dim3((rank_max + WPL_NW - 1) / WPL_NW, B), dim3(64 * WPL_NW), 0, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
+      hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
     } else {
+      // two blocks per thread: the last 7 x 6 components of the eigenvectors in the worker waves' registers (RR = 6), the rest
+      // in LDS; three blocks per thread (ranks above 82) have no registers to spare
       const bool three = nblk > 2 * (size_t)(JS_NT - 64);
-      const int rr = (!three && gpet_opt_jacobi_wreg() >= 6) ? 6 : 0;
-      const int nreg = ((7 * rr < mm ? 7 * rr : mm) & ~1);
+      const int nreg = three ? 0 : ((7 * 6 < mm ? 7 * 6 : mm) & ~1);
       const size_t lds = (8 * nbp + 4 + (size_t)(mm - nreg) * mm) * sizeof(double);
       if (three) hipLaunchKernelGGL((k_jacobi_ahead<3, false, 0, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
-      else if (rr == 6) hipLaunchKernelGGL((k_jacobi_ahead<2, false, 6, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_ahead<2, false, 0, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
+      else hipLaunchKernelGGL((k_jacobi_ahead<2, false, 6, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
     }
   } else {
     const size_t nblk = (size_t)(mm / 2) * (mm / 2 + 1) / 2;
-    const int rr_ = logw ? 0 : gpet_opt_jacobi_wreg();
-    // (ranks above 88 -- three blocks per thread -- have no registers to spare)
-    const int rr = nblk > 2 * JS_NT ? 0 : rr_ >= 8 ? 8 : rr_ >= 6 ? 6 : rr_ >= 4 ? 4 : 0;
-    // (W in LDS: the component pairs that are not in registers -- sized for the widest edge of the batch)
-    const int nreg = ((7 * rr < mm ? 7 * rr : mm) & ~1);
-    const size_t lds = (4 * ((nblk + 1) & ~(size_t)1) + (size_t)(logw ? mm : mm - nreg) * mm) * sizeof(double);
+    const size_t lds = (4 * ((nblk + 1) & ~(size_t)1) + (size_t)mm * mm) * sizeof(double);
     const dim3 grid(1, B), block(JS_NT);
     if (logw) {
       // small batch: rotations logged, eigenvectors by a second kernel (one wave per row of W)
-      if (nblk <= 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<2, true, 0>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_seat<3, true, 0>), grid, block, lds, st, d_edges, scaled_out, warm);
-      if (option("wpass_lds")) hipLaunchKernelGGL(k_jacobi_wpass_lds, dim3((rank_max + WPL_NW - 1) / WPL_NW, B), dim3(64 * WPL_NW), 0, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
+      if (nblk <= 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<2, true>), grid, block, lds, st, d_edges, scaled_out, warm);
+      else hipLaunchKernelGGL((k_jacobi_seat<3, true>), grid, block, lds, st, d_edges, scaled_out, warm);
+      hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
     } else {
-      if (nblk > 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<3, false, 0>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else if (rr == 8) hipLaunchKernelGGL((k_jacobi_seat<2, false, 8>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else if (rr == 6) hipLaunchKernelGGL((k_jacobi_seat<2, false, 6>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else if (rr == 4) hipLaunchKernelGGL((k_jacobi_seat<2, false, 4>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_seat<2, false, 0>), grid, block, lds, st, d_edges, scaled_out, warm);
+      if (nblk > 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<3, false>), grid, block, lds, st, d_edges, scaled_out, warm);
+      else hipLaunchKernelGGL((k_jacobi_seat<2, false>), grid, block, lds, st, d_edges, scaled_out, warm);
     }
   }
 }
@@ -384,7 +331,7 @@ hipError_t launch_factor(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
   }
   const int t = cdiv(bd.r_cap, 16);
   if (parts & 2u) hipLaunchKernelGGL(k_gram, dim3(t, t, B), dim3(256), 0, st, d_edges);
-  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r_cap, 0, bd.jlog != 0 && gpet_opt_jacobi_logw() != 0, bd.r_cap);
+  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r_cap, 0, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0, bd.r_cap);
   if (parts & 8u)
     hipLaunchKernelGGL(k_factor_rows, dim3(bd.r_cap, B), dim3(256), (size_t)bd.r_cap * sizeof(double), st, d_edges);
   return hipGetLastError();
@@ -422,7 +369,7 @@ hipError_t launch_struct_iteration(hipStream_t st, EdgeDev* d_edges, int B, cons
     const int l_in_lds = full <= (size_t)STRUCT_H_LDS_MAX ? 1 : 0;  // (gpet_batch_create checked that `rowm` fits)
     hipLaunchKernelGGL(k_struct_H, dim3(1, B), dim3(1024), l_in_lds ? full : rowm, st, d_edges, l_in_lds);
   }
-  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r0_max > 0 ? bd.r0_max : bd.r_cap, 1, bd.jlog != 0 && gpet_opt_jacobi_logw() != 0, bd.r_cap);
+  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r0_max > 0 ? bd.r0_max : bd.r_cap, 1, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0, bd.r_cap);
   if (parts & 8u) {
     // the variant k_struct_rows picks for r0_max: [4 KS][16 MT + 1] eigenvector tile
     const int rm = bd.r0_max;
@@ -662,7 +609,7 @@ hipError_t launch_sample(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
 // false: the shape does not allow it (the caller enqueues launch_score + launch_kde)
 bool score_tail_applies(const BatchDims& bd) {
   const size_t lds = (size_t)(2 * SC_PAIRS + 2) * (bd.M | 1) * sizeof(float);
-  return lds <= 150 * 1024 && bd.S >= 64 && bd.S <= 1024 && bd.n_keep <= KDE_PREP_MAXB && !option("topk_rank");
+  return lds <= 150 * 1024 && bd.S >= 64 && bd.S <= 1024 && bd.n_keep <= KDE_PREP_MAXB && !opt(Opt::topk_rank);
 }
 hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
   hipError_t e = launch_score(st, d_edges, B, bd, 1u, true);  // (the tiles only, their partial sums left for k_score_tail)
@@ -695,7 +642,7 @@ hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims
     }
   }
   if (parts & 2u) {
-    if (bd.S <= 1024 && !option("topk_rank")) hipLaunchKernelGGL(k_topk_sort, dim3(1, B), dim3(512), 0, st, d_edges);
+    if (bd.S <= 1024 && !opt(Opt::topk_rank)) hipLaunchKernelGGL(k_topk_sort, dim3(1, B), dim3(512), 0, st, d_edges);
     else hipLaunchKernelGGL(k_topk, dim3(cdiv(bd.S, 256), B), dim3(256), 0, st, d_edges);
   }
   return hipGetLastError();

@@ -993,7 +993,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(GPET_L
 }
 
 bool lml16_fit_applies(int n_max, int lag_cap) {
-  return n_max <= L16_MAXN && lag_cap > 0 && lag_cap <= L16_LAG_MAX && gpet_opt_lml_mfma() != 0;
+  return n_max <= L16_MAXN && lag_cap > 0 && lag_cap <= L16_LAG_MAX;
 }
 
 hipError_t launch_lml16_fit(hipStream_t st, EdgeDev* d_edges, void* d_probs, int P, const LbCfg& cfg, int lag_cap, int max_evals,
@@ -1012,7 +1012,7 @@ hipError_t launch_lml(hipStream_t st, EdgeDev* d_edges, int P, int n_max, const 
   // up to 108 training points on a lattice (lag_cap > 0: every training set of the launch sits on one with fewer than
   // lag_cap points; the caller knows): the block sweep on the matrix cores, two waves per problem, correlation tables
   // of lag_cap entries in dynamic LDS
-  if (n_max <= L16_MAXN && lag_cap > 0 && lag_cap <= L16_LAG_MAX && gpet_opt_lml_mfma()) {
+  if (n_max <= L16_MAXN && lag_cap > 0 && lag_cap <= L16_LAG_MAX) {
     const size_t dyn = (size_t)2 * lag_cap * sizeof(double);
     hipLaunchKernelGGL(k_lml16, dim3(P), dim3(128), dyn, st, d_edges, d_edge_of, d_theta, d_f, d_g, d_count, lag_cap);
     return hipGetLastError();
@@ -1020,7 +1020,7 @@ hipError_t launch_lml(hipStream_t st, EdgeDev* d_edges, int P, int n_max, const 
   // two tiles per thread: the only form above 128 training points, and the faster one for big launches (fewer
   // instructions per problem: 109 instead of 134 us at 900 problems of 98 points, 1.07 instead of 1.41 ms at 13312) --
   // small launches are latency-bound and keep one tile per thread (64 instead of 80 us at 256 problems)
-  if (n_max > 128 || gpet_opt_lml_two_tiles_from() <= P) {
+  if (n_max > 128 || opt(Opt::lml_two_tiles_from) <= P) {
     const int nb2 = (n_max + 1 + 3) >> 2;
     const int tiles = nb2 * (nb2 + 1) / 2;
     int threads = (((tiles + 1) / 2 + 63) / 64) * 64;

@@ -34,7 +34,6 @@
 
 #include "gpet_dev.h"
 #include "gpet_kernels.h"
-#include "gpet_options.h"
 
 namespace gpet {
 
@@ -322,12 +321,6 @@ bool normals4_applies(const EdgeDev* h_edges, int B) {
   for (int e = 1; e < B; ++e)
     if (h_edges[e].Lg != Lg || h_edges[e].S != S || h_edges[e].z_cols != zc) return false;
   return true;
-}
-
-int& gpet_opt_rng4() {
-  static const int i_ = option_index("rng4");
-  int& v = option_at(i_);
-  return v;
 }
 
 hipError_t launch_normals4(hipStream_t st, EdgeDev* d_edges, int B, const unsigned int* d_seeds, int add_iter, int iter_abs,

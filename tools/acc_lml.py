@@ -21,12 +21,9 @@ for name, stage in [("trace_rbf500", "stage_rbf500"), ("trace_mat128", "stage_ma
     th[:, 2] = np.log(rng.uniform(1e-4, 1.0, size=40))
     th[0] = np.log([5.0, 5.0, 1.0])
     ref = [orc.lml_and_grad(t, pr["xs"], pr["yt"], pr["w"], tr.kernel_type, tr.kernel_nu) for t in th]
-    for mode in (0, 1):
-        L.set_option("lml_mfma", mode)
-        f, gr = b.lml_batch(np.zeros(40, dtype=np.int32), th)
-        ef = [abs(f[i] + ref[i][0]) / (1 + abs(ref[i][0])) for i in range(40) if np.isfinite(ref[i][0])]
-        eg = [np.abs(gr[i] + ref[i][1]).max() / (1 + np.abs(ref[i][1]).max()) for i in range(40) if np.isfinite(ref[i][0])]
-        k = int(np.argmax(ef))
-        print("%s n=%d mode %d: max rel err f %.2e (theta %s, cond-ish c/nl %.1e), g %.2e" %
-              (name, pr["xs"].size, mode, max(ef), np.round(np.exp(th[k]), 5), np.exp(th[k][0] - th[k][2]), max(eg)))
-    L.set_option("lml_mfma", 1)
+    f, gr = b.lml_batch(np.zeros(40, dtype=np.int32), th)
+    ef = [abs(f[i] + ref[i][0]) / (1 + abs(ref[i][0])) for i in range(40) if np.isfinite(ref[i][0])]
+    eg = [np.abs(gr[i] + ref[i][1]).max() / (1 + np.abs(ref[i][1]).max()) for i in range(40) if np.isfinite(ref[i][0])]
+    k = int(np.argmax(ef))
+    print("%s n=%d: max rel err f %.2e (theta %s, cond-ish c/nl %.1e), g %.2e" %
+          (name, pr["xs"].size, max(ef), np.round(np.exp(th[k]), 5), np.exp(th[k][0] - th[k][2]), max(eg)))

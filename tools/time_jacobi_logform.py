@@ -1,5 +1,5 @@
 """Eigen stage (pre-rotation + Jacobi [+ rotation-log pass]) of a batch at the bench's mid-trace state: the form that updates W inside
-the rounds against the rotation-log form with the log pass sharing the log through LDS (k_jacobi_wpass_lds), per batch size.
+the rounds against the rotation-log form with its separate log pass (k_jacobi_wpass), per batch size.
 One process per configuration (jlog_max_b is read when a batch is created).  usage: python tools/time_jacobi_logform.py <edges>"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,5 +17,5 @@ b = tr._batch
 b.iterate(seeds, 7)
 b.profile_stage(120, 1)  # the fit and H of the NEXT iteration (its observation set is on the device): the Jacobi below then has real work,
 b.profile_stage(121, 1)  # warm-started from the last iteration's eigenvectors like in the loop
-print("%d edges, jlog_max_b=%d wpass_lds=%d: eigen stage %.3f ms (sweeps %d)" % (E, L.get_option("jlog_max_b"), L.get_option("wpass_lds"),
-                                                                                  b.profile_stage(122, 20), int(b.scalars(0).lml)), flush=True)
+print("%d edges, jlog_max_b=%d: eigen stage %.3f ms (sweeps %d)" % (E, L.get_option("jlog_max_b"), b.profile_stage(122, 20),
+                                                                   int(b.scalars(0).lml)), flush=True)
