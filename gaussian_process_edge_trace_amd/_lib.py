@@ -42,6 +42,32 @@ class GpetScalars(C.Structure):
                 ("n_removed", C.c_int32), ("force", C.c_int32)]
 
 
+class GpetResultHead(C.Structure):
+    """gpet_result_head: the head of one edge's result record (gpet_batch_results / gpet_gather_results)."""
+    _fields_ = [("edge_len", C.c_int32), ("n_iter", C.c_int32), ("n_obs", C.c_int32), ("status", C.c_int32),
+                ("theta", C.c_double * 3), ("nlml", C.c_double)]
+
+
+def result_bytes(len_cap):
+    """Bytes of one result record for ``len_cap`` points (gpet_result_bytes)."""
+    n = C.c_size_t()
+    rc = load().gpet_result_bytes(int(len_cap), C.byref(n))
+    if rc:
+        raise GpetError(rc, "gpet_result_bytes(%d)" % int(len_cap))
+    return n.value
+
+
+def decode_results(raw, n, len_cap):
+    """numpy views of ``n`` result records (include/gpet_hip.h, "Result records"): trace (n, len_cap, 2) int64 yx,
+    lower / upper (n, len_cap) f64, and per edge edge_len, n_iter, n_obs, status, theta (n, 3), nlml."""
+    L = int(len_cap)
+    dt = np.dtype([("edge_len", "<i4"), ("n_iter", "<i4"), ("n_obs", "<i4"), ("status", "<i4"), ("theta", "<f8", (3,)),
+                   ("nlml", "<f8"), ("trace", "<i8", (L, 2)), ("lower", "<f8", (L,)), ("upper", "<f8", (L,))])
+    assert dt.itemsize == result_bytes(L) and C.sizeof(GpetResultHead) == dt.fields["trace"][1]
+    rec = np.frombuffer(raw, dtype=dt, count=int(n))
+    return {k: np.array(rec[k]) for k in dt.names}
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -115,6 +141,9 @@ SYMBOLS = {
     "gpet_dev_copy": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "gpet_allgather_i64": (C.c_int, [_P, _P, _P, _P]),
     "gpet_gather_traces": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    "gpet_result_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "gpet_batch_results": (C.c_int, [_P, C.c_int64, _P, C.c_int]),
+    "gpet_gather_results": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
 }
 COMM_ID_BYTES = 128
 
@@ -307,6 +336,16 @@ class Comm:
         self.ctx.check(self.lib.gpet_gather_traces(self.h, loc.ctypes.data if loc.size else None, int(n_edges), int(edge_len),
                                                    out.ctypes.data))
         return out
+
+    def gather_results(self, batch, n_edges, len_cap):
+        """Result records of every edge (gpet_gather_results): ``batch`` is this rank's Batch (its block of edges, after
+        its converged fits) or None on a rank that owns no edges.  Returns decode_results of the n_edges records in global
+        order, the same on every rank."""
+        n = int(n_edges)
+        raw = np.empty(max(1, n * result_bytes(len_cap)), dtype=np.uint8)
+        self.ctx.check(self.lib.gpet_gather_results(self.h, batch.h if batch is not None else None, n, int(len_cap),
+                                                    raw.ctypes.data))
+        return decode_results(raw, n, len_cap)
 
     def allgather_i64(self, local, counts):
         loc = np.ascontiguousarray(np.asarray(local, dtype=np.int64).reshape(-1))
@@ -521,6 +560,14 @@ class Batch:
         self.ctx.check(self.lib.gpet_final_fit_all(self.h, s, mean.ctypes.data, std.ctypes.data, th.ctypes.data, Lg,
                                                    C.byref(rounds)))
         return mean, std, th[:, :3].copy(), th[:, 3].copy(), rounds.value
+
+    def results(self, len_cap=None):
+        """Result records of every edge (gpet_batch_results), valid after final_fit_all on the current trace: a dict of
+        numpy arrays as decode_results returns it.  ``len_cap`` defaults to the widest edge."""
+        L = self._max_info("Lg") if len_cap is None else int(len_cap)
+        raw = np.empty(max(1, self.B * result_bytes(L)), dtype=np.uint8)
+        self.ctx.check(self.lib.gpet_batch_results(self.h, L, raw.ctypes.data, 0))
+        return decode_results(raw, self.B, L)
 
     def set_option(self, name, value):
         """This batch's own copy of a tuning switch (gpet_batch_set_option); returns the previous value (-1 = automatic)."""

@@ -428,6 +428,7 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->ev_l1) (void)hipEventDestroy(b->ev_l1);
   if (b->d_fin_stage) (void)hipFree(b->d_fin_stage);
   if (b->d_fin_n) (void)hipFree(b->d_fin_n);
+  if (b->d_results) (void)hipFree(b->d_results);
   if (b->fit) {
     (void)hipStreamSynchronize(b->fit);
     (void)hipStreamDestroy(b->fit);
@@ -539,6 +540,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
   gpet_ctx* c = b->ctx;
   EdgeDev& E = b->h_edges[e];
   if (n_obs > E.obs_cap) return fail(c, GPET_ERR_BAD_ARG, "n_obs=%d exceeds obs_cap=%d", n_obs, E.obs_cap);
+  b->have_results = false;
   // the pixel kernels index the density images with the observations (gpet.py:568: kde_arr[pre_fobs[:,0], pre_fobs[:,1]]
   // raises IndexError in the reference for pixels outside the image)
   for (int i = 0; i < n_obs; ++i)
@@ -731,7 +733,7 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
     case GPET_BUF_BEST_COSTS: dst = E.best_costs; cap = (size_t)E.n_keep * 8; break;
     case GPET_BUF_MEAN: dst = E.mean; cap = Lg * 8; break;
     case GPET_BUF_COV: dst = E.cov; cap = Lg * Lg * 8; b->have_fit = true; break;
-    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); break;
+    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); b->have_results = false; break;
     default:
       return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_write: buffer %d is not writable", which);
   }
@@ -796,6 +798,7 @@ int gpet_batch_clear_injected_factor(gpet_batch* b, int e) {
 
 static int batch_reset(gpet_batch* b, bool next_frame) {
   gpet_ctx* c = b->ctx;
+  b->have_results = false;
   b->h_nobs_prev.assign(b->B, 0);
   b->iters_issued = 0;
   b->norm_issued = 0;

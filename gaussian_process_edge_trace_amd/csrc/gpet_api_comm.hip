@@ -74,6 +74,16 @@ static void block_of(size_t n, int world, int rank, size_t& lo, size_t& hi) {  /
   hi = lo + base + ((size_t)rank < rem ? 1 : 0);
 }
 
+static int grow_scratch(gpet_comm* c, size_t need) {  // the gathers' device staging: send block | world receive blocks
+  if (need <= c->scratch_bytes) return GPET_OK;
+  if (c->scratch) (void)hipFree(c->scratch);
+  c->scratch = nullptr;
+  c->scratch_bytes = 0;
+  HIPCHK(c->ctx, hipMalloc(&c->scratch, need));
+  c->scratch_bytes = need;
+  return GPET_OK;
+}
+
 extern "C" {
 
 int gpet_comm_unique_id(void* id128) {
@@ -192,14 +202,8 @@ int gpet_allgather_i64(gpet_comm* c, const int64_t* h_local, const int64_t* coun
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // blocks of different lengths: padded to the longest (the traces of a rank's edges: blocks differ by one edge at most)
-  const size_t need = (size_t)(c->world + 1) * cap * sizeof(int64_t);
-  if (need > c->scratch_bytes) {
-    if (c->scratch) (void)hipFree(c->scratch);
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&c->scratch, need));
-    c->scratch_bytes = need;
-  }
+  int rc = grow_scratch(c, (size_t)(c->world + 1) * cap * sizeof(int64_t));
+  if (rc) return rc;
   int64_t* d_send = reinterpret_cast<int64_t*>(c->scratch);
   int64_t* d_recv = d_send + cap;
   HIPCHK(ctx, hipMemsetAsync(d_send, 0, cap * sizeof(int64_t), ctx->stream));
@@ -224,6 +228,46 @@ int gpet_gather_traces(gpet_comm* c, const int64_t* h_local, int64_t n_edges, in
     counts[(size_t)r] = (int64_t)(hi - lo) * edge_len * 2;
   }
   return gpet_allgather_i64(c, h_local, counts.data(), h_all);
+}
+
+int gpet_gather_results(gpet_comm* c, gpet_batch* local, int64_t n_edges, int64_t len_cap, void* h_all) {
+  if (!c || n_edges < 0 || !h_all) return GPET_ERR_BAD_ARG;
+  gpet_ctx* ctx = c->ctx;
+  const size_t rec = result_record_bytes(len_cap);
+  if (rec == 0) return fail(ctx, GPET_ERR_BAD_ARG, "gpet_gather_results: len_cap=%lld out of range", (long long)len_cap);
+  size_t lo, hi;
+  block_of((size_t)n_edges, c->world, c->rank, lo, hi);
+  const size_t mine = hi - lo;
+  if (local && local->ctx != ctx)
+    return fail(ctx, GPET_ERR_BAD_ARG, "gpet_gather_results: the batch's context is not the communicator's");
+  if ((local ? (size_t)local->B : 0) != mine)
+    return fail(ctx, GPET_ERR_BAD_ARG, "gpet_gather_results: rank %d owns %zu edges, the batch holds %d", c->rank, mine,
+                local ? local->B : 0);
+  GPET_BATCH_SCOPE(local);
+  if (n_edges == 0) return GPET_OK;
+  if (!c->comm) return gpet_batch_results(local, len_cap, h_all, 0);  // (a world of one: every edge is this rank's)
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // blocks padded to the longest: ranks [0, rem) hold cap = base + 1 edges, the others base (gpet_comm_block)
+  const size_t world = (size_t)c->world, base = (size_t)n_edges / world, rem = (size_t)n_edges % world;
+  const size_t cap = base + (rem ? 1 : 0), blk = cap * rec;
+  int rc = grow_scratch(c, (world + 1) * blk);
+  if (rc) return rc;
+  char* d_send = c->scratch;
+  char* d_recv = d_send + blk;
+  if (mine < cap) HIPCHK(ctx, hipMemsetAsync(d_send + mine * rec, 0, (cap - mine) * rec, ctx->stream));
+  if (mine) {
+    rc = enqueue_results(local, len_cap, d_send);  // (packed on the device, straight into the send block)
+    if (rc) return rc;
+  }
+  NCCLCHK(ctx, rccl().AllGather(d_send, d_recv, blk / sizeof(int64_t), ncclInt64, c->comm, ctx->stream));
+  // global edge order on the host: the full blocks are contiguous; the short ones drop their one record of padding
+  char* dst = static_cast<char*>(h_all);
+  HIPCHK(ctx, hipMemcpyAsync(dst, d_recv, (rem ? rem : world) * blk, hipMemcpyDeviceToHost, ctx->stream));
+  if (rem && base)
+    HIPCHK(ctx, hipMemcpy2DAsync(dst + rem * blk, base * rec, d_recv + rem * blk, blk, base * rec, world - rem,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, gpet_wait(ctx->stream));
+  return GPET_OK;
 }
 
 }  // extern "C"

@@ -104,6 +104,7 @@ int gpet_final_predict_all(gpet_batch* b, const double* par, double* mean_out, d
   HIPCHK(c, hipSetDevice(c->device));
   for (int e = 0; e < b->B; ++e)
     if (b->h_edges[e].fin_n < 1) return fail(c, GPET_ERR_STATE, "gpet_final_predict_all before the training sets are set");
+  b->have_results = false;  // (a caller's own parameters: not the optimum gpet_batch_results reports)
   // (slots 9..11 of every edge stay: the lattice of its training set)
   HIPCHK(c, hipMemcpy2DAsync(b->d_fin_par, 12 * sizeof(double), par, 12 * sizeof(double), 9 * sizeof(double), b->B,
                              hipMemcpyHostToDevice, c->stream));
@@ -353,6 +354,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   GPET_BATCH_SCOPE(b);
   if (!b || !seeds || !mean_out || !std_out || stride < b->bd.Lg) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
+  b->have_results = false;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = fetch_all_scalars(b);  // (synchronises the loop's stream: the observation sets are final)
   if (rc) return rc;
@@ -394,6 +396,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   }
   if (rounds_out) *rounds_out = rounds;
   b->have_fit = false;  // the loop's L/alpha were overwritten by the converged fit
+  b->have_results = true;  // (fin_out + lb_theta_out: what gpet_batch_results packs)
   return check_device_status(b);
 }
 
@@ -404,6 +407,7 @@ int gpet_final_optimize(gpet_batch* b, int n_starts, const double* starts, const
   gpet_ctx* c = b->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   const int B = b->B, P = n_starts * B;
+  b->have_results = false;  // (lb_theta_out is about to hold another optimum)
   LbCfg cfg;
   cfg.nstart = n_starts;
   for (int k = 0; k < 3; ++k) {

@@ -7,6 +7,8 @@
 //   gpet_api_final.hip   the converged fit (f2): objective, device L-BFGS-B, posterior at the optimum
 //   gpet_api_loop.hip    the device-resident loop (a8): gpet_trace_iterate
 //   gpet_api_comm.hip    multi-GPU helpers on RCCL (8e): communicator, broadcast of the gradient image, gather of the traces
+//                        and of the result records
+//   gpet_api_results.hip the finished result record of every edge (k_finish_results): gpet_result_bytes, gpet_batch_results
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -107,6 +109,11 @@ struct gpet_batch {
   // -1 = no lattice (caller-supplied x off any grid) -> the vector objective kernels; see fin_lattice()
   std::vector<int> fin_lag;
   bool have_fit = false, have_factor = false, have_normals = false, have_samples = false, have_scores = false;
+  // gpet_final_fit_all has run on the current trace: d_fin_out / lb_theta_out hold what gpet_batch_results packs (cleared by
+  // everything that starts another trace or overwrites the converged fit)
+  bool have_results = false;
+  char* d_results = nullptr;           // device staging of gpet_batch_results into host memory (grown on demand)
+  size_t results_bytes = 0;
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it
 };
 // first statement of every entry point that works on a batch: its option table for the calling thread
@@ -137,6 +144,12 @@ hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, i
                               int iter_abs, int n_ahead, int z_store);
 int normals_auto(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter, int iter_abs,
                  int n_ahead, int z_store, bool allow_chunked = true);
+// ---- gpet_api_results.hip -------------------------------------------------------------------------------------------------
+// bytes of one result record (gpet_result_head + its arrays) for len_cap points; 0 if len_cap is out of range
+size_t result_record_bytes(int64_t len_cap);
+// the records of every edge of b into DEVICE memory d_dst on the context's stream (no wait); fails (GPET_ERR_BAD_ARG, message
+// set) before a converged fit of the current trace or when len_cap is below the batch's widest edge
+int enqueue_results(gpet_batch* b, int64_t len_cap, void* d_dst);
 // ---- gpet_api_batch.hip ---------------------------------------------------------------------------------------------------
 int fetch_all_scalars(gpet_batch* b);
 int check_device_status(gpet_batch* b);

@@ -7,6 +7,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   GPET_BATCH_SCOPE(b);
   if (!b || !base_seeds || !n_active || max_iters < 0) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
+  b->have_results = false;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(b->d_seeds, base_seeds, sizeof(uint32_t) * b->B, hipMemcpyHostToDevice, c->stream));
   // Normals: the seeds of upcoming iterations are known (gpet.py:839), so the RNG stream runs ahead of the loop on

@@ -330,6 +330,18 @@ def device_final_fits(batch, ps, obs_list, iters):
     return out, rounds
 
 
+def results_from_records(rec, return_std):
+    """Per-edge results in the form ``finish`` returns them -- edge_trace (edge_len, 2) int64 yx, or (edge_trace, (lower,
+    upper)) with ``return_std`` -- from decoded result records (_lib.decode_results), trimmed to each edge's own length;
+    and the statistics dict(n_iter, n_obs, theta, nlml), one entry per edge."""
+    out = []
+    for e, L in enumerate(rec["edge_len"].tolist()):
+        et = rec["trace"][e, :L]
+        out.append((et, (rec["lower"][e, :L], rec["upper"][e, :L])) if return_std else et)
+    stats = dict(n_iter=rec["n_iter"], n_obs=rec["n_obs"], theta=rec["theta"], nlml=rec["nlml"])
+    return out, stats
+
+
 class GP_Edge_Tracing_Batch(object):
     """B independent edges traced together on one GPU (BASELINE config 4's per-GPU share).
 
@@ -469,6 +481,13 @@ class GP_Edge_Tracing_Batch(object):
             et = np.rint(curve[:, [1, 0]]).astype(int)
             out.append((et, (mean - 1.96 * std, mean + 1.96 * std)) if self.return_std else et)
         return out
+
+    def results(self):
+        """What ``finish`` returned for every edge, recomputed on the device from the converged fits it left there
+        (gpet_batch_results: the same bits), plus the statistics of each trace: (per-edge results, dict(n_iter, n_obs,
+        theta, nlml)).  Valid after ``__call__`` or ``finish``; before a converged fit of the current trace it raises
+        GpetError."""
+        return results_from_records(self._batch.results(), self.return_std)
 
     def __call__(self, max_iter=1000):
         t0 = t.time()

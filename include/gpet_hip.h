@@ -313,7 +313,30 @@ int gpet_lml_stats(gpet_batch* b, int reset, double* kernel_ms, int64_t* evaluat
  *                                                                d_grad to gpet_batch_create2(..., GPET_GRAD_ON_DEVICE)
  *           gpet_gather_traces(comm, local, n_edges, len, all)   host int64 [n_local][len][2] -> [n_edges][len][2] on every
  *                                                                rank, in global edge order (blocks as gpet_comm_block)
- *           gpet_allgather_i64(comm, local, counts, all)         the same for blocks of counts[r] int64 per rank (sequences) */
+ *           gpet_allgather_i64(comm, local, counts, all)         the same for blocks of counts[r] int64 per rank (sequences)
+ *           gpet_gather_results(comm, batch, n_edges, cap, all)  the finished result RECORD of every edge (below) -> host
+ *                                                                [n_edges] records on every rank, in global edge order
+ * Result records: what GP_Edge_Tracing(..., return_std=True) returns for an edge (gpet.py:874-886, 902-903) plus the trace's
+ * statistics, in one fixed layout that a host in any language reads without the library:
+ *   record = gpet_result_head | int64 trace[len_cap][2] (yx: rint(mean), x_st + k; gpet.py:885-886)
+ *                             | f64 lower[len_cap] | f64 upper[len_cap]  (mean -/+ 1.96 std, gpet.py:876)
+ *   entries past the edge's own edge_len are zero; gpet_result_bytes gives the size of one record (48 + 32 len_cap bytes).
+ *   gpet_batch_results(batch, len_cap, dst, on_device)   the B records of a batch, contiguous, computed on the device from the
+ *       converged fit (k_finish_results, bit for bit what the host computes from gpet_final_fit_all's mean / std): valid only
+ *       after gpet_final_fit_all has run on the batch's current trace (GPET_ERR_BAD_ARG before it and after gpet_batch_reset,
+ *       gpet_batch_set_images, gpet_batch_set_obs or more loop iterations); len_cap >= the batch's widest edge.  dst is host
+ *       memory (on_device = 0: complete on return) or device memory (1: enqueued on the context's stream).
+ *   gpet_gather_results: each rank packs its block straight into the communicator's device buffer and ONE all-gather of the
+ *       padded blocks runs; batch is NULL on a rank that owns no edges, else its B equals the rank's block and its context is
+ *       the communicator's.  A world of one without a communicator is a copy. */
+typedef struct gpet_result_head {  /* one per edge, followed by its arrays */
+  int32_t edge_len;  /* points of this edge's x-grid                                gpet.py:112 */
+  int32_t n_iter;    /* loop iterations                                             gpet.py:865 */
+  int32_t n_obs;     /* final observation count                                     gpet.py:861 */
+  int32_t status;    /* gpet_status raised on the device for this edge */
+  double theta[3];   /* log(constant, length_scale, noise_level) at the optimum     gpet.py:241-248 */
+  double nlml;       /* -log marginal likelihood at the optimum */
+} gpet_result_head;
 typedef struct gpet_comm gpet_comm;
 #define GPET_COMM_ID_BYTES 128
 int gpet_comm_unique_id(void* id128);
@@ -330,6 +353,9 @@ int gpet_dev_free(gpet_ctx* ctx, void* ptr);
 int gpet_dev_copy(gpet_ctx* ctx, void* dst, const void* src, size_t bytes, int to_host);
 int gpet_allgather_i64(gpet_comm* comm, const int64_t* h_local, const int64_t* counts, int64_t* h_all);
 int gpet_gather_traces(gpet_comm* comm, const int64_t* h_local, int64_t n_edges, int64_t edge_len, int64_t* h_all);
+int gpet_result_bytes(int64_t len_cap, size_t* bytes);
+int gpet_batch_results(gpet_batch* b, int64_t len_cap, void* dst, int dst_on_device);
+int gpet_gather_results(gpet_comm* comm, gpet_batch* local, int64_t n_edges, int64_t len_cap, void* h_all);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
