@@ -6,7 +6,10 @@ int nu_to_code(double nu) {
   if (nu == 0.5) return 0;
   if (nu == 1.5) return 1;
   if (nu == 2.5) return 2;
-  if (nu > 0.0 && nu <= 1e6) return 3;  // any other smoothness: Bessel form by quadrature (gpet.py:134)
+  // any other smoothness: Bessel form by quadrature (gpet.py:134).  Both bounds keep its node count bounded: from above
+  // the step shrinks as 0.45 / sqrt(nu); from below the node range reaches down to -40 / nu where q = nu r^2 / 2 is tiny
+  // (and where q underflows to 0, below nu ~ 1e-291, the count is unbounded).  The tests pin both ends.
+  if (nu >= 0.01 && nu <= 1000.0) return 3;
   return -1;
 }
 
@@ -167,7 +170,7 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
         p.n_keep > p.n_samples || p.delta_x < 1 || p.length_scale <= 0)
       return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: edge %d has inconsistent parameters", e);
     if (p.kernel_type == GPET_KERNEL_MATERN && nu_to_code(p.nu) < 0)
-      return fail(c, GPET_ERR_UNSUPPORTED, "Matern nu=%g is not a positive finite smoothness", p.nu);
+      return fail(c, GPET_ERR_UNSUPPORTED, "Matern nu=%g is outside 0.01 <= nu <= 1000 (nu = inf is the RBF kernel)", p.nu);
     E.M = M;
     E.N = N;
     E.x_st = p.x_st;
@@ -205,7 +208,9 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
     E.kernel_type = p.kernel_type;
     E.nu_code = p.kernel_type == GPET_KERNEL_MATERN ? nu_to_code(p.nu) : 2;
     E.nu_gen = p.nu;
-    E.inv_gamma_nu = (E.nu_code == 3) ? 1.0 / tgamma(p.nu) : 1.0;
+    // (1 / Gamma(nu); above nu = 170, where matern_gen's sum of ~Gamma(nu) / h would overflow, -lgamma(nu), which it
+    //  folds into its exponent)
+    E.inv_gamma_nu = (E.nu_code != 3) ? 1.0 : (p.nu <= 170.0 ? 1.0 / tgamma(p.nu) : -lgamma(p.nu));
     E.tab_ok = 1;
     if (E.nu_code == 3) any_gen_nu = true;
     E.fix_endpoints = p.fix_endpoints;

@@ -53,10 +53,21 @@ __device__ __forceinline__ void xcd_edge_part(int nparts, int& edge, int& part) 
 // kernel_options = {'kernel': 'Matern', 'nu': ...}, gpet.py:134):
 //   rho(r) = 2^(1-nu) / Gamma(nu) (sqrt(2 nu) r)^nu K_nu(sqrt(2 nu) r)  =  1 / Gamma(nu) int exp(nu s - e^s - q e^-s) ds,
 // q = nu r^2 / 2  (substitute u = e^s in the Gamma-mixture-of-Gaussians form of x^nu K_nu(x)).  The integrand decays
-// doubly exponentially on both sides, so the trapezoid rule converges geometrically: absolute error <= 3e-14 against
-// scipy.special.kv for nu in [0.7, 20] with the step below (~60-400 nodes).  Also d rho / d log(length_scale)
+// doubly exponentially on both sides, so the trapezoid rule converges geometrically: absolute error <= 4e-14 for
+// 0.1 <= nu <= 170 with the step below (~60-600 nodes; ~1e-13 at nu = 500 and ~6e-13 at nu = 1000, where nu s itself
+// carries that rounding), pinned against an exact reference by tests/test_gpu_matern_nu.py.  Also d rho / d log(length_scale)
 // = 2 q / Gamma(nu) int exp((nu - 1) s - e^s - q e^-s) ds -- analytic, where sklearn differentiates numerically.
+// inv_gamma: 1 / Gamma(nu) for nu <= 170; above, it is -lgamma(nu) < 0 instead, folded into the exponent (+ 0.0 at
+// nu <= 170: the same arithmetic bit for bit).  Gamma(nu) itself is finite up to nu = 171.62, but the running sum,
+// ~Gamma(nu) / h, overflows from nu ~ 170.97 and the peak term exp(nu s - e^s) from nu ~ 171.3.
+// r == 0 (a zero distance off a self-kernel's diagonal; callers write the diagonal themselves) is evaluated at eps with
+// a zero derivative, as sklearn does: it adds eps to exact zeros, and its forward difference of two equal values is 0.
+// 0.01 <= nu <= 1000 (nu_to_code).
 __device__ double matern_gen(double nu, double inv_gamma, double r, double* dlogl) {
+  const bool at_zero = (r == 0.0);
+  if (at_zero) r = 2.220446049250313e-16;  // np.finfo(float).eps
+  const double lsh = inv_gamma > 0.0 ? 0.0 : inv_gamma;
+  const double scale = inv_gamma > 0.0 ? inv_gamma : 1.0;
   const double q = 0.5 * nu * r * r;
   double h = 0.45 * rsqrt(nu);
   if (h > 0.2) h = 0.2;
@@ -71,12 +82,12 @@ __device__ double matern_gen(double nu, double inv_gamma, double r, double* dlog
   for (int k = n0; k <= n1; ++k) {
     const double sv = (double)k * h;
     const double es = exp(sv);
-    const double w = exp(nu * sv - es - q / es);
+    const double w = exp(nu * sv - es - q / es + lsh);
     sum += w;
     dsum += w / es;
   }
-  if (dlogl != nullptr) *dlogl = 2.0 * q * h * dsum * inv_gamma;
-  return h * sum * inv_gamma;
+  if (dlogl != nullptr) *dlogl = at_zero ? 0.0 : 2.0 * q * h * dsum * scale;
+  return h * sum * scale;
 }
 
 // sklearn kernels.py RBF / Matern on pre-scaled 1-D inputs a = x_i / l, b = x_j / l.
