@@ -568,7 +568,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
   }
   b->iters_issued = 0;   // (all edges of a batch are restarted together)
   if ((int)b->h_nobs_prev.size() != b->B) b->h_nobs_prev.assign(b->B, 0);
-  b->h_nobs_prev[e] = n_obs;  // (the loop's group sizes follow the growth of the observation sets from here)
+  b->h_nobs_prev[e] = n_obs;  // (a batch of up to 64 edges sizes the loop's groups by the growth of its observation sets from here: next_group)
   b->norm_issued = 0;
   if (b->structured)
     for (int i = 0; i < n_obs; ++i)

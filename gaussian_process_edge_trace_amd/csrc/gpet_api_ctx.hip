@@ -75,58 +75,6 @@ int fin_lattice(const double* x, int n, double* hinv) {
   return (int)mr;
 }
 
-// One sequential walk per stream: the register-resident generator (four streams per wave, gpet_rng.hip) when the batch is
-// homogeneous and the launch has enough streams to fill the GPU with single waves (2 048 = half of its SIMDs; a wave of
-// four streams takes ~2.5 ms against 0.6 ms for a three-wave workgroup per stream, so small launches keep the old kernel),
-// else one workgroup per stream (k_mt_normals).  The same numbers either way.
-hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l,
-                                     int add_iter, int iter_abs, int n_ahead, int z_store) {
-  const int o = opt(Opt::rng4);
-  if (b->bd.rng4 && (o > 0 || (o < 0 && (long long)B_l * n_ahead >= 2048)))
-    return launch_normals4(st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store, b->bd.Lg, b->bd.S, b->bd.z_cols);
-  return launch_normals(st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store);
-}
-
-// The normals of `n_ahead` iterations of B_l edges: one workgroup per stream (k_mt_normals), or -- when that leaves
-// most of the GPU idle and the streams are long -- every stream cut into chunks that many workgroups generate at once
-// (MT19937 jump-ahead, launch_normals_chunked).  The same numbers either way.
-int normals_auto(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
-                        int iter_abs, int n_ahead, int z_store, bool allow_chunked) {
-  gpet_ctx* c = b->ctx;
-  if (b->rng_mode == 1) {  // opt-in Philox mode (gpet_batch_set_rng)
-    HIPCHK(c, launch_normals_philox(st, edges_l, B_l, b->bd, seeds_l, add_iter, iter_abs, n_ahead, z_store));
-    return GPET_OK;
-  }
-  const int streams = B_l * n_ahead;
-  const int nc = mtj_chunks((long long)b->bd.S * b->bd.Lg);
-  const int o = opt(Opt::rng_chunked);  // -1: by launch shape
-  const bool force4 = opt(Opt::rng4) > 0 && b->bd.rng4;  // (tests: the register-resident generator on any launch shape)
-  // (the chunked form works in the batch's ONE jump workspace: a launch that runs beside another chunked launch of the same batch
-  //  -- the tail of a small batch's first normals on the fit stream, gpet_trace_iterate -- must take the sequential kernel)
-  const bool chunked = allow_chunked && !force4 && nc >= 2 && (o > 0 || (o < 0 && streams <= 32 && nc >= 4));
-  if (!chunked) {
-    HIPCHK(c, launch_normals_seq(b, st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store));
-    return GPET_OK;
-  }
-  const size_t need = mtj_work_bytes(streams, nc);
-  if (need > b->mtj_bytes) {
-    if (b->mtj_work) {
-      HIPCHK(c, hipDeviceSynchronize());  // (launches that use the old workspace may still be in flight)
-      (void)hipFree(b->mtj_work);
-      b->mtj_work = nullptr;
-      b->mtj_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc(&b->mtj_work, need));
-    b->mtj_bytes = need;
-  }
-  if (!b->d_mtj_poly) {
-    HIPCHK(c, hipMalloc(&b->d_mtj_poly, mtj_poly_bytes()));
-    HIPCHK(c, hipMemcpy(b->d_mtj_poly, mtj_poly_host(), mtj_poly_bytes(), hipMemcpyHostToDevice));
-  }
-  HIPCHK(c, launch_normals_chunked(st, edges_l, B_l, seeds_l, add_iter, iter_abs, n_ahead, z_store, b->mtj_work, nc, b->d_mtj_poly));
-  return GPET_OK;
-}
-
 extern "C" {
 
 int gpet_abi_version(void) { return GPET_ABI_VERSION; }

@@ -1,11 +1,14 @@
 // Internals shared by the translation units of the C ABI (include/gpet_hip.h): contexts and batches as the library sees them,
 // the error / wait helpers, and the few host-side helpers more than one unit needs.  Host-side plumbing only: all arithmetic
 // lives in the kernels (gpet_kernels.hip, gpet_eig.hip, gpet_lbfgsb.hip, gpet_rng.hip).
-//   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image), the shared helpers' definitions
+//   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image), the shared helpers' definitions (waits, errors, lattice)
 //   gpet_api_batch.hip   batches: creation (arena layout), destruction, images, observations, reset, reads / writes
 //   gpet_api_stages.hip  the per-stage entry points (a2-a7, f1) and gpet_profile_stage
 //   gpet_api_final.hip   the converged fit (f2): objective, device L-BFGS-B, posterior at the optimum
-//   gpet_api_loop.hip    the device-resident loop (a8): gpet_trace_iterate
+//   gpet_api_loop.hip    the device-resident loop (a8): gpet_trace_iterate, a short driver over its pieces (compaction, one function
+//                        per normals mode, the kernel chain of an iteration, the end of a group); the dispatch of the normal
+//                        generators (normals_auto, launch_normals_seq)
+//   gpet_loop_plan.h     the loop's scheduling decisions as plain data (no HIP): options -> LoopPlan, the chunked head, group sizes
 //   gpet_api_comm.hip    multi-GPU helpers on RCCL (8e): communicator, broadcast of the gradient image, gather of the traces
 //                        and of the result records
 //   gpet_api_results.hip the finished result record of every edge (k_finish_results): gpet_result_bytes, gpet_batch_results
@@ -57,7 +60,8 @@ struct gpet_batch {
   long long* d_obs = nullptr;          // [B][obs_cap_max][2] contiguous observations: one copy reads them all
   long long* d_init = nullptr;         // [B][n_init_max][2] contiguous init points: one copy writes them all
   std::vector<gpet_scalars> h_scalars;
-  std::vector<int> h_nobs_prev;        // observations per edge at the last group boundary of the loop (adaptive group sizes)
+  std::vector<int> h_nobs_prev;        // observations per edge at the last group boundary of the loop: batches up to 64 edges size
+                                       // the next group by their growth (next_group, gpet_loop_plan.h)
   int iters_issued = 0;                // iterations enqueued since the last reset (== sc->iter of active edges)
   int rng_mode = 0;                    // 0: MT19937 + polar method = numpy's RandomState stream; 1: Philox4x32-10 + Box-Muller (opt-in)
   hipStream_t side = nullptr;          // RNG stream: normals of upcoming iterations run ahead of the loop
@@ -140,6 +144,7 @@ struct Carver {  // lays buffers out in one arena (256-byte aligned); with base 
   }
 };
 int fin_lattice(const double* x, int n, double* hinv);
+// ---- gpet_api_loop.hip ----------------------------------------------------------------------------------------------------
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
                               int iter_abs, int n_ahead, int z_store);
 int normals_auto(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter, int iter_abs,

@@ -248,7 +248,7 @@ hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const B
   return hipGetLastError();
 }
 
-static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int rank_max, int scaled_out, bool logw, int r_cap) {
+static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int rank_max, int scaled_out, bool logw) {
   const int mm = (rank_max + 1) & ~1;
   static PerDeviceOnce once;
   if (once.first()) {
@@ -268,7 +268,6 @@ static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int ran
   }
   // warm start (structured loop only: there the matrix of an iteration is a small change of the last one's)
   const int warm = scaled_out ? opt(Opt::jacobi_warm) : 0;
-  (void)r_cap;
   if (warm) {
     const int nt = (rank_max + 15) >> 4;
 #define GPET_PR_LAUNCH(NT_)                                                                                                \
@@ -331,7 +330,7 @@ hipError_t launch_factor(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
   }
   const int t = cdiv(bd.r_cap, 16);
   if (parts & 2u) hipLaunchKernelGGL(k_gram, dim3(t, t, B), dim3(256), 0, st, d_edges);
-  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r_cap, 0, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0, bd.r_cap);
+  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r_cap, 0, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0);
   if (parts & 8u)
     hipLaunchKernelGGL(k_factor_rows, dim3(bd.r_cap, B), dim3(256), (size_t)bd.r_cap * sizeof(double), st, d_edges);
   return hipGetLastError();
@@ -369,7 +368,7 @@ hipError_t launch_struct_iteration(hipStream_t st, EdgeDev* d_edges, int B, cons
     const int l_in_lds = full <= (size_t)STRUCT_H_LDS_MAX ? 1 : 0;  // (gpet_batch_create checked that `rowm` fits)
     hipLaunchKernelGGL(k_struct_H, dim3(1, B), dim3(1024), l_in_lds ? full : rowm, st, d_edges, l_in_lds);
   }
-  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r0_max > 0 ? bd.r0_max : bd.r_cap, 1, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0, bd.r_cap);
+  if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r0_max > 0 ? bd.r0_max : bd.r_cap, 1, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0);
   if (parts & 8u) {
     // the variant k_struct_rows picks for r0_max: [4 KS][16 MT + 1] eigenvector tile
     const int rm = bd.r0_max;
