@@ -1,91 +1,6 @@
-// C ABI, part 2: batches of edges -- arena layout and creation, destruction, images, observation sets, reset, reads and writes.
+// C ABI, part 2: batches of edges -- creation (a driver over gpet_batch_plan.h, which resolves the edges and lays out the arena),
+// destruction, images, observation sets, reset, reads and writes.
 #include "gpet_api_internal.h"
-
-namespace {
-int nu_to_code(double nu) {
-  if (nu == 0.5) return 0;
-  if (nu == 1.5) return 1;
-  if (nu == 2.5) return 2;
-  // any other smoothness: Bessel form by quadrature (gpet.py:134).  Both bounds keep its node count bounded: from above
-  // the step shrinks as 0.45 / sqrt(nu); from below the node range reaches down to -40 / nu where q = nu r^2 / 2 is tiny
-  // (and where q underflows to 0, below nu ~ 1e-291, the count is unbounded).  The tests pin both ends.
-  if (nu >= 0.01 && nu <= 1000.0) return 3;
-  return -1;
-}
-
-// lays out one edge's buffers; with base == nullptr only measures
-void carve_edge(Carver& cv, EdgeDev& E, bool own_image, int batch_lg) {
-  const size_t Lg = E.Lg, nc = E.n_cap, rc = E.r_cap, S = E.S;
-  const size_t px = (size_t)E.M * E.N, gpx = (size_t)(E.M + 2) * (E.N + 2);
-  E.init_xy = cv.take<long long>(2 * (size_t)E.n_init);
-  E.obs_xy = cv.take<long long>(2 * (size_t)E.obs_cap);
-  E.obs_new = cv.take<long long>(2 * (size_t)E.obs_cap);
-  E.xt = cv.take<double>(nc);
-  E.yt = cv.take<double>(nc);
-  E.wt = cv.take<double>(nc);
-  E.alpha = cv.take<double>(nc);
-  E.chol_inv = cv.take<double>(nc > 128 ? (nc / 64 + 1) * 4096 : 1);
-  E.solve_z = cv.take<double>(nc > 128 ? nc : 1);
-  E.solve_flag = cv.take<int>(nc > 128 ? 2 * (nc / 64 + 1) : 2);
-  E.K = cv.take<double>(nc * nc);
-  E.V = cv.take<double>(nc * Lg);
-  E.mean = cv.take<double>(Lg);
-  E.std = cv.take<double>(Lg);
-  E.cov = cv.take<double>(Lg * Lg);
-  E.G = cv.take<double>(rc * Lg);
-  E.perm = cv.take<int>(rc);
-  E.C = cv.take<double>(rc * rc);
-  E.W = cv.take<double>(rc * rc);
-  E.Wq = cv.take<double>(2 * rc * rc);
-  E.Cw = cv.take<double>(rc * rc);
-  E.wq_tag = cv.take<int>(2);
-  E.theta = cv.take<double>(rc);
-  E.order = cv.take<int>(rc);
-  E.Q0 = cv.take<double>(rc * Lg);
-  E.lam0 = cv.take<double>(rc);
-  E.beta = cv.take<double>(rc);
-  E.h0 = cv.take<double>(rc);
-  E.rho_tab = cv.take<double>((size_t)E.N);
-  E.eig = cv.take<EigState>(1);
-  // (transposed copy of G: the any-rank factor, and the multi-workgroup pivoted Cholesky -- which launch_factor picks per BATCH
-  //  from the widest edge, pchol_multi_applies, and which then writes Gt of EVERY edge of the batch: the condition is the batch's)
-  E.Gt = cv.take<double>((rc > 96 || batch_lg > 1024) ? Lg * rc : 1);
-  E.Ap = cv.take<double>(rc > 96 ? 2 * Lg * rc : 1);
-  E.ap_tag = cv.take<int>(3);
-  E.pcx_d = cv.take<double>(Lg);
-  E.pcx_cand = cv.take<double>(16 * ((size_t)E.N / 32 + 2));  // (indexed with the widest edge of the batch)
-  E.jlog = cv.take<double>(E.jlog_cap > 0 ? (size_t)E.jlog_cap * 2 * rc * (rc / 2 + 1) : 2);
-  E.A = cv.take<double>((size_t)E.a_rows_cap * Lg + 64);  // (+ 64: the sample GEMM loads whole 64-column tiles of the last row)
-  E.Z = cv.take<double>((size_t)E.z_ring * S * (size_t)E.z_cols);
-  E.Yp = (int)((Lg + 15) & ~(size_t)15);
-  // (+ the spare region of the sample GEMM's idle lanes: they write 16 bytes at (Sround + 4 g) Yp + 2 lane doubles, g < 4, lane < 64 --
-  //  up to 128 doubles into row Sround + 12 whatever the pitch is, so the slack is sized in elements, not in rows)
-  E.Y = cv.take<double>((((S + 127) & ~(size_t)127) + 12) * (size_t)E.Yp + 128 + (size_t)E.Yp);
-  E.costs = cv.take<double>(S);
-  E.cost_part = cv.take<double>(S * 2 * (Lg / 30 + 2));  // (15 Simpson pairs = 30 columns per tile of the scorer)
-  E.best_costs = cv.take<double>((size_t)E.n_keep + 1);
-  E.best_idx = cv.take<int>((size_t)E.n_keep + 1);
-  E.bins = cv.take<double>(gpx);
-  E.tmpk = cv.take<double>(gpx);
-  E.kde = cv.take<float>(px);
-  E.kde_band = cv.take<int>(2 * ((size_t)E.N / 16 + 2));
-  E.colsum = cv.take<double>((size_t)E.N);
-  E.kde_wsum = cv.take<double>(2);
-  E.colbest = cv.take<double>((size_t)E.N);
-  E.colbest_y = cv.take<int>((size_t)E.N);
-  E.mm = cv.take<unsigned int>(4);
-  E.binbest = cv.take<unsigned long long>((size_t)E.n_bins);
-  E.binarg = cv.take<long long>((size_t)E.n_bins);
-  E.fin_x = cv.take<double>(nc);
-  E.fin_y = cv.take<double>(nc);
-  E.fin_w = cv.take<double>(nc);
-  E.fin_par = cv.take<double>(12);
-  if (own_image) {
-    E.grad = cv.take<float>(px);
-    E.grad_kde = cv.take<float>(px);
-  }
-}
-}  // namespace
 
 extern "C" {
 
@@ -134,9 +49,68 @@ int gpet_batch_create(gpet_ctx* c, int B, int M, int N, const float* const* grad
   return gpet_batch_create2(c, B, M, N, grad, share_image, params, init_xy, 0u, out);
 }
 
+// the edges' device scalars back to those of a fresh batch (enqueued on the context's stream; h_scalars is the staging copy)
+static hipError_t upload_pristine_scalars(gpet_batch* b) {
+  pristine_scalars(b->params.data(), b->h_edges.data(), b->B, b->h_scalars.data());
+  return hipMemcpyAsync(b->d_scalars, b->h_scalars.data(), sizeof(gpet_scalars) * (size_t)b->B, hipMemcpyHostToDevice, b->ctx->stream);
+}
+
+// Structured loop path: eigenbasis of the grid's correlation matrix, once per class of edges (basis_classes).  Usable when the
+// LDS Jacobi applies (capacity <= 96) and every training point lies on the grid; option "struct_path" = 0 disables it.
+static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
+  gpet_ctx* c = b->ctx;
+  const int B = b->B;
+  b->structured = false;
+  if (b->bd.r_cap > 96 || !opt(Opt::struct_path) || !struct_eligible(b->h_edges.data(), B, b->bd.N, init_xy)) return GPET_OK;
+  // The basis is computed for the first edge of every class only (a batch of 1 024 equal edges: one factorisation instead of 1 024,
+  // 7.5 ms of the constructor) and the others read that edge's copy, which then stays in L2 for the whole batch (k_struct_H
+  // gathers its rows, k_struct_rows streams it: 288 KB per edge at rank 72, Lg 500).
+  std::vector<int> rep_of, reps;
+  basis_classes(b->h_edges.data(), B, rep_of, reps);
+  if ((int)reps.size() == B) {
+    HIPCHK(c, launch_struct_basis(c->stream, b->d_edges, B, b->bd));
+  } else {
+    std::vector<EdgeDev> h_rep(reps.size());
+    for (size_t k = 0; k < reps.size(); ++k) h_rep[k] = b->h_edges[reps[k]];
+    EdgeDev* d_rep = nullptr;
+    HIPCHK(c, hipMalloc(&d_rep, sizeof(EdgeDev) * reps.size()));
+    hipError_t e1 = hipMemcpyAsync(d_rep, h_rep.data(), sizeof(EdgeDev) * reps.size(), hipMemcpyHostToDevice, c->stream);
+    if (e1 == hipSuccess) e1 = launch_struct_basis(c->stream, d_rep, (int)reps.size(), b->bd);
+    if (e1 == hipSuccess) e1 = gpet_wait(c->stream);
+    (void)hipFree(d_rep);
+    HIPCHK(c, e1);
+  }
+  int rc = fetch_all_scalars(b);
+  if (rc) return rc;
+  bool ok = true;
+  int r0_max = 0;
+  for (int e = 0; e < B; ++e) {
+    EdgeDev& E = b->h_edges[e];
+    const EdgeDev& F = b->h_edges[rep_of[(size_t)e]];
+    const gpet_scalars& s = b->h_scalars[rep_of[(size_t)e]];
+    if (s.status != GPET_OK || s.rank < 1 || s.rank >= E.r_cap) ok = false;  // rank capacity reached
+    E.r0 = s.rank;
+    if (rep_of[(size_t)e] != e) {
+      E.Q0 = F.Q0;
+      E.lam0 = F.lam0;
+      E.h0 = F.h0;  // (the sign convention's weights in that basis)
+    }
+    if (s.rank > r0_max) r0_max = s.rank;
+  }
+  b->bd.r0_max = r0_max;
+  if (!struct_h_fits_lds(b->bd, r0_max)) ok = false;
+  // back to the pristine scalar state
+  for (int e = 0; e < B; ++e) b->h_edges[e].structured = ok ? 1 : 0;
+  HIPCHK(c, upload_pristine_scalars(b));
+  HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * B, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gpet_wait(c->stream));
+  b->structured = ok;
+  return GPET_OK;
+}
+
 int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
                        const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
-  if (!c || !out || B <= 0 || M < 2 || N < 2 || !grad || !params || !init_xy)
+  if (!c || !out || !batch_shape_ok(B, M, N) || !grad || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
   HIPCHK(c, hipSetDevice(c->device));
@@ -150,112 +124,25 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   b->B = B;
   b->share_image = share_image ? 1 : 0;
   b->h_edges.resize(B);
+  b->h_scalars.resize(B);
   b->params.assign(params, params + B);
-  BatchDims bd{};
-  bd.M = M;
-  bd.N = N;
-  bd.lg_even = 1;
-  bool any_big = false, any_gen_nu = false;
+  // the edges' geometry and capacities, the batch's dimensions
+  const bool any_big = any_big_edge(params, B);
+  const int jlog_max_b = opt(Opt::jlog_max_b);
+  bool any_gen_nu = false;
   for (int e = 0; e < B; ++e) {
-    const int Lg_e = params[e].x_en - params[e].x_st + 1;
-    const int cap = params[e].factor_cap > 0 ? params[e].factor_cap : 96;
-    if ((cap < Lg_e ? cap : Lg_e) > 96) any_big = true;
+    const EdgeCheck chk = resolve_edge(b->h_edges[e], params[e], B, M, N, any_big, jlog_max_b);
+    if (chk == EdgeCheck::inconsistent)
+      return fail(c, edge_check_status(chk), "gpet_batch_create: edge %d has inconsistent parameters", e);
+    if (chk == EdgeCheck::matern_nu)
+      return fail(c, edge_check_status(chk), "Matern nu=%g is outside 0.01 <= nu <= 1000 (nu = inf is the RBF kernel)", params[e].nu);
+    if (b->h_edges[e].nu_code == 3) any_gen_nu = true;
   }
-  for (int e = 0; e < B; ++e) {
-    const gpet_params& p = params[e];
-    EdgeDev& E = b->h_edges[e];
-    memset(&E, 0, sizeof E);
-    const int Lg = p.x_en - p.x_st + 1;
-    if (p.x_st < 0 || p.x_en >= N || Lg < 4 || p.n_init < 1 || p.n_samples < 1 || p.n_keep < 0 ||
-        p.n_keep > p.n_samples || p.delta_x < 1 || p.length_scale <= 0)
-      return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: edge %d has inconsistent parameters", e);
-    if (p.kernel_type == GPET_KERNEL_MATERN && nu_to_code(p.nu) < 0)
-      return fail(c, GPET_ERR_UNSUPPORTED, "Matern nu=%g is outside 0.01 <= nu <= 1000 (nu = inf is the RBF kernel)", p.nu);
-    E.M = M;
-    E.N = N;
-    E.x_st = p.x_st;
-    E.x_en = p.x_en;
-    E.Lg = Lg;
-    E.S = p.n_samples;
-    E.n_keep = p.n_keep;
-    E.n_init = p.n_init;
-    // bins of np.round((x - x_st)/delta_x) over every image column (gpet.py:605-606)
-    E.bin_lo = (int)rint((double)(0 - p.x_st) / (double)p.delta_x);
-    E.n_bins = (int)rint((double)(N - 1 - p.x_st) / (double)p.delta_x) - E.bin_lo + 2;
-    E.obs_cap = p.obs_cap > E.n_bins ? p.obs_cap : E.n_bins;
-    E.n_cap = E.n_init + E.obs_cap;
-    E.r_cap = p.factor_cap > 0 ? p.factor_cap : 96;  // <= 96: the LDS-resident Jacobi path
-    if (E.r_cap > Lg) E.r_cap = Lg;
-    // A capacity above 96 selects the whole-GPU Jacobi on the full covariance; that path is
-    // chosen per batch, so then every edge keeps all Lg directions.
-    if (any_big) E.r_cap = Lg;
-    E.z_cols = p.z_cols > 0 ? p.z_cols : E.r_cap;
-    if (E.z_cols > Lg) E.z_cols = Lg;
-    if (any_big) E.z_cols = Lg;
-    if (E.z_cols < E.r_cap) E.r_cap = E.z_cols;
-    E.a_rows_cap = (E.z_cols >= Lg) ? Lg : E.r_cap;
-    // ring of pre-generated normals: look-ahead + 2 slots.  Small batches are latency-bound in the generator and draw
-    // 8 iterations ahead (gpet_trace_iterate); a batch that fills the GPU draws 1 ahead (up to 3 by option): 4 slots
-    // instead of 16 -- at 1024 edges of the bench shape 2.4 GB instead of 9.4 GB of an 18 GB arena.  Full-stream mode
-    // (z_cols == Lg: full-rank covariances, tests) holds whole 8 MB streams per slot: 2.
-    // slots of the normals ring: 16 for small batches (eight iterations ahead on the side stream), 9 above 64 edges (the
-    // eight iterations of a group are generated by one launch), 2 when a row holds the whole grid (config 3)
-    E.z_ring = (E.z_cols >= Lg && Lg > 128) ? 2 : (B <= 64 ? 16 : 9);
-    // small batches are bound by the chain of Jacobi rounds: their rotations are logged and the eigenvectors formed by a
-    // second kernel (k_jacobi_wpass); 40 sweeps x (m - 1) rounds x m / 2 pairs x 16 bytes = 2.9 MB per edge at rank 96
-    const int jlog_max_b = opt(Opt::jlog_max_b);  // (32: the rotation-log form pays while the chain of rounds is the time)
-    E.jlog_cap = (B <= jlog_max_b && E.r_cap <= 96) ? 40 : 0;
-    E.kernel_type = p.kernel_type;
-    E.nu_code = p.kernel_type == GPET_KERNEL_MATERN ? nu_to_code(p.nu) : 2;
-    E.nu_gen = p.nu;
-    // (1 / Gamma(nu); above nu = 170, where matern_gen's sum of ~Gamma(nu) / h would overflow, -lgamma(nu), which it
-    //  folds into its exponent)
-    E.inv_gamma_nu = (E.nu_code != 3) ? 1.0 : (p.nu <= 170.0 ? 1.0 / tgamma(p.nu) : -lgamma(p.nu));
-    E.tab_ok = 1;
-    if (E.nu_code == 3) any_gen_nu = true;
-    E.fix_endpoints = p.fix_endpoints;
-    E.delta_x = p.delta_x;
-    E.pixel_thresh = p.pixel_thresh;
-    E.algo_thresh = Lg / p.delta_x - (p.pixel_thresh - 1);  // gpet.py:117-119
-    E.sigma_f = p.sigma_f;
-    E.length_scale = p.length_scale;
-    E.noise_y = p.noise_y;
-    E.jitter = p.jitter;
-    if (Lg > bd.Lg) bd.Lg = Lg;
-    if (Lg & 1) bd.lg_even = 0;
-    if (E.S > bd.S) bd.S = E.S;
-    if (E.n_keep > bd.n_keep) bd.n_keep = E.n_keep;
-    if (E.z_cols > bd.z_cols) bd.z_cols = E.z_cols;
-    if (E.r_cap > bd.r_cap) bd.r_cap = E.r_cap;
-    if (E.n_cap > bd.n_cap) bd.n_cap = E.n_cap;
-    if (E.n_bins > bd.n_bins) bd.n_bins = E.n_bins;
-    if (E.obs_cap > bd.obs_cap) bd.obs_cap = E.obs_cap;
-    if (E.a_rows_cap > bd.a_rows_cap) bd.a_rows_cap = E.a_rows_cap;
-    if (bd.z_ring == 0 || E.z_ring < bd.z_ring) bd.z_ring = E.z_ring;
-    bd.jlog = E.jlog_cap > 0 ? 1 : 0;
-  }
-  bd.rng4 = normals4_applies(b->h_edges.data(), B) ? 1 : 0;
-  b->bd = bd;
-  // measure, allocate, carve
-  const size_t px = (size_t)M * N;
+  b->bd = reduce_dims(b->h_edges.data(), B, M, N);
+  b->bd.rng4 = normals4_applies(b->h_edges.data(), B) ? 1 : 0;
+  // the arena: measure, allocate, place
   Carver meas;
-  std::vector<EdgeDev> tmp = b->h_edges;
-  float* shared_grad = nullptr;
-  float* shared_kde = nullptr;
-  if (b->share_image) {
-    shared_grad = meas.take<float>(px);
-    shared_kde = meas.take<float>(px);
-  }
-  (void)meas.take<gpet_scalars>((size_t)B);
-  (void)meas.take<double>((size_t)B * 2 * bd.Lg);
-  (void)meas.take<double>((size_t)B * 12);
-  (void)meas.take<long long>((size_t)B * 2 * bd.obs_cap);
-  int n_init_max = 1;
-  for (int e = 0; e < B; ++e) n_init_max = b->h_edges[e].n_init > n_init_max ? b->h_edges[e].n_init : n_init_max;
-  (void)meas.take<long long>((size_t)B * 2 * (size_t)n_init_max);
-  for (int e = 0; e < B; ++e) carve_edge(meas, tmp[e], !b->share_image, bd.Lg);
-  (void)shared_grad;
-  (void)shared_kde;
+  layout_batch(meas, b->h_edges.data(), B, b->bd, b->share_image != 0);
   b->arena_bytes = meas.off + 256;
   hipError_t he = hipMalloc(&b->arena, b->arena_bytes);
   if (he != hipSuccess) {
@@ -265,153 +152,43 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   HIPCHK(c, hipMemsetAsync(b->arena, 0, b->arena_bytes, c->stream));
   Carver cv;
   cv.base = b->arena;
-  if (b->share_image) {
-    shared_grad = cv.take<float>(px);
-    shared_kde = cv.take<float>(px);
-  }
-  b->d_scalars = cv.take<gpet_scalars>((size_t)B);
-  b->d_fin_out = cv.take<double>((size_t)B * 2 * bd.Lg);
-  b->d_fin_par = cv.take<double>((size_t)B * 12);
-  b->d_obs = cv.take<long long>((size_t)B * 2 * bd.obs_cap);
-  b->d_init = cv.take<long long>((size_t)B * 2 * (size_t)n_init_max);
-  b->h_scalars.resize(B);
-  for (int e = 0; e < B; ++e) {
-    EdgeDev& E = b->h_edges[e];
-    E.sc = b->d_scalars + e;
-    E.fin_out = b->d_fin_out + (size_t)e * 2 * bd.Lg;
-    carve_edge(cv, E, !b->share_image, bd.Lg);
-    E.fin_par = b->d_fin_par + (size_t)e * 12;                 // (batch-contiguous; the per-edge carve is unused)
-    E.obs_xy = b->d_obs + (size_t)e * 2 * bd.obs_cap;
-    E.init_xy = b->d_init + (size_t)e * 2 * (size_t)n_init_max;  // (batch-contiguous; the per-edge carve is unused)
-    if (b->share_image) {
-      E.grad = shared_grad;
-      E.grad_kde = shared_kde;
-    }
-  }
+  const BatchBlocks bb = layout_batch(cv, b->h_edges.data(), B, b->bd, b->share_image != 0);
+  b->d_scalars = bb.scalars;
+  b->d_fin_out = bb.fin_out;
+  b->d_fin_par = bb.fin_par;
+  b->d_obs = bb.obs;
+  b->d_init = bb.init;
+  // small allocations, streams, events
   HIPCHK(c, hipMalloc(&b->d_edges, sizeof(EdgeDev) * B));
   HIPCHK(c, hipMalloc(&b->d_seeds, sizeof(unsigned int) * B));
   HIPCHK(c, hipMalloc(&b->d_minmax, sizeof(unsigned int) * 2 * (size_t)B));
-  {
-    // (the stream the normals run ahead of the loop on: default priority -- lowest / highest were measured, +-0)
-    HIPCHK(c, hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
-  }
-  {
-    int pr_least = 0, pr_greatest = 0;
-    HIPCHK(c, hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-    // the stream the converged fits' objective runs on has the highest priority (its launches are small and many)
-    const int prio = pr_greatest;
-    HIPCHK(c, hipStreamCreateWithPriority(&b->fit, hipStreamNonBlocking, prio));
-  }
+  // (the stream the normals run ahead of the loop on: default priority -- lowest / highest were measured, +-0)
+  HIPCHK(c, hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
+  // the stream the converged fits' objective runs on has the highest priority (its launches are small and many)
+  int pr_least = 0, pr_greatest = 0;
+  HIPCHK(c, hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+  HIPCHK(c, hipStreamCreateWithPriority(&b->fit, hipStreamNonBlocking, pr_greatest));
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_norm[i], hipEventDisableTiming));
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_gemm[i], hipEventDisableTiming));
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pix[i], hipEventDisableTiming));
   HIPCHK(c, hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming));
   // upload: gradient image(s) re-normalised on the device (gpet.py:97), inits, initial scalars
-  HIPCHK(c, hipMalloc(&b->d_raw, px * sizeof(float)));
-  {
-    int rcu = upload_images(b, grad, flags);
-    if (rcu) return rcu;
-  }
+  HIPCHK(c, hipMalloc(&b->d_raw, (size_t)M * N * sizeof(float)));
+  int rc = upload_images(b, grad, flags);
+  if (rc) return rc;
   // (one copy each for the init points and the initial scalars of all edges: 3 x B small copies were most of the constructor)
-  std::vector<long long> h_init((size_t)B * 2 * (size_t)n_init_max, 0);
-  auto pristine_scalars = [&]() {
-    for (int e = 0; e < B; ++e) {
-      gpet_scalars& s0 = b->h_scalars[e];
-      memset(&s0, 0, sizeof s0);
-      s0.score_thresh = params[e].score_thresh;
-      s0.done = (0 >= b->h_edges[e].algo_thresh) ? 1 : 0;  // gpet.py:829 with no observations yet
-    }
-    return hipMemcpyAsync(b->d_scalars, b->h_scalars.data(), sizeof(gpet_scalars) * (size_t)B, hipMemcpyHostToDevice, c->stream);
-  };
+  std::vector<long long> h_init((size_t)B * 2 * (size_t)bb.n_init_max, 0);
   for (int e = 0; e < B; ++e)
-    memcpy(&h_init[(size_t)e * 2 * (size_t)n_init_max], init_xy[e], sizeof(long long) * 2 * (size_t)b->h_edges[e].n_init);
+    memcpy(&h_init[(size_t)e * 2 * (size_t)bb.n_init_max], init_xy[e], sizeof(long long) * 2 * (size_t)b->h_edges[e].n_init);
   HIPCHK(c, hipMemcpyAsync(b->d_init, h_init.data(), sizeof(long long) * h_init.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, pristine_scalars());
+  HIPCHK(c, upload_pristine_scalars(b));
   HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * B, hipMemcpyHostToDevice, c->stream));
   if (any_gen_nu) HIPCHK(c, launch_rho_tab(c->stream, b->d_edges, B, N));
   // gradient KDE of every distinct image (gpet.py:127)
   HIPCHK(c, launch_kde(c->stream, b->d_edges, b->share_image ? 1 : B, b->bd, 1));
   HIPCHK(c, gpet_wait(c->stream));
-  // structured loop path: eigenbasis of the grid's correlation matrix, once per edge.  Usable when the
-  // LDS Jacobi applies (capacity <= 96) and every init x lies on the grid; option "struct_path" = 0 disables it.
-  b->structured = false;
-  if (!any_big && opt(Opt::struct_path)) {
-    bool ok = true;
-    // without fix_endpoints the pixel selection admits every image column (gpet.py:655-657 only filters when it is
-    // set), so the loop can accept observations outside [x_st, x_en] unless the edge spans the whole image: those are
-    // not on the grid the prior eigenbasis indexes
-    for (int e = 0; e < B && ok; ++e)
-      if (!b->h_edges[e].fix_endpoints && !(b->h_edges[e].x_st == 0 && b->h_edges[e].x_en == N - 1)) ok = false;
-    for (int e = 0; e < B && ok; ++e)
-      for (int i = 0; i < b->h_edges[e].n_init; ++i) {
-        const int64_t x = init_xy[e][2 * i];
-        if (x < b->h_edges[e].x_st || x > b->h_edges[e].x_en) ok = false;
-      }
-    if (ok) {
-      // Edges of the same grid length, first column, kernel and length scale have the same prior eigenbasis bit for bit
-      // (k_rho_fill forms the lags as fl((x_st+i)/l) - fl((x_st+j)/l), which depends on x_st in the last bits unless l is
-      // a power of two -- so x_st is part of the match; the amplitude is not: the matrix has unit amplitude).  It is computed
-      // for the first edge of every such class only (a batch of 1 024 equal edges: one factorisation instead of 1 024, 7.5 ms
-      // of the constructor) and the others read that edge's copy, which then stays in L2 for the whole batch (k_struct_H
-      // gathers its rows, k_struct_rows streams it: 288 KB per edge at rank 72, Lg 500).
-      std::vector<int> rep_of((size_t)B), reps;
-      for (int e = 0; e < B; ++e) {
-        const EdgeDev& E = b->h_edges[e];
-        int found = -1;
-        for (size_t k = reps.size() > 8 ? reps.size() - 8 : 0; k < reps.size() && found < 0; ++k) {  // (batches are homogeneous or nearly so: a short search)
-          const EdgeDev& F = b->h_edges[reps[k]];
-          if (F.Lg == E.Lg && F.x_st == E.x_st && F.kernel_type == E.kernel_type && F.nu_code == E.nu_code && F.nu_gen == E.nu_gen &&
-              F.length_scale == E.length_scale && F.r_cap == E.r_cap)
-            found = reps[k];
-        }
-        if (found < 0) {
-          found = e;
-          reps.push_back(e);
-        }
-        rep_of[(size_t)e] = found;
-      }
-      if ((int)reps.size() == B) {
-        HIPCHK(c, launch_struct_basis(c->stream, b->d_edges, B, b->bd));
-      } else {
-        std::vector<EdgeDev> h_rep(reps.size());
-        for (size_t k = 0; k < reps.size(); ++k) h_rep[k] = b->h_edges[reps[k]];
-        EdgeDev* d_rep = nullptr;
-        HIPCHK(c, hipMalloc(&d_rep, sizeof(EdgeDev) * reps.size()));
-        hipError_t e1 = hipMemcpyAsync(d_rep, h_rep.data(), sizeof(EdgeDev) * reps.size(), hipMemcpyHostToDevice, c->stream);
-        if (e1 == hipSuccess) e1 = launch_struct_basis(c->stream, d_rep, (int)reps.size(), b->bd);
-        if (e1 == hipSuccess) e1 = gpet_wait(c->stream);
-        (void)hipFree(d_rep);
-        HIPCHK(c, e1);
-      }
-      int rc2 = fetch_all_scalars(b);
-      if (rc2) return rc2;
-      int r0_max = 0;
-      for (int e = 0; e < B; ++e) {
-        EdgeDev& E = b->h_edges[e];
-        const EdgeDev& F = b->h_edges[rep_of[(size_t)e]];
-        const gpet_scalars& s = b->h_scalars[rep_of[(size_t)e]];
-        if (s.status != GPET_OK || s.rank < 1 || s.rank >= E.r_cap) ok = false;  // rank capacity reached
-        E.r0 = s.rank;
-        if (rep_of[(size_t)e] != e) {
-          E.Q0 = F.Q0;
-          E.lam0 = F.lam0;
-          E.h0 = F.h0;  // (the sign convention's weights in that basis)
-        }
-        if (s.rank > r0_max) r0_max = s.rank;
-      }
-      b->bd.r0_max = r0_max;
-      // (n_cap <= 128: k_struct_H keeps U in LDS -- it fits with L streamed row by row; larger: U in HBM, blocked)
-      if (b->bd.n_cap <= 128 &&
-          ((size_t)b->bd.n_cap * (r0_max | 1) + b->bd.n_cap + b->bd.r_cap) * sizeof(double) > (size_t)STRUCT_H_LDS_MAX)
-        ok = false;
-      // back to the pristine scalar state
-      for (int e = 0; e < B; ++e) b->h_edges[e].structured = ok ? 1 : 0;
-      HIPCHK(c, pristine_scalars());
-      HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * B, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, gpet_wait(c->stream));
-      b->structured = ok;
-    }
-  }
+  rc = setup_struct_basis(b, init_xy);
+  if (rc) return rc;
   guard.b = nullptr;  // success: the caller owns the batch
   *out = b;
   return GPET_OK;
@@ -823,13 +600,7 @@ static int batch_reset(gpet_batch* b, bool next_frame) {
       }
     }
   }
-  for (int e = 0; e < b->B; ++e) {
-    gpet_scalars& s0 = b->h_scalars[e];
-    memset(&s0, 0, sizeof s0);
-    s0.score_thresh = b->params[e].score_thresh;
-    s0.done = (0 >= b->h_edges[e].algo_thresh) ? 1 : 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(b->d_scalars, b->h_scalars.data(), sizeof(gpet_scalars) * b->B, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, upload_pristine_scalars(b));
   HIPCHK(c, gpet_wait(c->stream));
   return GPET_OK;
 }

@@ -2,7 +2,10 @@
 // the error / wait helpers, and the few host-side helpers more than one unit needs.  Host-side plumbing only: all arithmetic
 // lives in the kernels (gpet_kernels.hip, gpet_eig.hip, gpet_lbfgsb.hip, gpet_rng.hip).
 //   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image), the shared helpers' definitions (waits, errors, lattice)
-//   gpet_api_batch.hip   batches: creation (arena layout), destruction, images, observations, reset, reads / writes
+//   gpet_api_batch.hip   batches: creation (a short driver over gpet_batch_plan.h), destruction, images, observations, reset,
+//                        reads / writes
+//   gpet_batch_plan.h    what batch creation decides, as plain data (no HIP): edge parameters -> EdgeDev fields and BatchDims, the
+//                        arena's layout (layout_batch: the one place where buffer sizes live; Carver), structured-path planning
 //   gpet_api_stages.hip  the per-stage entry points (a2-a7, f1) and gpet_profile_stage
 //   gpet_api_final.hip   the converged fit (f2): objective, device L-BFGS-B, posterior at the optimum
 //   gpet_api_loop.hip    the device-resident loop (a8): gpet_trace_iterate, a short driver over its pieces (compaction, one function
@@ -132,17 +135,6 @@ int fail(gpet_ctx* ctx, int code, const char* fmt, ...);
     if (e_ != hipSuccess)                                                                          \
       return fail((ctx), GPET_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
-struct Carver {  // lays buffers out in one arena (256-byte aligned); with base == nullptr it only measures
-  size_t off = 0;
-  char* base = nullptr;
-  template <typename T>
-  T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
 int fin_lattice(const double* x, int n, double* hinv);
 // ---- gpet_api_loop.hip ----------------------------------------------------------------------------------------------------
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
