@@ -24,6 +24,11 @@ OK, ERR_BAD_ARG, ERR_HIP, ERR_NOT_PD, ERR_ITER_CAP, ERR_RANK_CAP, ERR_UNSUPPORTE
 KERNEL_RBF, KERNEL_MATERN = 0, 1
 GRAD_ON_DEVICE = 1  # gpet_batch_create2 / gpet_batch_set_images flag: the gradient image pointers are device pointers
 IMAGES_NEXT_FRAME = 2  # gpet_batch_set_images: the images continue the sequences just traced
+RAW_ON_DEVICE = 4  # gpet_grad_images / gpet_batch_create_raw / gpet_batch_set_raw_images: the frame pointers are device pointers
+# pixel types of raw frames (GPET_PIX_*): the dtypes that go to the device as they are
+PIX_U8, PIX_U16, PIX_F32, PIX_F64 = range(4)
+PIX_OF_DTYPE = {np.dtype(np.uint8): PIX_U8, np.dtype(np.uint16): PIX_U16, np.dtype(np.float32): PIX_F32,
+                np.dtype(np.float64): PIX_F64}
 
 
 class GpetParams(C.Structure):
@@ -68,6 +73,65 @@ def decode_results(raw, n, len_cap):
     return {k: np.array(rec[k]) for k in dt.names}
 
 
+def pix_code(dtype):
+    """GPET_PIX_* of a numpy dtype (or its name); ValueError for a dtype the device does not read."""
+    dt = np.dtype(dtype)
+    if dt not in PIX_OF_DTYPE:
+        raise ValueError("raw frames on the device must be uint8, uint16, float32 or float64, not %s" % dt)
+    return PIX_OF_DTYPE[dt]
+
+
+def native_frames(imgs):
+    """Raw frames as the library takes them: (list of C-contiguous (M, N) arrays of ONE dtype, GPET_PIX_* code).  ``imgs`` is a
+    (T, M, N) array or a sequence of (M, N) arrays.  uint8, uint16, float32 and float64 frames (native byte order) go up as
+    they are -- no copy of a contiguous one; a stack of any other dtype, or of mixed dtypes, is converted to float64, which is
+    what comp_grad_img does with every image."""
+    frames = [np.asarray(f) for f in imgs]
+    if not frames:
+        raise ValueError("no frames")
+    dts = {f.dtype for f in frames}
+    dt = dts.pop() if len(dts) == 1 else None
+    if dt is None or dt not in PIX_OF_DTYPE or not dt.isnative:
+        dt = np.dtype(np.float64)
+    frames = [np.ascontiguousarray(f, dtype=dt) for f in frames]
+    if frames[0].ndim != 2 or any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("raw frames must be 2-D arrays of one shape")
+    return frames, PIX_OF_DTYPE[dt]
+
+
+class RawFrames(object):
+    """The ``raw=`` argument of Batch / Batch.set_images: frames plus the kernel that makes gradient images of them.
+    Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
+    ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all."""
+
+    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None):
+        if (frames is None) == (device_ptrs is None):
+            raise ValueError("raw frames come either from the host or as device pointers")
+        self.kernel = np.ascontiguousarray(kernel, dtype=np.float64)
+        if self.kernel.ndim != 2 or self.kernel.size == 0:
+            raise ValueError("the gradient kernel must be a non-empty 2-D array")
+        if device_ptrs is not None:
+            if dtype is None or shape is None:
+                raise ValueError("device frames need their dtype and shape")
+            self.frames, self.pix, self.flags = None, pix_code(dtype), RAW_ON_DEVICE
+            self.ptrs = [int(p) for p in device_ptrs]
+            self.shape = (int(shape[0]), int(shape[1]))
+        else:
+            self.frames, self.pix = native_frames(frames)
+            self.flags = 0
+            self.ptrs = [f.ctypes.data for f in self.frames]
+            self.shape = self.frames[0].shape
+
+    def __len__(self):
+        return len(self.ptrs)
+
+    def pointer_array(self):
+        return (_P * len(self.ptrs))(*self.ptrs)
+
+    def kernel_args(self):
+        return self.kernel.ctypes.data, self.kernel.shape[0], self.kernel.shape[1]
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -91,12 +155,17 @@ SYMBOLS = {
     "gpet_timer_start": (C.c_int, [_P]),
     "gpet_timer_stop_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "gpet_grad_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "gpet_grad_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_uint,
+                                   C.POINTER(_P)]),
     "gpet_normalise_f32": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "gpet_batch_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int,
                                     C.POINTER(GpetParams), C.POINTER(_P), C.POINTER(_P)]),
     "gpet_batch_create2": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int,
                                      C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_create_raw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
     "gpet_batch_set_images": (C.c_int, [_P, C.POINTER(_P), C.c_uint]),
+    "gpet_batch_set_raw_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_uint]),
     "gpet_batch_destroy": (None, [_P]),
     "gpet_batch_size": (C.c_int, [_P]),
     "gpet_batch_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int]),
@@ -231,6 +300,11 @@ class Context:
         self.h = h
         self.device = device
         self._comms = []  # (weak references to the communicators built on this context: close() closes them first)
+        # A batch is destroyed THROUGH its context (gpet_batch_destroy waits on the context's stream), so the context must go
+        # last: close() closes the batches built on it first (weak references), and when the garbage collector finalises a
+        # context before batches of the same garbage (their weak references are dead by then, the count is not) the handle is
+        # kept until the last of them has closed.
+        self._batches, self._open_batches, self._close_pending = [], 0, False
 
     def check(self, rc):
         if rc != OK:
@@ -255,6 +329,15 @@ class Context:
                                             kernel.shape[0], kernel.shape[1], out.ctypes.data))
         return out
 
+    def grad_images(self, raw):
+        """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32."""
+        M, N = raw.shape
+        out = np.empty((len(raw), M, N), dtype=np.float32)
+        op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
+        kp, kh, kw = raw.kernel_args()
+        self.check(self.lib.gpet_grad_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, raw.flags, op))
+        return out
+
     def normalise_f32(self, img):
         a = np.ascontiguousarray(img, dtype=np.float32)
         out = np.empty_like(a)
@@ -268,8 +351,24 @@ class Context:
                 if cm is not None:
                     cm.close()
             self._comms = []
-            self.lib.gpet_ctx_destroy(self.h)
-            self.h = None
+            for ref in list(getattr(self, "_batches", [])):
+                b = ref()
+                if b is not None:
+                    b.close()
+            self._batches = []
+            if getattr(self, "_open_batches", 0) > 0:
+                self._close_pending = True
+                return
+            self._destroy()
+
+    def _destroy(self):
+        self.lib.gpet_ctx_destroy(self.h)
+        self.h = None
+
+    def _batch_closed(self):
+        self._open_batches -= 1
+        if self._close_pending and self._open_batches == 0 and self.h:
+            self._destroy()
 
     def __del__(self):
         try:
@@ -382,15 +481,22 @@ _DT = {BUF_X_TRAIN: np.float64, BUF_Y_TRAIN: np.float64, BUF_CHOL: np.float64, B
 class Batch:
     """gpet_batch: B independent edges processed together."""
 
-    def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None):
+    def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None, raw=None):
         """``grads``: float32 (M, N) arrays on the host -- or, with ``device_ptrs`` (a list of integer device
         addresses of f32 [M*N] images on the context's device, e.g. ``tensor.data_ptr()`` after an RCCL broadcast) and
-        ``shape`` = (M, N), nothing on the host at all: the library consumes the device images in place."""
+        ``shape`` = (M, N), nothing on the host at all: the library consumes the device images in place.  Or ``raw`` (a
+        RawFrames: frames + gradient kernel) instead of both: the gradient images are made on the device
+        (gpet_batch_create_raw)."""
         self.ctx = ctx
         self.lib = ctx.lib
         B = len(params)
         inits = [np.ascontiguousarray(i, dtype=np.int64) for i in inits]
-        if device_ptrs is not None:
+        if raw is not None:
+            if grads is not None or device_ptrs is not None:
+                raise ValueError("gradient images and raw frames are alternatives")
+            self.M, self.N = raw.shape
+            grads = raw  # (kept alive with the batch, like host gradient images)
+        elif device_ptrs is not None:
             self.M, self.N = int(shape[0]), int(shape[1])
             gp = (_P * len(device_ptrs))(*[int(p) for p in device_ptrs])
             flags = GRAD_ON_DEVICE
@@ -403,11 +509,21 @@ class Batch:
         ip = (_P * B)(*[i.ctypes.data for i in inits])
         pa = (GpetParams * B)(*params)
         h = _P()
-        ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags,
-                                              C.byref(h)))
+        if raw is not None:
+            assert len(raw) == (1 if share_image else B)
+            kp, kh, kw = raw.kernel_args()
+            ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
+                                                     1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
+        else:
+            ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags,
+                                                  C.byref(h)))
         self.h = h
         self.B = B
         import weakref
+        ctx._batches.append(weakref.ref(self))
+        ctx._open_batches += 1
+        if len(ctx._batches) > 4096:
+            ctx._batches[:] = [r for r in ctx._batches if r() is not None and getattr(r(), "h", None)]
         _live_batches.append(weakref.ref(self))
         if len(_live_batches) > 4096:  # (drop the references of batches that are gone)
             _live_batches[:] = [r for r in _live_batches if r() is not None and getattr(r(), "h", None)]
@@ -415,12 +531,19 @@ class Batch:
         self.share_image = bool(share_image)
         self._keep = (grads, inits)
 
-    def set_images(self, grads=None, device_ptrs=None, next_frame=False):
+    def set_images(self, grads=None, device_ptrs=None, next_frame=False, raw=None):
         """New gradient image(s) for the same edges, gradient KDE recomputed, loop state reset (gpet_batch_set_images).
         ``next_frame``: the images are the next frames of the sequences just traced, so an any-rank factor may start from
         the last trace's rows (GPET_IMAGES_NEXT_FRAME); otherwise nothing of an earlier trace is used."""
         n_img = 1 if self.share_image else self.B
         nf = IMAGES_NEXT_FRAME if next_frame else 0
+        if raw is not None:  # (a RawFrames: gpet_batch_set_raw_images)
+            if grads is not None or device_ptrs is not None:
+                raise ValueError("gradient images and raw frames are alternatives")
+            assert len(raw) == n_img and tuple(raw.shape) == (self.M, self.N)
+            kp, kh, kw = raw.kernel_args()
+            self.ctx.check(self.lib.gpet_batch_set_raw_images(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.flags | nf))
+            return
         if device_ptrs is not None:
             assert len(device_ptrs) == n_img
             gp = (_P * n_img)(*[int(p) for p in device_ptrs])
@@ -646,6 +769,7 @@ class Batch:
         if getattr(self, "h", None):
             self.lib.gpet_batch_destroy(self.h)
             self.h = None
+            self.ctx._batch_closed()
 
     def __del__(self):
         try:

@@ -44,6 +44,46 @@ static int upload_images(gpet_batch* b, const float* const* grad, unsigned int f
   return GPET_OK;
 }
 
+// The images of a batch as a caller may hand them over: finished f32 gradient images (gpet_batch_create2,
+// gpet_batch_set_images), or raw frames with the kernel that turns them into gradient images (gpet_batch_create_raw,
+// gpet_batch_set_raw_images).  Either way the arena's EdgeDev::grad buffers hold the normalised images afterwards.
+struct ImageSource {
+  const float* const* grad = nullptr;  // gradient images, or
+  const void* const* raw = nullptr;    // raw frames of pixel type pix, with
+  int pix = 0;
+  const double* kern = nullptr;        // the kh x kw kernel of gpet_utils.comp_grad_img
+  int kh = 0, kw = 0;
+  unsigned int flags = 0;              // GPET_GRAD_ON_DEVICE / GPET_RAW_ON_DEVICE (and GPET_IMAGES_NEXT_FRAME, not read here)
+};
+
+// raw frames -> comp_grad_img of each, straight into the arena: one batched pass on the device (conv_frames), no trip of a
+// gradient image through host memory.  One normalisation: the second one of the two-step path (comp_grad_img, then gpet.py:97)
+// subtracts a minimum of exactly 0 and divides by a span of exactly 1.
+static int convolve_images(gpet_batch* b, const ImageSource& s) {
+  gpet_ctx* c = b->ctx;
+  const int n_img = b->share_image ? 1 : b->B;
+  std::vector<float*> dst((size_t)n_img);
+  for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[g].grad;
+  const int rc = conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.kern, s.kh, s.kw, (s.flags & GPET_RAW_ON_DEVICE) != 0,
+                             dst.data(), b->d_minmax);
+  if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
+  return rc;
+}
+
+static int load_images(gpet_batch* b, const ImageSource& s) { return s.raw ? convolve_images(b, s) : upload_images(b, s.grad, s.flags); }
+
+// what can be refused before anything is allocated or enqueued (conv_frames checks the same on its own)
+static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img) {
+  if (!s.raw || !s.kern || s.kh <= 0 || s.kw <= 0) return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
+  if (!pix_bytes(s.pix)) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", s.pix);
+  if (!conv_fits_lds(s.kh, s.kw))
+    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", s.kh, s.kw,
+                conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
+  for (int g = 0; g < n_img; ++g)
+    if (!s.raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
+  return GPET_OK;
+}
+
 int gpet_batch_create(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
                       const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out) {
   return gpet_batch_create2(c, B, M, N, grad, share_image, params, init_xy, 0u, out);
@@ -108,11 +148,16 @@ static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
   return GPET_OK;
 }
 
-int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
-                       const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
-  if (!c || !out || !batch_shape_ok(B, M, N) || !grad || !params || !init_xy)
+// the one body of batch creation, whatever the images come as
+static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, const gpet_params* params,
+                             const int64_t* const* init_xy, gpet_batch** out) {
+  if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.raw) || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
+  if (src.raw) {
+    const int rc0 = check_raw_source(c, src, share_image ? 1 : B);
+    if (rc0) return rc0;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   gpet_batch* b = new (std::nothrow) gpet_batch();
   if (!b) return fail(c, GPET_ERR_HIP, "out of host memory");
@@ -172,9 +217,9 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_gemm[i], hipEventDisableTiming));
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pix[i], hipEventDisableTiming));
   HIPCHK(c, hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming));
-  // upload: gradient image(s) re-normalised on the device (gpet.py:97), inits, initial scalars
+  // upload: gradient image(s) re-normalised on the device (gpet.py:97) or made there from raw frames, inits, initial scalars
   HIPCHK(c, hipMalloc(&b->d_raw, (size_t)M * N * sizeof(float)));
-  int rc = upload_images(b, grad, flags);
+  int rc = load_images(b, src);
   if (rc) return rc;
   // (one copy each for the init points and the initial scalars of all edges: 3 x B small copies were most of the constructor)
   std::vector<long long> h_init((size_t)B * 2 * (size_t)bb.n_init_max, 0);
@@ -192,6 +237,28 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   guard.b = nullptr;  // success: the caller owns the batch
   *out = b;
   return GPET_OK;
+}
+
+int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
+                       const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
+  ImageSource src;
+  src.grad = grad;
+  src.flags = flags;
+  return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
+}
+
+int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                          int share_image, const gpet_params* params, const int64_t* const* init_xy, unsigned int flags,
+                          gpet_batch** out) {
+  if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw: bad argument");
+  ImageSource src;
+  src.raw = raw;
+  src.pix = pix;
+  src.kern = kern;
+  src.kh = kh;
+  src.kw = kw;
+  src.flags = flags;
+  return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
 }
 
 void gpet_batch_destroy(gpet_batch* b) {
@@ -611,18 +678,43 @@ int gpet_batch_reset(gpet_batch* b) {
   return batch_reset(b, false);
 }
 
-int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
-  GPET_BATCH_SCOPE(b);
-  if (!b || !grad) return GPET_ERR_BAD_ARG;
+// new images for an existing batch, whatever they come as (the one body of gpet_batch_set_images / gpet_batch_set_raw_images)
+static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
+  const unsigned int flags = src.flags;
   gpet_ctx* c = b->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, gpet_wait(c->stream));
-  int rc = upload_images(b, grad, flags);
+  int rc = load_images(b, src);
   if (rc) return rc;
   // gradient KDE of every distinct image (gpet.py:127), then the state of a fresh constructor
   HIPCHK(c, launch_kde(c->stream, b->d_edges, b->share_image ? 1 : b->B, b->bd, 1));
   b->have_fit = b->have_factor = b->have_normals = b->have_samples = b->have_scores = false;
   return batch_reset(b, (flags & GPET_IMAGES_NEXT_FRAME) != 0);
+}
+
+int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
+  GPET_BATCH_SCOPE(b);
+  if (!b || !grad) return GPET_ERR_BAD_ARG;
+  ImageSource src;
+  src.grad = grad;
+  src.flags = flags;
+  return batch_set_images_from(b, src);
+}
+
+// (a refused call -- unknown pixel type, null frame, oversized kernel -- has touched nothing: the batch traces on as it was)
+int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw, unsigned int flags) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  ImageSource src;
+  src.raw = raw;
+  src.pix = pix;
+  src.kern = kern;
+  src.kh = kh;
+  src.kw = kw;
+  src.flags = flags;
+  const int rc = check_raw_source(b->ctx, src, b->share_image ? 1 : b->B);
+  if (rc) return rc;
+  return batch_set_images_from(b, src);
 }
 
 }  // extern "C"

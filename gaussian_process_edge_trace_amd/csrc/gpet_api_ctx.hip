@@ -142,6 +142,8 @@ void gpet_ctx_destroy(gpet_ctx* c) {
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->scratch) (void)hipFree(c->scratch);
+  if (c->raw_dev) (void)hipFree(c->raw_dev);
+  if (c->raw_tab) (void)hipFree(c->raw_tab);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -189,11 +191,10 @@ int gpet_grad_image(gpet_ctx* c, const double* img, int M, int N, const double* 
   if (!c || !img || !kern || !out || M <= 0 || N <= 0 || kh <= 0 || kw <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_image: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t px = (size_t)M * N;
-  // scipy.ndimage.convolve == correlate with the flipped kernel; even extents shift the origin
+  // scipy.ndimage.convolve == correlate with the flipped kernel; even extents shift the origin (gpet_conv_plan.h)
   std::vector<double> wf((size_t)kh * kw);
-  for (int a = 0; a < kh; ++a)
-    for (int b = 0; b < kw; ++b) wf[(size_t)a * kw + b] = kern[(size_t)(kh - 1 - a) * kw + (kw - 1 - b)];
-  const int oy = kh / 2 - ((kh % 2 == 0) ? 1 : 0), ox = kw / 2 - ((kw % 2 == 0) ? 1 : 0);
+  conv_flip_taps(kern, kh, kw, wf.data());
+  const int oy = conv_origin(kh), ox = conv_origin(kw);
   Carver meas;
   (void)meas.take<double>(px);
   (void)meas.take<double>(wf.size());
@@ -218,6 +219,118 @@ int gpet_grad_image(gpet_ctx* c, const double* img, int M, int N, const double* 
   HIPCHK(c, hipMemcpyAsync(out, d_out, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, gpet_wait(c->stream));
   return GPET_OK;
+}
+
+// ---- a1 for stacks of raw frames ------------------------------------------------------
+}  // extern "C"
+
+// (device memory of the context that only grows; the stream is idle when it is replaced)
+static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return GPET_OK;
+  HIPCHK(c, gpet_wait(c->stream));
+  if (*mem) (void)hipFree(*mem);
+  *mem = nullptr;
+  *cap = 0;
+  HIPCHK(c, hipMalloc((void**)mem, bytes));
+  *cap = bytes;
+  return GPET_OK;
+}
+
+// n_img raw frames -> normalised f32 gradient images dst[g] (device), everything enqueued on the context's stream: the taps and
+// the pointer tables go up in one copy, host frames follow in the chunks of stage_plan (gpet_conv_plan.h) with ONE convolution
+// launch per chunk, device frames are read where they lie by one launch; one launch normalises all images.  Host frames are
+// copied straight out of the caller's (pageable) memory: packing each chunk into a ring of pinned slots first, so that the host
+// packs chunk k + 1 while the device works on chunk k, was built and measured -- 256 frames of 500 x 500: u8 8.8 against 8.8 ms,
+// f32 16.5 against 14.5, f64 20.7 against 18.6 -- and removed.  Nothing is waited for at the end: the caller waits before host
+// frames (and the context's tables) may change.  d_mm: [2 n_img] on the device.
+int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                bool on_dev, float* const* dst, unsigned int* d_mm) {
+  const size_t esz = (size_t)pix_bytes(pix);
+  if (!esz) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", pix);
+  if (!raw || !kern || !dst || n_img <= 0 || M <= 0 || N <= 0 || kh <= 0 || kw <= 0)
+    return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
+  if (!conv_fits_lds(kh, kw))
+    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw, conv_lds_bytes(kh, kw),
+                CONV_LDS_MAX);
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
+  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = (size_t)kh * kw;
+  const StagePlan sp = on_dev ? StagePlan{0, 0, 0, 0} : stage_plan(n_img, img_bytes);
+  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)sp.slots * sp.slot_bytes);
+  if (rc) return rc;
+  // one block, the same on both sides: source pointers | destination pointers | taps | reset values of the (min, max) slots
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_wf = 2 * o_dst, o_mm = o_wf + sizeof(double) * nt;
+  const size_t tab_bytes = o_mm + sizeof(unsigned int) * 2 * (size_t)n_img;
+  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
+  if (rc) return rc;
+  c->h_raw_tab.resize(tab_bytes);
+  char* h = c->h_raw_tab.data();
+  const void** h_src = (const void**)h;
+  float** h_dst = (float**)(h + o_dst);
+  unsigned int* h_mm = (unsigned int*)(h + o_mm);
+  for (int k = 0; k < sp.n_chunks; ++k)
+    for (int i = 0; i < stage_count(sp, k, n_img); ++i)
+      h_src[stage_first(sp, k) + i] = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes + (size_t)i * img_bytes;
+  for (int g = 0; g < n_img; ++g) {
+    if (on_dev) h_src[g] = raw[g];
+    h_dst[g] = dst[g];
+    h_mm[2 * g] = 0xFFFFFFFFu;
+    h_mm[2 * g + 1] = 0u;
+  }
+  conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
+  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_img, hipMemcpyDeviceToDevice, c->stream));
+  const void* const* d_src = (const void* const*)c->raw_tab;
+  float* const* d_dst = (float* const*)(c->raw_tab + o_dst);
+  const double* d_wf = (const double*)(c->raw_tab + o_wf);
+  if (on_dev) {
+    HIPCHK(c, launch_conv_batch(c->stream, pix, d_src, 0, n_img, M, N, d_wf, kh, kw, d_dst, d_mm));
+  } else {
+    // plain copies out of the caller's memory, image by image, in stream order behind the convolution that last read the slot
+    for (int k = 0; k < sp.n_chunks; ++k) {
+      const int first = stage_first(sp, k), cnt = stage_count(sp, k, n_img);
+      char* d_slot = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes;
+      for (int i = 0; i < cnt; ++i)
+        HIPCHK(c, hipMemcpyAsync(d_slot + (size_t)i * img_bytes, raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, launch_conv_batch(c->stream, pix, d_src, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm));
+    }
+  }
+  HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_img, px, d_mm));
+  return GPET_OK;
+}
+
+extern "C" {
+
+int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                     unsigned int flags, float* const* out) {
+  if (!c || !raw || !kern || !out || n_img <= 0 || M <= 0 || N <= 0 || kh <= 0 || kw <= 0)
+    return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: bad argument");
+  for (int g = 0; g < n_img; ++g)
+    if (!out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: output image %d is a null pointer", g);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t px = (size_t)M * N;
+  Carver meas;
+  (void)meas.take<float>(px * (size_t)n_img);
+  (void)meas.take<unsigned int>(2 * (size_t)n_img);
+  int rc = ctx_scratch(c, meas.off + 256);
+  if (rc) return rc;
+  Carver cv;
+  cv.base = c->scratch;
+  float* d_out = cv.take<float>(px * (size_t)n_img);
+  unsigned int* d_mm = cv.take<unsigned int>(2 * (size_t)n_img);
+  std::vector<float*> dst((size_t)n_img);
+  for (int g = 0; g < n_img; ++g) dst[(size_t)g] = d_out + (size_t)g * px;
+  rc = conv_frames(c, raw, n_img, pix, M, N, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
+  if (rc == GPET_OK)
+    for (int g = 0; g < n_img; ++g) {
+      hipError_t e = hipMemcpyAsync(out[g], dst[(size_t)g], px * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+      if (e != hipSuccess) {
+        (void)gpet_wait(c->stream);
+        return fail(c, GPET_ERR_HIP, "gpet_grad_images: copy of image %d failed: %s", g, hipGetErrorString(e));
+      }
+    }
+  HIPCHK(c, gpet_wait(c->stream));  // (also after an error: host frames already enqueued must not be read after the return)
+  return rc;
 }
 
 int gpet_normalise_f32(gpet_ctx* c, const float* img, size_t count, float* out) {

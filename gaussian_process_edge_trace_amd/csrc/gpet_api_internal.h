@@ -1,7 +1,10 @@
 // Internals shared by the translation units of the C ABI (include/gpet_hip.h): contexts and batches as the library sees them,
 // the error / wait helpers, and the few host-side helpers more than one unit needs.  Host-side plumbing only: all arithmetic
 // lives in the kernels (gpet_kernels.hip, gpet_eig.hip, gpet_lbfgsb.hip, gpet_rng.hip).
-//   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image), the shared helpers' definitions (waits, errors, lattice)
+//   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image; stacks of raw frames: conv_frames), the shared helpers'
+//                        definitions (waits, errors, lattice)
+//   gpet_conv_plan.h     what a1 decides before a launch, as plain data (no HIP): flipped taps and origin, pixel types, grid and LDS
+//                        bytes, the chunks host frames go up in
 //   gpet_api_batch.hip   batches: creation (a short driver over gpet_batch_plan.h), destruction, images, observations, reset,
 //                        reads / writes
 //   gpet_batch_plan.h    what batch creation decides, as plain data (no HIP): edge parameters -> EdgeDev fields and BatchDims, the
@@ -40,6 +43,11 @@ struct gpet_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   char* scratch = nullptr;  // device scratch of the a1 entry points (gpet_grad_image / gpet_normalise_f32), grown on demand
   size_t scratch_bytes = 0;
+  // raw frames (conv_frames): the device staging of host frames, the device block of pointer tables / taps / slot reset values
+  // with its host copy; grown on demand, freed with the context
+  char *raw_dev = nullptr, *raw_tab = nullptr;
+  size_t raw_dev_bytes = 0, raw_tab_bytes = 0;
+  std::vector<char> h_raw_tab;
   std::string err;
 };
 
@@ -136,6 +144,10 @@ int fail(gpet_ctx* ctx, int code, const char* fmt, ...);
       return fail((ctx), GPET_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 int fin_lattice(const double* x, int n, double* hinv);
+// n_img raw frames (host, or device with on_dev) -> normalised f32 gradient images at the device pointers dst[], enqueued on the
+// context's stream without a final wait; d_mm: device [2 n_img]
+int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                bool on_dev, float* const* dst, unsigned int* d_mm);
 // ---- gpet_api_loop.hip ----------------------------------------------------------------------------------------------------
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
                               int iter_abs, int n_ahead, int z_store);

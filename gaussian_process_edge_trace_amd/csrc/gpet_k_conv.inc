@@ -97,3 +97,79 @@ __global__ void k_normalise_f32(const float* __restrict__ in, size_t count, cons
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// a1, batched: raw frames -> gradient images of a whole batch (gpet_grad_images, gpet_batch_create_raw,
+//     gpet_batch_set_raw_images).  k_conv_relu for image img0 + blockIdx.z of a stack: pixels of type T become f64 on their
+//     way into the LDS patch (exact for u8, u16, f32), then the same taps in the same order, the same clamp, cast and
+//     order-key min/max -- into the image's own (min, max) slot.  The patch load is k_conv_relu's: consecutive lanes read
+//     consecutive pixels of a patch row (64 + kw - 1 of them: one or two cache lines of u8, nine of f64), each image is read
+//     once, and the f64 patch keeps the LDS reads of the tap loop 8 bytes wide whatever T is.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ void k_conv_relu_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
+                                  int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch [CONV_RY + kh - 1][64 + kw - 1]
+  const int g = img0 + blockIdx.z;
+  const T* __restrict__ img = src[g];
+  float* __restrict__ out = dst[g];
+  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
+  for (int i = tid; i < kh * kw; i += nthr) s_w[i] = wf[i];
+  const int pw = 64 + kw - 1, ph = CONV_RY + kh - 1;
+  double* s_p = s_w + kh * kw;
+  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * CONV_RY;
+  for (int e = tid; e < pw * ph; e += nthr) {
+    const int py = e / pw, px = e - py * pw;
+    int ry = y0 + py - oy, rx = x0 + px - ox;
+    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
+    s_p[e] = (double)img[(size_t)ry * N + rx];
+  }
+  __syncthreads();
+  const int x = x0 + threadIdx.x;
+  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
+  for (int yl = threadIdx.y; yl < CONV_RY; yl += blockDim.y) {
+    const int y = y0 + yl;
+    if (x < N && y < M) {
+      double acc = 0.0;
+      for (int a = 0; a < kh; ++a) {
+        const double* row = s_p + (yl + a) * pw + threadIdx.x;
+        for (int b = 0; b < kw; ++b) {
+          const double w = s_w[a * kw + b];
+          if (w == 0.0) continue;
+          acc = acc + row[b] * w;
+        }
+      }
+      if (acc < 0.0) acc = 0.0;
+      const float v = (float)acc;
+      out[(size_t)y * N + x] = v;
+      const unsigned int key = f32_order_key(v);
+      kmin = min(kmin, key);
+      kmax = max(kmax, key);
+    }
+  }
+  // workgroup min/max -> one atomic pair per wave, into the image's slot
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
+    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
+  }
+  if ((tid & 63) == 0) {
+    atomicMin(&minmax[2 * (size_t)g], kmin);
+    atomicMax(&minmax[2 * (size_t)g + 1], kmax);
+  }
+}
+
+// k_normalise_f32 in place for image img0 + blockIdx.y of a stack, with that image's (min, max) slot
+__global__ void k_normalise_f32_batch(float* const* __restrict__ imgs, int img0, size_t count, const unsigned int* minmax) {
+  const int g = img0 + blockIdx.y;
+  float* p = imgs[g];
+  const float mn = f32_from_key(minmax[2 * (size_t)g]);
+  const float mx = f32_from_key(minmax[2 * (size_t)g + 1]);
+  const float span = mx - mn;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+    const float a = p[i] - mn;
+    p[i] = a / span;
+  }
+}
+

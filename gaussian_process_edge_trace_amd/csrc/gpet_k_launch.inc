@@ -28,6 +28,46 @@ hipError_t launch_normalise(hipStream_t st, const float* d_in, size_t count, con
   return hipGetLastError();
 }
 
+// raw frames of a stack -> unnormalised f32 gradient images: images img0 .. img0 + n - 1 of the device pointer tables d_src /
+// d_dst in ONE launch (geometry: gpet_conv_plan.h); d_minmax holds a (min, max) slot per image of the stack
+static_assert(CONV_RY == CONV_TILE_Y && CONV_TILE_X == 64, "k_conv_relu_batch tiles as gpet_conv_plan.h says");
+template <typename T>
+static hipError_t launch_conv_batch_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+                                      int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
+  const ConvGrid cg = conv_grid(M, N);
+  hipLaunchKernelGGL(k_conv_relu_batch<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_lds_bytes(kh, kw), st, (const T* const*)d_src, img0,
+                     M, N, d_wf, kh, kw, conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
+  return hipGetLastError();
+}
+// (a grid holds 65 535 images along z or y: a longer stack takes more than one launch)
+hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+                             int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (!conv_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    hipError_t e = hipSuccess;
+    switch (pix) {
+      case PIX_U8: e = launch_conv_batch_t<uint8_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      case PIX_U16: e = launch_conv_batch_t<uint16_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      case PIX_F32: e = launch_conv_batch_t<float>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      default: e = launch_conv_batch_t<double>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// the n images of d_imgs normalised in place, each by its own slot of d_minmax, in one launch
+hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (n < 1) return hipErrorInvalidValue;
+  int blocks = (int)((count + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  for (int i = 0; i < n; i += 65535)
+    hipLaunchKernelGGL(k_normalise_f32_batch, dim3(blocks, n - i < 65535 ? n - i : 65535), dim3(256), 0, st, d_imgs, i, count, d_minmax);
+  return hipGetLastError();
+}
+
 // ---- a5 for many training points (generic path): K_*^T rows into V, mean, blocked V = L^-1 K_*^T, std ----
 __global__ void __launch_bounds__(256) k_kstar_build(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.z];

@@ -342,6 +342,69 @@ def results_from_records(rec, return_std):
     return out, stats
 
 
+def _as_list(x):
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
+def _raw_stack(raw_imgs):
+    """(frames, shared): a 2-D array is ONE frame shared by all edges; a list / tuple or a (B, M, N) array one frame per edge."""
+    if isinstance(raw_imgs, (list, tuple)):
+        return list(raw_imgs), False
+    a = np.asarray(raw_imgs)
+    if a.ndim == 2:
+        return [a], True
+    if a.ndim == 3:
+        return list(a), False
+    raise ValueError("raw_imgs must be an (M, N) frame, a (B, M, N) stack or a list of (M, N) frames")
+
+
+def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
+                         raw_dtype=None, grad_kernel=None):
+    """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
+    ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
+    images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
+    shape (``grad_shape``) and, raw ones, their dtype (``raw_dtype``)."""
+    have_grad = grad_imgs is not None or grad_device_ptrs is not None
+    have_raw = raw_imgs is not None or raw_device_ptrs is not None
+    if have_grad and have_raw:
+        raise ValueError("pass gradient images (grad_imgs / grad_device_ptrs) or raw frames (raw_imgs / raw_device_ptrs), not both")
+    if not have_grad and not have_raw:
+        raise ValueError("no images: pass grad_imgs, grad_device_ptrs, raw_imgs or raw_device_ptrs")
+    if grad_imgs is not None and grad_device_ptrs is not None:
+        raise ValueError("grad_imgs and grad_device_ptrs are alternatives")
+    if have_raw:
+        if raw_imgs is not None and raw_device_ptrs is not None:
+            raise ValueError("raw_imgs and raw_device_ptrs are alternatives")
+        if grad_kernel is None:
+            raise ValueError("raw frames need grad_kernel, the kernel comp_grad_img would be called with")
+        if raw_device_ptrs is not None:
+            if grad_shape is None or raw_dtype is None:
+                raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
+            ptrs = _as_list(raw_device_ptrs)
+            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape)
+            share = len(ptrs) == 1
+        else:
+            frames, share = _raw_stack(raw_imgs)
+            raw = _lib.RawFrames(grad_kernel, frames=frames)
+        if not share and len(raw) != n_edges:
+            raise ValueError("%d raw frames for %d edges" % (len(raw), n_edges))
+        return dict(kind="raw", share=share, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
+                    batch=dict(grads=None, raw=raw))
+    if grad_device_ptrs is not None:
+        if grad_shape is None:
+            raise ValueError("grad_device_ptrs need grad_shape = (M, N)")
+        ptrs = _as_list(grad_device_ptrs)
+        share = len(ptrs) == 1
+        assert share or len(ptrs) == n_edges
+        return dict(kind="grad", share=share, shape=tuple(grad_shape), on_device=True,
+                    batch=dict(grads=None, device_ptrs=ptrs, shape=grad_shape))
+    share = not isinstance(grad_imgs, (list, tuple))
+    imgs = [grad_imgs] if share else list(grad_imgs)
+    assert share or len(imgs) == n_edges
+    g32 = [np.ascontiguousarray(g, dtype=np.float32) for g in imgs]
+    return dict(kind="grad", share=share, shape=tuple(g32[0].shape), on_device=False, batch=dict(grads=g32))
+
+
 class GP_Edge_Tracing_Batch(object):
     """B independent edges traced together on one GPU (BASELINE config 4's per-GPU share).
 
@@ -357,22 +420,24 @@ class GP_Edge_Tracing_Batch(object):
     def __init__(self, inits, grad_imgs, seeds, kernel_options=(1, 3, 3), noise_y=1, N_samples=500, score_thresh=1,
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
-                 sample_dtype=None, rng=None):
+                 sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
-        consumed in place instead of ``grad_imgs``."""
-        on_dev = grad_device_ptrs is not None
-        if on_dev:
-            ptrs = list(grad_device_ptrs) if isinstance(grad_device_ptrs, (list, tuple)) else [grad_device_ptrs]
-            share = len(ptrs) == 1
-            shapes = [tuple(grad_shape)] * len(inits)
-        else:
-            share = not isinstance(grad_imgs, (list, tuple))
-            imgs = [grad_imgs] if share else list(grad_imgs)
-            shapes = [np.asarray(imgs[0 if share else e]).shape for e in range(len(inits))]
+        consumed in place instead of ``grad_imgs``.
+        ``raw_imgs`` + ``grad_kernel`` (with ``grad_imgs=None``): the frames themselves -- one (M, N) frame for all edges, or a
+        list / (B, M, N) stack with one per edge; uint8, uint16, float32 and float64 go to the device as they are, other
+        dtypes as float64 -- and the kernel ``comp_grad_img`` would be called with: the gradient images are made on the
+        device, all frames in one pass, and the batch equals the one built from ``comp_grad_img``'s outputs bit for bit.
+        ``raw_device_ptrs`` + ``raw_dtype`` + ``grad_shape``: the same for frames already on this GPU.  The kernel is
+        remembered for ``set_frame``."""
         B = len(inits)
-        assert len(seeds) == B and (share or (len(ptrs) if on_dev else len(imgs)) == B)
+        src = resolve_image_source(B, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel)
+        self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
+        self._raw_dtype = raw_dtype
+        share = src["share"]
+        shapes = [src["shape"]] * B
+        assert len(seeds) == B
         obs = [np.array([])] * B if obs is None else list(obs)
         inits = list(inits)  # (an ndarray of shape (B, n, 2) makes a fresh view per access: materialise the items once)
         # (edges with the same init points, observations and image shape resolve to the same parameters but for the seed, which
@@ -400,12 +465,8 @@ class GP_Edge_Tracing_Batch(object):
             self._ps.append(pe)
             abi.append(hit[1])
         self._ctx = _ctx if _ctx is not None else _lib.Context(device, stream)
-        if on_dev:
-            self._batch = _lib.Batch(self._ctx, None, abi, [p["init"] for p in self._ps], share_image=share,
-                                     device_ptrs=ptrs, shape=grad_shape)
-        else:
-            g32 = [np.ascontiguousarray(g, dtype=np.float32) for g in imgs]
-            self._batch = _lib.Batch(self._ctx, g32, abi, [p["init"] for p in self._ps], share_image=share)
+        kw = dict(src["batch"])
+        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, **kw)
         if sample_dtype is not None:
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
@@ -427,15 +488,29 @@ class GP_Edge_Tracing_Batch(object):
         self._batch.reset()
         self._set_obs()
 
-    def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True):
+    def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
+                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
         what depends only on them (arena, streams, the prior eigenbasis of the structured loop path) is reused.
         ``next_frame`` (default): the images continue the sequences just traced, so the any-rank (Matern) factor of the
         new trace's first iteration may start from the last trace's rows -- an iterative solve, the same rows to its
-        tolerance.  ``next_frame=False``: unrelated images; the trace is what a fresh object would compute, bit for bit."""
-        if grad_device_ptrs is not None:
+        tolerance.  ``next_frame=False``: unrelated images; the trace is what a fresh object would compute, bit for bit.
+        ``raw_imgs`` / ``raw_device_ptrs``: the frames themselves, as in the constructor; ``grad_kernel`` and ``raw_dtype``
+        default to the constructor's."""
+        if raw_imgs is not None or raw_device_ptrs is not None:
+            kern = self._grad_kernel if grad_kernel is None else grad_kernel
+            b = self._batch
+            n_img = 1 if b.share_image else self.B
+            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (b.M, b.N), raw_imgs, raw_device_ptrs,
+                                       self._raw_dtype if raw_dtype is None else raw_dtype, kern)
+            # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
+            if len(src["batch"]["raw"]) != n_img or src["shape"] != (b.M, b.N):
+                raise ValueError("the new frames do not fit the batch (%s, %d x %d)"
+                                 % ("one shared image" if b.share_image else "one image per edge", b.M, b.N))
+            b.set_images(raw=src["batch"]["raw"], next_frame=next_frame)
+        elif grad_device_ptrs is not None:
             self._batch.set_images(device_ptrs=list(grad_device_ptrs) if isinstance(grad_device_ptrs, (list, tuple))
                                    else [grad_device_ptrs], next_frame=next_frame)
         else:

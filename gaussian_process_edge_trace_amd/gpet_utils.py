@@ -1,6 +1,6 @@
 """Mirror of ``gp_edge_tracing/gpet_utils.py`` for the parts on (or feeding) the hot path.
 
-``comp_grad_img`` / ``normalise`` run on the GPU through libgpet_hip.so (a1); ``kernel_builder``
+``comp_grad_img`` / ``comp_grad_imgs`` / ``normalise`` run on the GPU through libgpet_hip.so (a1); ``kernel_builder``
 is host-side setup (a 11x5 table).  ``construct_test_img`` is this package's own generator of the
 reference's synthetic test image recipe (gpet_utils.py:163-253).  Called like the reference (no ``seed``) it returns the
 reference's own image bit for bit: scikit-image 0.18's ``random_noise(..., seed=1)`` (gpet_utils.py:251) is
@@ -59,6 +59,14 @@ def comp_grad_img(img, kernel, norm=True, astyp=np.float32, ctx=None):
     ``if normalise:`` tests the function object, gpet_utils.py:114)."""
     out = (ctx or _ctx()).grad_image(np.asarray(img, dtype=np.float64), np.asarray(kernel, dtype=np.float64))
     return out.astype(astyp)
+
+
+def comp_grad_imgs(imgs, kernel, ctx=None):
+    """``comp_grad_img`` of every frame of a stack in ONE batched GPU pass (gpet_grad_images): ``imgs`` is a (T, M, N) array
+    or a sequence of (M, N) frames, the result a (T, M, N) float32 array whose frame t equals ``comp_grad_img(imgs[t],
+    kernel)`` bit for bit.  uint8, uint16, float32 and float64 frames go to the device as they are (integer pixels mean their
+    exact float64 values); any other dtype is converted to float64 first, as ``comp_grad_img`` does with every image."""
+    return (ctx or _ctx()).grad_images(_lib.RawFrames(kernel, frames=imgs))
 
 
 def construct_test_img(size, amplitude, curvature, noise_level, ltype, intensity, gaps=False, seed=None):

@@ -48,17 +48,21 @@ def warm_start_obs(edge_trace, x_st, x_en, warm_every, algo_thresh, M=None):
 class SequenceTracer(object):
     """Traces ``init`` through ``frames`` (T gradient images of one shape) in ``n_chains`` chains on one GPU.
 
-    ``frames``: sequence of (M, N) gradient images; ``seeds``: one seed per frame (default: ``seed`` for all, like a
+    ``frames``: sequence of (M, N) gradient images -- or, with ``grad_kernel=K``, of raw frames (uint8, uint16, float32,
+    float64 as they are, see ``GP_Edge_Tracing_Batch``) whose gradient images ``comp_grad_img(frame, K)`` are made on the
+    device, every step's frames in one pass, at construction and through ``set_frame`` alike; ``seeds``: one seed per frame (default: ``seed`` for all, like a
     user re-creating ``GP_Edge_Tracing(..., seed=seed)`` per frame).  Remaining keyword arguments are the reference
     constructor's (gpet.py:22-35).  ``__call__`` returns the list of T results in frame order, each what
     ``GP_Edge_Tracing.__call__`` returns for that frame (trace, or (trace, credible interval) with ``return_std``)."""
 
-    def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, **kw):
+    def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
+                 **kw):
         self.frames = frames
         self.T = len(frames)
         self.init = np.asarray(init)
         self.kw = dict(kw)
         self.kw.pop("obs", None)
+        self.grad_kernel = grad_kernel
         self.chains = chain_slices(self.T, n_chains)
         self.seeds = [int(seed)] * self.T if seeds is None else [int(v) for v in seeds]
         p = resolve_params(self.init, np.asarray(frames[0]).shape, **{k: v for k, v in self.kw.items()
@@ -93,12 +97,16 @@ class SequenceTracer(object):
                 # streams and events are released now, not whenever the garbage collector gets to them)
                 if self._tracer is not None:
                     self._tracer._batch.close()
-                self._tracer = GP_Edge_Tracing_Batch([self.init] * len(active), imgs, seeds, obs=obs, device=self.device,
-                                                     _ctx=self._ctx, **self.kw)
+                images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
+                                                                                     grad_kernel=self.grad_kernel)
+                self._tracer = GP_Edge_Tracing_Batch([self.init] * len(active), seeds=seeds, obs=obs, device=self.device,
+                                                     _ctx=self._ctx, **images, **self.kw)
                 if self._ctx is None:
                     self._ctx = self._tracer._ctx
-            else:
+            elif self.grad_kernel is None:
                 self._tracer.set_frame(imgs, obs, seeds)
+            else:
+                self._tracer.set_frame(None, obs, seeds, raw_imgs=imgs)
             out = self._tracer(max_iter)
             iters = self._tracer.timings["iters"]
             for k, (c, f) in enumerate(active):

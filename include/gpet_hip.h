@@ -156,6 +156,22 @@ int gpet_timer_stop_ms(gpet_ctx* ctx, float* ms);
  * clamp-to-edge padding, negatives -> 0, float32 min-max normalisation. */
 int gpet_grad_image(gpet_ctx* ctx, const double* img, int M, int N, const double* kern, int kh, int kw,
                     float* out);
+/* Raw frames in the pixel type the caller has them in; every type converts to float64 exactly, so a frame means what
+ * np.asarray(frame, dtype=np.float64) means to gpet_utils.comp_grad_img (gpet_utils.py:95-119). */
+#define GPET_PIX_U8 0
+#define GPET_PIX_U16 1
+#define GPET_PIX_F32 2
+#define GPET_PIX_F64 3
+/* raw[] are DEVICE pointers on the context's device (a decoded video frame, a tensor an RCCL broadcast filled): read where
+ * they lie, no staging and no copy.  Without the flag raw[] are host pointers; the frames go up in chunks of whole images
+ * through a small staging ring the context owns. */
+#define GPET_RAW_ON_DEVICE 4u
+/* gpet_utils.comp_grad_img (gpet_utils.py:95-119) for n_img frames [M*N] of pixel type pix (GPET_PIX_*) in one batched
+ * pass: out[g] f32 [M*N] (host) is bit for bit what gpet_grad_image gives for frame g.  The number of kernel launches does
+ * not depend on n_img (one convolution per staging chunk, one normalisation).  flags: GPET_RAW_ON_DEVICE.
+ * GPET_ERR_BAD_ARG for an unknown pix, a null frame, or a kernel whose patch exceeds 64 KB of LDS. */
+int gpet_grad_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh,
+                     int kw, unsigned int flags, float* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
@@ -171,6 +187,15 @@ int gpet_batch_create(gpet_ctx* ctx, int B, int M, int N, const float* const* gr
 #define GPET_GRAD_ON_DEVICE 1u
 int gpet_batch_create2(gpet_ctx* ctx, int B, int M, int N, const float* const* grad, int share_image,
                        const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
+/* gpet_batch_create2 with the images given as raw frames and the kh x kw kernel (f64, host) of gpet_utils.comp_grad_img:
+ * what a caller of the reference writes as GP_Edge_Tracing(init, comp_grad_img(frame, kern), ...) (gpet_utils.py:95-119,
+ * then gpet.py:97,127).  raw: B pointers (one if share_image) to frames [M*N] of pixel type pix, host memory or, with
+ * GPET_RAW_ON_DEVICE, device memory.  The gradient images are made on the device, all frames in one pass, straight into
+ * the batch's buffers; the batch equals, bit for bit, the one gpet_batch_create2 builds from gpet_grad_image's outputs.
+ * GPET_ERR_BAD_ARG as for gpet_grad_images. */
+int gpet_batch_create_raw(gpet_ctx* ctx, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh,
+                          int kw, int share_image, const gpet_params* params, const int64_t* const* init_xy,
+                          unsigned int flags, gpet_batch** out);
 void gpet_batch_destroy(gpet_batch* b);
 int gpet_batch_size(const gpet_batch* b);
 /* out[0..count): Lg, S, n_keep, n_cap, factor_cap, z_cols, factor_rows_cap, n_bins, obs_cap, algo_thresh,
@@ -194,6 +219,11 @@ int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int 
  * flag -- and after gpet_batch_reset / gpet_batch_set_obs always -- nothing of an earlier trace is used: a trace depends
  * on (image, seed, observations) only, like the reference's single-use object. */
 #define GPET_IMAGES_NEXT_FRAME 2u
+/* gpet_batch_set_images with raw frames (gpet_utils.py:95-119 for every frame, then gpet.py:97,127; the next frame of a
+ * sequence, gpet.py:57-61): raw, pix, kern as in gpet_batch_create_raw; flags: GPET_RAW_ON_DEVICE, GPET_IMAGES_NEXT_FRAME.
+ * A call refused with GPET_ERR_BAD_ARG (unknown pix, null frame, oversized kernel) leaves the batch as it was. */
+int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                              unsigned int flags);
 
 /* set / get the observation set (xy int64) of edge e (gpet.py:100,820,857). */
 int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs);
