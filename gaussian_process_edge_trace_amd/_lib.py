@@ -31,6 +31,90 @@ PIX_OF_DTYPE = {np.dtype(np.uint8): PIX_U8, np.dtype(np.uint16): PIX_U16, np.dty
                 np.dtype(np.float64): PIX_F64}
 
 
+# denoising techniques / boundary modes of gpet_denoise (GPET_DN_*, GPET_DN_MODE_*)
+DN_NONE, DN_MEDIAN, DN_MINIMUM, DN_GAUSSIAN, DN_TVC = range(5)
+DN_OF_TECHNIQUE = {"median": DN_MEDIAN, "minimum": DN_MINIMUM, "gaussian": DN_GAUSSIAN, "tvc": DN_TVC}
+DN_NOT_BUILT = ("nl", "wavelet", "tvb")  # techniques of the reference's denoise() that are not stencils the device runs
+DN_MODE_OF_NAME = {"reflect": 0, "nearest": 1}
+DN_WINDOW_MAX = 81
+
+
+class GpetDenoise(C.Structure):
+    _fields_ = [("technique", C.c_int32), ("size_y", C.c_int32), ("size_x", C.c_int32), ("mode", C.c_int32),
+                ("sigma_y", C.c_double), ("sigma_x", C.c_double), ("truncate", C.c_double), ("weight", C.c_double),
+                ("eps", C.c_double), ("n_iter_max", C.c_int32)]
+
+
+def _dn_pair(v, conv, name):
+    if np.ndim(v) == 0:
+        return conv(v), conv(v)
+    v = list(v)
+    if len(v) != 2:
+        raise ValueError("denoise: %r must be a scalar or one value per image axis, not %r" % (name, v))
+    return conv(v[0]), conv(v[1])
+
+
+def denoise_spec(denoise):
+    """``(technique, kwargs)`` as gpet_utils.denoise takes them -> GpetDenoise, decided from the arguments alone (no device).
+    kwargs carry scipy's / scikit-image's own names: ``size`` and ``mode`` for 'median' / 'minimum'; ``sigma``, ``truncate``,
+    ``order`` (0 only) and ``mode`` for 'gaussian'; ``weight``, ``eps`` and ``n_iter_max`` for 'tvc'.  ValueError names a key
+    the device does not take (footprint, origin, cval, multichannel, ...) or a value it refuses; NotImplementedError names a
+    technique of the reference that is not built ('nl', 'wavelet', 'tvb').  A GpetDenoise passes through; None stays None."""
+    if denoise is None or isinstance(denoise, GpetDenoise):
+        return denoise
+    try:
+        technique, kwargs = denoise
+    except (TypeError, ValueError):
+        raise ValueError("denoise must be a (technique, kwargs) pair")
+    if technique in DN_NOT_BUILT:
+        raise NotImplementedError("denoising technique %r is not built for the device (built: %s)"
+                                  % (technique, ", ".join(sorted(DN_OF_TECHNIQUE))))
+    if technique not in DN_OF_TECHNIQUE:
+        raise ValueError("unknown denoising technique %r" % (technique,))
+    kw = dict(kwargs or {})
+    allowed = {"median": ("size", "mode"), "minimum": ("size", "mode"), "gaussian": ("sigma", "truncate", "order", "mode"),
+               "tvc": ("weight", "eps", "n_iter_max")}[technique]
+    for k in kw:
+        if k not in allowed:
+            raise ValueError("denoise: keyword %r of %r is not supported on the device (supported: %s)"
+                             % (k, technique, ", ".join(allowed)))
+    d = GpetDenoise(technique=DN_OF_TECHNIQUE[technique], size_y=0, size_x=0, mode=0, sigma_y=0.0, sigma_x=0.0, truncate=4.0,
+                    weight=0.1, eps=2.0e-4, n_iter_max=200)
+    if "mode" in kw:
+        if kw["mode"] not in DN_MODE_OF_NAME:
+            raise ValueError("denoise: mode %r is not supported on the device (supported: reflect, nearest)" % (kw["mode"],))
+        d.mode = DN_MODE_OF_NAME[kw["mode"]]
+    if technique in ("median", "minimum"):
+        if "size" not in kw:
+            raise ValueError("denoise: %r needs size" % (technique,))
+        d.size_y, d.size_x = _dn_pair(kw["size"], int, "size")
+        if d.size_y < 1 or d.size_x < 1 or d.size_y * d.size_x > DN_WINDOW_MAX:
+            raise ValueError("denoise: size %r: windows of 1 to %d pixels (9 x 9) are built" % (kw["size"], DN_WINDOW_MAX))
+    elif technique == "gaussian":
+        if "sigma" not in kw:
+            raise ValueError("denoise: 'gaussian' needs sigma")
+        if np.ndim(kw.get("order", 0)) != 0 or kw.get("order", 0) != 0:
+            raise ValueError("denoise: order %r is not supported on the device (0 only)" % (kw["order"],))
+        d.sigma_y, d.sigma_x = _dn_pair(kw["sigma"], float, "sigma")
+        d.truncate = float(kw.get("truncate", 4.0))
+        if not (d.sigma_y > 0 and d.sigma_x > 0 and d.truncate > 0):
+            raise ValueError("denoise: sigma and truncate must be above 0")
+    else:
+        d.weight = float(kw.get("weight", 0.1))
+        d.eps = float(kw.get("eps", 2.0e-4))
+        d.n_iter_max = int(kw.get("n_iter_max", 200))
+        if not d.weight > 0 or not d.eps >= 0 or d.n_iter_max < 1:
+            raise ValueError("denoise: weight must be above 0, eps not negative, n_iter_max at least 1")
+    return d
+
+
+def denoised_dtype(dn, pix):
+    """numpy dtype of a denoised frame of pixel type ``pix``: the frame's own for the filters, float64 for 'tvc'."""
+    if dn.technique == DN_TVC:
+        return np.dtype(np.float64)
+    return [dt for dt, code in PIX_OF_DTYPE.items() if code == pix][0]
+
+
 class GpetParams(C.Structure):
     _fields_ = [("kernel_type", C.c_int32), ("nu", C.c_double), ("sigma_f", C.c_double),
                 ("length_scale", C.c_double), ("noise_y", C.c_double), ("n_samples", C.c_int32),
@@ -102,13 +186,18 @@ def native_frames(imgs):
 class RawFrames(object):
     """The ``raw=`` argument of Batch / Batch.set_images: frames plus the kernel that makes gradient images of them.
     Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
-    ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all."""
+    ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all.
+    ``denoise``: optionally how the frames are denoised on the device before the kernel is applied, a ``(technique, kwargs)``
+    pair of gpet_utils.denoise (see denoise_spec).  ``kernel=None``: frames to denoise only (Context.denoise_images)."""
 
-    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None):
+    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
-        self.kernel = np.ascontiguousarray(kernel, dtype=np.float64)
-        if self.kernel.ndim != 2 or self.kernel.size == 0:
+        self.dn = denoise_spec(denoise)
+        self.kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
+        if kernel is None and self.dn is None:
+            raise ValueError("raw frames need a gradient kernel or a denoising technique")
+        if self.kernel is not None and (self.kernel.ndim != 2 or self.kernel.size == 0):
             raise ValueError("the gradient kernel must be a non-empty 2-D array")
         if device_ptrs is not None:
             if dtype is None or shape is None:
@@ -130,6 +219,9 @@ class RawFrames(object):
 
     def kernel_args(self):
         return self.kernel.ctypes.data, self.kernel.shape[0], self.kernel.shape[1]
+
+    def dn_arg(self):
+        return C.byref(self.dn)
 
 
 class GpetError(RuntimeError):
@@ -157,6 +249,10 @@ SYMBOLS = {
     "gpet_grad_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "gpet_grad_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_uint,
                                    C.POINTER(_P)]),
+    "gpet_denoise_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint,
+                                      C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "gpet_grad_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
+                                      C.POINTER(GpetDenoise), C.c_uint, C.POINTER(_P)]),
     "gpet_normalise_f32": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "gpet_batch_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int,
                                     C.POINTER(GpetParams), C.POINTER(_P), C.POINTER(_P)]),
@@ -164,7 +260,11 @@ SYMBOLS = {
                                      C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
     "gpet_batch_create_raw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_create_raw_dn": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int,
+                                           C.POINTER(GpetDenoise), C.c_int, C.POINTER(GpetParams), C.POINTER(_P), C.c_uint,
+                                           C.POINTER(_P)]),
     "gpet_batch_set_images": (C.c_int, [_P, C.POINTER(_P), C.c_uint]),
+    "gpet_batch_set_raw_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint]),
     "gpet_batch_set_raw_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_uint]),
     "gpet_batch_destroy": (None, [_P]),
     "gpet_batch_size": (C.c_int, [_P]),
@@ -335,8 +435,25 @@ class Context:
         out = np.empty((len(raw), M, N), dtype=np.float32)
         op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
         kp, kh, kw = raw.kernel_args()
+        if raw.dn is not None:
+            self.check(self.lib.gpet_grad_images_dn(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, raw.dn_arg(),
+                                                    raw.flags, op))
+            return out
         self.check(self.lib.gpet_grad_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, raw.flags, op))
         return out
+
+    def denoise_images(self, raw):
+        """gpet_denoise_images: every frame of ``raw`` (a RawFrames with a denoising technique) denoised in one batched pass ->
+        ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters)."""
+        if raw.dn is None:
+            raise ValueError("no denoising technique")
+        M, N = raw.shape
+        out = np.empty((len(raw), M, N), dtype=denoised_dtype(raw.dn, raw.pix))
+        op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
+        n_iter = np.zeros(len(raw), dtype=np.int32)
+        self.check(self.lib.gpet_denoise_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.dn_arg(), raw.flags, op,
+                                                n_iter.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, n_iter
 
     def normalise_f32(self, img):
         a = np.ascontiguousarray(img, dtype=np.float32)
@@ -512,8 +629,12 @@ class Batch:
         if raw is not None:
             assert len(raw) == (1 if share_image else B)
             kp, kh, kw = raw.kernel_args()
-            ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
-                                                     1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
+            if raw.dn is not None:
+                ctx.check(self.lib.gpet_batch_create_raw_dn(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
+                                                            raw.dn_arg(), 1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
+            else:
+                ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
+                                                         1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
         else:
             ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags,
                                                   C.byref(h)))
@@ -542,6 +663,10 @@ class Batch:
                 raise ValueError("gradient images and raw frames are alternatives")
             assert len(raw) == n_img and tuple(raw.shape) == (self.M, self.N)
             kp, kh, kw = raw.kernel_args()
+            if raw.dn is not None:
+                self.ctx.check(self.lib.gpet_batch_set_raw_images_dn(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.dn_arg(),
+                                                                     raw.flags | nf))
+                return
             self.ctx.check(self.lib.gpet_batch_set_raw_images(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.flags | nf))
             return
         if device_ptrs is not None:

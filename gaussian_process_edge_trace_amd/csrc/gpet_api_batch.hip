@@ -53,6 +53,7 @@ struct ImageSource {
   int pix = 0;
   const double* kern = nullptr;        // the kh x kw kernel of gpet_utils.comp_grad_img
   int kh = 0, kw = 0;
+  const DenoiseSpec* dn = nullptr;     // and, optionally, how the frames are denoised first (gpet_denoise_plan.h)
   unsigned int flags = 0;              // GPET_GRAD_ON_DEVICE / GPET_RAW_ON_DEVICE (and GPET_IMAGES_NEXT_FRAME, not read here)
 };
 
@@ -64,7 +65,7 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
   const int n_img = b->share_image ? 1 : b->B;
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[g].grad;
-  const int rc = conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.kern, s.kh, s.kw, (s.flags & GPET_RAW_ON_DEVICE) != 0,
+  const int rc = conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, (s.flags & GPET_RAW_ON_DEVICE) != 0,
                              dst.data(), b->d_minmax);
   if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
   return rc;
@@ -79,6 +80,8 @@ static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img) {
   if (!conv_fits_lds(s.kh, s.kw))
     return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", s.kh, s.kw,
                 conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
+  if (s.dn)
+    if (const char* why = dn_check(*s.dn, s.pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
   for (int g = 0; g < n_img; ++g)
     if (!s.raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
   return GPET_OK;
@@ -247,18 +250,26 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
 }
 
-int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
-                          int share_image, const gpet_params* params, const int64_t* const* init_xy, unsigned int flags,
-                          gpet_batch** out) {
-  if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw: bad argument");
+int gpet_batch_create_raw_dn(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                             const gpet_denoise* dn, int share_image, const gpet_params* params, const int64_t* const* init_xy,
+                             unsigned int flags, gpet_batch** out) {
+  if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_dn: bad argument");
+  const DenoiseSpec spec = dn_spec(dn);
   ImageSource src;
   src.raw = raw;
   src.pix = pix;
   src.kern = kern;
   src.kh = kh;
   src.kw = kw;
+  src.dn = dn ? &spec : nullptr;
   src.flags = flags;
   return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
+}
+
+int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                          int share_image, const gpet_params* params, const int64_t* const* init_xy, unsigned int flags,
+                          gpet_batch** out) {
+  return gpet_batch_create_raw_dn(c, B, M, N, raw, pix, kern, kh, kw, nullptr, share_image, params, init_xy, flags, out);
 }
 
 void gpet_batch_destroy(gpet_batch* b) {
@@ -701,20 +712,28 @@ int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int 
   return batch_set_images_from(b, src);
 }
 
-// (a refused call -- unknown pixel type, null frame, oversized kernel -- has touched nothing: the batch traces on as it was)
-int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw, unsigned int flags) {
+// (a refused call -- unknown pixel type, null frame, oversized kernel, a denoising spec that cannot run -- has touched nothing:
+//  the batch traces on as it was)
+int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                                 const gpet_denoise* dn, unsigned int flags) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
+  const DenoiseSpec spec = dn_spec(dn);
   ImageSource src;
   src.raw = raw;
   src.pix = pix;
   src.kern = kern;
   src.kh = kh;
   src.kw = kw;
+  src.dn = dn ? &spec : nullptr;
   src.flags = flags;
   const int rc = check_raw_source(b->ctx, src, b->share_image ? 1 : b->B);
   if (rc) return rc;
   return batch_set_images_from(b, src);
+}
+
+int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw, unsigned int flags) {
+  return gpet_batch_set_raw_images_dn(b, raw, pix, kern, kh, kw, nullptr, flags);
 }
 
 }  // extern "C"

@@ -224,6 +224,10 @@ int gpet_grad_image(gpet_ctx* c, const double* img, int M, int N, const double* 
 // ---- a1 for stacks of raw frames ------------------------------------------------------
 }  // extern "C"
 
+static_assert(DN_NONE == GPET_DN_NONE && DN_MEDIAN == GPET_DN_MEDIAN && DN_MINIMUM == GPET_DN_MINIMUM && DN_GAUSSIAN == GPET_DN_GAUSSIAN &&
+                  DN_TVC == GPET_DN_TVC && DN_MODE_REFLECT == GPET_DN_MODE_REFLECT && DN_MODE_NEAREST == GPET_DN_MODE_NEAREST,
+              "gpet_denoise_plan.h numbers techniques and modes as include/gpet_hip.h does");
+
 // (device memory of the context that only grows; the stream is idle when it is replaced)
 static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
   if (bytes <= *cap) return GPET_OK;
@@ -243,24 +247,42 @@ static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
 // packs chunk k + 1 while the device works on chunk k, was built and measured -- 256 frames of 500 x 500: u8 8.8 against 8.8 ms,
 // f32 16.5 against 14.5, f64 20.7 against 18.6 -- and removed.  Nothing is waited for at the end: the caller waits before host
 // frames (and the context's tables) may change.  d_mm: [2 n_img] on the device.
-int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                bool on_dev, float* const* dst, unsigned int* d_mm) {
+// With a denoising spec (dn, technique not NONE: gpet_denoise_plan.h) every chunk is denoised where it was staged before it is
+// convolved: the chunk's workspace follows its frames in the staging slot, the convolution reads the denoised frames in the pixel
+// type the technique leaves behind, and frames on the device go through chunks of the same budget too.  'tvc' iterates a chunk to
+// its end -- groups of DN_TVC_GROUP iterations, the count of finished images read between groups -- before the next is staged.
+// kern == nullptr: no convolution (gpet_denoise_images); dn_out: host buffers the denoised frames are copied to, n_iter_out: host
+// [n_img] iterations per image.
+int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
+                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out) {
   const size_t esz = (size_t)pix_bytes(pix);
+  const bool dn_on = dn && dn->technique != DN_NONE;
   if (!esz) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", pix);
-  if (!raw || !kern || !dst || n_img <= 0 || M <= 0 || N <= 0 || kh <= 0 || kw <= 0)
+  if (!raw || n_img <= 0 || M <= 0 || N <= 0 || (!kern && !dn_on) || (kern && (!dst || kh <= 0 || kw <= 0)))
     return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
-  if (!conv_fits_lds(kh, kw))
+  if (kern && !conv_fits_lds(kh, kw))
     return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw, conv_lds_bytes(kh, kw),
                 CONV_LDS_MAX);
+  if (dn)
+    if (const char* why = dn_check(*dn, pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
   for (int g = 0; g < n_img; ++g)
     if (!raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
-  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = (size_t)kh * kw;
-  const StagePlan sp = on_dev ? StagePlan{0, 0, 0, 0} : stage_plan(n_img, img_bytes);
+  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = kern ? (size_t)kh * kw : 0;
+  const DenoiseLayout L = dn_layout(dn_on ? dn->technique : DN_NONE, pix, M, N);
+  const int cpix = dn_on ? dn_out_pix(dn->technique, pix) : pix;  // what the convolution reads
+  const size_t stage_img = dn_stage_bytes(img_bytes, on_dev, L);
+  const StagePlan sp = (on_dev && !dn_on) ? StagePlan{0, 0, 0, 0} : dn_stage_plan(n_img, img_bytes, on_dev, L);
+  const size_t o_ws = (size_t)sp.per_chunk * stage_img;  // a chunk's workspace, behind its frames
   int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)sp.slots * sp.slot_bytes);
   if (rc) return rc;
   // one block, the same on both sides: source pointers | destination pointers | taps | reset values of the (min, max) slots
+  // | pointers to the denoised frames | Gaussian taps of the two axes | iterations per image | finished images of the chunk
+  const int ry = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_y, dn->truncate) : 0;
+  const int rx = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_x, dn->truncate) : 0;
   const size_t o_dst = sizeof(void*) * (size_t)n_img, o_wf = 2 * o_dst, o_mm = o_wf + sizeof(double) * nt;
-  const size_t tab_bytes = o_mm + sizeof(unsigned int) * 2 * (size_t)n_img;
+  const size_t o_dn = (o_mm + sizeof(unsigned int) * 2 * (size_t)n_img + 7) & ~(size_t)7;
+  const size_t o_gw = o_dn + (dn_on ? o_dst : 0), o_it = o_gw + (dn_on ? sizeof(double) * (size_t)(2 * ry + 1 + 2 * rx + 1) : 0);
+  const size_t tab_bytes = dn_on ? o_it + sizeof(int) * ((size_t)n_img + 1) : o_mm + sizeof(unsigned int) * 2 * (size_t)n_img;
   rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
   if (rc) return rc;
   c->h_raw_tab.resize(tab_bytes);
@@ -269,40 +291,83 @@ int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, 
   float** h_dst = (float**)(h + o_dst);
   unsigned int* h_mm = (unsigned int*)(h + o_mm);
   for (int k = 0; k < sp.n_chunks; ++k)
-    for (int i = 0; i < stage_count(sp, k, n_img); ++i)
-      h_src[stage_first(sp, k) + i] = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes + (size_t)i * img_bytes;
+    for (int i = 0; i < stage_count(sp, k, n_img); ++i) {
+      char* slot = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes;
+      if (!on_dev) h_src[stage_first(sp, k) + i] = slot + (size_t)i * stage_img;
+      if (dn_on) ((const void**)(h + o_dn))[stage_first(sp, k) + i] = slot + o_ws + (size_t)i * L.img_bytes + L.off_out;
+    }
   for (int g = 0; g < n_img; ++g) {
     if (on_dev) h_src[g] = raw[g];
-    h_dst[g] = dst[g];
+    h_dst[g] = dst ? dst[g] : nullptr;
     h_mm[2 * g] = 0xFFFFFFFFu;
     h_mm[2 * g + 1] = 0u;
   }
-  conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
+  if (kern) conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
+  if (dn_on && dn->technique == DN_GAUSSIAN) {
+    dn_gauss_taps(dn->sigma_y, ry, (double*)(h + o_gw));
+    dn_gauss_taps(dn->sigma_x, rx, (double*)(h + o_gw) + 2 * ry + 1);
+  }
   HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_img, hipMemcpyDeviceToDevice, c->stream));
+  if (kern)
+    HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_img, hipMemcpyDeviceToDevice, c->stream));
   const void* const* d_src = (const void* const*)c->raw_tab;
   float* const* d_dst = (float* const*)(c->raw_tab + o_dst);
   const double* d_wf = (const double*)(c->raw_tab + o_wf);
-  if (on_dev) {
+  const void* const* d_conv_src = dn_on ? (const void* const*)(c->raw_tab + o_dn) : d_src;
+  const double* d_gw = (const double*)(c->raw_tab + o_gw);
+  int* d_it = (int*)(c->raw_tab + o_it);
+  if (on_dev && !dn_on) {
     HIPCHK(c, launch_conv_batch(c->stream, pix, d_src, 0, n_img, M, N, d_wf, kh, kw, d_dst, d_mm));
   } else {
-    // plain copies out of the caller's memory, image by image, in stream order behind the convolution that last read the slot
+    // plain copies out of the caller's memory, image by image, in stream order behind the kernels that last read the slot
     for (int k = 0; k < sp.n_chunks; ++k) {
       const int first = stage_first(sp, k), cnt = stage_count(sp, k, n_img);
       char* d_slot = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes;
-      for (int i = 0; i < cnt; ++i)
-        HIPCHK(c, hipMemcpyAsync(d_slot + (size_t)i * img_bytes, raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, launch_conv_batch(c->stream, pix, d_src, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm));
+      if (!on_dev)
+        for (int i = 0; i < cnt; ++i)
+          HIPCHK(c, hipMemcpyAsync(d_slot + (size_t)i * stage_img, raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream));
+      if (dn_on) {
+        char* ws = d_slot + o_ws;
+        if (dn->technique == DN_GAUSSIAN) {
+          HIPCHK(c, launch_dn_gauss(c->stream, pix, d_src, first, cnt, M, N, *dn, d_gw, d_gw + 2 * ry + 1, ws, L));
+        } else if (dn->technique == DN_TVC) {
+          int* d_done = d_it + n_img;
+          HIPCHK(c, hipMemsetAsync(d_done, 0, sizeof(int), c->stream));
+          for (int issued = 0, done = 0; issued < dn->n_iter_max && done < cnt;) {
+            const int grp = dn->n_iter_max - issued < DN_TVC_GROUP ? dn->n_iter_max - issued : DN_TVC_GROUP;
+            for (int j = 0; j < grp; ++j)
+              HIPCHK(c, launch_dn_tvc_iter(c->stream, pix, d_src, first, cnt, M, N, *dn, issued + j, ws, L, d_it, d_done));
+            issued += grp;
+            if (issued < dn->n_iter_max) {
+              HIPCHK(c, hipMemcpyAsync(&done, d_done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+              HIPCHK(c, gpet_wait(c->stream));
+            }
+          }
+        } else {
+          HIPCHK(c, launch_dn_rank(c->stream, pix, d_src, first, cnt, M, N, *dn, ws, L));
+        }
+        if (dn_out)
+          for (int i = 0; i < cnt; ++i)
+            HIPCHK(c, hipMemcpyAsync(dn_out[first + i], ws + (size_t)i * L.img_bytes + L.off_out, px * (size_t)pix_bytes(cpix),
+                                     hipMemcpyDeviceToHost, c->stream));
+      }
+      if (kern) HIPCHK(c, launch_conv_batch(c->stream, cpix, d_conv_src, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm));
     }
   }
-  HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_img, px, d_mm));
+  if (n_iter_out) {
+    if (dn_on && dn->technique == DN_TVC)
+      HIPCHK(c, hipMemcpyAsync(n_iter_out, d_it, sizeof(int32_t) * (size_t)n_img, hipMemcpyDeviceToHost, c->stream));
+    else
+      for (int g = 0; g < n_img; ++g) n_iter_out[g] = 0;
+  }
+  if (kern) HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_img, px, d_mm));
   return GPET_OK;
 }
 
 extern "C" {
 
-int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                     unsigned int flags, float* const* out) {
+static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                            const DenoiseSpec* dn, unsigned int flags, float* const* out) {
   if (!c || !raw || !kern || !out || n_img <= 0 || M <= 0 || N <= 0 || kh <= 0 || kw <= 0)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: bad argument");
   for (int g = 0; g < n_img; ++g)
@@ -320,7 +385,7 @@ int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, in
   unsigned int* d_mm = cv.take<unsigned int>(2 * (size_t)n_img);
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = d_out + (size_t)g * px;
-  rc = conv_frames(c, raw, n_img, pix, M, N, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
+  rc = conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
   if (rc == GPET_OK)
     for (int g = 0; g < n_img; ++g) {
       hipError_t e = hipMemcpyAsync(out[g], dst[(size_t)g], px * sizeof(float), hipMemcpyDeviceToHost, c->stream);
@@ -329,6 +394,31 @@ int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, in
         return fail(c, GPET_ERR_HIP, "gpet_grad_images: copy of image %d failed: %s", g, hipGetErrorString(e));
       }
     }
+  HIPCHK(c, gpet_wait(c->stream));  // (also after an error: host frames already enqueued must not be read after the return)
+  return rc;
+}
+
+int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                     unsigned int flags, float* const* out) {
+  return grad_images_from(c, raw, n_img, pix, M, N, kern, kh, kw, nullptr, flags, out);
+}
+
+int gpet_grad_images_dn(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
+                        const gpet_denoise* dn, unsigned int flags, float* const* out) {
+  const DenoiseSpec spec = dn_spec(dn);
+  return grad_images_from(c, raw, n_img, pix, M, N, kern, kh, kw, dn ? &spec : nullptr, flags, out);
+}
+
+int gpet_denoise_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_denoise* dn,
+                        unsigned int flags, void* const* out, int32_t* n_iter_out) {
+  if (!c || !raw || !dn || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: bad argument");
+  if (dn->technique == GPET_DN_NONE) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: no technique");
+  for (int g = 0; g < n_img; ++g)
+    if (!out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: output image %d is a null pointer", g);
+  HIPCHK(c, hipSetDevice(c->device));
+  const DenoiseSpec spec = dn_spec(dn);
+  const int rc = conv_frames(c, raw, n_img, pix, M, N, &spec, nullptr, 0, 0, (flags & GPET_RAW_ON_DEVICE) != 0, nullptr, nullptr, out,
+                             n_iter_out);
   HIPCHK(c, gpet_wait(c->stream));  // (also after an error: host frames already enqueued must not be read after the return)
   return rc;
 }

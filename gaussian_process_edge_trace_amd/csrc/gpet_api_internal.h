@@ -5,6 +5,8 @@
 //                        definitions (waits, errors, lattice)
 //   gpet_conv_plan.h     what a1 decides before a launch, as plain data (no HIP): flipped taps and origin, pixel types, grid and LDS
 //                        bytes, the chunks host frames go up in
+//   gpet_denoise_plan.h  what the denoising stage in front of a1 decides (no HIP): spec and validation, window origin and rank, Gaussian
+//                        radius and taps, workspace per image, chunk sizes
 //   gpet_api_batch.hip   batches: creation (a short driver over gpet_batch_plan.h), destruction, images, observations, reset,
 //                        reads / writes
 //   gpet_batch_plan.h    what batch creation decides, as plain data (no HIP): edge parameters -> EdgeDev fields and BatchDims, the
@@ -43,8 +45,8 @@ struct gpet_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   char* scratch = nullptr;  // device scratch of the a1 entry points (gpet_grad_image / gpet_normalise_f32), grown on demand
   size_t scratch_bytes = 0;
-  // raw frames (conv_frames): the device staging of host frames, the device block of pointer tables / taps / slot reset values
-  // with its host copy; grown on demand, freed with the context
+  // raw frames (conv_frames): the device staging of host frames with the denoising workspace of a chunk behind them, the device
+  // block of pointer tables / taps / slot reset values with its host copy; grown on demand, freed with the context
   char *raw_dev = nullptr, *raw_tab = nullptr;
   size_t raw_dev_bytes = 0, raw_tab_bytes = 0;
   std::vector<char> h_raw_tab;
@@ -145,9 +147,27 @@ int fail(gpet_ctx* ctx, int code, const char* fmt, ...);
   } while (0)
 int fin_lattice(const double* x, int n, double* hinv);
 // n_img raw frames (host, or device with on_dev) -> normalised f32 gradient images at the device pointers dst[], enqueued on the
-// context's stream without a final wait; d_mm: device [2 n_img]
-int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                bool on_dev, float* const* dst, unsigned int* d_mm);
+// context's stream without a final wait; d_mm: device [2 n_img].  dn (may be nullptr): the frames are denoised first; kern ==
+// nullptr: denoising alone, into the host buffers dn_out[] (iterations per image: n_iter_out)
+int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
+                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out = nullptr,
+                int32_t* n_iter_out = nullptr);
+// the C ABI's gpet_denoise as the plan takes it (nullptr: no technique)
+static inline DenoiseSpec dn_spec(const gpet_denoise* d) {
+  DenoiseSpec s;
+  if (!d) return s;
+  s.technique = d->technique;
+  s.size_y = d->size_y;
+  s.size_x = d->size_x;
+  s.mode = d->mode;
+  s.sigma_y = d->sigma_y;
+  s.sigma_x = d->sigma_x;
+  s.truncate = d->truncate;
+  s.weight = d->weight;
+  s.eps = d->eps;
+  s.n_iter_max = d->n_iter_max;
+  return s;
+}
 // ---- gpet_api_loop.hip ----------------------------------------------------------------------------------------------------
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
                               int iter_abs, int n_ahead, int z_store);

@@ -68,6 +68,94 @@ hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, s
   return hipGetLastError();
 }
 
+// ---- a0: denoising of a chunk of raw frames (gpet_k_denoise.inc; geometry and workspace: gpet_denoise_plan.h) ----
+static_assert(sizeof(TvcState) == DN_TVC_STATE_BYTES, "the plan reserves k_dn_tvc_check's state");
+static_assert((CONV_RY + 1) * 65 * 2 * sizeof(double) == DN_TVC_LDS_BYTES, "k_dn_tvc_iter tiles as gpet_denoise_plan.h says");
+template <typename T>
+static void launch_dn_rank_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s, char* ws,
+                             const DenoiseLayout& L, int pix) {
+  const ConvGrid cg = conv_grid(M, N);
+  const dim3 gs(cg.gx, cg.gy, n), bs(64, 4);
+  const size_t lds = dn_rank_lds_bytes(s.size_y, s.size_x, pix);
+  const int rank = dn_rank(s.technique, s.size_y, s.size_x);
+  const T* const* src = (const T* const*)d_src;
+  if (s.size_y == 3 && s.size_x == 3)
+    hipLaunchKernelGGL((k_dn_rank<T, 3, 3>), gs, bs, lds, st, src, img0, ws, L.img_bytes, L.off_out, M, N, 3, 3, rank, s.mode);
+  else if (s.size_y == 5 && s.size_x == 5)
+    hipLaunchKernelGGL((k_dn_rank<T, 5, 5>), gs, bs, lds, st, src, img0, ws, L.img_bytes, L.off_out, M, N, 5, 5, rank, s.mode);
+  else
+    hipLaunchKernelGGL((k_dn_rank<T, 0, 0>), gs, bs, lds, st, src, img0, ws, L.img_bytes, L.off_out, M, N, s.size_y, s.size_x, rank, s.mode);
+}
+// (a grid holds 65 535 images along z: a longer chunk takes more than one launch)
+hipError_t launch_dn_rank(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
+                          char* ws, const DenoiseLayout& L) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (dn_check(s, pix) || (s.technique != DN_MEDIAN && s.technique != DN_MINIMUM) || n < 1) return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    char* w = ws + (size_t)i * L.img_bytes;
+    switch (pix) {
+      case PIX_U8: launch_dn_rank_t<uint8_t>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
+      case PIX_U16: launch_dn_rank_t<uint16_t>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
+      case PIX_F32: launch_dn_rank_t<float>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
+      default: launch_dn_rank_t<double>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
+    }
+  }
+  return hipGetLastError();
+}
+template <typename T>
+static void launch_dn_gauss_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
+                              const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {
+  const dim3 gs(cdiv(N, 64), cdiv(M, 4), n), bs(64, 4);
+  // axis 0 first: frame -> tmp, then axis 1: tmp -> out, each stored in the frame's type as scipy stores it
+  hipLaunchKernelGGL(k_dn_gauss_pass<T>, gs, bs, 0, st, (const T* const*)d_src, img0, ws, L.img_bytes, (size_t)0, L.off_tmp, M, N, 0, d_wy,
+                     dn_gauss_radius(s.sigma_y, s.truncate), s.mode);
+  hipLaunchKernelGGL(k_dn_gauss_pass<T>, gs, bs, 0, st, (const T* const*)nullptr, img0, ws, L.img_bytes, L.off_tmp, L.off_out, M, N, 1, d_wx,
+                     dn_gauss_radius(s.sigma_x, s.truncate), s.mode);
+}
+hipError_t launch_dn_gauss(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
+                           const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (dn_check(s, pix) || s.technique != DN_GAUSSIAN || n < 1 || cdiv(M, 4) > 65535) return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    char* w = ws + (size_t)i * L.img_bytes;
+    switch (pix) {
+      case PIX_U8: launch_dn_gauss_t<uint8_t>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
+      case PIX_U16: launch_dn_gauss_t<uint16_t>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
+      case PIX_F32: launch_dn_gauss_t<float>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
+      default: launch_dn_gauss_t<double>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
+    }
+  }
+  return hipGetLastError();
+}
+template <typename T>
+static void launch_dn_tvc_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, int it, double tau_w, char* ws,
+                            const DenoiseLayout& L) {
+  const ConvGrid cg = conv_grid(M, N);
+  hipLaunchKernelGGL(k_dn_tvc_iter<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), 0, st, (const T* const*)d_src, img0, ws, L.img_bytes, L.off_out,
+                     L.off_p, L.plane_bytes, L.off_part, M, N, it, tau_w);
+}
+hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
+                              int it, char* ws, const DenoiseLayout& L, int* d_n_iter, int* d_n_done) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (dn_check(s, pix) || s.technique != DN_TVC || n < 1 || it < 0) return hipErrorInvalidValue;
+  const double tau_w = 0.25 / s.weight;  // (the reference's `tau / weight`, formed once)
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    char* w = ws + (size_t)i * L.img_bytes;
+    switch (pix) {
+      case PIX_U8: launch_dn_tvc_t<uint8_t>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
+      case PIX_U16: launch_dn_tvc_t<uint16_t>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
+      case PIX_F32: launch_dn_tvc_t<float>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
+      default: launch_dn_tvc_t<double>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
+    }
+  }
+  hipLaunchKernelGGL(k_dn_tvc_check, dim3(n), dim3(256), 0, st, ws, L.img_bytes, L.off_part, L.n_wg, img0, it, s.weight, s.eps,
+                     (double)((size_t)M * N), d_n_iter, d_n_done);
+  return hipGetLastError();
+}
+
 // ---- a5 for many training points (generic path): K_*^T rows into V, mean, blocked V = L^-1 K_*^T, std ----
 __global__ void __launch_bounds__(256) k_kstar_build(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.z];

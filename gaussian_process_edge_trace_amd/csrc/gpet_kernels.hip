@@ -18,6 +18,7 @@ namespace gpet {
 // device helpers and launch-time constants; 25 s with hipcc), in this order:
 #include "gpet_k_common.inc"
 #include "gpet_k_conv.inc"
+#include "gpet_k_denoise.inc"
 #include "gpet_k_fit.inc"
 #include "gpet_k_factor.inc"
 #include "gpet_k_rng.inc"

@@ -359,13 +359,16 @@ def _raw_stack(raw_imgs):
 
 
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
-                         raw_dtype=None, grad_kernel=None):
+                         raw_dtype=None, grad_kernel=None, denoise=None):
     """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
     ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
     images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
-    shape (``grad_shape``) and, raw ones, their dtype (``raw_dtype``)."""
+    shape (``grad_shape``) and, raw ones, their dtype (``raw_dtype``).  ``denoise`` = (technique, kwargs) of
+    ``gpet_utils.denoise``: raw frames are denoised on the device first; gradient images cannot be."""
     have_grad = grad_imgs is not None or grad_device_ptrs is not None
     have_raw = raw_imgs is not None or raw_device_ptrs is not None
+    if denoise is not None and not have_raw:
+        raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs with grad_kernel): gradient images are past that stage")
     if have_grad and have_raw:
         raise ValueError("pass gradient images (grad_imgs / grad_device_ptrs) or raw frames (raw_imgs / raw_device_ptrs), not both")
     if not have_grad and not have_raw:
@@ -381,11 +384,11 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
             if grad_shape is None or raw_dtype is None:
                 raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
             ptrs = _as_list(raw_device_ptrs)
-            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape)
+            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape, denoise=denoise)
             share = len(ptrs) == 1
         else:
             frames, share = _raw_stack(raw_imgs)
-            raw = _lib.RawFrames(grad_kernel, frames=frames)
+            raw = _lib.RawFrames(grad_kernel, frames=frames, denoise=denoise)
         if not share and len(raw) != n_edges:
             raise ValueError("%d raw frames for %d edges" % (len(raw), n_edges))
         return dict(kind="raw", share=share, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
@@ -420,7 +423,8 @@ class GP_Edge_Tracing_Batch(object):
     def __init__(self, inits, grad_imgs, seeds, kernel_options=(1, 3, 3), noise_y=1, N_samples=500, score_thresh=1,
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
-                 sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None):
+                 sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
+                 denoise=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -430,9 +434,14 @@ class GP_Edge_Tracing_Batch(object):
         dtypes as float64 -- and the kernel ``comp_grad_img`` would be called with: the gradient images are made on the
         device, all frames in one pass, and the batch equals the one built from ``comp_grad_img``'s outputs bit for bit.
         ``raw_device_ptrs`` + ``raw_dtype`` + ``grad_shape``: the same for frames already on this GPU.  The kernel is
-        remembered for ``set_frame``."""
+        remembered for ``set_frame``.
+        ``denoise=(technique, kwargs)`` (raw frames only): ``gpet_utils.denoise`` of every frame on the device, in the same
+        pass, before the kernel is applied; the batch equals the one built from ``gpet_utils.denoise_imgs``' outputs bit for
+        bit.  Remembered for ``set_frame`` like the kernel."""
         B = len(inits)
-        src = resolve_image_source(B, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel)
+        src = resolve_image_source(B, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
+                                   denoise)
+        self._denoise = denoise
         self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
         self._raw_dtype = raw_dtype
         share = src["share"]
@@ -489,7 +498,7 @@ class GP_Edge_Tracing_Batch(object):
         self._set_obs()
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
-                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None):
+                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -497,14 +506,18 @@ class GP_Edge_Tracing_Batch(object):
         ``next_frame`` (default): the images continue the sequences just traced, so the any-rank (Matern) factor of the
         new trace's first iteration may start from the last trace's rows -- an iterative solve, the same rows to its
         tolerance.  ``next_frame=False``: unrelated images; the trace is what a fresh object would compute, bit for bit.
-        ``raw_imgs`` / ``raw_device_ptrs``: the frames themselves, as in the constructor; ``grad_kernel`` and ``raw_dtype``
-        default to the constructor's."""
+        ``raw_imgs`` / ``raw_device_ptrs``: the frames themselves, as in the constructor; ``grad_kernel``, ``raw_dtype`` and
+        ``denoise`` default to the constructor's (``denoise=None``); ``denoise=False`` takes these frames as they are, without
+        denoising, whatever the constructor was given."""
+        if denoise not in (None, False) and raw_imgs is None and raw_device_ptrs is None:
+            raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
         if raw_imgs is not None or raw_device_ptrs is not None:
             kern = self._grad_kernel if grad_kernel is None else grad_kernel
             b = self._batch
             n_img = 1 if b.share_image else self.B
             src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (b.M, b.N), raw_imgs, raw_device_ptrs,
-                                       self._raw_dtype if raw_dtype is None else raw_dtype, kern)
+                                       self._raw_dtype if raw_dtype is None else raw_dtype, kern,
+                                       None if denoise is False else (self._denoise if denoise is None else denoise))
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
             if len(src["batch"]["raw"]) != n_img or src["shape"] != (b.M, b.N):
                 raise ValueError("the new frames do not fit the batch (%s, %d x %d)"

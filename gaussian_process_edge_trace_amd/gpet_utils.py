@@ -1,6 +1,7 @@
 """Mirror of ``gp_edge_tracing/gpet_utils.py`` for the parts on (or feeding) the hot path.
 
-``comp_grad_img`` / ``comp_grad_imgs`` / ``normalise`` run on the GPU through libgpet_hip.so (a1); ``kernel_builder``
+``comp_grad_img`` / ``comp_grad_imgs`` / ``normalise`` run on the GPU through libgpet_hip.so (a1), and so do ``denoise`` /
+``denoise_imgs`` (a0) for the reference's 'median', 'minimum', 'gaussian' and 'tvc'; ``kernel_builder``
 is host-side setup (a 11x5 table).  ``construct_test_img`` is this package's own generator of the
 reference's synthetic test image recipe (gpet_utils.py:163-253).  Called like the reference (no ``seed``) it returns the
 reference's own image bit for bit: scikit-image 0.18's ``random_noise(..., seed=1)`` (gpet_utils.py:251) is
@@ -61,12 +62,44 @@ def comp_grad_img(img, kernel, norm=True, astyp=np.float32, ctx=None):
     return out.astype(astyp)
 
 
-def comp_grad_imgs(imgs, kernel, ctx=None):
+def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None):
     """``comp_grad_img`` of every frame of a stack in ONE batched GPU pass (gpet_grad_images): ``imgs`` is a (T, M, N) array
     or a sequence of (M, N) frames, the result a (T, M, N) float32 array whose frame t equals ``comp_grad_img(imgs[t],
     kernel)`` bit for bit.  uint8, uint16, float32 and float64 frames go to the device as they are (integer pixels mean their
-    exact float64 values); any other dtype is converted to float64 first, as ``comp_grad_img`` does with every image."""
-    return (ctx or _ctx()).grad_images(_lib.RawFrames(kernel, frames=imgs))
+    exact float64 values); any other dtype is converted to float64 first, as ``comp_grad_img`` does with every image.
+    ``denoise=(technique, kwargs)``: the frames are denoised on the device first, in the same pass -- the result equals
+    ``comp_grad_imgs(denoise_imgs(imgs, technique, kwargs), kernel)`` bit for bit."""
+    raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise)  # (refuses a bad spec before a device is needed)
+    return (ctx or _ctx()).grad_images(raw)
+
+
+def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False):
+    """``denoise`` of every frame of a stack in ONE batched GPU pass (gpet_denoise_images): ``imgs`` is a (T, M, N) array or a
+    sequence of (M, N) frames of one dtype, the result a (T, M, N) array whose frame t equals ``denoise(imgs[t], technique,
+    kwargs)`` bit for bit.  ``return_n_iter``: also the iterations 'tvc' ran per frame (0 for the filters)."""
+    raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs))  # (refuses a bad spec before a device is needed)
+    out, n_iter = (ctx or _ctx()).denoise_images(raw)
+    return (out, n_iter) if return_n_iter else out
+
+
+def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
+    """The reference's ``denoise`` (gpet_utils.py:122-158) on the GPU for its four deterministic stencils: 'median' and
+    'minimum' (scipy.ndimage: ``size``, ``mode``), 'gaussian' (scipy.ndimage: ``sigma``, ``truncate``, ``order=0``, ``mode``)
+    and 'tvc' (scikit-image's Chambolle total variation: ``weight``, ``eps``, ``n_iter_max``); modes 'reflect' (the default) and
+    'nearest'.  The result has the reference's dtype and, for uint8 / uint16 / float32 / float64 images, its values: the
+    filters' bit for bit (the Gaussian taps come from the C library's exp, which differs from numpy's by one unit in the last
+    place for some arguments -- visible in float64 results only), 'tvc' bit for bit with one deviation: a float32 image is
+    iterated in float64 (the result is the reference's on ``image.astype(float64)``).  Images of any other dtype are converted
+    to float64 first.  Any other keyword raises ValueError naming it; 'nl', 'wavelet' and 'tvb' raise NotImplementedError; an
+    unknown technique prints the reference's message and returns None, as the reference does.  ``plot`` and ``verbose`` are
+    accepted and ignored."""
+    if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.DN_NOT_BUILT:
+        print("Denoising technique not implemented.")
+        return None
+    if plot or verbose:
+        import warnings
+        warnings.warn("plot and verbose are accepted for API compatibility but ignored by the GPU denoiser")
+    return denoise_imgs([np.asarray(image)], technique, kwargs, ctx=ctx)[0]
 
 
 def construct_test_img(size, amplitude, curvature, noise_level, ltype, intensity, gaps=False, seed=None):

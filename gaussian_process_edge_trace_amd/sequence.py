@@ -50,19 +50,23 @@ class SequenceTracer(object):
 
     ``frames``: sequence of (M, N) gradient images -- or, with ``grad_kernel=K``, of raw frames (uint8, uint16, float32,
     float64 as they are, see ``GP_Edge_Tracing_Batch``) whose gradient images ``comp_grad_img(frame, K)`` are made on the
-    device, every step's frames in one pass, at construction and through ``set_frame`` alike; ``seeds``: one seed per frame (default: ``seed`` for all, like a
+    device, every step's frames in one pass, at construction and through ``set_frame`` alike -- after
+    ``gpet_utils.denoise`` of every frame, on the device in the same pass, with ``denoise=(technique, kwargs)``; ``seeds``: one seed per frame (default: ``seed`` for all, like a
     user re-creating ``GP_Edge_Tracing(..., seed=seed)`` per frame).  Remaining keyword arguments are the reference
     constructor's (gpet.py:22-35).  ``__call__`` returns the list of T results in frame order, each what
     ``GP_Edge_Tracing.__call__`` returns for that frame (trace, or (trace, credible interval) with ``return_std``)."""
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
-                 **kw):
+                 denoise=None, **kw):
         self.frames = frames
         self.T = len(frames)
         self.init = np.asarray(init)
         self.kw = dict(kw)
         self.kw.pop("obs", None)
         self.grad_kernel = grad_kernel
+        if denoise is not None and grad_kernel is None:
+            raise ValueError("denoise needs raw frames, i.e. grad_kernel")
+        self.denoise = denoise
         self.chains = chain_slices(self.T, n_chains)
         self.seeds = [int(seed)] * self.T if seeds is None else [int(v) for v in seeds]
         p = resolve_params(self.init, np.asarray(frames[0]).shape, **{k: v for k, v in self.kw.items()
@@ -98,7 +102,8 @@ class SequenceTracer(object):
                 if self._tracer is not None:
                     self._tracer._batch.close()
                 images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
-                                                                                     grad_kernel=self.grad_kernel)
+                                                                                     grad_kernel=self.grad_kernel,
+                                                                                     denoise=self.denoise)
                 self._tracer = GP_Edge_Tracing_Batch([self.init] * len(active), seeds=seeds, obs=obs, device=self.device,
                                                      _ctx=self._ctx, **images, **self.kw)
                 if self._ctx is None:

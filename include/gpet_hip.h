@@ -172,6 +172,42 @@ int gpet_grad_image(gpet_ctx* ctx, const double* img, int M, int N, const double
  * GPET_ERR_BAD_ARG for an unknown pix, a null frame, or a kernel whose patch exceeds 64 KB of LDS. */
 int gpet_grad_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh,
                      int kw, unsigned int flags, float* const* out);
+/* ---- a0: gpet_utils.denoise in front of a1 (gpet_utils.py:122-158) ---------------------- */
+/* The four techniques of the reference's denoise() that are deterministic stencils, on the device, for whole stacks:
+ * 'median' / 'minimum' (scipy.ndimage.median_filter / minimum_filter: size, mode), 'gaussian' (scipy.ndimage.gaussian_filter:
+ * sigma per axis, truncate, mode; order 0) and 'tvc' (skimage.restoration.denoise_tv_chambolle: weight, eps, n_iter_max).
+ * The denoised frame has the reference's dtype: the frame's own pixel type for the three filters (integer frames are
+ * quantised after each Gaussian pass, as scipy does), float64 for 'tvc' (u8 / u16 enter through img_as_float; an f32 frame is
+ * promoted to f64, where the reference would iterate in f32). */
+#define GPET_DN_NONE 0
+#define GPET_DN_MEDIAN 1
+#define GPET_DN_MINIMUM 2
+#define GPET_DN_GAUSSIAN 3
+#define GPET_DN_TVC 4
+#define GPET_DN_MODE_REFLECT 0 /* d c b a | a b c d | d c b a: scipy's default */
+#define GPET_DN_MODE_NEAREST 1 /* a a a a | a b c d | d d d d */
+typedef struct gpet_denoise {
+  int32_t technique;       /* GPET_DN_* */
+  int32_t size_y, size_x;  /* median / minimum: the window, at most 81 pixels (9 x 9) */
+  int32_t mode;            /* median / minimum / gaussian: GPET_DN_MODE_* */
+  double sigma_y, sigma_x; /* gaussian: both above 0 */
+  double truncate;         /* gaussian: radius int(truncate * sigma + 0.5); scipy's default 4.0 */
+  double weight;           /* tvc: above 0; skimage's default 0.1 */
+  double eps;              /* tvc: stop when |E_prev - E| < eps * E_0; skimage's default 2e-4 */
+  int32_t n_iter_max;      /* tvc: at least 1; skimage's default 200 */
+} gpet_denoise;
+/* denoise() of n_img frames [M*N] of pixel type pix in one batched pass: out[g] (host) receives frame g denoised, in the
+ * pixel type described above; n_iter_out (host, [n_img], may be NULL): iterations 'tvc' ran on frame g, 0 for the filters.
+ * A filter is one kernel launch per staging chunk (the Gaussian two) however many frames the chunk holds; the number of chunks
+ * grows with n_img once frames and workspace fill the 64 MB slot.  flags: GPET_RAW_ON_DEVICE.  GPET_ERR_BAD_ARG for
+ * technique NONE or unknown, a window above 81 pixels, sigma <= 0, weight <= 0, an unknown mode, n_iter_max < 1, an unknown
+ * pix or a null frame. */
+int gpet_denoise_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_denoise* dn,
+                        unsigned int flags, void* const* out, int32_t* n_iter_out);
+/* gpet_grad_images of the denoised frames, in one device pass: out[g] is bit for bit gpet_grad_images of what
+ * gpet_denoise_images returns for frame g.  dn NULL or technique NONE: gpet_grad_images itself. */
+int gpet_grad_images_dn(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh,
+                        int kw, const gpet_denoise* dn, unsigned int flags, float* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
@@ -196,6 +232,11 @@ int gpet_batch_create2(gpet_ctx* ctx, int B, int M, int N, const float* const* g
 int gpet_batch_create_raw(gpet_ctx* ctx, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh,
                           int kw, int share_image, const gpet_params* params, const int64_t* const* init_xy,
                           unsigned int flags, gpet_batch** out);
+/* gpet_batch_create_raw with the frames denoised first (gpet_denoise): the batch equals, bit for bit, the one
+ * gpet_batch_create_raw builds from gpet_denoise_images' outputs.  dn NULL or technique NONE: gpet_batch_create_raw itself. */
+int gpet_batch_create_raw_dn(gpet_ctx* ctx, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh,
+                             int kw, const gpet_denoise* dn, int share_image, const gpet_params* params,
+                             const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
 void gpet_batch_destroy(gpet_batch* b);
 int gpet_batch_size(const gpet_batch* b);
 /* out[0..count): Lg, S, n_keep, n_cap, factor_cap, z_cols, factor_rows_cap, n_bins, obs_cap, algo_thresh,
@@ -224,6 +265,12 @@ int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int 
  * A call refused with GPET_ERR_BAD_ARG (unknown pix, null frame, oversized kernel) leaves the batch as it was. */
 int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw,
                               unsigned int flags);
+
+/* gpet_batch_set_raw_images with the frames denoised first; dn NULL or technique NONE: gpet_batch_set_raw_images itself.  A
+ * call refused with GPET_ERR_BAD_ARG (as gpet_batch_set_raw_images, or a spec gpet_denoise_images refuses) leaves the batch as
+ * it was. */
+int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw,
+                                 const gpet_denoise* dn, unsigned int flags);
 
 /* set / get the observation set (xy int64) of edge e (gpet.py:100,820,857). */
 int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs);
