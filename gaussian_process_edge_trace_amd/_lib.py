@@ -263,6 +263,14 @@ SYMBOLS = {
     "gpet_batch_create_raw_dn": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int,
                                            C.POINTER(GpetDenoise), C.c_int, C.POINTER(GpetParams), C.POINTER(_P), C.c_uint,
                                            C.POINTER(_P)]),
+    "gpet_batch_create_mapped": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P),
+                                           C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_create_raw_mapped": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.c_int,
+                                               _P, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.POINTER(GpetParams), C.POINTER(_P),
+                                               C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_image_count": (C.c_int, [_P]),
+    "gpet_batch_warm_start": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "gpet_batch_warm_start_ready": (C.c_int, [_P]),
     "gpet_batch_set_images": (C.c_int, [_P, C.POINTER(_P), C.c_uint]),
     "gpet_batch_set_raw_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint]),
     "gpet_batch_set_raw_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_uint]),
@@ -598,15 +606,28 @@ _DT = {BUF_X_TRAIN: np.float64, BUF_Y_TRAIN: np.float64, BUF_CHOL: np.float64, B
 class Batch:
     """gpet_batch: B independent edges processed together."""
 
-    def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None, raw=None):
+    def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None, raw=None,
+                 image_of=None):
         """``grads``: float32 (M, N) arrays on the host -- or, with ``device_ptrs`` (a list of integer device
         addresses of f32 [M*N] images on the context's device, e.g. ``tensor.data_ptr()`` after an RCCL broadcast) and
         ``shape`` = (M, N), nothing on the host at all: the library consumes the device images in place.  Or ``raw`` (a
         RawFrames: frames + gradient kernel) instead of both: the gradient images are made on the device
-        (gpet_batch_create_raw)."""
+        (gpet_batch_create_raw).  ``image_of``: an image map -- B indices into the images, of which there are then ``n_img``
+        (the length of the list of images given, ``grads`` a list of (M, N) arrays or an (n_img, M, N) stack) instead of one
+        or B; the library checks the map against that count (gpet_batch_create_mapped / gpet_batch_create_raw_mapped)."""
         self.ctx = ctx
         self.lib = ctx.lib
         B = len(params)
+        if image_of is not None:
+            if share_image:
+                raise ValueError("share_image and image_of are alternatives")
+            image_of = [int(v) for v in image_of]
+            if len(image_of) != B:
+                raise ValueError("image_of has %d entries for %d edges" % (len(image_of), B))
+            if raw is None and device_ptrs is None and np.ndim(grads) == 2:
+                grads = [grads]  # (a 2-D array is ONE image)
+            n_img = len(raw if raw is not None else device_ptrs if device_ptrs is not None else grads)
+            io = (C.c_int32 * B)(*image_of)
         inits = [np.ascontiguousarray(i, dtype=np.int64) for i in inits]
         if raw is not None:
             if grads is not None or device_ptrs is not None:
@@ -626,7 +647,15 @@ class Batch:
         ip = (_P * B)(*[i.ctypes.data for i in inits])
         pa = (GpetParams * B)(*params)
         h = _P()
-        if raw is not None:
+        if image_of is not None:  # (the library checks the map: its message says what is wrong with it)
+            if raw is not None:
+                kp, kh, kw = raw.kernel_args()
+                ctx.check(self.lib.gpet_batch_create_raw_mapped(ctx.h, B, self.M, self.N, n_img, io, raw.pointer_array(), raw.pix, kp,
+                                                                kh, kw, raw.dn_arg() if raw.dn is not None else None, pa, ip,
+                                                                raw.flags, C.byref(h)))
+            else:
+                ctx.check(self.lib.gpet_batch_create_mapped(ctx.h, B, self.M, self.N, n_img, io, gp, pa, ip, flags, C.byref(h)))
+        elif raw is not None:
             assert len(raw) == (1 if share_image else B)
             kp, kh, kw = raw.kernel_args()
             if raw.dn is not None:
@@ -650,13 +679,15 @@ class Batch:
             _live_batches[:] = [r for r in _live_batches if r() is not None and getattr(r(), "h", None)]
         self._scored = False
         self.share_image = bool(share_image)
+        self.n_img = self.lib.gpet_batch_image_count(h)  # images the batch holds: 1 shared, B own, or the map's
+        self.image_of = image_of
         self._keep = (grads, inits)
 
     def set_images(self, grads=None, device_ptrs=None, next_frame=False, raw=None):
         """New gradient image(s) for the same edges, gradient KDE recomputed, loop state reset (gpet_batch_set_images).
         ``next_frame``: the images are the next frames of the sequences just traced, so an any-rank factor may start from
         the last trace's rows (GPET_IMAGES_NEXT_FRAME); otherwise nothing of an earlier trace is used."""
-        n_img = 1 if self.share_image else self.B
+        n_img = self.n_img
         nf = IMAGES_NEXT_FRAME if next_frame else 0
         if raw is not None:  # (a RawFrames: gpet_batch_set_raw_images)
             if grads is not None or device_ptrs is not None:
@@ -714,6 +745,17 @@ class Batch:
     def set_obs(self, e, obs_xy):
         o = np.ascontiguousarray(np.asarray(obs_xy).reshape(-1, 2), dtype=np.int64)
         self.ctx.check(self.lib.gpet_batch_set_obs(self.h, e, o.ctypes.data if o.size else None, o.shape[0]))
+
+    def warm_start(self, warm_every):
+        """gpet_batch_warm_start: every edge's observation set for the next frame from its last converged fit, on the device
+        (the rule of sequence.warm_start_obs).  Returns the sizes of the sets."""
+        cnt = np.zeros(self.B, dtype=np.int32)
+        self.ctx.check(self.lib.gpet_batch_warm_start(self.h, int(warm_every), cnt.ctypes.data_as(C.POINTER(C.c_int32))))
+        return cnt
+
+    def warm_start_ready(self):
+        """Raises what warm_start would raise now (GpetError: no converged fits of a last trace), and touches nothing."""
+        self.ctx.check(self.lib.gpet_batch_warm_start_ready(self.h))
 
     def read(self, which, e=0):
         inf = self.info(e)

@@ -20,7 +20,7 @@ struct BatchGuard {
 static int upload_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
   gpet_ctx* c = b->ctx;
   const size_t px = (size_t)b->bd.M * b->bd.N;
-  const int n_img = b->share_image ? 1 : b->B;
+  const int n_img = b->n_img;
   const bool on_dev = (flags & GPET_GRAD_ON_DEVICE) != 0;
   for (int g = 0; g < n_img; ++g)
     if (!grad[g]) return fail(c, GPET_ERR_BAD_ARG, "gradient image %d is a null pointer", g);
@@ -38,7 +38,7 @@ static int upload_images(gpet_batch* b, const float* const* grad, unsigned int f
       src = b->d_raw;
     }
     HIPCHK(c, launch_minmax(c->stream, src, px, mm));
-    HIPCHK(c, launch_normalise(c->stream, src, px, mm, (float*)b->h_edges[g].grad));
+    HIPCHK(c, launch_normalise(c->stream, src, px, mm, (float*)b->h_edges[b->img_rep[g]].grad));
   }
   HIPCHK(c, gpet_wait(c->stream));  // (pageable sources and h_mm0 must stay valid until the copies have run)
   return GPET_OK;
@@ -62,9 +62,9 @@ struct ImageSource {
 // subtracts a minimum of exactly 0 and divides by a span of exactly 1.
 static int convolve_images(gpet_batch* b, const ImageSource& s) {
   gpet_ctx* c = b->ctx;
-  const int n_img = b->share_image ? 1 : b->B;
+  const int n_img = b->n_img;
   std::vector<float*> dst((size_t)n_img);
-  for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[g].grad;
+  for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[b->img_rep[g]].grad;
   const int rc = conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, (s.flags & GPET_RAW_ON_DEVICE) != 0,
                              dst.data(), b->d_minmax);
   if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
@@ -72,6 +72,20 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
 }
 
 static int load_images(gpet_batch* b, const ImageSource& s) { return s.raw ? convolve_images(b, s) : upload_images(b, s.grad, s.flags); }
+
+// gradient KDE of every image slot (gpet.py:127), once per slot through the slot's representative edge: where the representatives
+// are not the first n_img edges, over a device copy of their EdgeDev in slot order (as setup_struct_basis runs its classes)
+static int image_kde(gpet_batch* b) {
+  gpet_ctx* c = b->ctx;
+  if (b->rep_is_prefix) {
+    HIPCHK(c, launch_kde(c->stream, b->d_edges, b->n_img, b->bd, 1));
+    return GPET_OK;
+  }
+  for (int g = 0; g < b->n_img; ++g) b->h_img_edges[(size_t)g] = b->h_edges[b->img_rep[g]];
+  HIPCHK(c, hipMemcpyAsync(b->d_img_edges, b->h_img_edges.data(), sizeof(EdgeDev) * (size_t)b->n_img, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_kde(c->stream, b->d_img_edges, b->n_img, b->bd, 1));
+  return GPET_OK;
+}
 
 // what can be refused before anything is allocated or enqueued (conv_frames checks the same on its own)
 static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img) {
@@ -152,13 +166,21 @@ static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
 }
 
 // the one body of batch creation, whatever the images come as
-static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, const gpet_params* params,
-                             const int64_t* const* init_xy, gpet_batch** out) {
+// image_of == nullptr: one image for all edges (share_image) or one per edge; else the image map (n_img, image_of[B])
+static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, int n_img,
+                             const int32_t* image_of, const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out) {
   if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.raw) || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
+  const bool mapped = image_of != nullptr;
+  if (mapped) {
+    if (const char* why = image_map_check(B, n_img, image_of)) return fail(c, GPET_ERR_BAD_ARG, "image map: %s (B = %d, n_img = %d)", why, B, n_img);
+    share_image = 0;
+  } else {
+    n_img = share_image ? 1 : B;
+  }
   if (src.raw) {
-    const int rc0 = check_raw_source(c, src, share_image ? 1 : B);
+    const int rc0 = check_raw_source(c, src, n_img);
     if (rc0) return rc0;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -171,6 +193,13 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   b->ctx = c;
   b->B = B;
   b->share_image = share_image ? 1 : 0;
+  b->n_img = n_img;
+  b->image_of.resize((size_t)B);
+  for (int e = 0; e < B; ++e) b->image_of[(size_t)e] = mapped ? image_of[e] : (share_image ? 0 : e);
+  b->img_rep.resize((size_t)n_img);
+  image_map_reps(B, n_img, b->image_of.data(), b->img_rep.data());
+  b->rep_is_prefix = true;
+  for (int g = 0; g < n_img; ++g) b->rep_is_prefix = b->rep_is_prefix && b->img_rep[(size_t)g] == g;
   b->h_edges.resize(B);
   b->h_scalars.resize(B);
   b->params.assign(params, params + B);
@@ -189,8 +218,13 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   b->bd = reduce_dims(b->h_edges.data(), B, M, N);
   b->bd.rng4 = normals4_applies(b->h_edges.data(), B) ? 1 : 0;
   // the arena: measure, allocate, place
+  // (an image map takes its slots at the front of the arena; without one the two layouts are what they always were)
+  auto lay = [&](Carver& cv) {
+    return mapped ? layout_batch(cv, b->h_edges.data(), B, b->bd, n_img, b->image_of.data())
+                  : layout_batch(cv, b->h_edges.data(), B, b->bd, b->share_image != 0);
+  };
   Carver meas;
-  layout_batch(meas, b->h_edges.data(), B, b->bd, b->share_image != 0);
+  lay(meas);
   b->arena_bytes = meas.off + 256;
   hipError_t he = hipMalloc(&b->arena, b->arena_bytes);
   if (he != hipSuccess) {
@@ -200,7 +234,7 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   HIPCHK(c, hipMemsetAsync(b->arena, 0, b->arena_bytes, c->stream));
   Carver cv;
   cv.base = b->arena;
-  const BatchBlocks bb = layout_batch(cv, b->h_edges.data(), B, b->bd, b->share_image != 0);
+  const BatchBlocks bb = lay(cv);
   b->d_scalars = bb.scalars;
   b->d_fin_out = bb.fin_out;
   b->d_fin_par = bb.fin_par;
@@ -210,6 +244,10 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   HIPCHK(c, hipMalloc(&b->d_edges, sizeof(EdgeDev) * B));
   HIPCHK(c, hipMalloc(&b->d_seeds, sizeof(unsigned int) * B));
   HIPCHK(c, hipMalloc(&b->d_minmax, sizeof(unsigned int) * 2 * (size_t)B));
+  if (!b->rep_is_prefix) {
+    b->h_img_edges.resize((size_t)n_img);
+    HIPCHK(c, hipMalloc(&b->d_img_edges, sizeof(EdgeDev) * (size_t)n_img));
+  }
   // (the stream the normals run ahead of the loop on: default priority -- lowest / highest were measured, +-0)
   HIPCHK(c, hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking));
   // the stream the converged fits' objective runs on has the highest priority (its launches are small and many)
@@ -232,8 +270,8 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   HIPCHK(c, upload_pristine_scalars(b));
   HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * B, hipMemcpyHostToDevice, c->stream));
   if (any_gen_nu) HIPCHK(c, launch_rho_tab(c->stream, b->d_edges, B, N));
-  // gradient KDE of every distinct image (gpet.py:127)
-  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->share_image ? 1 : B, b->bd, 1));
+  rc = image_kde(b);
+  if (rc) return rc;
   HIPCHK(c, gpet_wait(c->stream));
   rc = setup_struct_basis(b, init_xy);
   if (rc) return rc;
@@ -247,7 +285,33 @@ int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* gra
   ImageSource src;
   src.grad = grad;
   src.flags = flags;
-  return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
+  return batch_create_from(c, B, M, N, src, share_image, 0, nullptr, params, init_xy, out);
+}
+
+int gpet_batch_create_mapped(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, const float* const* grad,
+                             const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
+  if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
+  ImageSource src;
+  src.grad = grad;
+  src.flags = flags;
+  return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
+}
+
+int gpet_batch_create_raw_mapped(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, const void* const* raw, int pix,
+                                 const double* kern, int kh, int kw, const gpet_denoise* dn, const gpet_params* params,
+                                 const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
+  if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_mapped: bad argument");
+  if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
+  const DenoiseSpec spec = dn_spec(dn);
+  ImageSource src;
+  src.raw = raw;
+  src.pix = pix;
+  src.kern = kern;
+  src.kh = kh;
+  src.kw = kw;
+  src.dn = dn ? &spec : nullptr;
+  src.flags = flags;
+  return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
 }
 
 int gpet_batch_create_raw_dn(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
@@ -263,7 +327,7 @@ int gpet_batch_create_raw_dn(gpet_ctx* c, int B, int M, int N, const void* const
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
-  return batch_create_from(c, B, M, N, src, share_image, params, init_xy, out);
+  return batch_create_from(c, B, M, N, src, share_image, 0, nullptr, params, init_xy, out);
 }
 
 int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
@@ -283,6 +347,7 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->d_seeds_act) (void)hipFree(b->d_seeds_act);
   if (b->d_seeds) (void)hipFree(b->d_seeds);
   if (b->d_minmax) (void)hipFree(b->d_minmax);
+  if (b->d_img_edges) (void)hipFree(b->d_img_edges);
   if (b->d_raw) (void)hipFree(b->d_raw);
   if (b->ev_l0) (void)hipEventDestroy(b->ev_l0);
   if (b->ev_l1) (void)hipEventDestroy(b->ev_l1);
@@ -317,6 +382,8 @@ void gpet_batch_destroy(gpet_batch* b) {
 }
 
 int gpet_batch_size(const gpet_batch* b) { return b ? b->B : 0; }
+
+int gpet_batch_image_count(const gpet_batch* b) { return b ? b->n_img : 0; }
 
 int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count) {
   if (!b || e < 0 || e >= b->B || !out) return GPET_ERR_BAD_ARG;
@@ -401,6 +468,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
   EdgeDev& E = b->h_edges[e];
   if (n_obs > E.obs_cap) return fail(c, GPET_ERR_BAD_ARG, "n_obs=%d exceeds obs_cap=%d", n_obs, E.obs_cap);
   b->have_results = false;
+  b->have_last_fit = false;  // (the trace that follows is not the one the fits in d_fin_out belong to)
   // the pixel kernels index the density images with the observations (gpet.py:568: kde_arr[pre_fobs[:,0], pre_fobs[:,1]]
   // raises IndexError in the reference for pixels outside the image)
   for (int i = 0; i < n_obs; ++i)
@@ -435,6 +503,39 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
     HIPCHK(c, hipMemcpyAsync(E.obs_xy, obs_xy, sizeof(long long) * 2 * n_obs, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(E.sc, &s, sizeof s, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, gpet_wait(c->stream));
+  return GPET_OK;
+}
+
+// GPET_OK when gpet_batch_warm_start can run, else its refusal -- for a caller that swaps the images first and must not find out after
+int gpet_batch_warm_start_ready(gpet_batch* b) {
+  if (!b) return GPET_ERR_BAD_ARG;
+  if (!b->have_last_fit)
+    return fail(b->ctx, GPET_ERR_BAD_ARG, "gpet_batch_warm_start: no converged fits of a last trace on the device (run a trace to its "
+                                          "gpet_final_fit_all first; gpet_batch_set_obs or a warm start since then have used them up)");
+  return GPET_OK;
+}
+
+// The observation sets of the next frame from the converged fits of the last trace, on the device (k_warm_start: the rule of
+// sequence.warm_start_obs); leaves what B calls of gpet_batch_set_obs with those sets leave, with one wait in all.
+int gpet_batch_warm_start(gpet_batch* b, int warm_every, int32_t* n_obs_out) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  const int ready = gpet_batch_warm_start_ready(b);
+  if (ready) return ready;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_warm_start(c->stream, b->d_edges, b->B, warm_every));
+  b->have_results = false;
+  b->have_last_fit = false;
+  b->iters_issued = 0;
+  b->norm_issued = 0;
+  const int rc = fetch_all_scalars(b);  // (the one copy and the one wait: the counts are in the scalars)
+  if (rc) return rc;
+  b->h_nobs_prev.assign((size_t)b->B, 0);
+  for (int e = 0; e < b->B; ++e) {
+    b->h_nobs_prev[(size_t)e] = b->h_scalars[(size_t)e].n_obs;
+    if (n_obs_out) n_obs_out[e] = b->h_scalars[(size_t)e].n_obs;
+  }
   return GPET_OK;
 }
 
@@ -593,7 +694,7 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
     case GPET_BUF_BEST_COSTS: dst = E.best_costs; cap = (size_t)E.n_keep * 8; break;
     case GPET_BUF_MEAN: dst = E.mean; cap = Lg * 8; break;
     case GPET_BUF_COV: dst = E.cov; cap = Lg * Lg * 8; b->have_fit = true; break;
-    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); b->have_results = false; break;
+    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); b->have_results = b->have_last_fit = false; break;
     default:
       return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_write: buffer %d is not writable", which);
   }
@@ -698,7 +799,8 @@ static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
   int rc = load_images(b, src);
   if (rc) return rc;
   // gradient KDE of every distinct image (gpet.py:127), then the state of a fresh constructor
-  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->share_image ? 1 : b->B, b->bd, 1));
+  rc = image_kde(b);
+  if (rc) return rc;
   b->have_fit = b->have_factor = b->have_normals = b->have_samples = b->have_scores = false;
   return batch_reset(b, (flags & GPET_IMAGES_NEXT_FRAME) != 0);
 }
@@ -727,7 +829,7 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
-  const int rc = check_raw_source(b->ctx, src, b->share_image ? 1 : b->B);
+  const int rc = check_raw_source(b->ctx, src, b->n_img);
   if (rc) return rc;
   return batch_set_images_from(b, src);
 }

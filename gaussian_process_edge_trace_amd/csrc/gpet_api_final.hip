@@ -105,6 +105,7 @@ int gpet_final_predict_all(gpet_batch* b, const double* par, double* mean_out, d
   for (int e = 0; e < b->B; ++e)
     if (b->h_edges[e].fin_n < 1) return fail(c, GPET_ERR_STATE, "gpet_final_predict_all before the training sets are set");
   b->have_results = false;  // (a caller's own parameters: not the optimum gpet_batch_results reports)
+  b->have_last_fit = false;  // (nor a trace's converged fit)
   // (slots 9..11 of every edge stay: the lattice of its training set)
   HIPCHK(c, hipMemcpy2DAsync(b->d_fin_par, 12 * sizeof(double), par, 12 * sizeof(double), 9 * sizeof(double), b->B,
                              hipMemcpyHostToDevice, c->stream));
@@ -355,6 +356,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   if (!b || !seeds || !mean_out || !std_out || stride < b->bd.Lg) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   b->have_results = false;
+  b->have_last_fit = false;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = fetch_all_scalars(b);  // (synchronises the loop's stream: the observation sets are final)
   if (rc) return rc;
@@ -397,6 +399,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   if (rounds_out) *rounds_out = rounds;
   b->have_fit = false;  // the loop's L/alpha were overwritten by the converged fit
   b->have_results = true;  // (fin_out + lb_theta_out: what gpet_batch_results packs)
+  b->have_last_fit = true;  // (fin_out: what gpet_batch_warm_start reads, past the reset of the next frame)
   return check_device_status(b);
 }
 

@@ -92,6 +92,15 @@ struct gpet_batch {
   std::vector<unsigned int> h_mm0;     // their reset values (kept alive for the asynchronous copy)
   float* d_raw = nullptr;  // [M*N] staging of a user gradient image before its re-normalisation (gpet.py:97)
   int share_image = 0;
+  // the image map (gpet_batch_plan.h): n_img image slots, edge e reads slot image_of[e], img_rep[g] is the first edge of slot g --
+  // its EdgeDev::grad / grad_kde are where image g is written and what its gradient KDE runs through.  One shared image: 1 slot;
+  // one image per edge: B slots, the identity map
+  int n_img = 0;
+  std::vector<int32_t> image_of;
+  std::vector<int> img_rep;
+  bool rep_is_prefix = true;           // img_rep[g] == g for every slot: d_edges itself serves the per-slot launches
+  std::vector<EdgeDev> h_img_edges;    // else: the representatives' EdgeDev, in slot order, and their device copy
+  EdgeDev* d_img_edges = nullptr;
   bool structured = false;  // every edge can take the prior-eigenbasis loop path
   // converged-fit scratch (grown on demand)
   int lml_cap = 0;
@@ -129,6 +138,11 @@ struct gpet_batch {
   // gpet_final_fit_all has run on the current trace: d_fin_out / lb_theta_out hold what gpet_batch_results packs (cleared by
   // everything that starts another trace or overwrites the converged fit)
   bool have_results = false;
+  // the converged fits of the LAST trace are in d_fin_out: what gpet_batch_warm_start derives the next frame's observations from.
+  // Unlike have_results it survives gpet_batch_reset / gpet_batch_set_images (they do not touch d_fin_out); cleared by whatever
+  // starts the trace after (gpet_batch_set_obs, gpet_batch_warm_start, gpet_trace_iterate, gpet_select_pixels[_only], a write of
+  // the scalars) or overwrites the fit
+  bool have_last_fit = false;
   char* d_results = nullptr;           // device staging of gpet_batch_results into host memory (grown on demand)
   size_t results_bytes = 0;
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it

@@ -202,6 +202,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   if (!b || !base_seeds || !n_active || max_iters < 0) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   b->have_results = false;
+  b->have_last_fit = false;  // (another trace is under way: d_fin_out belongs to the one before until its own converged fit)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(b->d_seeds, base_seeds, sizeof(uint32_t) * b->B, hipMemcpyHostToDevice, c->stream));
   *n_active = b->B;

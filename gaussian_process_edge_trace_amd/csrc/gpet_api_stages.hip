@@ -105,6 +105,7 @@ int gpet_select_pixels(gpet_batch* b) {
   gpet_ctx* c = b->ctx;
   if (!b->have_scores) return fail(c, GPET_ERR_STATE, "gpet_select_pixels before gpet_score_curves");
   b->have_results = false;  // (a new observation set: another trace)
+  b->have_last_fit = false;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
   HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0));
@@ -168,6 +169,7 @@ int gpet_select_pixels_only(gpet_batch* b) {
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   b->have_results = false;  // (a new observation set: another trace)
+  b->have_last_fit = false;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
   HIPCHK(c, launch_pixels_reset(c->stream, b->d_edges, b->B, b->bd));

@@ -164,15 +164,43 @@ struct BatchBlocks {
   int n_init_max;
 };
 
-// Lays out the whole arena and sets every pointer of every edge: the shared images, the batch-contiguous blocks, then edge by
+// ---- image map ------------------------------------------------------------------------------------------------------------
+// Which image every edge of a batch reads: n_img image slots, edge e reads slot image_of[e] (a video frame or an OCT slice with a
+// few edges on it: the layers of a retina, the two walls of a vessel).  "One image for all" is the map n_img = 1, all zeros;
+// "one image per edge" keeps its own layout (the pair at the end of every edge's buffers).
+
+// nullptr, or what is wrong with the map (every slot must be read by at least one edge; the edges of a slot need not be adjacent)
+inline const char* image_map_check(int B, int n_img, const int32_t* image_of) {
+  if (n_img < 1) return "n_img must be at least 1";
+  if (n_img > B) return "more image slots than edges";
+  if (!image_of) return "image_of is a null pointer";
+  std::vector<char> used((size_t)n_img, 0);
+  for (int e = 0; e < B; ++e) {
+    if (image_of[e] < 0 || image_of[e] >= n_img) return "image_of holds an index outside [0, n_img)";
+    used[(size_t)image_of[e]] = 1;
+  }
+  for (int g = 0; g < n_img; ++g)
+    if (!used[(size_t)g]) return "an image slot is read by no edge";
+  return nullptr;
+}
+
+// rep[g]: the slot's representative, the first edge that reads slot g (a checked map: every slot has one)
+inline void image_map_reps(int B, int n_img, const int32_t* image_of, int* rep) {
+  for (int g = 0; g < n_img; ++g) rep[g] = -1;
+  for (int e = 0; e < B; ++e)
+    if (rep[image_of[e]] < 0) rep[image_of[e]] = e;
+}
+
+// Lays out the whole arena and sets every pointer of every edge: the image slots, the batch-contiguous blocks, then edge by
 // edge.  Called twice on the same edges: with cv.base == nullptr it measures (cv.off is the size; the pointers come out null),
-// with the arena as base it places.
-inline BatchBlocks layout_batch(Carver& cv, EdgeDev* edges, int B, const BatchDims& bd, bool share_image) {
+// with the arena as base it places.  n_img (grad, grad_kde) pairs are taken at the front and edge e points at pair
+// image_of[e] (image_of == nullptr: pair 0); n_img == 0: every edge takes a pair of its own behind its other buffers.
+inline BatchBlocks layout_batch_slots(Carver& cv, EdgeDev* edges, int B, const BatchDims& bd, int n_img, const int32_t* image_of) {
   const size_t px = (size_t)bd.M * bd.N, gpx = (size_t)(bd.M + 2) * (bd.N + 2);
-  float *shared_grad = nullptr, *shared_kde = nullptr;
-  if (share_image) {
-    shared_grad = cv.take<float>(px);
-    shared_kde = cv.take<float>(px);
+  std::vector<float*> slot_grad((size_t)n_img, nullptr), slot_kde((size_t)n_img, nullptr);
+  for (int g = 0; g < n_img; ++g) {
+    slot_grad[(size_t)g] = cv.take<float>(px);
+    slot_kde[(size_t)g] = cv.take<float>(px);
   }
   BatchBlocks bb{};
   bb.n_init_max = 1;
@@ -255,10 +283,21 @@ inline BatchBlocks layout_batch(Carver& cv, EdgeDev* edges, int B, const BatchDi
     E.fin_y = cv.take<double>(nc);
     E.fin_w = cv.take<double>(nc);
     cv.skip<double>(12);  // (reserved: fin_par points into the batch block)
-    E.grad = share_image ? shared_grad : cv.take<float>(px);
-    E.grad_kde = share_image ? shared_kde : cv.take<float>(px);
+    const size_t g = image_of ? (size_t)image_of[e] : 0;
+    E.grad = n_img ? slot_grad[g] : cv.take<float>(px);
+    E.grad_kde = n_img ? slot_kde[g] : cv.take<float>(px);
   }
   return bb;
+}
+
+// one image for all edges, or one per edge
+inline BatchBlocks layout_batch(Carver& cv, EdgeDev* edges, int B, const BatchDims& bd, bool share_image) {
+  return layout_batch_slots(cv, edges, B, bd, share_image ? 1 : 0, nullptr);
+}
+
+// a checked image map (image_map_check); n_img = 1 is the shared layout, offset for offset
+inline BatchBlocks layout_batch(Carver& cv, EdgeDev* edges, int B, const BatchDims& bd, int n_img, const int32_t* image_of) {
+  return layout_batch_slots(cv, edges, B, bd, n_img, image_of);
 }
 
 // ---- structured loop path -------------------------------------------------------------------------------------------------

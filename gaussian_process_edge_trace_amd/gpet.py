@@ -424,7 +424,7 @@ class GP_Edge_Tracing_Batch(object):
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
-                 denoise=None):
+                 denoise=None, image_of=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -437,14 +437,32 @@ class GP_Edge_Tracing_Batch(object):
         remembered for ``set_frame``.
         ``denoise=(technique, kwargs)`` (raw frames only): ``gpet_utils.denoise`` of every frame on the device, in the same
         pass, before the kernel is applied; the batch equals the one built from ``gpet_utils.denoise_imgs``' outputs bit for
-        bit.  Remembered for ``set_frame`` like the kernel."""
+        bit.  Remembered for ``set_frame`` like the kernel.
+        ``image_of``: an image map -- B indices, edge e reads image ``image_of[e]`` -- for frames with several edges on them
+        (the layers of a retina, the two walls of a vessel).  ``grad_imgs``, ``grad_device_ptrs``, ``raw_imgs`` and
+        ``raw_device_ptrs`` are then ``n_img = max(image_of) + 1`` long instead of B, every index must occur (in any order:
+        ``[0, 1, 2, 0, 1, 2]`` is valid), and ``set_frame`` expects ``n_img`` images.  Every image is uploaded, turned into a
+        gradient image, denoised and run through the gradient KDE once; the batch equals the one built from the B images
+        ``imgs[image_of[e]]`` bit for bit."""
         B = len(inits)
-        src = resolve_image_source(B, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
-                                   denoise)
+        if image_of is not None:
+            image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
+            if len(image_of) != B:
+                raise ValueError("image_of has %d entries for %d edges" % (len(image_of), B))
+            n_img = max(image_of) + 1
+            given = [a for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs) if a is not None]
+            if len(given) == 1 and not (isinstance(given[0], (list, tuple)) or np.ndim(given[0]) == 3):
+                raise ValueError("with image_of the images are a list (or stack) of n_img = %d" % n_img)
+            if len(given) == 1 and len(given[0]) != n_img:
+                raise ValueError("%d images for an image map of n_img = %d" % (len(given[0]), n_img))
+            if grad_imgs is not None:
+                grad_imgs = list(grad_imgs)
+        src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
+                                   raw_dtype, grad_kernel, denoise)
         self._denoise = denoise
         self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
         self._raw_dtype = raw_dtype
-        share = src["share"]
+        share = src["share"] and image_of is None  # (a map of one image is the shared layout, decided by the library)
         shapes = [src["shape"]] * B
         assert len(seeds) == B
         obs = [np.array([])] * B if obs is None else list(obs)
@@ -475,7 +493,7 @@ class GP_Edge_Tracing_Batch(object):
             abi.append(hit[1])
         self._ctx = _ctx if _ctx is not None else _lib.Context(device, stream)
         kw = dict(src["batch"])
-        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, **kw)
+        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, image_of=image_of, **kw)
         if sample_dtype is not None:
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
@@ -497,8 +515,14 @@ class GP_Edge_Tracing_Batch(object):
         self._batch.reset()
         self._set_obs()
 
+    def _images_text(self):
+        b = self._batch
+        if b.image_of is not None:
+            return "%d images, the batch's image map has n_img = %d" % (b.n_img, b.n_img)
+        return "one shared image" if b.share_image else "one image per edge, %d" % b.n_img
+
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
-                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None):
+                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -508,35 +532,60 @@ class GP_Edge_Tracing_Batch(object):
         tolerance.  ``next_frame=False``: unrelated images; the trace is what a fresh object would compute, bit for bit.
         ``raw_imgs`` / ``raw_device_ptrs``: the frames themselves, as in the constructor; ``grad_kernel``, ``raw_dtype`` and
         ``denoise`` default to the constructor's (``denoise=None``); ``denoise=False`` takes these frames as they are, without
-        denoising, whatever the constructor was given."""
+        denoising, whatever the constructor was given.
+        A batch with an image map takes ``n_img`` images.  A call whose images do not fit the batch raises ValueError, a
+        ``warm_every`` without a last trace raises GpetError, and both leave the batch as it was.
+        ``warm_every=k`` instead of ``obs``: the warm start is made on the device (gpet_batch_warm_start) -- every edge's
+        observations from its own last converged fit by the rule of ``sequence.warm_start_obs(trace, x_st, x_en, k, algo_thresh,
+        M)`` -- with no trip of the traces through the host; the sets are read back once, so that ``reset()`` restores the same
+        warm start.  It needs the trace this object ran last (``__call__`` or ``finish``)."""
+        if warm_every is not None and obs is not None:
+            raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
+        if warm_every is not None:
+            self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
         if denoise not in (None, False) and raw_imgs is None and raw_device_ptrs is None:
             raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
         if raw_imgs is not None or raw_device_ptrs is not None:
             kern = self._grad_kernel if grad_kernel is None else grad_kernel
             b = self._batch
-            n_img = 1 if b.share_image else self.B
+            n_img = b.n_img
+            if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
+                raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
+            have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
+            if not (n_img == 1 and np.ndim(have) == 2) and len(have) != n_img:
+                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % (len(have), self._images_text(), b.M, b.N))
             src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (b.M, b.N), raw_imgs, raw_device_ptrs,
                                        self._raw_dtype if raw_dtype is None else raw_dtype, kern,
                                        None if denoise is False else (self._denoise if denoise is None else denoise))
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
             if len(src["batch"]["raw"]) != n_img or src["shape"] != (b.M, b.N):
-                raise ValueError("the new frames do not fit the batch (%s, %d x %d)"
-                                 % ("one shared image" if b.share_image else "one image per edge", b.M, b.N))
+                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"
+                                 % (len(src["batch"]["raw"]), self._images_text(), b.M, b.N))
             b.set_images(raw=src["batch"]["raw"], next_frame=next_frame)
         elif grad_device_ptrs is not None:
-            self._batch.set_images(device_ptrs=list(grad_device_ptrs) if isinstance(grad_device_ptrs, (list, tuple))
-                                   else [grad_device_ptrs], next_frame=next_frame)
+            ptrs = _as_list(grad_device_ptrs)
+            if len(ptrs) != self._batch.n_img:
+                raise ValueError("the new images do not fit the batch: %d given (%s)" % (len(ptrs), self._images_text()))
+            self._batch.set_images(device_ptrs=ptrs, next_frame=next_frame)
         else:
             imgs = list(grad_imgs) if isinstance(grad_imgs, (list, tuple)) else [grad_imgs]
+            if len(imgs) != self._batch.n_img or any(np.shape(g) != (self._batch.M, self._batch.N) for g in imgs):
+                raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
+                                 % (len(imgs), self._images_text(), self._batch.M, self._batch.N))
             self._batch.set_images([np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
-        obs = [np.array([])] * self.B if obs is None else list(obs)
+        if warm_every is not None:
+            self._batch.warm_start(warm_every)
+            obs = self._batch.read_obs_all()  # (what reset() sets again)
+        else:
+            obs = [np.array([])] * self.B if obs is None else list(obs)
         for e, p in enumerate(self._ps):
             p["obs"] = np.asarray(obs[e]).reshape(-1, 2).astype(np.int64)
             if seeds is not None:
                 p["seed"] = int(seeds[e])
         if seeds is not None:
             self.seeds = [int(v) for v in seeds]
-        self._set_obs()
+        if warm_every is None:
+            self._set_obs()
 
     def run_loop(self, max_iter=1000, chunk=64):
         """The device-resident while-loops of all edges (gpet.py:829-870); returns iterations per edge.

@@ -1,4 +1,5 @@
-"""Image-sequence tracing (BASELINE config 5): one edge followed through the frames of a sequence.
+"""Image-sequence tracing (BASELINE config 5): one edge, or the few edges of every frame, followed through the frames of a
+sequence.
 
 The reference traces one image per ``GP_Edge_Tracing`` object; a sequence is chained by the user through the
 constructor's ``obs`` argument (gp_edge_tracing/gpet.py:57-61, 100, 820): pixels of the previous frame's trace are the
@@ -9,6 +10,11 @@ A chain is serial by construction (frame t needs trace t-1).  Parallelism comes 
 of T frames is cut into C chains of consecutive frames, the first frame of every chain starting cold (SURVEY 8e);
 step s of all chains is one batch of C edges on the GPU (``GP_Edge_Tracing_Batch``, one image per edge), and chains
 spread over the GPUs of a node like independent edges do (``sharding.trace_sequence_sharded``).
+
+A frame often carries several edges (the layers of a retina, the two walls of a vessel): with E inits step s is one batch of
+C x E edges, chain-major, on C images -- the batch's image map says which edge reads which (``image_of``), so a frame is
+uploaded and prepared once.  From one step to the next the traces stay on the device: the warm start of every edge is made
+there from its own converged fit (``set_frame(..., warm_every=k)``, the rule of ``warm_start_obs`` below).
 """
 from __future__ import annotations
 
@@ -45,6 +51,20 @@ def warm_start_obs(edge_trace, x_st, x_en, warm_every, algo_thresh, M=None):
         step *= 2
 
 
+def _inits_of(init):
+    """(list of E (n_init, 2) arrays, multi): a 2-D array is ONE init (results as for one edge); a list / tuple or a 3-D array
+    holds E of them, which may span different columns."""
+    if isinstance(init, (list, tuple)):
+        inits = [np.asarray(i) for i in init]
+        if inits and inits[0].ndim == 1:  # (a nested list of points: one init)
+            return [np.asarray(init)], False
+        return inits, True
+    a = np.asarray(init)
+    if a.ndim == 3:
+        return [a[k] for k in range(a.shape[0])], True
+    return [a], False
+
+
 class SequenceTracer(object):
     """Traces ``init`` through ``frames`` (T gradient images of one shape) in ``n_chains`` chains on one GPU.
 
@@ -54,13 +74,21 @@ class SequenceTracer(object):
     ``gpet_utils.denoise`` of every frame, on the device in the same pass, with ``denoise=(technique, kwargs)``; ``seeds``: one seed per frame (default: ``seed`` for all, like a
     user re-creating ``GP_Edge_Tracing(..., seed=seed)`` per frame).  Remaining keyword arguments are the reference
     constructor's (gpet.py:22-35).  ``__call__`` returns the list of T results in frame order, each what
-    ``GP_Edge_Tracing.__call__`` returns for that frame (trace, or (trace, credible interval) with ``return_std``)."""
+    ``GP_Edge_Tracing.__call__`` returns for that frame (trace, or (trace, credible interval) with ``return_std``).
+
+    ``init``: one (n_init, 2) array -- or a list (or 3-D array) of E of them, the E edges of every frame, which may span
+    different columns.  Then every entry of the result is a list of E results, ``iterations[t]`` a list of E counts, and
+    edge k's results are what ``SequenceTracer(frames, init[k], ...)`` gives: the E edges of a frame share its seed."""
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
                  denoise=None, **kw):
         self.frames = frames
         self.T = len(frames)
-        self.init = np.asarray(init)
+        self.inits, self.multi = _inits_of(init)
+        if not self.inits:
+            raise ValueError("no init")
+        self.E = len(self.inits)
+        self.init = self.inits[0] if not self.multi else self.inits
         self.kw = dict(kw)
         self.kw.pop("obs", None)
         self.grad_kernel = grad_kernel
@@ -69,12 +97,11 @@ class SequenceTracer(object):
         self.denoise = denoise
         self.chains = chain_slices(self.T, n_chains)
         self.seeds = [int(seed)] * self.T if seeds is None else [int(v) for v in seeds]
-        p = resolve_params(self.init, np.asarray(frames[0]).shape, **{k: v for k, v in self.kw.items()
-                                                                      if k in ("kernel_options", "noise_y", "N_samples", "score_thresh",
-                                                                               "delta_x", "keep_ratio", "pixel_thresh", "return_std",
-                                                                               "fix_endpoints")})
-        self._p = p
-        self.warm_every = int(warm_every) if warm_every else 2 * p["delta_x"]
+        ctor = {k: v for k, v in self.kw.items() if k in ("kernel_options", "noise_y", "N_samples", "score_thresh", "delta_x",
+                                                           "keep_ratio", "pixel_thresh", "return_std", "fix_endpoints")}
+        self._ps = [resolve_params(i, np.asarray(frames[0]).shape, **ctor) for i in self.inits]
+        self._p = self._ps[0]
+        self.warm_every = int(warm_every) if warm_every else 2 * self._p["delta_x"]
         self.device, self._ctx = device, _ctx
         self.iterations = [0] * self.T
         self._tracer = None
@@ -84,40 +111,46 @@ class SequenceTracer(object):
 
     def __call__(self, max_iter=1000):
         results = [None] * self.T
-        prev = {}  # chain index -> previous edge trace
+        prev = {}  # (chain index, edge of the frame) -> previous edge trace
         n_steps = max(hi - lo for lo, hi in self.chains)
-        C = len(self.chains)
+        E = self.E
         for s in range(n_steps):
             active = [(c, lo + s) for c, (lo, hi) in enumerate(self.chains) if lo + s < hi]
-            obs = []
-            for c, f in active:
-                obs.append(np.zeros((0, 2), dtype=np.int64) if s == 0 else
-                           warm_start_obs(prev[c], self._p["x_st"], self._p["x_en"], self.warm_every, self._p["algo_thresh"],
-                                          self._p["M"]))
             imgs = [np.asarray(self.frames[f]) for _, f in active]
-            seeds = [self.seeds[f] for _, f in active]
-            if self._tracer is None or len(active) != self._tracer.B:
+            seeds = [self.seeds[f] for _, f in active for _ in range(E)]  # (chain-major: the E edges of a frame are adjacent)
+            if self._tracer is None or len(active) * E != self._tracer.B:
                 # (first step, or the shorter chains have run out: a smaller batch from here on; the old batch's arena,
-                # streams and events are released now, not whenever the garbage collector gets to them)
+                # streams and events are released now, not whenever the garbage collector gets to them.  The new batch's
+                # warm start comes from the traces on the host: the converged fits went with the old batch)
+                obs = []
+                for c, f in active:
+                    for k, p in enumerate(self._ps):
+                        obs.append(np.zeros((0, 2), dtype=np.int64) if s == 0 else
+                                   warm_start_obs(prev[c, k], p["x_st"], p["x_en"], self.warm_every, p["algo_thresh"], p["M"]))
                 if self._tracer is not None:
                     self._tracer._batch.close()
                 images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
                                                                                      grad_kernel=self.grad_kernel,
                                                                                      denoise=self.denoise)
-                self._tracer = GP_Edge_Tracing_Batch([self.init] * len(active), seeds=seeds, obs=obs, device=self.device,
-                                                     _ctx=self._ctx, **images, **self.kw)
+                # (several edges per frame: one image per chain, read by its E edges; one edge per frame is a batch with one
+                # image per edge, as ever)
+                image_of = [ci for ci in range(len(active)) for _ in range(E)] if E > 1 else None
+                self._tracer = GP_Edge_Tracing_Batch([i for _ in active for i in self.inits], seeds=seeds, obs=obs,
+                                                     device=self.device, _ctx=self._ctx, image_of=image_of, **images, **self.kw)
                 if self._ctx is None:
                     self._ctx = self._tracer._ctx
             elif self.grad_kernel is None:
-                self._tracer.set_frame(imgs, obs, seeds)
+                self._tracer.set_frame(imgs, None, seeds, warm_every=self.warm_every)
             else:
-                self._tracer.set_frame(None, obs, seeds, raw_imgs=imgs)
+                self._tracer.set_frame(None, None, seeds, raw_imgs=imgs, warm_every=self.warm_every)
             out = self._tracer(max_iter)
             iters = self._tracer.timings["iters"]
-            for k, (c, f) in enumerate(active):
-                results[f] = out[k]
-                self.iterations[f] = iters[k]
-                prev[c] = out[k][0] if self._tracer.return_std else out[k]
+            for ci, (c, f) in enumerate(active):
+                res = out[ci * E:(ci + 1) * E]
+                results[f] = list(res) if self.multi else res[0]
+                self.iterations[f] = list(iters[ci * E:(ci + 1) * E]) if self.multi else iters[ci * E]
+                for k in range(E):
+                    prev[c, k] = res[k][0] if self._tracer.return_std else res[k]
         return results
 
 

@@ -237,8 +237,25 @@ int gpet_batch_create_raw(gpet_ctx* ctx, int B, int M, int N, const void* const*
 int gpet_batch_create_raw_dn(gpet_ctx* ctx, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh,
                              int kw, const gpet_denoise* dn, int share_image, const gpet_params* params,
                              const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
+/* Batches with an image map: n_img images for B edges, edge e reads image image_of[e] -- a video frame or an OCT slice with
+ * several edges on it (the layers of a retina, the two walls of a vessel) is uploaded, turned into a gradient image, denoised
+ * and run through the gradient KDE (gpet.py:127) once, not once per edge.  1 <= n_img <= B, 0 <= image_of[e] < n_img, every
+ * image read by at least one edge; the edges of an image need not be adjacent ([0,1,2,0,1,2] is valid).  grad: n_img pointers
+ * as in gpet_batch_create2 (flags: GPET_GRAD_ON_DEVICE).  The batch equals, bit for bit, the one gpet_batch_create2 builds from
+ * the B images grad[image_of[e]]; n_img = 1 is the shared-image batch.  GPET_ERR_BAD_ARG (gpet_last_error names the cause) for
+ * a map that breaks one of the rules or a null image. */
+int gpet_batch_create_mapped(gpet_ctx* ctx, int B, int M, int N, int n_img, const int32_t* image_of, const float* const* grad,
+                             const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
+/* The same with the images given as n_img raw frames (raw, pix, kern as in gpet_batch_create_raw; flags: GPET_RAW_ON_DEVICE),
+ * denoised first if dn is not NULL (gpet_batch_create_raw_dn). */
+int gpet_batch_create_raw_mapped(gpet_ctx* ctx, int B, int M, int N, int n_img, const int32_t* image_of, const void* const* raw,
+                                 int pix, const double* kern, int kh, int kw, const gpet_denoise* dn, const gpet_params* params,
+                                 const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
 void gpet_batch_destroy(gpet_batch* b);
 int gpet_batch_size(const gpet_batch* b);
+/* Images the batch holds: 1 if it shares one image, B with one image per edge, n_img with an image map.  That many pointers
+ * gpet_batch_set_images, gpet_batch_set_raw_images and gpet_batch_set_raw_images_dn take. */
+int gpet_batch_image_count(const gpet_batch* b);
 /* out[0..count): Lg, S, n_keep, n_cap, factor_cap, z_cols, factor_rows_cap, n_bins, obs_cap, algo_thresh,
  * structured (1: the loop uses the prior-eigenbasis path), r0 (rank of the grid's correlation matrix), z_ring (slots
  * of pre-generated normals per edge), arena size of the batch in MiB */
@@ -249,8 +266,8 @@ int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count);
 int gpet_batch_reset(gpet_batch* b);
 
 /* New gradient image(s) for an existing batch of the same geometry and parameters -- the next frame of an image
- * sequence (gpet.py:57-61: a trace warm-starts the next one through `obs`): grad as in gpet_batch_create2 (one pointer
- * if the batch shares its image, else B), re-normalised, gradient KDE recomputed (gpet.py:97,127), then
+ * sequence (gpet.py:57-61: a trace warm-starts the next one through `obs`): grad as in gpet_batch_create2
+ * (gpet_batch_image_count(b) pointers: one if the batch shares its image, n_img with an image map, else B), re-normalised, gradient KDE recomputed (gpet.py:97,127), then
  * gpet_batch_reset.  The per-edge work that depends only on the geometry and the kernel (the prior eigenbasis of the
  * structured loop path) is kept. */
 int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int flags);
@@ -274,6 +291,20 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
 
 /* set / get the observation set (xy int64) of edge e (gpet.py:100,820,857). */
 int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs);
+/* The warm start of the next frame of a sequence (gpet.py:57-61) for every edge at once, on the device: edge e's new observation
+ * set is derived from its own last converged fit, which gpet_final_fit_all left in device memory -- call it after the images were
+ * swapped (gpet_batch_set_images with GPET_IMAGES_NEXT_FRAME), where gpet_batch_set_obs would be called.  The trace is
+ * rint(mean) on the edge's x-grid (the rounding of gpet_batch_results); candidates are the grid indices step, 2 step, ...
+ * < Lg - 1 with step = max(1, warm_every); a candidate with x_st < x < x_en and 0 <= y <= M - 1 is kept; while algo_thresh or
+ * more (and not zero) are kept -- the next trace's loop would not run, gpet.py:829 -- step is doubled.  The kept pixels are the
+ * observation set, (x, y) in ascending x.  The batch is then in the state B calls of gpet_batch_set_obs with those sets leave,
+ * after ONE wait instead of B.  n_obs_out (host, [B], may be NULL): the sizes of the sets.  GPET_ERR_BAD_ARG (with a message)
+ * when the last trace's converged fits are not there: on a fresh batch, and after gpet_batch_set_obs or a warm start without a
+ * trace in between. */
+int gpet_batch_warm_start(gpet_batch* b, int warm_every, int32_t* n_obs_out);
+/* GPET_OK when gpet_batch_warm_start would run now, else its GPET_ERR_BAD_ARG and message, with nothing touched: ask before
+ * gpet_batch_set_images, which cannot be undone once the warm start is refused. */
+int gpet_batch_warm_start_ready(gpet_batch* b);
 int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes);
 /* Writable: FACTOR (rows = factor rows; marks the factor as injected so gpet_gp_factor leaves
  * it alone), NORMALS, SAMPLES, COSTS, BEST_IDX, BEST_COSTS (a caller's own choice of best curves for
