@@ -601,6 +601,14 @@ int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
       HIPCHK(c, gpet_wait(c->stream));
       return GPET_OK;
     }
+    case GPET_BUF_FIN_OUT: {
+      // dense [2][Lg]: on the device the std half sits at the widest edge's stride (bd.Lg), whatever this edge's width
+      if (bytes < 2 * Lg * 8) return fail(c, GPET_ERR_BAD_ARG, "FIN_OUT read needs %zu bytes", 2 * Lg * 8);
+      HIPCHK(c, hipMemcpyAsync((char*)dst, E.fin_out, Lg * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync((char*)dst + Lg * 8, E.fin_out + b->bd.Lg, Lg * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, gpet_wait(c->stream));
+      return GPET_OK;
+    }
     case GPET_BUF_CHOL: {
       // compact n x n lower-triangular copy (upper part zeroed)
       if (bytes < n * n * 8) return fail(c, GPET_ERR_BAD_ARG, "CHOL read needs %zu bytes", n * n * 8);
@@ -684,6 +692,14 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
         else ((double*)tmp.data())[at] = in[i];
       }
       if (!tmp.empty()) HIPCHK(c, hipMemcpyAsync(E.Y, tmp.data(), tmp.size(), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, gpet_wait(c->stream));
+      return GPET_OK;
+    }
+    case GPET_BUF_FIN_OUT: {
+      // (dense [2][Lg] in; no state flag changes: have_results / have_last_fit stay as the last converged fit left them)
+      if (bytes != 2 * Lg * 8) return fail(c, GPET_ERR_BAD_ARG, "FIN_OUT write: expected %zu bytes", 2 * Lg * 8);
+      HIPCHK(c, hipMemcpyAsync(E.fin_out, src, Lg * 8, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(E.fin_out + b->bd.Lg, (const char*)src + Lg * 8, Lg * 8, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, gpet_wait(c->stream));
       return GPET_OK;
     }

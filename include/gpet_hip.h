@@ -95,8 +95,13 @@ typedef enum gpet_buf {
                              *                (gpet.py:235-238; sklearn_gpr.py:229-234), as gpet_final_fit_all built them */
   GPET_BUF_FIN_PAR = 21,  /* f64 [12]       optimum and transforms: constant, length_scale, noise_level, X_m, X_s, y_m,
                            *                y_s, m2, s2, 0, 0, 0 */
-  GPET_BUF_FIN_STARTS = 22  /* f64 [13][3]  theta0 + the 12 restart points of the last gpet_final_fit_all
+  GPET_BUF_FIN_STARTS = 22, /* f64 [13][3]  theta0 + the 12 restart points of the last gpet_final_fit_all
                              *                (gpet.py:244-245; sklearn_gpr.py:283-288) */
+  GPET_BUF_FIN_OUT = 23   /* f64 [2][Lg]    converged fit's output block: posterior mean in pixels, then std in standardised
+                           *                units (gpet.py:266), as gpet_final_fit_all left them -- what gpet_batch_results and
+                           *                gpet_batch_warm_start read.  Writable (tests inject fits no scene produces): exactly
+                           *                2 * Lg * 8 bytes; a write changes no state flag, so a record or a warm start after it
+                           *                reads the written values where the last converged fit allowed one */
 } gpet_buf;
 
 /* Per-edge scalar state kept on the device (GPET_BUF_SCALARS). */
