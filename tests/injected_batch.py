@@ -1,0 +1,28 @@
+"""Batches for the tests that inject a stage's inputs (tests/test_gpu_sample_gemm_exact.py, tests/test_gpu_score_injected.py).
+
+They come from the constructor's own parameter functions (gpet.resolve_params, gpet.to_abi_params) and _lib.Batch rather than
+from GP_Edge_Tracing: the constructor, like the reference's, turns N_samples <= 100 into 1000, and these tests need the exact
+count -- 63 sample rows for a row block that is not full, 40 for the wave-per-curve scorer.  Sample counts below 101 are
+therefore reachable through the C ABI only, never through the Python constructor."""
+import numpy as np
+
+KERNEL = {'kernel': 'RBF', 'sigma_f': 2, 'length_scale': 10}
+
+
+def make_batch(amd, ctx, grad, spans, S, factor_cap=0, z_cols=0, sample_dtype=None):
+    """A batch of the edges spans = [(x_st, Lg)] on the one image grad with S samples per edge, of any S >= 1."""
+    from gaussian_process_edge_trace_amd.gpet import resolve_params, to_abi_params
+    rows = grad.shape[0]
+    params, inits = [], []
+    for x_st, Lg in spans:
+        init = np.array([[x_st, 1], [x_st + Lg - 1, rows - 2]])
+        p = resolve_params(init, grad.shape, KERNEL, noise_y=1, N_samples=max(S, 101), score_thresh=1, delta_x=5, keep_ratio=0.25,
+                           pixel_thresh=2, seed=1, fix_endpoints=True)
+        q = to_abi_params(p, factor_cap=factor_cap, z_cols=z_cols)
+        q.n_samples, q.n_keep = S, max(1, S // 4)
+        params.append(q)
+        inits.append(p["init"])
+    b = amd._lib.Batch(ctx, [grad], params, inits, share_image=len(spans) > 1)
+    if sample_dtype is not None:
+        b.set_sample_dtype(sample_dtype)
+    return b
