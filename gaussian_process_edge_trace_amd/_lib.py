@@ -157,6 +157,102 @@ def decode_results(raw, n, len_cap):
     return {k: np.array(rec[k]) for k in dt.names}
 
 
+# iteration history (gpet_batch_set_history): what a record holds beyond its head
+HISTORY_LEVELS = {None: 0, "off": 0, "obs": 1, "curves": 2, "full": 3}
+
+
+class GpetHistoryPlan(C.Structure):
+    """gpet_history_plan: sizes and offsets of a batch's iteration history (gpet_history_layout)."""
+    _fields_ = [("level", C.c_int32), ("iter_cap", C.c_int32), ("obs_cap", C.c_int32), ("len_cap", C.c_int32),
+                ("edge_bytes", C.c_int64), ("record_bytes", C.c_int64), ("off_records", C.c_int64), ("off_obs", C.c_int64),
+                ("off_curve", C.c_int64), ("off_mean", C.c_int64), ("off_std", C.c_int64)]
+
+
+class GpetHistoryEdgeHead(C.Structure):
+    """gpet_history_edge_head: in front of every edge's records."""
+    _fields_ = [("n_rec", C.c_int32), ("dropped", C.c_int32), ("n_iter", C.c_int32), ("edge_len", C.c_int32)]
+
+
+class GpetHistoryHead(C.Structure):
+    """gpet_history_head: the head of one iteration's record."""
+    _fields_ = [("iter", C.c_int32), ("n_obs", C.c_int32), ("best_idx", C.c_int32), ("rank", C.c_int32),
+                ("n_removed", C.c_int32), ("reserved", C.c_int32), ("score_thresh", C.c_double),
+                ("optimal_cost", C.c_double), ("y_s", C.c_double)]
+
+
+def history_level(level):
+    """0..3 of None / 'obs' / 'curves' / 'full' (or the number itself); ValueError for anything else."""
+    if isinstance(level, (int, np.integer)) and not isinstance(level, bool) and 0 <= int(level) <= 3:
+        return int(level)
+    if level is None or (isinstance(level, str) and level in HISTORY_LEVELS):
+        return HISTORY_LEVELS[level]
+    raise ValueError("history must be None, 'obs', 'curves' or 'full', not %r" % (level,))
+
+
+def history_plan(level, iter_cap, obs_cap, len_cap):
+    """The layout csrc/gpet_history_plan.h computes (the library reports its own through gpet_history_layout): for hosts and
+    tests that build or decode a history without a device."""
+    level, iter_cap, obs_cap, len_cap = int(level), int(iter_cap), int(obs_cap), int(len_cap)
+    if not (1 <= level <= 3 and iter_cap >= 1 and obs_cap >= 1 and len_cap >= 1):
+        raise ValueError("no history for level=%d iter_cap=%d obs_cap=%d len_cap=%d" % (level, iter_cap, obs_cap, len_cap))
+    p = GpetHistoryPlan(level=level, iter_cap=iter_cap, obs_cap=obs_cap, len_cap=len_cap)
+    p.off_records = C.sizeof(GpetHistoryEdgeHead)
+    off = p.off_obs = C.sizeof(GpetHistoryHead)
+    off += 8 * obs_cap
+    if level >= 2:
+        p.off_curve = off
+        off += 8 * len_cap
+    if level >= 3:
+        p.off_mean = off
+        p.off_std = off + 8 * len_cap
+        off += 16 * len_cap
+    p.record_bytes = off
+    p.edge_bytes = p.off_records + iter_cap * off
+    return p
+
+
+def decode_history(raw, layout, lens, obs_caps, x_sts=None):
+    """The iteration histories of ``len(lens)`` edges from the bytes gpet_batch_history returns (include/gpet_hip.h,
+    "iteration history"); plain numpy, no device.  ``layout``: the GpetHistoryPlan of the batch; ``lens`` / ``obs_caps``: every
+    edge's own grid length and observation capacity; ``x_sts``: every edge's first grid column (default 0), the x of the curves.
+    One dict per edge: ``n_iter`` (records kept), ``dropped``, ``obs`` (list of (n, 2) int64 xy), ``n_obs``, ``score_thresh``,
+    ``optimal_cost``, ``best_idx``, ``rank``, ``n_removed``, ``y_s`` (arrays of n_iter); from level 2 ``optimal_curves`` (list of
+    (Lg, 2) float64 xy, like the reference's iter_optimal_curves); with level 3 ``mean`` and ``std`` (n_iter, Lg)."""
+    P = layout
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    n = len(lens)
+    if buf.size < n * P.edge_bytes:
+        raise ValueError("history of %d edges needs %d bytes, got %d" % (n, n * P.edge_bytes, buf.size))
+    head = np.dtype([("iter", "<i4"), ("n_obs", "<i4"), ("best_idx", "<i4"), ("rank", "<i4"), ("n_removed", "<i4"),
+                     ("reserved", "<i4"), ("score_thresh", "<f8"), ("optimal_cost", "<f8"), ("y_s", "<f8")])
+    assert head.itemsize == C.sizeof(GpetHistoryHead) == P.off_obs and C.sizeof(GpetHistoryEdgeHead) == P.off_records
+    out = []
+    for e in range(n):
+        reg = buf[e * P.edge_bytes:(e + 1) * P.edge_bytes]
+        n_rec, dropped = (int(v) for v in reg[:8].view("<i4"))
+        n_rec = max(0, min(n_rec, P.iter_cap))
+        recs = reg[P.off_records:P.off_records + n_rec * P.record_bytes].reshape(n_rec, P.record_bytes)
+        Lg, x0 = int(lens[e]), 0 if x_sts is None else int(x_sts[e])
+        h = np.ascontiguousarray(recs[:, :P.off_obs]).view(head).reshape(n_rec)
+
+        def sect(off, count, dt):
+            return np.ascontiguousarray(recs[:, off:off + count * np.dtype(dt).itemsize]).view(dt).reshape(n_rec, count)
+        obs = sect(P.off_obs, 2 * P.obs_cap, "<i4").reshape(n_rec, P.obs_cap, 2).astype(np.int64)
+        d = dict(n_iter=n_rec, dropped=dropped,
+                 obs=[obs[i, :max(0, min(int(h["n_obs"][i]), int(obs_caps[e]), P.obs_cap))] for i in range(n_rec)])
+        for k in ("n_obs", "score_thresh", "optimal_cost", "best_idx", "rank", "n_removed", "y_s"):
+            d[k] = np.array(h[k])
+        if P.level >= 2:
+            x = (x0 + np.arange(Lg)).astype(np.float64)
+            cur = sect(P.off_curve, P.len_cap, "<f8")
+            d["optimal_curves"] = [np.stack((x, cur[i, :Lg]), -1) for i in range(n_rec)]
+        if P.level >= 3:
+            d["mean"] = sect(P.off_mean, P.len_cap, "<f8")[:, :Lg].copy()
+            d["std"] = sect(P.off_std, P.len_cap, "<f8")[:, :Lg].copy()
+        out.append(d)
+    return out
+
+
 def pix_code(dtype):
     """GPET_PIX_* of a numpy dtype (or its name); ValueError for a dtype the device does not read."""
     dt = np.dtype(dtype)
@@ -321,6 +417,10 @@ SYMBOLS = {
     "gpet_result_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "gpet_batch_results": (C.c_int, [_P, C.c_int64, _P, C.c_int]),
     "gpet_gather_results": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    "gpet_batch_set_history": (C.c_int, [_P, C.c_int, C.c_int]),
+    "gpet_history_layout": (C.c_int, [_P, C.POINTER(GpetHistoryPlan)]),
+    "gpet_batch_history": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),
+    "gpet_history_record": (C.c_int, [_P]),
 }
 COMM_ID_BYTES = 128
 
@@ -682,6 +782,7 @@ class Batch:
         self.n_img = self.lib.gpet_batch_image_count(h)  # images the batch holds: 1 shared, B own, or the map's
         self.image_of = image_of
         self._keep = (grads, inits)
+        self._x_st = [int(p.x_st) for p in params]
 
     def set_images(self, grads=None, device_ptrs=None, next_frame=False, raw=None):
         """New gradient image(s) for the same edges, gradient KDE recomputed, loop state reset (gpet_batch_set_images).
@@ -858,6 +959,32 @@ class Batch:
         raw = np.empty(max(1, self.B * result_bytes(L)), dtype=np.uint8)
         self.ctx.check(self.lib.gpet_batch_results(self.h, L, raw.ctypes.data, 0))
         return decode_results(raw, self.B, L)
+
+    def set_history(self, level, iter_cap=64):
+        """Iteration history of the traces this batch runs (gpet_batch_set_history): ``level`` None / 'obs' / 'curves' / 'full'
+        (or 0..3), ``iter_cap`` records per edge.  None frees the storage."""
+        self.ctx.check(self.lib.gpet_batch_set_history(self.h, history_level(level), int(iter_cap)))
+
+    def history_layout(self):
+        p = GpetHistoryPlan()
+        self.ctx.check(self.lib.gpet_history_layout(self.h, C.byref(p)))
+        return p
+
+    def history_record(self):
+        """gpet_history_record: the history kernel once on what the buffers hold (tests inject their own)."""
+        self.ctx.check(self.lib.gpet_history_record(self.h))
+
+    def history(self):
+        """The iteration history of the current trace, one dict per edge (decode_history): one copy, one wait.  GpetError
+        (ERR_STATE) when the batch keeps none."""
+        p = self.history_layout()
+        raw = np.empty(self.B * p.edge_bytes, dtype=np.uint8)
+        self.ctx.check(self.lib.gpet_batch_history(self.h, -1, raw.ctypes.data, raw.nbytes, 0))
+        cache = self.__dict__.setdefault("_hist_dims", None)
+        if cache is None:
+            inf = [self.info(e) for e in range(self.B)]
+            cache = self._hist_dims = ([i["Lg"] for i in inf], [i["obs_cap"] for i in inf])
+        return decode_history(raw, p, cache[0], cache[1], self._x_st)
 
     def set_option(self, name, value):
         """This batch's own copy of a tuning switch (gpet_batch_set_option); returns the previous value (-1 = automatic)."""

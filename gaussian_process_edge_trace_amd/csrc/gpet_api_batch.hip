@@ -354,6 +354,7 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->d_fin_stage) (void)hipFree(b->d_fin_stage);
   if (b->d_fin_n) (void)hipFree(b->d_fin_n);
   if (b->d_results) (void)hipFree(b->d_results);
+  if (b->d_hist) (void)hipFree(b->d_hist);
   if (b->fit) {
     (void)hipStreamSynchronize(b->fit);
     (void)hipStreamDestroy(b->fit);
@@ -490,6 +491,8 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
     if (rc3) return rc3;
   }
   b->iters_issued = 0;   // (all edges of a batch are restarted together)
+  int rc4 = history_clear(b, e);  // (the history is the trace's that ends here)
+  if (rc4) return rc4;
   if ((int)b->h_nobs_prev.size() != b->B) b->h_nobs_prev.assign(b->B, 0);
   b->h_nobs_prev[e] = n_obs;  // (a batch of up to 64 edges sizes the loop's groups by the growth of its observation sets from here: next_group)
   b->norm_issued = 0;
@@ -525,6 +528,8 @@ int gpet_batch_warm_start(gpet_batch* b, int warm_every, int32_t* n_obs_out) {
   if (ready) return ready;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, launch_warm_start(c->stream, b->d_edges, b->B, warm_every));
+  const int rc_h = history_clear(b, -1);
+  if (rc_h) return rc_h;
   b->have_results = false;
   b->have_last_fit = false;
   b->iters_issued = 0;
@@ -796,6 +801,8 @@ static int batch_reset(gpet_batch* b, bool next_frame) {
     }
   }
   HIPCHK(c, upload_pristine_scalars(b));
+  const int rc_h = history_clear(b, -1);
+  if (rc_h) return rc_h;
   HIPCHK(c, gpet_wait(c->stream));
   return GPET_OK;
 }

@@ -20,6 +20,9 @@
 //   gpet_api_comm.hip    multi-GPU helpers on RCCL (8e): communicator, broadcast of the gradient image, gather of the traces
 //                        and of the result records
 //   gpet_api_results.hip the finished result record of every edge (k_finish_results): gpet_result_bytes, gpet_batch_results
+//   gpet_api_history.hip the iteration history (k_history): gpet_batch_set_history, gpet_history_layout, gpet_batch_history,
+//                        gpet_history_record
+//   gpet_history_plan.h  the history's record layout and storage size as plain data (no HIP)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -145,6 +148,10 @@ struct gpet_batch {
   bool have_last_fit = false;
   char* d_results = nullptr;           // device staging of gpet_batch_results into host memory (grown on demand)
   size_t results_bytes = 0;
+  // iteration history (gpet_batch_set_history): storage of its own, B regions of hist.edge_bytes (gpet_history_plan.h); hist.level == 0
+  // and d_hist == nullptr: off -- the loop then enqueues nothing for it
+  char* d_hist = nullptr;
+  gpet_history_plan hist{};
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it
 };
 // first statement of every entry point that works on a batch: its option table for the calling thread
@@ -193,6 +200,9 @@ size_t result_record_bytes(int64_t len_cap);
 // the records of every edge of b into DEVICE memory d_dst on the context's stream (no wait); fails (GPET_ERR_BAD_ARG, message
 // set) before a converged fit of the current trace or when len_cap is below the batch's widest edge
 int enqueue_results(gpet_batch* b, int64_t len_cap, void* d_dst);
+// ---- gpet_api_history.hip -------------------------------------------------------------------------------------------------
+// empties the iteration history of edge e (e < 0: of every edge) on the context's stream: whatever starts another trace calls it
+int history_clear(gpet_batch* b, int e);
 // ---- gpet_api_batch.hip ---------------------------------------------------------------------------------------------------
 int fetch_all_scalars(gpet_batch* b);
 int check_device_status(gpet_batch* b);

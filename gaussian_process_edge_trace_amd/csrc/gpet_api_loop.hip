@@ -169,6 +169,8 @@ struct Loop {
     }
     HIPCHK(c, launch_pixels(c->stream, edges_l, B_l, b->bd, 1));
     HIPCHK(c, hipEventRecord(b->ev_pix[cur % 16], c->stream));
+    // opt-in history: the record of this iteration for the edges that completed it (their counter is now iters_issued + 1)
+    if (b->d_hist) HIPCHK(c, launch_history(c->stream, edges_l, B_l, b->hist, b->iters_issued + 1));
     b->iters_issued += 1;
     return GPET_OK;
   }

@@ -102,6 +102,7 @@ struct EdgeDev {
   // the matrix-core objective k_lml16 tabulates the correlation at the lags 0..lagmax
   double* fin_par;       // [12]
   double* fin_out;       // [2 * Lg_max] mean (pixels) then std, in the batch's contiguous output block
+  char* hist;            // this edge's region of the iteration history (gpet_history_plan.h), outside the arena; nullptr: history off
 };
 
 }  // namespace gpet

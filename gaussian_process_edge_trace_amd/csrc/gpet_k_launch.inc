@@ -775,4 +775,10 @@ hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims
   return hipGetLastError();
 }
 
-
+hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const gpet_history_plan& P, int iter_expect) {
+  (void)hipGetLastError();
+  // (the waves beyond four only serve the statistics of level 3: heads, observations and curve are a few hundred stores per edge)
+  const int threads = (P.level >= 3 ? HISTORY_WAVES : 4) * WAVE;
+  hipLaunchKernelGGL(k_history, dim3(history_tiles(P.level, P.len_cap), B), dim3(threads), 0, st, d_edges, P, iter_expect);
+  return hipGetLastError();
+}

@@ -26,6 +26,7 @@ namespace gpet {
 #include "gpet_k_kde_pix.inc"
 #include "gpet_k_lml.inc"
 #include "gpet_k_warm.inc"
+#include "gpet_k_history.inc"
 #include "gpet_k_launch.inc"
 
 }  // namespace gpet

@@ -110,12 +110,14 @@ class GP_Edge_Tracing(object):
 
     Keywords beyond the reference's signature (keyword-only): ``device``, ``stream``, ``factor_cap``, ``z_cols``,
     ``sample_dtype`` ("f32": samples stored in single precision) and ``rng`` ("philox": counter-based generator) --
-    the last two are opt-in modes outside the reference-parity statements."""
+    the last two are opt-in modes outside the reference-parity statements -- and ``history`` ('obs', 'curves' or 'full') with
+    ``history_cap``: what ``return_lines=True`` collects per iteration is recorded on the device instead, the loop runs in
+    its normal groups without a wait per iteration, and ``history()`` returns it after ``__call__``."""
 
     def __init__(self, init, grad_img, kernel_options=(1, 3, 3), noise_y=1, obs=np.array([], dtype=np.int8),
                  N_samples=500, score_thresh=1, delta_x=20, keep_ratio=0.1, pixel_thresh=5, seed=42,
                  return_std=False, fix_endpoints=True, *, device=0, stream=None, factor_cap=0, z_cols=0,
-                 sample_dtype=None, rng=None, _ctx=None):
+                 sample_dtype=None, rng=None, history=None, history_cap=64, _ctx=None):
         p = resolve_params(init, np.asarray(grad_img).shape, kernel_options, noise_y, obs, N_samples, score_thresh,
                            delta_x, keep_ratio, pixel_thresh, seed, return_std, fix_endpoints)
         self._p = p
@@ -135,6 +137,9 @@ class GP_Edge_Tracing(object):
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:  # ("philox": the counter-based generator instead of numpy's RandomState stream)
             self._batch.set_rng(rng)
+        self._history = _lib.history_level(history)
+        if self._history:  # (keyword beyond the reference's signature: per-iteration records kept on the device, see history())
+            self._batch.set_history(self._history, history_cap)
         self.grad_img = self._batch.read(_lib.BUF_GRAD).astype(np.float64)
         self._n_iter = 0
 
@@ -263,6 +268,12 @@ class GP_Edge_Tracing(object):
         self.score_thresh = b.scalars().score_thresh
         return b.read(_lib.BUF_OBS)
 
+    def history(self):
+        """The iteration history of the last ``__call__`` (constructor keyword ``history``): the dict ``_lib.decode_history``
+        gives for this edge -- ``obs``, ``score_thresh``, ``optimal_cost``, ``best_idx`` per iteration, from 'curves'
+        ``optimal_curves``, with 'full' ``mean`` and ``std`` of the samples per column.  GpetError without ``history``."""
+        return self._batch.history()[0]
+
     def __call__(self, print_final_diagnostics=False, show_init_post=False, show_post_iter=False, verbose=False,
                  return_lines=False, max_iter=1000):
         """Runs the trace (gpet.py:768-908).  The while-loop of the reference (gpet.py:829-870)
@@ -279,7 +290,8 @@ class GP_Edge_Tracing(object):
         while not b.scalars().done:
             if n_iter >= max_iter:
                 raise _lib.GpetError(_lib.ERR_ITER_CAP, f"trace did not converge in {max_iter} iterations")
-            step = min(1 if (return_lines or verbose) else 4, max_iter - n_iter)
+            # (with a device history and nothing to show per iteration: whole groups, the loop returns when the edge is done)
+            step = min(1 if (return_lines or verbose) else (64 if self._history else 4), max_iter - n_iter)
             st = t.time()
             if verbose:
                 print('Fitting Gaussian process and computing next set of observations...')
@@ -296,6 +308,7 @@ class GP_Edge_Tracing(object):
                 print(f'Number of observations: {s.n_obs}')
                 print(f'Iteration {n_iter + 1} - Time Elapsed: {round(t.time() - st, 4)}\n\n')
         self._n_iter = n_iter
+        self.iter_optimal_costs = iter_optimal_costs  # (with return_lines: best_costs[0] of every iteration, gpet.py:449)
         pre_fobs = b.read(_lib.BUF_OBS)
         self.score_thresh = b.scalars().score_thresh
         # final hyper-parameter-optimised fit (gpet.py:874-876), seed = seed + N_iter; on the device
@@ -424,7 +437,7 @@ class GP_Edge_Tracing_Batch(object):
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
-                 denoise=None, image_of=None):
+                 denoise=None, image_of=None, history=None, history_cap=64):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -443,7 +456,12 @@ class GP_Edge_Tracing_Batch(object):
         ``raw_device_ptrs`` are then ``n_img = max(image_of) + 1`` long instead of B, every index must occur (in any order:
         ``[0, 1, 2, 0, 1, 2]`` is valid), and ``set_frame`` expects ``n_img`` images.  Every image is uploaded, turned into a
         gradient image, denoised and run through the gradient KDE once; the batch equals the one built from the B images
-        ``imgs[image_of[e]]`` bit for bit."""
+        ``imgs[image_of[e]]`` bit for bit.
+        ``history`` = 'obs', 'curves' or 'full' (default None: off): every loop iteration of every edge leaves a record on the
+        device -- the new observation set, the score threshold, the optimal cost and sample index; from 'curves' the optimal
+        curve; with 'full' the per-column mean and std of all samples -- read with ``history()`` after ``run_loop`` or
+        ``__call__``.  ``history_cap``: records kept per edge; later iterations are counted in ``dropped``, the trace is not
+        affected.  No result depends on the level."""
         B = len(inits)
         if image_of is not None:
             image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
@@ -498,6 +516,8 @@ class GP_Edge_Tracing_Batch(object):
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
             self._batch.set_rng(rng)
+        if _lib.history_level(history):
+            self._batch.set_history(history, history_cap)
         self._set_obs()
         self.B = B
         self.return_std = return_std
@@ -618,6 +638,12 @@ class GP_Edge_Tracing_Batch(object):
             et = np.rint(curve[:, [1, 0]]).astype(int)
             out.append((et, (mean - 1.96 * std, mean + 1.96 * std)) if self.return_std else et)
         return out
+
+    def history(self):
+        """The iteration history of the current trace (constructor keyword ``history``), one dict per edge as
+        ``_lib.decode_history`` returns it; valid after ``run_loop`` or ``__call__``.  ``reset()``, ``set_frame`` and new
+        observations empty it.  GpetError (ERR_STATE) when the batch was built without ``history``."""
+        return self._batch.history()
 
     def results(self):
         """What ``finish`` returned for every edge, recomputed on the device from the converged fits it left there

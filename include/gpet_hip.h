@@ -353,6 +353,72 @@ int gpet_select_pixels_only(gpet_batch* b);
  * launched over the edges still running only.  Returns the number of edges still not done in *n_active. */
 int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters, int* n_active);
 
+/* ---- iteration history: what __call__(return_lines=True) returns per iteration (gpet.py:840-866), kept on the device --------
+ * Opt-in.  With a history enabled, gpet_trace_iterate runs one more kernel per iteration (k_history, after the pixel selection,
+ * on the context's stream) that appends ONE record for every edge that completed that iteration, at slot iter - 1 of the edge's
+ * region; nothing waits on the host and no sample matrix travels.  With it off (the default) the loop enqueues exactly what it
+ * enqueued before, and no result depends on the level either way.
+ * Storage: one device allocation of its own, B regions of edge_bytes, in one fixed layout that a host in any language decodes
+ * with the numbers of gpet_history_plan:
+ *   region = gpet_history_edge_head | record[iter_cap]                              (records at off_records + k * record_bytes)
+ *   record = gpet_history_head                                                       the scalars after the iteration
+ *          | int32 obs[obs_cap][2]        at off_obs    the new observation set, xy, as the pixel selection left it (gpet.py:857)
+ *          | f64 curve[len_cap]           at off_curve  level >= 2: the optimal curve = sample row best_idx (gpet.py:443-449),
+ *                                                       widened exactly from f32 under gpet_batch_set_sample_dtype
+ *          | f64 mean[len_cap]            at off_mean   level 3: per-column mean of all S samples          (gpet.py:687)
+ *          | f64 std[len_cap]             at off_std    level 3: per-column population std (np.std)       (gpet.py:688)
+ *   obs_cap / len_cap are the batch's largest observation capacity / widest edge; entries past an edge's own n_obs / edge
+ *   length are zero, and so are records past n_rec.  The statistics are two passes in f64 without contraction, rows summed in
+ *   a fixed partition and order: edge e's values do not depend on the batch around it.
+ * iter_cap: an edge that runs past iter_cap iterations traces on unchanged; its later records are dropped and counted in
+ *   `dropped` (nothing is overwritten, no error).
+ * Lifetime: the history is the current trace's.  gpet_batch_reset, gpet_batch_set_images (and the raw forms) and
+ *   gpet_batch_warm_start empty every edge's region, gpet_batch_set_obs empties edge e's. */
+/* (named _plan, not _layout: C keeps typedef names and functions in one name space, and the call below is gpet_history_layout) */
+typedef struct gpet_history_plan {
+  int32_t level;        /* 1 'obs', 2 'curves', 3 'full' */
+  int32_t iter_cap;     /* records per edge */
+  int32_t obs_cap;      /* observation pairs per record */
+  int32_t len_cap;      /* points per curve / mean / std section */
+  int64_t edge_bytes;   /* one edge's region: off_records + iter_cap * record_bytes */
+  int64_t record_bytes;
+  int64_t off_records;  /* in the region: the first record (= sizeof(gpet_history_edge_head)) */
+  int64_t off_obs;      /* in a record: the observation pairs (= sizeof(gpet_history_head)) */
+  int64_t off_curve;    /* in a record; 0 below level 2 */
+  int64_t off_mean;     /* in a record; 0 below level 3 */
+  int64_t off_std;      /* in a record; 0 below level 3 */
+} gpet_history_plan;
+typedef struct gpet_history_edge_head {  /* one per edge, followed by its records */
+  int32_t n_rec;     /* records kept: min(iterations recorded, iter_cap) */
+  int32_t dropped;   /* iterations that found no slot left */
+  int32_t n_iter;    /* iteration count of the edge at its last record (= n_rec + dropped after a loop) */
+  int32_t edge_len;  /* points of this edge's x-grid (0 until the first record) */
+} gpet_history_edge_head;
+typedef struct gpet_history_head {  /* one per record, followed by its sections */
+  int32_t iter;         /* the iteration, 1-based                                     gpet.py:865 */
+  int32_t n_obs;        /* observations after it                                      gpet.py:861 */
+  int32_t best_idx;     /* index of the optimal curve among the samples (best_idx[0]) gpet.py:443 */
+  int32_t rank;         /* rows of the factor the samples were drawn from */
+  int32_t n_removed;    /* curve points outside the image                             gpet.py:498-500 */
+  int32_t reserved;
+  double score_thresh;  /* after the iteration                                        gpet.py:595 */
+  double optimal_cost;  /* best_costs[0]                                              gpet.py:449 */
+  double y_s;           /* std(y) + 1 of the iteration's fit                          gpet.py:228 */
+} gpet_history_head;
+/* level 0: off, the storage is freed; 1..3: (re)allocate for iter_cap records per edge, zeroed, and point the edges at it.
+ * GPET_ERR_BAD_ARG for another level or iter_cap < 1.  Call between traces, not while a loop is enqueued. */
+int gpet_batch_set_history(gpet_batch* b, int level, int iter_cap);
+/* the numbers above for this batch; GPET_ERR_STATE when the history is off */
+int gpet_history_layout(gpet_batch* b, gpet_history_plan* out);
+/* Edge e's region (edge_bytes), or with e = -1 all B regions (B * edge_bytes), into host memory (dst_on_device = 0: complete on
+ * return) or device memory (1: enqueued on the context's stream): one copy, one wait.  `bytes` is the room at dst.
+ * GPET_ERR_STATE when the history is off, GPET_ERR_BAD_ARG when dst is too small. */
+int gpet_batch_history(gpet_batch* b, int e, void* dst, size_t bytes, int dst_on_device);
+/* The history kernel once, alone, on whatever the buffers hold now (GPET_BUF_SAMPLES, _BEST_IDX, _BEST_COSTS, _OBS, _SCALARS):
+ * every edge whose iteration count is at least 1 gets the record of slot iter - 1 (re)written -- a per-stage entry point like
+ * gpet_select_pixels_only, there so that tests can inject inputs no scene produces.  GPET_ERR_STATE when the history is off. */
+int gpet_history_record(gpet_batch* b);
+
 /* ---- f2: converged fit (gpet.py:232-248; sklearn_gpr.py:254-295, 475-585) ----------------- */
 /* Upload edge e's standardised training set (x, y standardised as gpet.py:235-238 and
  * sklearn_gpr.py:229-234 do; w = per-point noise weights), n <= the batch's training-set capacity (register-tile objective
