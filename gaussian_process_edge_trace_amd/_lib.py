@@ -398,6 +398,7 @@ SYMBOLS = {
     "gpet_final_fit_all": (C.c_int, [_P, C.POINTER(C.c_uint32), _P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     "gpet_final_optimize": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int32)]),
     "gpet_batch_set_sample_dtype": (C.c_int, [_P, C.c_int]),
+    "gpet_batch_set_sample_arith": (C.c_int, [_P, C.c_int]),
     "gpet_batch_set_rng": (C.c_int, [_P, C.c_int]),
     "gpet_batch_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "gpet_batch_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int)]),
@@ -423,6 +424,7 @@ SYMBOLS = {
     "gpet_history_record": (C.c_int, [_P]),
 }
 COMM_ID_BYTES = 128
+SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
 
 _lib = None
 
@@ -1007,11 +1009,17 @@ class Batch:
         self.ctx.check(self.lib.gpet_batch_set_rng(self.h, 1 if rng == "philox" else 0))
 
     def set_sample_dtype(self, dtype):
-        """Storage type of the posterior samples: "f64" (default, the reference's) or "f32" (gpet_batch_set_sample_dtype:
-        the GEMM rounds on store, consumers widen; opt-in, BASELINE config 2's "fp32 posterior samples")."""
-        if dtype not in (None, "f64", "f32", "float64", "float32"):
-            raise ValueError("sample_dtype must be 'f64' or 'f32'")
-        self.ctx.check(self.lib.gpet_batch_set_sample_dtype(self.h, 1 if dtype in ("f32", "float32") else 0))
+        """Type of the posterior samples: "f64" (default, the reference's), "f32" (gpet_batch_set_sample_dtype: the GEMM
+        multiplies in f64 and rounds on store, consumers widen; opt-in, BASELINE config 2's "fp32 posterior samples") or
+        "f32mma" (gpet_batch_set_sample_arith: f32 storage AND the GEMM on the f32 matrix cores -- per sample a k-ascending
+        chain of fmaf over the narrowed normals and factor, then (acc + mean) * y_s in f64; include/gpet_hip.h has the
+        definition, tests/f32_chain.py evaluates it; opt-in, not the reference's numbers)."""
+        if dtype not in (None, "f64", "f32", "f32mma", "float64", "float32"):
+            raise ValueError("sample_dtype must be 'f64', 'f32' or 'f32mma'")
+        if dtype == "f32mma":
+            self.ctx.check(self.lib.gpet_batch_set_sample_arith(self.h, SAMPLE_ARITH_F32))
+        else:  # (sets the arithmetic back to f64 as well)
+            self.ctx.check(self.lib.gpet_batch_set_sample_dtype(self.h, 1 if dtype in ("f32", "float32") else 0))
 
     def final_optimize(self, starts, bounds):
         """Device L-BFGS-B on the training sets of final_set_training(_all) (gpet_final_optimize): starts

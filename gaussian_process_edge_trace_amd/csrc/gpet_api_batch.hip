@@ -761,8 +761,25 @@ int gpet_batch_set_sample_dtype(gpet_batch* b, int f32) {
   const int v = f32 ? 1 : 0;
   for (int e = 0; e < b->B; ++e) b->h_edges[e].y_f32 = v;
   b->bd.y_f32 = v;
+  b->bd.y_arith = GPET_SAMPLE_ARITH_F64;  // (no batch holds f64 storage with f32 arithmetic)
   HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * (size_t)b->B, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, gpet_wait(c->stream));
+  b->have_samples = false;
+  return GPET_OK;
+}
+
+int gpet_batch_set_sample_arith(gpet_batch* b, int arith) {
+  GPET_BATCH_SCOPE(b);
+  if (!b || (arith != GPET_SAMPLE_ARITH_F64 && arith != GPET_SAMPLE_ARITH_F32)) return GPET_ERR_BAD_ARG;
+  if (arith == GPET_SAMPLE_ARITH_F32) {  // the storage goes with it
+    const int rc = gpet_batch_set_sample_dtype(b, 1);
+    if (rc != GPET_OK) return rc;
+  }
+  gpet_ctx* c = b->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gpet_wait(c->stream));
+  if (b->side) HIPCHK(c, gpet_wait(b->side));
+  b->bd.y_arith = arith;
   b->have_samples = false;
   return GPET_OK;
 }

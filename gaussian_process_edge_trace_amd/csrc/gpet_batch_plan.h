@@ -18,6 +18,7 @@ struct BatchDims {
   int y_f32;  // samples stored as f32 (gpet_batch_set_sample_dtype): which instantiation of the GEMM / scorer to launch
   int rng4;   // every edge has the same even grid length >= 64, the same S and z_cols: the register-resident generator k_mt_normals4 applies
   int lg_even;  // every edge of the batch has an even grid length (no Simpson tail: the fused sample + score kernel applies)
+  int y_arith;  // sample GEMM on the f32 matrix cores (gpet_batch_set_sample_arith; implies y_f32): which family launch_sample takes
 };
 
 struct Carver {  // lays buffers out in one arena (256-byte aligned); with base == nullptr it only measures

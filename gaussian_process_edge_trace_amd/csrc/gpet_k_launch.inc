@@ -678,8 +678,51 @@ hipError_t launch_pixels(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
   return hipGetLastError();
 }
 
+// The sample GEMM on the f32 matrix cores (bd.y_arith, gpet_batch_set_sample_arith): the capacity rules of the f64 family below --
+// GEMM_KMAX, the KS ladder, the column runs ncs -- with one kernel per K extent (every extent fits two workgroups per CU).  The
+// register form keeps the posterior mean in LDS; an edge too wide for that (about 15 000 columns) takes the generic form.
+static void launch_sample_f32(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int rank_max) {
+  const size_t lds_top = ((size_t)4 * 24 * GEMM32_LDA) * sizeof(float) + ((size_t)bd.Lg + 64) * sizeof(double);
+  if (bd.r_cap <= GEMM_KMAX && bd.a_rows_cap <= GEMM_KMAX && lds_top <= (size_t)GEMM_LDS_MAX) {
+    const int rm = rank_max > 0 && rank_max <= bd.r_cap ? rank_max : (bd.r_cap > bd.a_rows_cap ? bd.r_cap : bd.a_rows_cap);
+    const int ks = (rm + 3) >> 2;
+    const int rparts = cdiv(bd.S, 128), ctiles = cdiv(bd.Lg, 64);
+    int ncs = cdiv(256, B * rparts);
+    ncs = ncs > ctiles ? ctiles : (ncs < 1 ? 1 : ncs);
+    if (ncs > 8) ncs = 8;
+    const dim3 grid(rparts * ncs, B), block(512);
+    {  // (the chunk plus the posterior mean of a wide edge exceed the 64 KB a kernel gets without asking)
+      static PerDeviceOnce once;
+      if (once.first()) {
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<8>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<12>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<16>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<18>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<20>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<24>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+      }
+    }
+#define GPET_GEMM32_LAUNCH(KS_)                                                                                     \
+  hipLaunchKernelGGL((k_sample_f32_r<KS_>), grid, block,                                                            \
+                     ((size_t)4 * KS_ * GEMM32_LDA) * sizeof(float) + ((size_t)bd.Lg + 64) * sizeof(double), st, d_edges, ncs)
+    if (ks <= 8) GPET_GEMM32_LAUNCH(8);
+    else if (ks <= 12) GPET_GEMM32_LAUNCH(12);
+    else if (ks <= 16) GPET_GEMM32_LAUNCH(16);
+    else if (ks <= 18) GPET_GEMM32_LAUNCH(18);
+    else if (ks <= 20) GPET_GEMM32_LAUNCH(20);
+    else GPET_GEMM32_LAUNCH(24);
+#undef GPET_GEMM32_LAUNCH
+  } else {
+    hipLaunchKernelGGL(k_sample_f32, dim3(cdiv(bd.Lg, 64), cdiv(bd.S, 64), B), dim3(256), 0, st, d_edges);
+  }
+}
+
 hipError_t launch_sample(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int rank_max) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (bd.y_arith) {  // (opt-in; with it off everything below is enqueued as before)
+    launch_sample_f32(st, d_edges, B, bd, rank_max);
+    return hipGetLastError();
+  }
   // rank <= 96 everywhere in the batch (factor capacity): Z rows stay in registers; otherwise
   // (full factors injected by tests, Matern ranks) the K-chunked kernel.  rank_max: the largest rank any
   // edge can have in this launch (r0_max inside the structured loop, else the factor capacity).

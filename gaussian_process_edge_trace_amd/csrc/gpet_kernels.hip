@@ -23,6 +23,7 @@ namespace gpet {
 #include "gpet_k_factor.inc"
 #include "gpet_k_rng.inc"
 #include "gpet_k_sample_score.inc"
+#include "gpet_k_sample_f32.inc"
 #include "gpet_k_kde_pix.inc"
 #include "gpet_k_lml.inc"
 #include "gpet_k_warm.inc"

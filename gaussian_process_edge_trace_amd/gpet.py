@@ -109,7 +109,8 @@ class GP_Edge_Tracing(object):
     from ``self.obs`` again (it resets the device state first), so a trace is not affected by earlier seam calls.
 
     Keywords beyond the reference's signature (keyword-only): ``device``, ``stream``, ``factor_cap``, ``z_cols``,
-    ``sample_dtype`` ("f32": samples stored in single precision) and ``rng`` ("philox": counter-based generator) --
+    ``sample_dtype`` ("f32": samples stored in single precision; "f32mma": that, and the sample GEMM on the f32 matrix cores, an
+    ordered fmaf chain per sample -- ``_lib.Batch.set_sample_dtype``) and ``rng`` ("philox": counter-based generator) --
     the last two are opt-in modes outside the reference-parity statements -- and ``history`` ('obs', 'curves' or 'full') with
     ``history_cap``: what ``return_lines=True`` collects per iteration is recorded on the device instead, the loop runs in
     its normal groups without a wait per iteration, and ``history()`` returns it after ``__call__``."""
@@ -133,7 +134,7 @@ class GP_Edge_Tracing(object):
         g32 = np.asarray(grad_img).astype(np.float32)
         self._abi = to_abi_params(p, factor_cap=factor_cap, z_cols=z_cols)
         self._batch = _lib.Batch(self._ctx, [g32], [self._abi], [p["init"]])
-        if sample_dtype is not None:  # (keyword beyond the reference's signature: "f32" stores the samples in single precision)
+        if sample_dtype is not None:  # (keyword beyond the reference's signature: "f32" stores the samples in single precision, "f32mma" also multiplies in it)
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:  # ("philox": the counter-based generator instead of numpy's RandomState stream)
             self._batch.set_rng(rng)

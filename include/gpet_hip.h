@@ -468,6 +468,23 @@ int gpet_batch_set_rng(gpet_batch* b, int mode);
  * sample_y (oracle mode sample_dtype="f32").  Call between traces, not while a loop is enqueued. */
 int gpet_batch_set_sample_dtype(gpet_batch* b, int f32);
 
+/* Arithmetic of the sample GEMM of this batch: GPET_SAMPLE_ARITH_F64 (default: products and sums on the f64 matrix cores, whatever
+ * the storage type) or GPET_SAMPLE_ARITH_F32 -- BASELINE config 2's "fp32 posterior samples" as arithmetic, on the f32 matrix
+ * cores.  For an edge with factor rows A[k][j], normals Z[s][k], posterior mean mean[j], scale y_s and rank r the result is
+ * DEFINED as
+ *     z = (float)Z[s][k],  a = (float)A[k][j]             round to nearest even, once each
+ *     acc_0 = +0.0f
+ *     acc_{k+1} = fmaf(z_k, a_k, acc_k)                   k = 0, 1, ..., r-1 ascending, one accumulator per (s, j)
+ *     Y[s][j] = (float)(((double)acc_r + mean[j]) * y_s)  the add and the multiply in f64, each rounded, not contracted
+ * bit for bit (f32 subnormals kept; normals and factor rows beyond the rank are not read as values).  F32 also switches the
+ * storage to f32, since the two go together; gpet_batch_set_sample_dtype keeps its meaning and in addition sets the arithmetic
+ * back to F64, so no batch holds f64 storage with f32 arithmetic.  Any other value: GPET_ERR_BAD_ARG, the batch as it was.  NOT
+ * the reference's numbers (there is no oracle mode; tests/f32_chain.py evaluates the definition).  Call between traces, not while
+ * a loop is enqueued.  (Added without a change of GPET_ABI_VERSION: the surface only grew.) */
+#define GPET_SAMPLE_ARITH_F64 0
+#define GPET_SAMPLE_ARITH_F32 1
+int gpet_batch_set_sample_arith(gpet_batch* b, int arith);
+
 /* The optimiser alone, for a caller's own training sets (GaussianProcessRegressor.fit with optimizer="fmin_l_bfgs_b",
  * sklearn_gpr.py:254-295, 587-607): L-BFGS-B from n_starts start points per edge (starts [B][n_starts][3], theta = log
  * (constant, length_scale, noise_level)) inside bounds [3][2] = (lo, hi) per component, on the training sets of
