@@ -279,17 +279,58 @@ def native_frames(imgs):
     return frames, PIX_OF_DTYPE[dt]
 
 
+def split_kernels(kernel):
+    """(list of float64 2-D kernels, multi): a list or tuple of 2-D kernels, or a 3-D array, is several kernels; a 2-D array or a
+    nested list of numbers is ONE kernel (multi False), as it always was."""
+    if isinstance(kernel, (list, tuple)):
+        multi = len(kernel) > 0 and np.ndim(kernel[0]) == 2
+    else:
+        multi = np.ndim(kernel) == 3
+    ks = [np.ascontiguousarray(k, dtype=np.float64) for k in (kernel if multi else [kernel])]
+    if any(k.ndim != 2 or k.size == 0 for k in ks):
+        raise ValueError("the gradient kernel must be a non-empty 2-D array (grad_kernel: one, or a list of them)")
+    return ks, multi
+
+
+def derive_slots(frame_of_edge, kernel_of):
+    """The slot table of a batch whose edge e reads raw frame ``frame_of_edge[e]`` through kernel ``kernel_of[e]``: the distinct
+    (frame, kernel) pairs in order of first occurrence are the image slots.  Returns ``(frame_of, kernel_of_slot, image_of)``:
+    slot g is made of frame ``frame_of[g]`` with kernel ``kernel_of_slot[g]``, edge e reads slot ``image_of[e]``.  Pure: no
+    device, no library."""
+    frame_of_edge, kernel_of = [int(v) for v in frame_of_edge], [int(v) for v in kernel_of]
+    if len(frame_of_edge) != len(kernel_of):
+        raise ValueError("kernel_of has %d entries for %d edges" % (len(kernel_of), len(frame_of_edge)))
+    slot, frame_of, kernel_of_slot, image_of = {}, [], [], []
+    for pair in zip(frame_of_edge, kernel_of):
+        if pair not in slot:
+            slot[pair] = len(frame_of)
+            frame_of.append(pair[0])
+            kernel_of_slot.append(pair[1])
+        image_of.append(slot[pair])
+    return frame_of, kernel_of_slot, image_of
+
+
 class RawFrames(object):
     """The ``raw=`` argument of Batch / Batch.set_images: frames plus the kernel that makes gradient images of them.
     Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
     ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all.
     ``denoise``: optionally how the frames are denoised on the device before the kernel is applied, a ``(technique, kwargs)``
-    pair of gpet_utils.denoise (see denoise_spec).  ``kernel=None``: frames to denoise only (Context.denoise_images)."""
+    pair of gpet_utils.denoise (see denoise_spec).  ``kernel=None``: frames to denoise only (Context.denoise_images).
+    ``slots=(frame_of, kernel_of)``: a slot table -- ``kernel`` is then a list of kernels (split_kernels) and image g is made of
+    frame ``frame_of[g]`` with kernel ``kernel_of[g]`` (the library's *_multi calls); ``len()`` stays the number of frames,
+    ``n_slots`` is the number of images."""
 
-    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None):
+    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
         self.dn = denoise_spec(denoise)
+        self.slots = None
+        if slots is not None:
+            self.kernels = split_kernels(kernel)[0]
+            self.slots = ([int(v) for v in slots[0]], [int(v) for v in slots[1]])
+            if len(self.slots[0]) != len(self.slots[1]) or not self.slots[0]:
+                raise ValueError("a slot table has one frame index and one kernel index per image slot")
+            kernel = self.kernels[0]
         self.kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
         if kernel is None and self.dn is None:
             raise ValueError("raw frames need a gradient kernel or a denoising technique")
@@ -318,6 +359,16 @@ class RawFrames(object):
 
     def dn_arg(self):
         return C.byref(self.dn)
+
+    @property
+    def n_slots(self):
+        return len(self.slots[0]) if self.slots is not None else len(self.ptrs)
+
+    def multi_args(self):
+        """n_kern, kern, kh, kw, frame_of, kernel_of as the *_multi calls take them (the arrays live as long as the tuple)."""
+        nk, ns = len(self.kernels), self.n_slots
+        return (nk, (_P * nk)(*[k.ctypes.data for k in self.kernels]), (C.c_int32 * nk)(*[k.shape[0] for k in self.kernels]),
+                (C.c_int32 * nk)(*[k.shape[1] for k in self.kernels]), (C.c_int32 * ns)(*self.slots[0]), (C.c_int32 * ns)(*self.slots[1]))
 
 
 class GpetError(RuntimeError):
@@ -349,6 +400,9 @@ SYMBOLS = {
                                       C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_grad_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                       C.POINTER(GpetDenoise), C.c_uint, C.POINTER(_P)]),
+    "gpet_grad_images_multi": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(GpetDenoise), C.c_int,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint, C.POINTER(_P)]),
     "gpet_normalise_f32": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "gpet_batch_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P), C.c_int,
                                     C.POINTER(GpetParams), C.POINTER(_P), C.POINTER(_P)]),
@@ -364,12 +418,19 @@ SYMBOLS = {
     "gpet_batch_create_raw_mapped": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.c_int,
                                                _P, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.POINTER(GpetParams), C.POINTER(_P),
                                                C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_create_raw_multi": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(_P),
+                                              C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(GpetDenoise),
+                                              C.POINTER(GpetParams), C.POINTER(_P), C.c_uint, C.POINTER(_P)]),
     "gpet_batch_image_count": (C.c_int, [_P]),
     "gpet_batch_warm_start": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
     "gpet_batch_warm_start_ready": (C.c_int, [_P]),
     "gpet_batch_set_images": (C.c_int, [_P, C.POINTER(_P), C.c_uint]),
     "gpet_batch_set_raw_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint]),
     "gpet_batch_set_raw_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, _P, C.c_int, C.c_int, C.c_uint]),
+    "gpet_batch_set_raw_images_multi": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                  C.POINTER(GpetDenoise), C.c_uint]),
     "gpet_batch_destroy": (None, [_P]),
     "gpet_batch_size": (C.c_int, [_P]),
     "gpet_batch_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int]),
@@ -542,6 +603,14 @@ class Context:
     def grad_images(self, raw):
         """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32."""
         M, N = raw.shape
+        if raw.slots is not None:  # (a slot table: gpet_grad_images_multi -> (n_slots, M, N), slot g of frame_of[g], kernel_of[g])
+            ns = raw.n_slots
+            out = np.empty((ns, M, N), dtype=np.float32)
+            op = (_P * ns)(*[out[g].ctypes.data for g in range(ns)])
+            nk, kp, kh, kw, fo, ko = raw.multi_args()
+            self.check(self.lib.gpet_grad_images_multi(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, nk, kp, kh, kw,
+                                                       raw.dn_arg() if raw.dn is not None else None, ns, fo, ko, raw.flags, op))
+            return out
         out = np.empty((len(raw), M, N), dtype=np.float32)
         op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
         kp, kh, kw = raw.kernel_args()
@@ -728,7 +797,7 @@ class Batch:
                 raise ValueError("image_of has %d entries for %d edges" % (len(image_of), B))
             if raw is None and device_ptrs is None and np.ndim(grads) == 2:
                 grads = [grads]  # (a 2-D array is ONE image)
-            n_img = len(raw if raw is not None else device_ptrs if device_ptrs is not None else grads)
+            n_img = raw.n_slots if raw is not None else len(device_ptrs if device_ptrs is not None else grads)
             io = (C.c_int32 * B)(*image_of)
         inits = [np.ascontiguousarray(i, dtype=np.int64) for i in inits]
         if raw is not None:
@@ -750,7 +819,12 @@ class Batch:
         pa = (GpetParams * B)(*params)
         h = _P()
         if image_of is not None:  # (the library checks the map: its message says what is wrong with it)
-            if raw is not None:
+            if raw is not None and raw.slots is not None:
+                nk, kp, kh, kw, fo, ko = raw.multi_args()
+                ctx.check(self.lib.gpet_batch_create_raw_multi(ctx.h, B, self.M, self.N, n_img, io, len(raw), raw.pointer_array(), raw.pix,
+                                                               nk, kp, kh, kw, fo, ko, raw.dn_arg() if raw.dn is not None else None,
+                                                               pa, ip, raw.flags, C.byref(h)))
+            elif raw is not None:
                 kp, kh, kw = raw.kernel_args()
                 ctx.check(self.lib.gpet_batch_create_raw_mapped(ctx.h, B, self.M, self.N, n_img, io, raw.pointer_array(), raw.pix, kp,
                                                                 kh, kw, raw.dn_arg() if raw.dn is not None else None, pa, ip,
@@ -758,6 +832,8 @@ class Batch:
             else:
                 ctx.check(self.lib.gpet_batch_create_mapped(ctx.h, B, self.M, self.N, n_img, io, gp, pa, ip, flags, C.byref(h)))
         elif raw is not None:
+            if raw.slots is not None:
+                raise ValueError("a slot table comes with the image map of its slots (image_of)")
             assert len(raw) == (1 if share_image else B)
             kp, kh, kw = raw.kernel_args()
             if raw.dn is not None:
@@ -795,7 +871,13 @@ class Batch:
         if raw is not None:  # (a RawFrames: gpet_batch_set_raw_images)
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
-            assert len(raw) == n_img and tuple(raw.shape) == (self.M, self.N)
+            assert raw.n_slots == n_img and tuple(raw.shape) == (self.M, self.N)
+            if raw.slots is not None:  # (gpet_batch_set_raw_images_multi: the library checks the table)
+                nk, kp, kh, kw, fo, ko = raw.multi_args()
+                self.ctx.check(self.lib.gpet_batch_set_raw_images_multi(self.h, len(raw), raw.pointer_array(), raw.pix, nk, kp, kh, kw, fo,
+                                                                        ko, raw.dn_arg() if raw.dn is not None else None,
+                                                                        raw.flags | nf))
+                return
             kp, kh, kw = raw.kernel_args()
             if raw.dn is not None:
                 self.ctx.check(self.lib.gpet_batch_set_raw_images_dn(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.dn_arg(),

@@ -55,6 +55,10 @@ struct ImageSource {
   int kh = 0, kw = 0;
   const DenoiseSpec* dn = nullptr;     // and, optionally, how the frames are denoised first (gpet_denoise_plan.h)
   unsigned int flags = 0;              // GPET_GRAD_ON_DEVICE / GPET_RAW_ON_DEVICE (and GPET_IMAGES_NEXT_FRAME, not read here)
+  // or raw frames with a slot table (gpet_conv_multi_plan.h): n_frames of them, slot g made of frame multi->frame_of[g] with
+  // kernel multi->kernel_of[g]; kern / kh / kw are then unused
+  const ConvMulti* multi = nullptr;
+  int n_frames = 0;
 };
 
 // raw frames -> comp_grad_img of each, straight into the arena: one batched pass on the device (conv_frames), no trip of a
@@ -65,8 +69,9 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
   const int n_img = b->n_img;
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[b->img_rep[g]].grad;
-  const int rc = conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, (s.flags & GPET_RAW_ON_DEVICE) != 0,
-                             dst.data(), b->d_minmax);
+  const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
+  const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, b->bd.M, b->bd.N, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax)
+                         : conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax);
   if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
   return rc;
 }
@@ -89,14 +94,19 @@ static int image_kde(gpet_batch* b) {
 
 // what can be refused before anything is allocated or enqueued (conv_frames checks the same on its own)
 static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img) {
-  if (!s.raw || !s.kern || s.kh <= 0 || s.kw <= 0) return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
+  if (!s.raw || (!s.multi && (!s.kern || s.kh <= 0 || s.kw <= 0))) return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
   if (!pix_bytes(s.pix)) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", s.pix);
-  if (!conv_fits_lds(s.kh, s.kw))
+  if (s.multi) {
+    if (s.multi->n_img != n_img)
+      return fail(c, GPET_ERR_BAD_ARG, "slot table: %d slots for a batch of %d image slots", s.multi->n_img, n_img);
+    const int rc = check_conv_multi(c, *s.multi, s.n_frames);
+    if (rc) return rc;
+  } else if (!conv_fits_lds(s.kh, s.kw))
     return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", s.kh, s.kw,
                 conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
   if (s.dn)
     if (const char* why = dn_check(*s.dn, s.pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
-  for (int g = 0; g < n_img; ++g)
+  for (int g = 0; g < (s.multi ? s.n_frames : n_img); ++g)
     if (!s.raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
   return GPET_OK;
 }
@@ -311,6 +321,24 @@ int gpet_batch_create_raw_mapped(gpet_ctx* c, int B, int M, int N, int n_img, co
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
+  return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
+}
+
+int gpet_batch_create_raw_multi(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, int n_frames, const void* const* raw,
+                                int pix, int n_kern, const double* const* kern, const int32_t* kh, const int32_t* kw, const int32_t* frame_of,
+                                const int32_t* kernel_of, const gpet_denoise* dn, const gpet_params* params, const int64_t* const* init_xy,
+                                unsigned int flags, gpet_batch** out) {
+  if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_multi: bad argument");
+  if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
+  const DenoiseSpec spec = dn_spec(dn);
+  const ConvMulti mk{n_kern, kern, kh, kw, n_img, frame_of, kernel_of};
+  ImageSource src;
+  src.raw = raw;
+  src.pix = pix;
+  src.dn = dn ? &spec : nullptr;
+  src.flags = flags;
+  src.multi = &mk;
+  src.n_frames = n_frames;
   return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
 }
 
@@ -869,6 +897,26 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
+  const int rc = check_raw_source(b->ctx, src, b->n_img);
+  if (rc) return rc;
+  return batch_set_images_from(b, src);
+}
+
+// (refused as gpet_batch_set_raw_images_dn refuses, and for a table slot_table_check or the LDS bound refuses: nothing touched)
+int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* const* raw, int pix, int n_kern, const double* const* kern,
+                                    const int32_t* kh, const int32_t* kw, const int32_t* frame_of, const int32_t* kernel_of,
+                                    const gpet_denoise* dn, unsigned int flags) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  const DenoiseSpec spec = dn_spec(dn);
+  const ConvMulti mk{n_kern, kern, kh, kw, b->n_img, frame_of, kernel_of};
+  ImageSource src;
+  src.raw = raw;
+  src.pix = pix;
+  src.dn = dn ? &spec : nullptr;
+  src.flags = flags;
+  src.multi = &mk;
+  src.n_frames = n_frames;
   const int rc = check_raw_source(b->ctx, src, b->n_img);
   if (rc) return rc;
   return batch_set_images_from(b, src);

@@ -253,21 +253,30 @@ static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
 // its end -- groups of DN_TVC_GROUP iterations, the count of finished images read between groups -- before the next is staged.
 // kern == nullptr: no convolution (gpet_denoise_images); dn_out: host buffers the denoised frames are copied to, n_iter_out: host
 // [n_img] iterations per image.
-int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
-                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out) {
+// mk (may be nullptr): a slot table (gpet_conv_multi_plan.h).  n_img then counts the FRAMES -- staged and denoised once each, in
+// the same chunks -- while dst[] and d_mm are per slot (mk->n_img of them): one k_conv_relu_multi launch per chunk writes every
+// slot of the chunk's frames, and the kernels' taps, descriptors and the slot lists go up in the same one table copy.
+static int conv_frames_body(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
+                            int kh, int kw, const ConvMulti* mk, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out,
+                            int32_t* n_iter_out) {
   const size_t esz = (size_t)pix_bytes(pix);
   const bool dn_on = dn && dn->technique != DN_NONE;
   if (!esz) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", pix);
   if (!raw || n_img <= 0 || M <= 0 || N <= 0 || (!kern && !dn_on) || (kern && (!dst || kh <= 0 || kw <= 0)))
     return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
-  if (kern && !conv_fits_lds(kh, kw))
+  if (mk) {
+    const int rc_t = check_conv_multi(c, *mk, n_img);
+    if (rc_t) return rc_t;
+  } else if (kern && !conv_fits_lds(kh, kw))
     return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw, conv_lds_bytes(kh, kw),
                 CONV_LDS_MAX);
   if (dn)
     if (const char* why = dn_check(*dn, pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
   for (int g = 0; g < n_img; ++g)
     if (!raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
-  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = kern ? (size_t)kh * kw : 0;
+  const ConvUnion cu = mk ? conv_union(mk->n_kern, mk->kh, mk->kw) : ConvUnion{0, 0, 0, 0, 0};
+  const int n_out = mk ? mk->n_img : n_img;  // gradient images written: one per slot, or one per frame
+  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = mk ? cu.taps : kern ? (size_t)kh * kw : 0;
   const DenoiseLayout L = dn_layout(dn_on ? dn->technique : DN_NONE, pix, M, N);
   const int cpix = dn_on ? dn_out_pix(dn->technique, pix) : pix;  // what the convolution reads
   const size_t stage_img = dn_stage_bytes(img_bytes, on_dev, L);
@@ -279,10 +288,14 @@ int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, 
   // | pointers to the denoised frames | Gaussian taps of the two axes | iterations per image | finished images of the chunk
   const int ry = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_y, dn->truncate) : 0;
   const int rx = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_x, dn->truncate) : 0;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_wf = 2 * o_dst, o_mm = o_wf + sizeof(double) * nt;
-  const size_t o_dn = (o_mm + sizeof(unsigned int) * 2 * (size_t)n_img + 7) & ~(size_t)7;
+  // | with a slot table: kernel descriptors | slots of each frame (offsets, list) | kernel of each slot
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_wf = o_dst + sizeof(void*) * (size_t)n_out, o_mm = o_wf + sizeof(double) * nt;
+  const size_t o_dn = (o_mm + sizeof(unsigned int) * 2 * (size_t)n_out + 7) & ~(size_t)7;
   const size_t o_gw = o_dn + (dn_on ? o_dst : 0), o_it = o_gw + (dn_on ? sizeof(double) * (size_t)(2 * ry + 1 + 2 * rx + 1) : 0);
-  const size_t tab_bytes = dn_on ? o_it + sizeof(int) * ((size_t)n_img + 1) : o_mm + sizeof(unsigned int) * 2 * (size_t)n_img;
+  const size_t o_end = dn_on ? o_it + sizeof(int) * ((size_t)n_img + 1) : o_mm + sizeof(unsigned int) * 2 * (size_t)n_out;
+  const size_t o_kd = (o_end + 7) & ~(size_t)7, o_so = o_kd + (mk ? sizeof(ConvKernDesc) * (size_t)mk->n_kern : 0);
+  const size_t o_sl = o_so + (mk ? sizeof(int32_t) * ((size_t)n_img + 1) : 0), o_ko = o_sl + (mk ? sizeof(int32_t) * (size_t)n_out : 0);
+  const size_t tab_bytes = mk ? o_ko + sizeof(int32_t) * (size_t)n_out : o_end;
   rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
   if (rc) return rc;
   c->h_raw_tab.resize(tab_bytes);
@@ -296,28 +309,44 @@ int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, 
       if (!on_dev) h_src[stage_first(sp, k) + i] = slot + (size_t)i * stage_img;
       if (dn_on) ((const void**)(h + o_dn))[stage_first(sp, k) + i] = slot + o_ws + (size_t)i * L.img_bytes + L.off_out;
     }
-  for (int g = 0; g < n_img; ++g) {
+  for (int g = 0; g < n_img; ++g)
     if (on_dev) h_src[g] = raw[g];
+  for (int g = 0; g < n_out; ++g) {
     h_dst[g] = dst ? dst[g] : nullptr;
     h_mm[2 * g] = 0xFFFFFFFFu;
     h_mm[2 * g + 1] = 0u;
   }
-  if (kern) conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
+  if (mk) {
+    ConvKernDesc* kd = (ConvKernDesc*)(h + o_kd);
+    conv_kern_descs(mk->n_kern, mk->kh, mk->kw, kd);
+    for (int k = 0; k < mk->n_kern; ++k) conv_flip_taps(mk->kern[k], mk->kh[k], mk->kw[k], (double*)(h + o_wf) + kd[k].w0);
+    frame_slots(n_img, n_out, mk->frame_of, (int32_t*)(h + o_so), (int32_t*)(h + o_sl));
+    memcpy(h + o_ko, mk->kernel_of, sizeof(int32_t) * (size_t)n_out);
+  } else if (kern)
+    conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
   if (dn_on && dn->technique == DN_GAUSSIAN) {
     dn_gauss_taps(dn->sigma_y, ry, (double*)(h + o_gw));
     dn_gauss_taps(dn->sigma_x, rx, (double*)(h + o_gw) + 2 * ry + 1);
   }
   HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
   if (kern)
-    HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_img, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_out, hipMemcpyDeviceToDevice, c->stream));
   const void* const* d_src = (const void* const*)c->raw_tab;
   float* const* d_dst = (float* const*)(c->raw_tab + o_dst);
   const double* d_wf = (const double*)(c->raw_tab + o_wf);
   const void* const* d_conv_src = dn_on ? (const void* const*)(c->raw_tab + o_dn) : d_src;
   const double* d_gw = (const double*)(c->raw_tab + o_gw);
   int* d_it = (int*)(c->raw_tab + o_it);
+  // frames first .. first + cnt - 1 of `from` (pixel type p) -> the gradient images of the frames, or of all their slots
+  auto convolve = [&](int p, const void* const* from, int first, int cnt) {
+    if (mk)
+      return launch_conv_multi(c->stream, p, from, first, cnt, M, N, d_wf, cu, (const ConvKernDesc*)(c->raw_tab + o_kd),
+                               (const int32_t*)(c->raw_tab + o_so), (const int32_t*)(c->raw_tab + o_sl),
+                               (const int32_t*)(c->raw_tab + o_ko), d_dst, d_mm);
+    return launch_conv_batch(c->stream, p, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
+  };
   if (on_dev && !dn_on) {
-    HIPCHK(c, launch_conv_batch(c->stream, pix, d_src, 0, n_img, M, N, d_wf, kh, kw, d_dst, d_mm));
+    HIPCHK(c, convolve(pix, d_src, 0, n_img));
   } else {
     // plain copies out of the caller's memory, image by image, in stream order behind the kernels that last read the slot
     for (int k = 0; k < sp.n_chunks; ++k) {
@@ -351,7 +380,7 @@ int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, 
             HIPCHK(c, hipMemcpyAsync(dn_out[first + i], ws + (size_t)i * L.img_bytes + L.off_out, px * (size_t)pix_bytes(cpix),
                                      hipMemcpyDeviceToHost, c->stream));
       }
-      if (kern) HIPCHK(c, launch_conv_batch(c->stream, cpix, d_conv_src, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm));
+      if (kern) HIPCHK(c, convolve(cpix, d_conv_src, first, cnt));
     }
   }
   if (n_iter_out) {
@@ -360,16 +389,51 @@ int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, 
     else
       for (int g = 0; g < n_img; ++g) n_iter_out[g] = 0;
   }
-  if (kern) HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_img, px, d_mm));
+  if (kern) HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_out, px, d_mm));
   return GPET_OK;
+}
+
+int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
+                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out) {
+  return conv_frames_body(c, raw, n_img, pix, M, N, dn, kern, kh, kw, nullptr, on_dev, dst, d_mm, dn_out, n_iter_out);
+}
+
+int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames) {
+  if (!mk.kern || !mk.kh || !mk.kw) return fail(c, GPET_ERR_BAD_ARG, "slot table: the kernels are a null pointer");
+  if (const char* why = slot_table_check(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
+    return fail(c, GPET_ERR_BAD_ARG, "slot table: %s (n_frames = %d, n_kern = %d, n_img = %d)", why, n_frames, mk.n_kern, mk.n_img);
+  for (int k = 0; k < mk.n_kern; ++k)
+    if (!mk.kern[k] || mk.kh[k] <= 0 || mk.kw[k] <= 0) return fail(c, GPET_ERR_BAD_ARG, "slot table: kernel %d is empty or a null pointer", k);
+  if (!conv_union_fits_lds(mk.n_kern, mk.kh, mk.kw)) {
+    const ConvUnion u = conv_union(mk.n_kern, mk.kh, mk.kw);
+    return fail(c, GPET_ERR_BAD_ARG, "the %d kernels need %zu bytes of LDS for their taps and their union patch of %d x %d, more than %zu",
+                mk.n_kern, conv_union_lds_bytes(u), conv_union_rows(u), conv_union_cols(u), CONV_LDS_MAX);
+  }
+  return GPET_OK;
+}
+
+// one kernel on every frame in frame order is the single-kernel path itself: the same launches in the same order
+int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
+                      bool on_dev, float* const* dst, unsigned int* d_mm) {
+  const int rc = check_conv_multi(c, mk, n_frames);
+  if (rc) return rc;
+  if (slot_table_is_identity(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
+    return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], nullptr, on_dev, dst, d_mm, nullptr, nullptr);
+  // (with a table the body reads `kern` only as "there is a convolution": taps and extents come from mk)
+  return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], &mk, on_dev, dst, d_mm, nullptr, nullptr);
 }
 
 extern "C" {
 
+// n_img output images; mk == nullptr: of n_img frames with the one kernel, else of n_frames frames by the slot table
 static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                            const DenoiseSpec* dn, unsigned int flags, float* const* out) {
-  if (!c || !raw || !kern || !out || n_img <= 0 || M <= 0 || N <= 0 || kh <= 0 || kw <= 0)
+                            const DenoiseSpec* dn, unsigned int flags, float* const* out, const ConvMulti* mk = nullptr, int n_frames = 0) {
+  if (!c || !raw || !out || n_img <= 0 || M <= 0 || N <= 0 || (!mk && (!kern || kh <= 0 || kw <= 0)))
     return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: bad argument");
+  if (mk) {
+    const int rc_t = check_conv_multi(c, *mk, n_frames);  // (before the scratch is sized by the table)
+    if (rc_t) return rc_t;
+  }
   for (int g = 0; g < n_img; ++g)
     if (!out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: output image %d is a null pointer", g);
   HIPCHK(c, hipSetDevice(c->device));
@@ -385,7 +449,8 @@ static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int 
   unsigned int* d_mm = cv.take<unsigned int>(2 * (size_t)n_img);
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = d_out + (size_t)g * px;
-  rc = conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
+  rc = mk ? conv_frames_multi(c, raw, n_frames, pix, M, N, dn, *mk, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm)
+          : conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
   if (rc == GPET_OK)
     for (int g = 0; g < n_img; ++g) {
       hipError_t e = hipMemcpyAsync(out[g], dst[(size_t)g], px * sizeof(float), hipMemcpyDeviceToHost, c->stream);
@@ -407,6 +472,14 @@ int gpet_grad_images_dn(gpet_ctx* c, const void* const* raw, int n_img, int pix,
                         const gpet_denoise* dn, unsigned int flags, float* const* out) {
   const DenoiseSpec spec = dn_spec(dn);
   return grad_images_from(c, raw, n_img, pix, M, N, kern, kh, kw, dn ? &spec : nullptr, flags, out);
+}
+
+int gpet_grad_images_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, int n_kern, const double* const* kern,
+                           const int32_t* kh, const int32_t* kw, const gpet_denoise* dn, int n_img, const int32_t* frame_of,
+                           const int32_t* kernel_of, unsigned int flags, float* const* out) {
+  const DenoiseSpec spec = dn_spec(dn);
+  const ConvMulti mk{n_kern, kern, kh, kw, n_img, frame_of, kernel_of};
+  return grad_images_from(c, raw, n_img, pix, M, N, nullptr, 0, 0, dn ? &spec : nullptr, flags, out, &mk, n_frames);
 }
 
 int gpet_denoise_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_denoise* dn,

@@ -173,6 +173,23 @@ int fin_lattice(const double* x, int n, double* hinv);
 int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
                 int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out = nullptr,
                 int32_t* n_iter_out = nullptr);
+// the slot table of a multi-kernel source as the C ABI hands it over (gpet_conv_multi_plan.h): slot g of n_img is frame frame_of[g]
+// with kernel kernel_of[g] of the n_kern kernels kern[k] (kh[k] x kw[k])
+struct ConvMulti {
+  int n_kern;
+  const double* const* kern;
+  const int32_t* kh;
+  const int32_t* kw;
+  int n_img;
+  const int32_t* frame_of;
+  const int32_t* kernel_of;
+};
+// GPET_OK, or GPET_ERR_BAD_ARG with the reason: a table slot_table_check refuses, an empty kernel, a union patch beyond the LDS
+int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames);
+// conv_frames for a slot table: n_frames raw frames -> the mk.n_img gradient images dst[g] (d_mm: device [2 mk.n_img]); every frame
+// is staged and denoised once.  One kernel on every frame in order takes conv_frames' own path
+int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
+                      bool on_dev, float* const* dst, unsigned int* d_mm);
 // the C ABI's gpet_denoise as the plan takes it (nullptr: no technique)
 static inline DenoiseSpec dn_spec(const gpet_denoise* d) {
   DenoiseSpec s;

@@ -173,3 +173,73 @@ __global__ void k_normalise_f32_batch(float* const* __restrict__ imgs, int img0,
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// a1, batched, several kernels on shared frames (gpet_grad_images_multi, gpet_batch_create_raw_multi,
+//     gpet_batch_set_raw_images_multi; the table: gpet_conv_multi_plan.h).  blockIdx.z is a FRAME: its workgroup loads the union
+//     patch of all kernels once -- k_conv_relu_batch's load, with the union's halo -- and the flipped taps of all kernels, then
+//     evaluates every slot of the frame out of that patch: slot g's kernel k reads patch row yl + a + kd[k].dy, column
+//     tx + b + kd[k].dx for its tap (a, b), which is the pixel k_conv_relu_batch reads for it.  Per output the products, their
+//     order, the skipped zero taps, the clamp and the cast are k_conv_relu_batch's, so a slot's image has its bits.  One
+//     order-key (min, max) atomic pair per wave and slot.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ void k_conv_relu_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
+                                  const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
+                                  const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
+                                  const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_w[];  // [n_taps] taps of all kernels, then the union patch [ph][pw]
+  const int f = frame0 + blockIdx.z;
+  const T* __restrict__ img = src[f];
+  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
+  for (int i = tid; i < n_taps; i += nthr) s_w[i] = wf[i];
+  double* s_p = s_w + n_taps;
+  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * CONV_RY;
+  for (int e = tid; e < pw * ph; e += nthr) {
+    const int py = e / pw, px = e - py * pw;
+    int ry = y0 + py - top, rx = x0 + px - left;
+    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
+    s_p[e] = (double)img[(size_t)ry * N + rx];
+  }
+  __syncthreads();
+  const int x = x0 + threadIdx.x;
+  for (int si = slot_off[f]; si < slot_off[f + 1]; ++si) {
+    const int g = slot_list[si];
+    const ConvKernDesc K = kd[kernel_of[g]];
+    const double* __restrict__ w_k = s_w + K.w0;
+    float* __restrict__ out = dst[g];
+    unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
+    for (int yl = threadIdx.y; yl < CONV_RY; yl += blockDim.y) {
+      const int y = y0 + yl;
+      if (x < N && y < M) {
+        double acc = 0.0;
+        for (int a = 0; a < K.kh; ++a) {
+          const double* row = s_p + (yl + a + K.dy) * pw + threadIdx.x + K.dx;
+          for (int b = 0; b < K.kw; ++b) {
+            const double w = w_k[a * K.kw + b];
+            if (w == 0.0) continue;
+            acc = acc + row[b] * w;
+          }
+        }
+        if (acc < 0.0) acc = 0.0;
+        const float v = (float)acc;
+        out[(size_t)y * N + x] = v;
+        const unsigned int key = f32_order_key(v);
+        kmin = min(kmin, key);
+        kmax = max(kmax, key);
+      }
+    }
+    // wave min/max -> one atomic pair per wave, into the slot's pair
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
+      kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
+    }
+    if ((tid & 63) == 0) {
+      atomicMin(&minmax[2 * (size_t)g], kmin);
+      atomicMax(&minmax[2 * (size_t)g + 1], kmax);
+    }
+  }
+}
+

@@ -57,6 +57,37 @@ hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, 
   }
   return hipSuccess;
 }
+// frames frame0 .. frame0 + n - 1 of d_src -> the unnormalised f32 gradient images of all their slots in ONE launch: the device
+// tables of gpet_conv_multi_plan.h (taps of all kernels, kernel descriptors, slots of each frame, kernel of each slot), d_dst and
+// d_minmax per SLOT
+template <typename T>
+static hipError_t launch_conv_multi_t(hipStream_t st, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                                      const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                                      const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
+  const ConvGrid cg = conv_grid(M, N);
+  hipLaunchKernelGGL(k_conv_relu_multi<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_union_lds_bytes(u), st, (const T* const*)d_src, frame0,
+                     M, N, d_wf, (int)u.taps, d_kd, u.top, u.left, conv_union_rows(u), conv_union_cols(u), d_slot_off, d_slot_list,
+                     d_kernel_of, d_dst, d_minmax);
+  return hipGetLastError();
+}
+hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                             const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                             const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (u.taps == 0 || conv_union_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    hipError_t e = hipSuccess;
+    switch (pix) {
+      case PIX_U8: e = launch_conv_multi_t<uint8_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      case PIX_U16: e = launch_conv_multi_t<uint16_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      case PIX_F32: e = launch_conv_multi_t<float>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      default: e = launch_conv_multi_t<double>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 // the n images of d_imgs normalised in place, each by its own slot of d_minmax, in one launch
 hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches

@@ -4,6 +4,7 @@
 
 #include "gpet_batch_plan.h"  // EdgeDev (gpet_dev.h), BatchDims, STRUCT_H_LDS_MAX
 #include "gpet_conv_plan.h"   // pixel types, conv geometry, staging plan
+#include "gpet_conv_multi_plan.h"  // slot table of a multi-kernel source: validation, union patch, slots of each frame
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 
@@ -18,6 +19,11 @@ hipError_t launch_normalise(hipStream_t st, const float* d_in, size_t count, con
 // launch each; every image of the stack has its own (min, max) slot in d_minmax
 hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
                              int kh, int kw, float* const* d_dst, unsigned int* d_minmax);
+// the same for a slot table (gpet_conv_multi_plan.h): frames frame0 .. frame0 + n - 1 of d_src, every slot of each of them, one
+// launch; d_dst and d_minmax are per slot
+hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                             const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                             const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax);
 hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax);
 // a0 (gpet_denoise_plan.h): images img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) are the n images of a chunk
 // whose workspace starts at ws; the denoised frame lands at L.off_out of every image's block.  One launch (two for the Gaussian's

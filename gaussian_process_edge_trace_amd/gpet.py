@@ -373,12 +373,16 @@ def _raw_stack(raw_imgs):
 
 
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
-                         raw_dtype=None, grad_kernel=None, denoise=None):
+                         raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None):
     """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
     ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
     images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
     shape (``grad_shape``) and, raw ones, their dtype (``raw_dtype``).  ``denoise`` = (technique, kwargs) of
-    ``gpet_utils.denoise``: raw frames are denoised on the device first; gradient images cannot be."""
+    ``gpet_utils.denoise``: raw frames are denoised on the device first; gradient images cannot be.
+    ``grad_kernel`` a list of kernels with ``kernel_of`` (one index per edge): edge e reads its raw frame -- ``image_of[e]`` if
+    ``image_of`` is given (``n_edges`` then counts the frames), else the shared one or its own -- through
+    ``grad_kernel[kernel_of[e]]``.  The dict then also has ``image_of``, the edge-to-slot map of the slot table
+    (``_lib.derive_slots``) the ``raw`` of ``batch`` carries, and ``edge_frames``, the frame of every edge."""
     have_grad = grad_imgs is not None or grad_device_ptrs is not None
     have_raw = raw_imgs is not None or raw_device_ptrs is not None
     if denoise is not None and not have_raw:
@@ -389,11 +393,46 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
         raise ValueError("no images: pass grad_imgs, grad_device_ptrs, raw_imgs or raw_device_ptrs")
     if grad_imgs is not None and grad_device_ptrs is not None:
         raise ValueError("grad_imgs and grad_device_ptrs are alternatives")
+    if kernel_of is not None and not have_raw:
+        raise ValueError("kernel_of picks the gradient kernel of raw frames (raw_imgs / raw_device_ptrs with grad_kernel): "
+                         "gradient images are past that stage")
     if have_raw:
         if raw_imgs is not None and raw_device_ptrs is not None:
             raise ValueError("raw_imgs and raw_device_ptrs are alternatives")
         if grad_kernel is None:
             raise ValueError("raw frames need grad_kernel, the kernel comp_grad_img would be called with")
+        kernels, multi = _lib.split_kernels(grad_kernel)
+        if multi and kernel_of is None:
+            raise ValueError("a list of %d kernels in grad_kernel needs kernel_of, the kernel index of every edge" % len(kernels))
+        if kernel_of is not None:
+            kernel_of = [int(v) for v in np.asarray(kernel_of).reshape(-1)]
+            if any(k < 0 or k >= len(kernels) for k in kernel_of):
+                raise ValueError("kernel_of holds an index outside grad_kernel's %d kernels" % len(kernels))
+            if set(kernel_of) != set(range(len(kernels))):
+                raise ValueError("kernel_of never uses kernel %d of grad_kernel" % min(set(range(len(kernels))) - set(kernel_of)))
+            if image_of is not None and len(image_of) != len(kernel_of):
+                raise ValueError("kernel_of has %d entries, image_of %d" % (len(kernel_of), len(image_of)))
+            if raw_device_ptrs is not None:
+                if grad_shape is None or raw_dtype is None:
+                    raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
+                frames = _as_list(raw_device_ptrs)
+                share = len(frames) == 1
+            else:
+                frames, share = _raw_stack(raw_imgs)
+            B = len(kernel_of)
+            if image_of is None and not share and len(frames) != B:
+                raise ValueError("kernel_of has %d entries for %d raw frames, one per edge" % (B, len(frames)))
+            edge_frames = [int(v) for v in image_of] if image_of is not None else ([0] * B if share else list(range(B)))
+            if image_of is not None and len(frames) != n_edges:
+                raise ValueError("%d raw frames for %d frames of the image map" % (len(frames), n_edges))
+            frame_of, kernel_of_slot, edge_slot = _lib.derive_slots(edge_frames, kernel_of)
+            if raw_device_ptrs is not None:
+                raw = _lib.RawFrames(kernels, device_ptrs=frames, dtype=raw_dtype, shape=grad_shape, denoise=denoise,
+                                     slots=(frame_of, kernel_of_slot))
+            else:
+                raw = _lib.RawFrames(kernels, frames=frames, denoise=denoise, slots=(frame_of, kernel_of_slot))
+            return dict(kind="raw", share=False, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
+                        batch=dict(grads=None, raw=raw), image_of=edge_slot, edge_frames=edge_frames)
         if raw_device_ptrs is not None:
             if grad_shape is None or raw_dtype is None:
                 raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
@@ -438,7 +477,7 @@ class GP_Edge_Tracing_Batch(object):
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
-                 denoise=None, image_of=None, history=None, history_cap=64):
+                 denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -458,6 +497,13 @@ class GP_Edge_Tracing_Batch(object):
         ``[0, 1, 2, 0, 1, 2]`` is valid), and ``set_frame`` expects ``n_img`` images.  Every image is uploaded, turned into a
         gradient image, denoised and run through the gradient KDE once; the batch equals the one built from the B images
         ``imgs[image_of[e]]`` bit for bit.
+        ``grad_kernel=[K0, K1, ...]`` with ``kernel_of`` (B indices): edge e reads its raw frame through
+        ``grad_kernel[kernel_of[e]]`` -- the upper wall of a dark lumen is a bright-to-dark edge, the lower wall dark-to-bright,
+        on the same frame.  With ``image_of``, that argument keeps meaning "edge e reads raw frame ``image_of[e]``" (the frames
+        are ``max(image_of) + 1`` long); without it the frame is shared or per edge as ever.  The image slots are the distinct
+        (frame, kernel) pairs (``_lib.derive_slots``); every frame is uploaded, denoised and staged on the device once, however
+        many kernels read it, and the batch equals the one built from ``comp_grad_imgs(frames, K[k])``' outputs bit for bit.
+        ``set_frame(raw_imgs=...)`` then expects as many frames as the constructor got and reuses kernels and table.
         ``history`` = 'obs', 'curves' or 'full' (default None: off): every loop iteration of every edge leaves a record on the
         device -- the new observation set, the score threshold, the optimal cost and sample index; from 'curves' the optimal
         curve; with 'full' the per-column mean and std of all samples -- read with ``history()`` after ``run_loop`` or
@@ -476,10 +522,21 @@ class GP_Edge_Tracing_Batch(object):
                 raise ValueError("%d images for an image map of n_img = %d" % (len(given[0]), n_img))
             if grad_imgs is not None:
                 grad_imgs = list(grad_imgs)
+        if kernel_of is not None and len(np.asarray(kernel_of).reshape(-1)) != B:
+            raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
         src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
-                                   raw_dtype, grad_kernel, denoise)
+                                   raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of)
         self._denoise = denoise
-        self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
+        # (a slot table: the kernels, the kernel and the frame of every edge are remembered for set_frame; the batch's own image
+        #  map is then the edge-to-slot map)
+        self._kernel_of, self._edge_frames, self._n_frames = None, None, None
+        if "image_of" in src:
+            self._kernel_of = [int(v) for v in np.asarray(kernel_of).reshape(-1)]
+            self._edge_frames, self._n_frames = src["edge_frames"], len(src["batch"]["raw"])
+            self._grad_kernel = src["batch"]["raw"].kernels
+            image_of = src["image_of"]
+        else:
+            self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
         self._raw_dtype = raw_dtype
         share = src["share"] and image_of is None  # (a map of one image is the shared layout, decided by the library)
         shapes = [src["shape"]] * B
@@ -538,6 +595,8 @@ class GP_Edge_Tracing_Batch(object):
 
     def _images_text(self):
         b = self._batch
+        if self._kernel_of is not None:
+            return "%d raw frames behind the %d image slots of the batch's slot table" % (self._n_frames, b.n_img)
         if b.image_of is not None:
             return "%d images, the batch's image map has n_img = %d" % (b.n_img, b.n_img)
         return "one shared image" if b.share_image else "one image per edge, %d" % b.n_img
@@ -569,7 +628,8 @@ class GP_Edge_Tracing_Batch(object):
         if raw_imgs is not None or raw_device_ptrs is not None:
             kern = self._grad_kernel if grad_kernel is None else grad_kernel
             b = self._batch
-            n_img = b.n_img
+            multi = self._kernel_of is not None
+            n_img = self._n_frames if multi else b.n_img  # (frames expected)
             if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
                 raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
             have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
@@ -577,7 +637,8 @@ class GP_Edge_Tracing_Batch(object):
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % (len(have), self._images_text(), b.M, b.N))
             src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (b.M, b.N), raw_imgs, raw_device_ptrs,
                                        self._raw_dtype if raw_dtype is None else raw_dtype, kern,
-                                       None if denoise is False else (self._denoise if denoise is None else denoise))
+                                       None if denoise is False else (self._denoise if denoise is None else denoise),
+                                       kernel_of=self._kernel_of, image_of=self._edge_frames)
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
             if len(src["batch"]["raw"]) != n_img or src["shape"] != (b.M, b.N):
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"

@@ -68,9 +68,19 @@ def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None):
     kernel)`` bit for bit.  uint8, uint16, float32 and float64 frames go to the device as they are (integer pixels mean their
     exact float64 values); any other dtype is converted to float64 first, as ``comp_grad_img`` does with every image.
     ``denoise=(technique, kwargs)``: the frames are denoised on the device first, in the same pass -- the result equals
-    ``comp_grad_imgs(denoise_imgs(imgs, technique, kwargs), kernel)`` bit for bit."""
-    raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise)  # (refuses a bad spec before a device is needed)
-    return (ctx or _ctx()).grad_images(raw)
+    ``comp_grad_imgs(denoise_imgs(imgs, technique, kwargs), kernel)`` bit for bit.
+    ``kernel`` may also be a list or tuple of 2-D kernels, or a 3-D array (a 2-D array or a nested list of numbers is ONE
+    kernel): the result is then (T, n_kern, M, N) and ``[t, k]`` equals ``comp_grad_imgs(imgs, kernel[k])[t]`` bit for bit, with
+    and without ``denoise``; every frame is uploaded and denoised once, however many kernels read it
+    (gpet_grad_images_multi)."""
+    kernels, multi = _lib.split_kernels(kernel)
+    if not multi:
+        raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise)  # (refuses a bad spec before a device is needed)
+        return (ctx or _ctx()).grad_images(raw)
+    T, K = len(imgs), len(kernels)
+    raw = _lib.RawFrames(kernels, frames=imgs, denoise=denoise, slots=([t for t in range(T) for _ in range(K)], list(range(K)) * T))
+    out = (ctx or _ctx()).grad_images(raw)
+    return out.reshape((T, K) + out.shape[1:])
 
 
 def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False):

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import split_kernels
 from .gpet import GP_Edge_Tracing_Batch, resolve_params
 
 
@@ -78,10 +79,15 @@ class SequenceTracer(object):
 
     ``init``: one (n_init, 2) array -- or a list (or 3-D array) of E of them, the E edges of every frame, which may span
     different columns.  Then every entry of the result is a list of E results, ``iterations[t]`` a list of E counts, and
-    edge k's results are what ``SequenceTracer(frames, init[k], ...)`` gives: the E edges of a frame share its seed."""
+    edge k's results are what ``SequenceTracer(frames, init[k], ...)`` gives: the E edges of a frame share its seed.
+
+    ``grad_kernel=[K_0 .. K_{E-1}]``: one kernel per init, for edges of opposite polarity on the same raw frames (the two walls
+    of a vessel) -- or fewer kernels plus ``kernel_of`` with E indices into them.  Every frame is uploaded, denoised and staged
+    on the device once, and edge k's results are what ``SequenceTracer(frames, init[k], grad_kernel=K[kernel_of[k]], ...)``
+    gives, bit for bit."""
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
-                 denoise=None, **kw):
+                 denoise=None, kernel_of=None, **kw):
         self.frames = frames
         self.T = len(frames)
         self.inits, self.multi = _inits_of(init)
@@ -94,6 +100,25 @@ class SequenceTracer(object):
         self.grad_kernel = grad_kernel
         if denoise is not None and grad_kernel is None:
             raise ValueError("denoise needs raw frames, i.e. grad_kernel")
+        self.kernel_of = None
+        if kernel_of is not None and grad_kernel is None:
+            raise ValueError("kernel_of picks the gradient kernel of raw frames, i.e. needs grad_kernel")
+        if grad_kernel is not None:
+            kernels, multi = split_kernels(grad_kernel)
+            if multi or kernel_of is not None:
+                if kernel_of is None:
+                    if len(kernels) != self.E:
+                        raise ValueError("%d kernels in grad_kernel for %d inits: pass one per init, or kernel_of with one index "
+                                         "per init" % (len(kernels), self.E))
+                    kernel_of = range(self.E)
+                kernel_of = [int(v) for v in kernel_of]
+                if len(kernel_of) != self.E:
+                    raise ValueError("kernel_of has %d entries for %d inits" % (len(kernel_of), self.E))
+                if any(k < 0 or k >= len(kernels) for k in kernel_of):
+                    raise ValueError("kernel_of holds an index outside grad_kernel's %d kernels" % len(kernels))
+                used = sorted(set(kernel_of))  # (kernels no init uses are dropped: the library refuses a kernel no slot reads)
+                self.grad_kernel = [kernels[k] for k in used]
+                self.kernel_of = [used.index(k) for k in kernel_of]
         self.denoise = denoise
         self.chains = chain_slices(self.T, n_chains)
         self.seeds = [int(seed)] * self.T if seeds is None else [int(v) for v in seeds]
@@ -132,9 +157,11 @@ class SequenceTracer(object):
                 images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
                                                                                      grad_kernel=self.grad_kernel,
                                                                                      denoise=self.denoise)
+                if self.kernel_of is not None:  # (chain-major, like the inits: C frames, C x distinct kernels image slots)
+                    images["kernel_of"] = [k for _ in active for k in self.kernel_of]
                 # (several edges per frame: one image per chain, read by its E edges; one edge per frame is a batch with one
                 # image per edge, as ever)
-                image_of = [ci for ci in range(len(active)) for _ in range(E)] if E > 1 else None
+                image_of = [ci for ci in range(len(active)) for _ in range(E)] if E > 1 or self.kernel_of is not None else None
                 self._tracer = GP_Edge_Tracing_Batch([i for _ in active for i in self.inits], seeds=seeds, obs=obs,
                                                      device=self.device, _ctx=self._ctx, image_of=image_of, **images, **self.kw)
                 if self._ctx is None:

@@ -213,6 +213,17 @@ int gpet_denoise_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pi
  * gpet_denoise_images returns for frame g.  dn NULL or technique NONE: gpet_grad_images itself. */
 int gpet_grad_images_dn(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh,
                         int kw, const gpet_denoise* dn, unsigned int flags, float* const* out);
+/* Several kernels on shared frames: a slot table.  n_frames raw frames, n_kern kernels kern[k] of kh[k] x kw[k] (f64, host; the
+ * extents may differ and may be even or odd), n_img image slots: slot g is gpet_grad_images_dn of frame frame_of[g] with kernel
+ * kernel_of[g], bit for bit -- the two walls of a vessel are a bright-to-dark and a dark-to-bright edge on the same frame.  Every
+ * frame is uploaded, denoised (dn; NULL: not at all) and staged on the device once, however many kernels read it.  out[g]
+ * (host, f32 [M*N]): slot g.  GPET_ERR_BAD_ARG, gpet_last_error naming the cause, for an index out of range, a frame or a kernel
+ * no slot reads, the same (frame, kernel) pair twice (edges that want the same image share a slot through image_of), more than
+ * 8 kernels, kernels whose taps and union patch exceed 64 KB of LDS, and whatever gpet_grad_images_dn refuses.  n_kern = 1 with
+ * one slot per frame in frame order (frame_of[g] = g) is gpet_grad_images_dn itself. */
+int gpet_grad_images_multi(gpet_ctx* ctx, const void* const* raw, int n_frames, int pix, int M, int N, int n_kern,
+                           const double* const* kern, const int32_t* kh, const int32_t* kw, const gpet_denoise* dn, int n_img,
+                           const int32_t* frame_of, const int32_t* kernel_of, unsigned int flags, float* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
@@ -256,6 +267,14 @@ int gpet_batch_create_mapped(gpet_ctx* ctx, int B, int M, int N, int n_img, cons
 int gpet_batch_create_raw_mapped(gpet_ctx* ctx, int B, int M, int N, int n_img, const int32_t* image_of, const void* const* raw,
                                  int pix, const double* kern, int kh, int kw, const gpet_denoise* dn, const gpet_params* params,
                                  const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
+/* The same with a slot table (gpet_grad_images_multi): the n_img image slots of the map are made of n_frames raw frames and
+ * n_kern kernels, slot g of frame frame_of[g] with kernel kernel_of[g]; image_of maps the B edges to slots as ever.  The batch
+ * equals, bit for bit, the one gpet_batch_create_mapped builds from gpet_grad_images_multi's outputs; one kernel with one slot per
+ * frame in frame order is gpet_batch_create_raw_mapped itself.  GPET_ERR_BAD_ARG as for gpet_grad_images_multi and the map. */
+int gpet_batch_create_raw_multi(gpet_ctx* ctx, int B, int M, int N, int n_img, const int32_t* image_of, int n_frames,
+                                const void* const* raw, int pix, int n_kern, const double* const* kern, const int32_t* kh,
+                                const int32_t* kw, const int32_t* frame_of, const int32_t* kernel_of, const gpet_denoise* dn,
+                                const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out);
 void gpet_batch_destroy(gpet_batch* b);
 int gpet_batch_size(const gpet_batch* b);
 /* Images the batch holds: 1 if it shares one image, B with one image per edge, n_img with an image map.  That many pointers
@@ -293,6 +312,13 @@ int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, co
  * it was. */
 int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw,
                                  const gpet_denoise* dn, unsigned int flags);
+
+/* gpet_batch_set_raw_images_dn with a slot table (gpet_batch_create_raw_multi): n_frames frames, and a table of
+ * gpet_batch_image_count(b) slots.  A call refused with GPET_ERR_BAD_ARG (a bad table, the LDS bound, a null frame, a bad
+ * denoising spec) leaves the batch as it was. */
+int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* const* raw, int pix, int n_kern,
+                                    const double* const* kern, const int32_t* kh, const int32_t* kw, const int32_t* frame_of,
+                                    const int32_t* kernel_of, const gpet_denoise* dn, unsigned int flags);
 
 /* set / get the observation set (xy int64) of edge e (gpet.py:100,820,857). */
 int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs);
