@@ -66,6 +66,9 @@ def denoise_spec(denoise):
         technique, kwargs = denoise
     except (TypeError, ValueError):
         raise ValueError("denoise must be a (technique, kwargs) pair")
+    if technique == "nl":  # (a stage of its own: RawFrames takes it through nlmeans_spec)
+        raise NotImplementedError("denoising technique 'nl' is no gpet_denoise technique: with fast_mode=False it is built as a "
+                                  "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built")
     if technique in DN_NOT_BUILT:
         raise NotImplementedError("denoising technique %r is not built for the device (built: %s)"
                                   % (technique, ", ".join(sorted(DN_OF_TECHNIQUE))))
@@ -113,6 +116,77 @@ def denoised_dtype(dn, pix):
     if dn.technique == DN_TVC:
         return np.dtype(np.float64)
     return [dt for dt, code in PIX_OF_DTYPE.items() if code == pix][0]
+
+
+# non-local means (gpet_nlmeans, GPET_NLM_*): a stage of its own in front of the raw-frame path, not a gpet_denoise technique
+NLM_OUT_ON_DEVICE = 8  # gpet_nlmeans_images: out[] are device pointers
+NLM_PATCH_MAX, NLM_DIST_MAX = 15, 31
+NLM_KEYS = ("patch_size", "patch_distance", "h", "sigma", "fast_mode", "multichannel")
+
+
+class GpetNlmeans(C.Structure):
+    _fields_ = [("patch_size", C.c_int32), ("patch_distance", C.c_int32), ("h", C.c_double), ("sigma", C.c_double),
+                ("taps", C.c_void_p)]
+
+
+def nlmeans_taps(patch_size, h):
+    """The Gaussian patch weights of scikit-image's classic non-local means, formed with numpy exactly as the library forms them:
+    ``exp(-(x_a^2 + x_b^2) / (2 A^2))`` over ``x = -off .. off`` with ``A = (s - 1) / 4``, times ``1 / (sum * h * h)`` -> (s, s)."""
+    s = int(patch_size) + (1 if int(patch_size) % 2 == 0 else 0)
+    off = s // 2
+    A = (s - 1.0) / 4.0
+    x = np.arange(-off, off + 1, dtype=np.float64)
+    xr, xc = np.meshgrid(x, x, indexing="ij")
+    w = np.ascontiguousarray(np.exp(-(xr * xr + xc * xc) / (2 * A * A)))
+    w *= 1.0 / (np.sum(w) * h * h)
+    return w
+
+
+class NlmeansSpec(object):
+    """What nlmeans_spec returns: ``c`` the gpet_nlmeans of the call, ``taps`` the (s, s) float64 array it points to (kept alive
+    here), ``s`` the odd patch extent."""
+
+    def __init__(self, patch_size, patch_distance, h, sigma, taps):
+        self.s = patch_size + (1 if patch_size % 2 == 0 else 0)
+        self.taps = np.ascontiguousarray(taps, dtype=np.float64)
+        self.c = GpetNlmeans(patch_size=patch_size, patch_distance=patch_distance, h=h, sigma=sigma, taps=self.taps.ctypes.data)
+
+    def arg(self):
+        return C.byref(self.c)
+
+
+def nlmeans_spec(kwargs, taps=None):
+    """The keyword arguments of ``gpet_utils.denoise(image, 'nl', kwargs)`` = scikit-image's ``denoise_nl_means`` -> NlmeansSpec,
+    decided from the arguments alone (no device): ``patch_size`` (7), ``patch_distance`` (11), ``h`` (0.1), ``sigma`` (0.0),
+    ``fast_mode`` and ``multichannel=False``.  Only the classic algorithm is built: a missing or true ``fast_mode`` (the library's
+    default, another algorithm) raises NotImplementedError.  Any other key raises ValueError naming it, and so does a value the
+    device refuses.  ``taps``: (s, s) patch weights to use instead of the ones nlmeans_taps derives (a numpy whose exp differs in
+    the last place gives taps one unit apart; tests inject a fixture's)."""
+    kw = dict(kwargs or {})
+    for k in kw:
+        if k not in NLM_KEYS:
+            raise ValueError("denoise: keyword %r of 'nl' is not supported on the device (supported: %s)" % (k, ", ".join(NLM_KEYS)))
+    if kw.get("fast_mode", True):
+        raise NotImplementedError("denoising technique 'nl' is built for fast_mode=False only (scikit-image's classic non-local "
+                                  "means); fast_mode=True, the library's default, is another algorithm and not built for the "
+                                  "device: pass fast_mode=False")
+    if kw.get("multichannel", False):
+        raise ValueError("denoise: multichannel=True of 'nl' is not supported on the device (frames are 2-D, single-channel)")
+    ps, d = int(kw.get("patch_size", 7)), int(kw.get("patch_distance", 11))
+    h, sigma = float(kw.get("h", 0.1)), float(kw.get("sigma", 0.0))
+    s = ps + (1 if ps % 2 == 0 else 0)
+    if ps < 2 or s > NLM_PATCH_MAX:
+        raise ValueError("denoise: patch_size %r: patches of 3 x 3 to %d x %d pixels are built" % (ps, NLM_PATCH_MAX, NLM_PATCH_MAX))
+    if d < 0 or d > NLM_DIST_MAX:
+        raise ValueError("denoise: patch_distance %r: distances of 0 to %d are built" % (d, NLM_DIST_MAX))
+    if not (h > 0 and np.isfinite(h)) or not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError("denoise: h must be above 0 and sigma not negative")
+    if taps is None:
+        taps = nlmeans_taps(s, h)
+    taps = np.ascontiguousarray(taps, dtype=np.float64)
+    if taps.shape != (s, s):
+        raise ValueError("denoise: the taps of a %d x %d patch are an array of that shape, not %r" % (s, s, taps.shape))
+    return NlmeansSpec(ps, d, h, sigma, taps)
 
 
 class GpetParams(C.Structure):
@@ -323,6 +397,12 @@ class RawFrames(object):
     def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
+        # ('nl' is a stage of its own: the frames go through Context.nlmeans_images into device memory first -- see nlm_resolved)
+        self.nlm = None
+        if isinstance(denoise, NlmeansSpec):
+            self.nlm, denoise = denoise, None
+        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] == "nl":
+            self.nlm, denoise = nlmeans_spec(denoise[1]), None
         self.dn = denoise_spec(denoise)
         self.slots = None
         if slots is not None:
@@ -332,7 +412,7 @@ class RawFrames(object):
                 raise ValueError("a slot table has one frame index and one kernel index per image slot")
             kernel = self.kernels[0]
         self.kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
-        if kernel is None and self.dn is None:
+        if kernel is None and self.dn is None and self.nlm is None:
             raise ValueError("raw frames need a gradient kernel or a denoising technique")
         if self.kernel is not None and (self.kernel.ndim != 2 or self.kernel.size == 0):
             raise ValueError("the gradient kernel must be a non-empty 2-D array")
@@ -350,6 +430,18 @@ class RawFrames(object):
 
     def __len__(self):
         return len(self.ptrs)
+
+    def nlm_resolved(self, ctx, buf):
+        """These frames as the raw-frame calls take them: without non-local means, self; with it, the frames denoised into the
+        device memory of ``buf`` (a NlmFrames; enqueued on the context's stream) as float64 device frames with the same kernels and
+        slot table and no further denoising."""
+        if self.nlm is None:
+            return self
+        M, N = self.shape
+        ptrs = buf.reserve(len(self), M * N * 8)
+        ctx.nlmeans_images(self, out_device_ptrs=ptrs)
+        kernel = self.kernels if self.slots is not None else self.kernel
+        return RawFrames(kernel, device_ptrs=ptrs, dtype=np.float64, shape=(M, N), slots=self.slots)
 
     def pointer_array(self):
         return (_P * len(self.ptrs))(*self.ptrs)
@@ -398,6 +490,8 @@ SYMBOLS = {
                                    C.POINTER(_P)]),
     "gpet_denoise_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint,
                                       C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "gpet_nlmeans_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeans), C.c_uint,
+                                      C.POINTER(_P)]),
     "gpet_grad_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                       C.POINTER(GpetDenoise), C.c_uint, C.POINTER(_P)]),
     "gpet_grad_images_multi": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P),
@@ -557,6 +651,35 @@ def load():
     return lib
 
 
+class NlmFrames(object):
+    """Device memory (gpet_dev_alloc) for the float64 frames a non-local means pass leaves behind: owned by the object that
+    feeds them to the raw-frame path, grown on demand, reused from frame to frame, freed on close()."""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptr, self.bytes = ctx, None, 0
+
+    def reserve(self, n, frame_bytes):
+        """Room for n frames of frame_bytes each -> their device addresses."""
+        pitch = (int(frame_bytes) + 255) & ~255
+        if n * pitch > self.bytes:
+            self.close()
+            d = _P()
+            self.ctx.check(self.ctx.lib.gpet_dev_alloc(self.ctx.h, n * pitch, C.byref(d)))
+            self.ptr, self.bytes = d, n * pitch
+        return [self.ptr.value + g * pitch for g in range(n)]
+
+    def close(self):
+        if self.ptr is not None and getattr(self.ctx, "h", None):
+            self.ctx.lib.gpet_dev_free(self.ctx.h, self.ptr)  # (hipFree waits for the device)
+        self.ptr, self.bytes = None, 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """gpet_ctx: one device + one HIP stream."""
 
@@ -603,6 +726,12 @@ class Context:
     def grad_images(self, raw):
         """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32."""
         M, N = raw.shape
+        if raw.nlm is not None:  # (non-local means first, into device memory of this call; the calls below end with a wait)
+            buf = NlmFrames(self)
+            try:
+                return self.grad_images(raw.nlm_resolved(self, buf))
+            finally:
+                buf.close()
         if raw.slots is not None:  # (a slot table: gpet_grad_images_multi -> (n_slots, M, N), slot g of frame_of[g], kernel_of[g])
             ns = raw.n_slots
             out = np.empty((ns, M, N), dtype=np.float32)
@@ -624,6 +753,8 @@ class Context:
     def denoise_images(self, raw):
         """gpet_denoise_images: every frame of ``raw`` (a RawFrames with a denoising technique) denoised in one batched pass ->
         ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters)."""
+        if raw.nlm is not None:
+            return self.nlmeans_images(raw), np.zeros(len(raw), dtype=np.int32)
         if raw.dn is None:
             raise ValueError("no denoising technique")
         M, N = raw.shape
@@ -633,6 +764,26 @@ class Context:
         self.check(self.lib.gpet_denoise_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.dn_arg(), raw.flags, op,
                                                 n_iter.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, n_iter
+
+    def nlmeans_images(self, raw, out_device_ptrs=None):
+        """gpet_nlmeans_images: non-local means of every frame of ``raw`` (a RawFrames made with ``denoise=('nl', kwargs)`` or a
+        NlmeansSpec) in one batched pass -> (T, M, N) float64.  ``out_device_ptrs``: device addresses of float64 (M, N) frames to
+        write instead (GPET_NLM_OUT_ON_DEVICE; returns None) -- with frames on the device too, nothing is waited for."""
+        if raw.nlm is None:
+            raise ValueError("no non-local means spec")
+        M, N = raw.shape
+        T = len(raw)
+        if out_device_ptrs is not None:
+            if len(out_device_ptrs) != T:
+                raise ValueError("%d output frames for %d frames" % (len(out_device_ptrs), T))
+            op = (_P * T)(*[int(p) for p in out_device_ptrs])
+            self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), T, raw.pix, M, N, raw.nlm.arg(),
+                                                    raw.flags | NLM_OUT_ON_DEVICE, op))
+            return None
+        out = np.empty((T, M, N), dtype=np.float64)
+        op = (_P * T)(*[out[g].ctypes.data for g in range(T)])
+        self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), T, raw.pix, M, N, raw.nlm.arg(), raw.flags, op))
+        return out
 
     def normalise_f32(self, img):
         a = np.ascontiguousarray(img, dtype=np.float32)
@@ -789,6 +940,10 @@ class Batch:
         self.ctx = ctx
         self.lib = ctx.lib
         B = len(params)
+        self._nlm_buf = None  # device frames of a non-local means pass in front of the raw-frame path (NlmFrames), kept for set_images
+        if raw is not None and raw.nlm is not None:
+            self._nlm_buf = NlmFrames(ctx)
+            raw = raw.nlm_resolved(ctx, self._nlm_buf)
         if image_of is not None:
             if share_image:
                 raise ValueError("share_image and image_of are alternatives")
@@ -872,6 +1027,10 @@ class Batch:
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
             assert raw.n_slots == n_img and tuple(raw.shape) == (self.M, self.N)
+            if raw.nlm is not None:  # (refused before the images are swapped: the batch stays on its old frames)
+                if self._nlm_buf is None:
+                    self._nlm_buf = NlmFrames(self.ctx)
+                raw = raw.nlm_resolved(self.ctx, self._nlm_buf)
             if raw.slots is not None:  # (gpet_batch_set_raw_images_multi: the library checks the table)
                 nk, kp, kh, kw, fo, ko = raw.multi_args()
                 self.ctx.check(self.lib.gpet_batch_set_raw_images_multi(self.h, len(raw), raw.pointer_array(), raw.pix, nk, kp, kh, kw, fo,
@@ -1153,6 +1312,8 @@ class Batch:
         if getattr(self, "h", None):
             self.lib.gpet_batch_destroy(self.h)
             self.h = None
+            if getattr(self, "_nlm_buf", None) is not None:
+                self._nlm_buf.close()
             self.ctx._batch_closed()
 
     def __del__(self):

@@ -496,6 +496,71 @@ int gpet_denoise_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
   return rc;
 }
 
+// Non-local means (gpet_nlmeans_plan.h).  One device block, the same on both sides: source pointers | destination pointers | taps.
+// Host frames and host outputs go through the staging slot in chunks -- a chunk's frames, then its f64 results -- with one launch
+// per chunk; frames and outputs on the device are read and written where they lie by one launch.
+int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
+                        unsigned int flags, void* const* out) {
+  if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: bad argument");
+  NlmSpec sp;
+  sp.patch_size = spec->patch_size;
+  sp.patch_distance = spec->patch_distance;
+  sp.h = spec->h;
+  sp.sigma = spec->sigma;
+  sp.taps = spec->taps;
+  const int s = nlm_patch(sp.patch_size), d = sp.patch_distance;
+  if (const char* why = nlm_check(sp, pix, M, N)) {
+    if (s >= 3 && s <= NLM_PATCH_MAX && d >= 0 && d <= NLM_DIST_MAX && nlm_lds_bytes(s, d) > NLM_LDS_MAX)
+      return fail(c, GPET_ERR_BAD_ARG, "nlmeans: %s: patch %d, distance %d need %zu bytes, more than %zu", why, s, d, nlm_lds_bytes(s, d),
+                  NLM_LDS_MAX);
+    return fail(c, GPET_ERR_BAD_ARG, "nlmeans: %s (patch_size %d, patch_distance %d, h %g, sigma %g, frames %d x %d)", why, sp.patch_size, d,
+                sp.h, sp.sigma, M, N);
+  }
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: frame or output %d is a null pointer", g);
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_NLM_OUT_ON_DEVICE) != 0;
+  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
+  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
+  const StagePlan plan = st_in + st_out ? stage_plan(n_img, st_in + st_out) : StagePlan{n_img, 1, 0, 0};
+  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.slots * plan.slot_bytes);
+  if (rc) return rc;
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_w = 2 * o_dst, tab_bytes = o_w + sizeof(double) * (size_t)(s * s);
+  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
+  if (rc) return rc;
+  c->h_raw_tab.resize(tab_bytes);
+  char* h = c->h_raw_tab.data();
+  const void** h_src = (const void**)h;
+  void** h_dst = (void**)(h + o_dst);
+  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
+  for (int k = 0; k < plan.n_chunks; ++k)
+    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
+      const int g = stage_first(plan, k) + i;
+      char* slot = plan.slots ? c->raw_dev + (size_t)stage_slot(plan, k) * plan.slot_bytes : nullptr;
+      h_src[g] = in_dev ? raw[g] : slot + (size_t)i * st_in;
+      h_dst[g] = out_dev ? out[g] : slot + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
+    }
+  memcpy(h + o_w, sp.taps, sizeof(double) * (size_t)(s * s));
+  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  const void* const* d_src = (const void* const*)c->raw_tab;
+  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
+  const double* d_w = (const double*)(c->raw_tab + o_w);
+  const double var2 = 2.0 * sp.sigma * sp.sigma;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
+    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
+    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_nlmeans(c->stream, pix, d_src, d_dst, first, cnt, M, N, s, d, d_w, var2);
+    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
+  }
+  // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
+  if (!in_dev || !out_dev || e != hipSuccess) (void)gpet_wait(c->stream);
+  HIPCHK(c, e);
+  return GPET_OK;
+}
+
 int gpet_normalise_f32(gpet_ctx* c, const float* img, size_t count, float* out) {
   if (!c || !img || !out || count == 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_normalise_f32: bad argument");
   HIPCHK(c, hipSetDevice(c->device));

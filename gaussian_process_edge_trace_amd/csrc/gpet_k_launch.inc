@@ -134,6 +134,37 @@ hipError_t launch_dn_rank(hipStream_t st, int pix, const void* const* d_src, int
   }
   return hipGetLastError();
 }
+// ---- a0: non-local means (gpet_k_nlmeans.inc; geometry: gpet_nlmeans_plan.h) ----
+template <typename T>
+static void launch_nlmeans_t(hipStream_t st, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N, int s, int d,
+                             const double* d_taps, double var2) {
+  const NlmGrid g = nlm_grid(M, N);
+  const dim3 gs(g.gx, g.gy, n), bs(NLM_TILE, NLM_TILE);
+  const size_t lds = nlm_lds_bytes(s, d);
+  const T* const* src = (const T* const*)d_src;
+  if (s == 7)
+    hipLaunchKernelGGL((k_nlmeans<T, 7>), gs, bs, lds, st, src, d_dst, img0, M, N, s, d, d_taps, var2);
+  else
+    hipLaunchKernelGGL((k_nlmeans<T, 0>), gs, bs, lds, st, src, d_dst, img0, M, N, s, d, d_taps, var2);
+}
+hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N, int s,
+                          int d, const double* d_taps, double var2) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  const NlmGrid g = nlm_grid(M, N);
+  if (!pix_bytes(pix) || n < 1 || s < 3 || s % 2 == 0 || s > NLM_PATCH_MAX || d < 0 || d > NLM_DIST_MAX || s / 2 >= (M < N ? M : N) ||
+      nlm_lds_bytes(s, d) > NLM_LDS_MAX || g.gy > 65535)
+    return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    switch (pix) {
+      case PIX_U8: launch_nlmeans_t<uint8_t>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
+      case PIX_U16: launch_nlmeans_t<uint16_t>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
+      case PIX_F32: launch_nlmeans_t<float>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
+      default: launch_nlmeans_t<double>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
+    }
+  }
+  return hipGetLastError();
+}
 template <typename T>
 static void launch_dn_gauss_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
                               const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {

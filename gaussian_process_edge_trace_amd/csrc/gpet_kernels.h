@@ -6,6 +6,7 @@
 #include "gpet_conv_plan.h"   // pixel types, conv geometry, staging plan
 #include "gpet_conv_multi_plan.h"  // slot table of a multi-kernel source: validation, union patch, slots of each frame
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
+#include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 
 namespace gpet {
@@ -36,6 +37,10 @@ hipError_t launch_dn_gauss(hipStream_t st, int pix, const void* const* d_src, in
 // counter of the chunk)
 hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
                               int it, char* ws, const DenoiseLayout& L, int* d_n_iter, int* d_n_done);
+// a0, non-local means (gpet_nlmeans_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) -> the f64
+// frames of the DEVICE pointer table d_dst at the same indices; s: the odd patch extent, d_taps: [s * s] on the device
+hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N, int s,
+                          int d, const double* d_taps, double var2);
 hipError_t launch_fit_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int want_cov,
                               unsigned parts = ~0u);
 hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

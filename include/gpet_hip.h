@@ -224,6 +224,33 @@ int gpet_grad_images_dn(gpet_ctx* ctx, const void* const* raw, int n_img, int pi
 int gpet_grad_images_multi(gpet_ctx* ctx, const void* const* raw, int n_frames, int pix, int M, int N, int n_kern,
                            const double* const* kern, const int32_t* kh, const int32_t* kw, const gpet_denoise* dn, int n_img,
                            const int32_t* frame_of, const int32_t* kernel_of, unsigned int flags, float* const* out);
+/* ---- a0: non-local means, gpet_utils.denoise(image, 'nl', kwargs) (gpet_utils.py:133-134) -- */
+/* scikit-image 0.18.3's denoise_nl_means(image, patch_size, patch_distance, h, fast_mode=False, sigma) on 2-D single-channel
+ * frames, bit for bit: the classic algorithm (Gaussian-weighted patch distances, the 5.0 cutoff at patch-row starts, the
+ * integer-trick exponential), in float64, in the library's order of operations (csrc/gpet_nlmeans_plan.h states it).  A stage of
+ * its own, not a gpet_denoise technique: milliseconds per frame, one kernel launch per staging chunk.  fast_mode=True (the
+ * library's default, another algorithm) is not built.  The frame is widened to float64 as it is -- u8 / u16 frames keep their
+ * range, so h and sigma are in the frame's units -- and the result is float64; an f32 frame gives the library's result on the
+ * frame widened to f64 (the library would run in f32).  The weight of a candidate whose final patch distance exceeds 708 is
+ * +0.0 (there the library's exponential is undefined): parity is claimed where no final distance exceeds 708. */
+typedef struct gpet_nlmeans {
+  int32_t patch_size;     /* an even size means the next odd one s; 3 <= s <= 15, s / 2 < min(M, N); skimage's default 7 */
+  int32_t patch_distance; /* d: candidates up to d pixels away in each direction, 0 <= d <= 31; skimage's default 11 */
+  double h;               /* above 0: cut-off distance in grey levels; skimage's default 0.1 */
+  double sigma;           /* not negative: noise standard deviation, 2 sigma^2 is taken off every squared difference */
+  const double* taps;     /* host, [s * s]: w[a][b] = exp(-(x_a^2 + x_b^2) / (2 A^2)) / (sum h^2), A = (s - 1) / 4 -- an input,
+                           * because numpy's exp and the C library's differ in the last place for some arguments */
+} gpet_nlmeans;
+/* out[] are DEVICE pointers (f64 [M*N] each) on the context's device: with GPET_RAW_ON_DEVICE too, nothing is waited for -- the
+ * stage is enqueued on the context's stream and whatever follows on that stream reads its output */
+#define GPET_NLM_OUT_ON_DEVICE 8u
+/* Non-local means of n_img frames [M*N] of pixel type pix: out[g] f64 [M*N] receives frame g.  Host frames go up in the staging
+ * chunks of the raw-frame calls.  flags: GPET_RAW_ON_DEVICE, GPET_NLM_OUT_ON_DEVICE.  GPET_ERR_BAD_ARG, gpet_last_error naming
+ * the cause, for a patch below 3 or above 15, d above 31, a patch radius not below min(M, N), h <= 0, sigma < 0, taps that are
+ * not finite, a tile neighbourhood (16 + 2 d + 2 (s / 2) pixels each way, f64) beyond 64 KB of LDS, an unknown pix, a null
+ * frame or output. */
+int gpet_nlmeans_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
+                        unsigned int flags, void* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
