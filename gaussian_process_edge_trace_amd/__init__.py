@@ -8,6 +8,7 @@ from . import gpet_utils
 from . import _lib
 from .sequence import SequenceTracer, trace_sequence
 from .pipeline import run_in_flight
+from .ensemble import trace_ensemble
 
 __all__ = ["GP_Edge_Tracing", "GaussianProcessRegressor", "gpet_utils", "GP_Edge_Tracing_Batch", "SequenceTracer",
-           "trace_sequence", "run_in_flight"]
+           "trace_sequence", "run_in_flight", "trace_ensemble"]

@@ -231,6 +231,107 @@ def decode_results(raw, n, len_cap):
     return {k: np.array(rec[k]) for k in dt.names}
 
 
+# seed ensembles (gpet_batch_ensemble)
+ENSEMBLE_MAX = 1024  # GPET_ENSEMBLE_MAX: members of one group
+
+
+class GpetEnsembleHead(C.Structure):
+    """gpet_ensemble_head: the head of one group's record (gpet_batch_ensemble)."""
+    _fields_ = [("n_members", C.c_int32), ("edge_len", C.c_int32), ("x_st", C.c_int32), ("medoid", C.c_int32),
+                ("best_cost", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double)]
+
+
+ENSEMBLE_F64 = ("median", "q_lo", "q_hi", "min", "max")  # the f64 sections of a record, in order
+
+
+def ensemble_layout(n_groups, n_edges, len_cap):
+    """The layout csrc/gpet_ensemble_plan.h computes, for hosts and tests that build or decode an ensemble buffer without a
+    device: dict(record_bytes, off_trace, off_median, off_q_lo, off_q_hi, off_min, off_max, off_agree, off_cost, off_off,
+    total_bytes); ValueError for arguments that describe no buffer."""
+    G, B, L = int(n_groups), int(n_edges), int(len_cap)
+    if G < 1 or B < 1 or L < 1 or L > 1 << 24:
+        raise ValueError("no ensemble buffer for n_groups=%d n_edges=%d len_cap=%d" % (G, B, L))
+    d = dict(off_trace=C.sizeof(GpetEnsembleHead))
+    off = d["off_trace"] + 16 * L
+    for k in ENSEMBLE_F64:
+        d["off_" + k] = off
+        off += 8 * L
+    d["off_agree"] = off
+    d["record_bytes"] = off + ((4 * L + 7) & ~7)
+    d["off_cost"] = G * d["record_bytes"]
+    d["off_off"] = d["off_cost"] + 8 * B
+    d["total_bytes"] = d["off_off"] + ((4 * B + 7) & ~7)
+    return d
+
+
+def ensemble_bytes(n_groups, n_edges, len_cap):
+    """Bytes gpet_batch_ensemble writes for ``n_groups`` groups over ``n_edges`` edges of up to ``len_cap`` points
+    (gpet_ensemble_bytes)."""
+    n = C.c_size_t()
+    rc = load().gpet_ensemble_bytes(int(n_groups), int(n_edges), int(len_cap), C.byref(n))
+    if rc:
+        raise GpetError(rc, "gpet_ensemble_bytes(%d, %d, %d)" % (int(n_groups), int(n_edges), int(len_cap)))
+    return n.value
+
+
+def decode_ensemble(raw, n_groups, n_edges, len_cap, group_of=None):
+    """What gpet_batch_ensemble wrote (include/gpet_hip.h, "seed ensembles"), plain numpy, no device: (groups, cost, off) with
+    ``cost`` (n_edges,) f64 the final cost of every edge, ``off`` (n_edges,) int32 (-1: not a member of any group) and one dict per
+    group: ``n_members``, ``edge_len``, ``x_st``, ``tol``, ``medoid``, ``best_cost`` (edge indices, -1 without members), ``trace``
+    (edge_len, 2) int64 yx, ``median``, ``q_lo``, ``q_hi``, ``min``, ``max`` (edge_len,) f64 and ``agree`` (edge_len,) int32 --
+    and, with ``group_of`` (the table the call was given), ``members`` (edge indices, ascending) with their ``off`` and ``cost``."""
+    G, B, L = int(n_groups), int(n_edges), int(len_cap)
+    lay = ensemble_layout(G, B, L)
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    if buf.size < lay["total_bytes"]:
+        raise ValueError("an ensemble of %d groups, %d edges, len_cap %d needs %d bytes, got %d" % (G, B, L, lay["total_bytes"], buf.size))
+    dt = np.dtype([("n_members", "<i4"), ("edge_len", "<i4"), ("x_st", "<i4"), ("medoid", "<i4"), ("best_cost", "<i4"),
+                   ("reserved", "<i4"), ("tol", "<f8"), ("trace", "<i8", (L, 2))] + [(k, "<f8", (L,)) for k in ENSEMBLE_F64]
+                  + [("agree", "<i4", (L,)), ("pad", "u1", (lay["record_bytes"] - lay["off_agree"] - 4 * L,))])
+    assert dt.itemsize == lay["record_bytes"] and dt.fields["trace"][1] == lay["off_trace"] and dt.fields["agree"][1] == lay["off_agree"]
+    rec = np.frombuffer(buf[:lay["off_cost"]].tobytes(), dtype=dt, count=G)
+    cost = np.frombuffer(buf[lay["off_cost"]:lay["off_off"]].tobytes(), dtype="<f8").copy()
+    off = np.frombuffer(buf[lay["off_off"]:lay["off_off"] + 4 * B].tobytes(), dtype="<i4").copy()
+    if group_of is not None:
+        group_of = np.asarray(group_of).reshape(-1)
+        if group_of.shape[0] != B:
+            raise ValueError("group_of has %d entries for %d edges" % (group_of.shape[0], B))
+    groups = []
+    for g in range(G):
+        n = max(0, min(int(rec["edge_len"][g]), L))
+        d = dict(n_members=int(rec["n_members"][g]), edge_len=n, x_st=int(rec["x_st"][g]), tol=float(rec["tol"][g]),
+                 medoid=int(rec["medoid"][g]), best_cost=int(rec["best_cost"][g]), trace=np.array(rec["trace"][g, :n]),
+                 agree=np.array(rec["agree"][g, :n]))
+        for k in ENSEMBLE_F64:
+            d[k] = np.array(rec[k][g, :n])
+        if group_of is not None:
+            d["members"] = np.flatnonzero((group_of == g) & (off >= 0)).astype(np.int64)
+            d["off"] = off[d["members"]]
+            d["cost"] = cost[d["members"]]
+        groups.append(d)
+    return groups, cost, off
+
+
+def check_group_table(group_of, n_edges):
+    """``group_of`` as the int32 table gpet_batch_ensemble takes and its number of groups; ValueError for a table of the wrong
+    length, an index below -1 or a group index that does not occur (what needs no device to be refused)."""
+    g = np.asarray(group_of)
+    if g.ndim != 1 or g.shape[0] != int(n_edges):
+        raise ValueError("group_of must hold one group index per edge (%d), got shape %s" % (int(n_edges), g.shape))
+    if g.size and not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("group_of must hold integers")
+    g = g.astype(np.int32)
+    if (g < -1).any():
+        raise ValueError("group_of holds an index below -1 (-1 means: in no group)")
+    n_groups = int(g.max()) + 1 if g.size else 0
+    if n_groups < 1:
+        raise ValueError("group_of assigns no edge to a group")
+    missing = sorted(set(range(n_groups)) - set(g.tolist()))
+    if missing:
+        raise ValueError("group_of never uses group %d of %d (every index must occur)" % (missing[0], n_groups))
+    return np.ascontiguousarray(g), n_groups
+
+
 # iteration history (gpet_batch_set_history): what a record holds beyond its head
 HISTORY_LEVELS = {None: 0, "off": 0, "obs": 1, "curves": 2, "full": 3}
 
@@ -577,6 +678,9 @@ SYMBOLS = {
     "gpet_history_layout": (C.c_int, [_P, C.POINTER(GpetHistoryPlan)]),
     "gpet_batch_history": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),
     "gpet_history_record": (C.c_int, [_P]),
+    "gpet_batch_final_costs": (C.c_int, [_P, _P, C.c_int]),
+    "gpet_ensemble_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
+    "gpet_batch_ensemble": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_double, C.c_int64, _P, C.c_int]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1202,6 +1306,31 @@ class Batch:
         raw = np.empty(max(1, self.B * result_bytes(L)), dtype=np.uint8)
         self.ctx.check(self.lib.gpet_batch_results(self.h, L, raw.ctypes.data, 0))
         return decode_results(raw, self.B, L)
+
+    def final_costs(self):
+        """The scorer's cost of every edge's converged mean curve on its own gradient image, (B,) f64 (gpet_batch_final_costs:
+        the reference's cost_funct(optim_mean_curve), gpet.py:888-890); +inf for an edge whose device status is not OK.  Valid
+        when ``results`` is; the loop's samples and scores are not touched."""
+        out = np.empty(self.B, dtype=np.float64)
+        self.ctx.check(self.lib.gpet_batch_final_costs(self.h, out.ctypes.data, 0))
+        return out
+
+    def ensemble(self, group_of, tol=2.0, len_cap=None, device_ptr=None):
+        """Per-column consensus over the converged fits of every group of edges (gpet_batch_ensemble; include/gpet_hip.h has the
+        definition): ``group_of`` one group index per edge (-1: in no group), ``tol`` in pixels.  Returns ``decode_ensemble``'s
+        (groups, cost, off).  ``device_ptr``: the buffer (``ensemble_bytes`` bytes of device memory) is filled on the device
+        instead and nothing is returned; the call is then only enqueued on the context's stream."""
+        g, n_groups = check_group_table(group_of, self.B)
+        if not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
+        L = self._max_info("Lg") if len_cap is None else int(len_cap)
+        gp = g.ctypes.data_as(C.POINTER(C.c_int32))
+        if device_ptr is not None:
+            self.ctx.check(self.lib.gpet_batch_ensemble(self.h, n_groups, gp, float(tol), L, int(device_ptr), 1))
+            return None
+        raw = np.empty(ensemble_layout(n_groups, self.B, L)["total_bytes"], dtype=np.uint8)
+        self.ctx.check(self.lib.gpet_batch_ensemble(self.h, n_groups, gp, float(tol), L, raw.ctypes.data, 0))
+        return decode_ensemble(raw, n_groups, self.B, L, g)
 
     def set_history(self, level, iter_cap=64):
         """Iteration history of the traces this batch runs (gpet_batch_set_history): ``level`` None / 'obs' / 'curves' / 'full'

@@ -383,6 +383,7 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->d_fin_n) (void)hipFree(b->d_fin_n);
   if (b->d_results) (void)hipFree(b->d_results);
   if (b->d_hist) (void)hipFree(b->d_hist);
+  ensemble_free(b);
   if (b->fit) {
     (void)hipStreamSynchronize(b->fit);
     (void)hipStreamDestroy(b->fit);

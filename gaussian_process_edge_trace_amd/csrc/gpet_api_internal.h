@@ -23,6 +23,8 @@
 //   gpet_api_history.hip the iteration history (k_history): gpet_batch_set_history, gpet_history_layout, gpet_batch_history,
 //                        gpet_history_record
 //   gpet_history_plan.h  the history's record layout and storage size as plain data (no HIP)
+//   gpet_api_ensemble.hip seed ensembles: gpet_batch_final_costs, gpet_ensemble_bytes, gpet_batch_ensemble
+//   gpet_ensemble_plan.h the layout of an ensemble's buffer, the validation of its arguments, member tables and tile width (no HIP)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -148,6 +150,9 @@ struct gpet_batch {
   bool have_last_fit = false;
   char* d_results = nullptr;           // device staging of gpet_batch_results into host memory (grown on demand)
   size_t results_bytes = 0;
+  // seed ensembles (gpet_api_ensemble.hip): the scratch of gpet_batch_final_costs / gpet_batch_ensemble, allocations of their own made
+  // on first use (nullptr: never called -- the batch then holds and enqueues nothing for them)
+  struct EnsembleScratch* ens = nullptr;
   // iteration history (gpet_batch_set_history): storage of its own, B regions of hist.edge_bytes (gpet_history_plan.h); hist.level == 0
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;
@@ -220,6 +225,9 @@ int enqueue_results(gpet_batch* b, int64_t len_cap, void* d_dst);
 // ---- gpet_api_history.hip -------------------------------------------------------------------------------------------------
 // empties the iteration history of edge e (e < 0: of every edge) on the context's stream: whatever starts another trace calls it
 int history_clear(gpet_batch* b, int e);
+// ---- gpet_api_ensemble.hip ------------------------------------------------------------------------------------------------
+// frees the scratch of the ensemble entry points (gpet_batch_destroy)
+void ensemble_free(gpet_batch* b);
 // ---- gpet_api_batch.hip ---------------------------------------------------------------------------------------------------
 int fetch_all_scalars(gpet_batch* b);
 int check_device_status(gpet_batch* b);

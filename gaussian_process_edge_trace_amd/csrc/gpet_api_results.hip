@@ -7,20 +7,6 @@
 
 namespace gpet {
 
-// int64 of an integer-valued double, from its bits: what x86's truncating conversion (numpy's astype(int)) gives, INT64_MIN
-// for NaN and out-of-range values included.  (The compiler's f64 -> i64 conversion splits the value with a fused
-// multiply-add; this keeps the kernel free of them, so the disassembly shows that the interval is not contracted.)
-__device__ inline long long int_f64_to_i64(double r) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(r);
-  const int biased = (int)((u >> 52) & 0x7ff);
-  if (biased < 1023) return 0;                             // |r| < 1: rint left +-0 (subnormals are not integers)
-  const int ex = biased - 1075;                            // |r| = mant * 2^ex
-  if (ex >= 11) return (long long)0x8000000000000000ull;   // |r| >= 2^63, inf, NaN
-  const unsigned long long mant = (u & 0xfffffffffffffull) | (1ull << 52);
-  const unsigned long long mag = ex >= 0 ? mant << ex : mant >> -ex;
-  return (u >> 63) ? -(long long)mag : (long long)mag;
-}
-
 // One workgroup per edge, striding over len_cap.  fin_out of edge e: mean (pixels) at [0, Lg), std (standardised units, as
 // the reference returns it) at [out_stride, out_stride + Lg); theta [B][4] = log(constant, length_scale, noise_level), -LML.
 __global__ __launch_bounds__(256) void k_finish_results(const EdgeDev* __restrict__ edges, const double* __restrict__ theta,

@@ -850,34 +850,42 @@ hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, 
   return launch_kde(st, d_edges, B, bd, 0, 2u, 1);  // (k_kde_fused, raw band: the loop's form)
 }
 
+// the costs of rows 0 .. S - 1 of every edge's sample matrix (S = bd.S: launch_score's first part; S = 1: the one-row views of
+// launch_final_costs).  Which kernels run is decided by the BATCH's shape, bd, whatever S is: a row's cost does not depend on S
+hipError_t launch_score_rows(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int S, bool no_combine) {
+  (void)hipGetLastError();
+  const size_t lds = (size_t)(2 * SC_PAIRS + 2) * (bd.M | 1) * sizeof(float);
+  if (lds <= 150 * 1024 && B * 1 > 0 && bd.S >= 64) {
+    static PerDeviceOnce once;
+    if (once.first())
+    {
+      (void)hipFuncSetAttribute((const void*)k_score_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+      (void)hipFuncSetAttribute((const void*)k_score_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    }
+    const int n_tiles = cdiv((bd.Lg - 2) / 2, SC_PAIRS);
+    // curves per workgroup: 1024, or down to 128 while the tiles alone leave CUs empty (every part stages the slab again)
+    int cpw = SC_CURVES;
+    while (cpw > 128 && B * n_tiles * cdiv(S, cpw) < 256) cpw >>= 1;
+    if (bd.y_f32) hipLaunchKernelGGL(k_score_tile<true>, dim3(n_tiles, cdiv(S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
+    else hipLaunchKernelGGL(k_score_tile<false>, dim3(n_tiles, cdiv(S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
+    if (!no_combine) hipLaunchKernelGGL(k_score_combine, dim3(cdiv(S, 256), B), dim3(256), 0, st, d_edges, n_tiles);
+  } else {
+    if (bd.y_f32) hipLaunchKernelGGL(k_score<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, d_edges);
+    else hipLaunchKernelGGL(k_score<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, d_edges);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts, bool no_combine) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (parts & 1u) {
-    const size_t lds = (size_t)(2 * SC_PAIRS + 2) * (bd.M | 1) * sizeof(float);
-    if (lds <= 150 * 1024 && B * 1 > 0 && bd.S >= 64) {
-      static PerDeviceOnce once;
-      if (once.first())
-      {
-        (void)hipFuncSetAttribute((const void*)k_score_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_score_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      }
-      const int n_tiles = cdiv((bd.Lg - 2) / 2, SC_PAIRS);
-      // curves per workgroup: 1024, or down to 128 while the tiles alone leave CUs empty (every part stages the slab again)
-      int cpw = SC_CURVES;
-      while (cpw > 128 && B * n_tiles * cdiv(bd.S, cpw) < 256) cpw >>= 1;
-      if (bd.y_f32) hipLaunchKernelGGL(k_score_tile<true>, dim3(n_tiles, cdiv(bd.S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
-      else hipLaunchKernelGGL(k_score_tile<false>, dim3(n_tiles, cdiv(bd.S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
-      if (!no_combine) hipLaunchKernelGGL(k_score_combine, dim3(cdiv(bd.S, 256), B), dim3(256), 0, st, d_edges, n_tiles);
-    } else {
-      if (bd.y_f32) hipLaunchKernelGGL(k_score<true>, dim3(cdiv(bd.S, 4), B), dim3(256), 0, st, d_edges);
-      else hipLaunchKernelGGL(k_score<false>, dim3(cdiv(bd.S, 4), B), dim3(256), 0, st, d_edges);
-    }
-  }
+  hipError_t e_rows = hipSuccess;
+  if (parts & 1u) e_rows = launch_score_rows(st, d_edges, B, bd, bd.S, no_combine);
   if (parts & 2u) {
     if (bd.S <= 1024 && !opt(Opt::topk_rank)) hipLaunchKernelGGL(k_topk_sort, dim3(1, B), dim3(512), 0, st, d_edges);
     else hipLaunchKernelGGL(k_topk, dim3(cdiv(bd.S, 256), B), dim3(256), 0, st, d_edges);
   }
-  return hipGetLastError();
+  const hipError_t e_top = hipGetLastError();
+  return e_rows != hipSuccess ? e_rows : e_top;
 }
 
 hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const gpet_history_plan& P, int iter_expect) {

@@ -8,8 +8,23 @@
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
+#include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 
 namespace gpet {
+
+// int64 of an integer-valued double, from its bits: what x86's truncating conversion (numpy's astype(int)) gives, INT64_MIN
+// for NaN and out-of-range values included.  (The compiler's f64 -> i64 conversion splits the value with a fused
+// multiply-add; this keeps the kernel free of them, so the disassembly shows that the interval is not contracted.)
+__device__ inline long long int_f64_to_i64(double r) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(r);
+  const int biased = (int)((u >> 52) & 0x7ff);
+  if (biased < 1023) return 0;                             // |r| < 1: rint left +-0 (subnormals are not integers)
+  const int ex = biased - 1075;                            // |r| = mant * 2^ex
+  if (ex >= 11) return (long long)0x8000000000000000ull;   // |r| >= 2^63, inf, NaN
+  const unsigned long long mant = (u & 0xfffffffffffffull) | (1ull << 52);
+  const unsigned long long mag = ex >= 0 ? mant << ex : mant >> -ex;
+  return (u >> 63) ? -(long long)mag : (long long)mag;
+}
 
 hipError_t launch_conv(hipStream_t st, const double* d_img, int M, int N, const double* d_wf, int kh, int kw, int oy,
                        int ox, float* d_tmp, unsigned int* d_minmax);
@@ -87,7 +102,18 @@ hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const g
 hipError_t launch_pixels_reset(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);
 hipError_t launch_sample(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int rank_max = 0);
 hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts = ~0u, bool no_combine = false);
+// part 1 of launch_score (the costs) over the first S rows of every edge's sample matrix, by the variant bd selects (launch_score: S = bd.S)
+hipError_t launch_score_rows(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int S, bool no_combine);
 bool score_tail_applies(const BatchDims& bd);
+// seed ensembles (gpet_k_ensemble.inc).  Final costs: the scorer on a one-row view of every edge's converged mean -- view / view_sc
+// [B], rows [B][row_stride] doubles (row_stride >= the widest row pitch), part [B][fincost_part_stride] doubles, cost [B]
+size_t fincost_part_stride(const BatchDims& bd);
+hipError_t launch_final_costs(hipStream_t st, const EdgeDev* d_edges, int B, const BatchDims& bd, EdgeDev* d_view, gpet_scalars* d_view_sc,
+                              double* d_rows, size_t row_stride, double* d_part, double* d_cost);
+// the reduction (k_ensemble over the plan's workgroups, then k_ensemble_pick) into DEVICE memory d_dst, zeroed by the caller like d_off_acc [B]
+hipError_t launch_ensemble(hipStream_t st, const EdgeDev* d_edges, int B, int G, const EnsembleGroup* d_groups, const int32_t* d_members,
+                           const int32_t* d_member_group, const int32_t* d_wg_group, const int32_t* d_wg_tile, int n_wg, size_t lds,
+                           double tol, long long len_cap, const EnsembleLayout& L, const double* d_cost, int* d_off_acc, char* d_dst);
 hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);
 
 // converged fit on the device (gpet_lbfgsb.hip): training sets + start points, L-BFGS-B state machines, best restart

@@ -30,5 +30,6 @@ namespace gpet {
 #include "gpet_k_warm.inc"
 #include "gpet_k_history.inc"
 #include "gpet_k_launch.inc"
+#include "gpet_k_ensemble.inc"
 
 }  // namespace gpet

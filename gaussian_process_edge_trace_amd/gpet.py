@@ -269,6 +269,12 @@ class GP_Edge_Tracing(object):
         self.score_thresh = b.scalars().score_thresh
         return b.read(_lib.BUF_OBS)
 
+    def final_cost(self):
+        """The cost of the converged mean curve of the last ``__call__`` -- the reference's ``cost_funct(optim_mean_curve)``, the
+        last entry of its ``iter_optimal_costs`` (gpet.py:888-890) -- computed on the device from the converged fit
+        (gpet_batch_final_costs); the samples and scores of the loop stay as they are.  GpetError before ``__call__``."""
+        return float(self._batch.final_costs()[0])
+
     def history(self):
         """The iteration history of the last ``__call__`` (constructor keyword ``history``): the dict ``_lib.decode_history``
         gives for this edge -- ``obs``, ``score_thresh``, ``optimal_cost``, ``best_idx`` per iteration, from 'curves'
@@ -713,6 +719,41 @@ class GP_Edge_Tracing_Batch(object):
         theta, nlml)).  Valid after ``__call__`` or ``finish``; before a converged fit of the current trace it raises
         GpetError."""
         return results_from_records(self._batch.results(), self.return_std)
+
+    def final_costs(self):
+        """(B,) f64: the scorer's cost of every edge's converged mean curve on its own gradient image -- the reference's
+        ``cost_funct(optim_mean_curve)`` (gpet.py:888-890), the algorithm's own figure of merit for a finished trace -- computed on
+        the device (gpet_batch_final_costs); +inf for an edge the device stopped with an error.  Valid when ``results`` is, raises
+        what it raises; the loop's samples and scores are not touched."""
+        return self._batch.final_costs()
+
+    def group_table(self, group_of=None):
+        """``group_of`` of ``ensemble`` as the int32 table the library takes; None: one group of all edges, a ValueError if their
+        x-grids differ.  Needs no device."""
+        if group_of is None:
+            grids = {(p["x_st"], p["x_en"]) for p in self._ps}
+            if len(grids) > 1:
+                raise ValueError("ensemble(group_of=None) makes ONE group of all edges, but their x-grids differ: %s"
+                                 % sorted(grids)[:4])
+            group_of = np.zeros(self.B, dtype=np.int32)
+        return _lib.check_group_table(group_of, self.B)[0]
+
+    def ensemble(self, group_of=None, tol=2):
+        """Consensus across the traces of one edge (gpet_batch_ensemble): ``group_of`` one group index per edge, -1 for "in no
+        group" (None: one group of all edges); the members of a group are its edges minus those the device stopped with an error.
+        Per group and column the order statistics of the members' converged means are taken on the device; returns one dict per
+        group: ``trace`` (Lg, 2) int64 yx, the rounded median; ``median``, ``q_lo``, ``q_hi``, ``min``, ``max`` (Lg,);
+        ``agree`` (Lg,) members within ``tol`` pixels of the consensus per column; ``members`` (edge indices) with ``off`` (columns
+        where the member is more than ``tol`` pixels off the consensus) and ``cost`` (``final_costs``) per member; ``medoid`` (the
+        member with the smallest ``off``, then cost, then index -- a real trace, what ``GP_Edge_Tracing`` returns for its seed) and
+        ``best_cost`` (the member of smallest cost), both edge indices, -1 in a group without members.  Valid when ``results``
+        is, raises what it raises."""
+        g = self.group_table(group_of)
+        if not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
+        groups, _, _ = self._batch.ensemble(g, tol)
+        keys = ("trace", "median", "q_lo", "q_hi", "min", "max", "agree", "members", "off", "cost", "medoid", "best_cost")
+        return [{k: d[k] for k in keys} for d in groups]
 
     def __call__(self, max_iter=1000):
         t0 = t.time()

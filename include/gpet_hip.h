@@ -606,6 +606,49 @@ int gpet_result_bytes(int64_t len_cap, size_t* bytes);
 int gpet_batch_results(gpet_batch* b, int64_t len_cap, void* dst, int dst_on_device);
 int gpet_gather_results(gpet_comm* comm, gpet_batch* local, int64_t n_edges, int64_t len_cap, void* h_all);
 
+/* ---- seed ensembles: final costs and a per-column consensus over the traces of one edge -------------------------------------
+ * The tracer is stochastic; a batch that traces one edge with many seeds holds many converged fits of it.  Two reductions are
+ * made where those fits lie (fin_out), both valid exactly when gpet_batch_results is (after gpet_final_fit_all on the current
+ * trace; GPET_ERR_BAD_ARG otherwise) and both leaving the loop's state -- samples, costs, best curves, scalars, history --
+ * untouched (their scratch is an allocation of its own, made on first use):
+ *   gpet_batch_final_costs(batch, dst, on_device)   cost[e], f64 [B]: the scorer's cost of edge e's converged mean curve on its
+ *       own gradient image -- cost_funct(optim_mean_curve), gpet.py:888-890 -- bit for bit what gpet_score_curves writes to
+ *       costs[s] when that curve stands in row s of edge e's sample matrix in this batch (the same kernels, launched on a
+ *       one-row view of the means; with f32 samples the mean is rounded to f32 as a write of the samples rounds it).  An edge
+ *       whose gpet_scalars.status is not GPET_OK gets +inf.
+ *   gpet_batch_ensemble(batch, G, group_of, tol, len_cap, dst, on_device)   group_of[B]: the group of every edge in [0, G), or -1
+ *       for "in no group"; every index in [0, G) occurs; all edges assigned to a group share x_st and x_en; tol >= 0 in pixels;
+ *       len_cap >= the batch's widest edge.  The MEMBERS of group g are its edges in ascending order minus those whose status
+ *       is not GPET_OK, at most GPET_ENSEMBLE_MAX.  With n members, v_m[k] the converged mean (pixels) of member m at grid index
+ *       k, and s[0..n-1] the v_m[k] in ascending order (equal values in member order):
+ *         min = s[0], max = s[n-1], q_lo = s[(n-1)/4], q_hi = s[n-1-(n-1)/4], median = (s[(n-1)/2] + s[n/2]) * 0.5
+ *         (integer divisions; selections and one exact add and halving: np.sort / np.median along the member axis, bit for bit)
+ *         c[k] = (int64) rint(median[k]), round half to even; the consensus trace is (c[k], x_st + k), yx like a result record's
+ *         agree[k] = number of members with |rint(v_m[k]) - c[k]| <= tol
+ *         off[e]   = number of columns with |rint(v_e[k]) - c[k]| > tol for a member e; -1 for every other edge
+ *         medoid   = the member with the smallest off, ties to the smaller final cost, then to the smaller edge index
+ *         best_cost = the member with the smallest final cost, ties to the smaller edge index
+ *       (both are edge indices; the final costs are those of gpet_batch_final_costs, computed inside the call).  A group without
+ *       members has n_members = 0, medoid = best_cost = -1 and zero arrays.  NaN means are not ordered.
+ *   dst = G records | f64 cost[B] | int32 off[B] (padded to 8 bytes), gpet_ensemble_bytes(G, B, len_cap) in all;
+ *   record = gpet_ensemble_head | int64 trace[len_cap][2] | f64 median | q_lo | q_hi | min | max [len_cap] each
+ *                               | int32 agree[len_cap] (padded to 8 bytes); entries past the group's edge_len are zero.
+ *   dst is host memory (on_device = 0: complete on return) or device memory (1: enqueued on the context's stream). */
+#define GPET_ENSEMBLE_MAX 1024
+typedef struct gpet_ensemble_head {  /* one per group, followed by its arrays */
+  int32_t n_members; /* members of the group (assigned edges with status GPET_OK) */
+  int32_t edge_len;  /* points of the group's x-grid */
+  int32_t x_st;      /* its first column */
+  int32_t medoid;    /* edge index, -1 without members */
+  int32_t best_cost; /* edge index, -1 without members */
+  int32_t reserved;
+  double tol;        /* the tolerance the counts were made with */
+} gpet_ensemble_head;
+int gpet_batch_final_costs(gpet_batch* b, double* dst, int dst_on_device);
+int gpet_ensemble_bytes(int n_groups, int n_edges, int64_t len_cap, size_t* bytes);
+int gpet_batch_ensemble(gpet_batch* b, int n_groups, const int32_t* group_of, double tol, int64_t len_cap, void* dst,
+                        int dst_on_device);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
