@@ -332,6 +332,37 @@ def check_group_table(group_of, n_edges):
     return np.ascontiguousarray(g), n_groups
 
 
+# seed ensembles in sequences (gpet_batch_warm_start_groups): where a group's edges take the next frame's observations from
+WARM_MEDOID, WARM_BEST_COST, WARM_CONSENSUS = 0, 1, 2
+WARM_FROM = {"medoid": WARM_MEDOID, "best_cost": WARM_BEST_COST, "consensus": WARM_CONSENSUS}
+WARM_SRC_NONE, WARM_SRC_CONSENSUS = -1, -2  # what src_out holds besides an edge index
+
+
+def warm_from(name):
+    """``'medoid'`` / ``'best_cost'`` / ``'consensus'`` (or the GPET_WARM_* value) as the library takes it; ValueError otherwise."""
+    if name in WARM_FROM:
+        return WARM_FROM[name]
+    if isinstance(name, (int, np.integer)) and not isinstance(name, bool) and int(name) in WARM_FROM.values():
+        return int(name)
+    raise ValueError("warm_from must be one of %s, not %r" % (sorted(WARM_FROM), name))
+
+
+def warm_sources(group_of, groups, frm):
+    """The source of every edge's warm start, as gpet_batch_warm_start_groups reports it in ``src_out`` (csrc/gpet_warm_plan.h),
+    from ``group_of`` and the groups' dicts (``medoid``, ``best_cost``; -1 in a group without members): the edge itself outside any
+    group, else the group's medoid / best-cost member, WARM_SRC_CONSENSUS, or WARM_SRC_NONE for a group without members."""
+    frm = warm_from(frm)
+    out = np.empty(len(group_of), dtype=np.int32)
+    for e, g in enumerate(np.asarray(group_of).tolist()):
+        if g < 0:
+            out[e] = e
+        elif groups[g]["medoid"] < 0:
+            out[e] = WARM_SRC_NONE
+        else:
+            out[e] = (groups[g]["medoid"], groups[g]["best_cost"], WARM_SRC_CONSENSUS)[frm]
+    return out
+
+
 # iteration history (gpet_batch_set_history): what a record holds beyond its head
 HISTORY_LEVELS = {None: 0, "off": 0, "obs": 1, "curves": 2, "full": 3}
 
@@ -681,6 +712,10 @@ SYMBOLS = {
     "gpet_batch_final_costs": (C.c_int, [_P, _P, C.c_int]),
     "gpet_ensemble_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
     "gpet_batch_ensemble": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_double, C.c_int64, _P, C.c_int]),
+    "gpet_batch_ensemble_keep": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_double]),
+    "gpet_batch_ensemble_kept": (C.c_int, [_P, C.c_int64, _P, C.c_int]),
+    "gpet_batch_warm_start_groups": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gpet_batch_warm_start_from": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1331,6 +1366,52 @@ class Batch:
         raw = np.empty(ensemble_layout(n_groups, self.B, L)["total_bytes"], dtype=np.uint8)
         self.ctx.check(self.lib.gpet_batch_ensemble(self.h, n_groups, gp, float(tol), L, raw.ctypes.data, 0))
         return decode_ensemble(raw, n_groups, self.B, L, g)
+
+    def ensemble_keep(self, group_of, tol=2.0):
+        """gpet_batch_ensemble_keep: the reduction of ``ensemble`` into an allocation the batch owns, to warm-start the next frame
+        from (``warm_start_groups``).  Call it before the images are swapped: the final costs are scored on the current ones."""
+        g, n_groups = check_group_table(group_of, self.B)
+        if not float(tol) >= 0.0:
+            raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
+        self._kept_groups = None
+        self.ctx.check(self.lib.gpet_batch_ensemble_keep(self.h, n_groups, g.ctypes.data_as(C.POINTER(C.c_int32)), float(tol)))
+        self._kept_groups = (g, n_groups)
+
+    def ensemble_kept(self, len_cap=None, device_ptr=None, raw=False):
+        """gpet_batch_ensemble_kept: the kept ensemble as ``ensemble`` returns it -- ``decode_ensemble``'s (groups, cost, off), or
+        with ``raw`` the bytes themselves; ``device_ptr``: copied there on the device instead, nothing returned.  GpetError when
+        none is kept."""
+        L = self._max_info("Lg") if len_cap is None else int(len_cap)
+        if device_ptr is not None:
+            self.ctx.check(self.lib.gpet_batch_ensemble_kept(self.h, L, int(device_ptr), 1))
+            return None
+        kept = getattr(self, "_kept_groups", None)
+        n_groups = kept[1] if kept else 1
+        buf = np.empty(ensemble_layout(n_groups, self.B, L)["total_bytes"], dtype=np.uint8)
+        self.ctx.check(self.lib.gpet_batch_ensemble_kept(self.h, L, buf.ctypes.data, 0))
+        return buf if raw else decode_ensemble(buf, n_groups, self.B, L, kept[0] if kept else None)
+
+    def warm_start_groups(self, frm, warm_every):
+        """gpet_batch_warm_start_groups: every edge's observation set for the next frame from the source of its group in the kept
+        ensemble -- ``frm`` 'medoid', 'best_cost' or 'consensus' -- on the device; edges in no group from their own fit, the edges
+        of a group without members get none.  Returns (sizes of the sets, source per edge: an edge index, WARM_SRC_NONE or
+        WARM_SRC_CONSENSUS)."""
+        cnt, src = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        p = C.POINTER(C.c_int32)
+        self.ctx.check(self.lib.gpet_batch_warm_start_groups(self.h, warm_from(frm), int(warm_every), cnt.ctypes.data_as(p),
+                                                             src.ctypes.data_as(p)))
+        return cnt, src
+
+    def warm_start_from(self, src_of, warm_every):
+        """gpet_batch_warm_start_from: edge e's observation set for the next frame from the last converged fit of edge
+        ``src_of[e]`` (-1: the empty set).  Returns the sizes of the sets."""
+        src = np.ascontiguousarray(np.asarray(src_of).reshape(-1), dtype=np.int32)
+        if src.shape[0] != self.B:
+            raise ValueError("src_of has %d entries for %d edges" % (src.shape[0], self.B))
+        cnt = np.zeros(self.B, dtype=np.int32)
+        p = C.POINTER(C.c_int32)
+        self.ctx.check(self.lib.gpet_batch_warm_start_from(self.h, src.ctypes.data_as(p), int(warm_every), cnt.ctypes.data_as(p)))
+        return cnt
 
     def set_history(self, level, iter_cap=64):
         """Iteration history of the traces this batch runs (gpet_batch_set_history): ``level`` None / 'obs' / 'curves' / 'full'

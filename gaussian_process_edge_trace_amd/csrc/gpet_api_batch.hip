@@ -459,6 +459,26 @@ int check_device_status(gpet_batch* b) {
   return GPET_OK;
 }
 
+// What every warm start does once its kernel is enqueued (gpet_batch_warm_start, gpet_batch_warm_start_groups / _from): the histories
+// emptied, the flags of a new trace, the one copy of the scalars with the one wait -- the counts are in them.
+int warm_start_finish(gpet_batch* b, int32_t* n_obs_out) {
+  const int rc_h = history_clear(b, -1);
+  if (rc_h) return rc_h;
+  b->have_results = false;
+  b->have_last_fit = false;
+  b->ens_kept = false;  // (a kept ensemble belongs to the trace these fits ended)
+  b->iters_issued = 0;
+  b->norm_issued = 0;
+  const int rc = fetch_all_scalars(b);  // (the one copy and the one wait: the counts are in the scalars)
+  if (rc) return rc;
+  b->h_nobs_prev.assign((size_t)b->B, 0);
+  for (int e = 0; e < b->B; ++e) {
+    b->h_nobs_prev[(size_t)e] = b->h_scalars[(size_t)e].n_obs;
+    if (n_obs_out) n_obs_out[e] = b->h_scalars[(size_t)e].n_obs;
+  }
+  return GPET_OK;
+}
+
 extern "C" {
 
 // The any-rank factor's rows of the trace that ends here may serve as the FIRST warm start of the next one -- only when
@@ -499,6 +519,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
   if (n_obs > E.obs_cap) return fail(c, GPET_ERR_BAD_ARG, "n_obs=%d exceeds obs_cap=%d", n_obs, E.obs_cap);
   b->have_results = false;
   b->have_last_fit = false;  // (the trace that follows is not the one the fits in d_fin_out belong to)
+  b->ens_kept = false;
   // the pixel kernels index the density images with the observations (gpet.py:568: kde_arr[pre_fobs[:,0], pre_fobs[:,1]]
   // raises IndexError in the reference for pixels outside the image)
   for (int i = 0; i < n_obs; ++i)
@@ -557,20 +578,7 @@ int gpet_batch_warm_start(gpet_batch* b, int warm_every, int32_t* n_obs_out) {
   if (ready) return ready;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, launch_warm_start(c->stream, b->d_edges, b->B, warm_every));
-  const int rc_h = history_clear(b, -1);
-  if (rc_h) return rc_h;
-  b->have_results = false;
-  b->have_last_fit = false;
-  b->iters_issued = 0;
-  b->norm_issued = 0;
-  const int rc = fetch_all_scalars(b);  // (the one copy and the one wait: the counts are in the scalars)
-  if (rc) return rc;
-  b->h_nobs_prev.assign((size_t)b->B, 0);
-  for (int e = 0; e < b->B; ++e) {
-    b->h_nobs_prev[(size_t)e] = b->h_scalars[(size_t)e].n_obs;
-    if (n_obs_out) n_obs_out[e] = b->h_scalars[(size_t)e].n_obs;
-  }
-  return GPET_OK;
+  return warm_start_finish(b, n_obs_out);
 }
 
 int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
@@ -856,6 +864,7 @@ static int batch_reset(gpet_batch* b, bool next_frame) {
 int gpet_batch_reset(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
+  b->ens_kept = false;  // (gpet_batch_set_images goes through batch_reset itself and leaves a kept ensemble alone)
   return batch_reset(b, false);
 }
 

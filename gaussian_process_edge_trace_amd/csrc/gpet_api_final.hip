@@ -357,6 +357,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   gpet_ctx* c = b->ctx;
   b->have_results = false;
   b->have_last_fit = false;
+  b->ens_kept = false;  // (a kept ensemble is the last converged fits')
   HIPCHK(c, hipSetDevice(c->device));
   int rc = fetch_all_scalars(b);  // (synchronises the loop's stream: the observation sets are final)
   if (rc) return rc;

@@ -25,6 +25,9 @@
 //   gpet_history_plan.h  the history's record layout and storage size as plain data (no HIP)
 //   gpet_api_ensemble.hip seed ensembles: gpet_batch_final_costs, gpet_ensemble_bytes, gpet_batch_ensemble
 //   gpet_ensemble_plan.h the layout of an ensemble's buffer, the validation of its arguments, member tables and tile width (no HIP)
+//                        and, for sequences, gpet_batch_ensemble_keep / _kept, gpet_batch_warm_start_groups / _from
+//   gpet_warm_plan.h     the source of every edge's warm start (medoid, best cost, consensus, another edge, none), the refusals, the
+//                        kept ensemble's size (no HIP)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -153,6 +156,10 @@ struct gpet_batch {
   // seed ensembles (gpet_api_ensemble.hip): the scratch of gpet_batch_final_costs / gpet_batch_ensemble, allocations of their own made
   // on first use (nullptr: never called -- the batch then holds and enqueues nothing for them)
   struct EnsembleScratch* ens = nullptr;
+  // gpet_batch_ensemble_keep has left the ensemble of the last converged fits in the scratch (with its group table): what
+  // gpet_batch_warm_start_groups takes its sources from.  Survives gpet_batch_set_images; cleared by every warm start, gpet_batch_set_obs,
+  // gpet_batch_reset and the next gpet_final_fit_all
+  bool ens_kept = false;
   // iteration history (gpet_batch_set_history): storage of its own, B regions of hist.edge_bytes (gpet_history_plan.h); hist.level == 0
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;
@@ -230,6 +237,8 @@ int history_clear(gpet_batch* b, int e);
 void ensemble_free(gpet_batch* b);
 // ---- gpet_api_batch.hip ---------------------------------------------------------------------------------------------------
 int fetch_all_scalars(gpet_batch* b);
+// the end of every warm start, after its kernel: histories, flags, the one copy of the scalars and the one wait; n_obs_out may be nullptr
+int warm_start_finish(gpet_batch* b, int32_t* n_obs_out);
 int check_device_status(gpet_batch* b);
 // what the loop's generator stores of a sample row: the r0 (rounded to 4) leading normals a structured batch multiplies
 static inline int loop_z_store(const gpet_batch* b) {

@@ -68,3 +68,114 @@ hipError_t launch_warm_start(hipStream_t st, EdgeDev* d_edges, int B, int warm_e
   hipLaunchKernelGGL(k_warm_start, dim3(B), dim3(64), 0, st, d_edges, warm_every);
   return hipGetLastError();
 }
+
+// ---- warm start from a source other than the edge itself (gpet_batch_warm_start_groups, gpet_batch_warm_start_from) ------------
+// src[e] of every edge from the heads of the kept ensemble's records: thread per edge, the rule of warm_source (gpet_warm_plan.h).
+// The heads were written by k_ensemble_pick before the images were swapped; nothing here reads an edge's scalars.
+__global__ void __launch_bounds__(256) k_warm_sources(int B, const int32_t* __restrict__ group_of, const char* __restrict__ kept,
+                                                      long long record_bytes, int from, int32_t* __restrict__ src) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B) return;
+  const int g = group_of[e];
+  if (g < 0) {
+    src[e] = warm_source(e, g, 0, -1, -1, from);
+    return;
+  }
+  const gpet_ensemble_head* h = reinterpret_cast<const gpet_ensemble_head*>(kept + (size_t)g * (size_t)record_bytes);
+  src[e] = warm_source(e, g, h->n_members, h->medoid, h->best_cost, from);
+}
+
+// k_warm_start for destination edge e = blockIdx.x with the trace taken from src[e] (gpet_warm_plan.h): s >= 0 -- rint of edge s's
+// converged mean; WARM_SRC_CONSENSUS -- the int64 row c[k] of the kept record of e's group (INT64_MIN where the median was NaN: it
+// fails the row test as on the host); anything else -- nothing, the empty set.  Candidate rule, ballots, compaction and end state are
+// k_warm_start's, and every bound is the DESTINATION's (x_st, x_en, Lg, M, algo_thresh, obs_cap): source and destination share the
+// x-grid (checked on the host: gpet_ensemble_plan.h for groups, warm_from_check for a caller's table), so index k < Lg - 1 is inside
+// the source's fin_out and inside the record's len_cap rows.
+// A wave writes only its OWN edge's obs_xy, scalars and tags, with plain per-lane stores (no atomics).  Of other edges it reads the
+// EdgeDev entry (the table no kernel writes) and fin_out (written by the converged fit alone, long before this launch) -- never their
+// gpet_scalars: the source's own wave is rewriting those in this very launch, so what is a member and what the source is was decided
+// before it, by the ensemble reduction and the src table.
+__global__ void __launch_bounds__(64) k_warm_start_src(EdgeDev* edges, int B, const int32_t* __restrict__ src,
+                                                       const int32_t* __restrict__ group_of, const char* __restrict__ kept,
+                                                       long long record_bytes, long long off_trace, int warm_every) {
+  const int e = blockIdx.x;
+  const EdgeDev E = edges[e];
+  gpet_scalars* sc = E.sc;  // (the destination's own)
+  const int lane = threadIdx.x;
+  const int s = src[e];     // (uniform over the wave: every branch on it is)
+  const double* __restrict__ mean = nullptr;
+  const long long* __restrict__ cons = nullptr;
+  if (s >= 0 && s < B) mean = edges[s].fin_out;
+  else if (s == WARM_SRC_CONSENSUS && kept && group_of && group_of[e] >= 0)
+    cons = reinterpret_cast<const long long*>(kept + (size_t)group_of[e] * (size_t)record_bytes + (size_t)off_trace);
+  const long long last = (long long)E.Lg - 1;  // candidates are grid indices below it
+  const double y_max = (double)(E.M - 1);
+  const long long yi_max = (long long)E.M - 1;
+  auto kept_at = [&](long long k) {  // (k < last) as k_warm_start's; the row from the source
+    const long long x = (long long)E.x_st + k;
+    bool row_in;
+    if (mean) {
+      const double y = rint(mean[k]);  // (NaN fails both comparisons)
+      row_in = y >= 0.0 && y <= y_max;
+    } else {
+      const long long y = cons[2 * k];
+      row_in = y >= 0 && y <= yi_max;
+    }
+    return x > E.x_st && x < E.x_en && row_in;
+  };
+  long long step = warm_every > 1 ? warm_every : 1;
+  int n_keep = 0;
+  if (mean || cons) {
+    for (;;) {
+      int cnt = 0;
+      for (long long k0 = step; k0 < last; k0 += step * WAVE) {  // (uniform trip count: every lane reaches the ballot)
+        const long long k = k0 + step * lane;
+        cnt += __popcll(__ballot(k < last && kept_at(k)));
+      }
+      n_keep = cnt;
+      if (n_keep < E.algo_thresh || n_keep == 0) break;
+      step *= 2;  // (ends: no candidate is left once step >= Lg - 1)
+    }
+    if (n_keep > E.obs_cap) n_keep = E.obs_cap;  // (cannot happen, as in k_warm_start; the stores below stay inside obs_xy)
+    int base = 0;
+    for (long long k0 = step; k0 < last; k0 += step * WAVE) {
+      const long long k = k0 + step * lane;
+      const bool take = k < last && kept_at(k);
+      const unsigned long long bal = __ballot(take);
+      const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+      if (take && pos < n_keep) {
+        E.obs_xy[2 * pos] = (long long)E.x_st + k;
+        E.obs_xy[2 * pos + 1] = mean ? (long long)rint(mean[k]) : cons[2 * k];  // (an integer in [0, M - 1]: exact)
+      }
+      base += __popcll(bal);
+    }
+  }
+  if (lane == 0) {
+    const int iters_done = sc->iter;
+    sc->n_obs = n_keep;
+    sc->done = (n_keep >= E.algo_thresh) ? 1 : 0;
+    sc->status = GPET_OK;
+    sc->iter = 0;
+    E.wq_tag[0] = 0;
+    E.wq_tag[1] = 0;
+    if (iters_done >= 1) {
+      E.ap_tag[0] = 0;
+      E.ap_tag[1] = 0;
+      E.ap_tag[2] = 0;
+    }
+  }
+}
+
+hipError_t launch_warm_sources(hipStream_t st, int B, const int32_t* d_group_of, const char* d_kept, long long record_bytes, int from,
+                               int32_t* d_src) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_warm_sources, dim3(cdiv(B, 256)), dim3(256), 0, st, B, d_group_of, d_kept, record_bytes, from, d_src);
+  return hipGetLastError();
+}
+
+hipError_t launch_warm_start_src(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
+                                 long long record_bytes, long long off_trace, int warm_every) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_warm_start_src, dim3(B), dim3(64), 0, st, d_edges, B, d_src, d_group_of, d_kept, record_bytes, off_trace, warm_every);
+  return hipGetLastError();
+}

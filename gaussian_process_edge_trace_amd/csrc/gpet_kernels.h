@@ -9,6 +9,7 @@
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
+#include "gpet_warm_plan.h"  // warm start from a group's medoid / best cost / consensus or from another edge: source per edge, refusals
 
 namespace gpet {
 
@@ -97,6 +98,13 @@ hipError_t launch_rho_tab(hipStream_t st, EdgeDev* d_edges, int B, int N);
 hipError_t launch_fin_scatter(hipStream_t st, EdgeDev* d_edges, int B, const double* d_stage, const int* d_n, int stride);
 // the next frame's observation sets from the last converged fits (gpet_k_warm.inc): one wave per edge
 hipError_t launch_warm_start(hipStream_t st, EdgeDev* d_edges, int B, int warm_every);
+// d_src[e] of every edge from the heads of the kept ensemble's records (d_kept, records of record_bytes) and d_group_of, by warm_source
+hipError_t launch_warm_sources(hipStream_t st, int B, const int32_t* d_group_of, const char* d_kept, long long record_bytes, int from,
+                               int32_t* d_src);
+// k_warm_start with the trace of edge e taken from d_src[e]: another edge's fit, the consensus row of its group's kept record (d_group_of,
+// d_kept; both may be nullptr when no entry is WARM_SRC_CONSENSUS), or nothing
+hipError_t launch_warm_start_src(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
+                                 long long record_bytes, long long off_trace, int warm_every);
 // the record of the iteration just completed for every edge whose counter equals iter_expect (0: every edge with a counter >= 1), gpet_k_history.inc
 hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const gpet_history_plan& P, int iter_expect);
 hipError_t launch_pixels_reset(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

@@ -587,6 +587,7 @@ class GP_Edge_Tracing_Batch(object):
         self.return_std = return_std
         self.seeds = [int(s) for s in seeds]
         self.timings = {}
+        self.last_ensemble = None  # (set_frame(warm_from=...): the ensemble of the frame it left)
 
     def _set_obs(self):
         for e, p in enumerate(self._ps):
@@ -608,7 +609,8 @@ class GP_Edge_Tracing_Batch(object):
         return "one shared image" if b.share_image else "one image per edge, %d" % b.n_img
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
-                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None):
+                  raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None, warm_from=None,
+                  group_of=None, tol=2):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -624,11 +626,32 @@ class GP_Edge_Tracing_Batch(object):
         ``warm_every=k`` instead of ``obs``: the warm start is made on the device (gpet_batch_warm_start) -- every edge's
         observations from its own last converged fit by the rule of ``sequence.warm_start_obs(trace, x_st, x_en, k, algo_thresh,
         M)`` -- with no trip of the traces through the host; the sets are read back once, so that ``reset()`` restores the same
-        warm start.  It needs the trace this object ran last (``__call__`` or ``finish``)."""
+        warm start.  It needs the trace this object ran last (``__call__`` or ``finish``).
+        ``warm_from='medoid'``, ``'best_cost'`` or ``'consensus'`` with ``warm_every`` (and ``group_of``, ``tol`` as ``ensemble``
+        takes them): the batch traces seed ensembles, and every edge assigned to a group takes its observations from the group's
+        medoid, its member of smallest final cost, or the consensus trace -- edges in no group from their own fit, the edges of a
+        group without members none.  The ensemble is reduced and kept on the device BEFORE the images are swapped (its final costs
+        are scored on the frame just traced; gpet_batch_ensemble_keep), the warm start is made from it after the swap
+        (gpet_batch_warm_start_groups); ``last_ensemble`` is then the list ``ensemble(group_of, tol)`` would have returned for the
+        frame just left.  ``warm_from=None`` (default): every edge from its own fit, as above."""
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
+        if warm_from is not None:
+            if obs is not None:
+                raise ValueError("obs and warm_from are alternatives: the device derives the observations itself")
+            if warm_every is None:
+                raise ValueError("warm_from chooses the source of the device's warm start: it needs warm_every")
+            _lib.warm_from(warm_from)
+            groups = self.group_table(group_of)
+            if not float(tol) >= 0.0:
+                raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
         if warm_every is not None:
             self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
+        if warm_from is not None:
+            # (before the swap: the final costs that break the medoid's ties and define best_cost are those of the frame just traced)
+            self._batch.ensemble_keep(groups, tol)
+            keys = ("trace", "median", "q_lo", "q_hi", "min", "max", "agree", "members", "off", "cost", "medoid", "best_cost")
+            self.last_ensemble = [{k: d[k] for k in keys} for d in self._batch.ensemble_kept()[0]]
         if denoise not in (None, False) and raw_imgs is None and raw_device_ptrs is None:
             raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
         if raw_imgs is not None or raw_device_ptrs is not None:
@@ -661,7 +684,10 @@ class GP_Edge_Tracing_Batch(object):
                 raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
                                  % (len(imgs), self._images_text(), self._batch.M, self._batch.N))
             self._batch.set_images([np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
-        if warm_every is not None:
+        if warm_from is not None:
+            self._batch.warm_start_groups(warm_from, warm_every)
+            obs = self._batch.read_obs_all()  # (what reset() sets again)
+        elif warm_every is not None:
             self._batch.warm_start(warm_every)
             obs = self._batch.read_obs_all()  # (what reset() sets again)
         else:
@@ -674,6 +700,15 @@ class GP_Edge_Tracing_Batch(object):
             self.seeds = [int(v) for v in seeds]
         if warm_every is None:
             self._set_obs()
+
+    def warm_start_from(self, src_of, warm_every):
+        """The explicit form of the device's warm start (gpet_batch_warm_start_from), where ``set_frame`` would make it -- after the
+        images were swapped: edge e's observations from the last converged fit of edge ``src_of[e]`` (on the same columns), -1 for
+        none.  The sets are read back once, so that ``reset()`` restores them.  Returns their sizes."""
+        cnt = self._batch.warm_start_from(src_of, warm_every)
+        for p, o in zip(self._ps, self._batch.read_obs_all()):
+            p["obs"] = np.asarray(o).reshape(-1, 2).astype(np.int64)
+        return cnt
 
     def run_loop(self, max_iter=1000, chunk=64):
         """The device-resident while-loops of all edges (gpet.py:829-870); returns iterations per edge.

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from ._lib import split_kernels
 from .gpet import GP_Edge_Tracing_Batch, resolve_params
 
@@ -84,10 +85,35 @@ class SequenceTracer(object):
     ``grad_kernel=[K_0 .. K_{E-1}]``: one kernel per init, for edges of opposite polarity on the same raw frames (the two walls
     of a vessel) -- or fewer kernels plus ``kernel_of`` with E indices into them.  Every frame is uploaded, denoised and staged
     on the device once, and edge k's results are what ``SequenceTracer(frames, init[k], grad_kernel=K[kernel_of[k]], ...)``
-    gives, bit for bit."""
+    gives, bit for bit.
 
-    def __init__(self, frames, init, n_chains=1, warm_every=None, seed=42, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
-                 denoise=None, kernel_of=None, **kw):
+    ``ensemble_seeds=[s_0 .. s_{K-1}]``: every frame is traced with K seeds per init -- a step of C chains and E inits is one batch
+    of C x E x K edges (``step_tables``), member j of every frame with seed ``s_j`` (``seed`` / ``seeds`` are then refused) -- and
+    ALL K members of the next frame start from one source of their group, so a seed that strayed onto a neighbouring edge does
+    not hand its trace on: ``warm_from='medoid'`` (default; a real trace), ``'best_cost'`` or ``'consensus'``.  The group is
+    reduced and the warm start made on the device (``set_frame(..., warm_from=)``).  Every result is then the dict
+    ``trace_ensemble`` returns for that frame and init -- the reduction's arrays (``ensemble_tol`` = its ``tol``) plus ``seeds``,
+    ``medoid_seed`` and ``result``, the medoid member's own result -- and ``iterations[t]`` holds the K counts."""
+
+    _UNSET = object()
+
+    def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
+                 denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', **kw):
+        if ensemble_seeds is not None:
+            if seed is not SequenceTracer._UNSET or seeds is not None:
+                raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
+            ensemble_seeds = [int(v) for v in np.asarray(ensemble_seeds).reshape(-1)]
+            if not ensemble_seeds:
+                raise ValueError("ensemble_seeds is empty: an ensemble needs at least one seed")
+            if len(ensemble_seeds) > _lib.ENSEMBLE_MAX:
+                raise ValueError("%d ensemble_seeds: a group holds at most %d members" % (len(ensemble_seeds), _lib.ENSEMBLE_MAX))
+            if not float(ensemble_tol) >= 0.0:
+                raise ValueError("ensemble_tol must be >= 0 pixels, not %r" % (ensemble_tol,))
+            _lib.warm_from(warm_from)
+        if seed is SequenceTracer._UNSET:
+            seed = 42
+        self.ensemble_seeds, self.ensemble_tol, self.warm_from = ensemble_seeds, ensemble_tol, warm_from
+        self.K = 1 if ensemble_seeds is None else len(ensemble_seeds)
         self.frames = frames
         self.T = len(frames)
         self.inits, self.multi = _inits_of(init)
@@ -134,50 +160,118 @@ class SequenceTracer(object):
     def _frames_of_step(self, s):
         return [lo + s for lo, hi in self.chains if lo + s < hi]
 
-    def __call__(self, max_iter=1000):
-        results = [None] * self.T
-        prev = {}  # (chain index, edge of the frame) -> previous edge trace
-        n_steps = max(hi - lo for lo, hi in self.chains)
-        E = self.E
-        for s in range(n_steps):
-            active = [(c, lo + s) for c, (lo, hi) in enumerate(self.chains) if lo + s < hi]
-            imgs = [np.asarray(self.frames[f]) for _, f in active]
+    def step_tables(self, active):
+        """The layout of one step's batch, from the frames alone (no device).  ``active``: the step's (chain, frame) pairs.  A dict:
+        ``inits`` and ``seeds`` per edge, ``image_of`` and ``kernel_of`` (None where the batch does without), ``group_of`` (None
+        without ``ensemble_seeds``).  Edges are chain-major, then init-major, then member-minor: edge ``(ci * E + k) * K + j`` is
+        init k of the ci-th active chain's frame with seed ``ensemble_seeds[j]``, group ``ci * E + k`` its K members.  Without
+        ``ensemble_seeds`` K is 1 and the E edges of a frame share the frame's seed."""
+        E, K = self.E, self.K
+        ens = self.ensemble_seeds is not None
+        if ens:
+            seeds = [sd for _ in active for _ in range(E) for sd in self.ensemble_seeds]
+        else:
             seeds = [self.seeds[f] for _, f in active for _ in range(E)]  # (chain-major: the E edges of a frame are adjacent)
-            if self._tracer is None or len(active) * E != self._tracer.B:
-                # (first step, or the shorter chains have run out: a smaller batch from here on; the old batch's arena,
-                # streams and events are released now, not whenever the garbage collector gets to them.  The new batch's
-                # warm start comes from the traces on the host: the converged fits went with the old batch)
-                obs = []
-                for c, f in active:
-                    for k, p in enumerate(self._ps):
-                        obs.append(np.zeros((0, 2), dtype=np.int64) if s == 0 else
-                                   warm_start_obs(prev[c, k], p["x_st"], p["x_en"], self.warm_every, p["algo_thresh"], p["M"]))
-                if self._tracer is not None:
-                    self._tracer._batch.close()
-                images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
-                                                                                     grad_kernel=self.grad_kernel,
-                                                                                     denoise=self.denoise)
-                if self.kernel_of is not None:  # (chain-major, like the inits: C frames, C x distinct kernels image slots)
-                    images["kernel_of"] = [k for _ in active for k in self.kernel_of]
-                # (several edges per frame: one image per chain, read by its E edges; one edge per frame is a batch with one
-                # image per edge, as ever)
-                image_of = [ci for ci in range(len(active)) for _ in range(E)] if E > 1 or self.kernel_of is not None else None
-                self._tracer = GP_Edge_Tracing_Batch([i for _ in active for i in self.inits], seeds=seeds, obs=obs,
-                                                     device=self.device, _ctx=self._ctx, image_of=image_of, **images, **self.kw)
-                if self._ctx is None:
-                    self._ctx = self._tracer._ctx
-            elif self.grad_kernel is None:
-                self._tracer.set_frame(imgs, None, seeds, warm_every=self.warm_every)
-            else:
-                self._tracer.set_frame(None, None, seeds, raw_imgs=imgs, warm_every=self.warm_every)
-            out = self._tracer(max_iter)
-            iters = self._tracer.timings["iters"]
-            for ci, (c, f) in enumerate(active):
+        # (several edges per frame: one image per chain, read by its edges; one edge per frame is a batch with one image per edge,
+        # as ever)
+        image_of = ([ci for ci in range(len(active)) for _ in range(E * K)]
+                    if E > 1 or ens or self.kernel_of is not None else None)
+        # (chain-major, like the inits: C frames, C x distinct kernels image slots)
+        kernel_of = None if self.kernel_of is None else [k for _ in active for k in self.kernel_of for _ in range(K)]
+        group_of = np.repeat(np.arange(len(active) * E, dtype=np.int32), K) if ens else None
+        return dict(inits=[i for _ in active for i in self.inits for _ in range(K)], seeds=seeds, image_of=image_of,
+                    kernel_of=kernel_of, group_of=group_of)
+
+    def _source_trace(self, d, res):
+        """The trace the members of the next frame start from, on the host (the rebuilt batch): the medoid's or the best-cost
+        member's own, or the consensus; None for a group without members."""
+        if d["medoid"] < 0:
+            return None
+        if self.warm_from in ("consensus", _lib.WARM_CONSENSUS):
+            return d["trace"]
+        r = res[d["medoid"] if self.warm_from in ("medoid", _lib.WARM_MEDOID) else d["best_cost"]]
+        return r[0] if self._tracer.return_std else r
+
+    def _close_step(self, pending, ens, results, prev):
+        """Files the results of the step traced last: ``pending`` = (active, results per edge, iterations per edge, group table), ``ens`` the
+        ensemble of its groups (None without ``ensemble_seeds``)."""
+        active, out, iters, _ = pending
+        E, K = self.E, self.K
+        for ci, (c, f) in enumerate(active):
+            if ens is None:
                 res = out[ci * E:(ci + 1) * E]
                 results[f] = list(res) if self.multi else res[0]
                 self.iterations[f] = list(iters[ci * E:(ci + 1) * E]) if self.multi else iters[ci * E]
                 for k in range(E):
                     prev[c, k] = res[k][0] if self._tracer.return_std else res[k]
+                continue
+            dicts, its = [], []
+            for k in range(E):
+                g = ci * E + k
+                d = dict(ens[g])
+                d["seeds"] = [self.ensemble_seeds[e - g * K] for e in d["members"]]
+                d["medoid_seed"] = self.ensemble_seeds[d["medoid"] - g * K] if d["medoid"] >= 0 else None
+                d["result"] = out[d["medoid"]] if d["medoid"] >= 0 else None
+                dicts.append(d)
+                its.append(list(iters[g * K:(g + 1) * K]))
+                prev[c, k] = self._source_trace(d, out)
+            results[f] = dicts if self.multi else dicts[0]
+            self.iterations[f] = its if self.multi else its[0]
+
+    def __call__(self, max_iter=1000):
+        results = [None] * self.T
+        prev = {}  # (chain index, edge of the frame) -> the trace the next frame starts from
+        n_steps = max(hi - lo for lo, hi in self.chains)
+        E, K = self.E, self.K
+        ens = self.ensemble_seeds is not None
+        pending = None  # the step traced last, filed once its ensemble is there: set_frame reduces it on its way to the next frame
+        for s in range(n_steps):
+            active = [(c, lo + s) for c, (lo, hi) in enumerate(self.chains) if lo + s < hi]
+            imgs = [np.asarray(self.frames[f]) for _, f in active]
+            tab = self.step_tables(active)
+            seeds = tab["seeds"]
+            if self._tracer is None or len(active) * E * K != self._tracer.B:
+                # (first step, or the shorter chains have run out: a smaller batch from here on; the old batch's arena,
+                # streams and events are released now, not whenever the garbage collector gets to them.  The new batch's
+                # warm start comes from the traces on the host: the converged fits went with the old batch)
+                if pending is not None:
+                    self._close_step(pending, self._tracer.ensemble(pending[3], self.ensemble_tol) if ens else None, results, prev)
+                    pending = None
+                obs = []
+                for c, f in active:
+                    for k, p in enumerate(self._ps):
+                        o = (np.zeros((0, 2), dtype=np.int64) if s == 0 or prev[c, k] is None else
+                             warm_start_obs(prev[c, k], p["x_st"], p["x_en"], self.warm_every, p["algo_thresh"], p["M"]))
+                        obs.extend([o] * K)
+                if self._tracer is not None:
+                    self._tracer._batch.close()
+                images = dict(grad_imgs=imgs) if self.grad_kernel is None else dict(grad_imgs=None, raw_imgs=imgs,
+                                                                                     grad_kernel=self.grad_kernel,
+                                                                                     denoise=self.denoise)
+                if tab["kernel_of"] is not None:
+                    images["kernel_of"] = tab["kernel_of"]
+                self._tracer = GP_Edge_Tracing_Batch(tab["inits"], seeds=seeds, obs=obs, device=self.device, _ctx=self._ctx,
+                                                     image_of=tab["image_of"], **images, **self.kw)
+                if self._ctx is None:
+                    self._ctx = self._tracer._ctx
+            else:
+                warm = dict(warm_every=self.warm_every)
+                if ens:  # (the ensemble of the step before is reduced and kept on the device, then warm-starts every member)
+                    warm.update(warm_from=self.warm_from, group_of=tab["group_of"], tol=self.ensemble_tol)
+                if self.grad_kernel is None:
+                    self._tracer.set_frame(imgs, None, seeds, **warm)
+                else:
+                    self._tracer.set_frame(None, None, seeds, raw_imgs=imgs, **warm)
+                if ens:
+                    self._close_step(pending, self._tracer.last_ensemble, results, prev)
+                    pending = None
+            out = self._tracer(max_iter)
+            pending = (active, out, list(self._tracer.timings["iters"]), tab["group_of"])
+            if not ens:
+                self._close_step(pending, None, results, prev)
+                pending = None
+        if pending is not None:
+            self._close_step(pending, self._tracer.ensemble(pending[3], self.ensemble_tol), results, prev)
         return results
 
 

@@ -649,6 +649,36 @@ int gpet_ensemble_bytes(int n_groups, int n_edges, int64_t len_cap, size_t* byte
 int gpet_batch_ensemble(gpet_batch* b, int n_groups, const int32_t* group_of, double tol, int64_t len_cap, void* dst,
                         int dst_on_device);
 
+/* ---- seed ensembles in sequences: the next frame's warm start from the group's medoid, best member or consensus ---------------
+ * In a sequence every frame is traced with K seeds per edge (one group per edge of the frame), and ALL K members of the next frame
+ * start from one source of their group -- so a seed that strayed in frame t does not hand its trace on.  Two calls around the swap
+ * of the images, because the final costs -- the medoid's tie-break, and what best_cost is -- are scored on the images every edge
+ * reads NOW, which the swap replaces, while the observations may only be set after it:
+ *   gpet_batch_ensemble_keep(batch, G, group_of, tol)   BEFORE gpet_batch_set_images: the reduction of gpet_batch_ensemble -- same
+ *       validity, members, ties and bits -- into an allocation the batch owns, with the table.  The kept ensemble survives
+ *       gpet_batch_set_images and its raw forms; a warm start of any kind, gpet_batch_set_obs, gpet_batch_reset and the next
+ *       gpet_final_fit_all drop it.
+ *   gpet_batch_ensemble_kept(batch, len_cap, dst, on_device)   copies it out in the layout of gpet_batch_ensemble, byte for byte
+ *       what that call writes for the same arguments; GPET_ERR_BAD_ARG (with a message) when none is kept.
+ *   gpet_batch_warm_start_groups(batch, from, warm_every, n_obs_out, src_out)   AFTER the swap, where gpet_batch_warm_start is
+ *       called, with its rule, its end state and its waits (one; the histories are emptied).  from: GPET_WARM_MEDOID, _BEST_COST
+ *       or _CONSENSUS.  Every edge ASSIGNED to group g -- one the device stopped with an error included: it is re-seeded from the
+ *       group -- gets its observations from g's source: rint of that member's converged mean, or the consensus row c[k] of g's
+ *       kept record; its bounds (x_st, x_en, M, algo_thresh) are its own.  An edge with group_of = -1 gets them from its own fit,
+ *       exactly as gpet_batch_warm_start; every edge of a group with n_members = 0 gets the empty set.  src_out (host, [B], may be
+ *       NULL): the source used -- an edge index (the edge itself outside any group), -1 for none, -2 for the consensus.
+ *       GPET_ERR_BAD_ARG (with a message, nothing touched) when gpet_batch_warm_start_ready refuses, or when no ensemble is kept.
+ *   gpet_batch_warm_start_from(batch, src_of, warm_every, n_obs_out)   the explicit form: src_of[e] in [0, B), or -1 for the
+ *       empty set.  GPET_ERR_BAD_ARG naming the edge when src_of[e] is out of range or e and its source differ in x_st or x_en.
+ *       No status is looked at: the caller chose.  With src_of[e] = e it leaves exactly what gpet_batch_warm_start leaves. */
+#define GPET_WARM_MEDOID 0
+#define GPET_WARM_BEST_COST 1
+#define GPET_WARM_CONSENSUS 2
+int gpet_batch_ensemble_keep(gpet_batch* b, int n_groups, const int32_t* group_of, double tol);
+int gpet_batch_ensemble_kept(gpet_batch* b, int64_t len_cap, void* dst, int dst_on_device);
+int gpet_batch_warm_start_groups(gpet_batch* b, int from, int warm_every, int32_t* n_obs_out, int32_t* src_out);
+int gpet_batch_warm_start_from(gpet_batch* b, const int32_t* src_of, int warm_every, int32_t* n_obs_out);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
