@@ -595,6 +595,45 @@ class RawFrames(object):
                 (C.c_int32 * nk)(*[k.shape[1] for k in self.kernels]), (C.c_int32 * ns)(*self.slots[0]), (C.c_int32 * ns)(*self.slots[1]))
 
 
+class GpetBand(C.Structure):
+    """gpet_band (include/gpet_hip.h): the bands of gpet_batch_create_banded."""
+    _fields_ = [("H", C.c_int32), ("n_pair", C.c_int32), ("r0", C.POINTER(C.c_int64)), ("pair_of", C.POINTER(C.c_int32))]
+
+
+class GpetBandImages(C.Structure):
+    """gpet_band_images: the full-frame images of a banded batch, gradient images or raw frames with a slot table."""
+    _fields_ = [("grad", C.POINTER(C.c_void_p)), ("raw", C.POINTER(C.c_void_p)), ("pix", C.c_int32), ("n_frames", C.c_int32),
+                ("n_kern", C.c_int32), ("reserved", C.c_int32), ("kern", C.POINTER(C.c_void_p)), ("kh", C.POINTER(C.c_int32)),
+                ("kw", C.POINTER(C.c_int32)), ("frame_of", C.POINTER(C.c_int32)), ("kernel_of", C.POINTER(C.c_int32)),
+                ("dn", C.POINTER(GpetDenoise)), ("flags", C.c_uint)]
+
+
+def band_place(M, H, lo, hi, i_lo, i_hi):
+    """The placement rule of a tracking band (csrc/gpet_band_plan.h, band_place): ``lo`` / ``hi`` the smallest and largest usable row
+    of the source's trace in full-frame rows, ``i_lo`` / ``i_hi`` those of the edge's init points.  Python integers, floor division."""
+    r0 = (int(lo) + int(hi)) // 2 - int(H) // 2
+    r0 = min(max(r0, 0), int(M) - int(H))
+    return max(min(r0, int(i_lo)), int(i_hi) - int(H) + 1)
+
+
+def band_refusal(M, H, r0, i_lo, i_hi):
+    """Why (r0, H) cannot be the band of an edge with init rows ``i_lo .. i_hi`` on an M-row frame (band_check of
+    csrc/gpet_band_plan.h, same order, same words), or None; ``r0=None``: the band is still to be placed."""
+    if H < 1:
+        return "band_rows must be at least 1"
+    if H > M:
+        return "band_rows exceeds the rows of the frame (H > M)"
+    if i_hi - i_lo + 1 > H:
+        return "the init rows span more rows than the band holds (i_hi - i_lo + 1 > H)"
+    if r0 is None:
+        return None
+    if r0 < 0 or r0 > M - H:
+        return "r0 lies outside [0, M - H]"
+    if i_lo < r0 or i_hi > r0 + H - 1:
+        return "an init point lies outside its band"
+    return None
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -716,6 +755,11 @@ SYMBOLS = {
     "gpet_batch_ensemble_kept": (C.c_int, [_P, C.c_int64, _P, C.c_int]),
     "gpet_batch_warm_start_groups": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gpet_batch_warm_start_from": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
+    "gpet_batch_create_banded": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(GpetBand), C.POINTER(GpetBandImages),
+                                           C.POINTER(GpetParams), C.POINTER(_P), C.POINTER(_P)]),
+    "gpet_batch_band_place": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
+    "gpet_batch_band_set": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "gpet_batch_band_r0": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1068,14 +1112,17 @@ class Batch:
     """gpet_batch: B independent edges processed together."""
 
     def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None, raw=None,
-                 image_of=None):
+                 image_of=None, band=None):
         """``grads``: float32 (M, N) arrays on the host -- or, with ``device_ptrs`` (a list of integer device
         addresses of f32 [M*N] images on the context's device, e.g. ``tensor.data_ptr()`` after an RCCL broadcast) and
         ``shape`` = (M, N), nothing on the host at all: the library consumes the device images in place.  Or ``raw`` (a
         RawFrames: frames + gradient kernel) instead of both: the gradient images are made on the device
         (gpet_batch_create_raw).  ``image_of``: an image map -- B indices into the images, of which there are then ``n_img``
         (the length of the list of images given, ``grads`` a list of (M, N) arrays or an (n_img, M, N) stack) instead of one
-        or B; the library checks the map against that count (gpet_batch_create_mapped / gpet_batch_create_raw_mapped)."""
+        or B; the library checks the map against that count (gpet_batch_create_mapped / gpet_batch_create_raw_mapped).
+        ``band`` = (H, r0): tracking bands (gpet_batch_create_banded) -- the images are full frames, ``inits`` in full-frame rows,
+        ``r0`` one first row per edge or None (placed from the inits); the batch's own shape ``(M, N)`` becomes (H, N),
+        ``frame_M`` stays the frames', and every row the batch returns is a band row (``band_r0()`` has the offsets)."""
         self.ctx = ctx
         self.lib = ctx.lib
         B = len(params)
@@ -1112,7 +1159,35 @@ class Batch:
         ip = (_P * B)(*[i.ctypes.data for i in inits])
         pa = (GpetParams * B)(*params)
         h = _P()
-        if image_of is not None:  # (the library checks the map: its message says what is wrong with it)
+        self.frame_M = self.M  # (rows of the frames set_images takes; a banded batch's own M is H)
+        self.band_rows = None
+        if band is not None:
+            H, r0 = int(band[0]), band[1]
+            pair_of = image_of if image_of is not None else ([0] * B if share_image else list(range(B)))
+            n_pair = max(pair_of) + 1
+            r0a = None if r0 is None else np.ascontiguousarray(np.asarray(r0).reshape(-1), dtype=np.int64)
+            if r0a is not None and r0a.shape[0] != B:
+                raise ValueError("band_r0 has %d entries for %d edges" % (r0a.shape[0], B))
+            bd = GpetBand(H, n_pair, None if r0a is None else r0a.ctypes.data_as(C.POINTER(C.c_int64)), (C.c_int32 * B)(*pair_of))
+            im = GpetBandImages()
+            if raw is not None:
+                if raw.slots is not None:
+                    nk, kp, kh, kw, fo, ko = raw.multi_args()
+                else:  # (one kernel on every frame in order: the slot table of the single-kernel calls)
+                    kp = (_P * 1)(raw.kernel.ctypes.data)
+                    kh, kw = (C.c_int32 * 1)(raw.kernel.shape[0]), (C.c_int32 * 1)(raw.kernel.shape[1])
+                    nk, fo, ko = 1, (C.c_int32 * len(raw))(*range(len(raw))), (C.c_int32 * len(raw))()
+                pr = raw.pointer_array()
+                im.raw, im.pix, im.n_frames, im.n_kern = C.cast(pr, C.POINTER(C.c_void_p)), raw.pix, len(raw), nk
+                im.kern, im.kh, im.kw, im.frame_of, im.kernel_of = C.cast(kp, C.POINTER(C.c_void_p)), kh, kw, fo, ko
+                if raw.dn is not None:
+                    im.dn = C.pointer(raw.dn)
+                im.flags = raw.flags
+            else:
+                im.grad, im.flags = C.cast(gp, C.POINTER(C.c_void_p)), flags
+            ctx.check(self.lib.gpet_batch_create_banded(ctx.h, B, self.M, self.N, C.byref(bd), C.byref(im), pa, ip, C.byref(h)))
+            self.band_rows, self.M = H, H
+        elif image_of is not None:  # (the library checks the map: its message says what is wrong with it)
             if raw is not None and raw.slots is not None:
                 nk, kp, kh, kw, fo, ko = raw.multi_args()
                 ctx.check(self.lib.gpet_batch_create_raw_multi(ctx.h, B, self.M, self.N, n_img, io, len(raw), raw.pointer_array(), raw.pix,
@@ -1165,7 +1240,7 @@ class Batch:
         if raw is not None:  # (a RawFrames: gpet_batch_set_raw_images)
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
-            assert raw.n_slots == n_img and tuple(raw.shape) == (self.M, self.N)
+            assert raw.n_slots == n_img and tuple(raw.shape) == (self.frame_M, self.N)
             if raw.nlm is not None:  # (refused before the images are swapped: the batch stays on its old frames)
                 if self._nlm_buf is None:
                     self._nlm_buf = NlmFrames(self.ctx)
@@ -1189,7 +1264,7 @@ class Batch:
             self.ctx.check(self.lib.gpet_batch_set_images(self.h, gp, GRAD_ON_DEVICE | nf))
             return
         grads = [np.ascontiguousarray(g, dtype=np.float32) for g in grads]
-        assert len(grads) == n_img and all(g.shape == (self.M, self.N) for g in grads)
+        assert len(grads) == n_img and all(g.shape == (self.frame_M, self.N) for g in grads)
         gp = (_P * n_img)(*[g.ctypes.data for g in grads])
         self.ctx.check(self.lib.gpet_batch_set_images(self.h, gp, nf))
 
@@ -1412,6 +1487,33 @@ class Batch:
         p = C.POINTER(C.c_int32)
         self.ctx.check(self.lib.gpet_batch_warm_start_from(self.h, src.ctypes.data_as(p), int(warm_every), cnt.ctypes.data_as(p)))
         return cnt
+
+    def band_place(self, src_of=None, frm=None):
+        """gpet_batch_band_place: every edge's band for the next frame from the trace of its source, on the device, before the images
+        are swapped -- ``src_of`` a table as ``warm_start_from`` takes it; else ``frm`` ('medoid', 'best_cost', 'consensus': the source of
+        the edge's group in the kept ensemble); else the edge itself.  Enqueued only: ``band_r0()`` reads the table after the swap."""
+        p = C.POINTER(C.c_int32)
+        if src_of is not None:
+            src = np.ascontiguousarray(np.asarray(src_of).reshape(-1), dtype=np.int32)
+            if src.shape[0] != self.B:
+                raise ValueError("src_of has %d entries for %d edges" % (src.shape[0], self.B))
+            self.ctx.check(self.lib.gpet_batch_band_place(self.h, src.ctypes.data_as(p), -1))
+            return
+        self.ctx.check(self.lib.gpet_batch_band_place(self.h, None, -1 if frm is None else warm_from(frm)))
+
+    def band_set(self, r0):
+        """gpet_batch_band_set: the bands of the next swap, one first row per edge; GpetError (nothing touched) for a band that cannot
+        hold its edge's init points."""
+        a = np.ascontiguousarray(np.asarray(r0).reshape(-1), dtype=np.int64)
+        if a.shape[0] != self.B:
+            raise ValueError("band has %d entries for %d edges" % (a.shape[0], self.B))
+        self.ctx.check(self.lib.gpet_batch_band_set(self.h, a.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def band_r0(self):
+        """gpet_batch_band_r0: the first row of every edge's band as the image slots are now, (B,) int64."""
+        out = np.zeros(self.B, dtype=np.int64)
+        self.ctx.check(self.lib.gpet_batch_band_r0(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
 
     def set_history(self, level, iter_cap=64):
         """Iteration history of the traces this batch runs (gpet_batch_set_history): ``level`` None / 'obs' / 'curves' / 'full'

@@ -76,7 +76,99 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
   return rc;
 }
 
-static int load_images(gpet_batch* b, const ImageSource& s) { return s.raw ? convolve_images(b, s) : upload_images(b, s.grad, s.flags); }
+// ---- tracking bands (gpet_band_plan.h, gpet_k_band.inc) --------------------------------------------------------------------------
+// The n_pair full-frame gradient images into the batch's own memory: raw frames through conv_frames with the full frame's rows (the
+// convolution sees the rows above and below every band, the min-max is the full frame's); gradient images as they are.
+static int band_load_full(gpet_batch* b, const ImageSource& s) {
+  gpet_ctx* c = b->ctx;
+  BandState& bs = b->band;
+  const size_t px = (size_t)bs.M * b->bd.N;
+  std::vector<float*> dst((size_t)bs.n_pair);
+  for (int p = 0; p < bs.n_pair; ++p) dst[(size_t)p] = bs.G + (size_t)p * px;
+  if (s.raw) {
+    const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
+    const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, bs.M, b->bd.N, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax)
+                           : conv_frames(c, s.raw, bs.n_pair, s.pix, bs.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax);
+    if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
+    return rc;
+  }
+  const bool on_dev = (s.flags & GPET_GRAD_ON_DEVICE) != 0;
+  for (int p = 0; p < bs.n_pair; ++p)
+    if (!s.grad[p]) return fail(c, GPET_ERR_BAD_ARG, "gradient image %d is a null pointer", p);
+  for (int p = 0; p < bs.n_pair; ++p)
+    HIPCHK(c, hipMemcpyAsync(dst[(size_t)p], s.grad[p], px * sizeof(float), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!on_dev) HIPCHK(c, gpet_wait(c->stream));  // (pageable sources must stay valid until the copies have run)
+  return GPET_OK;
+}
+
+// The image step of the slots: they move to the bands placed since the last swap (r0 and the init rows, on the device), then every
+// edge's band of its full-frame image -- G_pair + r0 * N, read where it lies -- goes through min / max and the normalisation into the
+// edge's own slot, as upload_images treats the image an unbanded batch is given.
+static int band_slots(gpet_batch* b) {
+  gpet_ctx* c = b->ctx;
+  BandState& bs = b->band;
+  const int B = b->B;
+  if (bs.pending) {
+    HIPCHK(c, launch_band_apply(c->stream, b->d_edges, B, bs.n_init_max, bs.pend, bs.init, bs.r0));
+    bs.pending = false;
+  }
+  b->h_mm0.assign((size_t)2 * B, 0u);  // (every caller waits for the stream before it returns)
+  for (int e = 0; e < B; ++e) b->h_mm0[2 * (size_t)e] = 0xFFFFFFFFu;
+  HIPCHK(c, hipMemcpyAsync(b->d_minmax, b->h_mm0.data(), sizeof(unsigned int) * 2 * B, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, launch_band_images(c->stream, b->d_edges, B, bs.d_G_of, bs.r0, bs.H, b->bd.N, b->d_minmax));
+  return GPET_OK;
+}
+
+static int load_images(gpet_batch* b, const ImageSource& s) {
+  if (b->band.H) {
+    const int rc = band_load_full(b, s);
+    return rc ? rc : band_slots(b);
+  }
+  return s.raw ? convolve_images(b, s) : upload_images(b, s.grad, s.flags);
+}
+
+// smallest and largest init row of an edge
+static void init_row_span(const int64_t* init_xy, int n_init, long long* i_lo, long long* i_hi) {
+  *i_lo = *i_hi = init_xy[1];
+  for (int i = 1; i < n_init; ++i) {
+    *i_lo = std::min<long long>(*i_lo, init_xy[2 * i + 1]);
+    *i_hi = std::max<long long>(*i_hi, init_xy[2 * i + 1]);
+  }
+}
+
+// the device memory and tables of a banded batch, once the arena is laid out (n_init_max) and before the images are loaded; r0: the
+// bands of the first frame, init_full: the caller's init points
+static int band_setup(gpet_batch* b, const gpet_band& band, int M_full, const long long* r0, const int64_t* const* init_full, int n_init_max) {
+  gpet_ctx* c = b->ctx;
+  BandState& bs = b->band;
+  const int B = b->B;
+  bs.M = M_full;
+  bs.n_pair = band.n_pair;
+  bs.n_init_max = n_init_max;
+  bs.pair_of.assign(band.pair_of, band.pair_of + B);
+  HIPCHK(c, hipMalloc(&bs.G, band_image_bytes(bs.n_pair, M_full, b->bd.N)));
+  HIPCHK(c, hipMalloc(&bs.tab, band_table_bytes(B, n_init_max)));
+  HIPCHK(c, hipMalloc(&bs.d_G_of, sizeof(float*) * (size_t)B));
+  const BandTables t = band_tables(B, n_init_max);
+  bs.r0 = bs.tab + t.off_r0;
+  bs.pend = bs.tab + t.off_pend;
+  bs.fit = bs.tab + t.off_fit;
+  bs.lohi = bs.tab + t.off_lohi;
+  bs.init = bs.tab + t.off_init;
+  bs.h_tab.assign(t.count, 0);
+  for (int e = 0; e < B; ++e) {
+    bs.h_tab[t.off_r0 + e] = bs.h_tab[t.off_pend + e] = bs.h_tab[t.off_fit + e] = r0[e];
+    init_row_span(init_full[e], b->h_edges[e].n_init, &bs.h_tab[t.off_lohi + 2 * (size_t)e], &bs.h_tab[t.off_lohi + 2 * (size_t)e + 1]);
+    memcpy(&bs.h_tab[t.off_init + (size_t)e * 2 * (size_t)n_init_max], init_full[e], sizeof(long long) * 2 * (size_t)b->h_edges[e].n_init);
+  }
+  HIPCHK(c, hipMemcpyAsync(bs.tab, bs.h_tab.data(), sizeof(long long) * t.count, hipMemcpyHostToDevice, c->stream));
+  std::vector<const float*> g_of((size_t)B);
+  for (int e = 0; e < B; ++e) g_of[(size_t)e] = bs.G + (size_t)bs.pair_of[(size_t)e] * (size_t)M_full * (size_t)b->bd.N;
+  HIPCHK(c, hipMemcpyAsync(bs.d_G_of, g_of.data(), sizeof(float*) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gpet_wait(c->stream));  // (g_of is a local)
+  bs.H = band.H;  // (from here on the batch is banded)
+  return GPET_OK;
+}
 
 // gradient KDE of every image slot (gpet.py:127), once per slot through the slot's representative edge: where the representatives
 // are not the first n_img edges, over a device copy of their EdgeDev in slot order (as setup_struct_basis runs its classes)
@@ -177,11 +269,46 @@ static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
 
 // the one body of batch creation, whatever the images come as
 // image_of == nullptr: one image for all edges (share_image) or one per edge; else the image map (n_img, image_of[B])
+// band != nullptr (gpet_batch_create_banded): M is the full frame's, init_xy in its rows; the batch's own shape becomes (band->H, N)
+// with one image slot per edge, and src describes the band->n_pair full-frame images
 static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, int n_img,
-                             const int32_t* image_of, const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out) {
+                             const int32_t* image_of, const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out,
+                             const gpet_band* band = nullptr) {
   if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.raw) || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
+  const int M_full = M;
+  const int64_t* const* const init_full = init_xy;
+  std::vector<long long> band_r0;
+  std::vector<std::vector<int64_t>> band_init;
+  std::vector<const int64_t*> band_init_p;
+  if (band) {
+    if (!band->pair_of) return fail(c, GPET_ERR_BAD_ARG, "band: pair_of is a null pointer");
+    if (const char* why = image_map_check(B, band->n_pair, band->pair_of))
+      return fail(c, GPET_ERR_BAD_ARG, "band: image table: %s (B = %d, n_pair = %d)", why, B, band->n_pair);
+    band_r0.resize((size_t)B);
+    band_init.resize((size_t)B);
+    band_init_p.resize((size_t)B);
+    for (int e = 0; e < B; ++e) {
+      if (!init_xy[e] || params[e].n_init < 1) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_banded: edge %d has no init points", e);
+      long long i_lo, i_hi;
+      init_row_span(init_xy[e], params[e].n_init, &i_lo, &i_hi);
+      const long long r0 = band->r0 ? (long long)band->r0[e] : -1;
+      if (const char* why = band_check(M, band->H, r0, i_lo, i_hi, !band->r0))
+        return fail(c, GPET_ERR_BAD_ARG, "band of edge %d: %s (M = %d, H = %d, r0 = %lld, init rows %lld .. %lld)", e, why, M, (int)band->H,
+                    r0, i_lo, i_hi);
+      if (i_lo < 0 || i_hi > M - 1)
+        return fail(c, GPET_ERR_BAD_ARG, "band of edge %d: an init point lies outside the frame (init rows %lld .. %lld, M = %d)", e, i_lo, i_hi, M);
+      band_r0[(size_t)e] = band->r0 ? r0 : band_place(M, band->H, i_lo, i_hi, i_lo, i_hi);  // (the first frame: t = the init rows)
+      band_init[(size_t)e].assign(init_xy[e], init_xy[e] + 2 * (size_t)params[e].n_init);
+      for (int i = 0; i < params[e].n_init; ++i) band_init[(size_t)e][2 * (size_t)i + 1] -= band_r0[(size_t)e];
+      band_init_p[(size_t)e] = band_init[(size_t)e].data();
+    }
+    init_xy = band_init_p.data();
+    M = band->H;
+    share_image = 0;
+    image_of = nullptr;
+  }
   const bool mapped = image_of != nullptr;
   if (mapped) {
     if (const char* why = image_map_check(B, n_img, image_of)) return fail(c, GPET_ERR_BAD_ARG, "image map: %s (B = %d, n_img = %d)", why, B, n_img);
@@ -190,7 +317,7 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
     n_img = share_image ? 1 : B;
   }
   if (src.raw) {
-    const int rc0 = check_raw_source(c, src, n_img);
+    const int rc0 = check_raw_source(c, src, band ? band->n_pair : n_img);
     if (rc0) return rc0;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -270,7 +397,13 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   HIPCHK(c, hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming));
   // upload: gradient image(s) re-normalised on the device (gpet.py:97) or made there from raw frames, inits, initial scalars
   HIPCHK(c, hipMalloc(&b->d_raw, (size_t)M * N * sizeof(float)));
-  int rc = load_images(b, src);
+  int rc = GPET_OK;
+  if (band) {  // (the full-frame images now; the slots once d_edges is on the device: the band kernels read it)
+    rc = band_setup(b, *band, M_full, band_r0.data(), init_full, bb.n_init_max);
+    if (!rc) rc = band_load_full(b, src);
+  } else {
+    rc = load_images(b, src);
+  }
   if (rc) return rc;
   // (one copy each for the init points and the initial scalars of all edges: 3 x B small copies were most of the constructor)
   std::vector<long long> h_init((size_t)B * 2 * (size_t)bb.n_init_max, 0);
@@ -280,6 +413,10 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   HIPCHK(c, upload_pristine_scalars(b));
   HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * B, hipMemcpyHostToDevice, c->stream));
   if (any_gen_nu) HIPCHK(c, launch_rho_tab(c->stream, b->d_edges, B, N));
+  if (band) {
+    rc = band_slots(b);
+    if (rc) return rc;
+  }
   rc = image_kde(b);
   if (rc) return rc;
   HIPCHK(c, gpet_wait(c->stream));
@@ -364,6 +501,60 @@ int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* r
   return gpet_batch_create_raw_dn(c, B, M, N, raw, pix, kern, kh, kw, nullptr, share_image, params, init_xy, flags, out);
 }
 
+int gpet_batch_create_banded(gpet_ctx* c, int B, int M, int N, const gpet_band* band, const gpet_band_images* im,
+                             const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out) {
+  if (!band || !im || (!im->grad && !im->raw)) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_banded: bad argument");
+  ImageSource src;
+  src.flags = im->flags;
+  if (im->grad) {
+    src.grad = im->grad;
+    return batch_create_from(c, B, M, N, src, 0, 0, nullptr, params, init_xy, out, band);
+  }
+  if (!im->kern || !im->kh || !im->kw || !im->frame_of || !im->kernel_of)
+    return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_banded: raw frames need their kernels and the slot table");
+  const DenoiseSpec spec = dn_spec(im->dn);
+  const ConvMulti mk{im->n_kern, im->kern, im->kh, im->kw, band->n_pair, im->frame_of, im->kernel_of};
+  src.raw = im->raw;
+  src.pix = im->pix;
+  src.dn = im->dn ? &spec : nullptr;
+  src.multi = &mk;
+  src.n_frames = im->n_frames;
+  return batch_create_from(c, B, M, N, src, 0, 0, nullptr, params, init_xy, out, band);
+}
+
+// the explicit table for the next swap (the placed one: gpet_batch_band_place, gpet_api_ensemble.hip)
+int gpet_batch_band_set(gpet_batch* b, const int64_t* r0) {
+  GPET_BATCH_SCOPE(b);
+  if (!b || !r0) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  BandState& bs = b->band;
+  if (!bs.H) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_band_set: the batch has no bands (gpet_batch_create_banded makes one that has)");
+  const BandTables t = band_tables(b->B, bs.n_init_max);
+  for (int e = 0; e < b->B; ++e) {
+    const long long i_lo = bs.h_tab[t.off_lohi + 2 * (size_t)e], i_hi = bs.h_tab[t.off_lohi + 2 * (size_t)e + 1];
+    if (const char* why = band_check(bs.M, bs.H, r0[e], i_lo, i_hi))
+      return fail(c, GPET_ERR_BAD_ARG, "band of edge %d: %s (M = %d, H = %d, r0 = %lld, init rows %lld .. %lld)", e, why, bs.M, bs.H,
+                  (long long)r0[e], i_lo, i_hi);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gpet_wait(c->stream));  // (h_r0 may still be the source of an earlier copy)
+  bs.h_r0.assign(r0, r0 + b->B);
+  HIPCHK(c, hipMemcpyAsync(bs.pend, bs.h_r0.data(), sizeof(long long) * (size_t)b->B, hipMemcpyHostToDevice, c->stream));
+  bs.pending = true;
+  return GPET_OK;
+}
+
+int gpet_batch_band_r0(gpet_batch* b, int64_t* r0_out) {
+  GPET_BATCH_SCOPE(b);
+  if (!b || !r0_out) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  if (!b->band.H) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_band_r0: the batch has no bands");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(r0_out, b->band.r0, sizeof(long long) * (size_t)b->B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, gpet_wait(c->stream));
+  return GPET_OK;
+}
+
 void gpet_batch_destroy(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return;
@@ -384,6 +575,9 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->d_results) (void)hipFree(b->d_results);
   if (b->d_hist) (void)hipFree(b->d_hist);
   ensemble_free(b);
+  if (b->band.G) (void)hipFree(b->band.G);
+  if (b->band.tab) (void)hipFree(b->band.tab);
+  if (b->band.d_G_of) (void)hipFree(b->band.d_G_of);
   if (b->fit) {
     (void)hipStreamSynchronize(b->fit);
     (void)hipStreamDestroy(b->fit);
@@ -413,7 +607,7 @@ void gpet_batch_destroy(gpet_batch* b) {
 
 int gpet_batch_size(const gpet_batch* b) { return b ? b->B : 0; }
 
-int gpet_batch_image_count(const gpet_batch* b) { return b ? b->n_img : 0; }
+int gpet_batch_image_count(const gpet_batch* b) { return b ? batch_source_count(b) : 0; }
 
 int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count) {
   if (!b || e < 0 || e >= b->B || !out) return GPET_ERR_BAD_ARG;
@@ -577,7 +771,10 @@ int gpet_batch_warm_start(gpet_batch* b, int warm_every, int32_t* n_obs_out) {
   const int ready = gpet_batch_warm_start_ready(b);
   if (ready) return ready;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_warm_start(c->stream, b->d_edges, b->B, warm_every));
+  if (b->band.H)  // (across bands: k_warm_start_src's banded form with every edge its own source)
+    HIPCHK(c, launch_warm_start_band(c->stream, b->d_edges, b->B, nullptr, nullptr, nullptr, 0, 0, warm_every, b->band.fit, b->band.r0));
+  else
+    HIPCHK(c, launch_warm_start(c->stream, b->d_edges, b->B, warm_every));
   return warm_start_finish(b, n_obs_out);
 }
 
@@ -907,7 +1104,7 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
-  const int rc = check_raw_source(b->ctx, src, b->n_img);
+  const int rc = check_raw_source(b->ctx, src, batch_source_count(b));
   if (rc) return rc;
   return batch_set_images_from(b, src);
 }
@@ -919,7 +1116,7 @@ int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* con
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   const DenoiseSpec spec = dn_spec(dn);
-  const ConvMulti mk{n_kern, kern, kh, kw, b->n_img, frame_of, kernel_of};
+  const ConvMulti mk{n_kern, kern, kh, kw, batch_source_count(b), frame_of, kernel_of};
   ImageSource src;
   src.raw = raw;
   src.pix = pix;
@@ -927,7 +1124,7 @@ int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* con
   src.flags = flags;
   src.multi = &mk;
   src.n_frames = n_frames;
-  const int rc = check_raw_source(b->ctx, src, b->n_img);
+  const int rc = check_raw_source(b->ctx, src, batch_source_count(b));
   if (rc) return rc;
   return batch_set_images_from(b, src);
 }

@@ -323,19 +323,79 @@ static int warm_start_sourced(gpet_batch* b, int from, const int32_t* src_of, in
   if (src_of) {
     std::copy(src_of, src_of + B, s->h_src.begin());
     HIPCHK(c, hipMemcpyAsync(s->src, s->h_src.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_warm_start_src(st, b->d_edges, B, s->src, nullptr, nullptr, 0, 0, warm_every));
+    if (b->band.H) HIPCHK(c, launch_warm_start_band(st, b->d_edges, B, s->src, nullptr, nullptr, 0, 0, warm_every, b->band.fit, b->band.r0));
+    else HIPCHK(c, launch_warm_start_src(st, b->d_edges, B, s->src, nullptr, nullptr, 0, 0, warm_every));
   } else {
     const EnsembleLayout K = ensemble_layout(s->kept_G, B, s->kept_len_cap);
     const int32_t* d_group_of = reinterpret_cast<const int32_t*>(s->kept + warm_kept_group_off(s->kept_G, B, s->kept_len_cap));
     // the sources from the records' heads on the stream: the host does not wait for them, it reads them with the scalars below
     HIPCHK(c, launch_warm_sources(st, B, d_group_of, s->kept, (long long)K.record_bytes, from, s->src));
-    HIPCHK(c, launch_warm_start_src(st, b->d_edges, B, s->src, d_group_of, s->kept, (long long)K.record_bytes, (long long)K.off_trace,
-                                    warm_every));
+    if (b->band.H)
+      HIPCHK(c, launch_warm_start_band(st, b->d_edges, B, s->src, d_group_of, s->kept, (long long)K.record_bytes, (long long)K.off_trace,
+                                       warm_every, b->band.fit, b->band.r0));
+    else
+      HIPCHK(c, launch_warm_start_src(st, b->d_edges, B, s->src, d_group_of, s->kept, (long long)K.record_bytes, (long long)K.off_trace,
+                                      warm_every));
     if (src_out) HIPCHK(c, hipMemcpyAsync(s->h_src.data(), s->src, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
   }
   rc = warm_start_finish(b, n_obs_out);  // (the one copy of the scalars and the one wait, as gpet_batch_warm_start; drops the kept ensemble)
   if (rc) return rc;
   if (src_out) std::copy(s->h_src.begin(), s->h_src.end(), src_out);
+  return GPET_OK;
+}
+
+// Placement of every edge's band for the next frame (k_band_place, the rule of band_place), enqueued: the refusals are those of the warm
+// start that will follow with the same sources, checked the same way, and nothing is touched when one applies.
+int gpet_batch_band_place(gpet_batch* b, const int32_t* src_of, int from) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  const int B = b->B;
+  BandState& bs = b->band;
+  if (!bs.H) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_band_place: the batch has no bands (gpet_batch_create_banded makes one that has)");
+  const int ready = gpet_batch_warm_start_ready(b);
+  if (ready) return ready;
+  const bool groups = !src_of && from >= 0;
+  char msg[384];
+  if (groups) {
+    const int rc = warm_groups_check(from, b->ens_kept && b->ens && b->ens->kept, msg, sizeof msg);
+    if (rc) return fail(c, rc, "%s", msg);
+  } else if (src_of) {
+    std::vector<int32_t> x_st((size_t)B), x_en((size_t)B);
+    for (int e = 0; e < B; ++e) {
+      x_st[e] = b->h_edges[e].x_st;
+      x_en[e] = b->h_edges[e].x_en;
+    }
+    const int rc = warm_from_check(B, src_of, x_st.data(), x_en.data(), msg, sizeof msg);
+    if (rc) return fail(c, rc, "%s", msg);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int32_t* d_src = nullptr;
+  const int32_t* d_group_of = nullptr;
+  const char* d_kept = nullptr;
+  long long record_bytes = 0, off_trace = 0;
+  if (groups || src_of) {
+    EnsembleScratch* s = nullptr;
+    const int rc = scratch(b, &s);
+    if (rc) return rc;
+    if (!s->src) HIPCHK(c, hipMalloc(&s->src, sizeof(int32_t) * (size_t)B));
+    if (src_of) {
+      s->h_src.assign(src_of, src_of + B);  // (every call that used it has waited for its copy)
+      HIPCHK(c, hipMemcpyAsync(s->src, s->h_src.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, st));
+      HIPCHK(c, gpet_wait(st));             // (and so does this one: the explicit table is not the path of a sequence)
+    } else {
+      const EnsembleLayout K = ensemble_layout(s->kept_G, B, s->kept_len_cap);
+      d_group_of = reinterpret_cast<const int32_t*>(s->kept + warm_kept_group_off(s->kept_G, B, s->kept_len_cap));
+      d_kept = s->kept;
+      record_bytes = (long long)K.record_bytes;
+      off_trace = (long long)K.off_trace;
+      HIPCHK(c, launch_warm_sources(st, B, d_group_of, d_kept, record_bytes, from, s->src));
+    }
+    d_src = s->src;
+  }
+  HIPCHK(c, launch_band_place(st, b->d_edges, B, d_src, d_group_of, d_kept, record_bytes, off_trace, bs.M, bs.fit, bs.r0, bs.lohi, bs.pend));
+  bs.pending = true;
   return GPET_OK;
 }
 

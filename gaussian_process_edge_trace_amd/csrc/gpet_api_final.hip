@@ -401,6 +401,8 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   b->have_fit = false;  // the loop's L/alpha were overwritten by the converged fit
   b->have_results = true;  // (fin_out + lb_theta_out: what gpet_batch_results packs)
   b->have_last_fit = true;  // (fin_out: what gpet_batch_warm_start reads, past the reset of the next frame)
+  if (b->band.H)  // (and the bands these fits are expressed in: what placement and the warm start across bands add to their rows)
+    HIPCHK(c, hipMemcpyAsync(b->band.fit, b->band.r0, sizeof(long long) * (size_t)b->B, hipMemcpyDeviceToDevice, c->stream));
   return check_device_status(b);
 }
 

@@ -61,6 +61,21 @@ struct gpet_ctx {
   std::string err;
 };
 
+// what a banded batch owns in addition (gpet_band_plan.h): the full-frame gradient images, one per (frame, kernel) pair, and the int64
+// tables the band kernels read.  H == 0: the batch has no bands, holds nothing of this and enqueues nothing for it
+struct BandState {
+  int H = 0, M = 0;                  // rows of a band, rows of the full frame (the batch's own image shape is (H, N))
+  int n_pair = 0, n_init_max = 0;
+  std::vector<int32_t> pair_of;      // [B] the full-frame image of every edge
+  float* G = nullptr;                // [n_pair][M * N]
+  const float** d_G_of = nullptr;    // [B] device table: G + pair_of[e] * M * N
+  long long* tab = nullptr;          // band_tables(B, n_init_max), one allocation; the pointers below lie in it
+  long long *r0 = nullptr, *pend = nullptr, *fit = nullptr, *lohi = nullptr, *init = nullptr;
+  std::vector<long long> h_tab;      // the host copy the tables were uploaded from: (i_lo, i_hi) and the full-frame inits stay valid
+  std::vector<long long> h_r0;       // staging of gpet_batch_band_set (kept alive for the asynchronous copy)
+  bool pending = false;              // r0_pend holds bands the slots have not moved to yet (gpet_batch_band_place / _set)
+};
+
 struct gpet_batch {
   gpet_ctx* ctx = nullptr;
   int B = 0;
@@ -164,6 +179,7 @@ struct gpet_batch {
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;
   gpet_history_plan hist{};
+  BandState band;  // tracking bands (gpet_batch_create_banded)
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it
 };
 // first statement of every entry point that works on a batch: its option table for the calling thread
@@ -240,6 +256,8 @@ int fetch_all_scalars(gpet_batch* b);
 // the end of every warm start, after its kernel: histories, flags, the one copy of the scalars and the one wait; n_obs_out may be nullptr
 int warm_start_finish(gpet_batch* b, int32_t* n_obs_out);
 int check_device_status(gpet_batch* b);
+// the images a caller hands over on a banded batch: n_pair of them (else the batch's image slots)
+static inline int batch_source_count(const gpet_batch* b) { return b->band.H ? b->band.n_pair : b->n_img; }
 // what the loop's generator stores of a sample row: the r0 (rounded to 4) leading normals a structured batch multiplies
 static inline int loop_z_store(const gpet_batch* b) {
   if (!b->structured || b->bd.r0_max < 1) return 0;

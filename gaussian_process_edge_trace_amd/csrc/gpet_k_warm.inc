@@ -95,14 +95,20 @@ __global__ void __launch_bounds__(256) k_warm_sources(int B, const int32_t* __re
 // EdgeDev entry (the table no kernel writes) and fin_out (written by the converged fit alone, long before this launch) -- never their
 // gpet_scalars: the source's own wave is rewriting those in this very launch, so what is a member and what the source is was decided
 // before it, by the ensemble reduction and the src table.
+// BAND (gpet_k_band.inc launches it; gpet_band_plan.h): the rows of the source are in ITS band of the last converged fits, the
+// destination's image is the band the swap has just moved it to -- every row goes through the offset r0_fit[source] - r0_cur[e]
+// (the consensus row: the group shares one band, so the destination's own r0_fit) before the row test against the band's H = E.M rows.
+// Without BAND the two tables are not read and the kernel is what it was.
+template <bool BAND>
 __global__ void __launch_bounds__(64) k_warm_start_src(EdgeDev* edges, int B, const int32_t* __restrict__ src,
                                                        const int32_t* __restrict__ group_of, const char* __restrict__ kept,
-                                                       long long record_bytes, long long off_trace, int warm_every) {
+                                                       long long record_bytes, long long off_trace, int warm_every,
+                                                       const long long* __restrict__ r0_fit, const long long* __restrict__ r0_cur) {
   const int e = blockIdx.x;
   const EdgeDev E = edges[e];
   gpet_scalars* sc = E.sc;  // (the destination's own)
   const int lane = threadIdx.x;
-  const int s = src[e];     // (uniform over the wave: every branch on it is)
+  const int s = (BAND && !src) ? e : src[e];  // (uniform over the wave: every branch on it is; BAND without a table: the edge itself)
   const double* __restrict__ mean = nullptr;
   const long long* __restrict__ cons = nullptr;
   if (s >= 0 && s < B) mean = edges[s].fin_out;
@@ -111,14 +117,19 @@ __global__ void __launch_bounds__(64) k_warm_start_src(EdgeDev* edges, int B, co
   const long long last = (long long)E.Lg - 1;  // candidates are grid indices below it
   const double y_max = (double)(E.M - 1);
   const long long yi_max = (long long)E.M - 1;
+  long long off = 0;  // (BAND: from the source's band into the destination's; |off| < M, exact as a double)
+  if (BAND && (mean || cons)) off = r0_fit[mean ? s : e] - r0_cur[e];
+  const double off_d = (double)off;
   auto kept_at = [&](long long k) {  // (k < last) as k_warm_start's; the row from the source
     const long long x = (long long)E.x_st + k;
     bool row_in;
     if (mean) {
-      const double y = rint(mean[k]);  // (NaN fails both comparisons)
+      double y = rint(mean[k]);  // (NaN fails both comparisons)
+      if (BAND) y += off_d;
       row_in = y >= 0.0 && y <= y_max;
     } else {
-      const long long y = cons[2 * k];
+      long long y = cons[2 * k];
+      if (BAND) y = y < -(1ll << 40) ? y : y + off;  // (INT64_MIN, the NaN median, stays what it is)
       row_in = y >= 0 && y <= yi_max;
     }
     return x > E.x_st && x < E.x_en && row_in;
@@ -145,7 +156,9 @@ __global__ void __launch_bounds__(64) k_warm_start_src(EdgeDev* edges, int B, co
       const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
       if (take && pos < n_keep) {
         E.obs_xy[2 * pos] = (long long)E.x_st + k;
-        E.obs_xy[2 * pos + 1] = mean ? (long long)rint(mean[k]) : cons[2 * k];  // (an integer in [0, M - 1]: exact)
+        long long y = mean ? (long long)rint(mean[k]) : cons[2 * k];  // (an integer in [0, M - 1]: exact)
+        if (BAND) y += off;
+        E.obs_xy[2 * pos + 1] = y;
       }
       base += __popcll(bal);
     }
@@ -176,6 +189,7 @@ hipError_t launch_warm_sources(hipStream_t st, int B, const int32_t* d_group_of,
 hipError_t launch_warm_start_src(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
                                  long long record_bytes, long long off_trace, int warm_every) {
   (void)hipGetLastError();
-  hipLaunchKernelGGL(k_warm_start_src, dim3(B), dim3(64), 0, st, d_edges, B, d_src, d_group_of, d_kept, record_bytes, off_trace, warm_every);
+  hipLaunchKernelGGL(k_warm_start_src<false>, dim3(B), dim3(64), 0, st, d_edges, B, d_src, d_group_of, d_kept, record_bytes, off_trace, warm_every,
+                     (const long long*)nullptr, (const long long*)nullptr);
   return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
+#include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
 #include "gpet_warm_plan.h"  // warm start from a group's medoid / best cost / consensus or from another edge: source per edge, refusals
 
 namespace gpet {
@@ -105,6 +106,21 @@ hipError_t launch_warm_sources(hipStream_t st, int B, const int32_t* d_group_of,
 // d_kept; both may be nullptr when no entry is WARM_SRC_CONSENSUS), or nothing
 hipError_t launch_warm_start_src(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
                                  long long record_bytes, long long off_trace, int warm_every);
+// tracking bands (gpet_k_band.inc; the rule: gpet_band_plan.h).  The int64 tables are the banded batch's own, on the device.
+// r0_pend[e] = band_place of edge e from the trace of its source (d_src == nullptr: the edge itself; else as launch_warm_start_src)
+hipError_t launch_band_place(hipStream_t st, const EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
+                             long long record_bytes, long long off_trace, long long M, const long long* d_r0_fit, const long long* d_r0_cur,
+                             const long long* d_lohi, long long* d_r0_pend);
+// r0_cur = r0_pend, and every edge's init rows in the coordinates of its new band
+hipError_t launch_band_apply(hipStream_t st, const EdgeDev* d_edges, int B, int n_init_max, const long long* d_r0_pend,
+                             const long long* d_init_full, long long* d_r0_cur);
+// launch_minmax + launch_normalise of the band d_G_of[e] + r0_cur[e] * N (H x N) into EdgeDev::grad of every edge e
+hipError_t launch_band_images(hipStream_t st, const EdgeDev* d_edges, int B, const float* const* d_G_of, const long long* d_r0_cur, int H,
+                              int N, unsigned int* d_minmax);
+// launch_warm_start_src across bands: every row through r0_fit[source] - r0_cur[e]
+hipError_t launch_warm_start_band(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
+                                  long long record_bytes, long long off_trace, int warm_every, const long long* d_r0_fit,
+                                  const long long* d_r0_cur);
 // the record of the iteration just completed for every edge whose counter equals iter_expect (0: every edge with a counter >= 1), gpet_k_history.inc
 hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const gpet_history_plan& P, int iter_expect);
 hipError_t launch_pixels_reset(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

@@ -31,5 +31,6 @@ namespace gpet {
 #include "gpet_k_history.inc"
 #include "gpet_k_launch.inc"
 #include "gpet_k_ensemble.inc"
+#include "gpet_k_band.inc"
 
 }  // namespace gpet

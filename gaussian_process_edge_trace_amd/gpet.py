@@ -379,7 +379,8 @@ def _raw_stack(raw_imgs):
 
 
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
-                         raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None):
+                         raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None, band_rows=None, band_r0=None,
+                         inits=None):
     """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
     ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
     images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
@@ -388,7 +389,21 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
     ``grad_kernel`` a list of kernels with ``kernel_of`` (one index per edge): edge e reads its raw frame -- ``image_of[e]`` if
     ``image_of`` is given (``n_edges`` then counts the frames), else the shared one or its own -- through
     ``grad_kernel[kernel_of[e]]``.  The dict then also has ``image_of``, the edge-to-slot map of the slot table
-    (``_lib.derive_slots``) the ``raw`` of ``batch`` carries, and ``edge_frames``, the frame of every edge."""
+    (``_lib.derive_slots``) the ``raw`` of ``batch`` carries, and ``edge_frames``, the frame of every edge.
+    ``band_rows=H`` (with ``inits``, the init points of every edge, and optionally ``band_r0``): tracking bands -- the images are
+    full frames, and the dict also has ``band`` = (H, r0 list or None) as ``resolve_bands`` checked it and ``trace_shape`` = (H, N),
+    the shape the edges' parameters are resolved for.  ``band_rows=None``: exactly the dict described above."""
+    if band_rows is not None:
+        if all(a is None for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs)):
+            raise ValueError("band_rows needs images: the full frames (raw_imgs / raw_device_ptrs with grad_kernel) or full-frame "
+                             "gradient images (grad_imgs / grad_device_ptrs) the bands are cut from")
+        src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
+                                   denoise, kernel_of=kernel_of, image_of=image_of)
+        src["band"] = resolve_bands(inits, src["shape"][0], band_rows, band_r0)
+        src["trace_shape"] = (src["band"][0], src["shape"][1])
+        return src
+    if band_r0 is not None:
+        raise ValueError("band_r0 places the bands of band_rows: it needs band_rows")
     have_grad = grad_imgs is not None or grad_device_ptrs is not None
     have_raw = raw_imgs is not None or raw_device_ptrs is not None
     if denoise is not None and not have_raw:
@@ -467,6 +482,72 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
     return dict(kind="grad", share=share, shape=tuple(g32[0].shape), on_device=False, batch=dict(grads=g32))
 
 
+def init_row_span(init):
+    """(i_lo, i_hi): the smallest and largest row of an edge's init points ((n, 2) xy)."""
+    rows = np.asarray(init).reshape(-1, 2)[:, 1].astype(np.int64)
+    return int(rows.min()), int(rows.max())
+
+
+def resolve_bands(inits, M, band_rows, band_r0=None):
+    """(H, r0): the tracking bands of a batch as the constructor accepts them, decided without a device -- ``H = band_rows`` rows for
+    every edge, ``r0`` a list with one first row per edge, or None when ``band_r0`` is None (the library then places every band from
+    its edge's init rows, ``_lib.band_place``).  ValueError naming the edge and the cause (the words of csrc/gpet_band_plan.h's
+    band_check) for H > M, a ``band_r0`` of the wrong length, an r0 outside [0, M - H], init rows that span more than H rows, an init
+    outside its band."""
+    if inits is None:
+        raise ValueError("band_rows needs the init points of every edge")
+    H, M = int(band_rows), int(M)
+    r0 = None
+    if band_r0 is not None:
+        r0 = [int(v) for v in np.asarray(band_r0).reshape(-1)]
+        if len(r0) != len(inits):
+            raise ValueError("band_r0 has %d entries for %d edges" % (len(r0), len(inits)))
+    for e, init in enumerate(inits):
+        i_lo, i_hi = init_row_span(init)
+        why = _lib.band_refusal(M, H, None if r0 is None else r0[e], i_lo, i_hi)
+        if why is None and (i_lo < 0 or i_hi > M - 1):
+            why = "an init point lies outside the frame"
+        if why is not None:
+            raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %s, init rows %d .. %d)"
+                             % (e, why, M, H, "placed" if r0 is None else r0[e], i_lo, i_hi))
+    return H, r0
+
+
+def resolve_frame_band(band_rows, band, warm_every, n_edges):
+    """What ``set_frame(band=...)`` does with the bands, decided without a device: None (they stay), 'follow' (placed on the device
+    from the last traces) or a list of n_edges first rows.  ``band=None`` means 'follow' when ``warm_every`` is given on a banded
+    batch, else None.  ValueError for ``band`` on a batch without bands, an unknown word, a table of the wrong length."""
+    if band_rows is None:
+        if band is not None:
+            raise ValueError("band=%r: the batch has no tracking bands (it was built without band_rows)" % (band,))
+        return None
+    if band is None:
+        return "follow" if warm_every is not None else None
+    if isinstance(band, str):
+        if band != "follow":
+            raise ValueError("band must be 'follow' or one first row per edge, not %r" % (band,))
+        return band
+    r0 = [int(v) for v in np.asarray(band).reshape(-1)]
+    if len(r0) != n_edges:
+        raise ValueError("band has %d entries for %d edges" % (len(r0), n_edges))
+    return r0
+
+
+def _shift_rows(d, keys, r0, col=None):
+    """``d`` with ``r0`` added to the row-valued entries ``keys`` (column ``col`` of 2-D ones)."""
+    out = dict(d)
+    for k in keys:
+        if k not in d or d[k] is None:
+            continue
+        a = np.array(d[k], copy=True)
+        if col is None or a.ndim == 1:
+            a = a + r0
+        else:
+            a[..., col] += r0
+        out[k] = a
+    return out
+
+
 class GP_Edge_Tracing_Batch(object):
     """B independent edges traced together on one GPU (BASELINE config 4's per-GPU share).
 
@@ -483,7 +564,7 @@ class GP_Edge_Tracing_Batch(object):
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
-                 denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None):
+                 denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None, band_rows=None, band_r0=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -514,7 +595,13 @@ class GP_Edge_Tracing_Batch(object):
         device -- the new observation set, the score threshold, the optimal cost and sample index; from 'curves' the optimal
         curve; with 'full' the per-column mean and std of all samples -- read with ``history()`` after ``run_loop`` or
         ``__call__``.  ``history_cap``: records kept per edge; later iterations are counted in ``dropped``, the trace is not
-        affected.  No result depends on the level."""
+        affected.  No result depends on the level.
+        ``band_rows=H`` (with ``band_r0``, one first row per edge; default: placed from the init rows): tracking bands -- the images
+        are full frames (raw frames, or full-frame gradient images), and edge e traces rows ``r0 .. r0 + H - 1`` of its full-frame
+        gradient image only: bit for bit what a batch without bands gives for the cropped gradient image ``G[r0:r0 + H]`` and the
+        init ``init - (0, r0)``, with every row it returns (traces, intervals, ``history``, ``ensemble``, ``results``) raised by
+        ``r0`` again.  ``inits`` and ``obs`` are in full-frame rows; presets of ``kernel_options`` that depend on the image height
+        see H.  ``band_r0`` (attribute) holds the current table; ``set_frame(band=...)`` moves the bands."""
         B = len(inits)
         if image_of is not None:
             image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
@@ -531,8 +618,10 @@ class GP_Edge_Tracing_Batch(object):
         if kernel_of is not None and len(np.asarray(kernel_of).reshape(-1)) != B:
             raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
         src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
-                                   raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of)
+                                   raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of, band_rows=band_rows,
+                                   band_r0=band_r0, inits=None if band_rows is None else list(inits))
         self._denoise = denoise
+        self.band_rows, self.band_r0 = (None, None) if band_rows is None else (src["band"][0], src["band"][1])
         # (a slot table: the kernels, the kernel and the frame of every edge are remembered for set_frame; the batch's own image
         #  map is then the edge-to-slot map)
         self._kernel_of, self._edge_frames, self._n_frames = None, None, None
@@ -545,7 +634,7 @@ class GP_Edge_Tracing_Batch(object):
             self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
         self._raw_dtype = raw_dtype
         share = src["share"] and image_of is None  # (a map of one image is the shared layout, decided by the library)
-        shapes = [src["shape"]] * B
+        shapes = [src.get("trace_shape", src["shape"])] * B  # (banded: the parameters are those of the (H, N) crop)
         assert len(seeds) == B
         obs = [np.array([])] * B if obs is None else list(obs)
         inits = list(inits)  # (an ndarray of shape (B, n, 2) makes a fresh view per access: materialise the items once)
@@ -575,7 +664,14 @@ class GP_Edge_Tracing_Batch(object):
             abi.append(hit[1])
         self._ctx = _ctx if _ctx is not None else _lib.Context(device, stream)
         kw = dict(src["batch"])
+        if band_rows is not None:
+            kw["band"] = (self.band_rows, self.band_r0)
         self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, image_of=image_of, **kw)
+        if band_rows is not None:  # (the table as the library placed or took it; observations are kept in band rows from here on)
+            self.band_r0 = self._batch.band_r0()
+            self._init_span = [init_row_span(p["init"]) for p in self._ps]
+            for p, r0 in zip(self._ps, self.band_r0):
+                p["obs"] = p["obs"] - np.array([0, int(r0)], dtype=np.int64)
         if sample_dtype is not None:
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
@@ -610,7 +706,7 @@ class GP_Edge_Tracing_Batch(object):
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
                   raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None, warm_from=None,
-                  group_of=None, tol=2):
+                  group_of=None, tol=2, band=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -633,7 +729,13 @@ class GP_Edge_Tracing_Batch(object):
         group without members none.  The ensemble is reduced and kept on the device BEFORE the images are swapped (its final costs
         are scored on the frame just traced; gpet_batch_ensemble_keep), the warm start is made from it after the swap
         (gpet_batch_warm_start_groups); ``last_ensemble`` is then the list ``ensemble(group_of, tol)`` would have returned for the
-        frame just left.  ``warm_from=None`` (default): every edge from its own fit, as above."""
+        frame just left.  ``warm_from=None`` (default): every edge from its own fit, as above.
+        ``band`` (a batch with ``band_rows``): ``'follow'`` -- every band is placed on the device from the trace its edge's warm start
+        comes from (its own fit, or its group's source with ``warm_from``; ``_lib.band_place``), after the ensemble is kept and before
+        the images are swapped, so a group's members share one band -- or one first row per edge; the default is ``'follow'`` with
+        ``warm_every`` and "the bands stay" without.  The warm start then carries every row from the source's old band into the
+        edge's new one.  A band that cannot hold its edge's init points raises ValueError and leaves the batch as it was.  ``obs``
+        are in full-frame rows."""
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
         if warm_from is not None:
@@ -645,13 +747,27 @@ class GP_Edge_Tracing_Batch(object):
             groups = self.group_table(group_of)
             if not float(tol) >= 0.0:
                 raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
-        if warm_every is not None:
+        mode = resolve_frame_band(self.band_rows, band, warm_every, len(self._ps))
+        if isinstance(mode, list):
+            for e, r0 in enumerate(mode):
+                why = _lib.band_refusal(self._batch.frame_M, self.band_rows, r0, *self._init_span[e])
+                if why is not None:
+                    raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %d, init rows %d .. %d)"
+                                     % ((e, why, self._batch.frame_M, self.band_rows, r0) + self._init_span[e]))
+        if warm_every is not None or mode == "follow":
             self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
         if warm_from is not None:
             # (before the swap: the final costs that break the medoid's ties and define best_cost are those of the frame just traced)
             self._batch.ensemble_keep(groups, tol)
             keys = ("trace", "median", "q_lo", "q_hi", "min", "max", "agree", "members", "off", "cost", "medoid", "best_cost")
-            self.last_ensemble = [{k: d[k] for k in keys} for d in self._batch.ensemble_kept()[0]]
+            self.last_ensemble = self._ensemble_rows([{k: d[k] for k in keys} for d in self._batch.ensemble_kept()[0]], groups)
+
+        def swap(**kw):  # (placement sits between the kept ensemble and the swap; the swap reads the placed table on the device)
+            if mode == "follow":
+                self._batch.band_place(frm=warm_from)
+            elif mode is not None:
+                self._batch.band_set(mode)
+            self._batch.set_images(**kw)
         if denoise not in (None, False) and raw_imgs is None and raw_device_ptrs is None:
             raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
         if raw_imgs is not None or raw_device_ptrs is not None:
@@ -659,31 +775,32 @@ class GP_Edge_Tracing_Batch(object):
             b = self._batch
             multi = self._kernel_of is not None
             n_img = self._n_frames if multi else b.n_img  # (frames expected)
+            frame_M = b.frame_M
             if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
                 raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
             have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
             if not (n_img == 1 and np.ndim(have) == 2) and len(have) != n_img:
-                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % (len(have), self._images_text(), b.M, b.N))
-            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (b.M, b.N), raw_imgs, raw_device_ptrs,
+                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % (len(have), self._images_text(), frame_M, b.N))
+            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (frame_M, b.N), raw_imgs, raw_device_ptrs,
                                        self._raw_dtype if raw_dtype is None else raw_dtype, kern,
                                        None if denoise is False else (self._denoise if denoise is None else denoise),
                                        kernel_of=self._kernel_of, image_of=self._edge_frames)
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
-            if len(src["batch"]["raw"]) != n_img or src["shape"] != (b.M, b.N):
+            if len(src["batch"]["raw"]) != n_img or src["shape"] != (frame_M, b.N):
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"
-                                 % (len(src["batch"]["raw"]), self._images_text(), b.M, b.N))
-            b.set_images(raw=src["batch"]["raw"], next_frame=next_frame)
+                                 % (len(src["batch"]["raw"]), self._images_text(), frame_M, b.N))
+            swap(raw=src["batch"]["raw"], next_frame=next_frame)
         elif grad_device_ptrs is not None:
             ptrs = _as_list(grad_device_ptrs)
             if len(ptrs) != self._batch.n_img:
                 raise ValueError("the new images do not fit the batch: %d given (%s)" % (len(ptrs), self._images_text()))
-            self._batch.set_images(device_ptrs=ptrs, next_frame=next_frame)
+            swap(device_ptrs=ptrs, next_frame=next_frame)
         else:
             imgs = list(grad_imgs) if isinstance(grad_imgs, (list, tuple)) else [grad_imgs]
-            if len(imgs) != self._batch.n_img or any(np.shape(g) != (self._batch.M, self._batch.N) for g in imgs):
+            if len(imgs) != self._batch.n_img or any(np.shape(g) != (self._batch.frame_M, self._batch.N) for g in imgs):
                 raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
-                                 % (len(imgs), self._images_text(), self._batch.M, self._batch.N))
-            self._batch.set_images([np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
+                                 % (len(imgs), self._images_text(), self._batch.frame_M, self._batch.N))
+            swap(grads=[np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
         if warm_from is not None:
             self._batch.warm_start_groups(warm_from, warm_every)
             obs = self._batch.read_obs_all()  # (what reset() sets again)
@@ -692,6 +809,11 @@ class GP_Edge_Tracing_Batch(object):
             obs = self._batch.read_obs_all()  # (what reset() sets again)
         else:
             obs = [np.array([])] * self.B if obs is None else list(obs)
+        if self.band_rows is not None:
+            self.band_r0 = self._batch.band_r0()
+            if warm_every is None:  # (a caller's observations are in full-frame rows; the device's own are band rows already)
+                obs = [np.asarray(o).reshape(-1, 2).astype(np.int64) - np.array([0, int(r0)], dtype=np.int64)
+                       for o, r0 in zip(obs, self.band_r0)]
         for e, p in enumerate(self._ps):
             p["obs"] = np.asarray(obs[e]).reshape(-1, 2).astype(np.int64)
             if seeds is not None:
@@ -740,20 +862,61 @@ class GP_Edge_Tracing_Batch(object):
             curve = np.concatenate([p["x_grid"][:, None], mean[:, None]], axis=1)
             et = np.rint(curve[:, [1, 0]]).astype(int)
             out.append((et, (mean - 1.96 * std, mean + 1.96 * std)) if self.return_std else et)
+        if self.band_rows is not None:  # (band rows -> full-frame rows: one addition of r0)
+            for e, r0 in enumerate(self.band_r0):
+                if self.return_std:
+                    et, (lo, hi) = out[e]
+                    out[e] = (et + np.array([int(r0), 0]), (lo + float(r0), hi + float(r0)))
+                else:
+                    out[e] = out[e] + np.array([int(r0), 0])
+        return out
+
+    def _ensemble_rows(self, groups, group_of):
+        """The row fields of an ensemble's dicts in full-frame rows: the members of a group share one band."""
+        if self.band_rows is None:
+            return groups
+        out = []
+        for g, d in enumerate(groups):
+            idx = np.flatnonzero(np.asarray(group_of) == g)
+            r0s = {int(self.band_r0[e]) for e in idx}
+            if len(r0s) > 1:
+                raise ValueError("group %d: its edges lie in different bands (r0 = %s); a group of an ensemble shares one band"
+                                 % (g, sorted(r0s)))
+            r0 = r0s.pop() if r0s else 0
+            d = _shift_rows(d, ("trace",), r0, col=0)
+            out.append(_shift_rows(d, ("median", "q_lo", "q_hi", "min", "max"), float(r0)))
         return out
 
     def history(self):
         """The iteration history of the current trace (constructor keyword ``history``), one dict per edge as
         ``_lib.decode_history`` returns it; valid after ``run_loop`` or ``__call__``.  ``reset()``, ``set_frame`` and new
         observations empty it.  GpetError (ERR_STATE) when the batch was built without ``history``."""
-        return self._batch.history()
+        hist = self._batch.history()
+        if self.band_rows is not None:
+            for e, d in enumerate(hist):
+                r0 = int(self.band_r0[e])
+                d["obs"] = [o + np.array([0, r0], dtype=np.int64) for o in d["obs"]]
+                if "optimal_curves" in d:
+                    d["optimal_curves"] = [c + np.array([0.0, float(r0)]) for c in d["optimal_curves"]]
+                if "mean" in d:
+                    d["mean"] = d["mean"] + float(r0)
+        return hist
 
     def results(self):
         """What ``finish`` returned for every edge, recomputed on the device from the converged fits it left there
         (gpet_batch_results: the same bits), plus the statistics of each trace: (per-edge results, dict(n_iter, n_obs,
         theta, nlml)).  Valid after ``__call__`` or ``finish``; before a converged fit of the current trace it raises
         GpetError."""
-        return results_from_records(self._batch.results(), self.return_std)
+        rec = self._batch.results()
+        if self.band_rows is not None:
+            rec = dict(rec)
+            r0 = np.asarray(self.band_r0, dtype=np.int64)
+            tr = np.array(rec["trace"], copy=True)
+            tr[:, :, 0] += r0[:, None]
+            rec["trace"] = tr
+            rec["lower"] = rec["lower"] + r0[:, None].astype(np.float64)
+            rec["upper"] = rec["upper"] + r0[:, None].astype(np.float64)
+        return results_from_records(rec, self.return_std)
 
     def final_costs(self):
         """(B,) f64: the scorer's cost of every edge's converged mean curve on its own gradient image -- the reference's
@@ -788,7 +951,7 @@ class GP_Edge_Tracing_Batch(object):
             raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
         groups, _, _ = self._batch.ensemble(g, tol)
         keys = ("trace", "median", "q_lo", "q_hi", "min", "max", "agree", "members", "off", "cost", "medoid", "best_cost")
-        return [{k: d[k] for k in keys} for d in groups]
+        return self._ensemble_rows([{k: d[k] for k in keys} for d in groups], g)
 
     def __call__(self, max_iter=1000):
         t0 = t.time()

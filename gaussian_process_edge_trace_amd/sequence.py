@@ -93,12 +93,17 @@ class SequenceTracer(object):
     not hand its trace on: ``warm_from='medoid'`` (default; a real trace), ``'best_cost'`` or ``'consensus'``.  The group is
     reduced and the warm start made on the device (``set_frame(..., warm_from=)``).  Every result is then the dict
     ``trace_ensemble`` returns for that frame and init -- the reduction's arrays (``ensemble_tol`` = its ``tol``) plus ``seeds``,
-    ``medoid_seed`` and ``result``, the medoid member's own result -- and ``iterations[t]`` holds the K counts."""
+    ``medoid_seed`` and ``result``, the medoid member's own result -- and ``iterations[t]`` holds the K counts.
+
+    ``band_rows=H``: tracking bands (``GP_Edge_Tracing_Batch``) -- every edge traces inside H rows of its frame.  The first frame of
+    every chain is placed from the init rows, every later one follows the trace its warm start comes from
+    (``set_frame(..., band='follow')``, on the device); with ``ensemble_seeds`` the K members of a group share the band placed from
+    the group's source.  Results are in full-frame rows; presets of ``kernel_options`` that depend on the image height see H."""
 
     _UNSET = object()
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
-                 denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', **kw):
+                 denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, **kw):
         if ensemble_seeds is not None:
             if seed is not SequenceTracer._UNSET or seeds is not None:
                 raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
@@ -150,12 +155,27 @@ class SequenceTracer(object):
         self.seeds = [int(seed)] * self.T if seeds is None else [int(v) for v in seeds]
         ctor = {k: v for k, v in self.kw.items() if k in ("kernel_options", "noise_y", "N_samples", "score_thresh", "delta_x",
                                                            "keep_ratio", "pixel_thresh", "return_std", "fix_endpoints")}
-        self._ps = [resolve_params(i, np.asarray(frames[0]).shape, **ctor) for i in self.inits]
+        self.band_rows = None if band_rows is None else int(band_rows)
+        shape = np.asarray(frames[0]).shape
+        self._frame_M = int(shape[0])
+        if self.band_rows is not None:
+            shape = (self.band_rows, shape[1])  # (the parameters are those of the (H, N) crop)
+        self._ps = [resolve_params(i, shape, **ctor) for i in self.inits]
         self._p = self._ps[0]
         self.warm_every = int(warm_every) if warm_every else 2 * self._p["delta_x"]
         self.device, self._ctx = device, _ctx
         self.iterations = [0] * self.T
         self._tracer = None
+
+    def _place(self, p, trace):
+        """The first row of an edge's band from ``trace`` ((Lg, 2) yx, full-frame rows; None: from the init rows), ``_lib.band_place``."""
+        rows = p["init"][:, 1]
+        i_lo, i_hi = int(rows.min()), int(rows.max())
+        t = rows if trace is None else np.asarray(trace)[:, 0]
+        t = t[(t >= 0) & (t <= self._frame_M - 1)]
+        if t.size == 0:
+            t = rows
+        return _lib.band_place(self._frame_M, self.band_rows, int(t.min()), int(t.max()), i_lo, i_hi)
 
     def _frames_of_step(self, s):
         return [lo + s for lo, hi in self.chains if lo + s < hi]
@@ -237,11 +257,19 @@ class SequenceTracer(object):
                 if pending is not None:
                     self._close_step(pending, self._tracer.ensemble(pending[3], self.ensemble_tol) if ens else None, results, prev)
                     pending = None
-                obs = []
+                obs, r0s = [], []
                 for c, f in active:
                     for k, p in enumerate(self._ps):
-                        o = (np.zeros((0, 2), dtype=np.int64) if s == 0 or prev[c, k] is None else
-                             warm_start_obs(prev[c, k], p["x_st"], p["x_en"], self.warm_every, p["algo_thresh"], p["M"]))
+                        cold = s == 0 or prev[c, k] is None
+                        if self.band_rows is not None:  # (placed from the trace the warm start comes from, else from the inits)
+                            r0 = self._place(p, None if cold else prev[c, k])
+                            r0s.extend([r0] * K)
+                            shift = np.array([r0, 0])
+                        o = (np.zeros((0, 2), dtype=np.int64) if cold else
+                             warm_start_obs(prev[c, k] if self.band_rows is None else prev[c, k] - shift, p["x_st"], p["x_en"],
+                                            self.warm_every, p["algo_thresh"], p["M"]))
+                        if self.band_rows is not None:
+                            o = o + shift[[1, 0]]  # (the constructor takes observations in full-frame rows)
                         obs.extend([o] * K)
                 if self._tracer is not None:
                     self._tracer._batch.close()
@@ -250,6 +278,8 @@ class SequenceTracer(object):
                                                                                      denoise=self.denoise)
                 if tab["kernel_of"] is not None:
                     images["kernel_of"] = tab["kernel_of"]
+                if self.band_rows is not None:
+                    images.update(band_rows=self.band_rows, band_r0=r0s)
                 self._tracer = GP_Edge_Tracing_Batch(tab["inits"], seeds=seeds, obs=obs, device=self.device, _ctx=self._ctx,
                                                      image_of=tab["image_of"], **images, **self.kw)
                 if self._ctx is None:

@@ -679,6 +679,56 @@ int gpet_batch_ensemble_kept(gpet_batch* b, int64_t len_cap, void* dst, int dst_
 int gpet_batch_warm_start_groups(gpet_batch* b, int from, int warm_every, int32_t* n_obs_out, int32_t* src_out);
 int gpet_batch_warm_start_from(gpet_batch* b, const int32_t* src_of, int warm_every, int32_t* n_obs_out);
 
+/* ---- tracking bands: every edge traces inside a row band that follows it (the rules: csrc/gpet_band_plan.h) ----
+ * A band is (r0, H): rows r0 .. r0 + H - 1 of an M x N frame; H is the batch's, r0 per edge.  Edge e of a banded batch gives, bit for
+ * bit, what an unbanded batch gives on rows r0 .. r0 + H - 1 of the FULL-FRAME gradient image G (re-normalised over the band, as an
+ * unbanded batch re-normalises the image it is given) with init rows lowered by r0.  The batch's image shape is (H, N): every record
+ * it returns (results, history, ensembles, observation sets, gpet_batch_read) is in band rows; the caller adds r0.
+ *   gpet_batch_create_banded(ctx, B, M, N, band, images, params, init_xy, out)   init_xy in full-frame rows.  band->H; band->r0 [B] or
+ *       NULL (every edge placed from its own init rows by band_place); band->n_pair full-frame gradient images, edge e reads image
+ *       band->pair_of[e] (every index must occur).  images: the n_pair images as f32 gradient images (grad; GPET_GRAD_ON_DEVICE in
+ *       flags) -- taken as they are, G = grad -- or raw frames with a slot table as gpet_batch_create_raw_multi takes it (n_frames
+ *       frames, image p = comp_grad_img(frame frame_of[p], kern[kernel_of[p]]) after dn; GPET_RAW_ON_DEVICE), made once per pair into
+ *       memory the batch owns.  Refused with GPET_ERR_BAD_ARG and band_check's reason: H > M, r0 outside [0, M - H], init rows that
+ *       span more than H rows, an init outside its band.
+ *   gpet_batch_set_images and the gpet_batch_set_raw_images* calls take n_pair images on a banded batch (gpet_batch_image_count
+ *       returns n_pair), and move every slot to the band placed or set since the last swap -- r0 is read on the device.
+ *   gpet_batch_band_place(batch, src_of, from)   BEFORE the swap (after gpet_batch_ensemble_keep): r0 of every edge for the next
+ *       frame by band_place from the trace of its source in full-frame rows -- src_of[e] as gpet_batch_warm_start_from takes it (-1:
+ *       the band stays); src_of == NULL and from < 0: the edge itself; src_of == NULL and from = GPET_WARM_*: the source of its group
+ *       in the kept ensemble, as gpet_batch_warm_start_groups picks it.  One wave per edge, no host wait.  A source without a usable
+ *       row, or an edge that is its own source and was stopped with an error, keeps its band.
+ *   gpet_batch_band_set(batch, r0)   the explicit table instead; refused (nothing touched) by band_check, naming the edge.
+ *   gpet_batch_band_r0(batch, r0_out)   reads the table back: the bands the slots are at (after a swap: the placed ones).
+ *   gpet_batch_warm_start, _groups and _from on a banded batch carry every row from the source's band of the last converged fits
+ *       into the destination's new band: y = rint(mean_src[k]) + r0_src_old - r0_dst_new, kept when 0 <= y <= H - 1. */
+typedef struct gpet_band {
+  int32_t H;             /* rows of every band */
+  int32_t n_pair;        /* full-frame gradient images */
+  const int64_t* r0;     /* [B], or NULL: placed from the init rows */
+  const int32_t* pair_of; /* [B] */
+} gpet_band;
+typedef struct gpet_band_images {
+  const float* const* grad; /* [n_pair] f32 gradient images, or NULL and: */
+  const void* const* raw;   /* [n_frames] raw frames of pixel type pix */
+  int32_t pix;
+  int32_t n_frames;
+  int32_t n_kern;
+  int32_t reserved;
+  const double* const* kern; /* [n_kern] kernels of kh[k] x kw[k] */
+  const int32_t* kh;
+  const int32_t* kw;
+  const int32_t* frame_of;   /* [n_pair] */
+  const int32_t* kernel_of;  /* [n_pair] */
+  const gpet_denoise* dn;    /* may be NULL */
+  unsigned int flags;
+} gpet_band_images;
+int gpet_batch_create_banded(gpet_ctx* c, int B, int M, int N, const gpet_band* band, const gpet_band_images* images,
+                             const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out);
+int gpet_batch_band_place(gpet_batch* b, const int32_t* src_of, int from);
+int gpet_batch_band_set(gpet_batch* b, const int64_t* r0);
+int gpet_batch_band_r0(gpet_batch* b, int64_t* r0_out);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
