@@ -634,6 +634,22 @@ def band_refusal(M, H, r0, i_lo, i_hi):
     return None
 
 
+INIT_WINDOW_MAX, INIT_COLS_MAX = 4096, 64
+
+
+def init_follow_refusal(window, cols):
+    """Why (window, cols) cannot be followed with (init_follow_check of csrc/gpet_init_plan.h, same order, same words), or None."""
+    if window < 0:
+        return "init_follow: window must be at least 0 rows"
+    if window > INIT_WINDOW_MAX:
+        return "init_follow: window exceeds 4096 rows"
+    if cols < 0:
+        return "init_follow: cols must be at least 0 columns"
+    if cols > INIT_COLS_MAX:
+        return "init_follow: cols exceeds 64 columns"
+    return None
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -760,6 +776,9 @@ SYMBOLS = {
     "gpet_batch_band_place": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
     "gpet_batch_band_set": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "gpet_batch_band_r0": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "gpet_batch_init_follow": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "gpet_batch_set_init": (C.c_int, [_P, C.POINTER(_P)]),
+    "gpet_batch_init_xy": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1230,6 +1249,7 @@ class Batch:
         self.image_of = image_of
         self._keep = (grads, inits)
         self._x_st = [int(p.x_st) for p in params]
+        self._n_init = [int(p.n_init) for p in params]
 
     def set_images(self, grads=None, device_ptrs=None, next_frame=False, raw=None):
         """New gradient image(s) for the same edges, gradient KDE recomputed, loop state reset (gpet_batch_set_images).
@@ -1514,6 +1534,38 @@ class Batch:
         out = np.zeros(self.B, dtype=np.int64)
         self.ctx.check(self.lib.gpet_batch_band_r0(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
+
+    def _init_table(self, flat):
+        return [flat[e, :n].copy() for e, n in enumerate(self._n_init)]
+
+    def init_follow(self, window, cols):
+        """gpet_batch_init_follow: every init point of every edge moves onto the edge of the image its edge reads now, by the rule of
+        csrc/gpet_init_plan.h (rows within ``window`` of the point, scored over ``cols`` columns on either side; x stays), on the device.
+        Legal before the first iteration after creation, ``reset`` or ``set_images`` (GpetError ERR_STATE otherwise, nothing touched).
+        Returns the moved points, a list of (n_init, 2) int64 xy arrays in full-frame rows, after one wait."""
+        out = np.zeros((self.B, max(self._n_init), 2), dtype=np.int64)
+        self.ctx.check(self.lib.gpet_batch_init_follow(self.h, int(window), int(cols), out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return self._init_table(out)
+
+    def set_init(self, inits):
+        """gpet_batch_set_init: the caller's init points, one (n_init, 2) xy array per edge in full-frame rows, sorted by x as the batch
+        holds them.  The counts and the x of every point must be the batch's, the rows inside the frame and, on a banded batch, inside
+        the edge's current band: GpetError ERR_BAD_ARG naming the cause otherwise, ERR_STATE after the first iteration; nothing is
+        touched by a refused call."""
+        inits = [np.ascontiguousarray(np.asarray(i).reshape(-1, 2), dtype=np.int64) for i in inits]
+        if len(inits) != self.B:
+            raise GpetError(ERR_BAD_ARG, "set_init: %d init arrays for %d edges" % (len(inits), self.B))
+        for e, (i, n) in enumerate(zip(inits, self._n_init)):
+            if i.shape[0] != n:
+                raise GpetError(ERR_BAD_ARG, "set_init: edge %d has %d init points, the batch was created with %d" % (e, i.shape[0], n))
+        ip = (_P * self.B)(*[i.ctypes.data for i in inits])
+        self.ctx.check(self.lib.gpet_batch_set_init(self.h, ip))
+
+    def init_xy(self):
+        """gpet_batch_init_xy: the current init points, a list of (n_init, 2) int64 xy arrays in full-frame rows."""
+        out = np.zeros((self.B, max(self._n_init), 2), dtype=np.int64)
+        self.ctx.check(self.lib.gpet_batch_init_xy(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return self._init_table(out)
 
     def set_history(self, level, iter_cap=64):
         """Iteration history of the traces this batch runs (gpet_batch_set_history): ``level`` None / 'obs' / 'curves' / 'full'

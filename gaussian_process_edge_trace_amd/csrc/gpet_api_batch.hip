@@ -406,7 +406,9 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   }
   if (rc) return rc;
   // (one copy each for the init points and the initial scalars of all edges: 3 x B small copies were most of the constructor)
-  std::vector<long long> h_init((size_t)B * 2 * (size_t)bb.n_init_max, 0);
+  b->n_init_max = bb.n_init_max;
+  std::vector<long long>& h_init = b->h_init;
+  h_init.assign((size_t)B * 2 * (size_t)bb.n_init_max, 0);
   for (int e = 0; e < B; ++e)
     memcpy(&h_init[(size_t)e * 2 * (size_t)bb.n_init_max], init_xy[e], sizeof(long long) * 2 * (size_t)b->h_edges[e].n_init);
   HIPCHK(c, hipMemcpyAsync(b->d_init, h_init.data(), sizeof(long long) * h_init.size(), hipMemcpyHostToDevice, c->stream));
@@ -530,6 +532,8 @@ int gpet_batch_band_set(gpet_batch* b, const int64_t* r0) {
   BandState& bs = b->band;
   if (!bs.H) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_band_set: the batch has no bands (gpet_batch_create_banded makes one that has)");
   const BandTables t = band_tables(b->B, bs.n_init_max);
+  const int rc_t = band_refresh_host(b);  // (the init points may have moved on the device since the host copy was made)
+  if (rc_t) return rc_t;
   for (int e = 0; e < b->B; ++e) {
     const long long i_lo = bs.h_tab[t.off_lohi + 2 * (size_t)e], i_hi = bs.h_tab[t.off_lohi + 2 * (size_t)e + 1];
     if (const char* why = band_check(bs.M, bs.H, r0[e], i_lo, i_hi))

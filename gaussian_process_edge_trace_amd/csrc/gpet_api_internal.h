@@ -26,6 +26,8 @@
 //   gpet_api_ensemble.hip seed ensembles: gpet_batch_final_costs, gpet_ensemble_bytes, gpet_batch_ensemble
 //   gpet_ensemble_plan.h the layout of an ensemble's buffer, the validation of its arguments, member tables and tile width (no HIP)
 //                        and, for sequences, gpet_batch_ensemble_keep / _kept, gpet_batch_warm_start_groups / _from
+//   gpet_api_init.hip    endpoint tracking: gpet_batch_init_follow, gpet_batch_set_init, gpet_batch_init_xy
+//   gpet_init_plan.h     the rule that moves an init point, its refusals (no HIP)
 //   gpet_warm_plan.h     the source of every edge's warm start (medoid, best cost, consensus, another edge, none), the refusals, the
 //                        kept ensemble's size (no HIP)
 #pragma once
@@ -74,6 +76,7 @@ struct BandState {
   std::vector<long long> h_tab;      // the host copy the tables were uploaded from: (i_lo, i_hi) and the full-frame inits stay valid
   std::vector<long long> h_r0;       // staging of gpet_batch_band_set (kept alive for the asynchronous copy)
   bool pending = false;              // r0_pend holds bands the slots have not moved to yet (gpet_batch_band_place / _set)
+  bool moved = false;                // gpet_batch_init_follow has rewritten (i_lo, i_hi) and the inits on the device since h_tab was current
 };
 
 struct gpet_batch {
@@ -95,6 +98,9 @@ struct gpet_batch {
   double* d_fin_par = nullptr;         // [B][12] contiguous hyper-parameters / transforms of the converged fits
   long long* d_obs = nullptr;          // [B][obs_cap_max][2] contiguous observations: one copy reads them all
   long long* d_init = nullptr;         // [B][n_init_max][2] contiguous init points: one copy writes them all
+  int n_init_max = 0;
+  std::vector<long long> h_init;       // what d_init was last written from on the host: the x stay valid (no call moves them), the rows
+                                       // are stale after gpet_batch_init_follow; also the staging of gpet_batch_set_init
   std::vector<gpet_scalars> h_scalars;
   std::vector<int> h_nobs_prev;        // observations per edge at the last group boundary of the loop: batches up to 64 edges size
                                        // the next group by their growth (next_group, gpet_loop_plan.h)
@@ -251,6 +257,10 @@ int history_clear(gpet_batch* b, int e);
 // ---- gpet_api_ensemble.hip ------------------------------------------------------------------------------------------------
 // frees the scratch of the ensemble entry points (gpet_batch_destroy)
 void ensemble_free(gpet_batch* b);
+// ---- gpet_api_init.hip ----------------------------------------------------------------------------------------------------
+// the host copy of a banded batch's (i_lo, i_hi) and full-frame init tables made current again after gpet_batch_init_follow (one wait;
+// nothing to do when they are)
+int band_refresh_host(gpet_batch* b);
 // ---- gpet_api_batch.hip ---------------------------------------------------------------------------------------------------
 int fetch_all_scalars(gpet_batch* b);
 // the end of every warm start, after its kernel: histories, flags, the one copy of the scalars and the one wait; n_obs_out may be nullptr

@@ -10,6 +10,7 @@
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 #include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
+#include "gpet_init_plan.h"  // endpoint tracking: the rule that moves the init points, its refusals
 #include "gpet_warm_plan.h"  // warm start from a group's medoid / best cost / consensus or from another edge: source per edge, refusals
 
 namespace gpet {
@@ -121,6 +122,10 @@ hipError_t launch_band_images(hipStream_t st, const EdgeDev* d_edges, int B, con
 hipError_t launch_warm_start_band(hipStream_t st, EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,
                                   long long record_bytes, long long off_trace, int warm_every, const long long* d_r0_fit,
                                   const long long* d_r0_cur);
+// endpoint tracking (gpet_k_init.inc; the rule: gpet_init_plan.h): every init row of every edge onto the edge of EdgeDev::grad.  A banded
+// batch passes its tables (r0 of the slots, the full-frame init points, (i_lo, i_hi)), which are then written too; else three nullptr
+hipError_t launch_init_follow(hipStream_t st, const EdgeDev* d_edges, int B, int window, int cols, int n_init_max, const long long* d_r0_cur,
+                              long long* d_init_full, long long* d_lohi);
 // the record of the iteration just completed for every edge whose counter equals iter_expect (0: every edge with a counter >= 1), gpet_k_history.inc
 hipError_t launch_history(hipStream_t st, const EdgeDev* d_edges, int B, const gpet_history_plan& P, int iter_expect);
 hipError_t launch_pixels_reset(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

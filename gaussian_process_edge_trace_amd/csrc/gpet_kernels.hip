@@ -32,5 +32,6 @@ namespace gpet {
 #include "gpet_k_launch.inc"
 #include "gpet_k_ensemble.inc"
 #include "gpet_k_band.inc"
+#include "gpet_k_init.inc"
 
 }  // namespace gpet

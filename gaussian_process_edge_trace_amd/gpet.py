@@ -533,6 +533,76 @@ def resolve_frame_band(band_rows, band, warm_every, n_edges):
     return r0
 
 
+def resolve_init_follow(init_follow):
+    """``init_follow`` as the constructor, ``set_frame`` and ``SequenceTracer`` accept it, decided without a device: None, or
+    ``dict(window=w, cols=a)`` -> (w, a), integers within the limits of csrc/gpet_init_plan.h (``_lib.init_follow_refusal``).
+    ValueError naming the cause otherwise."""
+    if init_follow is None:
+        return None
+    if not isinstance(init_follow, dict) or set(init_follow) != {"window", "cols"}:
+        raise ValueError("init_follow must be None or dict(window=w, cols=a), not %r" % (init_follow,))
+    w, a = init_follow["window"], init_follow["cols"]
+    for name, v in (("window", w), ("cols", a)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("init_follow: %s must be an integer, not %r" % (name, v))
+    why = _lib.init_follow_refusal(int(w), int(a))
+    if why is not None:
+        raise ValueError("%s (window = %d, cols = %d)" % (why, w, a))
+    return int(w), int(a)
+
+
+def resolve_frame_init(init, init_follow, default_follow, cur_inits, frame_M, band_rows=None, band=None):
+    """What ``set_frame(init=..., init_follow=...)`` does with the init points, decided without a device: ('keep', None), ('follow',
+    (window, cols)) or ('set', list of (n_init, 2) int64 xy arrays sorted by x).  ``default_follow``: the constructor's setting as
+    ``resolve_init_follow`` returned it; ``cur_inits``: the batch's current table; ``band``: what ``resolve_frame_band`` decided.
+    ``init=None`` means 'follow' when the constructor or this call has ``init_follow``, else 'keep'.  ValueError for an unknown word,
+    'follow' without a window, ``init_follow`` next to 'keep' or a list, a list that differs from the batch in the number of edges, of
+    points or in an x, a row outside the frame and, on a banded batch, a list without an explicit ``band=[r0_e]`` or outside it
+    (``_lib.band_refusal``'s words)."""
+    call = resolve_init_follow(init_follow)
+    follow = call if call is not None else default_follow
+    if init is None:
+        return ("follow", follow) if follow is not None else ("keep", None)
+    if isinstance(init, str):
+        if init == "keep":
+            if call is not None:
+                raise ValueError("init='keep' and init_follow are alternatives: the window is what 'follow' searches")
+            return "keep", None
+        if init == "follow":
+            if follow is None:
+                raise ValueError("init='follow' needs init_follow=dict(window=w, cols=a), here or in the constructor")
+            return "follow", follow
+        raise ValueError("init must be None, 'keep', 'follow' or one array of init points per edge, not %r" % (init,))
+    if call is not None:
+        raise ValueError("init points given as arrays and init_follow are alternatives: nothing is searched for")
+    given = list(init)
+    if len(given) != len(cur_inits):
+        raise ValueError("init has %d entries for %d edges" % (len(given), len(cur_inits)))
+    if band_rows is not None and not isinstance(band, list):
+        raise ValueError("init points given as arrays on a batch with tracking bands need the bands too: band=[r0 of every edge]")
+    out = []
+    for e, (new, cur) in enumerate(zip(given, cur_inits)):
+        a = np.asarray(new)
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] != len(cur):
+            raise ValueError("init of edge %d has shape %s, the batch holds %d init points (n, 2)" % (e, a.shape, len(cur)))
+        if not np.array_equal(a, np.rint(a)):
+            raise ValueError("init of edge %d is not integral" % e)
+        a = a[np.argsort(a[:, 0])].astype(np.int64)
+        if not np.array_equal(a[:, 0], np.asarray(cur)[:, 0]):
+            raise ValueError("init of edge %d has x = %s, the batch was built with x = %s: the x of an init point cannot change"
+                             % (e, a[:, 0].tolist(), np.asarray(cur)[:, 0].tolist()))
+        i_lo, i_hi = init_row_span(a)
+        if i_lo < 0 or i_hi > frame_M - 1:
+            raise ValueError("init of edge %d: an init point lies outside the frame (init rows %d .. %d, M = %d)" % (e, i_lo, i_hi, frame_M))
+        if band_rows is not None:
+            why = _lib.band_refusal(frame_M, band_rows, band[e], i_lo, i_hi)
+            if why is not None:
+                raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %d, new init rows %d .. %d)"
+                                 % (e, why, frame_M, band_rows, band[e], i_lo, i_hi))
+        out.append(a)
+    return "set", out
+
+
 def _shift_rows(d, keys, r0, col=None):
     """``d`` with ``r0`` added to the row-valued entries ``keys`` (column ``col`` of 2-D ones)."""
     out = dict(d)
@@ -564,7 +634,8 @@ class GP_Edge_Tracing_Batch(object):
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
-                 denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None, band_rows=None, band_r0=None):
+                 denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None, band_rows=None, band_r0=None,
+                 init_follow=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -601,8 +672,15 @@ class GP_Edge_Tracing_Batch(object):
         gradient image only: bit for bit what a batch without bands gives for the cropped gradient image ``G[r0:r0 + H]`` and the
         init ``init - (0, r0)``, with every row it returns (traces, intervals, ``history``, ``ensemble``, ``results``) raised by
         ``r0`` again.  ``inits`` and ``obs`` are in full-frame rows; presets of ``kernel_options`` that depend on the image height
-        see H.  ``band_r0`` (attribute) holds the current table; ``set_frame(band=...)`` moves the bands."""
+        see H.  ``band_r0`` (attribute) holds the current table; ``set_frame(band=...)`` moves the bands.
+        ``init_follow=dict(window=w, cols=a)``: endpoint tracking -- once the images are made, every init point (x, y) of every edge
+        moves, on the device, to the row within ``w`` rows of y whose gradient summed over the columns ``x - a .. x + a`` is largest
+        (the rule: csrc/gpet_init_plan.h; ties to the nearest, then the upper row; nothing positive in reach: the point stays; x
+        never moves), so rough clicks land on the edge.  On a banded batch the search stays inside the band.  The setting is
+        remembered: ``set_frame`` then follows by default.  ``inits`` (attribute) is the current table, a list of (n_init, 2) int64
+        xy arrays in full-frame rows; ``reset()`` keeps it."""
         B = len(inits)
+        self._init_follow = resolve_init_follow(init_follow)
         if image_of is not None:
             image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
             if len(image_of) != B:
@@ -672,6 +750,10 @@ class GP_Edge_Tracing_Batch(object):
             self._init_span = [init_row_span(p["init"]) for p in self._ps]
             for p, r0 in zip(self._ps, self.band_r0):
                 p["obs"] = p["obs"] - np.array([0, int(r0)], dtype=np.int64)
+        if self._init_follow is not None:  # (the given points refined on the images just made)
+            self._take_inits(self._batch.init_follow(*self._init_follow))
+        else:
+            self.inits = [np.array(p["init"], dtype=np.int64) for p in self._ps]
         if sample_dtype is not None:
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
@@ -684,6 +766,14 @@ class GP_Edge_Tracing_Batch(object):
         self.seeds = [int(s) for s in seeds]
         self.timings = {}
         self.last_ensemble = None  # (set_frame(warm_from=...): the ensemble of the frame it left)
+
+    def _take_inits(self, table):
+        """The current init points as the library holds them now: ``inits``, every edge's parameters and the span the bands respect."""
+        self.inits = [np.array(i, dtype=np.int64) for i in table]
+        for p, i in zip(self._ps, self.inits):
+            p["init"] = i.astype(p["init"].dtype)
+        if self.band_rows is not None:
+            self._init_span = [init_row_span(i) for i in self.inits]
 
     def _set_obs(self):
         for e, p in enumerate(self._ps):
@@ -706,7 +796,7 @@ class GP_Edge_Tracing_Batch(object):
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
                   raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None, warm_from=None,
-                  group_of=None, tol=2, band=None):
+                  group_of=None, tol=2, band=None, init=None, init_follow=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -735,7 +825,14 @@ class GP_Edge_Tracing_Batch(object):
         the images are swapped, so a group's members share one band -- or one first row per edge; the default is ``'follow'`` with
         ``warm_every`` and "the bands stay" without.  The warm start then carries every row from the source's old band into the
         edge's new one.  A band that cannot hold its edge's init points raises ValueError and leaves the batch as it was.  ``obs``
-        are in full-frame rows."""
+        are in full-frame rows.
+        ``init``: ``'follow'`` -- after the images are swapped and before the warm start, every init point moves onto the edge of
+        the new image by the rule of the constructor's ``init_follow`` (or of ``init_follow=dict(window=w, cols=a)`` given here), on
+        the device, starting from where it is now; ``'keep'`` -- the points stay; or one (n_init, 2) xy array per edge in full-frame
+        rows, with the x and counts the batch has (on a banded batch only together with an explicit ``band=[r0_e]`` that holds them
+        as well as the current points).  Default: ``'follow'`` when the constructor or this call has ``init_follow``, else
+        ``'keep'``.  Bands are placed against the points as they are BEFORE this call; the search then stays inside the band.
+        Whatever is refused raises ValueError before anything is touched."""
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
         if warm_from is not None:
@@ -754,6 +851,7 @@ class GP_Edge_Tracing_Batch(object):
                 if why is not None:
                     raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %d, init rows %d .. %d)"
                                      % ((e, why, self._batch.frame_M, self.band_rows, r0) + self._init_span[e]))
+        imode, ipoints = resolve_frame_init(init, init_follow, self._init_follow, self.inits, self._batch.frame_M, self.band_rows, mode)
         if warm_every is not None or mode == "follow":
             self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
         if warm_from is not None:
@@ -801,6 +899,12 @@ class GP_Edge_Tracing_Batch(object):
                 raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
                                  % (len(imgs), self._images_text(), self._batch.frame_M, self._batch.N))
             swap(grads=[np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
+        # (the init points move between the swap and the warm start, which keeps columns strictly inside the end points only)
+        if imode == "follow":
+            self._take_inits(self._batch.init_follow(*ipoints))
+        elif imode == "set":
+            self._batch.set_init(ipoints)
+            self._take_inits(ipoints)
         if warm_from is not None:
             self._batch.warm_start_groups(warm_from, warm_every)
             obs = self._batch.read_obs_all()  # (what reset() sets again)

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import split_kernels
-from .gpet import GP_Edge_Tracing_Batch, resolve_params
+from .gpet import GP_Edge_Tracing_Batch, resolve_init_follow, resolve_params
 
 
 def chain_slices(n_frames, n_chains):
@@ -98,12 +98,19 @@ class SequenceTracer(object):
     ``band_rows=H``: tracking bands (``GP_Edge_Tracing_Batch``) -- every edge traces inside H rows of its frame.  The first frame of
     every chain is placed from the init rows, every later one follows the trace its warm start comes from
     (``set_frame(..., band='follow')``, on the device); with ``ensemble_seeds`` the K members of a group share the band placed from
-    the group's source.  Results are in full-frame rows; presets of ``kernel_options`` that depend on the image height see H."""
+    the group's source.  Results are in full-frame rows; presets of ``kernel_options`` that depend on the image height see H.
+
+    ``init_follow=dict(window=w, cols=a)``: endpoint tracking (``GP_Edge_Tracing_Batch``) -- on every frame the init points move onto
+    the edge of that frame, on the device, starting from where the frame before it in its chain left them (a chain's first frame:
+    from ``init``).  ``inits[t]`` holds the points frame t was traced with -- one (n_init, 2) int64 xy array in the order of ``init``,
+    or a list of E of them -- without ``init_follow`` the given ones.  The K members of an ensemble share init and image, hence the
+    result; with ``band_rows`` the bands are placed as ever, against the points of the frame before, and the search stays inside."""
 
     _UNSET = object()
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
-                 denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, **kw):
+                 denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, init_follow=None,
+                 **kw):
         if ensemble_seeds is not None:
             if seed is not SequenceTracer._UNSET or seeds is not None:
                 raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
@@ -121,11 +128,15 @@ class SequenceTracer(object):
         self.K = 1 if ensemble_seeds is None else len(ensemble_seeds)
         self.frames = frames
         self.T = len(frames)
-        self.inits, self.multi = _inits_of(init)
-        if not self.inits:
+        self._inits, self.multi = _inits_of(init)
+        if not self._inits:
             raise ValueError("no init")
-        self.E = len(self.inits)
-        self.init = self.inits[0] if not self.multi else self.inits
+        self.E = len(self._inits)
+        self.init = self._inits[0] if not self.multi else self._inits
+        resolve_init_follow(init_follow)  # (refused here, before a frame is looked at)
+        self.init_follow = init_follow
+        self.inits = [None] * self.T  # the init points every frame was traced with
+        self._cur = {}  # (chain, edge of the frame) -> the init points the chain's last frame left, in the order of `init`
         self.kw = dict(kw)
         self.kw.pop("obs", None)
         self.grad_kernel = grad_kernel
@@ -160,16 +171,34 @@ class SequenceTracer(object):
         self._frame_M = int(shape[0])
         if self.band_rows is not None:
             shape = (self.band_rows, shape[1])  # (the parameters are those of the (H, N) crop)
-        self._ps = [resolve_params(i, shape, **ctor) for i in self.inits]
+        self._ps = [resolve_params(i, shape, **ctor) for i in self._inits]
         self._p = self._ps[0]
         self.warm_every = int(warm_every) if warm_every else 2 * self._p["delta_x"]
         self.device, self._ctx = device, _ctx
         self.iterations = [0] * self.T
         self._tracer = None
 
-    def _place(self, p, trace):
-        """The first row of an edge's band from ``trace`` ((Lg, 2) yx, full-frame rows; None: from the init rows), ``_lib.band_place``."""
-        rows = p["init"][:, 1]
+    def _init_of(self, c, k):
+        """The init points the next frame of chain ``c`` starts from for edge ``k``: where the chain's last frame left them, else the given ones."""
+        return self._cur.get((c, k), self._inits[k])
+
+    def _file_inits(self, active):
+        """The step's init points as its batch holds them, filed per frame and carried per (chain, edge) in the order of ``init``."""
+        table = self._tracer.inits
+        for ci, (c, f) in enumerate(active):
+            got = []
+            for k in range(self.E):
+                mine = np.array(self._inits[k], dtype=np.int64)
+                mine[np.argsort(np.asarray(self._inits[k])[:, 0]), 1] = table[(ci * self.E + k) * self.K][:, 1]  # (the batch sorts by x, as resolve_params does)
+                if self.init_follow is not None:
+                    self._cur[c, k] = mine
+                got.append(mine)
+            self.inits[f] = got if self.multi else got[0]
+
+    def _place(self, p, trace, init=None):
+        """The first row of an edge's band from ``trace`` ((Lg, 2) yx, full-frame rows; None: from the init rows), ``_lib.band_place``;
+        ``init``: the edge's current init points (default: the given ones)."""
+        rows = p["init"][:, 1] if init is None else np.asarray(init)[:, 1]
         i_lo, i_hi = int(rows.min()), int(rows.max())
         t = rows if trace is None else np.asarray(trace)[:, 0]
         t = t[(t >= 0) & (t <= self._frame_M - 1)]
@@ -199,7 +228,7 @@ class SequenceTracer(object):
         # (chain-major, like the inits: C frames, C x distinct kernels image slots)
         kernel_of = None if self.kernel_of is None else [k for _ in active for k in self.kernel_of for _ in range(K)]
         group_of = np.repeat(np.arange(len(active) * E, dtype=np.int32), K) if ens else None
-        return dict(inits=[i for _ in active for i in self.inits for _ in range(K)], seeds=seeds, image_of=image_of,
+        return dict(inits=[self._init_of(c, k) for c, _ in active for k in range(E) for _ in range(K)], seeds=seeds, image_of=image_of,
                     kernel_of=kernel_of, group_of=group_of)
 
     def _source_trace(self, d, res):
@@ -262,7 +291,7 @@ class SequenceTracer(object):
                     for k, p in enumerate(self._ps):
                         cold = s == 0 or prev[c, k] is None
                         if self.band_rows is not None:  # (placed from the trace the warm start comes from, else from the inits)
-                            r0 = self._place(p, None if cold else prev[c, k])
+                            r0 = self._place(p, None if cold else prev[c, k], self._init_of(c, k))
                             r0s.extend([r0] * K)
                             shift = np.array([r0, 0])
                         o = (np.zeros((0, 2), dtype=np.int64) if cold else
@@ -280,6 +309,8 @@ class SequenceTracer(object):
                     images["kernel_of"] = tab["kernel_of"]
                 if self.band_rows is not None:
                     images.update(band_rows=self.band_rows, band_r0=r0s)
+                if self.init_follow is not None:  # (remembered by the batch: its set_frame then follows by default)
+                    images["init_follow"] = self.init_follow
                 self._tracer = GP_Edge_Tracing_Batch(tab["inits"], seeds=seeds, obs=obs, device=self.device, _ctx=self._ctx,
                                                      image_of=tab["image_of"], **images, **self.kw)
                 if self._ctx is None:
@@ -295,6 +326,7 @@ class SequenceTracer(object):
                 if ens:
                     self._close_step(pending, self._tracer.last_ensemble, results, prev)
                     pending = None
+            self._file_inits(active)
             out = self._tracer(max_iter)
             pending = (active, out, list(self._tracer.timings["iters"]), tab["group_of"])
             if not ens:

@@ -729,6 +729,28 @@ int gpet_batch_band_place(gpet_batch* b, const int32_t* src_of, int from);
 int gpet_batch_band_set(gpet_batch* b, const int64_t* r0);
 int gpet_batch_band_r0(gpet_batch* b, int64_t* r0_out);
 
+/* ---- endpoint tracking: the init points follow the edge from frame to frame (the rule: csrc/gpet_init_plan.h) ----
+ * The rule, for the init point (x, y) of an edge that reads the M x N image G (the H x N slot of a banded batch, rows in band
+ * coordinates): among the rows r in [max(0, y - window), min(M - 1, y + window)] whose score s(r) = sum of (double)G[r][c] over
+ * c = max(0, x - cols) .. min(N - 1, x + cols) is > 0, the one of largest s -- ties: the smallest |r - y|, then the smallest r -- becomes
+ * y; none: y stays.  x never changes; every init point of every edge is moved.  0 <= window <= 4096, 0 <= cols <= 64.
+ *   gpet_batch_init_follow(batch, window, cols, init_out)   applies the rule to every edge on the images the batch holds now (one wave per
+ *       edge, no host wait).  init_out (host, [B][n_init_max][2] xy in full-frame rows, n_init_max the largest n_init of the batch, unused
+ *       entries 0; may be NULL): filled after one wait.  On a banded batch the band tables follow (the full-frame init points and the
+ *       (i_lo, i_hi) span gpet_batch_band_place clamps against).
+ *   gpet_batch_set_init(batch, init_xy)   the caller's init points instead: init_xy[e] holds the batch's n_init points of edge e, xy in
+ *       full-frame rows, with the x the batch was created with; rows in [0, M - 1] of the frame and, on a banded batch, inside the edge's
+ *       current band.  Anything else: GPET_ERR_BAD_ARG with the reason, checked on the host before anything is written.
+ *   gpet_batch_init_xy(batch, out)   the current init points of all edges, [B][n_init_max][2] xy in full-frame rows.
+ * The first two are legal only while no iteration has run since creation, gpet_batch_reset or an image swap (else GPET_ERR_STATE,
+ * nothing touched).  They change neither the observation sets nor the last converged fits (the warm start after a swap still needs
+ * them) nor the next-frame factor state; gpet_batch_reset keeps the current init points.  In a frame change their place is: ensemble
+ * keep, band placement (against the old init span), image swap, init follow, warm start.  (Added without a change of
+ * GPET_ABI_VERSION: the surface only grew.) */
+int gpet_batch_init_follow(gpet_batch* b, int window, int cols, int64_t* init_out);
+int gpet_batch_set_init(gpet_batch* b, const int64_t* const* init_xy);
+int gpet_batch_init_xy(gpet_batch* b, int64_t* out);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
