@@ -730,6 +730,7 @@ SYMBOLS = {
     "gpet_curve_kde": (C.c_int, [_P]),
     "gpet_final_cov": (C.c_int, [_P]),
     "gpet_select_pixels_only": (C.c_int, [_P]),
+    "gpet_select_pixels_loop": (C.c_int, [_P]),
     "gpet_final_set_training": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
     "gpet_lml_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "gpet_lml_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
@@ -1658,6 +1659,11 @@ class Batch:
 
     def select_pixels_only(self):
         self.ctx.check(self.lib.gpet_select_pixels_only(self.h))
+
+    def select_pixels_loop(self):
+        """gpet_select_pixels_loop: select_pixels by the launches of the device loop -- BUF_KDE keeps the raw density of the
+        tiles' row bands only."""
+        self.ctx.check(self.lib.gpet_select_pixels_loop(self.h))
 
     def curve_kde(self):
         self.ctx.check(self.lib.gpet_curve_kde(self.h))

@@ -115,6 +115,24 @@ int gpet_select_pixels(gpet_batch* b) {
   return check_device_status(b);
 }
 
+// gpet_select_pixels in the form the device loop runs after its scorer (enqueue_iteration): the density stays raw and
+// band-limited in GPET_BUF_KDE, rows outside a tile's band keep what they held, the pixel kernels normalise on the fly
+int gpet_select_pixels_loop(gpet_batch* b) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  if (!b->have_scores) return fail(c, GPET_ERR_STATE, "gpet_select_pixels_loop before gpet_score_curves");
+  b->have_results = false;  // (a new observation set: another trace)
+  b->have_last_fit = false;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
+  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0, ~0u, 1));
+  HIPCHK(c, launch_pixels(c->stream, b->d_edges, b->B, b->bd, 1));
+  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
+  b->iters_issued += 1;  // k_pix_select advanced every active edge's iteration counter
+  return check_device_status(b);
+}
+
 int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
   GPET_BATCH_SCOPE(b);
   if (!b || !ms_per_rep || reps < 1) return GPET_ERR_BAD_ARG;

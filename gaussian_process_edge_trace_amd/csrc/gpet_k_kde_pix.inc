@@ -734,21 +734,33 @@ __global__ void __launch_bounds__(64) k_pix_select(EdgeDev* edges) {
   int n_pix = n_pre;
   int it = 0;
   bool stuck = false;
+  int n_all = 0;  // bins that hold a candidate at all (counted by the first pass): once a pass has found every one of them, no
+                  // smaller threshold finds more
   while ((n_pix - n_pre < E.pixel_thresh) && (n_pix < E.algo_thresh)) {
     if (it > 0) {
-      if (thresh == 0.0) {  // the reference would spin forever here (SURVEY 5, latent hang 1)
+      // the reference would spin forever here (SURVEY 5, latent hang 1).  Not `thresh == 0`: a threshold decayed by 0.95
+      // never gets there -- in f64 it stops at 9 units of the smallest subnormal, where x * 0.95 rounds back to x
+      const double next = thresh * 0.95;
+      if (n_pix >= n_all || !(next < thresh)) {  // (n_pix: the bins found by the last pass; !(next < thresh): the fixed point, or NaN)
         stuck = true;
         break;
       }
-      thresh = thresh * 0.95;
+      thresh = next;
     }
-    int cnt = 0;
+    int cnt = 0, held = 0;
     for (int b = lane; b < E.n_bins; b += WAVE) {
       const unsigned long long bits = E.binbest[b];
-      cnt += (E.binarg[b] != 0x7FFFFFFFFFFFFFFFll) && (__longlong_as_double((long long)bits) >= thresh);
+      const bool holds = E.binarg[b] != 0x7FFFFFFFFFFFFFFFll;
+      held += holds;
+      cnt += holds && (__longlong_as_double((long long)bits) >= thresh);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, WAVE);
+    if (it == 0) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) held += __shfl_xor(held, o, WAVE);
+      n_all = held;
+    }
     n_pix = cnt;
     ++it;
   }

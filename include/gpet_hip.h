@@ -394,6 +394,11 @@ int gpet_score_curves(gpet_batch* b);
  * GPET_BUF_BEST_IDX / _BEST_COSTS select among GPET_BUF_SAMPLES goes to GPET_BUF_KDE. */
 int gpet_curve_kde(gpet_batch* b);
 int gpet_select_pixels(gpet_batch* b);
+/* gpet_select_pixels by the kernels and in the form gpet_trace_iterate runs after its scorer: same observation set, score
+ * threshold and counters, but GPET_BUF_KDE keeps the RAW density, and only inside every 16-column tile's band of rows (the
+ * rows of the tile's surviving curve points, +-4); rows outside a band keep what they held.  There so that tests reach the
+ * loop's form of the stage on injected inputs. */
+int gpet_select_pixels_loop(gpet_batch* b);
 /* Pixel scoring / threshold decay / per-bin argmax only (gpet.py:532-618), on whatever curve KDE
  * is currently in GPET_BUF_KDE (tests inject the reference's). */
 int gpet_select_pixels_only(gpet_batch* b);

@@ -1,4 +1,5 @@
-"""Batches for the tests that inject a stage's inputs (tests/test_gpu_sample_gemm_exact.py, tests/test_gpu_score_injected.py).
+"""Batches for the tests that inject a stage's inputs (tests/test_gpu_sample_gemm_exact.py, tests/test_gpu_score_injected.py,
+tests/test_gpu_kde_pix_injected.py).
 
 They come from the constructor's own parameter functions (gpet.resolve_params, gpet.to_abi_params) and _lib.Batch rather than
 from GP_Edge_Tracing: the constructor, like the reference's, turns N_samples <= 100 into 1000, and these tests need the exact
@@ -9,17 +10,22 @@ import numpy as np
 KERNEL = {'kernel': 'RBF', 'sigma_f': 2, 'length_scale': 10}
 
 
-def make_batch(amd, ctx, grad, spans, S, factor_cap=0, z_cols=0, sample_dtype=None):
-    """A batch of the edges spans = [(x_st, Lg)] on the one image grad with S samples per edge, of any S >= 1."""
+def make_batch(amd, ctx, grad, spans, S, factor_cap=0, z_cols=0, sample_dtype=None, delta_x=5, fix_endpoints=True, pixel_thresh=2,
+               score_thresh=1, keep_ratio=0.25, M=None):
+    """A batch of the edges spans = [(x_st, Lg)] on the one image grad with S samples per edge, of any S >= 1.
+
+    delta_x, fix_endpoints, pixel_thresh, score_thresh: the constructor's, through its own clamping (delta_x <= 3 becomes 2).
+    keep_ratio: n_keep = max(1, int(keep_ratio * S)) curves are kept.  M: the row count the init points are placed by (the second
+    one on row M - 2), the image's own by default."""
     from gaussian_process_edge_trace_amd.gpet import resolve_params, to_abi_params
-    rows = grad.shape[0]
+    rows = grad.shape[0] if M is None else int(M)
     params, inits = [], []
     for x_st, Lg in spans:
         init = np.array([[x_st, 1], [x_st + Lg - 1, rows - 2]])
-        p = resolve_params(init, grad.shape, KERNEL, noise_y=1, N_samples=max(S, 101), score_thresh=1, delta_x=5, keep_ratio=0.25,
-                           pixel_thresh=2, seed=1, fix_endpoints=True)
+        p = resolve_params(init, grad.shape, KERNEL, noise_y=1, N_samples=max(S, 101), score_thresh=score_thresh, delta_x=delta_x,
+                           keep_ratio=keep_ratio, pixel_thresh=pixel_thresh, seed=1, fix_endpoints=fix_endpoints)
         q = to_abi_params(p, factor_cap=factor_cap, z_cols=z_cols)
-        q.n_samples, q.n_keep = S, max(1, S // 4)
+        q.n_samples, q.n_keep = S, max(1, int(keep_ratio * S))
         params.append(q)
         inits.append(p["init"])
     b = amd._lib.Batch(ctx, [grad], params, inits, share_image=len(spans) > 1)
