@@ -37,8 +37,10 @@ struct Carver {  // lays buffers out in one arena (256-byte aligned); with base 
   }
 };
 
+// dynamic LDS a kernel may ask for (of the 160 KB of a CU): the limit of every capacity rule here and in gpet_iter_plan.h
+#define LDS_DYN_MAX (150 * 1024)
 // dynamic LDS available to k_struct_H (the structured path needs at least U + one row of L + beta in it)
-#define STRUCT_H_LDS_MAX (150 * 1024)
+#define STRUCT_H_LDS_MAX LDS_DYN_MAX
 
 inline int nu_to_code(double nu) {
   if (nu == 0.5) return 0;

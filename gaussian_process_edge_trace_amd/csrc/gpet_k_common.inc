@@ -4,7 +4,6 @@
 // ---------------------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------------------
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(ENSEMBLE_THREADS) k_ensemble_pick(const Ensemb
 // cost[e] of every edge's converged mean on stream st.  view / view_sc: [B]; rows: [B][row_stride] doubles, row_stride >= the
 // batch's widest row pitch; part: [B][part_stride] doubles, part_stride >= 2 * the scorer's tile count (fincost_part_stride)
 size_t fincost_part_stride(const BatchDims& bd) {
-  const int n_tiles = cdiv((bd.Lg - 2) / 2, SC_PAIRS);
+  const int n_tiles = score_tiles(bd.Lg);
   return (size_t)2 * (n_tiles > 1 ? n_tiles : 1);
 }
 hipError_t launch_final_costs(hipStream_t st, const EdgeDev* d_edges, int B, const BatchDims& bd, EdgeDev* d_view, gpet_scalars* d_view_sc,

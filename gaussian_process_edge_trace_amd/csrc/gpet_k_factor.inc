@@ -1564,7 +1564,7 @@ __global__ void __launch_bounds__(256) k_struct_mean(EdgeDev* edges) {
 // LDS, wave w owns 16 of the 64 columns and all MT row tiles, so Q0 is read from HBM once per iteration.
 // The sign convention is applied as the rows are written (below).
 // MT (row tiles of 16) is a template parameter for the same reason as the K extent of the sample GEMM.
-#define SR_TJ 64
+// (SR_TJ = 64 grid columns per workgroup: gpet_iter_plan.h)
 typedef double v4f64_ __attribute__((ext_vector_type(4)));
 template <int MT, int KS>
 __device__ __forceinline__ void struct_rows_body(const EdgeDev& E, double* s_w, int tile) {

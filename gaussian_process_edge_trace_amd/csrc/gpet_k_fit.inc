@@ -1,4 +1,4 @@
-// Part of gpet_kernels.hip (included there, inside namespace gpet, in this order): a2-a5: training set, K, Cholesky, alpha (one workgroup per edge; blocked in HBM above 128 points) and predict.
+// Part of gpet_kernels.hip (included there, inside namespace gpet, in this order): a2-a5: training set, K, Cholesky, alpha (one workgroup per edge; blocked in HBM above 128 points) and predict, with the blocked predict of many training points.
 // ---------------------------------------------------------------------------------------
 // a2-a4  training-set assembly + K_obs + Cholesky + alpha   (one workgroup per edge)
 //        gpet.py:209-231, sklearn_gpr.py:221-227, 304-320
@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(576) k_fit(EdgeDev* edges) {
 // Cholesky (diagonal block in LDS / row-panel solve / trailing update on the f64 matrix cores) -> blocked solves
 // for alpha.  The panel kernels are enqueued for every 64-block of n_cap and return at once past the actual n.
 // ---------------------------------------------------------------------------------------
-#define CB 64
+// (CB = 64, the block: gpet_iter_plan.h)
 __global__ void __launch_bounds__(1024) k_fit_head(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.y];
   gpet_scalars* sc = E.sc;
@@ -1044,3 +1044,147 @@ __global__ void __launch_bounds__(64) k_predict(EdgeDev* edges, int out_stride) 
   }
 }
 
+// ---- a5 for many training points (generic path): K_*^T rows into V, mean, blocked V = L^-1 K_*^T, std ----
+__global__ void __launch_bounds__(256) k_kstar_build(EdgeDev* edges) {
+  const EdgeDev E = edges[blockIdx.z];
+  const gpet_scalars* sc = E.sc;
+  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
+  const int n = sc->n, Lg = E.Lg;
+  const int j = blockIdx.x * 64 + (threadIdx.x & 63);
+  const double amp = sc->amp, length = E.length_scale;
+  if (j >= Lg) return;
+  const double xq = (double)(E.x_st + j) / length;
+  for (int i = blockIdx.y * 4 + (threadIdx.x >> 6); i < n; i += gridDim.y * 4)
+    E.V[(size_t)i * Lg + j] = amp * corr_px(E, (double)(E.x_st + j), E.xt[i], length);
+}
+// block k0 of V = L^-1 K_*^T for 32 columns of the grid per workgroup, on the matrix cores:
+//   X = K_*^T[k0.., cols] - sum_{j0 < k0} L[k0.., j0..] V[j0.., cols]   (64 x 64 by 64 x 32 products, left-looking),
+//   V[k0.., cols] = L_kk^-1 X   (the inverse of the diagonal block from k_chol_diag).
+// Wave w owns rows 16 w .. 16 w + 15 of the block and both 16-column halves.
+#ifndef VS_COLS
+#define VS_COLS 16  // grid columns per workgroup (16, 32 or 64 by -DVS_COLS=..; at n = 1500, Lg = 2048: 3.42 / 3.62 / 4.09 ms per fit + predict + covariance)
+#endif
+#define VS_NH (VS_COLS / 16)          // 16-column halves per wave
+#define VS_PU (CB * VS_COLS / 256)    // prefetch registers of the V block per thread
+__global__ void __launch_bounds__(256) k_vsolve_mfma(EdgeDev* edges, int k0) {
+  const EdgeDev E = edges[blockIdx.y];
+  const gpet_scalars* sc = E.sc;
+  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
+  const int n = sc->n, Lg = E.Lg, ld = E.n_cap;
+  const int a0 = blockIdx.x * VS_COLS;
+  if (k0 >= n || a0 >= Lg) return;
+  const int nb = (n - k0) < CB ? (n - k0) : CB;
+  __shared__ double sL[CB][CB + 1];
+  __shared__ double sU[CB][VS_COLS + 1];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
+  v4f64c acc[VS_NH];
+#pragma unroll
+  for (int h = 0; h < VS_NH; ++h) acc[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
+  // the blocks of the next j0 are loaded into registers while the matrix cores work on the current ones (a launch has
+  // only Lg / 32 workgroups: nothing else hides the two dependent round trips per block otherwise -- 85 -> ~25 us)
+  double pl[16], pu[VS_PU];
+  auto fetch = [&](int j0) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int e = tid + 256 * u, i = e >> 6, t = e & 63;
+      pl[u] = (i < nb) ? E.K[(size_t)(k0 + i) * ld + j0 + t] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < VS_PU; ++u) {
+      const int e = tid + 256 * u, t = e / VS_COLS, a = e % VS_COLS;
+      pu[u] = (a0 + a < Lg) ? E.V[(size_t)(j0 + t) * Lg + a0 + a] : 0.0;
+    }
+  };
+  if (k0 > 0) fetch(0);
+  for (int j0 = 0; j0 < k0; j0 += CB) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int e = tid + 256 * u;
+      sL[e >> 6][e & 63] = pl[u];
+    }
+#pragma unroll
+    for (int u = 0; u < VS_PU; ++u) {
+      const int e = tid + 256 * u;
+      sU[e / VS_COLS][e % VS_COLS] = pu[u];
+    }
+    __syncthreads();
+    if (j0 + CB < k0) fetch(j0 + CB);
+#pragma unroll
+    for (int kk = 0; kk < CB; kk += 4) {
+      const double a = sL[16 * w + li][kk + lq];
+#pragma unroll
+      for (int h = 0; h < VS_NH; ++h) acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], acc[h], 0, 0, 0);
+    }
+  }
+  __syncthreads();
+  // X = B - acc into sU (rows of the block beyond n: zero), the inverse into sL
+  const double* inv = E.chol_inv + (size_t)(k0 / CB) * CB * CB;
+  for (int e = tid; e < CB * CB; e += 256) sL[e >> 6][e & 63] = inv[e];
+#pragma unroll
+  for (int h = 0; h < VS_NH; ++h)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
+      sU[i][a] = (i < nb && a0 + a < Lg) ? E.V[(size_t)(k0 + i) * Lg + a0 + a] - acc[h][g] : 0.0;
+    }
+  __syncthreads();
+#pragma unroll
+  for (int h = 0; h < VS_NH; ++h) acc[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int kk = 0; kk < CB; kk += 4) {
+    const double a = sL[16 * w + li][kk + lq];
+#pragma unroll
+    for (int h = 0; h < VS_NH; ++h) acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], acc[h], 0, 0, 0);
+  }
+#pragma unroll
+  for (int h = 0; h < VS_NH; ++h)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
+      if (i < nb && a0 + a < Lg) E.V[(size_t)(k0 + i) * Lg + a0 + a] = acc[h][g];
+    }
+}
+
+// Column sums over the n rows of V for many training points: a workgroup owns 16 grid columns, its 16 row-lanes take every
+// sixteenth row each (independent loads, a wave reads four rows of 128 contiguous bytes per instruction) and their
+// partial sums are added in row-lane order.  (One thread per column walking all n rows -- Lg / 256 workgroups on the
+// whole GPU -- took 0.39 + 0.36 ms at n = 1500, Lg = 2048.)
+//   STD = false: mean_j = y_std * sum_i K_*[i][j] alpha_i + y_mean   (sklearn_gpr.py:381-385; before V is overwritten)
+//   STD = true:  std_j = sqrt(max(amp - sum_i V[i][j]^2, 0) * y_std^2)   (sklearn_gpr.py:414-436)
+#define PB_COLS 16
+#define PB_LANES 16
+template <bool STD>
+__global__ void __launch_bounds__(PB_COLS * PB_LANES) k_pred_colsum_big(EdgeDev* edges) {
+  const EdgeDev E = edges[blockIdx.y];
+  const gpet_scalars* sc = E.sc;
+  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
+  __shared__ double s_part[PB_LANES][PB_COLS + 1];
+  const int n = sc->n, Lg = E.Lg;
+  const int c = threadIdx.x & (PB_COLS - 1), r = threadIdx.x / PB_COLS;
+  const int j = blockIdx.x * PB_COLS + c;
+  const GPET_GLOBAL double* __restrict__ Vg = as_global(E.V);
+  const GPET_GLOBAL double* __restrict__ al = as_global(E.alpha);
+  double sum = 0.0;
+  if (j < Lg) {
+#pragma unroll 8
+    for (int i = r; i < n; i += PB_LANES) {
+      const double v = Vg[(size_t)i * Lg + j];
+      sum += STD ? v * v : v * al[i];
+    }
+  }
+  s_part[r][c] = sum;
+  __syncthreads();
+  if (r == 0 && j < Lg) {
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < PB_LANES; ++q) t += s_part[q][c];
+    if (STD) {
+      double var = sc->amp - t;
+      if (var < 0.0) var = 0.0;
+      E.std[j] = sqrt(var * (sc->y_std * sc->y_std));
+    } else {
+      E.mean[j] = sc->y_std * t + sc->y_mean;
+    }
+  }
+}

@@ -5,6 +5,25 @@
 //     (bw=1, support 4), crop, float32 min-max.  (PARITY UNPINNED: KDEpy is not available.)
 //     Grid layout is x-major like KDEpy's: cell (gx, gy) at gx*(M+2)+gy.
 // ---------------------------------------------------------------------------------------
+// threads of the workgroup: NT where the kernel fixes them, NT = 0: blockDim.x, read where it is used as the kernels always did
+template <int NT>
+__device__ __forceinline__ auto wg_threads() {
+  if constexpr (NT != 0) return NT;
+  else return blockDim.x;
+}
+// the per-bin best score and its candidate back to "none" (before every pixel selection), by the threads of a workgroup
+template <int NT>
+__device__ __forceinline__ void pix_bins_reset(const EdgeDev& E, int tid) {
+  for (int i = tid; i < E.n_bins; i += wg_threads<NT>()) {
+    E.binbest[i] = 0ull;
+    E.binarg[i] = 0x7FFFFFFFFFFFFFFFll;
+  }
+}
+__global__ void __launch_bounds__(256) k_pix_reset(EdgeDev* edges) {
+  const EdgeDev E = edges[blockIdx.y];
+  pix_bins_reset<0>(E, threadIdx.x);
+}
+
 __global__ void __launch_bounds__(256) k_kde_clear(EdgeDev* edges, int mode) {
   const EdgeDev E = edges[blockIdx.y];
   const gpet_scalars* sc = E.sc;
@@ -17,10 +36,7 @@ __global__ void __launch_bounds__(256) k_kde_clear(EdgeDev* edges, int mode) {
       E.mm[0] = 0xFFFFFFFFu;
       E.mm[1] = 0u;
     }
-    for (int i = threadIdx.x; i < E.n_bins; i += blockDim.x) {
-      E.binbest[i] = 0ull;
-      E.binarg[i] = 0x7FFFFFFFFFFFFFFFll;
-    }
+    pix_bins_reset<0>(E, threadIdx.x);
     for (int i = threadIdx.x; i < E.N; i += blockDim.x) E.colsum[i] = 0.0;
   }
 }
@@ -146,29 +162,13 @@ __global__ void __launch_bounds__(256) k_kde_normalise(EdgeDev* edges, int mode)
 // ---- fused curve KDE (per-iteration path) ----------------------------------------------
 // k_kde_prep: total kept weight W (KDEpy normalises the weights by their sum), points removed
 // for lying outside the image (gpet.py:498-500), and the per-iteration resets.
-#define KDE_PREP_MAXB 1024
-__global__ void __launch_bounds__(1024) k_kde_prep(EdgeDev* edges) {
-  const EdgeDev E = edges[blockIdx.y];
-  gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  __shared__ double s_red[16];
-  __shared__ double s_inv;
-  __shared__ double s_ic[KDE_PREP_MAXB];   // 1 / cost of the kept curves, then their weights
-  __shared__ int s_row[KDE_PREP_MAXB];     // their sample rows
-  const int tid = threadIdx.x, nk = E.n_keep;
-  const bool staged = nk <= KDE_PREP_MAXB;
-  // the reciprocals in parallel, their sum by one thread in index order (the order of the sequential loop this
-  // replaces, which paid one global round trip and one division per curve on a single thread)
-  if (staged)
-    for (int b = tid; b < nk; b += blockDim.x) {
-      s_ic[b] = 1.0 / E.best_costs[b];
-      s_row[b] = E.best_idx[b];
-    }
-  for (int i = tid; i < E.n_bins; i += blockDim.x) {
-    E.binbest[i] = 0ull;
-    E.binarg[i] = 0x7FFFFFFFFFFFFFFFll;
-  }
-  __syncthreads();
+// kde_prep_body: everything after the kept curves' reciprocals and sample rows are staged (s_ic, s_row; `staged`: n_keep <=
+// KDE_PREP_MAXB, else they are read from global memory) and a barrier -- k_kde_prep's own, and k_score_tail's with staged = true.
+template <int NT>
+__device__ __forceinline__ void kde_prep_body(const EdgeDev& E, gpet_scalars* sc, double* s_ic, const int* s_row, double* s_red,
+                                              double& s_inv, int tid, int nk, bool staged) {
+  // the sum of the reciprocals by one thread in index order (the order of the sequential loop this replaces, which paid one
+  // global round trip and one division per curve on a single thread)
   if (tid == 0) {
     double inv_sum = 0.0;
     if (staged)
@@ -182,14 +182,14 @@ __global__ void __launch_bounds__(1024) k_kde_prep(EdgeDev* edges) {
   __syncthreads();
   const double inv_sum = s_inv, ymax = (double)(E.M - 1);
   if (staged) {
-    for (int b = tid; b < nk; b += blockDim.x) s_ic[b] = s_ic[b] / inv_sum;  // weight of curve b
+    for (int b = tid; b < nk; b += (int)wg_threads<NT>()) s_ic[b] = s_ic[b] / inv_sum;  // weight of curve b
     __syncthreads();
   }
   double wsum = 0.0;
   int removed = 0;
   if (staged) {
     // wave w takes curves w, w + 16, ...; its lanes walk the columns: coalesced rows, no division per point
-    const int lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
+    const int lane = tid & 63, wv = tid >> 6, nw = (int)wg_threads<NT>() >> 6;
     for (int b = wv; b < nk; b += nw) {
       const size_t row = (size_t)s_row[b] * E.Yp;
       const double wb = s_ic[b];
@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(1024) k_kde_prep(EdgeDev* edges) {
   } else {
     const int total = nk * E.Lg;
 #pragma unroll 4
-    for (int e = tid; e < total; e += blockDim.x) {
+    for (int e = tid; e < total; e += (int)wg_threads<NT>()) {
       const int b = e / E.Lg, k = e - b * E.Lg;
       const double y = y_ld(E, (size_t)E.best_idx[b] * E.Yp + k);
       const double wb = (1.0 / E.best_costs[b]) / inv_sum;
@@ -217,12 +217,31 @@ __global__ void __launch_bounds__(1024) k_kde_prep(EdgeDev* edges) {
     sc->n_removed = (int)rem;
   }
 }
+__global__ void __launch_bounds__(1024) k_kde_prep(EdgeDev* edges) {
+  const EdgeDev E = edges[blockIdx.y];
+  gpet_scalars* sc = E.sc;
+  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
+  __shared__ double s_red[16];
+  __shared__ double s_inv;
+  __shared__ double s_ic[KDE_PREP_MAXB];   // 1 / cost of the kept curves, then their weights
+  __shared__ int s_row[KDE_PREP_MAXB];     // their sample rows
+  const int tid = threadIdx.x, nk = E.n_keep;
+  const bool staged = nk <= KDE_PREP_MAXB;
+  if (staged)  // the reciprocals in parallel
+    for (int b = tid; b < nk; b += blockDim.x) {
+      s_ic[b] = 1.0 / E.best_costs[b];
+      s_row[b] = E.best_idx[b];
+    }
+  pix_bins_reset<0>(E, tid);
+  __syncthreads();
+  kde_prep_body<0>(E, sc, s_ic, s_row, s_red, s_inv, tid, nk, staged);
+}
 
 // Small batches (round 6): the three one-workgroup-per-edge steps between the tiled scorer and the fused KDE -- k_score_combine,
 // k_topk_sort, k_kde_prep -- as ONE launch.  A small batch is a latency chain in which every launch costs ~5 us of dispatch beside
-// its few microseconds of work; the arithmetic is the three kernels' own, in their order (partials added in tile order, bitonic sort
-// with the index as second key, reciprocal sum by one thread in index order), so costs, best_idx and the KDE weights are the same
-// bits.  Needs S <= 1024, n_keep <= KDE_PREP_MAXB and the tiled scorer's partial sums (the launcher checks).
+// its few microseconds of work; the arithmetic is the three kernels' own, in their order -- their bodies, called from here (partials
+// added in tile order, bitonic sort with the index as second key, reciprocal sum by one thread in index order) --, so costs, best_idx
+// and the KDE weights are the same bits.  Needs S <= 1024, n_keep <= KDE_PREP_MAXB and the tiled scorer's partial sums (the launcher checks).
 __global__ void __launch_bounds__(1024) k_score_tail(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.y];
   gpet_scalars* sc = E.sc;
@@ -238,44 +257,16 @@ __global__ void __launch_bounds__(1024) k_score_tail(EdgeDev* edges) {
   {
     double cost = INFINITY;  // (the padding of the sort: behind every finite cost, and behind +inf by index)
     if (tid < S) {
-      const int my_tiles = ((E.Lg - 2) / 2 + SC_PAIRS - 1) / SC_PAIRS;
-      double al = 0.0, li = 0.0;
-      for (int t = 0; t < my_tiles; ++t) {
-        al += E.cost_part[((size_t)t * E.S + tid) * 2];
-        li += E.cost_part[((size_t)t * E.S + tid) * 2 + 1];
-      }
-      if (E.y_f32) simpson_tail(E, reinterpret_cast<const float*>(E.Y) + (size_t)tid * E.Yp, al, li);
-      else simpson_tail(E, E.Y + (size_t)tid * E.Yp, al, li);
-      cost = al / li;
+      cost = score_combine_one(E, tid);
       E.costs[tid] = cost;
     }
     s_k[tid] = cost;
     s_i[tid] = tid;
   }
-  // (k_kde_prep's per-iteration resets: independent of everything else here)
-  for (int i = tid; i < E.n_bins; i += 1024) {
-    E.binbest[i] = 0ull;
-    E.binarg[i] = 0x7FFFFFFFFFFFFFFFll;
-  }
+  pix_bins_reset<1024>(E, tid);  // (k_kde_prep's per-iteration reset: independent of everything else here)
   __syncthreads();
-  // -- k_topk_sort: 512 compare-exchange pairs per step (the upper half of the workgroup only keeps the barriers company)
-  for (int k = 2; k <= 1024; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (tid < 512) {
-        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
-        const double a = s_k[i], b = s_k[l];
-        const int ia = s_i[i], ib = s_i[l];
-        const bool a_first = (a < b) || (a == b && ia < ib);
-        const bool up = (i & k) == 0;
-        if (a_first != up) {
-          s_k[i] = b;
-          s_k[l] = a;
-          s_i[i] = ib;
-          s_i[l] = ia;
-        }
-      }
-      __syncthreads();
-    }
+  // -- k_topk_sort (the upper half of the workgroup only keeps the barriers company)
+  bitonic_sort_1024<false>(s_k, s_i, tid);
   for (int b = tid; b < nk; b += 1024) {
     E.best_idx[b] = s_i[b];
     E.best_costs[b] = s_k[b];
@@ -284,45 +275,10 @@ __global__ void __launch_bounds__(1024) k_score_tail(EdgeDev* edges) {
   }
   __syncthreads();
   // -- k_kde_prep (its staged form: n_keep <= KDE_PREP_MAXB)
-  if (tid == 0) {
-    double inv_sum = 0.0;
-    for (int b = 0; b < nk; ++b) inv_sum += s_ic[b];
-    s_inv = inv_sum;
-    E.mm[0] = 0xFFFFFFFFu;
-    E.mm[1] = 0u;
-  }
-  __syncthreads();
-  const double inv_sum = s_inv, ymax = (double)(E.M - 1);
-  for (int b = tid; b < nk; b += 1024) s_ic[b] = s_ic[b] / inv_sum;  // weight of curve b
-  __syncthreads();
-  double wsum = 0.0;
-  int removed = 0;
-  {
-    const int lane = tid & 63, wv = tid >> 6, nw = 16;
-    for (int b = wv; b < nk; b += nw) {
-      const size_t row = (size_t)s_row[b] * E.Yp;
-      const double wb = s_ic[b];
-#pragma unroll 4
-      for (int k = lane; k < E.Lg; k += 64) {
-        const double y = y_ld(E, row + k);
-        if (y < 0.0 || y > ymax) ++removed; else wsum += wb;
-      }
-    }
-  }
-  wsum = block_sum(wsum, s_red);
-  const double rem = block_sum((double)removed, s_red);
-  if (tid == 0) {
-    E.colsum[0] = wsum;     // W
-    E.colsum[1] = inv_sum;  // sum of 1/cost over the kept curves
-    sc->n_removed = (int)rem;
-  }
+  kde_prep_body<1024>(E, sc, s_ic, s_row, s_red, s_inv, tid, nk, true);
 }
 
-#define KDE_TX 16
-#define KDE_H 128    // image rows per LDS row-chunk
-#define KDE_NB 128   // curves staged per pass
-#define KDE_THREADS 512
-
+// (KDE_TX = 16 columns per tile, KDE_H = 128 rows per chunk, KDE_NB = 128 curves per pass, KDE_THREADS = 512: gpet_iter_plan.h)
 // One workgroup per (16-column tile, edge).  The tile's curve points are staged in LDS once; the
 // rows that can receive weight are the band [ymin-4, ymax+5] of those points, and only that band is
 // processed, in chunks of KDE_H rows through ONE (KDE_TX+8) x (KDE_H+8) f64 LDS tile (39 KB per
@@ -604,7 +560,7 @@ __device__ __forceinline__ int bin_of(const EdgeDev& E, int x) {
 // best new candidate of every admissible column (first in row-major order among equals).
 // 32 columns x 8 row-lanes per workgroup: each thread scans every 8th row of its column (independent loads; a wave reads
 // two rows of 128 contiguous bytes per instruction: whole cache lines), then the 8 lanes of a column reduce in LDS.
-#define PIX_CX 32
+// (PIX_CX = 32: gpet_iter_plan.h)
 #define PIX_RY 8
 __global__ void __launch_bounds__(256) k_pix_columns(EdgeDev* edges, int raw_band) {
   const EdgeDev E = edges[blockIdx.y];
@@ -804,5 +760,3 @@ __global__ void __launch_bounds__(64) k_pix_select(EdgeDev* edges) {
     sc->done = (n_pix >= E.algo_thresh) ? 1 : 0;
   }
 }
-
-

@@ -1,4 +1,5 @@
-// Part of gpet_kernels.hip (included there, inside namespace gpet, in this order): launchers (and the kernels of the many-training-points predict, the Philox generator, small utilities).
+// Part of gpet_kernels.hip (included there, inside namespace gpet, in this order): launchers (and three one-line utility kernels).  The launchers of a loop
+// iteration only dispatch: gpet_iter_plan.h decides the variant, the grid and the LDS of every step.
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
@@ -218,151 +219,6 @@ hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src,
   return hipGetLastError();
 }
 
-// ---- a5 for many training points (generic path): K_*^T rows into V, mean, blocked V = L^-1 K_*^T, std ----
-__global__ void __launch_bounds__(256) k_kstar_build(EdgeDev* edges) {
-  const EdgeDev E = edges[blockIdx.z];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  const int n = sc->n, Lg = E.Lg;
-  const int j = blockIdx.x * 64 + (threadIdx.x & 63);
-  const double amp = sc->amp, length = E.length_scale;
-  if (j >= Lg) return;
-  const double xq = (double)(E.x_st + j) / length;
-  for (int i = blockIdx.y * 4 + (threadIdx.x >> 6); i < n; i += gridDim.y * 4)
-    E.V[(size_t)i * Lg + j] = amp * corr_px(E, (double)(E.x_st + j), E.xt[i], length);
-}
-// block k0 of V = L^-1 K_*^T for 32 columns of the grid per workgroup, on the matrix cores:
-//   X = K_*^T[k0.., cols] - sum_{j0 < k0} L[k0.., j0..] V[j0.., cols]   (64 x 64 by 64 x 32 products, left-looking),
-//   V[k0.., cols] = L_kk^-1 X   (the inverse of the diagonal block from k_chol_diag).
-// Wave w owns rows 16 w .. 16 w + 15 of the block and both 16-column halves.
-#ifndef VS_COLS
-#define VS_COLS 16  // grid columns per workgroup (16, 32 or 64 by -DVS_COLS=..; at n = 1500, Lg = 2048: 3.42 / 3.62 / 4.09 ms per fit + predict + covariance)
-#endif
-#define VS_NH (VS_COLS / 16)          // 16-column halves per wave
-#define VS_PU (CB * VS_COLS / 256)    // prefetch registers of the V block per thread
-__global__ void __launch_bounds__(256) k_vsolve_mfma(EdgeDev* edges, int k0) {
-  const EdgeDev E = edges[blockIdx.y];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  const int n = sc->n, Lg = E.Lg, ld = E.n_cap;
-  const int a0 = blockIdx.x * VS_COLS;
-  if (k0 >= n || a0 >= Lg) return;
-  const int nb = (n - k0) < CB ? (n - k0) : CB;
-  __shared__ double sL[CB][CB + 1];
-  __shared__ double sU[CB][VS_COLS + 1];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
-  v4f64c acc[VS_NH];
-#pragma unroll
-  for (int h = 0; h < VS_NH; ++h) acc[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
-  // the blocks of the next j0 are loaded into registers while the matrix cores work on the current ones (a launch has
-  // only Lg / 32 workgroups: nothing else hides the two dependent round trips per block otherwise -- 85 -> ~25 us)
-  double pl[16], pu[VS_PU];
-  auto fetch = [&](int j0) {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int e = tid + 256 * u, i = e >> 6, t = e & 63;
-      pl[u] = (i < nb) ? E.K[(size_t)(k0 + i) * ld + j0 + t] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < VS_PU; ++u) {
-      const int e = tid + 256 * u, t = e / VS_COLS, a = e % VS_COLS;
-      pu[u] = (a0 + a < Lg) ? E.V[(size_t)(j0 + t) * Lg + a0 + a] : 0.0;
-    }
-  };
-  if (k0 > 0) fetch(0);
-  for (int j0 = 0; j0 < k0; j0 += CB) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int e = tid + 256 * u;
-      sL[e >> 6][e & 63] = pl[u];
-    }
-#pragma unroll
-    for (int u = 0; u < VS_PU; ++u) {
-      const int e = tid + 256 * u;
-      sU[e / VS_COLS][e % VS_COLS] = pu[u];
-    }
-    __syncthreads();
-    if (j0 + CB < k0) fetch(j0 + CB);
-#pragma unroll
-    for (int kk = 0; kk < CB; kk += 4) {
-      const double a = sL[16 * w + li][kk + lq];
-#pragma unroll
-      for (int h = 0; h < VS_NH; ++h) acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], acc[h], 0, 0, 0);
-    }
-  }
-  __syncthreads();
-  // X = B - acc into sU (rows of the block beyond n: zero), the inverse into sL
-  const double* inv = E.chol_inv + (size_t)(k0 / CB) * CB * CB;
-  for (int e = tid; e < CB * CB; e += 256) sL[e >> 6][e & 63] = inv[e];
-#pragma unroll
-  for (int h = 0; h < VS_NH; ++h)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
-      sU[i][a] = (i < nb && a0 + a < Lg) ? E.V[(size_t)(k0 + i) * Lg + a0 + a] - acc[h][g] : 0.0;
-    }
-  __syncthreads();
-#pragma unroll
-  for (int h = 0; h < VS_NH; ++h) acc[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int kk = 0; kk < CB; kk += 4) {
-    const double a = sL[16 * w + li][kk + lq];
-#pragma unroll
-    for (int h = 0; h < VS_NH; ++h) acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], acc[h], 0, 0, 0);
-  }
-#pragma unroll
-  for (int h = 0; h < VS_NH; ++h)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
-      if (i < nb && a0 + a < Lg) E.V[(size_t)(k0 + i) * Lg + a0 + a] = acc[h][g];
-    }
-}
-
-// Column sums over the n rows of V for many training points: a workgroup owns 16 grid columns, its 16 row-lanes take every
-// sixteenth row each (independent loads, a wave reads four rows of 128 contiguous bytes per instruction) and their
-// partial sums are added in row-lane order.  (One thread per column walking all n rows -- Lg / 256 workgroups on the
-// whole GPU -- took 0.39 + 0.36 ms at n = 1500, Lg = 2048.)
-//   STD = false: mean_j = y_std * sum_i K_*[i][j] alpha_i + y_mean   (sklearn_gpr.py:381-385; before V is overwritten)
-//   STD = true:  std_j = sqrt(max(amp - sum_i V[i][j]^2, 0) * y_std^2)   (sklearn_gpr.py:414-436)
-#define PB_COLS 16
-#define PB_LANES 16
-template <bool STD>
-__global__ void __launch_bounds__(PB_COLS * PB_LANES) k_pred_colsum_big(EdgeDev* edges) {
-  const EdgeDev E = edges[blockIdx.y];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  __shared__ double s_part[PB_LANES][PB_COLS + 1];
-  const int n = sc->n, Lg = E.Lg;
-  const int c = threadIdx.x & (PB_COLS - 1), r = threadIdx.x / PB_COLS;
-  const int j = blockIdx.x * PB_COLS + c;
-  const GPET_GLOBAL double* __restrict__ Vg = as_global(E.V);
-  const GPET_GLOBAL double* __restrict__ al = as_global(E.alpha);
-  double sum = 0.0;
-  if (j < Lg) {
-#pragma unroll 8
-    for (int i = r; i < n; i += PB_LANES) {
-      const double v = Vg[(size_t)i * Lg + j];
-      sum += STD ? v * v : v * al[i];
-    }
-  }
-  s_part[r][c] = sum;
-  __syncthreads();
-  if (r == 0 && j < Lg) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < PB_LANES; ++q) t += s_part[q][c];
-    if (STD) {
-      double var = sc->amp - t;
-      if (var < 0.0) var = 0.0;
-      E.std[j] = sqrt(var * (sc->y_std * sc->y_std));
-    } else {
-      E.mean[j] = sc->y_std * t + sc->y_mean;
-    }
-  }
-}
-
 // hipFuncSetAttribute applies to the CURRENT device: remember per device what has been raised, so that one process
 // may hold contexts on several GPUs (the launchers run with the context's device current).
 struct PerDeviceOnce {
@@ -376,37 +232,55 @@ struct PerDeviceOnce {
   }
 };
 
+static dim3 dim3_of(const Grid3& g) { return dim3(g.x, g.y, g.z); }
+// f(std::integral_constant<int, KS>) for the K extent ks a plan chose (one of K_EXTENTS): the template instances of the sample GEMMs and of k_struct_rows
+template <typename F>
+static void for_k_extent(int ks, F&& f) {
+  switch (ks) {
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 18: f(std::integral_constant<int, 18>{}); break;
+    case 20: f(std::integral_constant<int, 20>{}); break;
+    default: f(std::integral_constant<int, 24>{}); break;
+  }
+}
+
 static void fit_predict_attrs() {
   static PerDeviceOnce once;
   if (!once.first()) return;
-  (void)hipFuncSetAttribute((const void*)k_fit<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_fit<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_predict<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_predict<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+  (void)hipFuncSetAttribute((const void*)k_fit<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+  (void)hipFuncSetAttribute((const void*)k_fit<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+  (void)hipFuncSetAttribute((const void*)k_predict<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+  (void)hipFuncSetAttribute((const void*)k_predict<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+}
+
+// the fit with K in LDS where the plan has it there (false: more possible training points than K fits LDS for -- the caller's blocked form)
+static bool launch_fit_in_lds(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, bool final_fit) {
+  const FitPlan p = fit_plan(bd);
+  if (!p.in_lds) return false;
+  fit_predict_attrs();
+  if (final_fit) hipLaunchKernelGGL((k_fit<true, true>), dim3(1, B), dim3(576), p.lds, st, d_edges);
+  else hipLaunchKernelGGL((k_fit<true, false>), dim3(1, B), dim3(576), p.lds, st, d_edges);
+  return true;
 }
 
 hipError_t launch_fit_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int want_cov, unsigned parts) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   fit_predict_attrs();
-  if (!(parts & 1u)) {
-  } else if (bd.n_cap <= 128)
-    hipLaunchKernelGGL((k_fit<true, false>), dim3(1, B), dim3(576),
-                       ((size_t)bd.n_cap * (bd.n_cap | 1) + bd.n_cap) * sizeof(double), st, d_edges);
-  else
-    launch_fit_blocked(st, d_edges, B, bd);
-  const size_t plds = ((size_t)bd.n_cap * 64 + 3 * (size_t)bd.n_cap) * sizeof(double);
+  if ((parts & 1u) && !launch_fit_in_lds(st, d_edges, B, bd, false)) launch_fit_blocked(st, d_edges, B, bd);
+  const PredictPlan pp = predict_plan(bd, false);
   if (!(parts & 2u)) {
-  } else if (bd.n_cap > 128 && plds > 150 * 1024) {
+  } else if (pp.form == PredictForm::through_hbm) {
     // many training points: V through HBM, blocked substitution with the panel kernel of the structured path
     hipLaunchKernelGGL(k_kstar_build, dim3(cdiv(bd.Lg, 64), 64, B), dim3(256), 0, st, d_edges);
     hipLaunchKernelGGL(k_pred_colsum_big<false>, dim3(cdiv(bd.Lg, PB_COLS), B), dim3(PB_COLS * PB_LANES), 0, st, d_edges);
     for (int k0 = 0; k0 < bd.n_cap; k0 += CB)
       hipLaunchKernelGGL(k_vsolve_mfma, dim3(cdiv(bd.Lg, VS_COLS), B), dim3(256), 0, st, d_edges, k0);
     hipLaunchKernelGGL(k_pred_colsum_big<true>, dim3(cdiv(bd.Lg, PB_COLS), B), dim3(PB_COLS * PB_LANES), 0, st, d_edges);
-  } else if (plds <= 150 * 1024)
-    hipLaunchKernelGGL((k_predict<true, false>), dim3(cdiv(bd.Lg, 64), B), dim3(64), plds, st, d_edges, 0);
-  else
-    hipLaunchKernelGGL((k_predict<false, false>), dim3(cdiv(bd.Lg, 64), B), dim3(64), 0, st, d_edges, 0);
+  } else {
+    hipLaunchKernelGGL((k_predict<true, false>), dim3(cdiv(bd.Lg, 64), B), dim3(64), pp.lds, st, d_edges, 0);
+  }
   if (want_cov && (parts & 4u)) {
     const int t = cdiv(bd.Lg, 64);
     hipLaunchKernelGGL(k_cov_mfma, dim3(t, t, B), dim3(256), 0, st, d_edges, 0);
@@ -425,14 +299,11 @@ hipError_t launch_final_cov(hipStream_t st, EdgeDev* d_edges, int B, const Batch
 hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
   (void)hipGetLastError();
   fit_predict_attrs();
-  if (bd.n_cap <= 128)
-    hipLaunchKernelGGL((k_fit<true, true>), dim3(1, B), dim3(576),
-                       ((size_t)bd.n_cap * (bd.n_cap | 1) + bd.n_cap) * sizeof(double), st, d_edges);
-  else
+  if (!launch_fit_in_lds(st, d_edges, B, bd, true))
     hipLaunchKernelGGL((k_fit<false, true>), dim3(1, B), dim3(256), (size_t)bd.n_cap * sizeof(double), st, d_edges);
-  const size_t plds = ((size_t)bd.n_cap * 64 + 3 * (size_t)bd.n_cap) * sizeof(double);
-  if (plds <= 150 * 1024)
-    hipLaunchKernelGGL((k_predict<true, true>), dim3(cdiv(bd.Lg, 64), B), dim3(64), plds, st, d_edges, bd.Lg);
+  const PredictPlan pp = predict_plan(bd, true);
+  if (pp.form == PredictForm::lds)
+    hipLaunchKernelGGL((k_predict<true, true>), dim3(cdiv(bd.Lg, 64), B), dim3(64), pp.lds, st, d_edges, bd.Lg);
   else
     hipLaunchKernelGGL((k_predict<false, true>), dim3(cdiv(bd.Lg, 64), B), dim3(64), 0, st, d_edges, bd.Lg);
   return hipGetLastError();
@@ -442,16 +313,16 @@ static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int ran
   const int mm = (rank_max + 1) & ~1;
   static PerDeviceOnce once;
   if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
 #define GPET_JS_ATTR(NU_, LOGW_) \
-  (void)hipFuncSetAttribute((const void*)k_jacobi_seat<NU_, LOGW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
+  (void)hipFuncSetAttribute((const void*)k_jacobi_seat<NU_, LOGW_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX)
     GPET_JS_ATTR(2, true); GPET_JS_ATTR(3, true);
     GPET_JS_ATTR(2, false); GPET_JS_ATTR(3, false);
 #undef GPET_JS_ATTR
 #define GPET_JA_ATTR(NU_, LOGW_, RR_, NT_) \
-  (void)hipFuncSetAttribute((const void*)k_jacobi_ahead<NU_, LOGW_, RR_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)
+  (void)hipFuncSetAttribute((const void*)k_jacobi_ahead<NU_, LOGW_, RR_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX)
     GPET_JA_ATTR(2, true, 0, JA_NT_LOG); GPET_JA_ATTR(3, true, 0, JA_NT_LOG);
     GPET_JA_ATTR(3, false, 0, JS_NT); GPET_JA_ATTR(2, false, 6, JS_NT);
 #undef GPET_JA_ATTR
@@ -529,21 +400,15 @@ hipError_t launch_factor(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
 // structured loop path: fit -> (U, H, mean) -> Jacobi (the LDS kernel, on E.C) -> factor rows
 hipError_t launch_struct_iteration(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts) {
   (void)hipGetLastError();
-  fit_predict_attrs();
   static PerDeviceOnce once;
   if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)k_struct_H, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_struct_rows<5, 20>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_struct_rows<6, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_struct_H, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    (void)hipFuncSetAttribute((const void*)k_struct_rows<5, 20>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    (void)hipFuncSetAttribute((const void*)k_struct_rows<6, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
   }
-  if (!(parts & 1u)) {
-  } else if (bd.n_cap <= 128)
-    hipLaunchKernelGGL((k_fit<true, false>), dim3(1, B), dim3(576),
-                       ((size_t)bd.n_cap * (bd.n_cap | 1) + bd.n_cap) * sizeof(double), st, d_edges);
-  else  // (more possible training points than K fits LDS for: blocked factorisation in HBM)
-    launch_fit_blocked(st, d_edges, B, bd);
-  if ((parts & 2u) && bd.n_cap > 128) {
-    // many training points: U through HBM, blocked substitution
+  if ((parts & 1u) && !launch_fit_in_lds(st, d_edges, B, bd, false)) launch_fit_blocked(st, d_edges, B, bd);
+  if ((parts & 2u) && !fit_plan(bd).in_lds) {
+    // many training points (the blocked fit): U through HBM, blocked substitution
     hipLaunchKernelGGL(k_structB_build, dim3(64, B), dim3(256), 0, st, d_edges);
     hipLaunchKernelGGL(k_struct_beta, dim3(1, B), dim3(128), 0, st, d_edges);
     const int cgroups = cdiv(bd.r0_max, SB_COLS);
@@ -553,25 +418,16 @@ hipError_t launch_struct_iteration(hipStream_t st, EdgeDev* d_edges, int B, cons
     hipLaunchKernelGGL(k_struct_Hbig, dim3(t16, t16, B), dim3(256), 0, st, d_edges);
     hipLaunchKernelGGL(k_struct_mean, dim3(cdiv(bd.Lg, 256), B), dim3(256), 0, st, d_edges);
   } else if (parts & 2u) {
-    const size_t full = ((size_t)bd.n_cap * (bd.r0_max | 1) + (size_t)bd.n_cap * (bd.n_cap + 1) / 2 + bd.r_cap) * sizeof(double);
-    const size_t rowm = ((size_t)bd.n_cap * (bd.r0_max | 1) + bd.n_cap + bd.r_cap) * sizeof(double);
-    const int l_in_lds = full <= (size_t)STRUCT_H_LDS_MAX ? 1 : 0;  // (gpet_batch_create checked that `rowm` fits)
-    hipLaunchKernelGGL(k_struct_H, dim3(1, B), dim3(1024), l_in_lds ? full : rowm, st, d_edges, l_in_lds);
+    const StructHPlan hp = struct_h_plan(bd);
+    hipLaunchKernelGGL(k_struct_H, dim3(1, B), dim3(1024), hp.lds, st, d_edges, hp.l_in_lds ? 1 : 0);
   }
   if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r0_max > 0 ? bd.r0_max : bd.r_cap, 1, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0);
   if (parts & 8u) {
-    // the variant k_struct_rows picks for r0_max: [4 KS][16 MT + 1] eigenvector tile
-    const int rm = bd.r0_max;
-    const int mt = rm <= 32 ? 2 : rm <= 48 ? 3 : rm <= 64 ? 4 : rm <= 80 ? 5 : 6;
-    const int ks = rm <= 32 ? 8 : rm <= 48 ? 12 : rm <= 64 ? 16 : rm <= 72 ? 18 : rm <= 80 ? 20 : 24;
-    const size_t lds = ((size_t)4 * ks * (16 * mt + 1) + 16 * mt) * sizeof(double);  // (+ the signs of the rows)
-    const dim3 grid(cdiv(bd.Lg, SR_TJ), B);
-    if (rm <= 32) hipLaunchKernelGGL((k_struct_rows<2, 8>), grid, dim3(256), lds, st, d_edges);
-    else if (rm <= 48) hipLaunchKernelGGL((k_struct_rows<3, 12>), grid, dim3(256), lds, st, d_edges);
-    else if (rm <= 64) hipLaunchKernelGGL((k_struct_rows<4, 16>), grid, dim3(256), lds, st, d_edges);
-    else if (rm <= 72) hipLaunchKernelGGL((k_struct_rows<5, 18>), grid, dim3(256), lds, st, d_edges);
-    else if (rm <= 80) hipLaunchKernelGGL((k_struct_rows<5, 20>), grid, dim3(256), lds, st, d_edges);
-    else hipLaunchKernelGGL((k_struct_rows<6, 24>), grid, dim3(256), lds, st, d_edges);
+    const StructRowsPlan rp = struct_rows_plan(bd, B);
+    for_k_extent(rp.ks, [&](auto ks) {
+      constexpr int KS = decltype(ks)::value;
+      hipLaunchKernelGGL((k_struct_rows<k_extent(4 * KS).mt, KS>), dim3_of(rp.grid), dim3(256), rp.lds, st, d_edges);
+    });
   }
   return hipGetLastError();
 }
@@ -588,51 +444,7 @@ hipError_t launch_struct_basis(hipStream_t st, EdgeDev* d_edges, int B, const Ba
   return launch_set_force(st, d_edges, B, 0);
 }
 
-// ---- opt-in counter-based normals (SURVEY K5 "fast Philox mode"; gpet_batch_set_rng) ---------------------------------
-// Philox4x32-10 (Salmon, Moraes, Dror & Shaw, SC'11; the Random123 known-answer vectors are in the tests) + Box-Muller.
-// The normal of (sample row s, column j) is a pure function of (seed of the iteration, s, j): counter = (j / 2, s, 0, 0),
-// key = (seed, "Phlx"); its four words give two 53-bit uniforms u1, u2 in (0, 1) and the pair
-// sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2) for columns j, j + 1.  No stream to walk: every thread writes its own pair, and
-// only the columns the factor multiplies are generated at all.  NOT the reference's numbers (sklearn_gpr.py:464 draws from
-// RandomState(seed)): a mode of its own with its own CPU twin in the tests (philox_standard_normal), never the default.
-__device__ __forceinline__ void philox4x32_10(unsigned int c[4], unsigned int k0, unsigned int k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (unsigned int)p1;
-    c[3] = (unsigned int)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-__global__ void __launch_bounds__(256) k_philox_normals(EdgeDev* edges, const unsigned int* seeds, int add_iter, int iter_abs,
-                                                        int z_store) {
-  const EdgeDev E = edges[blockIdx.z];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  const int iter_idx = (iter_abs >= 0 ? iter_abs : sc->iter) + (int)blockIdx.y;
-  double* __restrict__ Zs = E.Z + (size_t)(iter_idx % E.z_ring) * ((size_t)E.S * E.z_cols);
-  const int zc = E.z_cols, zs = (z_store > 0 && z_store < zc) ? z_store : zc;
-  const int hp = (zs + 1) >> 1;  // column pairs per row
-  const unsigned int key = seeds[blockIdx.z] + (add_iter ? (unsigned int)(iter_idx + 1) : 0u);  // (the loop's seed rule, gpet.py:839)
-  const long long total = (long long)E.S * hp;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-    const int srow = (int)(e / hp), jp = (int)(e - (long long)srow * hp);
-    unsigned int c[4] = {(unsigned int)jp, (unsigned int)srow, 0u, 0u};
-    philox4x32_10(c, key, 0x50686c78u);
-    const double u1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-    const double r = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincospi(2.0 * u2, &sn, &cs);
-    double* o = Zs + (size_t)srow * zc + 2 * jp;
-    o[0] = r * cs;
-    if (2 * jp + 1 < zs) o[1] = r * sn;
-  }
-}
+// opt-in counter-based normals (k_philox_normals, gpet_k_rng.inc; gpet_batch_set_rng)
 hipError_t launch_normals_philox(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, const unsigned int* d_seeds, int add_iter,
                                  int iter_abs, int n_ahead, int z_store) {
   (void)hipGetLastError();
@@ -658,10 +470,9 @@ hipError_t launch_kde(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& 
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (mode == 0) {
     // per-iteration path: one prep kernel + one fused bin/convolve kernel + normalise
-    const size_t lds = ((size_t)(KDE_TX + 8) * ((KDE_H + 8) | 1) + (size_t)KDE_NB * (KDE_TX + 8) + KDE_NB) * sizeof(double);
+    const KdeFusedPlan kp = kde_fused_plan(bd, B);
     if (parts & 1u) hipLaunchKernelGGL(k_kde_prep, dim3(1, B), dim3(1024), 0, st, d_edges);
-    if (parts & 2u)
-      hipLaunchKernelGGL(k_kde_fused, dim3(cdiv(bd.N, KDE_TX), B), dim3(KDE_THREADS), lds, st, d_edges, raw_band);
+    if (parts & 2u) hipLaunchKernelGGL(k_kde_fused, dim3_of(kp.grid), dim3(KDE_THREADS), kp.lds, st, d_edges, raw_band);
     if ((parts & 4u) && !raw_band) hipLaunchKernelGGL(k_kde_normalise, dim3(64, B), dim3(256), 0, st, d_edges, mode);
     return hipGetLastError();
   }
@@ -672,14 +483,6 @@ hipError_t launch_kde(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& 
   hipLaunchKernelGGL(k_kde_conv_x, dim3(cdiv(bd.M, KCX_T), cdiv(bd.N, KCX_T), B), dim3(256), 0, st, d_edges, mode);
   hipLaunchKernelGGL(k_kde_normalise, dim3(64, B), dim3(256), 0, st, d_edges, mode);
   return hipGetLastError();
-}
-
-__global__ void __launch_bounds__(256) k_pix_reset(EdgeDev* edges) {
-  const EdgeDev E = edges[blockIdx.y];
-  for (int i = threadIdx.x; i < E.n_bins; i += blockDim.x) {
-    E.binbest[i] = 0ull;
-    E.binarg[i] = 0x7FFFFFFFFFFFFFFFll;
-  }
 }
 
 __global__ void k_set_force(EdgeDev* edges, int v) { edges[blockIdx.x].sc->force = v; }
@@ -732,117 +535,62 @@ hipError_t launch_pixels_reset(hipStream_t st, EdgeDev* d_edges, int B, const Ba
 
 hipError_t launch_pixels(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int raw_band, unsigned parts) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (parts & 1u) hipLaunchKernelGGL(k_pix_columns, dim3(cdiv(bd.N, PIX_CX), B), dim3(256), 0, st, d_edges, raw_band);
-  const int nt = bd.N > bd.obs_cap ? bd.N : bd.obs_cap;
-  if (parts & 2u) hipLaunchKernelGGL(k_pix_old, dim3(cdiv(bd.obs_cap, 256), B), dim3(256), 0, st, d_edges, raw_band);
-  if (parts & 4u) hipLaunchKernelGGL(k_pix_argbest, dim3(cdiv(nt, 256), B), dim3(256), 0, st, d_edges, raw_band);
-  if (parts & 8u) hipLaunchKernelGGL(k_pix_select, dim3(1, B), dim3(64), 0, st, d_edges);
+  const PixelPlan pp = pixel_plan(bd, B);
+  if (parts & 1u) hipLaunchKernelGGL(k_pix_columns, dim3_of(pp.columns), dim3(256), 0, st, d_edges, raw_band);
+  if (parts & 2u) hipLaunchKernelGGL(k_pix_old, dim3_of(pp.old), dim3(256), 0, st, d_edges, raw_band);
+  if (parts & 4u) hipLaunchKernelGGL(k_pix_argbest, dim3_of(pp.argbest), dim3(256), 0, st, d_edges, raw_band);
+  if (parts & 8u) hipLaunchKernelGGL(k_pix_select, dim3_of(pp.select), dim3(64), 0, st, d_edges);
   return hipGetLastError();
 }
 
-// The sample GEMM on the f32 matrix cores (bd.y_arith, gpet_batch_set_sample_arith): the capacity rules of the f64 family below --
-// GEMM_KMAX, the KS ladder, the column runs ncs -- with one kernel per K extent (every extent fits two workgroups per CU).  The
-// register form keeps the posterior mean in LDS; an edge too wide for that (about 15 000 columns) takes the generic form.
-static void launch_sample_f32(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int rank_max) {
-  const size_t lds_top = ((size_t)4 * 24 * GEMM32_LDA) * sizeof(float) + ((size_t)bd.Lg + 64) * sizeof(double);
-  if (bd.r_cap <= GEMM_KMAX && bd.a_rows_cap <= GEMM_KMAX && lds_top <= (size_t)GEMM_LDS_MAX) {
-    const int rm = rank_max > 0 && rank_max <= bd.r_cap ? rank_max : (bd.r_cap > bd.a_rows_cap ? bd.r_cap : bd.a_rows_cap);
-    const int ks = (rm + 3) >> 2;
-    const int rparts = cdiv(bd.S, 128), ctiles = cdiv(bd.Lg, 64);
-    int ncs = cdiv(256, B * rparts);
-    ncs = ncs > ctiles ? ctiles : (ncs < 1 ? 1 : ncs);
-    if (ncs > 8) ncs = 8;
-    const dim3 grid(rparts * ncs, B), block(512);
-    {  // (the chunk plus the posterior mean of a wide edge exceed the 64 KB a kernel gets without asking)
-      static PerDeviceOnce once;
-      if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<8>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<12>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<16>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<18>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<20>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)k_sample_f32_r<24>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
-      }
-    }
-#define GPET_GEMM32_LAUNCH(KS_)                                                                                     \
-  hipLaunchKernelGGL((k_sample_f32_r<KS_>), grid, block,                                                            \
-                     ((size_t)4 * KS_ * GEMM32_LDA) * sizeof(float) + ((size_t)bd.Lg + 64) * sizeof(double), st, d_edges, ncs)
-    if (ks <= 8) GPET_GEMM32_LAUNCH(8);
-    else if (ks <= 12) GPET_GEMM32_LAUNCH(12);
-    else if (ks <= 16) GPET_GEMM32_LAUNCH(16);
-    else if (ks <= 18) GPET_GEMM32_LAUNCH(18);
-    else if (ks <= 20) GPET_GEMM32_LAUNCH(20);
-    else GPET_GEMM32_LAUNCH(24);
-#undef GPET_GEMM32_LAUNCH
-  } else {
-    hipLaunchKernelGGL(k_sample_f32, dim3(cdiv(bd.Lg, 64), cdiv(bd.S, 64), B), dim3(256), 0, st, d_edges);
-  }
+// The sample GEMM (sample_plan, gpet_iter_plan.h): f64 matrix cores, or the f32 ones (bd.y_arith, gpet_batch_set_sample_arith; with it
+// off everything is enqueued as before).  The f64 register form has an instance per (K extent, f32 samples, mean in LDS), KS 20 and 24
+// in the one-workgroup-per-CU kernel _rl; the f32 one an instance per K extent (every extent fits two workgroups per CU).
+template <int KS, bool F32, bool MU_LDS>
+static const void* sample_gemm_kernel() {
+  if constexpr (KS >= 20) return (const void*)k_sample_gemm_mfma_rl<KS, F32, MU_LDS>;
+  else return (const void*)k_sample_gemm_mfma_r<KS, F32, MU_LDS>;
 }
-
 hipError_t launch_sample(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int rank_max) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (bd.y_arith) {  // (opt-in; with it off everything below is enqueued as before)
-    launch_sample_f32(st, d_edges, B, bd, rank_max);
+  const bool f32mma = bd.y_arith != 0;
+  const SamplePlan p = sample_plan(bd, B, rank_max, f32mma);
+  if (!p.reg) {
+    if (f32mma) hipLaunchKernelGGL(k_sample_f32, dim3_of(p.grid), dim3(p.block), 0, st, d_edges);
+    else hipLaunchKernelGGL(k_sample_gemm_mfma, dim3_of(p.grid), dim3(p.block), 0, st, d_edges);
     return hipGetLastError();
   }
-  // rank <= 96 everywhere in the batch (factor capacity): Z rows stay in registers; otherwise
-  // (full factors injected by tests, Matern ranks) the K-chunked kernel.  rank_max: the largest rank any
-  // edge can have in this launch (r0_max inside the structured loop, else the factor capacity).
-  if (bd.r_cap <= GEMM_KMAX && bd.a_rows_cap <= GEMM_KMAX) {
-    const int rm = rank_max > 0 && rank_max <= bd.r_cap ? rank_max : (bd.r_cap > bd.a_rows_cap ? bd.r_cap : bd.a_rows_cap);
-    const int ks = (rm + 3) >> 2;
-    // column runs per row block: while the row blocks alone leave CUs empty (small batches are latency chains)
-    const int rparts = cdiv(bd.S, 128), ctiles = cdiv(bd.Lg, 64);
-    int ncs = cdiv(256, B * rparts);
-    ncs = ncs > ctiles ? ctiles : (ncs < 1 ? 1 : ncs);
-    if (ncs > 8) ncs = 8;
-    const dim3 grid(rparts * ncs, B), block(512);
-    {  // (the chunk plus the posterior mean of a wide edge exceed the 64 KB a kernel gets without asking: 66 KB at K = 96, Lg = 2048)
-      static PerDeviceOnce once;
-      if (once.first()) {
-#define GPET_GEMM_ATTR(KERNEL, KS_)                                                                                       \
-  (void)hipFuncSetAttribute((const void*)KERNEL<KS_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);  \
-  (void)hipFuncSetAttribute((const void*)KERNEL<KS_, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);   \
-  (void)hipFuncSetAttribute((const void*)KERNEL<KS_, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX); \
-  (void)hipFuncSetAttribute((const void*)KERNEL<KS_, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX)
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_r, 8);
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_r, 12);
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_r, 16);
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_r, 18);
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_rl, 20);
-        GPET_GEMM_ATTR(k_sample_gemm_mfma_rl, 24);
-#undef GPET_GEMM_ATTR
-      }
-    }
-    // (an edge too wide for its posterior mean to sit behind the chunk reads it from global memory in the epilogue)
-    const int mu_in_lds = ((size_t)4 * 24 * GEMM_LDA + bd.Lg + 64) * sizeof(double) <= (size_t)GEMM_LDS_MAX ? 1 : 0;
-#define GPET_GEMM_LAUNCH(KERNEL, KS_)                                                                                                  \
-  do {                                                                                                                                 \
-    const size_t lds_ = ((size_t)4 * KS_ * GEMM_LDA + (mu_in_lds ? bd.Lg + 64 : 0)) * sizeof(double);                                         \
-    if (bd.y_f32 && mu_in_lds) hipLaunchKernelGGL((KERNEL<KS_, true, true>), grid, block, lds_, st, d_edges, ncs);                        \
-    else if (bd.y_f32) hipLaunchKernelGGL((KERNEL<KS_, true, false>), grid, block, lds_, st, d_edges, ncs);                               \
-    else if (mu_in_lds) hipLaunchKernelGGL((KERNEL<KS_, false, true>), grid, block, lds_, st, d_edges, ncs);                              \
-    else hipLaunchKernelGGL((KERNEL<KS_, false, false>), grid, block, lds_, st, d_edges, ncs);                                            \
-  } while (0)
-    if (ks <= 8) GPET_GEMM_LAUNCH(k_sample_gemm_mfma_r, 8);
-    else if (ks <= 12) GPET_GEMM_LAUNCH(k_sample_gemm_mfma_r, 12);
-    else if (ks <= 16) GPET_GEMM_LAUNCH(k_sample_gemm_mfma_r, 16);
-    else if (ks <= 18) GPET_GEMM_LAUNCH(k_sample_gemm_mfma_r, 18);
-    else if (ks <= 20) GPET_GEMM_LAUNCH(k_sample_gemm_mfma_rl, 20);
-    else GPET_GEMM_LAUNCH(k_sample_gemm_mfma_rl, 24);
-#undef GPET_GEMM_LAUNCH
-  } else {
-    hipLaunchKernelGGL(k_sample_gemm_mfma, dim3(cdiv(bd.Lg, 64), cdiv(bd.S, 64), B), dim3(256), 0, st, d_edges);
-  }
+  // (the chunk plus the posterior mean of a wide edge exceed the 64 KB a kernel gets without asking: 66 KB at K = 96, Lg = 2048)
+  static PerDeviceOnce once[2];
+  if (once[f32mma].first())
+    for (const int ks_ : K_EXTENTS)
+      for_k_extent(ks_, [&](auto ks) {
+        constexpr int KS = decltype(ks)::value;
+        if (f32mma) {
+          (void)hipFuncSetAttribute((const void*)k_sample_f32_r<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        } else {
+          (void)hipFuncSetAttribute(sample_gemm_kernel<KS, false, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+          (void)hipFuncSetAttribute(sample_gemm_kernel<KS, true, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+          (void)hipFuncSetAttribute(sample_gemm_kernel<KS, false, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+          (void)hipFuncSetAttribute(sample_gemm_kernel<KS, true, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_MAX);
+        }
+      });
+  void* args[] = {(void*)&d_edges, (void*)&p.ncs};
+  for_k_extent(p.ks, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    const void* k = f32mma                     ? (const void*)k_sample_f32_r<KS>
+                    : p.y_f32 && p.mu_in_lds ? sample_gemm_kernel<KS, true, true>()
+                    : p.y_f32                ? sample_gemm_kernel<KS, true, false>()
+                    : p.mu_in_lds            ? sample_gemm_kernel<KS, false, true>()
+                                             : sample_gemm_kernel<KS, false, false>();
+    (void)hipLaunchKernel(k, dim3_of(p.grid), dim3(p.block), args, p.lds, st);
+  });
   return hipGetLastError();
 }
 
 // the loop's scoring + curve KDE of a small batch with k_score_combine, k_topk_sort and k_kde_prep as ONE launch (k_score_tail);
 // false: the shape does not allow it (the caller enqueues launch_score + launch_kde)
-bool score_tail_applies(const BatchDims& bd) {
-  const size_t lds = (size_t)(2 * SC_PAIRS + 2) * (bd.M | 1) * sizeof(float);
-  return lds <= 150 * 1024 && bd.S >= 64 && bd.S <= 1024 && bd.n_keep <= KDE_PREP_MAXB && !opt(Opt::topk_rank);
-}
+bool score_tail_applies(const BatchDims& bd) { return score_tail_applies(bd, opt(Opt::topk_rank)); }
 hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
   hipError_t e = launch_score(st, d_edges, B, bd, 1u, true);  // (the tiles only, their partial sums left for k_score_tail)
   if (e != hipSuccess) return e;
@@ -854,24 +602,19 @@ hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, 
 // launch_final_costs).  Which kernels run is decided by the BATCH's shape, bd, whatever S is: a row's cost does not depend on S
 hipError_t launch_score_rows(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int S, bool no_combine) {
   (void)hipGetLastError();
-  const size_t lds = (size_t)(2 * SC_PAIRS + 2) * (bd.M | 1) * sizeof(float);
-  if (lds <= 150 * 1024 && B * 1 > 0 && bd.S >= 64) {
+  const ScorePlan p = score_plan(bd, B, S);
+  if (p.tiled) {
     static PerDeviceOnce once;
-    if (once.first())
-    {
-      (void)hipFuncSetAttribute((const void*)k_score_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_score_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (once.first()) {
+      (void)hipFuncSetAttribute((const void*)k_score_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+      (void)hipFuncSetAttribute((const void*)k_score_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
     }
-    const int n_tiles = cdiv((bd.Lg - 2) / 2, SC_PAIRS);
-    // curves per workgroup: 1024, or down to 128 while the tiles alone leave CUs empty (every part stages the slab again)
-    int cpw = SC_CURVES;
-    while (cpw > 128 && B * n_tiles * cdiv(S, cpw) < 256) cpw >>= 1;
-    if (bd.y_f32) hipLaunchKernelGGL(k_score_tile<true>, dim3(n_tiles, cdiv(S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
-    else hipLaunchKernelGGL(k_score_tile<false>, dim3(n_tiles, cdiv(S, cpw), B), dim3(SC_THREADS), lds, st, d_edges, cpw);
-    if (!no_combine) hipLaunchKernelGGL(k_score_combine, dim3(cdiv(S, 256), B), dim3(256), 0, st, d_edges, n_tiles);
+    if (bd.y_f32) hipLaunchKernelGGL(k_score_tile<true>, dim3_of(p.tile_grid), dim3(SC_THREADS), p.lds, st, d_edges, p.cpw);
+    else hipLaunchKernelGGL(k_score_tile<false>, dim3_of(p.tile_grid), dim3(SC_THREADS), p.lds, st, d_edges, p.cpw);
+    if (!no_combine) hipLaunchKernelGGL(k_score_combine, dim3_of(p.combine_grid), dim3(256), 0, st, d_edges);
   } else {
-    if (bd.y_f32) hipLaunchKernelGGL(k_score<true>, dim3(cdiv(S, 4), B), dim3(256), 0, st, d_edges);
-    else hipLaunchKernelGGL(k_score<false>, dim3(cdiv(S, 4), B), dim3(256), 0, st, d_edges);
+    if (bd.y_f32) hipLaunchKernelGGL(k_score<true>, dim3_of(p.wave_grid), dim3(256), 0, st, d_edges);
+    else hipLaunchKernelGGL(k_score<false>, dim3_of(p.wave_grid), dim3(256), 0, st, d_edges);
   }
   return hipGetLastError();
 }
@@ -881,7 +624,7 @@ hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims
   hipError_t e_rows = hipSuccess;
   if (parts & 1u) e_rows = launch_score_rows(st, d_edges, B, bd, bd.S, no_combine);
   if (parts & 2u) {
-    if (bd.S <= 1024 && !opt(Opt::topk_rank)) hipLaunchKernelGGL(k_topk_sort, dim3(1, B), dim3(512), 0, st, d_edges);
+    if (topk_bitonic(bd, opt(Opt::topk_rank))) hipLaunchKernelGGL(k_topk_sort, dim3(1, B), dim3(512), 0, st, d_edges);
     else hipLaunchKernelGGL(k_topk, dim3(cdiv(bd.S, 256), B), dim3(256), 0, st, d_edges);
   }
   const hipError_t e_top = hipGetLastError();

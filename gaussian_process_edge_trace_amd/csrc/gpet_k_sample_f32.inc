@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_sample_f32(EdgeDev* edges) {
 // Row stride of the chunk in LDS (floats): an operand read is a ds_read_b32, served in two groups of 32 lanes over 32 banks; a
 // group reads 16 consecutive floats of TWO k-rows (k = 4q + lq, lq = 0, 1 or 2, 3).  With 80 (= 16 mod 32) the two rows fall on
 // disjoint bank halves; 64 or 96 would put them on the same 16 banks, a 2-way conflict on every read.
-#define GEMM32_LDA 80
+// (GEMM32_LDA = 80: gpet_iter_plan.h)
 template <int KS>
 __device__ __forceinline__ void sample_f32_body(const EdgeDev& E, const gpet_scalars* sc, float* s_fb, int part, int cpart, int ncs) {
   const GPET_GLOBAL double* __restrict__ meang = as_global(E.mean);

@@ -89,14 +89,7 @@ __global__ void __launch_bounds__(256) k_sample_gemm_mfma(EdgeDev* edges) {
 // stores 1.56 ms, and the stores with 1/18 of the MFMAs still 1.51 ms (2.7 TB/s; 2.85 TB/s with 512-byte runs per
 // instruction).  Measured slower or equal, and dropped: streaming (nontemporal) stores (+35 %), the chunk by LDS-DMA
 // with four 4-wave workgroups per CU (+8 %), a half-tile phase offset between the workgroups of a CU (+-0).
-#define GEMM_KMAX 96
-// row stride of the factor chunk in LDS (doubles): the operand read of a matrix instruction takes 16 consecutive columns of
-// FOUR rows (k = 4 q + lq); with 80 (= 32 dwords mod 64) the rows of each half-wave fall on disjoint bank halves -- 65 put
-// rows 2 banks apart and every read was a 2-way conflict
-#ifndef GEMM_LDA
-#define GEMM_LDA 80
-#endif
-#define GEMM_LDS_MAX (150 * 1024)
+// (GEMM_KMAX, the chunk's row stride GEMM_LDA and GEMM_LDS_MAX: gpet_iter_plan.h)
 // MU_LDS (the posterior mean behind the chunk in LDS) is a COMPILE-TIME switch: as a run-time one the mean had two producers --
 // an LDS read and a global load into the same registers -- and at their join the compiler waits for BOTH counters: every
 // store of a column group then waited (vmcnt(0)) for all the stores before it.
@@ -439,9 +432,7 @@ __global__ void __launch_bounds__(256) k_score(EdgeDev* edges) {
 // 16 consecutive lanes share a curve: one coalesced 256-byte read of its samples, successor data
 // by shuffle inside the group, group reduction by shuffle, and one (arc, integral) partial per
 // (tile, curve); k_score_combine adds the partials in tile order (deterministic) and divides.
-#define SC_PAIRS 15  // Simpson pairs per tile: 8 lanes x 2 pairs per curve; the sixteenth pair (= the next tile's first) only supplies data
-#define SC_CURVES 1024
-#define SC_THREADS 1024
+// (SC_PAIRS = 15 Simpson pairs per tile, SC_CURVES, SC_THREADS: gpet_iter_plan.h)
 // cross-lane moves of a double inside rows of 16 lanes by DPP (two v_mov_b32_dpp; __shfl_xor / __shfl_down with width 16
 // go through ds_bpermute and recompute the lane index every time): CTRL = row_ror:8 / row_ror:4 / quad_perm for the
 // butterfly, row_shl:1 for "the lane above" (lane 15 of a row has no source and reads 0: its callers replace the value)
@@ -596,13 +587,8 @@ __global__ void __launch_bounds__(SC_THREADS) __attribute__((amdgpu_waves_per_eu
   }
 }
 
-__global__ void __launch_bounds__(256) k_score_combine(EdgeDev* edges, int n_tiles) {
-  const EdgeDev E = edges[blockIdx.y];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= E.S) return;
-  (void)n_tiles;
+// the cost of sample s of a tiled launch: its partials added in tile order, the Simpson tail, the division (k_score_combine, k_score_tail)
+__device__ __forceinline__ double score_combine_one(const EdgeDev& E, int s) {
   const int my_tiles = ((E.Lg - 2) / 2 + SC_PAIRS - 1) / SC_PAIRS;  // this edge's own tile count
   double al = 0.0, li = 0.0;
   for (int t = 0; t < my_tiles; ++t) {
@@ -611,12 +597,42 @@ __global__ void __launch_bounds__(256) k_score_combine(EdgeDev* edges, int n_til
   }
   if (E.y_f32) simpson_tail(E, reinterpret_cast<const float*>(E.Y) + (size_t)s * E.Yp, al, li);
   else simpson_tail(E, E.Y + (size_t)s * E.Yp, al, li);
-  E.costs[s] = al / li;
+  return al / li;
+}
+__global__ void __launch_bounds__(256) k_score_combine(EdgeDev* edges) {
+  const EdgeDev E = edges[blockIdx.y];
+  const gpet_scalars* sc = E.sc;
+  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= E.S) return;
+  E.costs[s] = score_combine_one(E, s);
 }
 
 // argsort(costs)[:n_keep] for S <= 1024 by a bitonic sort of (cost, index) in LDS: 55 compare-exchange steps of 512
 // pairs instead of S^2 comparisons (rank counting, below: 0.20 ms per 1 024 edges).  Equal costs keep index order (the
 // index is the second key); -0.0 and +0.0 compare equal, as `<` on doubles has it.
+// the sort itself, (cost, index) ascending over all 1024 entries: 512 compare-exchange pairs per step, one per thread tid < 512.
+// ALL_PAIR: the workgroup has exactly those 512 threads (else the others only keep the barriers company).  Entered after a barrier.
+template <bool ALL_PAIR>
+__device__ __forceinline__ void bitonic_sort_1024(double* s_k, int* s_i, int tid) {
+  for (int k = 2; k <= 1024; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (ALL_PAIR || tid < 512) {
+        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
+        const double a = s_k[i], b = s_k[l];
+        const int ia = s_i[i], ib = s_i[l];
+        const bool a_first = (a < b) || (a == b && ia < ib);
+        const bool up = (i & k) == 0;
+        if (a_first != up) {
+          s_k[i] = b;
+          s_k[l] = a;
+          s_i[i] = ib;
+          s_i[l] = ia;
+        }
+      }
+      __syncthreads();
+    }
+}
 __global__ void __launch_bounds__(512) k_topk_sort(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.y];
   const gpet_scalars* sc = E.sc;
@@ -629,21 +645,7 @@ __global__ void __launch_bounds__(512) k_topk_sort(EdgeDev* edges) {
     s_i[e] = e;
   }
   __syncthreads();
-  for (int k = 2; k <= 1024; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
-      const double a = s_k[i], b = s_k[l];
-      const int ia = s_i[i], ib = s_i[l];
-      const bool a_first = (a < b) || (a == b && ia < ib);
-      const bool up = (i & k) == 0;
-      if (a_first != up) {
-        s_k[i] = b;
-        s_k[l] = a;
-        s_i[i] = ib;
-        s_i[l] = ia;
-      }
-      __syncthreads();
-    }
+  bitonic_sort_1024<true>(s_k, s_i, tid);
   for (int b = tid; b < E.n_keep; b += 512) {
     E.best_idx[b] = s_i[b];
     E.best_costs[b] = s_k[b];

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gpet_batch_plan.h"  // EdgeDev (gpet_dev.h), BatchDims, STRUCT_H_LDS_MAX
+#include "gpet_iter_plan.h"   // one loop iteration: kernel variant, grid and LDS of every step; the tile constants
 #include "gpet_conv_plan.h"   // pixel types, conv geometry, staging plan
 #include "gpet_conv_multi_plan.h"  // slot table of a multi-kernel source: validation, union patch, slots of each frame
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
@@ -133,7 +134,7 @@ hipError_t launch_sample(hipStream_t st, EdgeDev* d_edges, int B, const BatchDim
 hipError_t launch_score(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts = ~0u, bool no_combine = false);
 // part 1 of launch_score (the costs) over the first S rows of every edge's sample matrix, by the variant bd selects (launch_score: S = bd.S)
 hipError_t launch_score_rows(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int S, bool no_combine);
-bool score_tail_applies(const BatchDims& bd);
+bool score_tail_applies(const BatchDims& bd);  // (gpet_iter_plan.h's rule with the option topk_rank)
 // seed ensembles (gpet_k_ensemble.inc).  Final costs: the scorer on a one-row view of every edge's converged mean -- view / view_sc
 // [B], rows [B][row_stride] doubles (row_stride >= the widest row pitch), part [B][fincost_part_stride] doubles, cost [B]
 size_t fincost_part_stride(const BatchDims& bd);

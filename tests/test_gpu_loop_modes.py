@@ -52,3 +52,32 @@ def test_loop_modes_give_the_default_bits(run_trace, B, options):
     for e in range(B):
         assert np.array_equal(obs[e], obs0[e]), "observations of edge %d" % e
         assert np.array_equal(traces[e], traces0[e]), "trace of edge %d" % e
+
+
+def test_fused_tail_gives_the_three_kernels_bits(golden):
+    """k_score_tail against k_score_combine + k_topk_sort + k_kde_prep to the last bit of what they compute: two edges, every
+    history record of the loop (the cases above compare the integer observations and the traces only)."""
+    import gaussian_process_edge_trace_amd as amd
+    g = golden("stage_rbf500")
+    kw = dict(CTOR["stage_rbf500"])
+    kw.pop("seed")
+    ctx = amd._lib.Context(0)
+    runs = []
+    for fused in (0, 1):
+        tr = amd.GP_Edge_Tracing_Batch([g["in_init"]] * 2, g["ref_grad"], seeds=[3, 10], **kw, history="curves", _ctx=ctx)
+        try:
+            assert tr._batch.set_option("loop_fused_tail", fused) == -1
+            traces = [np.asarray(t) for t in tr()]
+            runs.append((list(tr.timings["iters"]), traces, tr.history()))
+        finally:
+            tr._batch.close()
+    (iters0, traces0, hist0), (iters1, traces1, hist1) = runs
+    assert iters0 == iters1 and min(iters0) >= 2
+    for e in range(2):
+        h0, h1 = hist0[e], hist1[e]
+        assert h0["n_iter"] == h1["n_iter"] == iters0[e] and h0["dropped"] == h1["dropped"] == 0
+        for k in ("optimal_cost", "best_idx", "n_removed", "score_thresh", "n_obs"):
+            assert h0[k].tobytes() == h1[k].tobytes() and len(h0[k]) == iters0[e], (e, k)
+        for i in range(iters0[e]):
+            assert h0["optimal_curves"][i].tobytes() == h1["optimal_curves"][i].tobytes(), (e, i)
+        assert traces0[e].tobytes() == traces1[e].tobytes(), e
