@@ -231,9 +231,13 @@ inline BatchBlocks layout_batch_slots(Carver& cv, EdgeDev* edges, int B, const B
     E.yt = cv.take<double>(nc);
     E.wt = cv.take<double>(nc);
     E.alpha = cv.take<double>(nc);
-    E.chol_inv = cv.take<double>(nc > 128 ? (nc / 64 + 1) * 4096 : 1);
-    E.solve_z = cv.take<double>(nc > 128 ? nc : 1);
-    E.solve_flag = cv.take<int>(nc > 128 ? 2 * (nc / 64 + 1) : 2);
+    // the scratch of the blocked fit (inverses of the diagonal blocks, the published solve vector, its flags), sized by the edge's
+    // own capacity but taken whenever the BATCH is blocked: fit_plan (gpet_iter_plan.h) decides by bd.n_cap, so the blocked kernels
+    // also run on an edge of 128 points or fewer that shares a batch with a larger one (and wrote past a one-element scratch)
+    const bool blocked = bd.n_cap > 128;
+    E.chol_inv = cv.take<double>(blocked ? (nc / 64 + 1) * 4096 : 1);
+    E.solve_z = cv.take<double>(blocked ? nc : 1);
+    E.solve_flag = cv.take<int>(blocked ? 2 * (nc / 64 + 1) : 2);
     E.K = cv.take<double>(nc * nc);
     E.V = cv.take<double>(nc * Lg);
     E.mean = cv.take<double>(Lg);

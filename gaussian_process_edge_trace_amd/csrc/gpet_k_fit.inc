@@ -1059,10 +1059,10 @@ __global__ void __launch_bounds__(256) k_kstar_build(EdgeDev* edges) {
 }
 // block k0 of V = L^-1 K_*^T for 32 columns of the grid per workgroup, on the matrix cores:
 //   X = K_*^T[k0.., cols] - sum_{j0 < k0} L[k0.., j0..] V[j0.., cols]   (64 x 64 by 64 x 32 products, left-looking),
-//   V[k0.., cols] = L_kk^-1 X   (the inverse of the diagonal block from k_chol_diag).
+//   V[k0.., cols] = L_kk^-1 X   (the inverse of the diagonal block from k_chol_diag, with one step of refinement).
 // Wave w owns rows 16 w .. 16 w + 15 of the block and both 16-column halves.
 #ifndef VS_COLS
-#define VS_COLS 16  // grid columns per workgroup (16, 32 or 64 by -DVS_COLS=..; at n = 1500, Lg = 2048: 3.42 / 3.62 / 4.09 ms per fit + predict + covariance)
+#define VS_COLS 16  // grid columns per workgroup (16, 32 or 64 by -DVS_COLS=..; at n = 1500, Lg = 2048: 3.42 / 3.62 / 4.09 ms per fit + predict + covariance, measured with the single product by the inverse, before the refinement step below)
 #endif
 #define VS_NH (VS_COLS / 16)          // 16-column halves per wave
 #define VS_PU (CB * VS_COLS / 256)    // prefetch registers of the V block per thread
@@ -1118,31 +1118,70 @@ __global__ void __launch_bounds__(256) k_vsolve_mfma(EdgeDev* edges, int k0) {
     }
   }
   __syncthreads();
-  // X = B - acc into sU (rows of the block beyond n: zero), the inverse into sL
+  // X = B - acc into sU (rows of the block beyond n: zero; a copy stays in registers), the inverse into sL
+  // (of a short last block only the leading nb x nb part of the inverse is taken: what the arena holds beyond it is not this
+  //  factorisation's, and would meet the zero rows of X and the zero columns of L_kk below as 0 * stale)
   const double* inv = E.chol_inv + (size_t)(k0 / CB) * CB * CB;
-  for (int e = tid; e < CB * CB; e += 256) sL[e >> 6][e & 63] = inv[e];
+  auto load_inverse = [&]() {
+    for (int e = tid; e < CB * CB; e += 256) sL[e >> 6][e & 63] = ((e >> 6) < nb && (e & 63) < nb) ? inv[e] : 0.0;
+  };
+  load_inverse();
+  double xr[VS_NH][4];
 #pragma unroll
   for (int h = 0; h < VS_NH; ++h)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
-      sU[i][a] = (i < nb && a0 + a < Lg) ? E.V[(size_t)(k0 + i) * Lg + a0 + a] - acc[h][g] : 0.0;
+      xr[h][g] = (i < nb && a0 + a < Lg) ? E.V[(size_t)(k0 + i) * Lg + a0 + a] - acc[h][g] : 0.0;
+      sU[i][a] = xr[h][g];
     }
   __syncthreads();
+  // V[k0.., cols] = L_kk^-1 X in three products on the matrix cores: v0 = Linv X, the residual r = X - L_kk v0, v = v0 + Linv r.
+  // The product with the explicit inverse ALONE (what this kernel did) is not a backward-stable solve: its error grows with the
+  // block's condition number, and on a training set with only the jitter on K's diagonal -- a point on every column of the edge --
+  // the covariance missed the componentwise bound of a substitution by a factor 2.6 (tests/test_gpu_posterior_injected.py).  One
+  // step of refinement with the residual formed from L_kk itself takes the inverse's error out to first order (Higham, Accuracy
+  // and Stability, ch. 12: fixed-precision refinement of an unstable solver).  Timed on an MI355X as 20 calls of
+  // gpet_gp_fit_predict without the covariance, one edge, n = 1500 training points, Lg = 2048, RBF: 2.49 ms with the single product,
+  // 2.69 ms with the refinement (8 us for each of the 24 launches); a substitution by groups of 16 lanes, 64 dependent steps per
+  // block, gave the same accuracy at 2.89 ms.
+  auto block_product = [&](v4f64c* out) {
 #pragma unroll
-  for (int h = 0; h < VS_NH; ++h) acc[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
+    for (int h = 0; h < VS_NH; ++h) out[h] = (v4f64c){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int kk = 0; kk < CB; kk += 4) {
-    const double a = sL[16 * w + li][kk + lq];
+    for (int kk = 0; kk < CB; kk += 4) {
+      const double a = sL[16 * w + li][kk + lq];
 #pragma unroll
-    for (int h = 0; h < VS_NH; ++h) acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], acc[h], 0, 0, 0);
+      for (int h = 0; h < VS_NH; ++h) out[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sU[kk + lq][16 * h + li], out[h], 0, 0, 0);
+    }
+  };
+  auto to_sU = [&](const v4f64c* src, bool residual) {  // sU <- src, or <- X - src
+#pragma unroll
+    for (int h = 0; h < VS_NH; ++h)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) sU[16 * w + lq + 4 * g][16 * h + li] = residual ? xr[h][g] - src[h][g] : src[h][g];
+  };
+  v4f64c v0[VS_NH], t[VS_NH];
+  block_product(v0);  // v0 = Linv X
+  __syncthreads();
+  to_sU(v0, false);
+  for (int e = tid; e < CB * CB; e += 256) {  // L_kk (zero above the diagonal and beyond a short last block, as the inverse and v0 are)
+    const int i = e >> 6, c = e & 63;
+    sL[i][c] = (i < nb && c <= i) ? E.K[(size_t)(k0 + i) * ld + k0 + c] : 0.0;
   }
+  __syncthreads();
+  block_product(t);  // L_kk v0
+  __syncthreads();
+  to_sU(t, true);    // r = X - L_kk v0
+  load_inverse();
+  __syncthreads();
+  block_product(t);  // Linv r
 #pragma unroll
   for (int h = 0; h < VS_NH; ++h)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int i = 16 * w + lq + 4 * g, a = 16 * h + li;
-      if (i < nb && a0 + a < Lg) E.V[(size_t)(k0 + i) * Lg + a0 + a] = acc[h][g];
+      if (i < nb && a0 + a < Lg) E.V[(size_t)(k0 + i) * Lg + a0 + a] = v0[h][g] + t[h][g];
     }
 }
 

@@ -358,7 +358,7 @@ def test_batch_shape_check(shim):
 def _sizes(E, bd, scalars_bytes, eig_bytes):
     """Documented size in bytes of every buffer an EdgeDev points to (csrc/gpet_dev.h), written out independently."""
     M, N, Lg, S, nc, rc = E["M"], E["N"], E["Lg"], E["S"], E["n_cap"], E["r_cap"]
-    big = nc > 128
+    big = bd["n_cap"] > 128   # (the blocked fit is chosen for the whole batch: every edge then has its scratch)
     s_round = (S + 127) // 128 * 128
     return dict(
         grad=4 * M * N, grad_kde=4 * M * N, init_xy=16 * E["n_init"], obs_xy=16 * E["obs_cap"], obs_new=16 * E["obs_cap"], sc=scalars_bytes,
@@ -374,9 +374,23 @@ def _sizes(E, bd, scalars_bytes, eig_bytes):
         binbest=8 * E["n_bins"], binarg=8 * E["n_bins"], fin_x=8 * nc, fin_y=8 * nc, fin_w=8 * nc, fin_par=96, fin_out=16 * bd["Lg"], rho_tab=8 * N)
 
 
-@pytest.mark.parametrize("name", [n for n in CASES if "B1024" not in n] + ["bench_B1024_shared"])
+# an edge of at most 128 training points in one batch with an edge of 302: the blocked fit runs on both
+_SMALL_WITH_BIG = [edge(x_st=100, x_en=199, delta_x=20), edge(obs_cap=300)]
+
+
+def test_small_edge_of_a_blocked_batch_has_the_blocked_scratch(shim):
+    p = plan(shim, _SMALL_WITH_BIG, 500, 500, 1)
+    E = p["edges"][0]
+    assert E["n_cap"] <= 128 < p["bd"]["n_cap"] == p["edges"][1]["n_cap"]
+    nb = E["n_cap"] // 64 + 1
+    assert E["off"]["solve_z"] - E["off"]["chol_inv"] >= 8 * 4096 * nb     # a 64 x 64 inverse per diagonal block
+    assert E["off"]["solve_flag"] - E["off"]["solve_z"] >= 8 * E["n_cap"]
+    assert E["off"]["K"] - E["off"]["solve_flag"] >= 4 * 2 * nb             # forward and backward flags of k_chol_solve_mw
+
+
+@pytest.mark.parametrize("name", [n for n in CASES if "B1024" not in n] + ["bench_B1024_shared", "small_with_big"])
 def test_layout_is_aligned_disjoint_and_inside_the_arena(shim, name):
-    ps, M, N, share = CASES[name][:4]
+    ps, M, N, share = (_SMALL_WITH_BIG, 500, 500, 1) if name == "small_with_big" else CASES[name][:4]
     p = plan(shim, ps, M, N, share)
     scalars_bytes, eig_bytes = shim.shim_sizes(0), shim.shim_sizes(1)
     assert (scalars_bytes, eig_bytes) == (80, 72)

@@ -199,7 +199,8 @@ def test_objective_and_gradient_every_kernel_against_exact(amd, ctx, nu):
 def test_converged_fit_and_lattice_objective_against_exact(amd, ctx, nu):
     """final_fit_all: the k_lml16 lattice objective (lml_batch after the fit has set the lattice) against the exact
     objective; at nu in {0.7, 5, 20} the fit's theta against scipy L-BFGS-B on the exact objective from the same 13
-    start points (log c and log l to 1e-4), its mean / std against the exact posterior at that theta; final_cov finite."""
+    start points (log c and log l to 1e-4), its mean / std and final_cov against the exact posterior at that theta (final_cov
+    finite and symmetric at every nu)."""
     L = amd._lib
     N = 96
     grad, truth = _image(N, 3)
@@ -219,7 +220,8 @@ def test_converged_fit_and_lattice_objective_against_exact(amd, ctx, nu):
     f, gr = b.lml_batch(np.zeros(th.shape[0], dtype=np.int32), th)
     _check_objective(f, gr, th, pr, nu, "lattice")
     b.final_cov()
-    assert np.all(np.isfinite(b.read(L.BUF_COV)))
+    cov = b.read(L.BUF_COV)
+    assert cov.shape == (N, N) and np.all(np.isfinite(cov)) and np.array_equal(cov, cov.T)
     if nu not in (0.7, 5.0, 20.0):
         return
     starts = b.read(L.BUF_FIN_STARTS)
@@ -239,6 +241,8 @@ def test_converged_fit_and_lattice_objective_against_exact(amd, ctx, nu):
     m_ref = pr["y_s"] * (pr["s2"] * post["mean"] + pr["m2"]) + pr["y_m"]
     np.testing.assert_allclose(mean[0][:N], m_ref, rtol=1e-5, atol=1e-4)
     np.testing.assert_allclose(std[0][:N], pr["s2"] * post["std"], rtol=1e-5, atol=1e-6)
+    # the covariance of the same posterior (sklearn_gpr.py:398-403): in the units of the std, not rescaled either
+    np.testing.assert_allclose(cov, pr["s2"] ** 2 * post["cov"], rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("nu", [0.06, 0.3, 0.7, 1.2, 7.5])

@@ -20,6 +20,7 @@ import subprocess
 import pytest
 
 from tests import curve_cost_exact as cx
+from tests import posterior_exact as px
 from tests.test_gpu_sample_gemm_exact import CASES as GEMM_CASES
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian_process_edge_trace_amd", "csrc")
@@ -288,6 +289,20 @@ def test_fit_and_predict(shim):
         assert shim.shim_predict(dims(n_cap=45), final, C.byref(lds)) == b"lds" and lds.value == 24120
     assert shim.shim_predict(dims(n_cap=287), 0, C.byref(lds)) == b"through_hbm" and lds.value == 0
     assert shim.shim_predict(dims(n_cap=287), 1, C.byref(lds)) == b"global" and lds.value == 0
+
+
+def test_posterior_table_capacities_reach_the_forms_they_name(shim):
+    """The capacities of tests/posterior_exact.py's table, by regime, against the header: K in LDS / blocked, V in LDS / through
+    HBM (loop) / global (converged fit) -- and both neighbours of each threshold are in the table."""
+    o = (C.c_int * 1)()
+    lds = C.c_longlong()
+    want = {"lds": (1, b"lds", b"lds"), "blocked": (0, b"lds", b"lds"), "hbm": (0, b"through_hbm", b"global")}
+    for regime, (caps, _) in px.REGIMES.items():
+        for n_cap in caps:
+            shim.shim_fit(dims(n_cap=n_cap), o)
+            got = (o[0], shim.shim_predict(dims(n_cap=n_cap), 0, C.byref(lds)), shim.shim_predict(dims(n_cap=n_cap), 1, C.byref(lds)))
+            assert got == want[regime] and px.regime_of(n_cap) == regime, (regime, n_cap, got)
+    assert {128, 129, 286, 287} <= set(px.ALL_CAPS)
 
 
 # ---- structured path ----
