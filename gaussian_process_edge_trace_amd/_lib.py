@@ -25,6 +25,7 @@ KERNEL_RBF, KERNEL_MATERN = 0, 1
 GRAD_ON_DEVICE = 1  # gpet_batch_create2 / gpet_batch_set_images flag: the gradient image pointers are device pointers
 IMAGES_NEXT_FRAME = 2  # gpet_batch_set_images: the images continue the sequences just traced
 RAW_ON_DEVICE = 4  # gpet_grad_images / gpet_batch_create_raw / gpet_batch_set_raw_images: the frame pointers are device pointers
+FRAMES_TRANSPOSED = 16  # the raw-frame calls and every batch creation with flags: a vertical batch -- frames in frame layout, images and batch shape (N, M)
 # pixel types of raw frames (GPET_PIX_*): the dtypes that go to the device as they are
 PIX_U8, PIX_U16, PIX_F32, PIX_F64 = range(4)
 PIX_OF_DTYPE = {np.dtype(np.uint8): PIX_U8, np.dtype(np.uint16): PIX_U16, np.dtype(np.float32): PIX_F32,
@@ -926,31 +927,39 @@ class Context:
                                             kernel.shape[0], kernel.shape[1], out.ctypes.data))
         return out
 
-    def grad_images(self, raw):
-        """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32."""
+    def grad_images(self, raw, transpose=False):
+        """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32.
+        ``transpose`` (GPET_FRAMES_TRANSPOSED): (T, N, M), every image the transpose of its frame's gradient image, made on the device."""
         M, N = raw.shape
         if raw.nlm is not None:  # (non-local means first, into device memory of this call; the calls below end with a wait)
             buf = NlmFrames(self)
             try:
-                return self.grad_images(raw.nlm_resolved(self, buf))
+                return self.grad_images(raw.nlm_resolved(self, buf), transpose)
             finally:
                 buf.close()
+        if transpose:
+            return self._grad_images(raw, N, M, raw.flags | FRAMES_TRANSPOSED)
+        return self._grad_images(raw, M, N, raw.flags)
+
+    def _grad_images(self, raw, Mo, No, flags):
+        """``grad_images`` behind the non-local means stage: outputs of shape (Mo, No), the library called with ``flags``."""
+        M, N = raw.shape
         if raw.slots is not None:  # (a slot table: gpet_grad_images_multi -> (n_slots, M, N), slot g of frame_of[g], kernel_of[g])
             ns = raw.n_slots
-            out = np.empty((ns, M, N), dtype=np.float32)
+            out = np.empty((ns, Mo, No), dtype=np.float32)
             op = (_P * ns)(*[out[g].ctypes.data for g in range(ns)])
             nk, kp, kh, kw, fo, ko = raw.multi_args()
             self.check(self.lib.gpet_grad_images_multi(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, nk, kp, kh, kw,
-                                                       raw.dn_arg() if raw.dn is not None else None, ns, fo, ko, raw.flags, op))
+                                                       raw.dn_arg() if raw.dn is not None else None, ns, fo, ko, flags, op))
             return out
-        out = np.empty((len(raw), M, N), dtype=np.float32)
+        out = np.empty((len(raw), Mo, No), dtype=np.float32)
         op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
         kp, kh, kw = raw.kernel_args()
         if raw.dn is not None:
             self.check(self.lib.gpet_grad_images_dn(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, raw.dn_arg(),
-                                                    raw.flags, op))
+                                                    flags, op))
             return out
-        self.check(self.lib.gpet_grad_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, raw.flags, op))
+        self.check(self.lib.gpet_grad_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, kp, kh, kw, flags, op))
         return out
 
     def denoise_images(self, raw):
@@ -1132,7 +1141,7 @@ class Batch:
     """gpet_batch: B independent edges processed together."""
 
     def __init__(self, ctx: Context, grads, params, inits, share_image=False, device_ptrs=None, shape=None, raw=None,
-                 image_of=None, band=None):
+                 image_of=None, band=None, transposed=False):
         """``grads``: float32 (M, N) arrays on the host -- or, with ``device_ptrs`` (a list of integer device
         addresses of f32 [M*N] images on the context's device, e.g. ``tensor.data_ptr()`` after an RCCL broadcast) and
         ``shape`` = (M, N), nothing on the host at all: the library consumes the device images in place.  Or ``raw`` (a
@@ -1142,8 +1151,14 @@ class Batch:
         or B; the library checks the map against that count (gpet_batch_create_mapped / gpet_batch_create_raw_mapped).
         ``band`` = (H, r0): tracking bands (gpet_batch_create_banded) -- the images are full frames, ``inits`` in full-frame rows,
         ``r0`` one first row per edge or None (placed from the inits); the batch's own shape ``(M, N)`` becomes (H, N),
-        ``frame_M`` stays the frames', and every row the batch returns is a band row (``band_r0()`` has the offsets)."""
+        ``frame_M`` stays the frames', and every row the batch returns is a band row (``band_r0()`` has the offsets).
+        ``transposed`` (GPET_FRAMES_TRANSPOSED): a vertical batch -- the images, of whatever kind, are (Mf, Nf) in the frame's layout
+        and stay so for ``set_images`` (``frame_shape``); the batch is the one on the transposes of their gradient images, made on the
+        device: ``(M, N)`` is (Nf, Mf) (banded: (H, Mf), ``frame_M`` = Nf), and ``params``, ``inits``, a band and everything the
+        batch takes or returns later are in THAT image's coordinates."""
         self.ctx = ctx
+        self.transposed = bool(transposed)
+        tf = FRAMES_TRANSPOSED if transposed else 0
         self.lib = ctx.lib
         B = len(params)
         self._nlm_buf = None  # device frames of a non-local means pass in front of the raw-frame path (NlmFrames), kept for set_images
@@ -1202,24 +1217,24 @@ class Batch:
                 im.kern, im.kh, im.kw, im.frame_of, im.kernel_of = C.cast(kp, C.POINTER(C.c_void_p)), kh, kw, fo, ko
                 if raw.dn is not None:
                     im.dn = C.pointer(raw.dn)
-                im.flags = raw.flags
+                im.flags = raw.flags | tf
             else:
-                im.grad, im.flags = C.cast(gp, C.POINTER(C.c_void_p)), flags
+                im.grad, im.flags = C.cast(gp, C.POINTER(C.c_void_p)), flags | tf
             ctx.check(self.lib.gpet_batch_create_banded(ctx.h, B, self.M, self.N, C.byref(bd), C.byref(im), pa, ip, C.byref(h)))
-            self.band_rows, self.M = H, H
+            self.band_rows = H
         elif image_of is not None:  # (the library checks the map: its message says what is wrong with it)
             if raw is not None and raw.slots is not None:
                 nk, kp, kh, kw, fo, ko = raw.multi_args()
                 ctx.check(self.lib.gpet_batch_create_raw_multi(ctx.h, B, self.M, self.N, n_img, io, len(raw), raw.pointer_array(), raw.pix,
                                                                nk, kp, kh, kw, fo, ko, raw.dn_arg() if raw.dn is not None else None,
-                                                               pa, ip, raw.flags, C.byref(h)))
+                                                               pa, ip, raw.flags | tf, C.byref(h)))
             elif raw is not None:
                 kp, kh, kw = raw.kernel_args()
                 ctx.check(self.lib.gpet_batch_create_raw_mapped(ctx.h, B, self.M, self.N, n_img, io, raw.pointer_array(), raw.pix, kp,
                                                                 kh, kw, raw.dn_arg() if raw.dn is not None else None, pa, ip,
-                                                                raw.flags, C.byref(h)))
+                                                                raw.flags | tf, C.byref(h)))
             else:
-                ctx.check(self.lib.gpet_batch_create_mapped(ctx.h, B, self.M, self.N, n_img, io, gp, pa, ip, flags, C.byref(h)))
+                ctx.check(self.lib.gpet_batch_create_mapped(ctx.h, B, self.M, self.N, n_img, io, gp, pa, ip, flags | tf, C.byref(h)))
         elif raw is not None:
             if raw.slots is not None:
                 raise ValueError("a slot table comes with the image map of its slots (image_of)")
@@ -1227,13 +1242,18 @@ class Batch:
             kp, kh, kw = raw.kernel_args()
             if raw.dn is not None:
                 ctx.check(self.lib.gpet_batch_create_raw_dn(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
-                                                            raw.dn_arg(), 1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
+                                                            raw.dn_arg(), 1 if share_image else 0, pa, ip, raw.flags | tf, C.byref(h)))
             else:
                 ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
-                                                         1 if share_image else 0, pa, ip, raw.flags, C.byref(h)))
+                                                         1 if share_image else 0, pa, ip, raw.flags | tf, C.byref(h)))
         else:
-            ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags,
+            ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags | tf,
                                                   C.byref(h)))
+        if transposed:  # (from here on the batch's own shape: rows of G.T are the frame's columns)
+            self.M, self.N = self.N, self.M
+            self.frame_M = self.M
+        if self.band_rows is not None:
+            self.M = self.band_rows
         self.h = h
         self.B = B
         import weakref
@@ -1252,6 +1272,11 @@ class Batch:
         self._x_st = [int(p.x_st) for p in params]
         self._n_init = [int(p.n_init) for p in params]
 
+    @property
+    def frame_shape(self):
+        """The shape of the images ``set_images`` takes, as they lie in the caller's memory."""
+        return (self.N, self.frame_M) if self.transposed else (self.frame_M, self.N)
+
     def set_images(self, grads=None, device_ptrs=None, next_frame=False, raw=None):
         """New gradient image(s) for the same edges, gradient KDE recomputed, loop state reset (gpet_batch_set_images).
         ``next_frame``: the images are the next frames of the sequences just traced, so an any-rank factor may start from
@@ -1261,7 +1286,7 @@ class Batch:
         if raw is not None:  # (a RawFrames: gpet_batch_set_raw_images)
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
-            assert raw.n_slots == n_img and tuple(raw.shape) == (self.frame_M, self.N)
+            assert raw.n_slots == n_img and tuple(raw.shape) == self.frame_shape
             if raw.nlm is not None:  # (refused before the images are swapped: the batch stays on its old frames)
                 if self._nlm_buf is None:
                     self._nlm_buf = NlmFrames(self.ctx)
@@ -1285,7 +1310,7 @@ class Batch:
             self.ctx.check(self.lib.gpet_batch_set_images(self.h, gp, GRAD_ON_DEVICE | nf))
             return
         grads = [np.ascontiguousarray(g, dtype=np.float32) for g in grads]
-        assert len(grads) == n_img and all(g.shape == (self.frame_M, self.N) for g in grads)
+        assert len(grads) == n_img and all(g.shape == self.frame_shape for g in grads)
         gp = (_P * n_img)(*[g.ctypes.data for g in grads])
         self.ctx.check(self.lib.gpet_batch_set_images(self.h, gp, nf))
 

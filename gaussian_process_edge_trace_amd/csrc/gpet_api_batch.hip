@@ -17,6 +17,8 @@ struct BatchGuard {
 // gradient image(s) as the user passes them -> re-normalised f32 on the device (gpet.py:97).
 // GPET_GRAD_ON_DEVICE: grad[] are device pointers (e.g. the tensor an RCCL broadcast has just filled): consumed in
 // place, no trip through host memory.
+// A vertical batch (b->transposed) takes the images in the frame's layout, bd.N rows of bd.M pixels: the order-free min / max reads
+// them as they lie, and the normaliser writes the transpose into the slot (launch_transpose) instead of the copy.
 static int upload_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
   gpet_ctx* c = b->ctx;
   const size_t px = (size_t)b->bd.M * b->bd.N;
@@ -38,7 +40,10 @@ static int upload_images(gpet_batch* b, const float* const* grad, unsigned int f
       src = b->d_raw;
     }
     HIPCHK(c, launch_minmax(c->stream, src, px, mm));
-    HIPCHK(c, launch_normalise(c->stream, src, px, mm, (float*)b->h_edges[b->img_rep[g]].grad));
+    if (b->transposed)
+      HIPCHK(c, launch_transpose(c->stream, src, b->bd.N, b->bd.M, mm, (float*)b->h_edges[b->img_rep[g]].grad));
+    else
+      HIPCHK(c, launch_normalise(c->stream, src, px, mm, (float*)b->h_edges[b->img_rep[g]].grad));
   }
   HIPCHK(c, gpet_wait(c->stream));  // (pageable sources and h_mm0 must stay valid until the copies have run)
   return GPET_OK;
@@ -70,8 +75,11 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[b->img_rep[g]].grad;
   const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
-  const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, b->bd.M, b->bd.N, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax)
-                         : conv_frames(c, s.raw, n_img, s.pix, b->bd.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax);
+  const bool tr = b->transposed;  // (the frames are then bd.N rows of bd.M pixels, and the slots receive their transposes)
+  const int Mf = tr ? b->bd.N : b->bd.M, Nf = tr ? b->bd.M : b->bd.N;
+  const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, Mf, Nf, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax, tr)
+                         : conv_frames(c, s.raw, n_img, s.pix, Mf, Nf, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax, nullptr,
+                                       nullptr, tr);
   if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
   return rc;
 }
@@ -79,24 +87,39 @@ static int convolve_images(gpet_batch* b, const ImageSource& s) {
 // ---- tracking bands (gpet_band_plan.h, gpet_k_band.inc) --------------------------------------------------------------------------
 // The n_pair full-frame gradient images into the batch's own memory: raw frames through conv_frames with the full frame's rows (the
 // convolution sees the rows above and below every band, the min-max is the full frame's); gradient images as they are.
+// A vertical batch stores the transposes -- G.T of every frame, bs.M rows of bd.N pixels like any other G, so that G + r0 * N stays
+// what it is: raw frames by the transposed-store convolution, gradient images by launch_transpose (host images through d_raw).
 static int band_load_full(gpet_batch* b, const ImageSource& s) {
   gpet_ctx* c = b->ctx;
   BandState& bs = b->band;
   const size_t px = (size_t)bs.M * b->bd.N;
   std::vector<float*> dst((size_t)bs.n_pair);
   for (int p = 0; p < bs.n_pair; ++p) dst[(size_t)p] = bs.G + (size_t)p * px;
+  const bool tr = b->transposed;
+  const int Mf = tr ? b->bd.N : bs.M, Nf = tr ? bs.M : b->bd.N;  // the frame as it lies in the caller's memory
   if (s.raw) {
     const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
-    const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, bs.M, b->bd.N, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax)
-                           : conv_frames(c, s.raw, bs.n_pair, s.pix, bs.M, b->bd.N, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax);
+    const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, Mf, Nf, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax, tr)
+                           : conv_frames(c, s.raw, bs.n_pair, s.pix, Mf, Nf, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax, nullptr,
+                                         nullptr, tr);
     if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
     return rc;
   }
   const bool on_dev = (s.flags & GPET_GRAD_ON_DEVICE) != 0;
   for (int p = 0; p < bs.n_pair; ++p)
     if (!s.grad[p]) return fail(c, GPET_ERR_BAD_ARG, "gradient image %d is a null pointer", p);
-  for (int p = 0; p < bs.n_pair; ++p)
-    HIPCHK(c, hipMemcpyAsync(dst[(size_t)p], s.grad[p], px * sizeof(float), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  for (int p = 0; p < bs.n_pair; ++p) {
+    if (!tr) {
+      HIPCHK(c, hipMemcpyAsync(dst[(size_t)p], s.grad[p], px * sizeof(float), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+      continue;
+    }
+    const float* from = s.grad[p];
+    if (!on_dev) {  // (d_raw holds a full frame on a vertical banded batch; the stream orders its reuse)
+      HIPCHK(c, hipMemcpyAsync(b->d_raw, s.grad[p], px * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      from = b->d_raw;
+    }
+    HIPCHK(c, launch_transpose(c->stream, from, Mf, Nf, nullptr, dst[(size_t)p]));
+  }
   if (!on_dev) HIPCHK(c, gpet_wait(c->stream));  // (pageable sources must stay valid until the copies have run)
   return GPET_OK;
 }
@@ -185,17 +208,18 @@ static int image_kde(gpet_batch* b) {
 }
 
 // what can be refused before anything is allocated or enqueued (conv_frames checks the same on its own)
-static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img) {
+// (tr: for a vertical batch, against the LDS bounds of the transposed-store kernels)
+static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img, bool tr) {
   if (!s.raw || (!s.multi && (!s.kern || s.kh <= 0 || s.kw <= 0))) return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
   if (!pix_bytes(s.pix)) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", s.pix);
   if (s.multi) {
     if (s.multi->n_img != n_img)
       return fail(c, GPET_ERR_BAD_ARG, "slot table: %d slots for a batch of %d image slots", s.multi->n_img, n_img);
-    const int rc = check_conv_multi(c, *s.multi, s.n_frames);
+    const int rc = check_conv_multi(c, *s.multi, s.n_frames, tr);
     if (rc) return rc;
-  } else if (!conv_fits_lds(s.kh, s.kw))
+  } else if (!(tr ? conv_t_fits_lds(s.kh, s.kw) : conv_fits_lds(s.kh, s.kw)))
     return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", s.kh, s.kw,
-                conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
+                tr ? conv_t_lds_bytes(s.kh, s.kw) : conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
   if (s.dn)
     if (const char* why = dn_check(*s.dn, s.pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
   for (int g = 0; g < (s.multi ? s.n_frames : n_img); ++g)
@@ -271,12 +295,16 @@ static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
 // image_of == nullptr: one image for all edges (share_image) or one per edge; else the image map (n_img, image_of[B])
 // band != nullptr (gpet_batch_create_banded): M is the full frame's, init_xy in its rows; the batch's own shape becomes (band->H, N)
 // with one image slot per edge, and src describes the band->n_pair full-frame images
+// src.flags & GPET_FRAMES_TRANSPOSED: M, N are the frames' as they lie; the batch is the one on the N x M transposes of their gradient
+// images -- everything below the swap, bands included, counts in the batch's own rows and columns
 static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, int n_img,
                              const int32_t* image_of, const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out,
                              const gpet_band* band = nullptr) {
   if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.raw) || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
+  const bool tr = (src.flags & GPET_FRAMES_TRANSPOSED) != 0;
+  if (tr) std::swap(M, N);
   const int M_full = M;
   const int64_t* const* const init_full = init_xy;
   std::vector<long long> band_r0;
@@ -317,7 +345,7 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
     n_img = share_image ? 1 : B;
   }
   if (src.raw) {
-    const int rc0 = check_raw_source(c, src, band ? band->n_pair : n_img);
+    const int rc0 = check_raw_source(c, src, band ? band->n_pair : n_img, tr);
     if (rc0) return rc0;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -330,6 +358,7 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   b->ctx = c;
   b->B = B;
   b->share_image = share_image ? 1 : 0;
+  b->transposed = tr;
   b->n_img = n_img;
   b->image_of.resize((size_t)B);
   for (int e = 0; e < B; ++e) b->image_of[(size_t)e] = mapped ? image_of[e] : (share_image ? 0 : e);
@@ -396,7 +425,7 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   for (int i = 0; i < 16; ++i) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pix[i], hipEventDisableTiming));
   HIPCHK(c, hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming));
   // upload: gradient image(s) re-normalised on the device (gpet.py:97) or made there from raw frames, inits, initial scalars
-  HIPCHK(c, hipMalloc(&b->d_raw, (size_t)M * N * sizeof(float)));
+  HIPCHK(c, hipMalloc(&b->d_raw, (size_t)(band && tr ? M_full : M) * N * sizeof(float)));  // (vertical and banded: a full frame)
   int rc = GPET_OK;
   if (band) {  // (the full-frame images now; the slots once d_edges is on the device: the band kernels read it)
     rc = band_setup(b, *band, M_full, band_r0.data(), init_full, bb.n_init_max);
@@ -1069,6 +1098,15 @@ int gpet_batch_reset(gpet_batch* b) {
   return batch_reset(b, false);
 }
 
+// The orientation of a batch is decided at its creation: a vertical batch takes its frames in frame layout without the bit being
+// repeated, and a set call that carries GPET_FRAMES_TRANSPOSED on a batch created without it is refused before anything is touched.
+static int check_set_orientation(gpet_batch* b, unsigned int flags) {
+  if ((flags & GPET_FRAMES_TRANSPOSED) && !b->transposed)
+    return fail(b->ctx, GPET_ERR_BAD_ARG, "GPET_FRAMES_TRANSPOSED on a batch that was created without it: the orientation of a batch "
+                                          "is decided at its creation");
+  return GPET_OK;
+}
+
 // new images for an existing batch, whatever they come as (the one body of gpet_batch_set_images / gpet_batch_set_raw_images)
 static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
   const unsigned int flags = src.flags;
@@ -1087,6 +1125,8 @@ static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
 int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
   GPET_BATCH_SCOPE(b);
   if (!b || !grad) return GPET_ERR_BAD_ARG;
+  const int rc_o = check_set_orientation(b, flags);
+  if (rc_o) return rc_o;
   ImageSource src;
   src.grad = grad;
   src.flags = flags;
@@ -1108,7 +1148,9 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
   src.kw = kw;
   src.dn = dn ? &spec : nullptr;
   src.flags = flags;
-  const int rc = check_raw_source(b->ctx, src, batch_source_count(b));
+  const int rc_o = check_set_orientation(b, flags);
+  if (rc_o) return rc_o;
+  const int rc = check_raw_source(b->ctx, src, batch_source_count(b), b->transposed);
   if (rc) return rc;
   return batch_set_images_from(b, src);
 }
@@ -1128,7 +1170,9 @@ int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* con
   src.flags = flags;
   src.multi = &mk;
   src.n_frames = n_frames;
-  const int rc = check_raw_source(b->ctx, src, batch_source_count(b));
+  const int rc_o = check_set_orientation(b, flags);
+  if (rc_o) return rc_o;
+  const int rc = check_raw_source(b->ctx, src, batch_source_count(b), b->transposed);
   if (rc) return rc;
   return batch_set_images_from(b, src);
 }

@@ -258,18 +258,18 @@ static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
 // slot of the chunk's frames, and the kernels' taps, descriptors and the slot lists go up in the same one table copy.
 static int conv_frames_body(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
                             int kh, int kw, const ConvMulti* mk, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out,
-                            int32_t* n_iter_out) {
+                            int32_t* n_iter_out, bool tr) {
   const size_t esz = (size_t)pix_bytes(pix);
   const bool dn_on = dn && dn->technique != DN_NONE;
   if (!esz) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", pix);
   if (!raw || n_img <= 0 || M <= 0 || N <= 0 || (!kern && !dn_on) || (kern && (!dst || kh <= 0 || kw <= 0)))
     return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
   if (mk) {
-    const int rc_t = check_conv_multi(c, *mk, n_img);
+    const int rc_t = check_conv_multi(c, *mk, n_img, tr);
     if (rc_t) return rc_t;
-  } else if (kern && !conv_fits_lds(kh, kw))
-    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw, conv_lds_bytes(kh, kw),
-                CONV_LDS_MAX);
+  } else if (kern && !(tr ? conv_t_fits_lds(kh, kw) : conv_fits_lds(kh, kw)))
+    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw,
+                tr ? conv_t_lds_bytes(kh, kw) : conv_lds_bytes(kh, kw), CONV_LDS_MAX);
   if (dn)
     if (const char* why = dn_check(*dn, pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
   for (int g = 0; g < n_img; ++g)
@@ -338,12 +338,14 @@ static int conv_frames_body(gpet_ctx* c, const void* const* raw, int n_img, int 
   const double* d_gw = (const double*)(c->raw_tab + o_gw);
   int* d_it = (int*)(c->raw_tab + o_it);
   // frames first .. first + cnt - 1 of `from` (pixel type p) -> the gradient images of the frames, or of all their slots
+  // (tr: the transposed-store forms -- the image at dst[g] is then N x M; the element-wise normaliser below does not care)
   auto convolve = [&](int p, const void* const* from, int first, int cnt) {
     if (mk)
-      return launch_conv_multi(c->stream, p, from, first, cnt, M, N, d_wf, cu, (const ConvKernDesc*)(c->raw_tab + o_kd),
-                               (const int32_t*)(c->raw_tab + o_so), (const int32_t*)(c->raw_tab + o_sl),
-                               (const int32_t*)(c->raw_tab + o_ko), d_dst, d_mm);
-    return launch_conv_batch(c->stream, p, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
+      return (tr ? launch_conv_multi_tr : launch_conv_multi)(c->stream, p, from, first, cnt, M, N, d_wf, cu,
+                                                             (const ConvKernDesc*)(c->raw_tab + o_kd), (const int32_t*)(c->raw_tab + o_so),
+                                                             (const int32_t*)(c->raw_tab + o_sl), (const int32_t*)(c->raw_tab + o_ko), d_dst,
+                                                             d_mm);
+    return (tr ? launch_conv_batch_tr : launch_conv_batch)(c->stream, p, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
   };
   if (on_dev && !dn_on) {
     HIPCHK(c, convolve(pix, d_src, 0, n_img));
@@ -394,44 +396,47 @@ static int conv_frames_body(gpet_ctx* c, const void* const* raw, int n_img, int 
 }
 
 int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
-                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out) {
-  return conv_frames_body(c, raw, n_img, pix, M, N, dn, kern, kh, kw, nullptr, on_dev, dst, d_mm, dn_out, n_iter_out);
+                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out, bool tr) {
+  return conv_frames_body(c, raw, n_img, pix, M, N, dn, kern, kh, kw, nullptr, on_dev, dst, d_mm, dn_out, n_iter_out, tr);
 }
 
-int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames) {
+int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames, bool tr) {
   if (!mk.kern || !mk.kh || !mk.kw) return fail(c, GPET_ERR_BAD_ARG, "slot table: the kernels are a null pointer");
   if (const char* why = slot_table_check(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
     return fail(c, GPET_ERR_BAD_ARG, "slot table: %s (n_frames = %d, n_kern = %d, n_img = %d)", why, n_frames, mk.n_kern, mk.n_img);
   for (int k = 0; k < mk.n_kern; ++k)
     if (!mk.kern[k] || mk.kh[k] <= 0 || mk.kw[k] <= 0) return fail(c, GPET_ERR_BAD_ARG, "slot table: kernel %d is empty or a null pointer", k);
-  if (!conv_union_fits_lds(mk.n_kern, mk.kh, mk.kw)) {
+  if (!(tr ? conv_union_t_fits_lds(mk.n_kern, mk.kh, mk.kw) : conv_union_fits_lds(mk.n_kern, mk.kh, mk.kw))) {
     const ConvUnion u = conv_union(mk.n_kern, mk.kh, mk.kw);
     return fail(c, GPET_ERR_BAD_ARG, "the %d kernels need %zu bytes of LDS for their taps and their union patch of %d x %d, more than %zu",
-                mk.n_kern, conv_union_lds_bytes(u), conv_union_rows(u), conv_union_cols(u), CONV_LDS_MAX);
+                mk.n_kern, tr ? conv_union_t_lds_bytes(u) : conv_union_lds_bytes(u), tr ? conv_union_t_rows(u) : conv_union_rows(u),
+                tr ? conv_union_t_cols(u) : conv_union_cols(u), CONV_LDS_MAX);
   }
   return GPET_OK;
 }
 
 // one kernel on every frame in frame order is the single-kernel path itself: the same launches in the same order
 int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
-                      bool on_dev, float* const* dst, unsigned int* d_mm) {
-  const int rc = check_conv_multi(c, mk, n_frames);
+                      bool on_dev, float* const* dst, unsigned int* d_mm, bool tr) {
+  const int rc = check_conv_multi(c, mk, n_frames, tr);
   if (rc) return rc;
   if (slot_table_is_identity(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
-    return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], nullptr, on_dev, dst, d_mm, nullptr, nullptr);
+    return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], nullptr, on_dev, dst, d_mm, nullptr, nullptr, tr);
   // (with a table the body reads `kern` only as "there is a convolution": taps and extents come from mk)
-  return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], &mk, on_dev, dst, d_mm, nullptr, nullptr);
+  return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], &mk, on_dev, dst, d_mm, nullptr, nullptr, tr);
 }
 
 extern "C" {
 
 // n_img output images; mk == nullptr: of n_img frames with the one kernel, else of n_frames frames by the slot table
+// (GPET_FRAMES_TRANSPOSED: every output is the N x M transpose of the frame's M x N gradient image)
 static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
                             const DenoiseSpec* dn, unsigned int flags, float* const* out, const ConvMulti* mk = nullptr, int n_frames = 0) {
   if (!c || !raw || !out || n_img <= 0 || M <= 0 || N <= 0 || (!mk && (!kern || kh <= 0 || kw <= 0)))
     return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: bad argument");
+  const bool tr = (flags & GPET_FRAMES_TRANSPOSED) != 0;
   if (mk) {
-    const int rc_t = check_conv_multi(c, *mk, n_frames);  // (before the scratch is sized by the table)
+    const int rc_t = check_conv_multi(c, *mk, n_frames, tr);  // (before the scratch is sized by the table)
     if (rc_t) return rc_t;
   }
   for (int g = 0; g < n_img; ++g)
@@ -449,8 +454,8 @@ static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int 
   unsigned int* d_mm = cv.take<unsigned int>(2 * (size_t)n_img);
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = d_out + (size_t)g * px;
-  rc = mk ? conv_frames_multi(c, raw, n_frames, pix, M, N, dn, *mk, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm)
-          : conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm);
+  rc = mk ? conv_frames_multi(c, raw, n_frames, pix, M, N, dn, *mk, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm, tr)
+          : conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm, nullptr, nullptr, tr);
   if (rc == GPET_OK)
     for (int g = 0; g < n_img; ++g) {
       hipError_t e = hipMemcpyAsync(out[g], dst[(size_t)g], px * sizeof(float), hipMemcpyDeviceToHost, c->stream);

@@ -186,6 +186,9 @@ struct gpet_batch {
   char* d_hist = nullptr;
   gpet_history_plan hist{};
   BandState band;  // tracking bands (gpet_batch_create_banded)
+  // a vertical batch (GPET_FRAMES_TRANSPOSED at creation): the caller's frames and gradient images are bd.N rows of (band.H ? band.M :
+  // bd.M) pixels, and load_images writes their transposes -- everything behind it works on the batch's own (M, N) as ever
+  bool transposed = false;
   OptionSet opts;  // the batch's own copy of the option table (gpet_options.h): taken at creation, gpet_batch_set_option changes it
 };
 // first statement of every entry point that works on a batch: its option table for the calling thread
@@ -203,10 +206,11 @@ int fail(gpet_ctx* ctx, int code, const char* fmt, ...);
 int fin_lattice(const double* x, int n, double* hinv);
 // n_img raw frames (host, or device with on_dev) -> normalised f32 gradient images at the device pointers dst[], enqueued on the
 // context's stream without a final wait; d_mm: device [2 n_img].  dn (may be nullptr): the frames are denoised first; kern ==
-// nullptr: denoising alone, into the host buffers dn_out[] (iterations per image: n_iter_out)
+// nullptr: denoising alone, into the host buffers dn_out[] (iterations per image: n_iter_out).  tr (GPET_FRAMES_TRANSPOSED): M, N
+// stay the frame's as it lies, and every dst[g] receives the N x M transpose of its gradient image (gpet_transpose_plan.h)
 int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
                 int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out = nullptr,
-                int32_t* n_iter_out = nullptr);
+                int32_t* n_iter_out = nullptr, bool tr = false);
 // the slot table of a multi-kernel source as the C ABI hands it over (gpet_conv_multi_plan.h): slot g of n_img is frame frame_of[g]
 // with kernel kernel_of[g] of the n_kern kernels kern[k] (kh[k] x kw[k])
 struct ConvMulti {
@@ -219,11 +223,12 @@ struct ConvMulti {
   const int32_t* kernel_of;
 };
 // GPET_OK, or GPET_ERR_BAD_ARG with the reason: a table slot_table_check refuses, an empty kernel, a union patch beyond the LDS
-int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames);
+// (tr: against the LDS bound of the transposed-store kernel)
+int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames, bool tr = false);
 // conv_frames for a slot table: n_frames raw frames -> the mk.n_img gradient images dst[g] (d_mm: device [2 mk.n_img]); every frame
 // is staged and denoised once.  One kernel on every frame in order takes conv_frames' own path
 int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
-                      bool on_dev, float* const* dst, unsigned int* d_mm);
+                      bool on_dev, float* const* dst, unsigned int* d_mm, bool tr = false);
 // the C ABI's gpet_denoise as the plan takes it (nullptr: no technique)
 static inline DenoiseSpec dn_spec(const gpet_denoise* d) {
   DenoiseSpec s;

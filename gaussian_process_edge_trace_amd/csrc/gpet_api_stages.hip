@@ -138,9 +138,32 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
   if (!b || !ms_per_rep || reps < 1) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   HIPCHK(c, hipSetDevice(c->device));
+  // 170: the in-place normaliser of the raw-frame path (k_normalise_f32_batch) over the batch's image slots, with the neutral pair
+  // (min 0, max 1) in every slot of d_minmax -- (x - 0) / 1 leaves every bit of the images as it is
+  float** d_slots = nullptr;
+  if (stage == 170) {
+    std::vector<float*> slots((size_t)b->n_img);
+    for (int g = 0; g < b->n_img; ++g) slots[(size_t)g] = (float*)b->h_edges[b->img_rep[g]].grad;
+    b->h_mm0.assign((size_t)2 * b->n_img, 0x80000000u);  // the order key of +0.0f ...
+    for (int g = 0; g < b->n_img; ++g) b->h_mm0[2 * (size_t)g + 1] = 0xBF800000u;  // ... and of 1.0f
+    HIPCHK(c, hipMalloc(&d_slots, sizeof(float*) * slots.size()));
+    hipError_t e = hipMemcpy(d_slots, slots.data(), sizeof(float*) * slots.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b->d_minmax, b->h_mm0.data(), sizeof(unsigned int) * b->h_mm0.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d_slots);
+      HIPCHK(c, e);
+    }
+  }
+  struct SlotGuard {
+    float** p;
+    ~SlotGuard() {
+      if (p) (void)hipFree(p);
+    }
+  } slot_guard{d_slots};
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));
   for (int r = 0; r < reps; ++r) {
     switch (stage) {
+      case 170: HIPCHK(c, launch_normalise_batch(c->stream, d_slots, b->n_img, (size_t)b->bd.M * b->bd.N, b->d_minmax)); break;
       case 0:
         if (b->structured) HIPCHK(c, launch_struct_iteration(c->stream, b->d_edges, b->B, b->bd, 1u | 2u));
         else HIPCHK(c, launch_fit_predict(c->stream, b->d_edges, b->B, b->bd, 1));

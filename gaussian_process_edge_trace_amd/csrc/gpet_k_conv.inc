@@ -243,3 +243,159 @@ __global__ void k_conv_relu_multi(const T* const* __restrict__ src, int frame0, 
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// a1, batched, transposed store (GPET_FRAMES_TRANSPOSED; geometry: gpet_transpose_plan.h).  k_conv_relu_batch with the tile turned:
+//     a workgroup of 64 x 4 threads owns 16 frame columns x 64 frame rows, threadIdx.x is the ROW within the tile, and pixel (y, x)
+//     is stored at x * M + y of the N x M image -- the 64 lanes of a wave write 64 consecutive floats.  The patch lies in LDS
+//     TRANSPOSED, [16 + kw - 1] columns of 64 + kh - 1 pixels at an odd pitch, so the lanes of a tap read (one patch row apart) are
+//     consecutive doubles, as they are in k_conv_relu_batch; the few writes of the patch load are the strided ones.
+//     Per pixel the products, their order, the skipped zero taps, the clamp, the cast and the order key are k_conv_relu_batch's:
+//     the image is that kernel's, transposed, bit for bit, and the (min, max) slot holds the same pair.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ void k_conv_tr_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
+                                    int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch, column-major: [CONV_T_TILE_X + kw - 1][pitch]
+  const int g = img0 + blockIdx.z;
+  const T* __restrict__ img = src[g];
+  float* __restrict__ out = dst[g];
+  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
+  for (int i = tid; i < kh * kw; i += nthr) s_w[i] = wf[i];
+  const int pw = CONV_T_TILE_X + kw - 1, ph = CONV_T_TILE_Y + kh - 1, pitch = conv_t_pitch(ph);
+  double* s_p = s_w + kh * kw;
+  const int x0 = conv_t_col(blockIdx.x, 0), y0 = conv_t_row(blockIdx.y, 0);
+  for (int e = tid; e < pw * ph; e += nthr) {
+    const int py = e / pw, px = e - py * pw;
+    int ry = y0 + py - oy, rx = x0 + px - ox;
+    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
+    s_p[px * pitch + py] = (double)img[(size_t)ry * N + rx];
+  }
+  __syncthreads();
+  const int yl = threadIdx.x, y = y0 + yl;
+  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
+  for (int xl = threadIdx.y; xl < CONV_T_TILE_X; xl += blockDim.y) {
+    const int x = x0 + xl;
+    if (x < N && y < M) {
+      double acc = 0.0;
+      for (int a = 0; a < kh; ++a) {
+        const double* row = s_p + xl * pitch + yl + a;  // (patch row yl + a of column xl; the next column is `pitch` further)
+        for (int b = 0; b < kw; ++b) {
+          const double w = s_w[a * kw + b];
+          if (w == 0.0) continue;
+          acc = acc + row[b * pitch] * w;
+        }
+      }
+      if (acc < 0.0) acc = 0.0;
+      const float v = (float)acc;
+      out[tr_offset(y, x, M)] = v;
+      const unsigned int key = f32_order_key(v);
+      kmin = min(kmin, key);
+      kmax = max(kmax, key);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
+    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
+  }
+  if ((tid & 63) == 0) {
+    atomicMin(&minmax[2 * (size_t)g], kmin);
+    atomicMax(&minmax[2 * (size_t)g + 1], kmax);
+  }
+}
+
+// k_conv_relu_multi with the tile turned the same way: the union patch column-major at the odd pitch, every slot of the frame out of it
+template <typename T>
+__global__ void k_conv_tr_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
+                                    const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
+                                    const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
+                                    const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_w[];  // [n_taps] taps of all kernels, then the union patch, column-major: [pw][pitch]
+  const int f = frame0 + blockIdx.z;
+  const T* __restrict__ img = src[f];
+  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
+  for (int i = tid; i < n_taps; i += nthr) s_w[i] = wf[i];
+  double* s_p = s_w + n_taps;
+  const int pitch = conv_t_pitch(ph);
+  const int x0 = conv_t_col(blockIdx.x, 0), y0 = conv_t_row(blockIdx.y, 0);
+  for (int e = tid; e < pw * ph; e += nthr) {
+    const int py = e / pw, px = e - py * pw;
+    int ry = y0 + py - top, rx = x0 + px - left;
+    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
+    s_p[px * pitch + py] = (double)img[(size_t)ry * N + rx];
+  }
+  __syncthreads();
+  const int yl = threadIdx.x, y = y0 + yl;
+  for (int si = slot_off[f]; si < slot_off[f + 1]; ++si) {
+    const int g = slot_list[si];
+    const ConvKernDesc K = kd[kernel_of[g]];
+    const double* __restrict__ w_k = s_w + K.w0;
+    float* __restrict__ out = dst[g];
+    unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
+    for (int xl = threadIdx.y; xl < CONV_T_TILE_X; xl += blockDim.y) {
+      const int x = x0 + xl;
+      if (x < N && y < M) {
+        double acc = 0.0;
+        for (int a = 0; a < K.kh; ++a) {
+          const double* row = s_p + (xl + K.dx) * pitch + yl + a + K.dy;
+          for (int b = 0; b < K.kw; ++b) {
+            const double w = w_k[a * K.kw + b];
+            if (w == 0.0) continue;
+            acc = acc + row[b * pitch] * w;
+          }
+        }
+        if (acc < 0.0) acc = 0.0;
+        const float v = (float)acc;
+        out[tr_offset(y, x, M)] = v;
+        const unsigned int key = f32_order_key(v);
+        kmin = min(kmin, key);
+        kmax = max(kmax, key);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
+      kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
+    }
+    if ((tid & 63) == 0) {
+      atomicMin(&minmax[2 * (size_t)g], kmin);
+      atomicMax(&minmax[2 * (size_t)g + 1], kmax);
+    }
+  }
+}
+
+// A finished M x N f32 image into the N x M one (gradient images a caller hands a vertical batch): a TR_TILE x TR_TILE tile through
+// LDS at pitch TR_PITCH -- consecutive lanes read a row of the source, then write a row of the destination.  NORM: every element
+// goes through k_normalise_f32's arithmetic with the image's (min, max) on its way (upload_images); else a plain copy
+// (band_load_full).
+template <bool NORM>
+__global__ void k_transpose_f32(const float* __restrict__ in, int M, int N, const unsigned int* minmax, float* __restrict__ out) {
+  __shared__ float s_t[TR_TILE * TR_PITCH];
+  float mn = 0.0f, span = 1.0f;
+  if (NORM) {
+    mn = f32_from_key(minmax[0]);
+    span = f32_from_key(minmax[1]) - mn;
+  }
+  const int x0 = blockIdx.x * TR_TILE, y0 = blockIdx.y * TR_TILE;
+  for (int r = threadIdx.y; r < TR_TILE; r += blockDim.y) {
+    const int y = y0 + r, x = x0 + threadIdx.x;
+    if (y < M && x < N) s_t[r * TR_PITCH + threadIdx.x] = in[(size_t)y * N + x];
+  }
+  __syncthreads();
+  for (int cc = threadIdx.y; cc < TR_TILE; cc += blockDim.y) {
+    const int x = x0 + cc, y = y0 + threadIdx.x;
+    if (y < M && x < N) {
+      float v = s_t[threadIdx.x * TR_PITCH + cc];
+      if (NORM) {
+        const float a = v - mn;
+        v = a / span;
+      }
+      out[tr_offset(y, x, M)] = v;
+    }
+  }
+}
+

@@ -100,6 +100,75 @@ hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, s
   return hipGetLastError();
 }
 
+// ---- vertical batches: the transposed-store forms (gpet_k_conv.inc; geometry: gpet_transpose_plan.h) ----
+// launch_conv_batch for an N x M image G.T at every d_dst[g]: the same launches with the turned tile
+template <typename T>
+static hipError_t launch_conv_batch_tr_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+                                         int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
+  const ConvGrid cg = conv_t_grid(M, N);
+  hipLaunchKernelGGL(k_conv_tr_batch<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_t_lds_bytes(kh, kw), st, (const T* const*)d_src, img0,
+                     M, N, d_wf, kh, kw, conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
+  return hipGetLastError();
+}
+hipError_t launch_conv_batch_tr(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+                                int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (!conv_t_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;  // (a frame of more than 4 M rows)
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    hipError_t e = hipSuccess;
+    switch (pix) {
+      case PIX_U8: e = launch_conv_batch_tr_t<uint8_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      case PIX_U16: e = launch_conv_batch_tr_t<uint16_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      case PIX_F32: e = launch_conv_batch_tr_t<float>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+      default: e = launch_conv_batch_tr_t<double>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+template <typename T>
+static hipError_t launch_conv_multi_tr_t(hipStream_t st, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                                         const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                                         const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
+  const ConvGrid cg = conv_t_grid(M, N);
+  hipLaunchKernelGGL(k_conv_tr_multi<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_union_t_lds_bytes(u), st, (const T* const*)d_src,
+                     frame0, M, N, d_wf, (int)u.taps, d_kd, u.top, u.left, conv_union_t_rows(u), conv_union_t_cols(u), d_slot_off,
+                     d_slot_list, d_kernel_of, d_dst, d_minmax);
+  return hipGetLastError();
+}
+hipError_t launch_conv_multi_tr(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                                const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                                const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (u.taps == 0 || conv_union_t_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;
+  for (int i = 0; i < n; i += 65535) {
+    const int m = n - i < 65535 ? n - i : 65535;
+    hipError_t e = hipSuccess;
+    switch (pix) {
+      case PIX_U8: e = launch_conv_multi_tr_t<uint8_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      case PIX_U16: e = launch_conv_multi_tr_t<uint16_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      case PIX_F32: e = launch_conv_multi_tr_t<float>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+      default: e = launch_conv_multi_tr_t<double>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// an M x N f32 image -> the N x M one at d_out (d_out != d_in); d_minmax != nullptr: launch_normalise's arithmetic on the way
+hipError_t launch_transpose(hipStream_t st, const float* d_in, int M, int N, const unsigned int* d_minmax, float* d_out) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  const TrGrid tg = tr_grid(M, N);
+  if (M < 1 || N < 1 || tg.gy > 65535 || d_in == d_out) return hipErrorInvalidValue;
+  if (d_minmax)
+    hipLaunchKernelGGL(k_transpose_f32<true>, dim3(tg.gx, tg.gy), dim3(TR_TILE, 4), 0, st, d_in, M, N, d_minmax, d_out);
+  else
+    hipLaunchKernelGGL(k_transpose_f32<false>, dim3(tg.gx, tg.gy), dim3(TR_TILE, 4), 0, st, d_in, M, N, d_minmax, d_out);
+  return hipGetLastError();
+}
+
 // ---- a0: denoising of a chunk of raw frames (gpet_k_denoise.inc; geometry and workspace: gpet_denoise_plan.h) ----
 static_assert(sizeof(TvcState) == DN_TVC_STATE_BYTES, "the plan reserves k_dn_tvc_check's state");
 static_assert((CONV_RY + 1) * 65 * 2 * sizeof(double) == DN_TVC_LDS_BYTES, "k_dn_tvc_iter tiles as gpet_denoise_plan.h says");

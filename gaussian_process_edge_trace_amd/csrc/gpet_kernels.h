@@ -6,6 +6,7 @@
 #include "gpet_iter_plan.h"   // one loop iteration: kernel variant, grid and LDS of every step; the tile constants
 #include "gpet_conv_plan.h"   // pixel types, conv geometry, staging plan
 #include "gpet_conv_multi_plan.h"  // slot table of a multi-kernel source: validation, union patch, slots of each frame
+#include "gpet_transpose_plan.h"  // vertical batches: the index map, the tile transpose, the transposed-store convolution
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
@@ -45,6 +46,16 @@ hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, 
                              const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
                              const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax);
 hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax);
+// vertical batches (gpet_transpose_plan.h): launch_conv_batch / launch_conv_multi whose image at d_dst[g] is the N x M transpose of
+// the M x N gradient image, per pixel the same bits and the same (min, max) slots
+hipError_t launch_conv_batch_tr(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+                                int kh, int kw, float* const* d_dst, unsigned int* d_minmax);
+hipError_t launch_conv_multi_tr(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+                                const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
+                                const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax);
+// an M x N f32 image on the device -> the N x M one at d_out, out of place; d_minmax != nullptr: every element through
+// launch_normalise's arithmetic with that (min, max) pair on its way
+hipError_t launch_transpose(hipStream_t st, const float* d_in, int M, int N, const unsigned int* d_minmax, float* d_out);
 // a0 (gpet_denoise_plan.h): images img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) are the n images of a chunk
 // whose workspace starts at ws; the denoised frame lands at L.off_out of every image's block.  One launch (two for the Gaussian's
 // passes) whatever n is; d_wy / d_wx: the Gaussian taps of the two axes on the device

@@ -45,7 +45,8 @@ def trace_ensemble(init, grad_img, seeds, tol=2, **ctor_kwargs):
     ``agree``, ``members``, ``off``, ``cost``, ``medoid``, ``best_cost``; member indices are batch edge indices, init-major) plus
     ``seeds`` (the members' seeds), ``medoid_seed`` and ``result``: the medoid member's own result as ``finish`` returns it (the
     trace, or (trace, credible interval) with ``return_std``) -- None if the device stopped every member.  One dict for one
-    init, a list for a list of inits."""
+    init, a list for a list of inits.  ``orientation='vertical'`` (a batch keyword): ``grad_img`` / the raw frame as it lies, ``init``
+    and every trace of the dict in the frame's coordinates, as the batch returns them."""
     inits, multi = _inits_of(init)
     if not float(tol) >= 0.0:
         raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))

@@ -362,6 +362,55 @@ def results_from_records(rec, return_std):
     return out, stats
 
 
+def resolve_orientation(orientation):
+    """True for ``orientation='vertical'``, False for ``'horizontal'`` (the default everywhere); ValueError for anything else."""
+    if orientation == "horizontal":
+        return False
+    if orientation == "vertical":
+        return True
+    raise ValueError("orientation must be 'horizontal' or 'vertical', not %r" % (orientation,))
+
+
+def swap_xy(points):
+    """The coordinate swap of a vertical batch, its own inverse: point-valued data -- an (..., 2) array, or a list of arrays -- with
+    the two coordinates of every point exchanged (a copy).  A vertical batch is the horizontal batch on the transposed gradient image:
+    a frame point (x, y) is the batch's (y, x), and a trace the batch returns as (row, column) of the transposed image is (column,
+    row) of the frame.  Position-valued vectors (``lower`` / ``upper``, ``mean``, an ensemble's ``median`` ...) are frame columns
+    indexed by frame row as they are, and are not touched."""
+    if isinstance(points, (list, tuple)) and all(isinstance(p, np.ndarray) for p in points):
+        return [swap_xy(p) for p in points]
+    a = np.asarray(points)
+    if a.ndim == 0 or a.shape[-1] != 2:
+        if a.size == 0:
+            return np.array(a, copy=True)
+        raise ValueError("points are (..., 2) arrays, not of shape %s" % (a.shape,))
+    return np.ascontiguousarray(a[..., ::-1])
+
+
+def swap_record(d, keys=("trace", "obs", "optimal_curves")):
+    """A copy of the dict ``d`` (a history, an ensemble, decoded result records) with its point-valued entries ``keys`` swapped by
+    ``swap_xy``; entries that are missing or None stay so, everything else is shared."""
+    out = dict(d)
+    for k in keys:
+        if out.get(k) is not None:
+            out[k] = swap_xy(out[k])
+    return out
+
+
+def vertical_inits(inits):
+    """The init points of vertical edges, given as (x, y) of the frame, in the batch's coordinates: swapped, after the check that the
+    points of an edge lie in distinct rows (they are what the trace is a function of)."""
+    out = []
+    for e, init in enumerate(inits):
+        a = np.asarray(init)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("init of edge %d has shape %s, not (n_init, 2)" % (e, a.shape))
+        if len(np.unique(a[:, 1])) != a.shape[0]:
+            raise ValueError("init of edge %d: two init points of a vertical edge lie in the same row (y = %s)" % (e, a[:, 1].tolist()))
+        out.append(swap_xy(a))
+    return out
+
+
 def _as_list(x):
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
@@ -380,7 +429,7 @@ def _raw_stack(raw_imgs):
 
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
                          raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None, band_rows=None, band_r0=None,
-                         inits=None):
+                         inits=None, transposed=False):
     """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
     ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
     images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
@@ -392,7 +441,21 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
     (``_lib.derive_slots``) the ``raw`` of ``batch`` carries, and ``edge_frames``, the frame of every edge.
     ``band_rows=H`` (with ``inits``, the init points of every edge, and optionally ``band_r0``): tracking bands -- the images are
     full frames, and the dict also has ``band`` = (H, r0 list or None) as ``resolve_bands`` checked it and ``trace_shape`` = (H, N),
-    the shape the edges' parameters are resolved for.  ``band_rows=None``: exactly the dict described above."""
+    the shape the edges' parameters are resolved for.  ``band_rows=None``: exactly the dict described above.
+    ``transposed`` (a vertical batch): the images are (M, N) in the frame's layout -- ``shape`` says so -- and ``trace_shape`` is that
+    of the transposed gradient image the batch traces, (N, M); a band is then H of its N rows (frame columns), ``trace_shape``
+    (H, M), and ``inits`` are in the batch's coordinates."""
+    if transposed:
+        src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
+                                   denoise, kernel_of=kernel_of, image_of=image_of)
+        M, N = src["shape"]
+        src["trace_shape"] = (N, M)
+        if band_rows is not None:
+            src["band"] = resolve_bands(inits, N, band_rows, band_r0)
+            src["trace_shape"] = (src["band"][0], M)
+        elif band_r0 is not None:
+            raise ValueError("band_r0 places the bands of band_rows: it needs band_rows")
+        return src
     if band_rows is not None:
         if all(a is None for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs)):
             raise ValueError("band_rows needs images: the full frames (raw_imgs / raw_device_ptrs with grad_kernel) or full-frame "
@@ -630,12 +693,14 @@ class GP_Edge_Tracing_Batch(object):
     Remaining keyword arguments are the reference constructor's (gpet.py:22-35), common to all edges.
     """
 
+    orientation, _tr, _swap = "horizontal", False, False  # (what the constructor sets for orientation='vertical')
+
     def __init__(self, inits, grad_imgs, seeds, kernel_options=(1, 3, 3), noise_y=1, N_samples=500, score_thresh=1,
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
                  denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None, band_rows=None, band_r0=None,
-                 init_follow=None):
+                 init_follow=None, orientation="horizontal", _batch_coords=False):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -678,7 +743,24 @@ class GP_Edge_Tracing_Batch(object):
         (the rule: csrc/gpet_init_plan.h; ties to the nearest, then the upper row; nothing positive in reach: the point stays; x
         never moves), so rough clicks land on the edge.  On a banded batch the search stays inside the band.  The setting is
         remembered: ``set_frame`` then follows by default.  ``inits`` (attribute) is the current table, a list of (n_init, 2) int64
-        xy arrays in full-frame rows; ``reset()`` keeps it."""
+        xy arrays in full-frame rows; ``reset()`` keeps it.
+        ``orientation='vertical'``: the edges run down the frame -- x is a function of y.  The batch is, bit for bit, the horizontal
+        batch on the TRANSPOSE of every frame's gradient image with the two coordinates of every point swapped, and whatever it returns
+        is swapped back (``swap_xy``): denoising and ``grad_kernel`` are applied to the frames as they lie (a vertical kernel:
+        ``kernel_builder(size, vertical_edges=True)``), the transposed image is written on the device in the same pass, and gradient
+        images given by the caller are in the frame's layout too.  ``inits``, ``obs`` and ``set_frame(init=[...])`` are (x, y) of the
+        frame; the init points of an edge lie in distinct rows.  Traces are (row, column) of the frame with one entry per traced
+        ROW; ``history()['obs']`` / ``['optimal_curves']`` are (x, y) of the frame; ``lower`` / ``upper``, the history's ``mean`` and an
+        ensemble's ``median``, ``q_lo``, ``q_hi``, ``min``, ``max`` are frame columns indexed by frame row.  Presets of
+        ``kernel_options`` see the transposed image: its height is the frame's width, the edge length the row span.  ``band_rows=H``
+        is a band of H frame COLUMNS with ``band_r0`` its first column; ``init_follow=dict(window=w, cols=a)`` searches w columns
+        left and right of a point, summing over a rows above and below: x moves, y never does."""
+        self.orientation = orientation
+        self._tr = resolve_orientation(orientation)       # the library holds the transposed gradient images
+        self._swap = self._tr and not _batch_coords       # ... and this object swaps the coordinates of what it takes and returns
+        if self._swap:
+            inits = vertical_inits(inits)
+            obs = None if obs is None else [swap_xy(np.asarray(o).reshape(-1, 2)) for o in obs]
         B = len(inits)
         self._init_follow = resolve_init_follow(init_follow)
         if image_of is not None:
@@ -697,7 +779,7 @@ class GP_Edge_Tracing_Batch(object):
             raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
         src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
                                    raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of, band_rows=band_rows,
-                                   band_r0=band_r0, inits=None if band_rows is None else list(inits))
+                                   band_r0=band_r0, inits=None if band_rows is None else list(inits), transposed=self._tr)
         self._denoise = denoise
         self.band_rows, self.band_r0 = (None, None) if band_rows is None else (src["band"][0], src["band"][1])
         # (a slot table: the kernels, the kernel and the frame of every edge are remembered for set_frame; the batch's own image
@@ -744,7 +826,8 @@ class GP_Edge_Tracing_Batch(object):
         kw = dict(src["batch"])
         if band_rows is not None:
             kw["band"] = (self.band_rows, self.band_r0)
-        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, image_of=image_of, **kw)
+        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, image_of=image_of,
+                                 transposed=self._tr, **kw)
         if band_rows is not None:  # (the table as the library placed or took it; observations are kept in band rows from here on)
             self.band_r0 = self._batch.band_r0()
             self._init_span = [init_row_span(p["init"]) for p in self._ps]
@@ -753,7 +836,7 @@ class GP_Edge_Tracing_Batch(object):
         if self._init_follow is not None:  # (the given points refined on the images just made)
             self._take_inits(self._batch.init_follow(*self._init_follow))
         else:
-            self.inits = [np.array(p["init"], dtype=np.int64) for p in self._ps]
+            self._inits = [np.array(p["init"], dtype=np.int64) for p in self._ps]
         if sample_dtype is not None:
             self._batch.set_sample_dtype(sample_dtype)
         if rng is not None:
@@ -769,11 +852,17 @@ class GP_Edge_Tracing_Batch(object):
 
     def _take_inits(self, table):
         """The current init points as the library holds them now: ``inits``, every edge's parameters and the span the bands respect."""
-        self.inits = [np.array(i, dtype=np.int64) for i in table]
-        for p, i in zip(self._ps, self.inits):
+        self._inits = [np.array(i, dtype=np.int64) for i in table]
+        for p, i in zip(self._ps, self._inits):
             p["init"] = i.astype(p["init"].dtype)
         if self.band_rows is not None:
-            self._init_span = [init_row_span(i) for i in self.inits]
+            self._init_span = [init_row_span(i) for i in self._inits]
+
+    @property
+    def inits(self):
+        """The current init points, a list of (n_init, 2) int64 xy arrays in the frame's coordinates (full-frame rows; the points of a
+        vertical edge ordered by y)."""
+        return swap_xy(self._inits) if self._swap else self._inits
 
     def _set_obs(self):
         for e, p in enumerate(self._ps):
@@ -832,7 +921,9 @@ class GP_Edge_Tracing_Batch(object):
         rows, with the x and counts the batch has (on a banded batch only together with an explicit ``band=[r0_e]`` that holds them
         as well as the current points).  Default: ``'follow'`` when the constructor or this call has ``init_follow``, else
         ``'keep'``.  Bands are placed against the points as they are BEFORE this call; the search then stays inside the band.
-        Whatever is refused raises ValueError before anything is touched."""
+        Whatever is refused raises ValueError before anything is touched.
+        A vertical batch takes its frames and gradient images in the frame's layout, ``obs`` and ``init`` as (x, y) of the frame, and
+        ``band`` as first frame columns."""
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
         if warm_from is not None:
@@ -844,6 +935,11 @@ class GP_Edge_Tracing_Batch(object):
             groups = self.group_table(group_of)
             if not float(tol) >= 0.0:
                 raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))
+        if self._swap:  # (a vertical batch: the caller's points into the batch's coordinates)
+            if obs is not None:
+                obs = [swap_xy(np.asarray(o).reshape(-1, 2)) for o in obs]
+            if init is not None and not isinstance(init, str):
+                init = vertical_inits(list(init))
         mode = resolve_frame_band(self.band_rows, band, warm_every, len(self._ps))
         if isinstance(mode, list):
             for e, r0 in enumerate(mode):
@@ -851,7 +947,7 @@ class GP_Edge_Tracing_Batch(object):
                 if why is not None:
                     raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %d, init rows %d .. %d)"
                                      % ((e, why, self._batch.frame_M, self.band_rows, r0) + self._init_span[e]))
-        imode, ipoints = resolve_frame_init(init, init_follow, self._init_follow, self.inits, self._batch.frame_M, self.band_rows, mode)
+        imode, ipoints = resolve_frame_init(init, init_follow, self._init_follow, self._inits, self._batch.frame_M, self.band_rows, mode)
         if warm_every is not None or mode == "follow":
             self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
         if warm_from is not None:
@@ -873,20 +969,20 @@ class GP_Edge_Tracing_Batch(object):
             b = self._batch
             multi = self._kernel_of is not None
             n_img = self._n_frames if multi else b.n_img  # (frames expected)
-            frame_M = b.frame_M
+            fshape = b.frame_shape  # (the frames as they lie: (frame_M, N), on a vertical batch (N, frame_M))
             if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
                 raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
             have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
             if not (n_img == 1 and np.ndim(have) == 2) and len(have) != n_img:
-                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % (len(have), self._images_text(), frame_M, b.N))
-            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, (frame_M, b.N), raw_imgs, raw_device_ptrs,
+                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % ((len(have), self._images_text()) + fshape))
+            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, fshape, raw_imgs, raw_device_ptrs,
                                        self._raw_dtype if raw_dtype is None else raw_dtype, kern,
                                        None if denoise is False else (self._denoise if denoise is None else denoise),
                                        kernel_of=self._kernel_of, image_of=self._edge_frames)
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
-            if len(src["batch"]["raw"]) != n_img or src["shape"] != (frame_M, b.N):
+            if len(src["batch"]["raw"]) != n_img or src["shape"] != fshape:
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"
-                                 % (len(src["batch"]["raw"]), self._images_text(), frame_M, b.N))
+                                 % ((len(src["batch"]["raw"]), self._images_text()) + fshape))
             swap(raw=src["batch"]["raw"], next_frame=next_frame)
         elif grad_device_ptrs is not None:
             ptrs = _as_list(grad_device_ptrs)
@@ -895,9 +991,9 @@ class GP_Edge_Tracing_Batch(object):
             swap(device_ptrs=ptrs, next_frame=next_frame)
         else:
             imgs = list(grad_imgs) if isinstance(grad_imgs, (list, tuple)) else [grad_imgs]
-            if len(imgs) != self._batch.n_img or any(np.shape(g) != (self._batch.frame_M, self._batch.N) for g in imgs):
+            if len(imgs) != self._batch.n_img or any(np.shape(g) != self._batch.frame_shape for g in imgs):
                 raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
-                                 % (len(imgs), self._images_text(), self._batch.frame_M, self._batch.N))
+                                 % ((len(imgs), self._images_text()) + self._batch.frame_shape))
             swap(grads=[np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
         # (the init points move between the swap and the warm start, which keeps columns strictly inside the end points only)
         if imode == "follow":
@@ -973,12 +1069,14 @@ class GP_Edge_Tracing_Batch(object):
                     out[e] = (et + np.array([int(r0), 0]), (lo + float(r0), hi + float(r0)))
                 else:
                     out[e] = out[e] + np.array([int(r0), 0])
+        if self._swap:  # (a vertical batch: (row, column) of the transposed image -> of the frame; the interval is frame columns as it is)
+            out = [(swap_xy(o[0]), o[1]) if self.return_std else swap_xy(o) for o in out]
         return out
 
     def _ensemble_rows(self, groups, group_of):
         """The row fields of an ensemble's dicts in full-frame rows: the members of a group share one band."""
         if self.band_rows is None:
-            return groups
+            return [swap_record(d, ("trace",)) for d in groups] if self._swap else groups
         out = []
         for g, d in enumerate(groups):
             idx = np.flatnonzero(np.asarray(group_of) == g)
@@ -988,7 +1086,8 @@ class GP_Edge_Tracing_Batch(object):
                                  % (g, sorted(r0s)))
             r0 = r0s.pop() if r0s else 0
             d = _shift_rows(d, ("trace",), r0, col=0)
-            out.append(_shift_rows(d, ("median", "q_lo", "q_hi", "min", "max"), float(r0)))
+            d = _shift_rows(d, ("median", "q_lo", "q_hi", "min", "max"), float(r0))
+            out.append(swap_record(d, ("trace",)) if self._swap else d)
         return out
 
     def history(self):
@@ -1004,6 +1103,8 @@ class GP_Edge_Tracing_Batch(object):
                     d["optimal_curves"] = [c + np.array([0.0, float(r0)]) for c in d["optimal_curves"]]
                 if "mean" in d:
                     d["mean"] = d["mean"] + float(r0)
+        if self._swap:
+            hist = [swap_record(d, ("obs", "optimal_curves")) for d in hist]
         return hist
 
     def results(self):
@@ -1020,6 +1121,8 @@ class GP_Edge_Tracing_Batch(object):
             rec["trace"] = tr
             rec["lower"] = rec["lower"] + r0[:, None].astype(np.float64)
             rec["upper"] = rec["upper"] + r0[:, None].astype(np.float64)
+        if self._swap:
+            rec = swap_record(rec, ("trace",))
         return results_from_records(rec, self.return_std)
 
     def final_costs(self):

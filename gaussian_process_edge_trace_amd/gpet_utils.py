@@ -62,7 +62,7 @@ def comp_grad_img(img, kernel, norm=True, astyp=np.float32, ctx=None):
     return out.astype(astyp)
 
 
-def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None):
+def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None, transpose=False):
     """``comp_grad_img`` of every frame of a stack in ONE batched GPU pass (gpet_grad_images): ``imgs`` is a (T, M, N) array
     or a sequence of (M, N) frames, the result a (T, M, N) float32 array whose frame t equals ``comp_grad_img(imgs[t],
     kernel)`` bit for bit.  uint8, uint16, float32 and float64 frames go to the device as they are (integer pixels mean their
@@ -72,14 +72,17 @@ def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None):
     ``kernel`` may also be a list or tuple of 2-D kernels, or a 3-D array (a 2-D array or a nested list of numbers is ONE
     kernel): the result is then (T, n_kern, M, N) and ``[t, k]`` equals ``comp_grad_imgs(imgs, kernel[k])[t]`` bit for bit, with
     and without ``denoise``; every frame is uploaded and denoised once, however many kernels read it
-    (gpet_grad_images_multi)."""
+    (gpet_grad_images_multi).
+    ``transpose=True``: the stage a vertical batch (``orientation='vertical'``) runs -- denoising and the kernel applied to the frames
+    as they lie, every image stored transposed on the device: (T, N, M), or (T, n_kern, N, M), equal to the result without it with
+    the last two axes swapped, bit for bit."""
     kernels, multi = _lib.split_kernels(kernel)
     if not multi:
         raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise)  # (refuses a bad spec before a device is needed)
-        return (ctx or _ctx()).grad_images(raw)
+        return (ctx or _ctx()).grad_images(raw, transpose)
     T, K = len(imgs), len(kernels)
     raw = _lib.RawFrames(kernels, frames=imgs, denoise=denoise, slots=([t for t in range(T) for _ in range(K)], list(range(K)) * T))
-    out = (ctx or _ctx()).grad_images(raw)
+    out = (ctx or _ctx()).grad_images(raw, transpose)
     return out.reshape((T, K) + out.shape[1:])
 
 

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import split_kernels
-from .gpet import GP_Edge_Tracing_Batch, resolve_init_follow, resolve_params
+from .gpet import GP_Edge_Tracing_Batch, resolve_init_follow, resolve_orientation, resolve_params, swap_record, swap_xy, vertical_inits
 
 
 def chain_slices(n_frames, n_chains):
@@ -104,13 +104,18 @@ class SequenceTracer(object):
     the edge of that frame, on the device, starting from where the frame before it in its chain left them (a chain's first frame:
     from ``init``).  ``inits[t]`` holds the points frame t was traced with -- one (n_init, 2) int64 xy array in the order of ``init``,
     or a list of E of them -- without ``init_follow`` the given ones.  The K members of an ensemble share init and image, hence the
-    result; with ``band_rows`` the bands are placed as ever, against the points of the frame before, and the search stays inside."""
+    result; with ``band_rows`` the bands are placed as ever, against the points of the frame before, and the search stays inside.
+
+    ``orientation='vertical'``: the edges run down the frames (``GP_Edge_Tracing_Batch``) -- the sequence is, bit for bit, the
+    horizontal one on the transposed gradient images with the coordinates of ``init`` swapped, and every result, ensemble dict and
+    ``inits[t]`` comes back in the frame's coordinates.  The frames -- raw or gradient images -- are given as they lie; the transposes
+    are made on the device.  ``warm_start_obs`` is applied to the traces of the transposed images."""
 
     _UNSET = object()
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
                  denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, init_follow=None,
-                 **kw):
+                 orientation="horizontal", **kw):
         if ensemble_seeds is not None:
             if seed is not SequenceTracer._UNSET or seeds is not None:
                 raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
@@ -128,9 +133,13 @@ class SequenceTracer(object):
         self.K = 1 if ensemble_seeds is None else len(ensemble_seeds)
         self.frames = frames
         self.T = len(frames)
+        self.orientation = orientation
+        self._tr = resolve_orientation(orientation)
         self._inits, self.multi = _inits_of(init)
         if not self._inits:
             raise ValueError("no init")
+        if self._tr:  # (from here on everything but what is handed back is in the coordinates of the transposed images)
+            self._inits = vertical_inits(self._inits)
         self.E = len(self._inits)
         self.init = self._inits[0] if not self.multi else self._inits
         resolve_init_follow(init_follow)  # (refused here, before a frame is looked at)
@@ -168,6 +177,8 @@ class SequenceTracer(object):
                                                            "keep_ratio", "pixel_thresh", "return_std", "fix_endpoints")}
         self.band_rows = None if band_rows is None else int(band_rows)
         shape = np.asarray(frames[0]).shape
+        if self._tr:
+            shape = (shape[1], shape[0])
         self._frame_M = int(shape[0])
         if self.band_rows is not None:
             shape = (self.band_rows, shape[1])  # (the parameters are those of the (H, N) crop)
@@ -193,7 +204,15 @@ class SequenceTracer(object):
                 if self.init_follow is not None:
                     self._cur[c, k] = mine
                 got.append(mine)
+            if self._tr:
+                got = swap_xy(got)
             self.inits[f] = got if self.multi else got[0]
+
+    def _result_out(self, res):
+        """A result of the step's batch as it is handed back: on a vertical sequence with the trace in the frame's coordinates."""
+        if not self._tr or res is None:
+            return res
+        return (swap_xy(res[0]), res[1]) if self._tracer.return_std else swap_xy(res)
 
     def _place(self, p, trace, init=None):
         """The first row of an edge's band from ``trace`` ((Lg, 2) yx, full-frame rows; None: from the init rows), ``_lib.band_place``;
@@ -249,7 +268,7 @@ class SequenceTracer(object):
         for ci, (c, f) in enumerate(active):
             if ens is None:
                 res = out[ci * E:(ci + 1) * E]
-                results[f] = list(res) if self.multi else res[0]
+                results[f] = [self._result_out(r) for r in res] if self.multi else self._result_out(res[0])
                 self.iterations[f] = list(iters[ci * E:(ci + 1) * E]) if self.multi else iters[ci * E]
                 for k in range(E):
                     prev[c, k] = res[k][0] if self._tracer.return_std else res[k]
@@ -260,10 +279,10 @@ class SequenceTracer(object):
                 d = dict(ens[g])
                 d["seeds"] = [self.ensemble_seeds[e - g * K] for e in d["members"]]
                 d["medoid_seed"] = self.ensemble_seeds[d["medoid"] - g * K] if d["medoid"] >= 0 else None
-                d["result"] = out[d["medoid"]] if d["medoid"] >= 0 else None
-                dicts.append(d)
-                its.append(list(iters[g * K:(g + 1) * K]))
+                d["result"] = self._result_out(out[d["medoid"]] if d["medoid"] >= 0 else None)
                 prev[c, k] = self._source_trace(d, out)
+                dicts.append(swap_record(d, ("trace",)) if self._tr else d)
+                its.append(list(iters[g * K:(g + 1) * K]))
             results[f] = dicts if self.multi else dicts[0]
             self.iterations[f] = its if self.multi else its[0]
 
@@ -312,7 +331,8 @@ class SequenceTracer(object):
                 if self.init_follow is not None:  # (remembered by the batch: its set_frame then follows by default)
                     images["init_follow"] = self.init_follow
                 self._tracer = GP_Edge_Tracing_Batch(tab["inits"], seeds=seeds, obs=obs, device=self.device, _ctx=self._ctx,
-                                                     image_of=tab["image_of"], **images, **self.kw)
+                                                     image_of=tab["image_of"], orientation=self.orientation, _batch_coords=self._tr,
+                                                     **images, **self.kw)
                 if self._ctx is None:
                     self._ctx = self._tracer._ctx
             else:

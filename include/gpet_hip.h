@@ -171,6 +171,19 @@ int gpet_grad_image(gpet_ctx* ctx, const double* img, int M, int N, const double
  * they lie, no staging and no copy.  Without the flag raw[] are host pointers; the frames go up in chunks of whole images
  * through a small staging ring the context owns. */
 #define GPET_RAW_ON_DEVICE 4u
+/* Vertical edges (added without a change of GPET_ABI_VERSION: one flag bit, no new export).  The tracer follows an edge that is a
+ * function of the column; an edge that runs down the frame is traced on the TRANSPOSE of the frame's gradient image.  With this flag
+ * M, N stay the frame as it lies in memory -- M rows of N pixels -- denoising and the kernel are applied to it as it lies, and what
+ * is written is the N x M transpose of its M x N gradient image, bit for bit, made on the device in the same pass.  Accepted by
+ * gpet_grad_images, gpet_grad_images_dn, gpet_grad_images_multi (out[g] is then f32 [N*M]), by every gpet_batch_create* that takes
+ * flags and in gpet_band_images.flags: the batch's image shape is then (N, M), gpet_params.x_st / x_en count frame ROWS, band->H
+ * <= N and band->r0 count frame COLUMNS, and gradient images given by the caller (grad[]) are M x N in frame layout as well.
+ * init_xy, observations and everything the batch returns are in the BATCH's coordinates -- x a frame row, y a frame column: a C
+ * caller swaps its own points.  The batch remembers its orientation: gpet_batch_set_images and gpet_batch_set_raw_images* take
+ * frames in frame layout on such a batch and need not repeat the bit; on a batch created without it a set call that carries the
+ * bit is refused with GPET_ERR_BAD_ARG and touches nothing.  Calls without a flags argument (gpet_batch_create, gpet_grad_image,
+ * gpet_normalise_f32) are unaffected. */
+#define GPET_FRAMES_TRANSPOSED 16u
 /* gpet_utils.comp_grad_img (gpet_utils.py:95-119) for n_img frames [M*N] of pixel type pix (GPET_PIX_*) in one batched
  * pass: out[g] f32 [M*N] (host) is bit for bit what gpet_grad_image gives for frame g.  The number of kernel launches does
  * not depend on n_img (one convolution per staging chunk, one normalisation).  flags: GPET_RAW_ON_DEVICE.
@@ -762,7 +775,8 @@ int gpet_batch_init_xy(gpet_batch* b, int64_t* out);
  * GEMM, 4 scoring+top-k, 5 curve KDE; single kernels: 100 fit, 101 predict, 102 covariance, 110 pivoted
  * Cholesky, 111 Gram, 112 Jacobi, 113 factor rows, 130 sample GEMM, 140 scoring, 141 top-k, 150 KDE prep,
  * 151 fused KDE (5, 150, 151: the loop form -- raw density, band rows only), 152 KDE normalise (stage-API form),
- * 160 column scan of the pixel selection (loop form);
+ * 160 column scan of the pixel selection (loop form); 170 the in-place normaliser of the raw-frame path over the batch's image
+ * slots (with the neutral pair min 0, max 1: the images keep their bits);
  * structured loop path: 120 fit, 121 U/H/mean, 122 Jacobi, 123 factor rows + sign pass.
  * (bench.py's roofline leg; leaves the loop state as-is.) */
 int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep);
