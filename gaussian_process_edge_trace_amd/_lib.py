@@ -70,6 +70,10 @@ def denoise_spec(denoise):
     if technique == "nl":  # (a stage of its own: RawFrames takes it through nlmeans_spec)
         raise NotImplementedError("denoising technique 'nl' is no gpet_denoise technique: with fast_mode=False it is built as a "
                                   "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built")
+    if technique == "wavelet":  # (a stage of its own as well: RawFrames takes it through wavelet_spec)
+        raise NotImplementedError("denoising technique 'wavelet' is no gpet_denoise technique: it is built as a stage of its own "
+                                  "(wavelet_spec, Context.wavelet_images) and runs when kwargs names the wavelet, e.g. "
+                                  "dict(wavelet='db1')")
     if technique in DN_NOT_BUILT:
         raise NotImplementedError("denoising technique %r is not built for the device (built: %s)"
                                   % (technique, ", ".join(sorted(DN_OF_TECHNIQUE))))
@@ -188,6 +192,150 @@ def nlmeans_spec(kwargs, taps=None):
     if taps.shape != (s, s):
         raise ValueError("denoise: the taps of a %d x %d patch are an array of that shape, not %r" % (s, s, taps.shape))
     return NlmeansSpec(ps, d, h, sigma, taps)
+
+
+# wavelet denoising (gpet_wavelet, GPET_WV_*): the second stage of its own in front of the raw-frame path
+WV_OUT_ON_DEVICE = 8  # gpet_wavelet_images: out[] are device pointers
+WV_TAPS_MAX, WV_LEVELS_MAX = 16, 16
+WV_MODES = {"soft": 0, "hard": 1}
+WV_METHODS = {"BayesShrink": 0, "VisuShrink": 1}
+WV_PPF75 = 0.6744897501960817  # scipy.stats.norm.ppf(0.75)
+WV_KEYS = ("sigma", "wavelet", "mode", "wavelet_levels", "method", "rescale_sigma", "multichannel", "convert2ycbcr")
+WV_TABLE_PATH = os.path.join(_HERE, "wavelet_table.json")
+_wv_table = None
+
+
+class GpetWavelet(C.Structure):
+    _fields_ = [("n_taps", C.c_int32), ("levels", C.c_int32), ("mode", C.c_int32), ("method", C.c_int32),
+                ("dec_lo", C.c_double * 16), ("sigma", C.c_double), ("rescale_sigma", C.c_int32), ("n_thresholds", C.c_int32),
+                ("ppf", C.c_double), ("c", C.c_double), ("thresholds", C.c_void_p), ("sigma_out", C.c_void_p),
+                ("thresholds_out", C.c_void_p), ("mean_sq_out", C.c_void_p), ("coeffs_out", C.c_void_p)]
+
+
+def wavelet_table():
+    """name -> dec_lo (list of floats) of the orthogonal wavelets the package carries (wavelet_table.json: PyWavelets' tables,
+    written by tests/golden/make_wavelet_fixture.py with 17 significant digits)."""
+    global _wv_table
+    if _wv_table is None:
+        import json
+        with open(WV_TABLE_PATH) as f:
+            _wv_table = {k: [float(v) for v in taps] for k, taps in json.load(f).items()}
+    return _wv_table
+
+
+def wavelet_max_level(n, n_taps):
+    """The largest L with (F - 1) * 2^L <= n (PyWavelets' dwt_max_level); 0 if there is none."""
+    L = 0
+    while (n_taps - 1) * 2 ** (L + 1) <= n:
+        L += 1
+    return L
+
+
+def wavelet_out_len(n, n_taps):
+    return (n + n_taps - 1) // 2
+
+
+class WaveletSpec(object):
+    """What wavelet_spec returns: ``c`` the gpet_wavelet of the call without what depends on the frames (VisuShrink's constant,
+    the injected thresholds: for_frames fills them in), ``name`` the wavelet, ``thresholds`` the injected table or None."""
+
+    def __init__(self, name, dec_lo, levels, mode, method, sigma, rescale_sigma, thresholds=None, ppf=WV_PPF75):
+        self.name, self.dec_lo = name, [float(v) for v in dec_lo]
+        self.thresholds = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        self.c = GpetWavelet(n_taps=len(self.dec_lo), levels=levels, mode=mode, method=method,
+                             dec_lo=(C.c_double * 16)(*self.dec_lo), sigma=sigma, rescale_sigma=int(rescale_sigma), ppf=ppf)
+
+    def levels_on(self, shape):
+        """The levels this spec means on (M, N) frames: its own, or max(max_level - 3, 1); ValueError for a frame the filter does
+        not fit and for an explicit value above max_level."""
+        top = wavelet_max_level(min(int(shape[0]), int(shape[1])), self.c.n_taps)
+        if top < 1:
+            raise ValueError("denoise: frames of %d x %d are below the reach of wavelet %r (%d taps): max_level is 0"
+                             % (shape[0], shape[1], self.name, self.c.n_taps))
+        if self.c.levels > top:
+            raise ValueError("denoise: wavelet_levels %d is above max_level %d of %d x %d frames under wavelet %r (the largest L with "
+                             "(F - 1) 2^L <= min(M, N))" % (self.c.levels, top, shape[0], shape[1], self.name))
+        L = self.c.levels if self.c.levels > 0 else max(top - 3, 1)
+        if L > WV_LEVELS_MAX:
+            raise ValueError("denoise: more than %d wavelet levels are not built" % WV_LEVELS_MAX)
+        return L
+
+    def pyramid(self, shape):
+        """[(mo, no, offset in doubles)] per level, finest first, and the doubles of one frame's pyramid (gpet_wavelet_plan.h:
+        wv_plan): a level's bands aa, ad, da, dd lie one after the other from its offset."""
+        m, n, off, out = int(shape[0]), int(shape[1]), 0, []
+        for _ in range(self.levels_on(shape)):
+            m, n = wavelet_out_len(m, self.c.n_taps), wavelet_out_len(n, self.c.n_taps)
+            out.append((m, n, off))
+            off += 4 * m * n
+        return out, off
+
+    def for_frames(self, T, shape):
+        """-> (gpet_wavelet of a call on T frames of ``shape``, what must stay alive as long as it is used)."""
+        L = self.levels_on(shape)
+        c = GpetWavelet.from_buffer_copy(self.c)
+        c.c = float(np.sqrt(2 * np.log(int(shape[0]) * int(shape[1]))))  # (as skimage forms it: numpy's log and sqrt)
+        keep = None
+        if self.thresholds is not None:
+            t = self.thresholds.reshape(-1, 3) if self.thresholds.size % 3 == 0 else self.thresholds.reshape(-1, 1)
+            if t.shape == (L, 3):
+                t = np.tile(t, (T, 1))
+            if t.shape != (T * L, 3):
+                raise ValueError("denoise: injected thresholds are (levels, 3) or (frames, levels, 3) = (%d, %d, 3), not %r"
+                                 % (T, L, self.thresholds.shape))
+            keep = np.ascontiguousarray(t)
+            c.thresholds, c.n_thresholds = keep.ctypes.data, keep.size
+        return c, keep
+
+
+def wavelet_spec(kwargs, thresholds=None):
+    """The keyword arguments of ``gpet_utils.denoise(image, 'wavelet', kwargs)`` = scikit-image's ``denoise_wavelet`` ->
+    WaveletSpec, decided from the arguments alone (no device): ``wavelet`` (a name of wavelet_table()), ``sigma`` (None: estimated
+    per frame), ``mode`` ('soft' / 'hard'), ``wavelet_levels`` (None: max(max_level - 3, 1)), ``method`` ('BayesShrink' /
+    'VisuShrink'), ``rescale_sigma`` (True); ``multichannel`` and ``convert2ycbcr`` only as False.  THE ``wavelet`` KEY MUST BE
+    SPELLED OUT: kwargs without it raise NotImplementedError, as 'wavelet' did before the stage was built (the library's default
+    would be 'db1').  Any other key raises ValueError naming it, and so does a wavelet that is not in the table (biorthogonal ones
+    among them) or a value the device refuses.  ``thresholds``: (levels, 3) or (frames, levels, 3) thresholds to use instead of
+    the derived ones -- level 1 (the finest) first, bands ad, da, dd; tests inject a fixture's, because the mean of squares under a
+    BayesShrink threshold is summed in the device's order, not numpy's."""
+    kw = dict(kwargs or {})
+    for k in kw:
+        if k not in WV_KEYS:
+            raise ValueError("denoise: keyword %r of 'wavelet' is not supported on the device (supported: %s)" % (k, ", ".join(WV_KEYS)))
+    if "wavelet" not in kw:
+        raise NotImplementedError("denoising technique 'wavelet' runs on the device only when kwargs names the wavelet key, e.g. "
+                                  "dict(wavelet='db1') (the library's default); without it 'wavelet' is not built")
+    for k in ("multichannel", "convert2ycbcr"):
+        if kw.get(k, False):
+            raise ValueError("denoise: %s=True of 'wavelet' is not supported on the device (frames are 2-D, single-channel)" % k)
+    name = kw["wavelet"]
+    table = wavelet_table()
+    if not isinstance(name, str) or name not in table:
+        raise ValueError("denoise: wavelet %r is not in the table of orthogonal wavelets the device runs (wavelet_table.json: %s)"
+                         % (name, ", ".join(table)))
+    mode, method = kw.get("mode", "soft"), kw.get("method", "BayesShrink")
+    if mode not in WV_MODES:
+        raise ValueError("denoise: mode %r of 'wavelet' is not supported (supported: soft, hard)" % (mode,))
+    if method not in WV_METHODS:
+        raise ValueError("denoise: method %r of 'wavelet' is not supported (supported: BayesShrink, VisuShrink)" % (method,))
+    levels = kw.get("wavelet_levels")
+    if levels is not None and (int(levels) != levels or int(levels) < 1):
+        raise ValueError("denoise: wavelet_levels %r: a whole number of at least 1, or None" % (levels,))
+    sigma = kw.get("sigma")
+    if sigma is not None and not (np.ndim(sigma) == 0 and float(sigma) > 0 and np.isfinite(float(sigma))):
+        raise ValueError("denoise: sigma %r of 'wavelet': one number above 0, or None" % (sigma,))
+    if thresholds is not None:
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thresholds.ndim not in (2, 3) or thresholds.shape[-1] != 3 or not (np.isfinite(thresholds).all() and (thresholds >= 0).all()):
+            raise ValueError("denoise: injected thresholds are finite, not negative and (levels, 3) or (frames, levels, 3)")
+    return WaveletSpec(name, table[name], 0 if levels is None else int(levels), WV_MODES[mode], WV_METHODS[method],
+                       float("nan") if sigma is None else float(sigma), bool(kw.get("rescale_sigma", True)), thresholds)
+
+
+# the stages of their own in front of the raw-frame path: technique -> (kwargs -> spec).  RawFrames.pre holds the spec,
+# RawFrames.pre_resolved runs it (Context.pre_images) into a PreFrames and hands float64 device frames on
+PRE_STAGES = {"nl": nlmeans_spec, "wavelet": wavelet_spec}
+PRE_SPECS = (NlmeansSpec, WaveletSpec)
 
 
 class GpetParams(C.Structure):
@@ -522,7 +670,8 @@ class RawFrames(object):
     Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
     ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all.
     ``denoise``: optionally how the frames are denoised on the device before the kernel is applied, a ``(technique, kwargs)``
-    pair of gpet_utils.denoise (see denoise_spec).  ``kernel=None``: frames to denoise only (Context.denoise_images).
+    pair of gpet_utils.denoise (see denoise_spec); 'nl' and 'wavelet' are stages of their own (nlmeans_spec, wavelet_spec: the
+    spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
     ``slots=(frame_of, kernel_of)``: a slot table -- ``kernel`` is then a list of kernels (split_kernels) and image g is made of
     frame ``frame_of[g]`` with kernel ``kernel_of[g]`` (the library's *_multi calls); ``len()`` stays the number of frames,
     ``n_slots`` is the number of images."""
@@ -530,12 +679,13 @@ class RawFrames(object):
     def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
-        # ('nl' is a stage of its own: the frames go through Context.nlmeans_images into device memory first -- see nlm_resolved)
-        self.nlm = None
-        if isinstance(denoise, NlmeansSpec):
-            self.nlm, denoise = denoise, None
-        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] == "nl":
-            self.nlm, denoise = nlmeans_spec(denoise[1]), None
+        # ('nl' and 'wavelet' are stages of their own: the frames go through Context.pre_images into device memory first -- see
+        # pre_resolved)
+        self.pre = None
+        if isinstance(denoise, PRE_SPECS):
+            self.pre, denoise = denoise, None
+        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGES:
+            self.pre, denoise = PRE_STAGES[denoise[0]](denoise[1]), None
         self.dn = denoise_spec(denoise)
         self.slots = None
         if slots is not None:
@@ -545,7 +695,7 @@ class RawFrames(object):
                 raise ValueError("a slot table has one frame index and one kernel index per image slot")
             kernel = self.kernels[0]
         self.kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
-        if kernel is None and self.dn is None and self.nlm is None:
+        if kernel is None and self.dn is None and self.pre is None:
             raise ValueError("raw frames need a gradient kernel or a denoising technique")
         if self.kernel is not None and (self.kernel.ndim != 2 or self.kernel.size == 0):
             raise ValueError("the gradient kernel must be a non-empty 2-D array")
@@ -560,21 +710,35 @@ class RawFrames(object):
             self.flags = 0
             self.ptrs = [f.ctypes.data for f in self.frames]
             self.shape = self.frames[0].shape
+        if self.wv is not None:
+            self.wv.levels_on(self.shape)  # (refuses levels the frames do not allow before a device is needed)
 
     def __len__(self):
         return len(self.ptrs)
 
-    def nlm_resolved(self, ctx, buf):
-        """These frames as the raw-frame calls take them: without non-local means, self; with it, the frames denoised into the
-        device memory of ``buf`` (a NlmFrames; enqueued on the context's stream) as float64 device frames with the same kernels and
-        slot table and no further denoising."""
-        if self.nlm is None:
+    @property
+    def nlm(self):
+        """The non-local means spec of these frames, or None."""
+        return self.pre if isinstance(self.pre, NlmeansSpec) else None
+
+    @property
+    def wv(self):
+        """The wavelet spec of these frames, or None."""
+        return self.pre if isinstance(self.pre, WaveletSpec) else None
+
+    def pre_resolved(self, ctx, buf):
+        """These frames as the raw-frame calls take them: without a stage of its own ('nl', 'wavelet'), self; with one, the frames
+        denoised into the device memory of ``buf`` (a PreFrames; enqueued on the context's stream) as float64 device frames with
+        the same kernels and slot table and no further denoising."""
+        if self.pre is None:
             return self
         M, N = self.shape
         ptrs = buf.reserve(len(self), M * N * 8)
-        ctx.nlmeans_images(self, out_device_ptrs=ptrs)
+        ctx.pre_images(self, out_device_ptrs=ptrs)
         kernel = self.kernels if self.slots is not None else self.kernel
         return RawFrames(kernel, device_ptrs=ptrs, dtype=np.float64, shape=(M, N), slots=self.slots)
+
+    nlm_resolved = pre_resolved
 
     def pointer_array(self):
         return (_P * len(self.ptrs))(*self.ptrs)
@@ -679,6 +843,8 @@ SYMBOLS = {
     "gpet_denoise_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetDenoise), C.c_uint,
                                       C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_nlmeans_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeans), C.c_uint,
+                                      C.POINTER(_P)]),
+    "gpet_wavelet_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetWavelet), C.c_uint,
                                       C.POINTER(_P)]),
     "gpet_grad_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                       C.POINTER(GpetDenoise), C.c_uint, C.POINTER(_P)]),
@@ -855,9 +1021,9 @@ def load():
     return lib
 
 
-class NlmFrames(object):
-    """Device memory (gpet_dev_alloc) for the float64 frames a non-local means pass leaves behind: owned by the object that
-    feeds them to the raw-frame path, grown on demand, reused from frame to frame, freed on close()."""
+class PreFrames(object):
+    """Device memory (gpet_dev_alloc) for the float64 frames a stage of its own ('nl', 'wavelet') leaves behind: owned by the
+    object that feeds them to the raw-frame path, grown on demand, reused from frame to frame, freed on close()."""
 
     def __init__(self, ctx):
         self.ctx, self.ptr, self.bytes = ctx, None, 0
@@ -882,6 +1048,9 @@ class NlmFrames(object):
             self.close()
         except Exception:
             pass
+
+
+NlmFrames = PreFrames  # (the name it had while non-local means was the only such stage)
 
 
 class Context:
@@ -931,10 +1100,10 @@ class Context:
         """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32.
         ``transpose`` (GPET_FRAMES_TRANSPOSED): (T, N, M), every image the transpose of its frame's gradient image, made on the device."""
         M, N = raw.shape
-        if raw.nlm is not None:  # (non-local means first, into device memory of this call; the calls below end with a wait)
-            buf = NlmFrames(self)
+        if raw.pre is not None:  # ('nl' / 'wavelet' first, into device memory of this call; the calls below end with a wait)
+            buf = PreFrames(self)
             try:
-                return self.grad_images(raw.nlm_resolved(self, buf), transpose)
+                return self.grad_images(raw.pre_resolved(self, buf), transpose)
             finally:
                 buf.close()
         if transpose:
@@ -965,8 +1134,8 @@ class Context:
     def denoise_images(self, raw):
         """gpet_denoise_images: every frame of ``raw`` (a RawFrames with a denoising technique) denoised in one batched pass ->
         ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters)."""
-        if raw.nlm is not None:
-            return self.nlmeans_images(raw), np.zeros(len(raw), dtype=np.int32)
+        if raw.pre is not None:
+            return self.pre_images(raw), np.zeros(len(raw), dtype=np.int32)
         if raw.dn is None:
             raise ValueError("no denoising technique")
         M, N = raw.shape
@@ -976,6 +1145,51 @@ class Context:
         self.check(self.lib.gpet_denoise_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.dn_arg(), raw.flags, op,
                                                 n_iter.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, n_iter
+
+    def pre_images(self, raw, out_device_ptrs=None):
+        """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images or wavelet_images."""
+        if raw.wv is not None:
+            return self.wavelet_images(raw, out_device_ptrs=out_device_ptrs)
+        return self.nlmeans_images(raw, out_device_ptrs=out_device_ptrs)
+
+    def wavelet_images(self, raw, out_device_ptrs=None, report=False):
+        """gpet_wavelet_images: wavelet denoising of every frame of ``raw`` (a RawFrames made with ``denoise=('wavelet', kwargs)``
+        or a WaveletSpec) in one batched pass -> (T, M, N) float64.  ``out_device_ptrs``: device addresses of float64 (M, N)
+        frames to write instead (GPET_WV_OUT_ON_DEVICE; returns None).  The call waits for the stream: a frame whose finest
+        diagonal band is all zero has no noise level and raises GpetError naming the frame.  ``report=True``: also a dict of
+        ``sigma`` (T,), ``thresholds`` and ``mean_sq`` (T, levels, 3; level 1 = finest first, bands ad, da, dd) and ``coeffs``, per
+        frame a list of dict(aa, ad, da, dd) per level (aa of every level but the coarsest holds the reconstruction)."""
+        if raw.wv is None:
+            raise ValueError("no wavelet spec")
+        M, N = raw.shape
+        T = len(raw)
+        c, keep = raw.wv.for_frames(T, (M, N))
+        rep = None
+        if report:
+            levels, fd = raw.wv.pyramid((M, N))
+            L = len(levels)
+            rep = dict(sigma=np.empty(T), thresholds=np.empty((T, L, 3)), mean_sq=np.full((T, L, 3), np.nan), pyramid=np.empty((T, fd)))
+            c.sigma_out, c.thresholds_out = rep["sigma"].ctypes.data, rep["thresholds"].ctypes.data
+            c.mean_sq_out, c.coeffs_out = rep["mean_sq"].ctypes.data, rep["pyramid"].ctypes.data
+        flags, out = raw.flags, None
+        if out_device_ptrs is not None:
+            if len(out_device_ptrs) != T:
+                raise ValueError("%d output frames for %d frames" % (len(out_device_ptrs), T))
+            op = (_P * T)(*[int(p) for p in out_device_ptrs])
+            flags |= WV_OUT_ON_DEVICE
+        else:
+            out = np.empty((T, M, N), dtype=np.float64)
+            op = (_P * T)(*[out[g].ctypes.data for g in range(T)])
+        self.check(self.lib.gpet_wavelet_images(self.h, raw.pointer_array(), T, raw.pix, M, N, C.byref(c), flags, op))
+        del keep
+        if not report:
+            return out
+        pyr = rep.pop("pyramid")
+        rep["coeffs"] = [[{k: pyr[g, off + b * mo * no: off + (b + 1) * mo * no].reshape(mo, no).copy()
+                           for b, k in enumerate(("aa", "ad", "da", "dd"))} for mo, no, off in levels] for g in range(T)]
+        if raw.wv.c.method != WV_METHODS["BayesShrink"] or raw.wv.thresholds is not None:
+            rep["mean_sq"] = None
+        return out, rep
 
     def nlmeans_images(self, raw, out_device_ptrs=None):
         """gpet_nlmeans_images: non-local means of every frame of ``raw`` (a RawFrames made with ``denoise=('nl', kwargs)`` or a
@@ -1161,10 +1375,10 @@ class Batch:
         tf = FRAMES_TRANSPOSED if transposed else 0
         self.lib = ctx.lib
         B = len(params)
-        self._nlm_buf = None  # device frames of a non-local means pass in front of the raw-frame path (NlmFrames), kept for set_images
-        if raw is not None and raw.nlm is not None:
-            self._nlm_buf = NlmFrames(ctx)
-            raw = raw.nlm_resolved(ctx, self._nlm_buf)
+        self._pre_buf = None  # device frames of a stage of its own in front of the raw-frame path (PreFrames), kept for set_images
+        if raw is not None and raw.pre is not None:
+            self._pre_buf = PreFrames(ctx)
+            raw = raw.pre_resolved(ctx, self._pre_buf)
         if image_of is not None:
             if share_image:
                 raise ValueError("share_image and image_of are alternatives")
@@ -1287,10 +1501,10 @@ class Batch:
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
             assert raw.n_slots == n_img and tuple(raw.shape) == self.frame_shape
-            if raw.nlm is not None:  # (refused before the images are swapped: the batch stays on its old frames)
-                if self._nlm_buf is None:
-                    self._nlm_buf = NlmFrames(self.ctx)
-                raw = raw.nlm_resolved(self.ctx, self._nlm_buf)
+            if raw.pre is not None:  # (refused before the images are swapped: the batch stays on its old frames)
+                if self._pre_buf is None:
+                    self._pre_buf = PreFrames(self.ctx)
+                raw = raw.pre_resolved(self.ctx, self._pre_buf)
             if raw.slots is not None:  # (gpet_batch_set_raw_images_multi: the library checks the table)
                 nk, kp, kh, kw, fo, ko = raw.multi_args()
                 self.ctx.check(self.lib.gpet_batch_set_raw_images_multi(self.h, len(raw), raw.pointer_array(), raw.pix, nk, kp, kh, kw, fo,
@@ -1707,8 +1921,8 @@ class Batch:
         if getattr(self, "h", None):
             self.lib.gpet_batch_destroy(self.h)
             self.h = None
-            if getattr(self, "_nlm_buf", None) is not None:
-                self._nlm_buf.close()
+            if getattr(self, "_pre_buf", None) is not None:
+                self._pre_buf.close()
             self.ctx._batch_closed()
 
     def __del__(self):

@@ -144,6 +144,7 @@ void gpet_ctx_destroy(gpet_ctx* c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->raw_dev) (void)hipFree(c->raw_dev);
   if (c->raw_tab) (void)hipFree(c->raw_tab);
+  if (c->wv_ws) (void)hipFree(c->wv_ws);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -563,6 +564,93 @@ int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
   // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
   if (!in_dev || !out_dev || e != hipSuccess) (void)gpet_wait(c->stream);
   HIPCHK(c, e);
+  return GPET_OK;
+}
+
+// Wavelet denoising (gpet_wavelet_plan.h).  One device block: source pointers | destination pointers | sigma [n_img] | thresholds
+// [n_img * levels * 3] | means of squares [the same].  Frames go chunk by chunk (wv_chunks): host frames and host outputs through the
+// staging slot, the pyramids through the context's workspace, 2 levels + 2 launches per chunk (+ 1 with injected thresholds).  The per-frame figures come back
+// in one copy at the end, which the call waits for: a frame without a noise level is an error.
+int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_wavelet* spec,
+                        unsigned int flags, void* const* out) {
+  if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: bad argument");
+  WvSpec sp;
+  sp.n_taps = spec->n_taps;
+  for (int k = 0; k < WV_TAPS_MAX; ++k) sp.dec_lo[k] = spec->dec_lo[k];
+  sp.levels = spec->levels;
+  sp.mode = spec->mode;
+  sp.method = spec->method;
+  sp.sigma = spec->sigma;
+  sp.rescale_sigma = spec->rescale_sigma;
+  sp.ppf = spec->ppf;
+  sp.c = spec->c;
+  sp.thresholds = spec->thresholds;
+  sp.n_thresholds = spec->n_thresholds;
+  if (const char* why = wv_check(sp, pix, M, N, n_img))
+    return fail(c, GPET_ERR_BAD_ARG, "wavelet: %s (%d taps, wavelet_levels %d, max_level %d, frames %d x %d, %d thresholds)", why, sp.n_taps,
+                sp.levels, sp.n_taps >= 2 ? wv_max_level(M < N ? M : N, sp.n_taps) : 0, M, N, sp.n_thresholds);
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: frame or output %d is a null pointer", g);
+  HIPCHK(c, hipSetDevice(c->device));
+  const WvPlan wp = wv_plan(M, N, sp.n_taps, wv_levels(sp, M, N));
+  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_WV_OUT_ON_DEVICE) != 0;
+  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
+  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
+  const size_t ws_bytes = dn_align(wp.frame_doubles * sizeof(double));
+  const StagePlan plan = wv_chunks(n_img, st_in + st_out, wp.frame_doubles);
+  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
+  if (rc) return rc;
+  rc = ctx_grow(c, &c->wv_ws, &c->wv_ws_bytes, (size_t)plan.per_chunk * ws_bytes);
+  if (rc) return rc;
+  const size_t n_thr = (size_t)n_img * wp.levels * 3;
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_sig = 2 * o_dst, o_thr = o_sig + sizeof(double) * (size_t)n_img,
+               o_ms = o_thr + sizeof(double) * n_thr, tab_bytes = o_ms + sizeof(double) * n_thr;
+  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
+  if (rc) return rc;
+  c->h_raw_tab.assign(tab_bytes, 0);
+  char* h = c->h_raw_tab.data();
+  const void** h_src = (const void**)h;
+  void** h_dst = (void**)(h + o_dst);
+  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
+  for (int k = 0; k < plan.n_chunks; ++k)
+    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
+      const int g = stage_first(plan, k) + i;
+      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
+      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
+    }
+  if (sp.thresholds) memcpy(h + o_thr, sp.thresholds, sizeof(double) * n_thr);
+  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  const void* const* d_src = (const void* const*)c->raw_tab;
+  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
+  double* d_sigma = (double*)(c->raw_tab + o_sig);
+  double* d_thr = (double*)(c->raw_tab + o_thr);
+  double* d_ms = (double*)(c->raw_tab + o_ms);
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
+    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
+    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_wavelet(c->stream, pix, d_src, d_dst, first, cnt, wp, sp, c->wv_ws, d_sigma, d_thr, d_ms);
+    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
+    for (int i = 0; i < cnt && spec->coeffs_out && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(spec->coeffs_out + (size_t)(first + i) * wp.frame_doubles, c->wv_ws + (size_t)i * wp.frame_doubles * sizeof(double),
+                         wp.frame_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h + o_sig, c->raw_tab + o_sig, tab_bytes - o_sig, hipMemcpyDeviceToHost, c->stream);
+  // (host memory of the caller and the context's own table are in flight, also after an error)
+  const hipError_t ew = gpet_wait(c->stream);
+  HIPCHK(c, e);
+  HIPCHK(c, ew);
+  const double* h_sigma = (const double*)(h + o_sig);
+  if (spec->sigma_out) memcpy(spec->sigma_out, h_sigma, sizeof(double) * (size_t)n_img);
+  if (spec->thresholds_out) memcpy(spec->thresholds_out, h + o_thr, sizeof(double) * n_thr);
+  if (spec->mean_sq_out) memcpy(spec->mean_sq_out, h + o_ms, sizeof(double) * n_thr);
+  for (int g = 0; g < n_img; ++g)
+    if (!(h_sigma[g] > 0.0 && h_sigma[g] < INFINITY))
+      return fail(c, GPET_ERR_BAD_ARG, !(sp.sigma != sp.sigma)
+                      ? "wavelet: frame %d is flat: a given sigma under rescale_sigma is scaled by (max - min) / (max - min) of the frame"
+                      : "wavelet: frame %d has no noise level: its finest diagonal band (dd of level 1) is all zero", g);
   return GPET_OK;
 }
 

@@ -60,6 +60,9 @@ struct gpet_ctx {
   char *raw_dev = nullptr, *raw_tab = nullptr;
   size_t raw_dev_bytes = 0, raw_tab_bytes = 0;
   std::vector<char> h_raw_tab;
+  // wavelet stage (gpet_wavelet_images): the coefficient pyramids of a chunk's frames (gpet_wavelet_plan.h); grown on demand
+  char* wv_ws = nullptr;
+  size_t wv_ws_bytes = 0;
   std::string err;
 };
 

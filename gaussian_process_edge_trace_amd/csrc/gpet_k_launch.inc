@@ -235,6 +235,53 @@ hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, dou
   }
   return hipGetLastError();
 }
+// ---- a0: wavelet denoising (gpet_k_wavelet.inc; geometry: gpet_wavelet_plan.h) ----
+template <typename T>
+static void launch_wv_fwd1_t(hipStream_t st, const void* const* d_src, int img0, int n, char* ws, const WvPlan& p, double scale,
+                             const WvFilters& flt) {
+  const WvLevel& v = p.lv[0];
+  const WvGrid g = wv_fwd_grid(v);
+  hipLaunchKernelGGL((k_wv_fwd<T>), dim3(g.gx, g.gy, n), dim3(WV_TILE, WV_TILE), wv_fwd_lds_bytes(p.F), st, (const T* const*)d_src, img0,
+                     (double*)ws, p.frame_doubles, (size_t)0, v.m, v.n, v.off, v.mo, v.no, p.F, scale, flt);
+}
+hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, const WvPlan& p,
+                          const WvSpec& sp, char* ws, double* d_sigma, double* d_thr, double* d_ms) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (!pix_bytes(pix) || n < 1 || n > WV_CHUNK_MAX || p.levels < 1 || p.levels > WV_LEVELS_MAX || p.F < 2 || p.F > WV_TAPS_MAX || p.F % 2 ||
+      wv_fwd_lds_bytes(p.F) > WV_LDS_MAX || wv_inv_lds_bytes(p.F) > WV_LDS_MAX)
+    return hipErrorInvalidValue;
+  for (int l = 0; l < p.levels; ++l)
+    if (wv_fwd_grid(p.lv[l]).gy > 65535 || wv_inv_grid(p.lv[l]).gy > 65535 || p.lv[l].m < p.F - 1 || p.lv[l].n < p.F - 1) return hipErrorInvalidValue;
+  const WvFilters flt = wv_filters(sp.dec_lo, p.F);
+  const bool integer = pix == PIX_U8 || pix == PIX_U16, given = !(sp.sigma != sp.sigma);
+  switch (pix) {
+    case PIX_U8: launch_wv_fwd1_t<uint8_t>(st, d_src, img0, n, ws, p, 1.0 / 255.0, flt); break;
+    case PIX_U16: launch_wv_fwd1_t<uint16_t>(st, d_src, img0, n, ws, p, 1.0 / 65535.0, flt); break;
+    case PIX_F32: launch_wv_fwd1_t<float>(st, d_src, img0, n, ws, p, 1.0, flt); break;
+    default: launch_wv_fwd1_t<double>(st, d_src, img0, n, ws, p, 1.0, flt); break;
+  }
+  for (int l = 1; l < p.levels; ++l) {
+    const WvLevel& v = p.lv[l];
+    const WvGrid g = wv_fwd_grid(v);
+    hipLaunchKernelGGL((k_wv_fwd<double>), dim3(g.gx, g.gy, n), dim3(WV_TILE, WV_TILE), wv_fwd_lds_bytes(p.F), st, (const double* const*)nullptr,
+                       img0, (double*)ws, p.frame_doubles, p.lv[l - 1].off, v.m, v.n, v.off, v.mo, v.no, p.F, 1.0, flt);
+  }
+  const int how = !given ? 0 : (integer && sp.rescale_sigma ? 1 : 2);
+  const size_t band1 = (size_t)p.lv[0].mo * p.lv[0].no;
+  hipLaunchKernelGGL(k_wv_sigma, dim3(n), dim3(WV_SIGMA_THREADS), 0, st, how, (const double*)ws, p.frame_doubles, p.lv[0].off + 3 * band1,
+                     (int)band1, d_src, pix, (size_t)p.lv[0].m * p.lv[0].n, img0, given ? sp.sigma : 0.0, sp.ppf, d_sigma);
+  if (!sp.thresholds)
+    hipLaunchKernelGGL(k_wv_thresh, dim3(3, p.levels, n), dim3(WV_THRESH_THREADS), 0, st, (const double*)ws, p, img0, sp.method, sp.c,
+                       (const double*)d_sigma, d_thr, d_ms);
+  for (int l = p.levels - 1; l >= 0; --l) {
+    const WvLevel& v = p.lv[l];
+    const WvGrid g = wv_inv_grid(v);
+    hipLaunchKernelGGL(k_wv_inv, dim3(g.gx, g.gy, n), dim3(WV_TILE, WV_TILE), wv_inv_lds_bytes(p.F), st, (double*)ws, p.frame_doubles, v.off, v.mo,
+                       v.no, l > 0 ? p.lv[l - 1].off : (size_t)0, l > 0 ? (double* const*)nullptr : d_dst, img0, v.m, v.n, p.F,
+                       (const double*)(d_thr + 3 * l), 3 * p.levels, sp.mode, l == 0 && integer ? 1 : 0, flt);
+  }
+  return hipGetLastError();
+}
 template <typename T>
 static void launch_dn_gauss_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
                               const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {

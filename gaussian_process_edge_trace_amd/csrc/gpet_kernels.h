@@ -9,6 +9,7 @@
 #include "gpet_transpose_plan.h"  // vertical batches: the index map, the tile transpose, the transposed-store convolution
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
+#include "gpet_wavelet_plan.h"  // wavelet denoising: spec, levels, pyramid layout, tiles, the threshold's summation order
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 #include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
@@ -71,6 +72,12 @@ hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src,
 // frames of the DEVICE pointer table d_dst at the same indices; s: the odd patch extent, d_taps: [s * s] on the device
 hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N, int s,
                           int d, const double* d_taps, double var2);
+// a0, wavelet denoising (gpet_wavelet_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) -> the
+// f64 frames of the DEVICE pointer table d_dst at the same indices, 2 levels + 2 launches (one fewer with injected thresholds).  ws: the
+// chunk's n pyramids; d_sigma [frames], d_thr / d_ms [frames * levels * 3] on the device, indexed by frame like the tables -- with
+// sp.thresholds the caller has filled d_thr.  sp.thresholds is only looked at for null.
+hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, const WvPlan& p,
+                          const WvSpec& sp, char* ws, double* d_sigma, double* d_thr, double* d_ms);
 hipError_t launch_fit_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int want_cov,
                               unsigned parts = ~0u);
 hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

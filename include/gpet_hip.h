@@ -264,6 +264,52 @@ typedef struct gpet_nlmeans {
  * frame or output. */
 int gpet_nlmeans_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
                         unsigned int flags, void* const* out);
+/* ---- a0: wavelet denoising, gpet_utils.denoise(image, 'wavelet', kwargs) (gpet_utils.py:137-138) -- */
+/* scikit-image 0.18.3's denoise_wavelet(image, sigma, wavelet, mode, wavelet_levels, method, rescale_sigma) on PyWavelets 1.1.1 for
+ * 2-D single-channel frames and an ORTHOGONAL wavelet given by its decomposition low-pass filter: a separable DWT with symmetric
+ * extension, the noise level from the median of the finest diagonal band, BayesShrink or VisuShrink thresholds, soft or hard
+ * shrinkage, the inverse transform.  All arithmetic is float64 in the library's order of operations (csrc/gpet_wavelet_plan.h
+ * states it); the result is float64.  A stage of its own like non-local means, about 2 levels + 2 kernel launches per staging
+ * chunk.  Two deviations: an f32 frame gives the library's result on the frame widened to f64, and the mean of squares under a
+ * BayesShrink threshold is summed in the order the plan header defines, not numpy's -- the two means differ by at most
+ * 2 (n - 1) 2^-53 relative for a band of n coefficients, and thresholds can be injected.  u8 / u16 frames enter as x / 255,
+ * x / 65535 and their result is clipped to [0, 1], as img_as_float and the library do. */
+#define GPET_WV_TAPS_MAX 16
+#define GPET_WV_SOFT 0
+#define GPET_WV_HARD 1
+#define GPET_WV_BAYES 0
+#define GPET_WV_VISU 1
+typedef struct gpet_wavelet {
+  int32_t n_taps;           /* F: taps of dec_lo, even, 2 .. 16 */
+  int32_t levels;           /* 0: max(max_level - 3, 1); else 1 .. max_level, the largest L with (F - 1) 2^L <= min(M, N) */
+  int32_t mode;             /* GPET_WV_SOFT / GPET_WV_HARD */
+  int32_t method;           /* GPET_WV_BAYES / GPET_WV_VISU */
+  double dec_lo[16];        /* the wavelet's decomposition low-pass filter (PyWavelets' dec_lo); the other three follow from it */
+  double sigma;             /* the noise standard deviation, above 0; NaN: estimated per frame */
+  int32_t rescale_sigma;    /* not 0: a given sigma of a u8 / u16 frame is scaled as the frame is (skimage's default) */
+  int32_t n_thresholds;     /* entries of thresholds: n_img * levels * 3 */
+  double ppf;               /* scipy.stats.norm.ppf(0.75) = 0.6744897501960817: the median is divided by it */
+  double c;                 /* VisuShrink: sqrt(2 log(M N)), formed by the caller */
+  const double* thresholds; /* host or NULL: thresholds to use instead of the derived ones, [frame][level, finest first][ad, da, dd] */
+  double* sigma_out;        /* host or NULL, [n_img]: the noise level of every frame */
+  double* thresholds_out;   /* host or NULL, [n_img * levels * 3]: the thresholds used */
+  double* mean_sq_out;      /* host or NULL, [n_img * levels * 3]: mean(x x) of every detail band (BayesShrink without injection) */
+  double* coeffs_out;       /* host or NULL, [n_img * frame_doubles]: every frame's pyramid, level after level (finest first), the
+                             * bands aa, ad, da, dd of a level one after the other, each (n + F - 1) / 2 per axis of the level's
+                             * input; aa of every level but the coarsest holds the reconstruction that replaced it */
+} gpet_wavelet;
+/* out[] are DEVICE pointers (f64 [M*N] each) on the context's device */
+#define GPET_WV_OUT_ON_DEVICE 8u
+/* Wavelet denoising of n_img frames [M*N] of pixel type pix: out[g] f64 [M*N] receives frame g.  Host frames go up in staging
+ * chunks; the coefficient pyramids (about 4/3 of a frame in f64 each) live in workspace the context owns, grown on demand and sized
+ * per chunk.  flags: GPET_RAW_ON_DEVICE, GPET_WV_OUT_ON_DEVICE.  The call waits for the stream before it returns: it reads every
+ * frame's noise level back.  GPET_ERR_BAD_ARG, gpet_last_error naming the cause, for a filter that is not 2 .. 16 taps (even),
+ * levels above max_level, a frame whose smaller extent the filter does not fit, an unknown mode, method or pix, sigma <= 0,
+ * thresholds of the wrong count, a null frame or output -- and, after the run, for a frame whose noise level is not a number: a
+ * finest diagonal band that is all zero (the library returns NaN there) or, with a given sigma under rescale_sigma, a flat integer
+ * frame; the message names the first such frame, and the outputs of that call are not to be used. */
+int gpet_wavelet_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_wavelet* spec,
+                        unsigned int flags, void* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
