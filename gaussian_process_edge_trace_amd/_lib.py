@@ -747,17 +747,20 @@ class RawFrames(object):
         return self.kernel.ctypes.data, self.kernel.shape[0], self.kernel.shape[1]
 
     def dn_arg(self):
-        return C.byref(self.dn)
+        return None if self.dn is None else C.byref(self.dn)
 
     @property
     def n_slots(self):
         return len(self.slots[0]) if self.slots is not None else len(self.ptrs)
 
     def multi_args(self):
-        """n_kern, kern, kh, kw, frame_of, kernel_of as the *_multi calls take them (the arrays live as long as the tuple)."""
-        nk, ns = len(self.kernels), self.n_slots
-        return (nk, (_P * nk)(*[k.ctypes.data for k in self.kernels]), (C.c_int32 * nk)(*[k.shape[0] for k in self.kernels]),
-                (C.c_int32 * nk)(*[k.shape[1] for k in self.kernels]), (C.c_int32 * ns)(*self.slots[0]), (C.c_int32 * ns)(*self.slots[1]))
+        """n_kern, kern, kh, kw, frame_of, kernel_of as the *_multi calls and gpet_band_images take them (the arrays live as long as
+        the tuple).  Without a slot table: the one kernel on every frame in order, the slot table of the single-kernel calls."""
+        ks = self.kernels if self.slots is not None else [self.kernel]
+        fo, ko = self.slots if self.slots is not None else (range(len(self)), [0] * len(self))
+        nk, ns = len(ks), len(fo)
+        return (nk, (_P * nk)(*[k.ctypes.data for k in ks]), (C.c_int32 * nk)(*[k.shape[0] for k in ks]),
+                (C.c_int32 * nk)(*[k.shape[1] for k in ks]), (C.c_int32 * ns)(*fo), (C.c_int32 * ns)(*ko))
 
 
 class GpetBand(C.Structure):
@@ -1118,8 +1121,8 @@ class Context:
             out = np.empty((ns, Mo, No), dtype=np.float32)
             op = (_P * ns)(*[out[g].ctypes.data for g in range(ns)])
             nk, kp, kh, kw, fo, ko = raw.multi_args()
-            self.check(self.lib.gpet_grad_images_multi(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, nk, kp, kh, kw,
-                                                       raw.dn_arg() if raw.dn is not None else None, ns, fo, ko, flags, op))
+            self.check(self.lib.gpet_grad_images_multi(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, nk, kp, kh, kw, raw.dn_arg(),
+                                                       ns, fo, ko, flags, op))
             return out
         out = np.empty((len(raw), Mo, No), dtype=np.float32)
         op = (_P * len(raw))(*[out[g].ctypes.data for g in range(len(raw))])
@@ -1152,6 +1155,18 @@ class Context:
             return self.wavelet_images(raw, out_device_ptrs=out_device_ptrs)
         return self.nlmeans_images(raw, out_device_ptrs=out_device_ptrs)
 
+    @staticmethod
+    def _pre_out(raw, out_device_ptrs, on_device):
+        """Where a stage of its own writes -> (array or None, pointers, flags): the device addresses given, one per frame, with the
+        stage's ``on_device`` flag, or a fresh (T, M, N) float64 array."""
+        T = len(raw)
+        if out_device_ptrs is not None:
+            if len(out_device_ptrs) != T:
+                raise ValueError("%d output frames for %d frames" % (len(out_device_ptrs), T))
+            return None, (_P * T)(*[int(p) for p in out_device_ptrs]), raw.flags | on_device
+        out = np.empty((T,) + tuple(raw.shape), dtype=np.float64)
+        return out, (_P * T)(*[out[g].ctypes.data for g in range(T)]), raw.flags
+
     def wavelet_images(self, raw, out_device_ptrs=None, report=False):
         """gpet_wavelet_images: wavelet denoising of every frame of ``raw`` (a RawFrames made with ``denoise=('wavelet', kwargs)``
         or a WaveletSpec) in one batched pass -> (T, M, N) float64.  ``out_device_ptrs``: device addresses of float64 (M, N)
@@ -1171,15 +1186,7 @@ class Context:
             rep = dict(sigma=np.empty(T), thresholds=np.empty((T, L, 3)), mean_sq=np.full((T, L, 3), np.nan), pyramid=np.empty((T, fd)))
             c.sigma_out, c.thresholds_out = rep["sigma"].ctypes.data, rep["thresholds"].ctypes.data
             c.mean_sq_out, c.coeffs_out = rep["mean_sq"].ctypes.data, rep["pyramid"].ctypes.data
-        flags, out = raw.flags, None
-        if out_device_ptrs is not None:
-            if len(out_device_ptrs) != T:
-                raise ValueError("%d output frames for %d frames" % (len(out_device_ptrs), T))
-            op = (_P * T)(*[int(p) for p in out_device_ptrs])
-            flags |= WV_OUT_ON_DEVICE
-        else:
-            out = np.empty((T, M, N), dtype=np.float64)
-            op = (_P * T)(*[out[g].ctypes.data for g in range(T)])
+        out, op, flags = self._pre_out(raw, out_device_ptrs, WV_OUT_ON_DEVICE)
         self.check(self.lib.gpet_wavelet_images(self.h, raw.pointer_array(), T, raw.pix, M, N, C.byref(c), flags, op))
         del keep
         if not report:
@@ -1198,17 +1205,8 @@ class Context:
         if raw.nlm is None:
             raise ValueError("no non-local means spec")
         M, N = raw.shape
-        T = len(raw)
-        if out_device_ptrs is not None:
-            if len(out_device_ptrs) != T:
-                raise ValueError("%d output frames for %d frames" % (len(out_device_ptrs), T))
-            op = (_P * T)(*[int(p) for p in out_device_ptrs])
-            self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), T, raw.pix, M, N, raw.nlm.arg(),
-                                                    raw.flags | NLM_OUT_ON_DEVICE, op))
-            return None
-        out = np.empty((T, M, N), dtype=np.float64)
-        op = (_P * T)(*[out[g].ctypes.data for g in range(T)])
-        self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), T, raw.pix, M, N, raw.nlm.arg(), raw.flags, op))
+        out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
+        self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlm.arg(), flags, op))
         return out
 
     def normalise_f32(self, img):
@@ -1420,12 +1418,7 @@ class Batch:
             bd = GpetBand(H, n_pair, None if r0a is None else r0a.ctypes.data_as(C.POINTER(C.c_int64)), (C.c_int32 * B)(*pair_of))
             im = GpetBandImages()
             if raw is not None:
-                if raw.slots is not None:
-                    nk, kp, kh, kw, fo, ko = raw.multi_args()
-                else:  # (one kernel on every frame in order: the slot table of the single-kernel calls)
-                    kp = (_P * 1)(raw.kernel.ctypes.data)
-                    kh, kw = (C.c_int32 * 1)(raw.kernel.shape[0]), (C.c_int32 * 1)(raw.kernel.shape[1])
-                    nk, fo, ko = 1, (C.c_int32 * len(raw))(*range(len(raw))), (C.c_int32 * len(raw))()
+                nk, kp, kh, kw, fo, ko = raw.multi_args()  # (one kernel: on every frame in order)
                 pr = raw.pointer_array()
                 im.raw, im.pix, im.n_frames, im.n_kern = C.cast(pr, C.POINTER(C.c_void_p)), raw.pix, len(raw), nk
                 im.kern, im.kh, im.kw, im.frame_of, im.kernel_of = C.cast(kp, C.POINTER(C.c_void_p)), kh, kw, fo, ko
@@ -1438,27 +1431,22 @@ class Batch:
             self.band_rows = H
         elif image_of is not None:  # (the library checks the map: its message says what is wrong with it)
             if raw is not None and raw.slots is not None:
-                nk, kp, kh, kw, fo, ko = raw.multi_args()
                 ctx.check(self.lib.gpet_batch_create_raw_multi(ctx.h, B, self.M, self.N, n_img, io, len(raw), raw.pointer_array(), raw.pix,
-                                                               nk, kp, kh, kw, fo, ko, raw.dn_arg() if raw.dn is not None else None,
-                                                               pa, ip, raw.flags | tf, C.byref(h)))
+                                                               *raw.multi_args(), raw.dn_arg(), pa, ip, raw.flags | tf, C.byref(h)))
             elif raw is not None:
-                kp, kh, kw = raw.kernel_args()
-                ctx.check(self.lib.gpet_batch_create_raw_mapped(ctx.h, B, self.M, self.N, n_img, io, raw.pointer_array(), raw.pix, kp,
-                                                                kh, kw, raw.dn_arg() if raw.dn is not None else None, pa, ip,
-                                                                raw.flags | tf, C.byref(h)))
+                ctx.check(self.lib.gpet_batch_create_raw_mapped(ctx.h, B, self.M, self.N, n_img, io, raw.pointer_array(), raw.pix,
+                                                                *raw.kernel_args(), raw.dn_arg(), pa, ip, raw.flags | tf, C.byref(h)))
             else:
                 ctx.check(self.lib.gpet_batch_create_mapped(ctx.h, B, self.M, self.N, n_img, io, gp, pa, ip, flags | tf, C.byref(h)))
         elif raw is not None:
             if raw.slots is not None:
                 raise ValueError("a slot table comes with the image map of its slots (image_of)")
             assert len(raw) == (1 if share_image else B)
-            kp, kh, kw = raw.kernel_args()
             if raw.dn is not None:
-                ctx.check(self.lib.gpet_batch_create_raw_dn(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
+                ctx.check(self.lib.gpet_batch_create_raw_dn(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, *raw.kernel_args(),
                                                             raw.dn_arg(), 1 if share_image else 0, pa, ip, raw.flags | tf, C.byref(h)))
             else:
-                ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, kp, kh, kw,
+                ctx.check(self.lib.gpet_batch_create_raw(ctx.h, B, self.M, self.N, raw.pointer_array(), raw.pix, *raw.kernel_args(),
                                                          1 if share_image else 0, pa, ip, raw.flags | tf, C.byref(h)))
         else:
             ctx.check(self.lib.gpet_batch_create2(ctx.h, B, self.M, self.N, gp, 1 if share_image else 0, pa, ip, flags | tf,
@@ -1506,17 +1494,13 @@ class Batch:
                     self._pre_buf = PreFrames(self.ctx)
                 raw = raw.pre_resolved(self.ctx, self._pre_buf)
             if raw.slots is not None:  # (gpet_batch_set_raw_images_multi: the library checks the table)
-                nk, kp, kh, kw, fo, ko = raw.multi_args()
-                self.ctx.check(self.lib.gpet_batch_set_raw_images_multi(self.h, len(raw), raw.pointer_array(), raw.pix, nk, kp, kh, kw, fo,
-                                                                        ko, raw.dn_arg() if raw.dn is not None else None,
-                                                                        raw.flags | nf))
-                return
-            kp, kh, kw = raw.kernel_args()
-            if raw.dn is not None:
-                self.ctx.check(self.lib.gpet_batch_set_raw_images_dn(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.dn_arg(),
-                                                                     raw.flags | nf))
-                return
-            self.ctx.check(self.lib.gpet_batch_set_raw_images(self.h, raw.pointer_array(), raw.pix, kp, kh, kw, raw.flags | nf))
+                self.ctx.check(self.lib.gpet_batch_set_raw_images_multi(self.h, len(raw), raw.pointer_array(), raw.pix, *raw.multi_args(),
+                                                                        raw.dn_arg(), raw.flags | nf))
+            elif raw.dn is not None:
+                self.ctx.check(self.lib.gpet_batch_set_raw_images_dn(self.h, raw.pointer_array(), raw.pix, *raw.kernel_args(),
+                                                                     raw.dn_arg(), raw.flags | nf))
+            else:
+                self.ctx.check(self.lib.gpet_batch_set_raw_images(self.h, raw.pointer_array(), raw.pix, *raw.kernel_args(), raw.flags | nf))
             return
         if device_ptrs is not None:
             assert len(device_ptrs) == n_img

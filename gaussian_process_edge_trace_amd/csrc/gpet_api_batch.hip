@@ -54,32 +54,40 @@ static int upload_images(gpet_batch* b, const float* const* grad, unsigned int f
 // gpet_batch_set_raw_images).  Either way the arena's EdgeDev::grad buffers hold the normalised images afterwards.
 struct ImageSource {
   const float* const* grad = nullptr;  // gradient images, or
-  const void* const* raw = nullptr;    // raw frames of pixel type pix, with
-  int pix = 0;
-  const double* kern = nullptr;        // the kh x kw kernel of gpet_utils.comp_grad_img
-  int kh = 0, kw = 0;
-  const DenoiseSpec* dn = nullptr;     // and, optionally, how the frames are denoised first (gpet_denoise_plan.h)
+  RawSourceArgs args;                  // raw frames (args.raw) with their kernels, as the entry point's arguments describe them
   unsigned int flags = 0;              // GPET_GRAD_ON_DEVICE / GPET_RAW_ON_DEVICE (and GPET_IMAGES_NEXT_FRAME, not read here)
-  // or raw frames with a slot table (gpet_conv_multi_plan.h): n_frames of them, slot g made of frame multi->frame_of[g] with
-  // kernel multi->kernel_of[g]; kern / kh / kw are then unused
-  const ConvMulti* multi = nullptr;
-  int n_frames = 0;
+  ImageSource(const float* const* grad_, unsigned int flags_) : grad(grad_), flags(flags_) {}
+  // raw frames with one kernel (one image per frame: the batch says how many, check_batch_source) or with a slot table
+  ImageSource(const void* const* raw, int pix, const double* kern, int kh, int kw, const gpet_denoise* dn, unsigned int flags_) : flags(flags_) {
+    args.frames(raw, 0, pix, dn, flags);
+    args.one_kernel(kern, kh, kw);
+  }
+  ImageSource(const void* const* raw, int n_frames, int pix, const gpet_denoise* dn, unsigned int flags_) : flags(flags_) {
+    args.frames(raw, n_frames, pix, dn, flags);
+  }
+  bool is_raw() const { return args.raw.frames != nullptr; }
 };
+
+// what a batch of `count` images, made of frames that lie as Mf x Nf (tr: transposed into the batch), fills in of a source: one
+// kernel makes one image of every frame
+static void batch_source(RawSource& s, int count, int Mf, int Nf, bool tr) {
+  if (!s.table) s.n_frames = s.n_img = count;
+  s.M = Mf;
+  s.N = Nf;
+  s.tr = tr;
+}
 
 // raw frames -> comp_grad_img of each, straight into the arena: one batched pass on the device (conv_frames), no trip of a
 // gradient image through host memory.  One normalisation: the second one of the two-step path (comp_grad_img, then gpet.py:97)
 // subtracts a minimum of exactly 0 and divides by a span of exactly 1.
-static int convolve_images(gpet_batch* b, const ImageSource& s) {
+static int convolve_images(gpet_batch* b, RawSource s) {
   gpet_ctx* c = b->ctx;
   const int n_img = b->n_img;
   std::vector<float*> dst((size_t)n_img);
   for (int g = 0; g < n_img; ++g) dst[(size_t)g] = (float*)b->h_edges[b->img_rep[g]].grad;
-  const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
   const bool tr = b->transposed;  // (the frames are then bd.N rows of bd.M pixels, and the slots receive their transposes)
-  const int Mf = tr ? b->bd.N : b->bd.M, Nf = tr ? b->bd.M : b->bd.N;
-  const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, Mf, Nf, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax, tr)
-                         : conv_frames(c, s.raw, n_img, s.pix, Mf, Nf, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax, nullptr,
-                                       nullptr, tr);
+  batch_source(s, n_img, tr ? b->bd.N : b->bd.M, tr ? b->bd.M : b->bd.N, tr);
+  const int rc = conv_frames(c, s, dst.data(), b->d_minmax);
   if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
   return rc;
 }
@@ -97,11 +105,10 @@ static int band_load_full(gpet_batch* b, const ImageSource& s) {
   for (int p = 0; p < bs.n_pair; ++p) dst[(size_t)p] = bs.G + (size_t)p * px;
   const bool tr = b->transposed;
   const int Mf = tr ? b->bd.N : bs.M, Nf = tr ? bs.M : b->bd.N;  // the frame as it lies in the caller's memory
-  if (s.raw) {
-    const bool on_dev = (s.flags & GPET_RAW_ON_DEVICE) != 0;
-    const int rc = s.multi ? conv_frames_multi(c, s.raw, s.n_frames, s.pix, Mf, Nf, s.dn, *s.multi, on_dev, dst.data(), b->d_minmax, tr)
-                           : conv_frames(c, s.raw, bs.n_pair, s.pix, Mf, Nf, s.dn, s.kern, s.kh, s.kw, on_dev, dst.data(), b->d_minmax, nullptr,
-                                         nullptr, tr);
+  if (s.is_raw()) {
+    RawSource rs = s.args.raw;
+    batch_source(rs, bs.n_pair, Mf, Nf, tr);
+    const int rc = conv_frames(c, rs, dst.data(), b->d_minmax);
     if (rc) (void)gpet_wait(c->stream);  // (host frames already enqueued must not be read after the return)
     return rc;
   }
@@ -147,7 +154,7 @@ static int load_images(gpet_batch* b, const ImageSource& s) {
     const int rc = band_load_full(b, s);
     return rc ? rc : band_slots(b);
   }
-  return s.raw ? convolve_images(b, s) : upload_images(b, s.grad, s.flags);
+  return s.is_raw() ? convolve_images(b, s.args.raw) : upload_images(b, s.grad, s.flags);
 }
 
 // smallest and largest init row of an edge
@@ -207,24 +214,15 @@ static int image_kde(gpet_batch* b) {
   return GPET_OK;
 }
 
-// what can be refused before anything is allocated or enqueued (conv_frames checks the same on its own)
+// what can be refused before anything is allocated or enqueued, for a batch of `count` images (conv_frames checks the same on its own)
 // (tr: for a vertical batch, against the LDS bounds of the transposed-store kernels)
-static int check_raw_source(gpet_ctx* c, const ImageSource& s, int n_img, bool tr) {
-  if (!s.raw || (!s.multi && (!s.kern || s.kh <= 0 || s.kw <= 0))) return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
-  if (!pix_bytes(s.pix)) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", s.pix);
-  if (s.multi) {
-    if (s.multi->n_img != n_img)
-      return fail(c, GPET_ERR_BAD_ARG, "slot table: %d slots for a batch of %d image slots", s.multi->n_img, n_img);
-    const int rc = check_conv_multi(c, *s.multi, s.n_frames, tr);
-    if (rc) return rc;
-  } else if (!(tr ? conv_t_fits_lds(s.kh, s.kw) : conv_fits_lds(s.kh, s.kw)))
-    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", s.kh, s.kw,
-                tr ? conv_t_lds_bytes(s.kh, s.kw) : conv_lds_bytes(s.kh, s.kw), CONV_LDS_MAX);
-  if (s.dn)
-    if (const char* why = dn_check(*s.dn, s.pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
-  for (int g = 0; g < (s.multi ? s.n_frames : n_img); ++g)
-    if (!s.raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
-  return GPET_OK;
+static int check_batch_source(gpet_ctx* c, const ImageSource& src, int count, bool tr) {
+  RawSource s = src.args.raw;
+  batch_source(s, count, 0, 0, tr);
+  // (between the pixel type and the table in check_raw_source's order; every entry point hands over the batch's own count today)
+  if (s.frames && pix_bytes(s.pix) && s.n_img != count)
+    return fail(c, GPET_ERR_BAD_ARG, "slot table: %d slots for a batch of %d image slots", s.n_img, count);
+  return check_raw_source(c, s);
 }
 
 int gpet_batch_create(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
@@ -300,7 +298,7 @@ static int setup_struct_basis(gpet_batch* b, const int64_t* const* init_xy) {
 static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource& src, int share_image, int n_img,
                              const int32_t* image_of, const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out,
                              const gpet_band* band = nullptr) {
-  if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.raw) || !params || !init_xy)
+  if (!c || !out || !batch_shape_ok(B, M, N) || (!src.grad && !src.is_raw()) || !params || !init_xy)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create: bad argument");
   *out = nullptr;
   const bool tr = (src.flags & GPET_FRAMES_TRANSPOSED) != 0;
@@ -344,8 +342,8 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   } else {
     n_img = share_image ? 1 : B;
   }
-  if (src.raw) {
-    const int rc0 = check_raw_source(c, src, band ? band->n_pair : n_img, tr);
+  if (src.is_raw()) {
+    const int rc0 = check_batch_source(c, src, band ? band->n_pair : n_img, tr);
     if (rc0) return rc0;
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -460,19 +458,13 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
 
 int gpet_batch_create2(gpet_ctx* c, int B, int M, int N, const float* const* grad, int share_image,
                        const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
-  ImageSource src;
-  src.grad = grad;
-  src.flags = flags;
-  return batch_create_from(c, B, M, N, src, share_image, 0, nullptr, params, init_xy, out);
+  return batch_create_from(c, B, M, N, ImageSource(grad, flags), share_image, 0, nullptr, params, init_xy, out);
 }
 
 int gpet_batch_create_mapped(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, const float* const* grad,
                              const gpet_params* params, const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
   if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
-  ImageSource src;
-  src.grad = grad;
-  src.flags = flags;
-  return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
+  return batch_create_from(c, B, M, N, ImageSource(grad, flags), 0, n_img, image_of, params, init_xy, out);
 }
 
 int gpet_batch_create_raw_mapped(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, const void* const* raw, int pix,
@@ -480,16 +472,7 @@ int gpet_batch_create_raw_mapped(gpet_ctx* c, int B, int M, int N, int n_img, co
                                  const int64_t* const* init_xy, unsigned int flags, gpet_batch** out) {
   if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_mapped: bad argument");
   if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
-  const DenoiseSpec spec = dn_spec(dn);
-  ImageSource src;
-  src.raw = raw;
-  src.pix = pix;
-  src.kern = kern;
-  src.kh = kh;
-  src.kw = kw;
-  src.dn = dn ? &spec : nullptr;
-  src.flags = flags;
-  return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
+  return batch_create_from(c, B, M, N, ImageSource(raw, pix, kern, kh, kw, dn, flags), 0, n_img, image_of, params, init_xy, out);
 }
 
 int gpet_batch_create_raw_multi(gpet_ctx* c, int B, int M, int N, int n_img, const int32_t* image_of, int n_frames, const void* const* raw,
@@ -498,15 +481,8 @@ int gpet_batch_create_raw_multi(gpet_ctx* c, int B, int M, int N, int n_img, con
                                 unsigned int flags, gpet_batch** out) {
   if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_multi: bad argument");
   if (!image_of) return fail(c, GPET_ERR_BAD_ARG, "image map: image_of is a null pointer");
-  const DenoiseSpec spec = dn_spec(dn);
-  const ConvMulti mk{n_kern, kern, kh, kw, n_img, frame_of, kernel_of};
-  ImageSource src;
-  src.raw = raw;
-  src.pix = pix;
-  src.dn = dn ? &spec : nullptr;
-  src.flags = flags;
-  src.multi = &mk;
-  src.n_frames = n_frames;
+  ImageSource src(raw, n_frames, pix, dn, flags);
+  src.args.slot_table(n_kern, kern, kh, kw, n_img, frame_of, kernel_of);
   return batch_create_from(c, B, M, N, src, 0, n_img, image_of, params, init_xy, out);
 }
 
@@ -514,16 +490,7 @@ int gpet_batch_create_raw_dn(gpet_ctx* c, int B, int M, int N, const void* const
                              const gpet_denoise* dn, int share_image, const gpet_params* params, const int64_t* const* init_xy,
                              unsigned int flags, gpet_batch** out) {
   if (!raw || !kern) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_raw_dn: bad argument");
-  const DenoiseSpec spec = dn_spec(dn);
-  ImageSource src;
-  src.raw = raw;
-  src.pix = pix;
-  src.kern = kern;
-  src.kh = kh;
-  src.kw = kw;
-  src.dn = dn ? &spec : nullptr;
-  src.flags = flags;
-  return batch_create_from(c, B, M, N, src, share_image, 0, nullptr, params, init_xy, out);
+  return batch_create_from(c, B, M, N, ImageSource(raw, pix, kern, kh, kw, dn, flags), share_image, 0, nullptr, params, init_xy, out);
 }
 
 int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* raw, int pix, const double* kern, int kh, int kw,
@@ -535,21 +502,11 @@ int gpet_batch_create_raw(gpet_ctx* c, int B, int M, int N, const void* const* r
 int gpet_batch_create_banded(gpet_ctx* c, int B, int M, int N, const gpet_band* band, const gpet_band_images* im,
                              const gpet_params* params, const int64_t* const* init_xy, gpet_batch** out) {
   if (!band || !im || (!im->grad && !im->raw)) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_banded: bad argument");
-  ImageSource src;
-  src.flags = im->flags;
-  if (im->grad) {
-    src.grad = im->grad;
-    return batch_create_from(c, B, M, N, src, 0, 0, nullptr, params, init_xy, out, band);
-  }
+  if (im->grad) return batch_create_from(c, B, M, N, ImageSource(im->grad, im->flags), 0, 0, nullptr, params, init_xy, out, band);
   if (!im->kern || !im->kh || !im->kw || !im->frame_of || !im->kernel_of)
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_create_banded: raw frames need their kernels and the slot table");
-  const DenoiseSpec spec = dn_spec(im->dn);
-  const ConvMulti mk{im->n_kern, im->kern, im->kh, im->kw, band->n_pair, im->frame_of, im->kernel_of};
-  src.raw = im->raw;
-  src.pix = im->pix;
-  src.dn = im->dn ? &spec : nullptr;
-  src.multi = &mk;
-  src.n_frames = im->n_frames;
+  ImageSource src(im->raw, im->n_frames, im->pix, im->dn, im->flags);
+  src.args.slot_table(im->n_kern, im->kern, im->kh, im->kw, band->n_pair, im->frame_of, im->kernel_of);
   return batch_create_from(c, B, M, N, src, 0, 0, nullptr, params, init_xy, out, band);
 }
 
@@ -1122,15 +1079,21 @@ static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
   return batch_reset(b, (flags & GPET_IMAGES_NEXT_FRAME) != 0);
 }
 
+// raw frames: the orientation, then everything check_raw_source refuses, before the batch is touched
+static int batch_set_raw_from(gpet_batch* b, const ImageSource& src) {
+  const int rc_o = check_set_orientation(b, src.flags);
+  if (rc_o) return rc_o;
+  const int rc = check_batch_source(b->ctx, src, batch_source_count(b), b->transposed);
+  if (rc) return rc;
+  return batch_set_images_from(b, src);
+}
+
 int gpet_batch_set_images(gpet_batch* b, const float* const* grad, unsigned int flags) {
   GPET_BATCH_SCOPE(b);
   if (!b || !grad) return GPET_ERR_BAD_ARG;
   const int rc_o = check_set_orientation(b, flags);
   if (rc_o) return rc_o;
-  ImageSource src;
-  src.grad = grad;
-  src.flags = flags;
-  return batch_set_images_from(b, src);
+  return batch_set_images_from(b, ImageSource(grad, flags));
 }
 
 // (a refused call -- unknown pixel type, null frame, oversized kernel, a denoising spec that cannot run -- has touched nothing:
@@ -1139,20 +1102,7 @@ int gpet_batch_set_raw_images_dn(gpet_batch* b, const void* const* raw, int pix,
                                  const gpet_denoise* dn, unsigned int flags) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
-  const DenoiseSpec spec = dn_spec(dn);
-  ImageSource src;
-  src.raw = raw;
-  src.pix = pix;
-  src.kern = kern;
-  src.kh = kh;
-  src.kw = kw;
-  src.dn = dn ? &spec : nullptr;
-  src.flags = flags;
-  const int rc_o = check_set_orientation(b, flags);
-  if (rc_o) return rc_o;
-  const int rc = check_raw_source(b->ctx, src, batch_source_count(b), b->transposed);
-  if (rc) return rc;
-  return batch_set_images_from(b, src);
+  return batch_set_raw_from(b, ImageSource(raw, pix, kern, kh, kw, dn, flags));
 }
 
 // (refused as gpet_batch_set_raw_images_dn refuses, and for a table slot_table_check or the LDS bound refuses: nothing touched)
@@ -1161,20 +1111,9 @@ int gpet_batch_set_raw_images_multi(gpet_batch* b, int n_frames, const void* con
                                     const gpet_denoise* dn, unsigned int flags) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
-  const DenoiseSpec spec = dn_spec(dn);
-  const ConvMulti mk{n_kern, kern, kh, kw, batch_source_count(b), frame_of, kernel_of};
-  ImageSource src;
-  src.raw = raw;
-  src.pix = pix;
-  src.dn = dn ? &spec : nullptr;
-  src.flags = flags;
-  src.multi = &mk;
-  src.n_frames = n_frames;
-  const int rc_o = check_set_orientation(b, flags);
-  if (rc_o) return rc_o;
-  const int rc = check_raw_source(b->ctx, src, batch_source_count(b), b->transposed);
-  if (rc) return rc;
-  return batch_set_images_from(b, src);
+  ImageSource src(raw, n_frames, pix, dn, flags);
+  src.args.slot_table(n_kern, kern, kh, kw, batch_source_count(b), frame_of, kernel_of);
+  return batch_set_raw_from(b, src);
 }
 
 int gpet_batch_set_raw_images(gpet_batch* b, const void* const* raw, int pix, const double* kern, int kh, int kw, unsigned int flags) {

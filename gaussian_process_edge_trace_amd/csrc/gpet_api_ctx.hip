@@ -1,5 +1,5 @@
-// C ABI of libgpet_hip.so (include/gpet_hip.h), part 1: contexts, options, timers, the gradient image (a1), and the helpers the
-// other parts share.
+// C ABI of libgpet_hip.so (include/gpet_hip.h), part 1: contexts, options, timers, a1 for one image (gpet_grad_image,
+// gpet_normalise_f32), and the helpers the other parts share.  Stacks of raw frames: gpet_api_frames.hip.
 #include "gpet_api_internal.h"
 
 // Host waits.  hipStreamSynchronize spins on a CPU core; with one process per GPU and a few driver threads per process
@@ -73,6 +73,20 @@ int fin_lattice(const double* x, int n, double* hinv) {
   }
   *hinv = hi_;
   return (int)mr;
+}
+
+// ---- a1 -------------------------------------------------------------------------------
+// The a1 entry points keep their device scratch in the context: one allocation, grown on demand, freed with the
+// context -- nothing to leak on an error path and no hipMalloc/hipFree per call.
+int ctx_scratch(gpet_ctx* c, size_t bytes) {
+  if (bytes <= c->scratch_bytes) return GPET_OK;
+  HIPCHK(c, gpet_wait(c->stream));
+  if (c->scratch) (void)hipFree(c->scratch);
+  c->scratch = nullptr;
+  c->scratch_bytes = 0;
+  HIPCHK(c, hipMalloc(&c->scratch, bytes));
+  c->scratch_bytes = bytes;
+  return GPET_OK;
 }
 
 extern "C" {
@@ -174,20 +188,6 @@ int gpet_timer_stop_ms(gpet_ctx* c, float* ms) {
   return GPET_OK;
 }
 
-// ---- a1 -------------------------------------------------------------------------------
-// The a1 entry points keep their device scratch in the context: one allocation, grown on demand, freed with the
-// context -- nothing to leak on an error path and no hipMalloc/hipFree per call.
-static int ctx_scratch(gpet_ctx* c, size_t bytes) {
-  if (bytes <= c->scratch_bytes) return GPET_OK;
-  HIPCHK(c, gpet_wait(c->stream));
-  if (c->scratch) (void)hipFree(c->scratch);
-  c->scratch = nullptr;
-  c->scratch_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->scratch, bytes));
-  c->scratch_bytes = bytes;
-  return GPET_OK;
-}
-
 int gpet_grad_image(gpet_ctx* c, const double* img, int M, int N, const double* kern, int kh, int kw, float* out) {
   if (!c || !img || !kern || !out || M <= 0 || N <= 0 || kh <= 0 || kw <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_image: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -222,438 +222,6 @@ int gpet_grad_image(gpet_ctx* c, const double* img, int M, int N, const double* 
   return GPET_OK;
 }
 
-// ---- a1 for stacks of raw frames ------------------------------------------------------
-}  // extern "C"
-
-static_assert(DN_NONE == GPET_DN_NONE && DN_MEDIAN == GPET_DN_MEDIAN && DN_MINIMUM == GPET_DN_MINIMUM && DN_GAUSSIAN == GPET_DN_GAUSSIAN &&
-                  DN_TVC == GPET_DN_TVC && DN_MODE_REFLECT == GPET_DN_MODE_REFLECT && DN_MODE_NEAREST == GPET_DN_MODE_NEAREST,
-              "gpet_denoise_plan.h numbers techniques and modes as include/gpet_hip.h does");
-
-// (device memory of the context that only grows; the stream is idle when it is replaced)
-static int ctx_grow(gpet_ctx* c, char** mem, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return GPET_OK;
-  HIPCHK(c, gpet_wait(c->stream));
-  if (*mem) (void)hipFree(*mem);
-  *mem = nullptr;
-  *cap = 0;
-  HIPCHK(c, hipMalloc((void**)mem, bytes));
-  *cap = bytes;
-  return GPET_OK;
-}
-
-// n_img raw frames -> normalised f32 gradient images dst[g] (device), everything enqueued on the context's stream: the taps and
-// the pointer tables go up in one copy, host frames follow in the chunks of stage_plan (gpet_conv_plan.h) with ONE convolution
-// launch per chunk, device frames are read where they lie by one launch; one launch normalises all images.  Host frames are
-// copied straight out of the caller's (pageable) memory: packing each chunk into a ring of pinned slots first, so that the host
-// packs chunk k + 1 while the device works on chunk k, was built and measured -- 256 frames of 500 x 500: u8 8.8 against 8.8 ms,
-// f32 16.5 against 14.5, f64 20.7 against 18.6 -- and removed.  Nothing is waited for at the end: the caller waits before host
-// frames (and the context's tables) may change.  d_mm: [2 n_img] on the device.
-// With a denoising spec (dn, technique not NONE: gpet_denoise_plan.h) every chunk is denoised where it was staged before it is
-// convolved: the chunk's workspace follows its frames in the staging slot, the convolution reads the denoised frames in the pixel
-// type the technique leaves behind, and frames on the device go through chunks of the same budget too.  'tvc' iterates a chunk to
-// its end -- groups of DN_TVC_GROUP iterations, the count of finished images read between groups -- before the next is staged.
-// kern == nullptr: no convolution (gpet_denoise_images); dn_out: host buffers the denoised frames are copied to, n_iter_out: host
-// [n_img] iterations per image.
-// mk (may be nullptr): a slot table (gpet_conv_multi_plan.h).  n_img then counts the FRAMES -- staged and denoised once each, in
-// the same chunks -- while dst[] and d_mm are per slot (mk->n_img of them): one k_conv_relu_multi launch per chunk writes every
-// slot of the chunk's frames, and the kernels' taps, descriptors and the slot lists go up in the same one table copy.
-static int conv_frames_body(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
-                            int kh, int kw, const ConvMulti* mk, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out,
-                            int32_t* n_iter_out, bool tr) {
-  const size_t esz = (size_t)pix_bytes(pix);
-  const bool dn_on = dn && dn->technique != DN_NONE;
-  if (!esz) return fail(c, GPET_ERR_BAD_ARG, "unknown pixel type %d (GPET_PIX_U8 = 0 .. GPET_PIX_F64 = 3)", pix);
-  if (!raw || n_img <= 0 || M <= 0 || N <= 0 || (!kern && !dn_on) || (kern && (!dst || kh <= 0 || kw <= 0)))
-    return fail(c, GPET_ERR_BAD_ARG, "raw frames: bad argument");
-  if (mk) {
-    const int rc_t = check_conv_multi(c, *mk, n_img, tr);
-    if (rc_t) return rc_t;
-  } else if (kern && !(tr ? conv_t_fits_lds(kh, kw) : conv_fits_lds(kh, kw)))
-    return fail(c, GPET_ERR_BAD_ARG, "a %d x %d kernel needs %zu bytes of LDS for its patch, more than %zu", kh, kw,
-                tr ? conv_t_lds_bytes(kh, kw) : conv_lds_bytes(kh, kw), CONV_LDS_MAX);
-  if (dn)
-    if (const char* why = dn_check(*dn, pix)) return fail(c, GPET_ERR_BAD_ARG, "denoise: %s", why);
-  for (int g = 0; g < n_img; ++g)
-    if (!raw[g]) return fail(c, GPET_ERR_BAD_ARG, "raw frame %d is a null pointer", g);
-  const ConvUnion cu = mk ? conv_union(mk->n_kern, mk->kh, mk->kw) : ConvUnion{0, 0, 0, 0, 0};
-  const int n_out = mk ? mk->n_img : n_img;  // gradient images written: one per slot, or one per frame
-  const size_t px = (size_t)M * N, img_bytes = px * esz, nt = mk ? cu.taps : kern ? (size_t)kh * kw : 0;
-  const DenoiseLayout L = dn_layout(dn_on ? dn->technique : DN_NONE, pix, M, N);
-  const int cpix = dn_on ? dn_out_pix(dn->technique, pix) : pix;  // what the convolution reads
-  const size_t stage_img = dn_stage_bytes(img_bytes, on_dev, L);
-  const StagePlan sp = (on_dev && !dn_on) ? StagePlan{0, 0, 0, 0} : dn_stage_plan(n_img, img_bytes, on_dev, L);
-  const size_t o_ws = (size_t)sp.per_chunk * stage_img;  // a chunk's workspace, behind its frames
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)sp.slots * sp.slot_bytes);
-  if (rc) return rc;
-  // one block, the same on both sides: source pointers | destination pointers | taps | reset values of the (min, max) slots
-  // | pointers to the denoised frames | Gaussian taps of the two axes | iterations per image | finished images of the chunk
-  const int ry = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_y, dn->truncate) : 0;
-  const int rx = dn_on && dn->technique == DN_GAUSSIAN ? dn_gauss_radius(dn->sigma_x, dn->truncate) : 0;
-  // | with a slot table: kernel descriptors | slots of each frame (offsets, list) | kernel of each slot
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_wf = o_dst + sizeof(void*) * (size_t)n_out, o_mm = o_wf + sizeof(double) * nt;
-  const size_t o_dn = (o_mm + sizeof(unsigned int) * 2 * (size_t)n_out + 7) & ~(size_t)7;
-  const size_t o_gw = o_dn + (dn_on ? o_dst : 0), o_it = o_gw + (dn_on ? sizeof(double) * (size_t)(2 * ry + 1 + 2 * rx + 1) : 0);
-  const size_t o_end = dn_on ? o_it + sizeof(int) * ((size_t)n_img + 1) : o_mm + sizeof(unsigned int) * 2 * (size_t)n_out;
-  const size_t o_kd = (o_end + 7) & ~(size_t)7, o_so = o_kd + (mk ? sizeof(ConvKernDesc) * (size_t)mk->n_kern : 0);
-  const size_t o_sl = o_so + (mk ? sizeof(int32_t) * ((size_t)n_img + 1) : 0), o_ko = o_sl + (mk ? sizeof(int32_t) * (size_t)n_out : 0);
-  const size_t tab_bytes = mk ? o_ko + sizeof(int32_t) * (size_t)n_out : o_end;
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.resize(tab_bytes);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  float** h_dst = (float**)(h + o_dst);
-  unsigned int* h_mm = (unsigned int*)(h + o_mm);
-  for (int k = 0; k < sp.n_chunks; ++k)
-    for (int i = 0; i < stage_count(sp, k, n_img); ++i) {
-      char* slot = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes;
-      if (!on_dev) h_src[stage_first(sp, k) + i] = slot + (size_t)i * stage_img;
-      if (dn_on) ((const void**)(h + o_dn))[stage_first(sp, k) + i] = slot + o_ws + (size_t)i * L.img_bytes + L.off_out;
-    }
-  for (int g = 0; g < n_img; ++g)
-    if (on_dev) h_src[g] = raw[g];
-  for (int g = 0; g < n_out; ++g) {
-    h_dst[g] = dst ? dst[g] : nullptr;
-    h_mm[2 * g] = 0xFFFFFFFFu;
-    h_mm[2 * g + 1] = 0u;
-  }
-  if (mk) {
-    ConvKernDesc* kd = (ConvKernDesc*)(h + o_kd);
-    conv_kern_descs(mk->n_kern, mk->kh, mk->kw, kd);
-    for (int k = 0; k < mk->n_kern; ++k) conv_flip_taps(mk->kern[k], mk->kh[k], mk->kw[k], (double*)(h + o_wf) + kd[k].w0);
-    frame_slots(n_img, n_out, mk->frame_of, (int32_t*)(h + o_so), (int32_t*)(h + o_sl));
-    memcpy(h + o_ko, mk->kernel_of, sizeof(int32_t) * (size_t)n_out);
-  } else if (kern)
-    conv_flip_taps(kern, kh, kw, (double*)(h + o_wf));
-  if (dn_on && dn->technique == DN_GAUSSIAN) {
-    dn_gauss_taps(dn->sigma_y, ry, (double*)(h + o_gw));
-    dn_gauss_taps(dn->sigma_x, rx, (double*)(h + o_gw) + 2 * ry + 1);
-  }
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  if (kern)
-    HIPCHK(c, hipMemcpyAsync(d_mm, c->raw_tab + o_mm, sizeof(unsigned int) * 2 * (size_t)n_out, hipMemcpyDeviceToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  float* const* d_dst = (float* const*)(c->raw_tab + o_dst);
-  const double* d_wf = (const double*)(c->raw_tab + o_wf);
-  const void* const* d_conv_src = dn_on ? (const void* const*)(c->raw_tab + o_dn) : d_src;
-  const double* d_gw = (const double*)(c->raw_tab + o_gw);
-  int* d_it = (int*)(c->raw_tab + o_it);
-  // frames first .. first + cnt - 1 of `from` (pixel type p) -> the gradient images of the frames, or of all their slots
-  // (tr: the transposed-store forms -- the image at dst[g] is then N x M; the element-wise normaliser below does not care)
-  auto convolve = [&](int p, const void* const* from, int first, int cnt) {
-    if (mk)
-      return (tr ? launch_conv_multi_tr : launch_conv_multi)(c->stream, p, from, first, cnt, M, N, d_wf, cu,
-                                                             (const ConvKernDesc*)(c->raw_tab + o_kd), (const int32_t*)(c->raw_tab + o_so),
-                                                             (const int32_t*)(c->raw_tab + o_sl), (const int32_t*)(c->raw_tab + o_ko), d_dst,
-                                                             d_mm);
-    return (tr ? launch_conv_batch_tr : launch_conv_batch)(c->stream, p, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
-  };
-  if (on_dev && !dn_on) {
-    HIPCHK(c, convolve(pix, d_src, 0, n_img));
-  } else {
-    // plain copies out of the caller's memory, image by image, in stream order behind the kernels that last read the slot
-    for (int k = 0; k < sp.n_chunks; ++k) {
-      const int first = stage_first(sp, k), cnt = stage_count(sp, k, n_img);
-      char* d_slot = c->raw_dev + (size_t)stage_slot(sp, k) * sp.slot_bytes;
-      if (!on_dev)
-        for (int i = 0; i < cnt; ++i)
-          HIPCHK(c, hipMemcpyAsync(d_slot + (size_t)i * stage_img, raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream));
-      if (dn_on) {
-        char* ws = d_slot + o_ws;
-        if (dn->technique == DN_GAUSSIAN) {
-          HIPCHK(c, launch_dn_gauss(c->stream, pix, d_src, first, cnt, M, N, *dn, d_gw, d_gw + 2 * ry + 1, ws, L));
-        } else if (dn->technique == DN_TVC) {
-          int* d_done = d_it + n_img;
-          HIPCHK(c, hipMemsetAsync(d_done, 0, sizeof(int), c->stream));
-          for (int issued = 0, done = 0; issued < dn->n_iter_max && done < cnt;) {
-            const int grp = dn->n_iter_max - issued < DN_TVC_GROUP ? dn->n_iter_max - issued : DN_TVC_GROUP;
-            for (int j = 0; j < grp; ++j)
-              HIPCHK(c, launch_dn_tvc_iter(c->stream, pix, d_src, first, cnt, M, N, *dn, issued + j, ws, L, d_it, d_done));
-            issued += grp;
-            if (issued < dn->n_iter_max) {
-              HIPCHK(c, hipMemcpyAsync(&done, d_done, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-              HIPCHK(c, gpet_wait(c->stream));
-            }
-          }
-        } else {
-          HIPCHK(c, launch_dn_rank(c->stream, pix, d_src, first, cnt, M, N, *dn, ws, L));
-        }
-        if (dn_out)
-          for (int i = 0; i < cnt; ++i)
-            HIPCHK(c, hipMemcpyAsync(dn_out[first + i], ws + (size_t)i * L.img_bytes + L.off_out, px * (size_t)pix_bytes(cpix),
-                                     hipMemcpyDeviceToHost, c->stream));
-      }
-      if (kern) HIPCHK(c, convolve(cpix, d_conv_src, first, cnt));
-    }
-  }
-  if (n_iter_out) {
-    if (dn_on && dn->technique == DN_TVC)
-      HIPCHK(c, hipMemcpyAsync(n_iter_out, d_it, sizeof(int32_t) * (size_t)n_img, hipMemcpyDeviceToHost, c->stream));
-    else
-      for (int g = 0; g < n_img; ++g) n_iter_out[g] = 0;
-  }
-  if (kern) HIPCHK(c, launch_normalise_batch(c->stream, d_dst, n_out, px, d_mm));
-  return GPET_OK;
-}
-
-int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
-                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out, int32_t* n_iter_out, bool tr) {
-  return conv_frames_body(c, raw, n_img, pix, M, N, dn, kern, kh, kw, nullptr, on_dev, dst, d_mm, dn_out, n_iter_out, tr);
-}
-
-int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames, bool tr) {
-  if (!mk.kern || !mk.kh || !mk.kw) return fail(c, GPET_ERR_BAD_ARG, "slot table: the kernels are a null pointer");
-  if (const char* why = slot_table_check(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
-    return fail(c, GPET_ERR_BAD_ARG, "slot table: %s (n_frames = %d, n_kern = %d, n_img = %d)", why, n_frames, mk.n_kern, mk.n_img);
-  for (int k = 0; k < mk.n_kern; ++k)
-    if (!mk.kern[k] || mk.kh[k] <= 0 || mk.kw[k] <= 0) return fail(c, GPET_ERR_BAD_ARG, "slot table: kernel %d is empty or a null pointer", k);
-  if (!(tr ? conv_union_t_fits_lds(mk.n_kern, mk.kh, mk.kw) : conv_union_fits_lds(mk.n_kern, mk.kh, mk.kw))) {
-    const ConvUnion u = conv_union(mk.n_kern, mk.kh, mk.kw);
-    return fail(c, GPET_ERR_BAD_ARG, "the %d kernels need %zu bytes of LDS for their taps and their union patch of %d x %d, more than %zu",
-                mk.n_kern, tr ? conv_union_t_lds_bytes(u) : conv_union_lds_bytes(u), tr ? conv_union_t_rows(u) : conv_union_rows(u),
-                tr ? conv_union_t_cols(u) : conv_union_cols(u), CONV_LDS_MAX);
-  }
-  return GPET_OK;
-}
-
-// one kernel on every frame in frame order is the single-kernel path itself: the same launches in the same order
-int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
-                      bool on_dev, float* const* dst, unsigned int* d_mm, bool tr) {
-  const int rc = check_conv_multi(c, mk, n_frames, tr);
-  if (rc) return rc;
-  if (slot_table_is_identity(n_frames, mk.n_kern, mk.n_img, mk.frame_of, mk.kernel_of))
-    return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], nullptr, on_dev, dst, d_mm, nullptr, nullptr, tr);
-  // (with a table the body reads `kern` only as "there is a convolution": taps and extents come from mk)
-  return conv_frames_body(c, raw, n_frames, pix, M, N, dn, mk.kern[0], mk.kh[0], mk.kw[0], &mk, on_dev, dst, d_mm, nullptr, nullptr, tr);
-}
-
-extern "C" {
-
-// n_img output images; mk == nullptr: of n_img frames with the one kernel, else of n_frames frames by the slot table
-// (GPET_FRAMES_TRANSPOSED: every output is the N x M transpose of the frame's M x N gradient image)
-static int grad_images_from(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                            const DenoiseSpec* dn, unsigned int flags, float* const* out, const ConvMulti* mk = nullptr, int n_frames = 0) {
-  if (!c || !raw || !out || n_img <= 0 || M <= 0 || N <= 0 || (!mk && (!kern || kh <= 0 || kw <= 0)))
-    return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: bad argument");
-  const bool tr = (flags & GPET_FRAMES_TRANSPOSED) != 0;
-  if (mk) {
-    const int rc_t = check_conv_multi(c, *mk, n_frames, tr);  // (before the scratch is sized by the table)
-    if (rc_t) return rc_t;
-  }
-  for (int g = 0; g < n_img; ++g)
-    if (!out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_grad_images: output image %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t px = (size_t)M * N;
-  Carver meas;
-  (void)meas.take<float>(px * (size_t)n_img);
-  (void)meas.take<unsigned int>(2 * (size_t)n_img);
-  int rc = ctx_scratch(c, meas.off + 256);
-  if (rc) return rc;
-  Carver cv;
-  cv.base = c->scratch;
-  float* d_out = cv.take<float>(px * (size_t)n_img);
-  unsigned int* d_mm = cv.take<unsigned int>(2 * (size_t)n_img);
-  std::vector<float*> dst((size_t)n_img);
-  for (int g = 0; g < n_img; ++g) dst[(size_t)g] = d_out + (size_t)g * px;
-  rc = mk ? conv_frames_multi(c, raw, n_frames, pix, M, N, dn, *mk, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm, tr)
-          : conv_frames(c, raw, n_img, pix, M, N, dn, kern, kh, kw, (flags & GPET_RAW_ON_DEVICE) != 0, dst.data(), d_mm, nullptr, nullptr, tr);
-  if (rc == GPET_OK)
-    for (int g = 0; g < n_img; ++g) {
-      hipError_t e = hipMemcpyAsync(out[g], dst[(size_t)g], px * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) {
-        (void)gpet_wait(c->stream);
-        return fail(c, GPET_ERR_HIP, "gpet_grad_images: copy of image %d failed: %s", g, hipGetErrorString(e));
-      }
-    }
-  HIPCHK(c, gpet_wait(c->stream));  // (also after an error: host frames already enqueued must not be read after the return)
-  return rc;
-}
-
-int gpet_grad_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                     unsigned int flags, float* const* out) {
-  return grad_images_from(c, raw, n_img, pix, M, N, kern, kh, kw, nullptr, flags, out);
-}
-
-int gpet_grad_images_dn(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const double* kern, int kh, int kw,
-                        const gpet_denoise* dn, unsigned int flags, float* const* out) {
-  const DenoiseSpec spec = dn_spec(dn);
-  return grad_images_from(c, raw, n_img, pix, M, N, kern, kh, kw, dn ? &spec : nullptr, flags, out);
-}
-
-int gpet_grad_images_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, int n_kern, const double* const* kern,
-                           const int32_t* kh, const int32_t* kw, const gpet_denoise* dn, int n_img, const int32_t* frame_of,
-                           const int32_t* kernel_of, unsigned int flags, float* const* out) {
-  const DenoiseSpec spec = dn_spec(dn);
-  const ConvMulti mk{n_kern, kern, kh, kw, n_img, frame_of, kernel_of};
-  return grad_images_from(c, raw, n_img, pix, M, N, nullptr, 0, 0, dn ? &spec : nullptr, flags, out, &mk, n_frames);
-}
-
-int gpet_denoise_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_denoise* dn,
-                        unsigned int flags, void* const* out, int32_t* n_iter_out) {
-  if (!c || !raw || !dn || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: bad argument");
-  if (dn->technique == GPET_DN_NONE) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: no technique");
-  for (int g = 0; g < n_img; ++g)
-    if (!out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_denoise_images: output image %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const DenoiseSpec spec = dn_spec(dn);
-  const int rc = conv_frames(c, raw, n_img, pix, M, N, &spec, nullptr, 0, 0, (flags & GPET_RAW_ON_DEVICE) != 0, nullptr, nullptr, out,
-                             n_iter_out);
-  HIPCHK(c, gpet_wait(c->stream));  // (also after an error: host frames already enqueued must not be read after the return)
-  return rc;
-}
-
-// Non-local means (gpet_nlmeans_plan.h).  One device block, the same on both sides: source pointers | destination pointers | taps.
-// Host frames and host outputs go through the staging slot in chunks -- a chunk's frames, then its f64 results -- with one launch
-// per chunk; frames and outputs on the device are read and written where they lie by one launch.
-int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
-                        unsigned int flags, void* const* out) {
-  if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: bad argument");
-  NlmSpec sp;
-  sp.patch_size = spec->patch_size;
-  sp.patch_distance = spec->patch_distance;
-  sp.h = spec->h;
-  sp.sigma = spec->sigma;
-  sp.taps = spec->taps;
-  const int s = nlm_patch(sp.patch_size), d = sp.patch_distance;
-  if (const char* why = nlm_check(sp, pix, M, N)) {
-    if (s >= 3 && s <= NLM_PATCH_MAX && d >= 0 && d <= NLM_DIST_MAX && nlm_lds_bytes(s, d) > NLM_LDS_MAX)
-      return fail(c, GPET_ERR_BAD_ARG, "nlmeans: %s: patch %d, distance %d need %zu bytes, more than %zu", why, s, d, nlm_lds_bytes(s, d),
-                  NLM_LDS_MAX);
-    return fail(c, GPET_ERR_BAD_ARG, "nlmeans: %s (patch_size %d, patch_distance %d, h %g, sigma %g, frames %d x %d)", why, sp.patch_size, d,
-                sp.h, sp.sigma, M, N);
-  }
-  for (int g = 0; g < n_img; ++g)
-    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: frame or output %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_NLM_OUT_ON_DEVICE) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
-  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
-  const StagePlan plan = st_in + st_out ? stage_plan(n_img, st_in + st_out) : StagePlan{n_img, 1, 0, 0};
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.slots * plan.slot_bytes);
-  if (rc) return rc;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_w = 2 * o_dst, tab_bytes = o_w + sizeof(double) * (size_t)(s * s);
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.resize(tab_bytes);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  void** h_dst = (void**)(h + o_dst);
-  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
-  for (int k = 0; k < plan.n_chunks; ++k)
-    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
-      const int g = stage_first(plan, k) + i;
-      char* slot = plan.slots ? c->raw_dev + (size_t)stage_slot(plan, k) * plan.slot_bytes : nullptr;
-      h_src[g] = in_dev ? raw[g] : slot + (size_t)i * st_in;
-      h_dst[g] = out_dev ? out[g] : slot + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
-    }
-  memcpy(h + o_w, sp.taps, sizeof(double) * (size_t)(s * s));
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
-  const double* d_w = (const double*)(c->raw_tab + o_w);
-  const double var2 = 2.0 * sp.sigma * sp.sigma;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
-    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
-    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_nlmeans(c->stream, pix, d_src, d_dst, first, cnt, M, N, s, d, d_w, var2);
-    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
-  if (!in_dev || !out_dev || e != hipSuccess) (void)gpet_wait(c->stream);
-  HIPCHK(c, e);
-  return GPET_OK;
-}
-
-// Wavelet denoising (gpet_wavelet_plan.h).  One device block: source pointers | destination pointers | sigma [n_img] | thresholds
-// [n_img * levels * 3] | means of squares [the same].  Frames go chunk by chunk (wv_chunks): host frames and host outputs through the
-// staging slot, the pyramids through the context's workspace, 2 levels + 2 launches per chunk (+ 1 with injected thresholds).  The per-frame figures come back
-// in one copy at the end, which the call waits for: a frame without a noise level is an error.
-int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_wavelet* spec,
-                        unsigned int flags, void* const* out) {
-  if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: bad argument");
-  WvSpec sp;
-  sp.n_taps = spec->n_taps;
-  for (int k = 0; k < WV_TAPS_MAX; ++k) sp.dec_lo[k] = spec->dec_lo[k];
-  sp.levels = spec->levels;
-  sp.mode = spec->mode;
-  sp.method = spec->method;
-  sp.sigma = spec->sigma;
-  sp.rescale_sigma = spec->rescale_sigma;
-  sp.ppf = spec->ppf;
-  sp.c = spec->c;
-  sp.thresholds = spec->thresholds;
-  sp.n_thresholds = spec->n_thresholds;
-  if (const char* why = wv_check(sp, pix, M, N, n_img))
-    return fail(c, GPET_ERR_BAD_ARG, "wavelet: %s (%d taps, wavelet_levels %d, max_level %d, frames %d x %d, %d thresholds)", why, sp.n_taps,
-                sp.levels, sp.n_taps >= 2 ? wv_max_level(M < N ? M : N, sp.n_taps) : 0, M, N, sp.n_thresholds);
-  for (int g = 0; g < n_img; ++g)
-    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: frame or output %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const WvPlan wp = wv_plan(M, N, sp.n_taps, wv_levels(sp, M, N));
-  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_WV_OUT_ON_DEVICE) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
-  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
-  const size_t ws_bytes = dn_align(wp.frame_doubles * sizeof(double));
-  const StagePlan plan = wv_chunks(n_img, st_in + st_out, wp.frame_doubles);
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
-  if (rc) return rc;
-  rc = ctx_grow(c, &c->wv_ws, &c->wv_ws_bytes, (size_t)plan.per_chunk * ws_bytes);
-  if (rc) return rc;
-  const size_t n_thr = (size_t)n_img * wp.levels * 3;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_sig = 2 * o_dst, o_thr = o_sig + sizeof(double) * (size_t)n_img,
-               o_ms = o_thr + sizeof(double) * n_thr, tab_bytes = o_ms + sizeof(double) * n_thr;
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.assign(tab_bytes, 0);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  void** h_dst = (void**)(h + o_dst);
-  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
-  for (int k = 0; k < plan.n_chunks; ++k)
-    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
-      const int g = stage_first(plan, k) + i;
-      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
-      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
-    }
-  if (sp.thresholds) memcpy(h + o_thr, sp.thresholds, sizeof(double) * n_thr);
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
-  double* d_sigma = (double*)(c->raw_tab + o_sig);
-  double* d_thr = (double*)(c->raw_tab + o_thr);
-  double* d_ms = (double*)(c->raw_tab + o_ms);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
-    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
-    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_wavelet(c->stream, pix, d_src, d_dst, first, cnt, wp, sp, c->wv_ws, d_sigma, d_thr, d_ms);
-    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
-    for (int i = 0; i < cnt && spec->coeffs_out && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(spec->coeffs_out + (size_t)(first + i) * wp.frame_doubles, c->wv_ws + (size_t)i * wp.frame_doubles * sizeof(double),
-                         wp.frame_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h + o_sig, c->raw_tab + o_sig, tab_bytes - o_sig, hipMemcpyDeviceToHost, c->stream);
-  // (host memory of the caller and the context's own table are in flight, also after an error)
-  const hipError_t ew = gpet_wait(c->stream);
-  HIPCHK(c, e);
-  HIPCHK(c, ew);
-  const double* h_sigma = (const double*)(h + o_sig);
-  if (spec->sigma_out) memcpy(spec->sigma_out, h_sigma, sizeof(double) * (size_t)n_img);
-  if (spec->thresholds_out) memcpy(spec->thresholds_out, h + o_thr, sizeof(double) * n_thr);
-  if (spec->mean_sq_out) memcpy(spec->mean_sq_out, h + o_ms, sizeof(double) * n_thr);
-  for (int g = 0; g < n_img; ++g)
-    if (!(h_sigma[g] > 0.0 && h_sigma[g] < INFINITY))
-      return fail(c, GPET_ERR_BAD_ARG, !(sp.sigma != sp.sigma)
-                      ? "wavelet: frame %d is flat: a given sigma under rescale_sigma is scaled by (max - min) / (max - min) of the frame"
-                      : "wavelet: frame %d has no noise level: its finest diagonal band (dd of level 1) is all zero", g);
-  return GPET_OK;
-}
-
 int gpet_normalise_f32(gpet_ctx* c, const float* img, size_t count, float* out) {
   if (!c || !img || !out || count == 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_normalise_f32: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -677,7 +245,5 @@ int gpet_normalise_f32(gpet_ctx* c, const float* img, size_t count, float* out) 
   HIPCHK(c, gpet_wait(c->stream));
   return GPET_OK;
 }
-
-// ---- batch ----------------------------------------------------------------------------
 
 }  // extern "C"

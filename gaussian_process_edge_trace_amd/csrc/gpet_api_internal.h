@@ -1,8 +1,11 @@
 // Internals shared by the translation units of the C ABI (include/gpet_hip.h): contexts and batches as the library sees them,
 // the error / wait helpers, and the few host-side helpers more than one unit needs.  Host-side plumbing only: all arithmetic
 // lives in the kernels (gpet_kernels.hip, gpet_eig.hip, gpet_lbfgsb.hip, gpet_rng.hip).
-//   gpet_api_ctx.hip     contexts, options, timers, a1 (gradient image; stacks of raw frames: conv_frames), the shared helpers'
-//                        definitions (waits, errors, lattice)
+//   gpet_api_ctx.hip     contexts, options, timers, a1 for one image (gpet_grad_image, gpet_normalise_f32), the shared helpers'
+//                        definitions (waits, errors, lattice, the context's scratch)
+//   gpet_api_frames.hip  a1 for stacks of raw frames: RawSource and its refusals (check_raw_source), conv_frames, the entry points
+//                        on a context (gpet_grad_images*, gpet_denoise_images) and the stages of their own in front of them
+//                        (gpet_nlmeans_images, gpet_wavelet_images)
 //   gpet_conv_plan.h     what a1 decides before a launch, as plain data (no HIP): flipped taps and origin, pixel types, grid and LDS
 //                        bytes, the chunks host frames go up in
 //   gpet_denoise_plan.h  what the denoising stage in front of a1 decides (no HIP): spec and validation, window origin and rank, Gaussian
@@ -207,31 +210,43 @@ int fail(gpet_ctx* ctx, int code, const char* fmt, ...);
       return fail((ctx), GPET_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 int fin_lattice(const double* x, int n, double* hinv);
-// n_img raw frames (host, or device with on_dev) -> normalised f32 gradient images at the device pointers dst[], enqueued on the
-// context's stream without a final wait; d_mm: device [2 n_img].  dn (may be nullptr): the frames are denoised first; kern ==
-// nullptr: denoising alone, into the host buffers dn_out[] (iterations per image: n_iter_out).  tr (GPET_FRAMES_TRANSPOSED): M, N
-// stay the frame's as it lies, and every dst[g] receives the N x M transpose of its gradient image (gpet_transpose_plan.h)
-int conv_frames(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const DenoiseSpec* dn, const double* kern,
-                int kh, int kw, bool on_dev, float* const* dst, unsigned int* d_mm, void* const* dn_out = nullptr,
-                int32_t* n_iter_out = nullptr, bool tr = false);
-// the slot table of a multi-kernel source as the C ABI hands it over (gpet_conv_multi_plan.h): slot g of n_img is frame frame_of[g]
-// with kernel kernel_of[g] of the n_kern kernels kern[k] (kh[k] x kw[k])
-struct ConvMulti {
-  int n_kern;
-  const double* const* kern;
-  const int32_t* kh;
-  const int32_t* kw;
-  int n_img;
-  const int32_t* frame_of;
-  const int32_t* kernel_of;
+// (device scratch of the a1 entry points in the context, grown on demand: c->scratch holds at least `bytes` afterwards)
+int ctx_scratch(gpet_ctx* c, size_t bytes);
+// ---- gpet_api_frames.hip --------------------------------------------------------------------------------------------------
+// A stack of raw frames and what makes gradient images of them: the one description every raw-frame entry point fills in and
+// conv_frames takes.  Image slot g of n_img is frame frame_of[g] convolved with kernel kernel_of[g] (gpet_conv_multi_plan.h);
+// table == false: the entry point has one kernel, the two table pointers are null, and image g is frame g with kernel 0 (n_img ==
+// n_frames).  n_kern == 0: no convolution, the frames are denoised alone (gpet_denoise_images).
+struct RawSource {
+  const void* const* frames = nullptr;  // [n_frames] host pointers, or device pointers with on_dev
+  int n_frames = 0;
+  int pix = 0;                          // GPET_PIX_*
+  int M = 0, N = 0;                     // the frame as it lies in the caller's memory
+  bool on_dev = false;                  // GPET_RAW_ON_DEVICE
+  bool tr = false;                      // GPET_FRAMES_TRANSPOSED: every image is the N x M transpose of its frame's gradient image
+  const DenoiseSpec* dn = nullptr;      // how the frames are denoised first (gpet_denoise_plan.h), or nullptr
+  int n_kern = 0;
+  const double* const* kern = nullptr;  // [n_kern] kernels of kh[k] x kw[k]
+  const int32_t* kh = nullptr;
+  const int32_t* kw = nullptr;
+  bool table = false;                   // the caller gave a slot table: checked as one (check_conv_multi), whatever it holds
+  int n_img = 0;
+  const int32_t* frame_of = nullptr;
+  const int32_t* kernel_of = nullptr;
 };
-// GPET_OK, or GPET_ERR_BAD_ARG with the reason: a table slot_table_check refuses, an empty kernel, a union patch beyond the LDS
-// (tr: against the LDS bound of the transposed-store kernel)
-int check_conv_multi(gpet_ctx* c, const ConvMulti& mk, int n_frames, bool tr = false);
-// conv_frames for a slot table: n_frames raw frames -> the mk.n_img gradient images dst[g] (d_mm: device [2 mk.n_img]); every frame
-// is staged and denoised once.  One kernel on every frame in order takes conv_frames' own path
-int conv_frames_multi(gpet_ctx* c, const void* const* raw, int n_frames, int pix, int M, int N, const DenoiseSpec* dn, const ConvMulti& mk,
-                      bool on_dev, float* const* dst, unsigned int* d_mm, bool tr = false);
+// GPET_OK, or GPET_ERR_BAD_ARG with the reason, before anything is allocated or enqueued -- in this order: a missing argument, the
+// pixel type, the kernels (one kernel: against the LDS bound of its own patch, conv[_t]_fits_lds; a table: check_conv_multi), the
+// denoising spec, null frames.  conv_frames calls it itself; batch creation and the set calls call it ahead of any allocation
+int check_raw_source(gpet_ctx* c, const RawSource& s);
+// the table of s alone: a table slot_table_check refuses, an empty kernel, a union patch beyond the LDS (s.tr: against the bound of
+// the transposed-store kernel)
+int check_conv_multi(gpet_ctx* c, const RawSource& s);
+// The frames of s -> normalised f32 gradient images at the device pointers dst[g], one per image slot (s.n_img), enqueued on the
+// context's stream without a final wait; d_mm: device [2 s.n_img].  Every frame is staged and denoised once.  s.n_kern == 0:
+// denoising alone, into the host buffers dn_out[] (iterations per image: n_iter_out).  s.tr: M, N stay the frame's as it lies, and
+// every dst[g] receives the N x M transpose of its gradient image (gpet_transpose_plan.h)
+int conv_frames(gpet_ctx* c, const RawSource& s, float* const* dst, unsigned int* d_mm, void* const* dn_out = nullptr,
+                int32_t* n_iter_out = nullptr);
 // the C ABI's gpet_denoise as the plan takes it (nullptr: no technique)
 static inline DenoiseSpec dn_spec(const gpet_denoise* d) {
   DenoiseSpec s;
@@ -248,6 +263,51 @@ static inline DenoiseSpec dn_spec(const gpet_denoise* d) {
   s.n_iter_max = d->n_iter_max;
   return s;
 }
+// A RawSource as the arguments of a C entry point describe it, with what they leave no home for: the DenoiseSpec made of the
+// gpet_denoise and, for an entry point with one kernel, the one-element kernel arrays.  raw points into the object, so it is filled
+// where it stands and never copied.  A batch fills in M, N and, for one kernel, the frame count itself (batch_source)
+struct RawSourceArgs {
+  RawSource raw;
+  DenoiseSpec spec;
+  const double* kern1 = nullptr;
+  int32_t kh1 = 0, kw1 = 0;
+  RawSourceArgs() = default;
+  RawSourceArgs(const RawSourceArgs&) = delete;
+  RawSourceArgs& operator=(const RawSourceArgs&) = delete;
+  void frames(const void* const* f, int n_frames, int pix, const gpet_denoise* dn, unsigned int flags, int M = 0, int N = 0) {
+    spec = dn_spec(dn);
+    raw.M = M;
+    raw.N = N;
+    raw.frames = f;
+    raw.n_frames = n_frames;
+    raw.pix = pix;
+    raw.dn = dn ? &spec : nullptr;
+    raw.on_dev = (flags & GPET_RAW_ON_DEVICE) != 0;
+    raw.tr = (flags & GPET_FRAMES_TRANSPOSED) != 0;
+  }
+  // one kernel on every frame in order
+  void one_kernel(const double* k, int kh, int kw) {
+    kern1 = k;
+    kh1 = kh;
+    kw1 = kw;
+    raw.n_kern = 1;
+    raw.kern = &kern1;
+    raw.kh = &kh1;
+    raw.kw = &kw1;
+    raw.n_img = raw.n_frames;
+  }
+  void slot_table(int n_kern, const double* const* k, const int32_t* kh, const int32_t* kw, int n_img, const int32_t* frame_of,
+                  const int32_t* kernel_of) {
+    raw.n_kern = n_kern;
+    raw.kern = k;
+    raw.kh = kh;
+    raw.kw = kw;
+    raw.table = true;
+    raw.n_img = n_img;
+    raw.frame_of = frame_of;
+    raw.kernel_of = kernel_of;
+  }
+};
 // ---- gpet_api_loop.hip ----------------------------------------------------------------------------------------------------
 hipError_t launch_normals_seq(gpet_batch* b, hipStream_t st, EdgeDev* edges_l, int B_l, const unsigned int* seeds_l, int add_iter,
                               int iter_abs, int n_ahead, int z_store);
