@@ -74,6 +74,9 @@ def denoise_spec(denoise):
         raise NotImplementedError("denoising technique 'wavelet' is no gpet_denoise technique: it is built as a stage of its own "
                                   "(wavelet_spec, Context.wavelet_images) and runs when kwargs names the wavelet, e.g. "
                                   "dict(wavelet='db1')")
+    if technique == "tvb":  # (the third such stage: RawFrames takes it through tvb_spec)
+        raise NotImplementedError("denoising technique 'tvb' is no gpet_denoise technique: it is built as a stage of its own "
+                                  "(tvb_spec, Context.tvb_images) and runs when kwargs gives weight, e.g. dict(weight=5)")
     if technique in DN_NOT_BUILT:
         raise NotImplementedError("denoising technique %r is not built for the device (built: %s)"
                                   % (technique, ", ".join(sorted(DN_OF_TECHNIQUE))))
@@ -332,10 +335,64 @@ def wavelet_spec(kwargs, thresholds=None):
                        float("nan") if sigma is None else float(sigma), bool(kw.get("rescale_sigma", True)), thresholds)
 
 
+# split-Bregman TV denoising (gpet_tvb, GPET_TVB_*): the third stage of its own in front of the raw-frame path
+TVB_OUT_ON_DEVICE = 8  # gpet_tvb_images: out[] are device pointers
+TVB_KEYS = ("weight", "max_iter", "eps", "isotropic", "multichannel")
+TVB_DIAG_MAX = 768  # min(M, N) at most: the hand-over of a diagonal stays inside 64 KB of LDS (gpet_tvb_plan.h)
+TVB_CHUNK_BUDGET = 256 << 20  # bytes a chunk's workspaces and staging stay inside (gpet_tvb_plan.h: TVB_CHUNK_BUDGET)
+
+
+def tvb_frame_bytes(M, N):
+    """Bytes of one frame's workspace (gpet_tvb_plan.h: tvb_frame_bytes): six skewed float64 arrays of (M + 2)(N + 2), to 256 bytes."""
+    return (6 * (int(M) + 2) * (int(N) + 2) * 8 + 255) & ~255
+
+
+class GpetTvb(C.Structure):
+    _fields_ = [("weight", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int32), ("isotropic", C.c_int32)]
+
+
+class TvbSpec(object):
+    """What tvb_spec returns: ``c`` the gpet_tvb of the call."""
+
+    def __init__(self, weight, eps, max_iter, isotropic):
+        self.c = GpetTvb(weight=weight, eps=eps, max_iter=max_iter, isotropic=int(bool(isotropic)))
+
+    def arg(self):
+        return C.byref(self.c)
+
+
+def tvb_spec(kwargs):
+    """The keyword arguments of ``gpet_utils.denoise(image, 'tvb', kwargs)`` = scikit-image's ``denoise_tv_bregman`` -> TvbSpec,
+    decided from the arguments alone (no device): ``weight`` (above 0), ``max_iter`` (100), ``eps`` (1e-3), ``isotropic`` (True);
+    ``multichannel`` only as False.  THE ``weight`` KEY MUST BE GIVEN: it is a required argument of the library (the reference
+    itself fails without it), and kwargs without it raise NotImplementedError, as 'tvb' did before the stage was built.  Any other
+    key raises ValueError naming it, and so does a value the device refuses."""
+    kw = dict(kwargs or {})
+    for k in kw:
+        if k not in TVB_KEYS:
+            raise ValueError("denoise: keyword %r of 'tvb' is not supported on the device (supported: %s)" % (k, ", ".join(TVB_KEYS)))
+    if "weight" not in kw:
+        raise NotImplementedError("denoising technique 'tvb' runs on the device only when kwargs gives weight, the library's required "
+                                  "argument, e.g. dict(weight=5); without it 'tvb' is not built")
+    if kw.get("multichannel", False):
+        raise ValueError("denoise: multichannel=True of 'tvb' is not supported on the device (frames are 2-D, single-channel)")
+    weight, eps, max_iter = kw["weight"], kw.get("eps", 1e-3), kw.get("max_iter", 100)
+    if not (np.ndim(weight) == 0 and float(weight) > 0 and np.isfinite(float(weight))):
+        raise ValueError("denoise: weight %r of 'tvb': one finite number above 0" % (weight,))
+    if not (np.ndim(eps) == 0 and float(eps) >= 0):
+        raise ValueError("denoise: eps %r of 'tvb': one number, not negative" % (eps,))
+    if not (np.ndim(max_iter) == 0 and int(max_iter) == max_iter and int(max_iter) >= 1):
+        raise ValueError("denoise: max_iter %r of 'tvb': a whole number of at least 1" % (max_iter,))
+    return TvbSpec(float(weight), float(eps), int(max_iter), bool(kw.get("isotropic", True)))
+
+
 # the stages of their own in front of the raw-frame path: technique -> (kwargs -> spec).  RawFrames.pre holds the spec,
 # RawFrames.pre_resolved runs it (Context.pre_images) into a PreFrames and hands float64 device frames on
 PRE_STAGES = {"nl": nlmeans_spec, "wavelet": wavelet_spec}
-PRE_SPECS = (NlmeansSpec, WaveletSpec)
+# (PRE_STAGES is pinned as exactly these two by tests/test_wavelet_host.py; every stage of its own, 'tvb' included, is looked up in
+# PRE_STAGE_OF)
+PRE_STAGE_OF = dict(PRE_STAGES, tvb=tvb_spec)
+PRE_SPECS = (NlmeansSpec, WaveletSpec, TvbSpec)
 
 
 class GpetParams(C.Structure):
@@ -670,8 +727,8 @@ class RawFrames(object):
     Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
     ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all.
     ``denoise``: optionally how the frames are denoised on the device before the kernel is applied, a ``(technique, kwargs)``
-    pair of gpet_utils.denoise (see denoise_spec); 'nl' and 'wavelet' are stages of their own (nlmeans_spec, wavelet_spec: the
-    spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
+    pair of gpet_utils.denoise (see denoise_spec); 'nl', 'wavelet' and 'tvb' are stages of their own (nlmeans_spec, wavelet_spec,
+    tvb_spec: the spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
     ``slots=(frame_of, kernel_of)``: a slot table -- ``kernel`` is then a list of kernels (split_kernels) and image g is made of
     frame ``frame_of[g]`` with kernel ``kernel_of[g]`` (the library's *_multi calls); ``len()`` stays the number of frames,
     ``n_slots`` is the number of images."""
@@ -679,13 +736,13 @@ class RawFrames(object):
     def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
-        # ('nl' and 'wavelet' are stages of their own: the frames go through Context.pre_images into device memory first -- see
+        # ('nl', 'wavelet' and 'tvb' are stages of their own: the frames go through Context.pre_images into device memory first -- see
         # pre_resolved)
         self.pre = None
         if isinstance(denoise, PRE_SPECS):
             self.pre, denoise = denoise, None
-        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGES:
-            self.pre, denoise = PRE_STAGES[denoise[0]](denoise[1]), None
+        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGE_OF:
+            self.pre, denoise = PRE_STAGE_OF[denoise[0]](denoise[1]), None
         self.dn = denoise_spec(denoise)
         self.slots = None
         if slots is not None:
@@ -712,6 +769,9 @@ class RawFrames(object):
             self.shape = self.frames[0].shape
         if self.wv is not None:
             self.wv.levels_on(self.shape)  # (refuses levels the frames do not allow before a device is needed)
+        if self.tvb is not None and (min(self.shape) < 2 or min(self.shape) > TVB_DIAG_MAX):
+            raise ValueError("denoise: 'tvb' takes frames of at least 2 x 2 pixels whose smaller extent is at most %d, not %d x %d"
+                             % (TVB_DIAG_MAX, self.shape[0], self.shape[1]))
 
     def __len__(self):
         return len(self.ptrs)
@@ -726,8 +786,13 @@ class RawFrames(object):
         """The wavelet spec of these frames, or None."""
         return self.pre if isinstance(self.pre, WaveletSpec) else None
 
+    @property
+    def tvb(self):
+        """The split-Bregman spec of these frames, or None."""
+        return self.pre if isinstance(self.pre, TvbSpec) else None
+
     def pre_resolved(self, ctx, buf):
-        """These frames as the raw-frame calls take them: without a stage of its own ('nl', 'wavelet'), self; with one, the frames
+        """These frames as the raw-frame calls take them: without a stage of its own ('nl', 'wavelet', 'tvb'), self; with one, the frames
         denoised into the device memory of ``buf`` (a PreFrames; enqueued on the context's stream) as float64 device frames with
         the same kernels and slot table and no further denoising."""
         if self.pre is None:
@@ -847,6 +912,8 @@ SYMBOLS = {
                                       C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_nlmeans_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeans), C.c_uint,
                                       C.POINTER(_P)]),
+    "gpet_tvb_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetTvb), C.c_uint,
+                                  C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_wavelet_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetWavelet), C.c_uint,
                                       C.POINTER(_P)]),
     "gpet_grad_images_dn": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
@@ -1025,7 +1092,7 @@ def load():
 
 
 class PreFrames(object):
-    """Device memory (gpet_dev_alloc) for the float64 frames a stage of its own ('nl', 'wavelet') leaves behind: owned by the
+    """Device memory (gpet_dev_alloc) for the float64 frames a stage of its own ('nl', 'wavelet', 'tvb') leaves behind: owned by the
     object that feeds them to the raw-frame path, grown on demand, reused from frame to frame, freed on close()."""
 
     def __init__(self, ctx):
@@ -1103,7 +1170,7 @@ class Context:
         """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32.
         ``transpose`` (GPET_FRAMES_TRANSPOSED): (T, N, M), every image the transpose of its frame's gradient image, made on the device."""
         M, N = raw.shape
-        if raw.pre is not None:  # ('nl' / 'wavelet' first, into device memory of this call; the calls below end with a wait)
+        if raw.pre is not None:  # ('nl' / 'wavelet' / 'tvb' first, into device memory of this call; the calls below end with a wait)
             buf = PreFrames(self)
             try:
                 return self.grad_images(raw.pre_resolved(self, buf), transpose)
@@ -1136,7 +1203,9 @@ class Context:
 
     def denoise_images(self, raw):
         """gpet_denoise_images: every frame of ``raw`` (a RawFrames with a denoising technique) denoised in one batched pass ->
-        ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters)."""
+        ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters, 'nl' and 'wavelet'; the sweeps of 'tvb')."""
+        if raw.tvb is not None:
+            return self.tvb_images(raw, return_n_iter=True)
         if raw.pre is not None:
             return self.pre_images(raw), np.zeros(len(raw), dtype=np.int32)
         if raw.dn is None:
@@ -1150,7 +1219,9 @@ class Context:
         return out, n_iter
 
     def pre_images(self, raw, out_device_ptrs=None):
-        """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images or wavelet_images."""
+        """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images, wavelet_images or tvb_images."""
+        if raw.tvb is not None:
+            return self.tvb_images(raw, out_device_ptrs=out_device_ptrs)
         if raw.wv is not None:
             return self.wavelet_images(raw, out_device_ptrs=out_device_ptrs)
         return self.nlmeans_images(raw, out_device_ptrs=out_device_ptrs)
@@ -1197,6 +1268,20 @@ class Context:
         if raw.wv.c.method != WV_METHODS["BayesShrink"] or raw.wv.thresholds is not None:
             rep["mean_sq"] = None
         return out, rep
+
+    def tvb_images(self, raw, out_device_ptrs=None, return_n_iter=False):
+        """gpet_tvb_images: split-Bregman TV denoising of every frame of ``raw`` (a RawFrames made with ``denoise=('tvb', kwargs)``
+        or a TvbSpec) in one batched pass, one workgroup per frame -> (T, M, N) float64.  ``out_device_ptrs``: device addresses of
+        float64 (M, N) frames to write instead (GPET_TVB_OUT_ON_DEVICE; returns None) -- with frames on the device too and
+        without ``return_n_iter``, nothing is waited for.  ``return_n_iter``: also the sweeps every frame ran, (T,) int32."""
+        if raw.tvb is None:
+            raise ValueError("no split-Bregman spec")
+        M, N = raw.shape
+        out, op, flags = self._pre_out(raw, out_device_ptrs, TVB_OUT_ON_DEVICE)
+        n_iter = np.zeros(len(raw), dtype=np.int32) if return_n_iter else None
+        self.check(self.lib.gpet_tvb_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.tvb.arg(), flags, op,
+                                            n_iter.ctypes.data_as(C.POINTER(C.c_int32)) if return_n_iter else None))
+        return (out, n_iter) if return_n_iter else out
 
     def nlmeans_images(self, raw, out_device_ptrs=None):
         """gpet_nlmeans_images: non-local means of every frame of ``raw`` (a RawFrames made with ``denoise=('nl', kwargs)`` or a

@@ -1,7 +1,7 @@
 // C ABI, a1 for stacks of raw frames: the one description of a raw-frame source (RawSource, gpet_api_internal.h) with its refusals,
 // conv_frames -- every frame staged and denoised once, its gradient images made on the device --, the entry points on a context
-// (gpet_grad_images*, gpet_denoise_images) and the two stages of their own in front of them (gpet_nlmeans_images,
-// gpet_wavelet_images).
+// (gpet_grad_images*, gpet_denoise_images) and the three stages of their own in front of them (gpet_nlmeans_images,
+// gpet_wavelet_images, gpet_tvb_images).
 #include "gpet_api_internal.h"
 
 static_assert(DN_NONE == GPET_DN_NONE && DN_MEDIAN == GPET_DN_MEDIAN && DN_MINIMUM == GPET_DN_MINIMUM && DN_GAUSSIAN == GPET_DN_GAUSSIAN &&
@@ -433,6 +433,76 @@ int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
       return fail(c, GPET_ERR_BAD_ARG, !(sp.sigma != sp.sigma)
                       ? "wavelet: frame %d is flat: a given sigma under rescale_sigma is scaled by (max - min) / (max - min) of the frame"
                       : "wavelet: frame %d has no noise level: its finest diagonal band (dd of level 1) is all zero", g);
+  return GPET_OK;
+}
+
+// Split-Bregman TV denoising (gpet_tvb_plan.h).  One device block: source pointers | destination pointers | states [n_img].  Frames
+// go chunk by chunk (tvb_chunks): host frames and host outputs through the staging slot, the skewed arrays through the context's
+// workspace; per chunk one prologue, tvb_launches(max_iter) sweep launches and one epilogue, enqueued without waiting.  The sweep
+// counts come back in one copy at the end, only when the caller asks for them.
+int gpet_tvb_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_tvb* spec, unsigned int flags,
+                    void* const* out, int32_t* n_iter_out) {
+  if (!c || !raw || !spec || !out || n_img <= 0)
+    return fail(c, GPET_ERR_BAD_ARG, "gpet_tvb_images: bad argument (%s)", !c ? "no context" : !raw ? "raw is a null pointer" : !spec ? "spec is a null pointer"
+                                                                           : !out ? "out is a null pointer" : "no frame");
+  TvbSpec sp;
+  sp.weight = spec->weight;
+  sp.eps = spec->eps;
+  sp.max_iter = spec->max_iter;
+  sp.isotropic = spec->isotropic != 0;
+  if (const char* why = tvb_check(sp, pix, M, N, n_img))
+    return fail(c, GPET_ERR_BAD_ARG, "tvb: %s (weight %g, eps %g, max_iter %d, frames %d x %d)", why, sp.weight, sp.eps, sp.max_iter, M, N);
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_tvb_images: frame or output %d is a null pointer", g);
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_TVB_OUT_ON_DEVICE) != 0;
+  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
+  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
+  const size_t ws_bytes = tvb_frame_bytes(M, N);
+  const StagePlan plan = tvb_chunks(n_img, st_in + st_out, M, N);
+  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
+  if (rc) return rc;
+  rc = ctx_grow(c, &c->tvb_ws, &c->tvb_ws_bytes, (size_t)plan.per_chunk * ws_bytes);
+  if (rc) return rc;
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_state = 2 * o_dst, tab_bytes = o_state + sizeof(TvbState) * (size_t)n_img;
+  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
+  if (rc) return rc;
+  c->h_raw_tab.assign(tab_bytes, 0);
+  char* h = c->h_raw_tab.data();
+  const void** h_src = (const void**)h;
+  void** h_dst = (void**)(h + o_dst);
+  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
+  for (int k = 0; k < plan.n_chunks; ++k)
+    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
+      const int g = stage_first(plan, k) + i;
+      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
+      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
+    }
+  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  const void* const* d_src = (const void* const*)c->raw_tab;
+  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
+  TvbState* d_state = (TvbState*)(c->raw_tab + o_state);
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
+    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
+    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_tvb(c->stream, pix, d_src, d_dst, first, cnt, M, N, sp, c->tvb_ws, d_state);
+    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
+  }
+  if (e == hipSuccess && n_iter_out) e = hipMemcpyAsync(h + o_state, c->raw_tab + o_state, tab_bytes - o_state, hipMemcpyDeviceToHost, c->stream);
+  // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
+  if (!in_dev || !out_dev || n_iter_out || e != hipSuccess) {
+    const hipError_t ew = gpet_wait(c->stream);
+    HIPCHK(c, e);
+    HIPCHK(c, ew);
+  }
+  HIPCHK(c, e);
+  if (n_iter_out) {
+    const TvbState* hs = (const TvbState*)(h + o_state);
+    for (int g = 0; g < n_img; ++g) n_iter_out[g] = hs[g].n_iter;
+  }
   return GPET_OK;
 }
 

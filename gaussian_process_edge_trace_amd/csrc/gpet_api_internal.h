@@ -5,7 +5,7 @@
 //                        definitions (waits, errors, lattice, the context's scratch)
 //   gpet_api_frames.hip  a1 for stacks of raw frames: RawSource and its refusals (check_raw_source), conv_frames, the entry points
 //                        on a context (gpet_grad_images*, gpet_denoise_images) and the stages of their own in front of them
-//                        (gpet_nlmeans_images, gpet_wavelet_images)
+//                        (gpet_nlmeans_images, gpet_wavelet_images, gpet_tvb_images)
 //   gpet_conv_plan.h     what a1 decides before a launch, as plain data (no HIP): flipped taps and origin, pixel types, grid and LDS
 //                        bytes, the chunks host frames go up in
 //   gpet_denoise_plan.h  what the denoising stage in front of a1 decides (no HIP): spec and validation, window origin and rank, Gaussian
@@ -66,6 +66,9 @@ struct gpet_ctx {
   // wavelet stage (gpet_wavelet_images): the coefficient pyramids of a chunk's frames (gpet_wavelet_plan.h); grown on demand
   char* wv_ws = nullptr;
   size_t wv_ws_bytes = 0;
+  // split-Bregman stage (gpet_tvb_images): the skewed arrays of a chunk's frames (gpet_tvb_plan.h); grown on demand
+  char* tvb_ws = nullptr;
+  size_t tvb_ws_bytes = 0;
   std::string err;
 };
 

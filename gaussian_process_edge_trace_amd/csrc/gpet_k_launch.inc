@@ -282,6 +282,35 @@ hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, dou
   }
   return hipGetLastError();
 }
+// ---- a0: split-Bregman TV denoising (gpet_k_tvb.inc; geometry: gpet_tvb_plan.h) ----
+template <typename T>
+static void launch_tvb_unpack_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, char* ws, double scale) {
+  const size_t cells = tvb_cells(M, N);
+  hipLaunchKernelGGL((k_tvb_unpack<T>), dim3((unsigned)((cells + TVB_THREADS - 1) / TVB_THREADS), 1, n), dim3(TVB_THREADS), 0, st,
+                     (const T* const*)d_src, img0, (double*)ws, tvb_frame_bytes(M, N) / sizeof(double), M, N, scale);
+}
+hipError_t launch_tvb(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                      const TvbSpec& sp, char* ws, TvbState* d_state) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (n < 1 || n > TVB_CHUNK_MAX || tvb_check(sp, pix, M, N, n) || tvb_lds_bytes(M, N) > TVB_LDS_MAX) return hipErrorInvalidValue;
+  switch (pix) {
+    case PIX_U8: launch_tvb_unpack_t<uint8_t>(st, d_src, img0, n, M, N, ws, 1.0 / 255.0); break;
+    case PIX_U16: launch_tvb_unpack_t<uint16_t>(st, d_src, img0, n, M, N, ws, 1.0 / 65535.0); break;
+    case PIX_F32: launch_tvb_unpack_t<float>(st, d_src, img0, n, M, N, ws, 1.0); break;
+    default: launch_tvb_unpack_t<double>(st, d_src, img0, n, M, N, ws, 1.0); break;
+  }
+  const size_t stride = tvb_frame_bytes(M, N) / sizeof(double);
+  const double lam = 2.0 * sp.weight, norm = sp.weight + 4.0 * lam, inv_lam = 1.0 / lam;
+  static_assert(TVB_CELLS_MAX == 2, "one instance of the sweep kernel per number of cells a lane can own");
+  const auto sweeps = tvb_cells_per_lane(M, N) > 1 ? k_tvb_sweeps<2> : k_tvb_sweeps<1>;
+  for (int k = 0; k < tvb_launches(sp.max_iter); ++k)
+    hipLaunchKernelGGL(sweeps, dim3(1, 1, n), dim3(TVB_THREADS), tvb_lds_bytes(M, N), st, (double*)ws, stride, d_state, img0, M, N, lam, sp.weight,
+                       norm, inv_lam, sp.eps, sp.max_iter, sp.isotropic);
+  const size_t px = (size_t)M * N;
+  hipLaunchKernelGGL(k_tvb_out, dim3((unsigned)((px + TVB_THREADS - 1) / TVB_THREADS), 1, n), dim3(TVB_THREADS), 0, st, (const double*)ws, stride,
+                     d_dst, img0, M, N);
+  return hipGetLastError();
+}
 template <typename T>
 static void launch_dn_gauss_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
                               const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {

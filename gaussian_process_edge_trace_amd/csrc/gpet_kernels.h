@@ -10,6 +10,7 @@
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_wavelet_plan.h"  // wavelet denoising: spec, levels, pyramid layout, tiles, the threshold's summation order
+#include "gpet_tvb_plan.h"      // split-Bregman TV denoising: spec, skewed workspace, workgroup, sweeps per launch, the order of acc
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 #include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
@@ -78,6 +79,11 @@ hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, dou
 // sp.thresholds the caller has filled d_thr.  sp.thresholds is only looked at for null.
 hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, const WvPlan& p,
                           const WvSpec& sp, char* ws, double* d_sigma, double* d_thr, double* d_ms);
+// a0, split-Bregman TV denoising (gpet_tvb_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) ->
+// the f64 frames of the DEVICE pointer table d_dst at the same indices: one prologue, tvb_launches(max_iter) sweep launches, one
+// epilogue.  ws: the chunk's n workspaces (tvb_frame_bytes apart); d_state [frames] on the device, zero before the first launch
+hipError_t launch_tvb(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                      const TvbSpec& sp, char* ws, TvbState* d_state);
 hipError_t launch_fit_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int want_cov,
                               unsigned parts = ~0u);
 hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

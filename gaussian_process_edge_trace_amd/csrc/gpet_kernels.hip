@@ -21,6 +21,7 @@ namespace gpet {
 #include "gpet_k_denoise.inc"
 #include "gpet_k_nlmeans.inc"
 #include "gpet_k_wavelet.inc"
+#include "gpet_k_tvb.inc"
 #include "gpet_k_fit.inc"
 #include "gpet_k_factor.inc"
 #include "gpet_k_rng.inc"

@@ -1,8 +1,8 @@
 """Mirror of ``gp_edge_tracing/gpet_utils.py`` for the parts on (or feeding) the hot path.
 
 ``comp_grad_img`` / ``comp_grad_imgs`` / ``normalise`` run on the GPU through libgpet_hip.so (a1), and so do ``denoise`` /
-``denoise_imgs`` (a0) for the reference's 'median', 'minimum', 'gaussian', 'tvc', 'nl' (fast_mode=False) and 'wavelet' (the
-wavelet named); ``kernel_builder``
+``denoise_imgs`` (a0) for the reference's 'median', 'minimum', 'gaussian', 'tvc', 'nl' (fast_mode=False), 'wavelet' (the
+wavelet named) and 'tvb' (weight given); ``kernel_builder``
 is host-side setup (a 11x5 table).  ``construct_test_img`` is this package's own generator of the
 reference's synthetic test image recipe (gpet_utils.py:163-253).  Called like the reference (no ``seed``) it returns the
 reference's own image bit for bit: scikit-image 0.18's ``random_noise(..., seed=1)`` (gpet_utils.py:251) is
@@ -91,8 +91,9 @@ def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False):
     """``denoise`` of every frame of a stack in ONE batched GPU pass (gpet_denoise_images): ``imgs`` is a (T, M, N) array or a
     sequence of (M, N) frames of one dtype, the result a (T, M, N) array whose frame t equals ``denoise(imgs[t], technique,
     kwargs)`` bit for bit.  ``return_n_iter``: also the iterations 'tvc' ran per frame (0 for the filters).  'nl' with
-    ``fast_mode=False`` and 'wavelet' with the ``wavelet`` key are stages of their own (gpet_nlmeans_images, gpet_wavelet_images):
-    float64 frames whatever the frames' dtype."""
+    ``fast_mode=False``, 'wavelet' with the ``wavelet`` key and 'tvb' with ``weight`` are stages of their own (gpet_nlmeans_images,
+    gpet_wavelet_images, gpet_tvb_images): float64 frames whatever the frames' dtype; for 'tvb' ``return_n_iter`` gives the sweeps
+    every frame ran (0 for 'nl' and 'wavelet')."""
     raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs))  # (refuses a bad spec before a device is needed)
     out, n_iter = (ctx or _ctx()).denoise_images(raw)
     return (out, n_iter) if return_n_iter else out
@@ -106,7 +107,7 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     filters' bit for bit (the Gaussian taps come from the C library's exp, which differs from numpy's by one unit in the last
     place for some arguments -- visible in float64 results only), 'tvc' bit for bit with one deviation: a float32 image is
     iterated in float64 (the result is the reference's on ``image.astype(float64)``).  Images of any other dtype are converted
-    to float64 first.  Any other keyword raises ValueError naming it; 'tvb' raises NotImplementedError; an
+    to float64 first.  Any other keyword raises ValueError naming it; an
     unknown technique prints the reference's message and returns None, as the reference does.  ``plot`` and ``verbose`` are
     accepted and ignored.
     'nl' is scikit-image's non-local means with ``fast_mode=False`` (``patch_size``, ``patch_distance``, ``h``, ``sigma``): the
@@ -120,7 +121,14 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     mean of squares under a BayesShrink threshold is summed in the device's own order (within 2 (n - 1) 2^-53 relative of numpy's;
     DESIGN.md 9) -- everything else is the library's bit for bit.  It runs only when kwargs names the ``wavelet`` key
     (``dict(wavelet='db1')`` is the library's default call); without the key 'wavelet' raises NotImplementedError as it always
-    did.  A frame whose finest diagonal band is all zero raises GpetError naming the frame (the library returns NaN)."""
+    did.  A frame whose finest diagonal band is all zero raises GpetError naming the frame (the library returns NaN).
+    'tvb' is scikit-image's split-Bregman ``denoise_tv_bregman`` (``weight``, ``max_iter``, ``eps``, ``isotropic``) in float64: integer
+    frames enter as x / 255, x / 65535, a float32 frame gives the library's result on ``image.astype(float64)``, the result is not
+    clipped.  The sweeps keep the library's raster order (one workgroup walks a frame's anti-diagonals); only the sum of squared
+    changes under the stopping rule is added in the device's own order (within 2 (n - 1) 2^-53 relative of the library's;
+    DESIGN.md 9), so the output is the library's bit for bit wherever the sweep counts agree.  It runs only when kwargs gives
+    ``weight``, the library's required argument; without it 'tvb' raises NotImplementedError as it always did.  Frames of at least
+    2 x 2 pixels whose smaller extent is at most 768."""
     if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.DN_NOT_BUILT:
         print("Denoising technique not implemented.")
         return None

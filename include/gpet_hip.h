@@ -310,6 +310,33 @@ typedef struct gpet_wavelet {
  * frame; the message names the first such frame, and the outputs of that call are not to be used. */
 int gpet_wavelet_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_wavelet* spec,
                         unsigned int flags, void* const* out);
+/* ---- a0: split-Bregman total-variation denoising, gpet_utils.denoise(image, 'tvb', kwargs) -- */
+/* scikit-image 0.18.3's denoise_tv_bregman(image, weight, max_iter, eps, isotropic) on 2-D single-channel frames: Gauss-Seidel
+ * sweeps over u with the split variables dx, dy and the Bregman variables bx, by, until the root mean square change of a sweep is
+ * at most eps or max_iter sweeps have run.  All arithmetic is float64 in the library's order of operations
+ * (csrc/gpet_tvb_plan.h states it); the result is float64 and is not clipped.  The raster order of a sweep is kept: the cells of
+ * an anti-diagonal are independent, one workgroup per frame walks the diagonals, and the frames of a call run side by side.  A
+ * stage of its own like non-local means and the wavelet stage.  Two deviations: an f32 frame gives the library's result on the
+ * frame widened to f64, and the sum of squared changes under the stopping rule is added in the order the plan header defines,
+ * not in raster order -- the two sums of n = M N terms differ by at most 2 (n - 1) 2^-53 relative, so the sweep counts can differ
+ * only when a sweep's rmse lies that close to eps; where the counts agree the output is the library's bit for bit.  u8 / u16 frames
+ * enter as x / 255, x / 65535 (a product with the rounded reciprocal). */
+typedef struct gpet_tvb {
+  double weight;     /* above 0: the library's required argument (lam = 2 weight) */
+  double eps;        /* not negative; the library's default 1e-3 */
+  int32_t max_iter;  /* at least 1; the library's default 100 */
+  int32_t isotropic; /* not 0: isotropic TV (the library's default), 0: anisotropic */
+} gpet_tvb;
+/* out[] are DEVICE pointers (f64 [M*N] each) on the context's device */
+#define GPET_TVB_OUT_ON_DEVICE 8u
+/* Split-Bregman denoising of n_img frames [M*N] of pixel type pix: out[g] f64 [M*N] receives frame g, n_iter_out[g] (host, or NULL)
+ * the sweeps frame g ran.  Host frames go up in staging chunks; every frame's six skewed arrays ((M + 2)(N + 2) doubles each) live in
+ * workspace the context owns, grown on demand and sized per chunk.  flags: GPET_RAW_ON_DEVICE, GPET_TVB_OUT_ON_DEVICE; with both and
+ * n_iter_out NULL nothing is waited for.  GPET_ERR_BAD_ARG, gpet_last_error naming the cause, for weight <= 0, eps < 0,
+ * max_iter < 1, M < 2 or N < 2 (the library raises on a 1-pixel axis), min(M, N) above 768 (a diagonal's hand-over must fit 64 KB
+ * of LDS), an unknown pix, a null spec, frame or output. */
+int gpet_tvb_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_tvb* spec, unsigned int flags,
+                    void* const* out, int32_t* n_iter_out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
