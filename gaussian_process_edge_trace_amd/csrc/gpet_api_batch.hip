@@ -861,8 +861,13 @@ int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
       HIPCHK(c, hipMemcpyAsync(ord.data(), E.order, (size_t)s.rank * 4, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, gpet_wait(c->stream));
     }
+    // (the rows' squared norms in the rows' order, which the Jacobi's own diagonal decided: within a group of eigenvalues that
+    //  are equal to rounding the norms need not follow it to the last bit -- the values leave in descending order)
+    std::vector<double> ev(s.rank);
+    for (int k = 0; k < s.rank; ++k) ev[k] = th[ord[k]];
+    std::sort(ev.begin(), ev.end(), [](double a, double b) { return a > b; });
     double* o = (double*)dst;
-    for (size_t k = 0; k < bytes / 8; ++k) o[k] = th[ord[k]];
+    for (size_t k = 0; k < bytes / 8; ++k) o[k] = ev[k];
     return GPET_OK;
   }
   if (bytes) {

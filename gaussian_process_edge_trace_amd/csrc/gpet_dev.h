@@ -19,6 +19,8 @@ struct EigState {
   int warm;                        // warm start (k_ojw_*): 0 = cold (pivoted Cholesky), 1 = the rows come from the previous iteration's, 2 = tried and failed
   int t_slot[2], stop_slot[2];     // blocked pivoting: rows so far / finished, as block (blk & 1) must see them -- a block
                                    // writes the OTHER slot, so workgroups of one launch never read what it writes
+  float prev_rel2;                 // maxrel of the sweep before, rounded to float (oj_verdict); +inf before the first sweep.  (In the
+                                   // record's last four bytes: its size, which the arena layout is pinned on, stays 72.)
 };
 
 // One entry per edge, stored in a device array; kernels index it with blockIdx.y.

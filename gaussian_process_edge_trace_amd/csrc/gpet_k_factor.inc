@@ -1678,6 +1678,9 @@ __global__ void __launch_bounds__(256) k_struct_rows(EdgeDev* edges) {
 
 // step 4: factor rows  A[k, :] = sum_t W[t, order[k]] * G[t, :]  (= sqrt(s_k) v_k up to sign).
 // Sign convention (LAPACK's is implementation-defined): sum_j A[k, j] / (j + 1) >= 0.
+// The eigenvalue the stage reports is the row's squared norm, as on the any-rank path (k_oj_norms): the Jacobi's diagonal entry,
+// which has ordered the rows, carries the rounding of every rotation of every sweep and differs from |A_k|^2 by up to 2e-14 of
+// it at rank 96 (tests/test_gpu_factor_injected.py), twice what the sum of squares itself can err by.
 __global__ void __launch_bounds__(256) k_factor_rows(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.y];
   const gpet_scalars* sc = E.sc;
@@ -1689,14 +1692,17 @@ __global__ void __launch_bounds__(256) k_factor_rows(EdgeDev* edges) {
   const int col = E.order[k];
   for (int t = threadIdx.x; t < r; t += blockDim.x) s_w[t] = E.W[(size_t)t * E.r_cap + col];
   __syncthreads();
-  double part = 0.0;
+  double part = 0.0, sq = 0.0;
   for (int j = threadIdx.x; j < Lg; j += blockDim.x) {
     double acc = 0.0;
     for (int t = 0; t < r; ++t) acc += s_w[t] * E.G[(size_t)t * Lg + j];
     E.A[(size_t)k * Lg + j] = acc;
     part += acc / (double)(j + 1);
+    sq += acc * acc;
   }
   const double dot = block_sum(part, s_red);
+  const double nrm2 = block_sum(sq, s_red);
+  if (threadIdx.x == 0) E.theta[col] = nrm2;
   if (dot < 0.0)
     for (int j = threadIdx.x; j < Lg; j += blockDim.x) E.A[(size_t)k * Lg + j] = -E.A[(size_t)k * Lg + j];
 }

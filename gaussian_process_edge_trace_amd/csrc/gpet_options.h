@@ -29,7 +29,7 @@ namespace gpet {
   X(oj_half_stage, -1, -1, 1, "any-rank Jacobi (k_oj_persist), even widths above 512 columns: a pair's 16-row panel staged in LDS one 512-column half at a time (66 KB, two workgroups per CU, the first half read a second time for the row update) instead of whole (131 KB at 1 024 columns, one per CU); the same bits; -1: where a round has more pair slots than the GPU has CUs") \
   X(oj_args, 1, 0, 1, "any-rank factor: per-edge pointers of small batches in the kernel arguments; 0: through the edge table") \
   X(oj_tol_exp, 8, 4, 15, "any-rank Jacobi stops after a sweep whose pairs were all orthogonal to 10^-x relative") \
-  X(oj_max_sweeps, 16, 1, 64, "sweep budget of the any-rank Jacobi") \
+  X(oj_max_sweeps, 20, 1, 64, "sweep budget of the any-rank Jacobi") \
   X(comm_force_rccl, 0, 0, 1, "testing: gpet_comm_create builds an RCCL communicator also for a world of one (whose collectives are otherwise plain copies)") \
   X(pchol_multi, 2, 0, 2, "edges wider than 1 024 columns of rank <= 96: pivoted Cholesky over the GPU instead of one workgroup (k_pchol): 2 = blocks of pivots within a tenth of the block's first (k_pcb_block), 1 = one pivot per launch in the greedy order (k_pcx_step)") \
   X(pcx_one_pivot, 0, 0, 1, "1: multi-workgroup pivoted Cholesky one pivot per launch (cross-check of the blocked candidate selection)") \

@@ -1,5 +1,5 @@
 """Batches for the tests that inject a stage's inputs (tests/test_gpu_sample_gemm_exact.py, tests/test_gpu_score_injected.py,
-tests/test_gpu_kde_pix_injected.py, tests/test_gpu_posterior_injected.py).
+tests/test_gpu_kde_pix_injected.py, tests/test_gpu_posterior_injected.py, tests/test_gpu_factor_injected.py).
 
 They come from the constructor's own parameter functions (gpet.resolve_params, gpet.to_abi_params) and _lib.Batch rather than
 from GP_Edge_Tracing: the constructor, like the reference's, turns N_samples <= 100 into 1000, and these tests need the exact
@@ -23,7 +23,8 @@ def make_batch(amd, ctx, grad, spans, S, factor_cap=0, z_cols=0, sample_dtype=No
     one on row M - 2), the image's own by default.
     kernel: the constructor's kernel_options dict (KERNEL by default).  obs_cap: the capacity of the observation set, so that
     n_cap = n_init + max(obs_cap, the edge's own bin count) -- by default the bin count alone, as the constructor has it.
-    delta_x, fix_endpoints, kernel and obs_cap may be lists with one entry per edge.
+    factor_cap: the capacity of the factor (0: 96 rows, or what the kernel's length scale asks for).
+    delta_x, fix_endpoints, kernel, obs_cap and factor_cap may be lists with one entry per edge.
     inits: one [n_init, 2] array of (x, y) init points per edge, sorted by x, instead of the two on the span's ends; the span
     stays spans[e], so any count from one init point up is reachable (the constructor reads the span off the init points)."""
     from gaussian_process_edge_trace_amd.gpet import resolve_params, to_abi_params
@@ -34,7 +35,7 @@ def make_batch(amd, ctx, grad, spans, S, factor_cap=0, z_cols=0, sample_dtype=No
         p = resolve_params(init, grad.shape, KERNEL if kernel is None else _of_edge(kernel, e), noise_y=1, N_samples=max(S, 101),
                            score_thresh=score_thresh, delta_x=_of_edge(delta_x, e), keep_ratio=keep_ratio, pixel_thresh=pixel_thresh, seed=1,
                            fix_endpoints=_of_edge(fix_endpoints, e))
-        q = to_abi_params(p, obs_cap=None if obs_cap is None else _of_edge(obs_cap, e), factor_cap=factor_cap, z_cols=z_cols)
+        q = to_abi_params(p, obs_cap=None if obs_cap is None else _of_edge(obs_cap, e), factor_cap=_of_edge(factor_cap, e), z_cols=z_cols)
         q.n_samples, q.n_keep = S, max(1, int(keep_ratio * S))
         if inits is not None:
             p["init"] = np.ascontiguousarray(inits[e], dtype=np.int64).reshape(-1, 2)
