@@ -977,6 +977,7 @@ SYMBOLS = {
     "gpet_final_predict_all": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "gpet_final_fit_all": (C.c_int, [_P, C.POINTER(C.c_uint32), _P, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
     "gpet_final_optimize": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "gpet_final_problems": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32)]),
     "gpet_batch_set_sample_dtype": (C.c_int, [_P, C.c_int]),
     "gpet_batch_set_sample_arith": (C.c_int, [_P, C.c_int]),
     "gpet_batch_set_rng": (C.c_int, [_P, C.c_int]),
@@ -1946,6 +1947,16 @@ class Batch:
         self.ctx.check(self.lib.gpet_final_optimize(self.h, starts.shape[1], starts.ctypes.data, bounds.ctypes.data,
                                                     th.ctypes.data, C.byref(rounds)))
         return th[:, :3].copy(), th[:, 3].copy(), rounds.value
+
+    def final_problems(self):
+        """Every (edge, start) problem of the last final_fit_all / final_optimize (gpet_final_problems), edge-major: dict of
+        x [P, 3], f [P], g [P, 3], iter, nfev, why [P] (integers)."""
+        n = C.c_int32()
+        self.ctx.check(self.lib.gpet_final_problems(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 10))
+        self.ctx.check(self.lib.gpet_final_problems(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return dict(x=out[:, 0:3].copy(), f=out[:, 3].copy(), g=out[:, 4:7].copy(), iter=out[:, 7].astype(np.int64),
+                    nfev=out[:, 8].astype(np.int64), why=out[:, 9].astype(np.int64))
 
     def lml_batch(self, edge_of, theta):
         edge_of = np.ascontiguousarray(edge_of, dtype=np.int32)

@@ -270,6 +270,7 @@ static int lb_ensure(gpet_batch* b, int P) {
 static int lb_rounds(gpet_batch* b, int P, int n_max, int lag_cap, const LbCfg& cfg, int* rounds_out) {
   gpet_ctx* c = b->ctx;
   hipStream_t st = b->fit;
+  b->lb_last_P = P;
   HIPCHK(c, launch_lb_init(st, b->lb_probs, P, b->lb_starts, b->lb_slot_edge[0], b->lb_slot_theta[0], b->lb_slot_src[0], cfg));
   // (for problem sets that are resident all at once -- 4 workgroups on each of 256 CUs -- the chain of a problem's ~50
   //  evaluations is what takes the time: 3.2 instead of 4.8 ms for a single edge; bigger sets are throughput-bound and a
@@ -440,6 +441,22 @@ int gpet_final_optimize(gpet_batch* b, int n_starts, const double* starts, const
   HIPCHK(c, gpet_wait(b->fit));
   if (rounds_out) *rounds_out = rounds;
   return check_device_status(b);
+}
+
+int gpet_final_problems(gpet_batch* b, double* out, int cap, int32_t* n_out) {
+  GPET_BATCH_SCOPE(b);
+  if (!b || !n_out || cap < 0 || (cap > 0 && !out)) return GPET_ERR_BAD_ARG;
+  gpet_ctx* c = b->ctx;
+  const int P = b->lb_last_P;
+  if (P < 1 || !b->lb_probs) return fail(c, GPET_ERR_STATE, "gpet_final_problems: no converged fit has run on this batch yet");
+  *n_out = P;
+  if (cap < P) return cap == 0 ? GPET_OK : fail(c, GPET_ERR_BAD_ARG, "gpet_final_problems: %d problems, room for %d", P, cap);
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<char> host(lb_prob_bytes() * (size_t)P);
+  HIPCHK(c, hipMemcpyAsync(host.data(), b->lb_probs, host.size(), hipMemcpyDeviceToHost, b->fit));
+  HIPCHK(c, gpet_wait(b->fit));
+  lb_unpack_records(host.data(), P, out);
+  return GPET_OK;
 }
 
 int gpet_lml_stats(gpet_batch* b, int reset, double* kernel_ms, int64_t* evaluations, int32_t* launches) {

@@ -151,6 +151,7 @@ struct gpet_batch {
   // device-resident converged fits (gpet_final_fit_all): one allocation, carved
   char* lb_mem = nullptr;
   int lb_cap_P = 0;  // problems the optimiser's workspace holds
+  int lb_last_P = 0;  // problems of the last run of the optimiser (gpet_final_problems)
   void* lb_probs = nullptr;
   double *lb_starts = nullptr, *lb_scratch = nullptr, *lb_f = nullptr, *lb_g = nullptr, *lb_theta_out = nullptr;
   int* lb_slot_edge[2] = {nullptr, nullptr};

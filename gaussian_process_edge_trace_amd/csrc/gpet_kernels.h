@@ -178,6 +178,8 @@ struct LbCfg {
 };
 LbCfg lb_default_cfg();  // the tracer's converged fit: gpet.py:246-248, theta0 + 12 restarts
 size_t lb_prob_bytes();
+// host copy of P problem records -> out[P][10] = x[3], f, g[3], iter, nfev, why (gpet_final_problems; LbProb stays private)
+void lb_unpack_records(const void* h_probs, int P, double* out);
 hipError_t launch_fin_prepare(hipStream_t st, EdgeDev* d_edges, int B, const unsigned int* d_seeds, double* d_starts,
                               double* d_scratch, int scratch_stride, int n_cap);
 hipError_t launch_lb_init(hipStream_t st, void* d_probs, int P, const double* d_starts, int* slot_edge, double* slot_theta,

@@ -2,8 +2,30 @@
 // round-based driver (k_lb_advance, one thread per problem and round) and the persistent objective kernel of
 // gpet_kernels.hip (k_lml16_fit: a problem's evaluations and its state machine in one workgroup).  The functions are
 // NOT inlined: both callers then run the same machine code, so a problem takes the same path either way.
+//
+// The header needs no HIP (only <math.h>): LB_DEV is __device__ under hipcc and empty for a host compiler, so the tests
+// compile the very same state machine on the CPU (with -ffp-contract=off, as the kernels that call it are) and drive it
+// against scipy (tests/test_lbfgsb_host.py).  LB_HIT(i) counts the branch i when LB_BRANCH_CENSUS is defined -- the
+// tests' second build, which shows that their corpus enters every branch; in the library it expands to nothing.
 #pragma once
-#include "gpet_kernels.h"
+#include <math.h>
+
+// LB_FP_STRICT opens every function of the state machine: no contraction of a * b + c into a fused multiply-add, so that
+// the device takes, on the same objective values, the very path of the host build that the tests pin against scipy (a kernel's
+// own "fp contract(off)" does not reach the functions it calls).  g++ takes -ffp-contract=off on its command line.
+#if defined(__clang__)
+#define LB_FP_STRICT _Pragma("clang fp contract(off)")
+#else
+#define LB_FP_STRICT
+#endif
+
+#if defined(__HIPCC__)
+#define LB_DEV __device__
+#define LB_DEV_INLINE __device__ __forceinline__
+#else
+#define LB_DEV
+#define LB_DEV_INLINE inline
+#endif
 
 // LB_FN: how the state machine's functions are compiled into the including unit.  Default: not inlined (the round-based driver
 // k_lb_advance, gpet_lbfgsb.hip).  gpet_kernels.hip defines it as inline for k_lml16_fit (round 6): inside that kernel a call costs
@@ -28,6 +50,37 @@ namespace gpet {
 
 enum { LB_TASK_FIRST = 0, LB_TASK_LS = 1, LB_TASK_DONE = 2 };
 
+// branches of the state machine that the host tests count (tests/test_lbfgsb_host.py names them in this order)
+enum {
+  LB_BR_LS_CONTINUE = 0,  // lb_ls_step: another trial point
+  LB_BR_LS_CONVERGED,     // lb_ls_step: sufficient decrease and curvature
+  LB_BR_LS_WARNING,       // lb_ls_step: step at a bound / interval exhausted
+  LB_BR_DCSTEP_1,         // lb_dcstep: higher function value
+  LB_BR_DCSTEP_2,         // lb_dcstep: derivatives of opposite sign
+  LB_BR_DCSTEP_3,         // lb_dcstep: derivative decreases in magnitude
+  LB_BR_DCSTEP_4,         // lb_dcstep: derivative does not decrease
+  LB_BR_CAUCHY_BREAK,     // lb_cauchy: the path went past a breakpoint
+  LB_BR_SUBSM_PROJECTED,  // lb_subsm: the projected point is kept
+  LB_BR_SUBSM_BACKTRACK,  // lb_subsm: backtracking from the Cauchy point
+  LB_BR_RESTART_ASCENT,   // ascent direction: memory dropped
+  LB_BR_RESTART_LNSRCH,   // line search failed: memory dropped
+  LB_BR_RESTART_STALE,    // subspace matrix out of date in the reference: memory dropped
+  LB_BR_SKIP_UPDATE,      // curvature too small: no pair stored
+  LB_BR_MEMORY_SHIFT,     // the oldest of LB_M pairs dropped
+  LB_BR_WHY_1,
+  LB_BR_WHY_2,
+  LB_BR_WHY_3,
+  LB_BR_WHY_4,
+  LB_BR_WHY_5,
+  LB_NBRANCH
+};
+#ifdef LB_BRANCH_CENSUS
+extern "C" long long lb_census[LB_NBRANCH];
+#define LB_HIT(i) ((void)++lb_census[i])
+#else
+#define LB_HIT(i) ((void)0)
+#endif
+
 struct LbProb {
   double x[3], g[3], f;
   double xe[3];  // the point whose objective value is pending
@@ -37,11 +90,14 @@ struct LbProb {
   double theta;
   double stp, stpmx, gd, gdold;
   double finit, ginit, gtest, width, width1, stx, fx, gx, sty, fy, gy, stmin, stmax;
-  int ncorr, brackt, stage, iter, nfev, ifun, task, why, edge, slot;
+  int ncorr, brackt, stage, iter, nfev, ifun, task, why, edge;
+  // the reference's subspace matrix, restated (gpet_lbfgsb.hip): stale = an iteration with stored pairs had no free
+  // variable at its Cauchy point, so the matrix was not brought up to date; rows = pairs whose rows it has ever formed
+  int stale, rows, pad_;
 };
 
 // bounds of theta = log(constant, length_scale, noise_level)  (gpet.py:246-248)
-static __device__ __forceinline__ void lb_bounds(double* lo, double* hi) {
+static LB_DEV_INLINE void lb_bounds(double* lo, double* hi) {
   lo[0] = log(0.01);
   hi[0] = log(1e3);
   lo[1] = log(0.1);
@@ -50,7 +106,8 @@ static __device__ __forceinline__ void lb_bounds(double* lo, double* hi) {
   hi[2] = log(1.0);
 }
 
-static __device__ LB_FN double lb_projgr(const double* x, const double* g, const double* l, const double* u) {
+static LB_DEV LB_FN double lb_projgr(const double* x, const double* g, const double* l, const double* u) {
+  LB_FP_STRICT
   double s = 0.0;
   for (int i = 0; i < 3; ++i) {
     double gi = g[i];
@@ -62,7 +119,8 @@ static __device__ LB_FN double lb_projgr(const double* x, const double* g, const
 }
 
 // B = theta I updated by the stored pairs, oldest first
-static __device__ LB_FN void lb_dense_B(const LbProb& p, double B[3][3]) {
+static LB_DEV LB_FN void lb_dense_B(const LbProb& p, double B[3][3]) {
+  LB_FP_STRICT
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) B[i][j] = (i == j) ? p.theta : 0.0;
   for (int k = 0; k < p.ncorr; ++k) {
@@ -79,8 +137,9 @@ static __device__ LB_FN void lb_dense_B(const LbProb& p, double B[3][3]) {
 
 // generalised Cauchy point (algorithm CP of Byrd et al.): first local minimiser of the quadratic model along the
 // projected steepest-descent path.  free[i] = variable i is not at a bound at xcp.
-static __device__ LB_FN void lb_cauchy(const double* x, const double* g, const double* l, const double* u, const double B[3][3],
+static LB_DEV LB_FN void lb_cauchy(const double* x, const double* g, const double* l, const double* u, const double B[3][3],
                           double sbgnrm, double* xcp, int* free_) {
+  LB_FP_STRICT
   for (int i = 0; i < 3; ++i) {
     xcp[i] = x[i];
     free_[i] = 0;
@@ -132,6 +191,7 @@ static __device__ LB_FN void lb_cauchy(const double* x, const double* g, const d
     const int ib = order[k];
     const double dt = t[ib] - tsum;
     if (dtm < dt) break;
+    LB_HIT(LB_BR_CAUCHY_BREAK);
     tsum += dt;
     for (int i = 0; i < 3; ++i) z[i] += dt * d[i];
     if (d[ib] > 0.0) {
@@ -142,20 +202,21 @@ static __device__ LB_FN void lb_cauchy(const double* x, const double* g, const d
       xcp[ib] = l[ib];
     }
     hit[ib] = 1;
+    // the derivatives of the model along the path are UPDATED across the breakpoint, as L-BFGS-B's cauchy does (with
+    // d' = d - d_b e_b, z' the point at the breakpoint: f1' = f1 + dt f2 + d_b^2 - d_b (B z')_b, f2' = f2 - 2 d_b (B d)_b +
+    // d_b^2 B_bb), not summed afresh from d' and z': where one variable's gradient dwarfs the others', f2 - d_b^2 cancels
+    // and the fresh sum is the more accurate one, but the Cauchy point then parts from the reference's by that error
+    const double dibp = d[ib];
+    const double Bz_b = B[ib][0] * z[0] + B[ib][1] * z[1] + B[ib][2] * z[2];
+    const double Bd_b = B[ib][0] * d[0] + B[ib][1] * d[1] + B[ib][2] * d[2];
     d[ib] = 0.0;
     if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) {  // every variable is fixed
       dtm = 0.0;
       done = true;
       break;
     }
-    f1 = 0.0;
-    f2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      const double Bz = B[i][0] * z[0] + B[i][1] * z[1] + B[i][2] * z[2];
-      const double Bd = B[i][0] * d[0] + B[i][1] * d[1] + B[i][2] * d[2];
-      f1 += (g[i] + Bz) * d[i];
-      f2 += d[i] * Bd;
-    }
+    f1 = f1 + dt * f2 + dibp * dibp - dibp * Bz_b;
+    f2 = f2 - 2.0 * dibp * Bd_b + dibp * dibp * B[ib][ib];
     f2 = fmax(LB_EPS * f2_org, f2);
     dtm = -f1 / f2;
   }
@@ -169,7 +230,8 @@ static __device__ LB_FN void lb_cauchy(const double* x, const double* g, const d
 }
 
 // x = A^-1 b for an m x m system, m <= 3, LU with partial pivoting (what numpy.linalg.solve / LAPACK gesv does)
-static __device__ LB_FN void lb_solve(int m, double A[3][3], double* b, double* x) {
+static LB_DEV LB_FN void lb_solve(int m, double A[3][3], double* b, double* x) {
+  LB_FP_STRICT
   int perm[3] = {0, 1, 2};
   for (int c = 0; c < m; ++c) {
     int pv = c;
@@ -198,8 +260,9 @@ static __device__ LB_FN void lb_solve(int m, double A[3][3], double* b, double* 
 }
 
 // subspace minimisation over the free variables at the Cauchy point, with the projection / backtracking of L-BFGS-B 3.0
-static __device__ LB_FN void lb_subsm(const double* x, const double* g, const double* xcp, const int* free_, const double* l,
+static LB_DEV LB_FN void lb_subsm(const double* x, const double* g, const double* xcp, const int* free_, const double* l,
                          const double* u, const double B[3][3], double* xn) {
+  LB_FP_STRICT
   int idx[3], m = 0;
   for (int i = 0; i < 3; ++i) {
     xn[i] = xcp[i];
@@ -223,9 +286,20 @@ static __device__ LB_FN void lb_subsm(const double* x, const double* g, const do
     if (xn[k] == l[k] || xn[k] == u[k]) iword = 1;
   }
   if (!iword) return;
-  double dd_p = 0.0;
-  for (int i = 0; i < 3; ++i) dd_p += (xn[i] - x[i]) * g[i];
-  if (dd_p > 0.0) {
+  // L-BFGS-B 3.0 keeps the projected point if it is a descent direction (dd_p <= 0) and backtracks from the Cauchy point
+  // otherwise.  dd_p is EXACTLY zero in exact arithmetic whenever the last line search ended at the minimiser along a
+  // direction that the projection reproduces (any quadratic whose Newton point lies outside the box), so its sign is then
+  // rounding noise, and a projected point taken on that noise is no descent direction: the line search returns to x and the
+  // run ends on the reduction-of-f test far from the optimum (scipy does the same where its noise falls that way).  Noise
+  // counts as "not a descent direction" here: dd_p carries the relative error of the 3 x 3 solve, cond(B) eps, up to 1e-10 at
+  // the condition numbers (1e6) that the tests cover.
+  double dd_p = 0.0, dd_abs = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    dd_p += (xn[i] - x[i]) * g[i];
+    dd_abs += fabs((xn[i] - x[i]) * g[i]);
+  }
+  if (dd_p > -1e-10 * dd_abs) {
+    LB_HIT(LB_BR_SUBSM_BACKTRACK);
     for (int i = 0; i < 3; ++i) xn[i] = xcp[i];
     double alpha = 1.0, temp1 = 1.0;
     int ibd = -1;
@@ -258,15 +332,19 @@ static __device__ LB_FN void lb_subsm(const double* x, const double* g, const do
       }
     }
     for (int a = 0; a < m; ++a) xn[idx[a]] = xn[idx[a]] + alpha * dF[a];
+  } else {
+    LB_HIT(LB_BR_SUBSM_PROJECTED);
   }
 }
 
 // MINPACK-2 dcstep: safeguarded cubic / quadratic step of the More-Thuente line search
-static __device__ LB_FN void lb_dcstep(double& stx, double& fx, double& dx, double& sty, double& fy, double& dy, double& stp,
+static LB_DEV LB_FN void lb_dcstep(double& stx, double& fx, double& dx, double& sty, double& fy, double& dy, double& stp,
                           double fp, double dp, int& brackt, double stpmin, double stpmax) {
+  LB_FP_STRICT
   const double sgnd = dp * (dx / fabs(dx));
   double stpf;
   if (fp > fx) {
+    LB_HIT(LB_BR_DCSTEP_1);
     const double th = 3.0 * (fx - fp) / (stp - stx) + dx + dp;
     const double s = fmax(fabs(th), fmax(fabs(dx), fabs(dp)));
     double gam = s * sqrt(fmax(0.0, (th / s) * (th / s) - (dx / s) * (dp / s)));
@@ -277,6 +355,7 @@ static __device__ LB_FN void lb_dcstep(double& stx, double& fx, double& dx, doub
     stpf = (fabs(stpc - stx) < fabs(stpq - stx)) ? stpc : stpc + (stpq - stpc) / 2.0;
     brackt = 1;
   } else if (sgnd < 0.0) {
+    LB_HIT(LB_BR_DCSTEP_2);
     const double th = 3.0 * (fx - fp) / (stp - stx) + dx + dp;
     const double s = fmax(fabs(th), fmax(fabs(dx), fabs(dp)));
     double gam = s * sqrt(fmax(0.0, (th / s) * (th / s) - (dx / s) * (dp / s)));
@@ -287,6 +366,7 @@ static __device__ LB_FN void lb_dcstep(double& stx, double& fx, double& dx, doub
     stpf = (fabs(stpc - stp) > fabs(stpq - stp)) ? stpc : stpq;
     brackt = 1;
   } else if (fabs(dp) < fabs(dx)) {
+    LB_HIT(LB_BR_DCSTEP_3);
     const double th = 3.0 * (fx - fp) / (stp - stx) + dx + dp;
     const double s = fmax(fabs(th), fmax(fabs(dx), fabs(dp)));
     double gam = s * sqrt(fmax(0.0, (th / s) * (th / s) - (dx / s) * (dp / s)));
@@ -307,6 +387,7 @@ static __device__ LB_FN void lb_dcstep(double& stx, double& fx, double& dx, doub
       stpf = fmax(stpmin, stpf);
     }
   } else {
+    LB_HIT(LB_BR_DCSTEP_4);
     if (brackt) {
       const double th = 3.0 * (fp - fy) / (sty - stp) + dy + dp;
       const double s = fmax(fabs(th), fmax(fabs(dy), fabs(dp)));
@@ -338,7 +419,8 @@ static __device__ LB_FN void lb_dcstep(double& stx, double& fx, double& dx, doub
 }
 
 // MINPACK-2 dcsrch, one return per objective evaluation.  Returns 0: evaluate at the new p.stp; 1: converged; 2: warning
-static __device__ LB_FN int lb_ls_step(LbProb& p, double f, double g) {
+static LB_DEV LB_FN int lb_ls_step(LbProb& p, double f, double g) {
+  LB_FP_STRICT
   const double stpmin = 0.0, stpmax = p.stpmx;
   double stp = p.stp;
   const double ftest = p.finit + stp * p.gtest;
@@ -349,7 +431,11 @@ static __device__ LB_FN int lb_ls_step(LbProb& p, double f, double g) {
   if (stp == stpmax && f <= ftest && g <= p.gtest) task = 2;
   if (stp == stpmin && (f > ftest || g >= p.gtest)) task = 2;
   if (f <= ftest && fabs(g) <= LB_GTOL * (-p.ginit)) task = 1;
-  if (task != 0) return task;
+  if (task != 0) {
+    LB_HIT(task == 1 ? LB_BR_LS_CONVERGED : LB_BR_LS_WARNING);
+    return task;
+  }
+  LB_HIT(LB_BR_LS_CONTINUE);
   if (p.stage == 1 && f <= p.fx && f > ftest) {
     const double fm = f - stp * p.gtest;
     double fxm = p.fx - p.stx * p.gtest, fym = p.fy - p.sty * p.gtest;
@@ -382,15 +468,19 @@ static __device__ LB_FN int lb_ls_step(LbProb& p, double f, double g) {
   return 0;
 }
 
-static __device__ LB_FN void lb_emit_trial(LbProb& p) {
+static LB_DEV LB_FN void lb_emit_trial(LbProb& p, const double* l, const double* u) {
+  LB_FP_STRICT
   p.ifun += 1;
   p.nfev += 1;
-  for (int i = 0; i < 3; ++i) p.xe[i] = (p.stp == 1.0) ? p.z[i] : p.stp * p.d[i] + p.xold[i];
+  // stp = stpmx = (bound - x) / d lands on the bound only to rounding: the trial point is kept inside the box, as scipy's
+  // line search keeps it (the objective is never asked for a point outside)
+  for (int i = 0; i < 3; ++i) p.xe[i] = (p.stp == 1.0) ? p.z[i] : fmin(u[i], fmax(l[i], p.stp * p.d[i] + p.xold[i]));
   p.task = LB_TASK_LS;
 }
 
 // search direction of a new iteration + the first trial point of its line search (or termination)
-static __device__ LB_FN void lb_begin_iteration(LbProb& p, const double* l, const double* u) {
+static LB_DEV LB_FN void lb_begin_iteration(LbProb& p, const double* l, const double* u) {
+  LB_FP_STRICT
   for (;;) {
     double B[3][3];
     lb_dense_B(p, B);
@@ -398,7 +488,20 @@ static __device__ LB_FN void lb_begin_iteration(LbProb& p, const double* l, cons
     double xcp[3];
     int free_[3];
     lb_cauchy(p.x, p.g, l, u, B, sbgnrm, xcp, free_);
-    if ((free_[0] || free_[1] || free_[2]) && p.ncorr > 0) lb_subsm(p.x, p.g, xcp, free_, l, u, B, p.z);
+    const bool any_free = free_[0] || free_[1] || free_[2];
+    if (any_free && p.ncorr > 0) {
+      if (p.stale && p.ncorr > p.rows) {  // (see LbProb::stale)
+        LB_HIT(LB_BR_RESTART_STALE);
+        p.ncorr = 0;
+        p.theta = 1.0;
+        p.stale = 0;
+        continue;
+      }
+      p.stale = 0;
+      if (p.ncorr > p.rows) p.rows = p.ncorr;
+    }
+    if (!any_free && p.ncorr > 0) p.stale = 1;
+    if (any_free && p.ncorr > 0) lb_subsm(p.x, p.g, xcp, free_, l, u, B, p.z);
     else
       for (int i = 0; i < 3; ++i) p.z[i] = xcp[i];
     for (int i = 0; i < 3; ++i) p.d[i] = p.z[i] - p.x[i];
@@ -433,8 +536,11 @@ static __device__ LB_FN void lb_begin_iteration(LbProb& p, const double* l, cons
       if (p.ncorr == 0) {
         p.task = LB_TASK_DONE;
         p.why = 4;
+        LB_HIT(LB_BR_WHY_4);
         return;
       }
+      LB_HIT(LB_BR_RESTART_ASCENT);
+      p.stale = 0;
       p.ncorr = 0;
       p.theta = 1.0;
       continue;
@@ -455,19 +561,42 @@ static __device__ LB_FN void lb_begin_iteration(LbProb& p, const double* l, cons
     p.gy = p.gd;
     p.stmin = 0.0;
     p.stmax = p.stp + 4.0 * p.stp;
-    lb_emit_trial(p);
+    lb_emit_trial(p, l, u);
     return;
   }
 }
 
+// a new problem: the start point projected onto the box, the first evaluation requested at p.xe
+static LB_DEV_INLINE void lb_init(LbProb& p, const double* start, const double* l, const double* u) {
+  for (int c = 0; c < 3; ++c) {
+    double v = start[c];
+    v = v < l[c] ? l[c] : (v > u[c] ? u[c] : v);
+    p.x[c] = v;
+    p.xe[c] = v;
+  }
+  p.ncorr = 0;
+  p.theta = 1.0;
+  p.iter = 0;
+  p.nfev = 1;
+  p.ifun = 0;
+  p.task = LB_TASK_FIRST;
+  p.why = 0;
+  p.stale = 0;
+  p.rows = 0;
+  p.pad_ = 0;
+  p.f = 0.0;
+}
+
 // consume the objective value at p.xe and move to the next trial point
-static __device__ LB_FN void lb_advance(LbProb& p, double f, const double* g, const double* l, const double* u) {
+static LB_DEV LB_FN void lb_advance(LbProb& p, double f, const double* g, const double* l, const double* u) {
+  LB_FP_STRICT
   if (p.task == LB_TASK_FIRST) {
     p.f = f;
     for (int i = 0; i < 3; ++i) p.g[i] = g[i];
     if (lb_projgr(p.x, p.g, l, u) <= LB_PGTOL) {
       p.task = LB_TASK_DONE;
       p.why = 1;
+      LB_HIT(LB_BR_WHY_1);
       return;
     }
     lb_begin_iteration(p, l, u);
@@ -492,14 +621,17 @@ static __device__ LB_FN void lb_advance(LbProb& p, double f, const double* g, co
       if (p.ncorr == 0) {
         p.task = LB_TASK_DONE;
         p.why = 5;
+        LB_HIT(LB_BR_WHY_5);
         return;
       }
+      LB_HIT(LB_BR_RESTART_LNSRCH);
+      p.stale = 0;
       p.ncorr = 0;
       p.theta = 1.0;
       lb_begin_iteration(p, l, u);
       return;
     }
-    lb_emit_trial(p);
+    lb_emit_trial(p, l, u);
     return;
   }
   // the line search accepted p.x: end of the iteration
@@ -508,12 +640,14 @@ static __device__ LB_FN void lb_advance(LbProb& p, double f, const double* g, co
   if (lb_projgr(p.x, p.g, l, u) <= LB_PGTOL) {
     p.task = LB_TASK_DONE;
     p.why = 2;
+    LB_HIT(LB_BR_WHY_2);
     return;
   }
   const double ddum0 = fmax(fabs(p.fold), fmax(fabs(p.f), 1.0));
   if ((p.fold - p.f) <= LB_FACTR_EPS * ddum0 || p.iter >= LB_MAXITER) {
     p.task = LB_TASK_DONE;
     p.why = 3;
+    LB_HIT(LB_BR_WHY_3);
     return;
   }
   double r[3], rr = 0.0;
@@ -532,6 +666,7 @@ static __device__ LB_FN void lb_advance(LbProb& p, double f, const double* g, co
   }
   if (dr > LB_EPS * ddum) {  // otherwise the update is skipped
     if (p.ncorr == LB_M) {
+      LB_HIT(LB_BR_MEMORY_SHIFT);
       for (int k = 1; k < LB_M; ++k)
         for (int i = 0; i < 3; ++i) {
           p.S[k - 1][i] = p.S[k][i];
@@ -545,6 +680,8 @@ static __device__ LB_FN void lb_advance(LbProb& p, double f, const double* g, co
     }
     p.ncorr += 1;
     p.theta = rr / dr;
+  } else {
+    LB_HIT(LB_BR_SKIP_UPDATE);
   }
   lb_begin_iteration(p, l, u);
 }

@@ -637,6 +637,14 @@ int gpet_batch_set_sample_arith(gpet_batch* b, int arith);
 int gpet_final_optimize(gpet_batch* b, int n_starts, const double* starts, const double* bounds, double* theta_out,
                         int32_t* rounds_out);
 
+/* What became of every problem of the last gpet_final_fit_all / gpet_final_optimize of this batch: *n_out = the number of
+ * (edge, start) problems P (edge-major, as the starts were given), and, if cap >= P, out[P][10] = the final point x[3], its
+ * objective value f, the gradient g[3], the number of iterations, the number of objective evaluations, and the reason for
+ * stopping (1: projected gradient <= pgtol at the start point, 2: the same after an iteration, 3: relative reduction of f <=
+ * factr * eps, 4: no descent direction, 5: line search failed).  cap = 0 only asks for the count; 0 < cap < P is
+ * GPET_ERR_BAD_ARG.  (Added without a change of GPET_ABI_VERSION: the surface only grew.) */
+int gpet_final_problems(gpet_batch* b, double* out, int cap, int32_t* n_out);
+
 /* Device time of the LML kernel launches of this batch since the last reset (hipEvents around each launch), the
  * number of objective evaluations and of launches; any of the outputs may be NULL.  (bench.py's roofline leg.) */
 int gpet_lml_stats(gpet_batch* b, int reset, double* kernel_ms, int64_t* evaluations, int32_t* launches);

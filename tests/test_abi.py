@@ -19,7 +19,7 @@ def test_header_declares_the_documented_surface():
     names = _declared_symbols()
     for must in ["gpet_ctx_create", "gpet_grad_image", "gpet_batch_create", "gpet_gp_fit_predict", "gpet_gp_factor",
                  "gpet_gp_normals", "gpet_gp_sample", "gpet_score_curves", "gpet_select_pixels", "gpet_trace_iterate",
-                 "gpet_lml_batch", "gpet_last_error"]:
+                 "gpet_lml_batch", "gpet_final_problems", "gpet_last_error"]:
         assert must in names
 
 
