@@ -158,8 +158,7 @@ void gpet_ctx_destroy(gpet_ctx* c) {
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->raw_dev) (void)hipFree(c->raw_dev);
   if (c->raw_tab) (void)hipFree(c->raw_tab);
-  if (c->wv_ws) (void)hipFree(c->wv_ws);
-  if (c->tvb_ws) (void)hipFree(c->tvb_ws);
+  if (c->pre_ws) (void)hipFree(c->pre_ws);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }

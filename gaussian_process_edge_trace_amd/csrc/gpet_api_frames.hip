@@ -282,11 +282,85 @@ int gpet_denoise_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
 }  // extern "C"
 
 // ---- the stages of their own in front of the raw-frame path --------------------------------------------------------------------
+// What differs between the stages, as pre_stage takes it.  A stage's device block, the same on both sides: source pointers |
+// destination pointers | the stage's extras.
+struct PreStage {
+  unsigned int out_dev_bit = 0;     // the stage's GPET_*_OUT_ON_DEVICE
+  size_t extras_bytes = 0;          // zero on the way up, but for init_bytes at init_off copied from init (nullptr: none)
+  const void* init = nullptr;
+  size_t init_off = 0, init_bytes = 0;
+  size_t ws_bytes = 0;              // what a frame keeps in the context's workspace (pre_ws)
+  bool read_back = false;           // the extras come back at the end, in one copy the call waits for ...
+  const char* h_extras = nullptr;   // ... into the host copy, which pre_stage leaves here
+};
+// a chunk as a stage's launch sees it: frames first .. first + cnt - 1 of the two pointer tables, the chunk's workspace
+struct PreChunk {
+  const void* const* d_src;
+  double* const* d_dst;
+  char* d_extras;
+  char* ws;
+  int first, cnt;
+};
+static const auto no_chunk_hook = [](const PreChunk&) { return hipSuccess; };
+
+// Frames raw[] -> f64 results out[] through one stage, everything enqueued on the context's stream.  Host frames and host outputs
+// go through the staging slot in the chunks of `chunks(staged bytes per frame)` -- a chunk's frames at i * st_in, then its results
+// at per_chunk * st_in + i * st_out --, frames and outputs on the device are read and written where they lie; per chunk: the
+// frames' copies, `launch`, the results' copies, `after_chunk`.  The call waits exactly when host memory of the caller is in flight
+// or the extras are read back, and after any enqueue error (frames already enqueued must not be read after the return), which is
+// reported in preference to the wait's own.
+template <typename Chunks, typename Launch, typename Hook>
+static int pre_stage(gpet_ctx* c, const void* const* raw, void* const* out, int n_img, int pix, int M, int N, unsigned int flags,
+                     PreStage& st, Chunks&& chunks, Launch&& launch, Hook&& after_chunk) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & st.out_dev_bit) != 0;
+  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
+  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
+  const StagePlan plan = chunks(st_in + st_out);
+  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
+  if (rc) return rc;
+  rc = ctx_grow(c, &c->pre_ws, &c->pre_ws_bytes, (size_t)plan.per_chunk * st.ws_bytes);
+  if (rc) return rc;
+  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_ex = 2 * o_dst, tab_bytes = o_ex + st.extras_bytes;
+  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
+  if (rc) return rc;
+  c->h_raw_tab.assign(tab_bytes, 0);
+  char* h = c->h_raw_tab.data();
+  const void** h_src = (const void**)h;
+  void** h_dst = (void**)(h + o_dst);
+  for (int k = 0; k < plan.n_chunks; ++k)
+    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
+      const int g = stage_first(plan, k) + i;
+      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
+      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
+    }
+  if (st.init) memcpy(h + o_ex + st.init_off, st.init, st.init_bytes);
+  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
+    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
+    const PreChunk ch{(const void* const*)c->raw_tab, (double* const*)(c->raw_tab + o_dst), c->raw_tab + o_ex, c->pre_ws, first, cnt};
+    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch(ch);
+    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = after_chunk(ch);
+  }
+  if (e == hipSuccess && st.read_back) e = hipMemcpyAsync(h + o_ex, c->raw_tab + o_ex, st.extras_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (!in_dev || !out_dev || st.read_back || e != hipSuccess) {
+    const hipError_t ew = gpet_wait(c->stream);
+    HIPCHK(c, e);
+    HIPCHK(c, ew);
+  }
+  st.h_extras = h + o_ex;
+  return GPET_OK;
+}
+
 extern "C" {
 
-// Non-local means (gpet_nlmeans_plan.h).  One device block, the same on both sides: source pointers | destination pointers | taps.
-// Host frames and host outputs go through the staging slot in chunks -- a chunk's frames, then its f64 results -- with one launch
-// per chunk; frames and outputs on the device are read and written where they lie by one launch.
+// Non-local means (gpet_nlmeans_plan.h).  Extras: the taps.  One launch per chunk of the staging slot; frames and outputs both on
+// the device take one launch and no wait.
 int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
                         unsigned int flags, void* const* out) {
   if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: bad argument");
@@ -306,53 +380,24 @@ int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
   }
   for (int g = 0; g < n_img; ++g)
     if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_images: frame or output %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_NLM_OUT_ON_DEVICE) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
-  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
-  const StagePlan plan = st_in + st_out ? stage_plan(n_img, st_in + st_out) : StagePlan{n_img, 1, 0, 0};
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.slots * plan.slot_bytes);
-  if (rc) return rc;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_w = 2 * o_dst, tab_bytes = o_w + sizeof(double) * (size_t)(s * s);
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.resize(tab_bytes);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  void** h_dst = (void**)(h + o_dst);
-  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
-  for (int k = 0; k < plan.n_chunks; ++k)
-    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
-      const int g = stage_first(plan, k) + i;
-      char* slot = plan.slots ? c->raw_dev + (size_t)stage_slot(plan, k) * plan.slot_bytes : nullptr;
-      h_src[g] = in_dev ? raw[g] : slot + (size_t)i * st_in;
-      h_dst[g] = out_dev ? out[g] : slot + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
-    }
-  memcpy(h + o_w, sp.taps, sizeof(double) * (size_t)(s * s));
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
-  const double* d_w = (const double*)(c->raw_tab + o_w);
+  PreStage st;
+  st.out_dev_bit = GPET_NLM_OUT_ON_DEVICE;
+  st.init = sp.taps;
+  st.extras_bytes = st.init_bytes = sizeof(double) * (size_t)(s * s);
   const double var2 = 2.0 * sp.sigma * sp.sigma;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
-    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
-    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_nlmeans(c->stream, pix, d_src, d_dst, first, cnt, M, N, s, d, d_w, var2);
-    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
-  if (!in_dev || !out_dev || e != hipSuccess) (void)gpet_wait(c->stream);
-  HIPCHK(c, e);
-  return GPET_OK;
+  return pre_stage(
+      c, raw, out, n_img, pix, M, N, flags, st,
+      [&](size_t staged) { return staged ? stage_plan(n_img, staged) : StagePlan{n_img, 1, 0, 0}; },
+      [&](const PreChunk& k) {
+        return launch_nlmeans(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, s, d, (const double*)k.d_extras, var2);
+      },
+      no_chunk_hook);
 }
 
-// Wavelet denoising (gpet_wavelet_plan.h).  One device block: source pointers | destination pointers | sigma [n_img] | thresholds
-// [n_img * levels * 3] | means of squares [the same].  Frames go chunk by chunk (wv_chunks): host frames and host outputs through the
-// staging slot, the pyramids through the context's workspace, 2 levels + 2 launches per chunk (+ 1 with injected thresholds).  The per-frame figures come back
-// in one copy at the end, which the call waits for: a frame without a noise level is an error.
+// Wavelet denoising (gpet_wavelet_plan.h).  Extras: sigma [n_img] | thresholds [n_img * levels * 3] | means of squares [the same].
+// Frames go chunk by chunk (wv_chunks), the pyramids through the context's workspace, 2 levels + 2 launches per chunk (+ 1 with
+// injected thresholds).  The per-frame figures come back at the end, which the call waits for: a frame without a noise level is an
+// error.
 int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_wavelet* spec,
                         unsigned int flags, void* const* out) {
   if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: bad argument");
@@ -373,61 +418,36 @@ int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
                 sp.levels, sp.n_taps >= 2 ? wv_max_level(M < N ? M : N, sp.n_taps) : 0, M, N, sp.n_thresholds);
   for (int g = 0; g < n_img; ++g)
     if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_wavelet_images: frame or output %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
   const WvPlan wp = wv_plan(M, N, sp.n_taps, wv_levels(sp, M, N));
-  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_WV_OUT_ON_DEVICE) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
-  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
-  const size_t ws_bytes = dn_align(wp.frame_doubles * sizeof(double));
-  const StagePlan plan = wv_chunks(n_img, st_in + st_out, wp.frame_doubles);
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
-  if (rc) return rc;
-  rc = ctx_grow(c, &c->wv_ws, &c->wv_ws_bytes, (size_t)plan.per_chunk * ws_bytes);
-  if (rc) return rc;
-  const size_t n_thr = (size_t)n_img * wp.levels * 3;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_sig = 2 * o_dst, o_thr = o_sig + sizeof(double) * (size_t)n_img,
-               o_ms = o_thr + sizeof(double) * n_thr, tab_bytes = o_ms + sizeof(double) * n_thr;
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.assign(tab_bytes, 0);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  void** h_dst = (void**)(h + o_dst);
-  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
-  for (int k = 0; k < plan.n_chunks; ++k)
-    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
-      const int g = stage_first(plan, k) + i;
-      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
-      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
-    }
-  if (sp.thresholds) memcpy(h + o_thr, sp.thresholds, sizeof(double) * n_thr);
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
-  double* d_sigma = (double*)(c->raw_tab + o_sig);
-  double* d_thr = (double*)(c->raw_tab + o_thr);
-  double* d_ms = (double*)(c->raw_tab + o_ms);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
-    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
-    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_wavelet(c->stream, pix, d_src, d_dst, first, cnt, wp, sp, c->wv_ws, d_sigma, d_thr, d_ms);
-    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
-    for (int i = 0; i < cnt && spec->coeffs_out && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(spec->coeffs_out + (size_t)(first + i) * wp.frame_doubles, c->wv_ws + (size_t)i * wp.frame_doubles * sizeof(double),
-                         wp.frame_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  const size_t n_thr = (size_t)n_img * wp.levels * 3, frame_bytes = wp.frame_doubles * sizeof(double);
+  PreStage st;
+  st.out_dev_bit = GPET_WV_OUT_ON_DEVICE;
+  st.extras_bytes = sizeof(double) * ((size_t)n_img + 2 * n_thr);
+  if (sp.thresholds) {
+    st.init = sp.thresholds;
+    st.init_off = sizeof(double) * (size_t)n_img;
+    st.init_bytes = sizeof(double) * n_thr;
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(h + o_sig, c->raw_tab + o_sig, tab_bytes - o_sig, hipMemcpyDeviceToHost, c->stream);
-  // (host memory of the caller and the context's own table are in flight, also after an error)
-  const hipError_t ew = gpet_wait(c->stream);
-  HIPCHK(c, e);
-  HIPCHK(c, ew);
-  const double* h_sigma = (const double*)(h + o_sig);
+  st.ws_bytes = dn_align(frame_bytes);
+  st.read_back = true;
+  const int rc = pre_stage(
+      c, raw, out, n_img, pix, M, N, flags, st, [&](size_t staged) { return wv_chunks(n_img, staged, wp.frame_doubles); },
+      [&](const PreChunk& k) {
+        double* d_sigma = (double*)k.d_extras;
+        return launch_wavelet(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, wp, sp, k.ws, d_sigma, d_sigma + n_img, d_sigma + n_img + n_thr);
+      },
+      [&](const PreChunk& k) {  // (the chunk's pyramids, by the frame's number in the stack)
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < k.cnt && spec->coeffs_out && e == hipSuccess; ++i)
+          e = hipMemcpyAsync(spec->coeffs_out + (size_t)(k.first + i) * wp.frame_doubles, k.ws + (size_t)i * frame_bytes, frame_bytes,
+                             hipMemcpyDeviceToHost, c->stream);
+        return e;
+      });
+  if (rc) return rc;
+  const double *h_sigma = (const double*)st.h_extras, *h_thr = h_sigma + n_img, *h_ms = h_thr + n_thr;
   if (spec->sigma_out) memcpy(spec->sigma_out, h_sigma, sizeof(double) * (size_t)n_img);
-  if (spec->thresholds_out) memcpy(spec->thresholds_out, h + o_thr, sizeof(double) * n_thr);
-  if (spec->mean_sq_out) memcpy(spec->mean_sq_out, h + o_ms, sizeof(double) * n_thr);
+  if (spec->thresholds_out) memcpy(spec->thresholds_out, h_thr, sizeof(double) * n_thr);
+  if (spec->mean_sq_out) memcpy(spec->mean_sq_out, h_ms, sizeof(double) * n_thr);
   for (int g = 0; g < n_img; ++g)
     if (!(h_sigma[g] > 0.0 && h_sigma[g] < INFINITY))
       return fail(c, GPET_ERR_BAD_ARG, !(sp.sigma != sp.sigma)
@@ -436,10 +456,9 @@ int gpet_wavelet_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
   return GPET_OK;
 }
 
-// Split-Bregman TV denoising (gpet_tvb_plan.h).  One device block: source pointers | destination pointers | states [n_img].  Frames
-// go chunk by chunk (tvb_chunks): host frames and host outputs through the staging slot, the skewed arrays through the context's
-// workspace; per chunk one prologue, tvb_launches(max_iter) sweep launches and one epilogue, enqueued without waiting.  The sweep
-// counts come back in one copy at the end, only when the caller asks for them.
+// Split-Bregman TV denoising (gpet_tvb_plan.h).  Extras: states [n_img].  Frames go chunk by chunk (tvb_chunks), the skewed arrays
+// through the context's workspace; per chunk one prologue, tvb_launches(max_iter) sweep launches and one epilogue, enqueued without
+// waiting.  The sweep counts come back at the end, only when the caller asks for them.
 int gpet_tvb_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_tvb* spec, unsigned int flags,
                     void* const* out, int32_t* n_iter_out) {
   if (!c || !raw || !spec || !out || n_img <= 0)
@@ -454,56 +473,22 @@ int gpet_tvb_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int
     return fail(c, GPET_ERR_BAD_ARG, "tvb: %s (weight %g, eps %g, max_iter %d, frames %d x %d)", why, sp.weight, sp.eps, sp.max_iter, M, N);
   for (int g = 0; g < n_img; ++g)
     if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_tvb_images: frame or output %d is a null pointer", g);
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & GPET_TVB_OUT_ON_DEVICE) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
-  const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
-  const size_t ws_bytes = tvb_frame_bytes(M, N);
-  const StagePlan plan = tvb_chunks(n_img, st_in + st_out, M, N);
-  int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
+  PreStage st;
+  st.out_dev_bit = GPET_TVB_OUT_ON_DEVICE;
+  st.extras_bytes = sizeof(TvbState) * (size_t)n_img;
+  st.ws_bytes = tvb_frame_bytes(M, N);
+  st.read_back = n_iter_out != nullptr;
+  const int rc = pre_stage(
+      c, raw, out, n_img, pix, M, N, flags, st, [&](size_t staged) { return tvb_chunks(n_img, staged, M, N); },
+      [&](const PreChunk& k) { return launch_tvb(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, sp, k.ws, (TvbState*)k.d_extras); },
+      no_chunk_hook);
   if (rc) return rc;
-  rc = ctx_grow(c, &c->tvb_ws, &c->tvb_ws_bytes, (size_t)plan.per_chunk * ws_bytes);
-  if (rc) return rc;
-  const size_t o_dst = sizeof(void*) * (size_t)n_img, o_state = 2 * o_dst, tab_bytes = o_state + sizeof(TvbState) * (size_t)n_img;
-  rc = ctx_grow(c, &c->raw_tab, &c->raw_tab_bytes, tab_bytes);
-  if (rc) return rc;
-  c->h_raw_tab.assign(tab_bytes, 0);
-  char* h = c->h_raw_tab.data();
-  const void** h_src = (const void**)h;
-  void** h_dst = (void**)(h + o_dst);
-  // (a chunk's slot: its frames at i * st_in, then its results at per_chunk * st_in + i * st_out)
-  for (int k = 0; k < plan.n_chunks; ++k)
-    for (int i = 0; i < stage_count(plan, k, n_img); ++i) {
-      const int g = stage_first(plan, k) + i;
-      h_src[g] = in_dev ? raw[g] : c->raw_dev + (size_t)i * st_in;
-      h_dst[g] = out_dev ? out[g] : c->raw_dev + (size_t)plan.per_chunk * st_in + (size_t)i * st_out;
-    }
-  HIPCHK(c, hipMemcpyAsync(c->raw_tab, h, tab_bytes, hipMemcpyHostToDevice, c->stream));
-  const void* const* d_src = (const void* const*)c->raw_tab;
-  double* const* d_dst = (double* const*)(c->raw_tab + o_dst);
-  TvbState* d_state = (TvbState*)(c->raw_tab + o_state);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < plan.n_chunks && e == hipSuccess; ++k) {
-    const int first = stage_first(plan, k), cnt = stage_count(plan, k, n_img);
-    for (int i = 0; i < cnt && !in_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync((void*)h_src[first + i], raw[first + i], img_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_tvb(c->stream, pix, d_src, d_dst, first, cnt, M, N, sp, c->tvb_ws, d_state);
-    for (int i = 0; i < cnt && !out_dev && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(out[first + i], h_dst[first + i], out_bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess && n_iter_out) e = hipMemcpyAsync(h + o_state, c->raw_tab + o_state, tab_bytes - o_state, hipMemcpyDeviceToHost, c->stream);
-  // host memory of the caller is in flight (also after an error: frames already enqueued must not be read after the return)
-  if (!in_dev || !out_dev || n_iter_out || e != hipSuccess) {
-    const hipError_t ew = gpet_wait(c->stream);
-    HIPCHK(c, e);
-    HIPCHK(c, ew);
-  }
-  HIPCHK(c, e);
   if (n_iter_out) {
-    const TvbState* hs = (const TvbState*)(h + o_state);
+    const TvbState* hs = (const TvbState*)st.h_extras;
     for (int g = 0; g < n_img; ++g) n_iter_out[g] = hs[g].n_iter;
   }
   return GPET_OK;
 }
 
 }  // extern "C"
+

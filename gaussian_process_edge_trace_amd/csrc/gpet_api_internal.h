@@ -63,12 +63,12 @@ struct gpet_ctx {
   char *raw_dev = nullptr, *raw_tab = nullptr;
   size_t raw_dev_bytes = 0, raw_tab_bytes = 0;
   std::vector<char> h_raw_tab;
-  // wavelet stage (gpet_wavelet_images): the coefficient pyramids of a chunk's frames (gpet_wavelet_plan.h); grown on demand
-  char* wv_ws = nullptr;
-  size_t wv_ws_bytes = 0;
-  // split-Bregman stage (gpet_tvb_images): the skewed arrays of a chunk's frames (gpet_tvb_plan.h); grown on demand
-  char* tvb_ws = nullptr;
-  size_t tvb_ws_bytes = 0;
+  // the stages in front of the raw-frame path (pre_stage): the workspace of a chunk's frames -- the wavelet stage's coefficient
+  // pyramids (gpet_wavelet_plan.h), the split-Bregman stage's skewed arrays (gpet_tvb_plan.h).  ONE block for all stages, as large
+  // as the largest chunk so far: the stages share the context's one stream, and the stream is waited for before the block is
+  // replaced, so a stage finds no other stage's work in it; grown on demand
+  char* pre_ws = nullptr;
+  size_t pre_ws_bytes = 0;
   std::string err;
 };
 

@@ -60,6 +60,17 @@ inline StagePlan stage_plan(int n_img, size_t img_bytes, size_t budget = STAGE_S
   p.slot_bytes = ((size_t)p.per_chunk * img_bytes + 255) & ~(size_t)255;
   return p;
 }
+// the chunks of a stage whose frames keep a workspace each (wavelet, split-Bregman): staging and workspace of a chunk together stay
+// inside the budget, and a chunk is one launch along gridDim.z
+constexpr int STAGE_GRID_Z_MAX = 65535;
+inline StagePlan stage_plan_z(int n_img, size_t bytes_per_img, size_t budget) {
+  StagePlan p = stage_plan(n_img, bytes_per_img, budget);
+  if (p.per_chunk > STAGE_GRID_Z_MAX) {
+    p.per_chunk = STAGE_GRID_Z_MAX;
+    p.n_chunks = (n_img + p.per_chunk - 1) / p.per_chunk;
+  }
+  return p;
+}
 inline int stage_slot(const StagePlan& p, int k) { return k % p.slots; }
 inline int stage_first(const StagePlan& p, int k) { return k * p.per_chunk; }                                // first image of chunk k
 inline int stage_count(const StagePlan& p, int k, int n_img) {                                               // images of chunk k

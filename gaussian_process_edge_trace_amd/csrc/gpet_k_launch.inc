@@ -29,6 +29,33 @@ hipError_t launch_normalise(hipStream_t st, const float* d_in, size_t count, con
   return hipGetLastError();
 }
 
+// ---- what every launcher over raw frames shares ----
+// f(PixTag<T>{}) with the pixel type of a code of gpet_conv_plan.h (any other code: double), and what f returns
+template <typename T>
+struct PixTag {
+  using type = T;
+};
+template <typename F>
+static auto for_pix(int pix, F&& f) {
+  switch (pix) {
+    case PIX_U8: return f(PixTag<uint8_t>{});
+    case PIX_U16: return f(PixTag<uint16_t>{});
+    case PIX_F32: return f(PixTag<float>{});
+    default: return f(PixTag<double>{});
+  }
+}
+// what the unit of an integer pixel type is worth in [0, 1] (1 for the floating types)
+static double pix_unit(int pix) { return pix == PIX_U8 ? 1.0 / 255.0 : pix == PIX_U16 ? 1.0 / 65535.0 : 1.0; }
+// a grid holds 65 535 images along z: f(offset, count) for n images in pieces of at most that, up to the first that fails
+template <typename F>
+static hipError_t for_grid_z(int n, F&& f) {
+  for (int i = 0; i < n; i += 65535) {
+    const hipError_t e = f(i, n - i < 65535 ? n - i : 65535);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // raw frames of a stack -> unnormalised f32 gradient images: images img0 .. img0 + n - 1 of the device pointer tables d_src /
 // d_dst in ONE launch (geometry: gpet_conv_plan.h); d_minmax holds a (min, max) slot per image of the stack
 static_assert(CONV_RY == CONV_TILE_Y && CONV_TILE_X == 64, "k_conv_relu_batch tiles as gpet_conv_plan.h says");
@@ -40,23 +67,14 @@ static hipError_t launch_conv_batch_t(hipStream_t st, const void* const* d_src, 
                      M, N, d_wf, kh, kw, conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
   return hipGetLastError();
 }
-// (a grid holds 65 535 images along z or y: a longer stack takes more than one launch)
 hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
                              int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (!conv_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    hipError_t e = hipSuccess;
-    switch (pix) {
-      case PIX_U8: e = launch_conv_batch_t<uint8_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      case PIX_U16: e = launch_conv_batch_t<uint16_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      case PIX_F32: e = launch_conv_batch_t<float>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      default: e = launch_conv_batch_t<double>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-    }
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_grid_z(n, [&](int i, int m) { return launch_conv_batch_t<T>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); });
+  });
 }
 // frames frame0 .. frame0 + n - 1 of d_src -> the unnormalised f32 gradient images of all their slots in ONE launch: the device
 // tables of gpet_conv_multi_plan.h (taps of all kernels, kernel descriptors, slots of each frame, kernel of each slot), d_dst and
@@ -76,18 +94,12 @@ hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, 
                              const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (u.taps == 0 || conv_union_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    hipError_t e = hipSuccess;
-    switch (pix) {
-      case PIX_U8: e = launch_conv_multi_t<uint8_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      case PIX_U16: e = launch_conv_multi_t<uint16_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      case PIX_F32: e = launch_conv_multi_t<float>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      default: e = launch_conv_multi_t<double>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-    }
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_grid_z(n, [&](int i, int m) {
+      return launch_conv_multi_t<T>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax);
+    });
+  });
 }
 // the n images of d_imgs normalised in place, each by its own slot of d_minmax, in one launch
 hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax) {
@@ -115,18 +127,10 @@ hipError_t launch_conv_batch_tr(hipStream_t st, int pix, const void* const* d_sr
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (!conv_t_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
   if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;  // (a frame of more than 4 M rows)
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    hipError_t e = hipSuccess;
-    switch (pix) {
-      case PIX_U8: e = launch_conv_batch_tr_t<uint8_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      case PIX_U16: e = launch_conv_batch_tr_t<uint16_t>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      case PIX_F32: e = launch_conv_batch_tr_t<float>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-      default: e = launch_conv_batch_tr_t<double>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); break;
-    }
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_grid_z(n, [&](int i, int m) { return launch_conv_batch_tr_t<T>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); });
+  });
 }
 template <typename T>
 static hipError_t launch_conv_multi_tr_t(hipStream_t st, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
@@ -144,18 +148,12 @@ hipError_t launch_conv_multi_tr(hipStream_t st, int pix, const void* const* d_sr
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (u.taps == 0 || conv_union_t_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
   if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    hipError_t e = hipSuccess;
-    switch (pix) {
-      case PIX_U8: e = launch_conv_multi_tr_t<uint8_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      case PIX_U16: e = launch_conv_multi_tr_t<uint16_t>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      case PIX_F32: e = launch_conv_multi_tr_t<float>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-      default: e = launch_conv_multi_tr_t<double>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax); break;
-    }
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_grid_z(n, [&](int i, int m) {
+      return launch_conv_multi_tr_t<T>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax);
+    });
+  });
 }
 // an M x N f32 image -> the N x M one at d_out (d_out != d_in); d_minmax != nullptr: launch_normalise's arithmetic on the way
 hipError_t launch_transpose(hipStream_t st, const float* d_in, int M, int N, const unsigned int* d_minmax, float* d_out) {
@@ -187,21 +185,17 @@ static void launch_dn_rank_t(hipStream_t st, const void* const* d_src, int img0,
   else
     hipLaunchKernelGGL((k_dn_rank<T, 0, 0>), gs, bs, lds, st, src, img0, ws, L.img_bytes, L.off_out, M, N, s.size_y, s.size_x, rank, s.mode);
 }
-// (a grid holds 65 535 images along z: a longer chunk takes more than one launch)
 hipError_t launch_dn_rank(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const DenoiseSpec& s,
                           char* ws, const DenoiseLayout& L) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (dn_check(s, pix) || (s.technique != DN_MEDIAN && s.technique != DN_MINIMUM) || n < 1) return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    char* w = ws + (size_t)i * L.img_bytes;
-    switch (pix) {
-      case PIX_U8: launch_dn_rank_t<uint8_t>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
-      case PIX_U16: launch_dn_rank_t<uint16_t>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
-      case PIX_F32: launch_dn_rank_t<float>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
-      default: launch_dn_rank_t<double>(st, d_src, img0 + i, m, M, N, s, w, L, pix); break;
-    }
-  }
+  for_pix(pix, [&](auto t) {  // (here and in the stages below every piece is enqueued; the error is read after the last)
+    using T = typename decltype(t)::type;
+    (void)for_grid_z(n, [&](int i, int m) {
+      launch_dn_rank_t<T>(st, d_src, img0 + i, m, M, N, s, ws + (size_t)i * L.img_bytes, L, pix);
+      return hipSuccess;
+    });
+  });
   return hipGetLastError();
 }
 // ---- a0: non-local means (gpet_k_nlmeans.inc; geometry: gpet_nlmeans_plan.h) ----
@@ -224,15 +218,13 @@ hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, dou
   if (!pix_bytes(pix) || n < 1 || s < 3 || s % 2 == 0 || s > NLM_PATCH_MAX || d < 0 || d > NLM_DIST_MAX || s / 2 >= (M < N ? M : N) ||
       nlm_lds_bytes(s, d) > NLM_LDS_MAX || g.gy > 65535)
     return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    switch (pix) {
-      case PIX_U8: launch_nlmeans_t<uint8_t>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
-      case PIX_U16: launch_nlmeans_t<uint16_t>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
-      case PIX_F32: launch_nlmeans_t<float>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
-      default: launch_nlmeans_t<double>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2); break;
-    }
-  }
+  for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    (void)for_grid_z(n, [&](int i, int m) {
+      launch_nlmeans_t<T>(st, d_src, d_dst, img0 + i, m, M, N, s, d, d_taps, var2);
+      return hipSuccess;
+    });
+  });
   return hipGetLastError();
 }
 // ---- a0: wavelet denoising (gpet_k_wavelet.inc; geometry: gpet_wavelet_plan.h) ----
@@ -254,12 +246,7 @@ hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, dou
     if (wv_fwd_grid(p.lv[l]).gy > 65535 || wv_inv_grid(p.lv[l]).gy > 65535 || p.lv[l].m < p.F - 1 || p.lv[l].n < p.F - 1) return hipErrorInvalidValue;
   const WvFilters flt = wv_filters(sp.dec_lo, p.F);
   const bool integer = pix == PIX_U8 || pix == PIX_U16, given = !(sp.sigma != sp.sigma);
-  switch (pix) {
-    case PIX_U8: launch_wv_fwd1_t<uint8_t>(st, d_src, img0, n, ws, p, 1.0 / 255.0, flt); break;
-    case PIX_U16: launch_wv_fwd1_t<uint16_t>(st, d_src, img0, n, ws, p, 1.0 / 65535.0, flt); break;
-    case PIX_F32: launch_wv_fwd1_t<float>(st, d_src, img0, n, ws, p, 1.0, flt); break;
-    default: launch_wv_fwd1_t<double>(st, d_src, img0, n, ws, p, 1.0, flt); break;
-  }
+  for_pix(pix, [&](auto t) { launch_wv_fwd1_t<typename decltype(t)::type>(st, d_src, img0, n, ws, p, pix_unit(pix), flt); });
   for (int l = 1; l < p.levels; ++l) {
     const WvLevel& v = p.lv[l];
     const WvGrid g = wv_fwd_grid(v);
@@ -293,12 +280,7 @@ hipError_t launch_tvb(hipStream_t st, int pix, const void* const* d_src, double*
                       const TvbSpec& sp, char* ws, TvbState* d_state) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (n < 1 || n > TVB_CHUNK_MAX || tvb_check(sp, pix, M, N, n) || tvb_lds_bytes(M, N) > TVB_LDS_MAX) return hipErrorInvalidValue;
-  switch (pix) {
-    case PIX_U8: launch_tvb_unpack_t<uint8_t>(st, d_src, img0, n, M, N, ws, 1.0 / 255.0); break;
-    case PIX_U16: launch_tvb_unpack_t<uint16_t>(st, d_src, img0, n, M, N, ws, 1.0 / 65535.0); break;
-    case PIX_F32: launch_tvb_unpack_t<float>(st, d_src, img0, n, M, N, ws, 1.0); break;
-    default: launch_tvb_unpack_t<double>(st, d_src, img0, n, M, N, ws, 1.0); break;
-  }
+  for_pix(pix, [&](auto t) { launch_tvb_unpack_t<typename decltype(t)::type>(st, d_src, img0, n, M, N, ws, pix_unit(pix)); });
   const size_t stride = tvb_frame_bytes(M, N) / sizeof(double);
   const double lam = 2.0 * sp.weight, norm = sp.weight + 4.0 * lam, inv_lam = 1.0 / lam;
   static_assert(TVB_CELLS_MAX == 2, "one instance of the sweep kernel per number of cells a lane can own");
@@ -325,16 +307,13 @@ hipError_t launch_dn_gauss(hipStream_t st, int pix, const void* const* d_src, in
                            const double* d_wy, const double* d_wx, char* ws, const DenoiseLayout& L) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (dn_check(s, pix) || s.technique != DN_GAUSSIAN || n < 1 || cdiv(M, 4) > 65535) return hipErrorInvalidValue;
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    char* w = ws + (size_t)i * L.img_bytes;
-    switch (pix) {
-      case PIX_U8: launch_dn_gauss_t<uint8_t>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
-      case PIX_U16: launch_dn_gauss_t<uint16_t>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
-      case PIX_F32: launch_dn_gauss_t<float>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
-      default: launch_dn_gauss_t<double>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, w, L); break;
-    }
-  }
+  for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    (void)for_grid_z(n, [&](int i, int m) {
+      launch_dn_gauss_t<T>(st, d_src, img0 + i, m, M, N, s, d_wy, d_wx, ws + (size_t)i * L.img_bytes, L);
+      return hipSuccess;
+    });
+  });
   return hipGetLastError();
 }
 template <typename T>
@@ -349,16 +328,13 @@ hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src,
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (dn_check(s, pix) || s.technique != DN_TVC || n < 1 || it < 0) return hipErrorInvalidValue;
   const double tau_w = 0.25 / s.weight;  // (the reference's `tau / weight`, formed once)
-  for (int i = 0; i < n; i += 65535) {
-    const int m = n - i < 65535 ? n - i : 65535;
-    char* w = ws + (size_t)i * L.img_bytes;
-    switch (pix) {
-      case PIX_U8: launch_dn_tvc_t<uint8_t>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
-      case PIX_U16: launch_dn_tvc_t<uint16_t>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
-      case PIX_F32: launch_dn_tvc_t<float>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
-      default: launch_dn_tvc_t<double>(st, d_src, img0 + i, m, M, N, it, tau_w, w, L); break;
-    }
-  }
+  for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    (void)for_grid_z(n, [&](int i, int m) {
+      launch_dn_tvc_t<T>(st, d_src, img0 + i, m, M, N, it, tau_w, ws + (size_t)i * L.img_bytes, L);
+      return hipSuccess;
+    });
+  });
   hipLaunchKernelGGL(k_dn_tvc_check, dim3(n), dim3(256), 0, st, ws, L.img_bytes, L.off_part, L.n_wg, img0, it, s.weight, s.eps,
                      (double)((size_t)M * N), d_n_iter, d_n_done);
   return hipGetLastError();

@@ -100,14 +100,9 @@ constexpr int TVB_CELLS_MAX = (TVB_DIAG_MAX + TVB_THREADS - 1) / TVB_THREADS;   
 // ---- chunks -----------------------------------------------------------------------------------------------------------------------
 // frames of a chunk: a chunk's staging (host frames, host results) and its workspace together stay inside the budget
 constexpr size_t TVB_CHUNK_BUDGET = (size_t)256 << 20;
-constexpr int TVB_CHUNK_MAX = 65535;  // gridDim.z
+constexpr int TVB_CHUNK_MAX = STAGE_GRID_Z_MAX;  // gridDim.z
 inline StagePlan tvb_chunks(int n_img, size_t staged_bytes_per_img, int M, int N) {
-  StagePlan p = stage_plan(n_img, staged_bytes_per_img + tvb_frame_bytes(M, N), TVB_CHUNK_BUDGET);
-  if (p.per_chunk > TVB_CHUNK_MAX) {
-    p.per_chunk = TVB_CHUNK_MAX;
-    p.n_chunks = (n_img + p.per_chunk - 1) / p.per_chunk;
-  }
-  return p;
+  return stage_plan_z(n_img, staged_bytes_per_img + tvb_frame_bytes(M, N), TVB_CHUNK_BUDGET);
 }
 inline int tvb_launches(int max_iter) { return (max_iter + TVB_SWEEPS_PER_LAUNCH - 1) / TVB_SWEEPS_PER_LAUNCH; }
 

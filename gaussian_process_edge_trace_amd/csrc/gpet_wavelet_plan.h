@@ -149,14 +149,9 @@ inline WvGrid wv_inv_grid(const WvLevel& v) {
 }
 // images of a chunk: a chunk's staging (host frames, host results) and its workspace together stay inside the budget
 constexpr size_t WV_CHUNK_BUDGET = (size_t)256 << 20;
-constexpr int WV_CHUNK_MAX = 65535;  // gridDim.z
+constexpr int WV_CHUNK_MAX = STAGE_GRID_Z_MAX;  // gridDim.z
 inline StagePlan wv_chunks(int n_img, size_t staged_bytes_per_img, size_t frame_doubles) {
-  StagePlan p = stage_plan(n_img, staged_bytes_per_img + ((frame_doubles * sizeof(double) + 255) & ~(size_t)255), WV_CHUNK_BUDGET);
-  if (p.per_chunk > WV_CHUNK_MAX) {
-    p.per_chunk = WV_CHUNK_MAX;
-    p.n_chunks = (n_img + p.per_chunk - 1) / p.per_chunk;
-  }
-  return p;
+  return stage_plan_z(n_img, staged_bytes_per_img + ((frame_doubles * sizeof(double) + 255) & ~(size_t)255), WV_CHUNK_BUDGET);
 }
 
 // ---- the summation order of a BayesShrink threshold ---------------------------------------------------------------------------------

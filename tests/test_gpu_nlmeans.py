@@ -110,6 +110,22 @@ def test_three_frames_in_one_call(amd, ctx, device_in, device_out):
     assert not np.array_equal(singles[0], singles[1]) and not np.array_equal(singles[0], singles[2])
 
 
+def test_a_stack_of_two_chunks_with_a_short_last_one(amd, ctx):
+    """Host in, host out: a float64 frame of 1024 x 1024 stages 8388608 bytes and its result as many, so 4 frames fill the 64 MiB
+    of a chunk and 5 frames are 4 + 1 (tests/test_raw_frames_host.py asserts the split).  The first frame of the first chunk, its
+    last frame and the one frame of the last chunk differ; every frame's result is that of its one-frame call, bit for bit.
+    (Frames and results on the device take one launch and no chunk.)"""
+    a = np.random.RandomState(3).rand(1024, 1024)
+    frames = dict(a=a, b=a[::-1].copy(), c=np.ascontiguousarray(a[:, ::-1]), filler=np.ascontiguousarray(a.T))
+    kw = dict(patch_size=3, patch_distance=1, h=0.1, sigma=0.0)
+    singles = {k: run(amd, ctx, [f], kw)[0] for k, f in frames.items()}
+    assert not np.array_equal(singles["a"], singles["b"]) and not np.array_equal(singles["a"], singles["c"])
+    names = ["a", "filler", "filler", "b", "c"]
+    out = run(amd, ctx, [frames[k] for k in names], kw)
+    for g, k in enumerate(names):
+        assert np.array_equal(out[g], singles[k]), (g, k)
+
+
 def test_u8_device_frames_into_device_memory(amd, ctx):
     img = FIX["in_u8_b"]
     out = run(amd, ctx, [img, img], dict(patch_size=7, patch_distance=11, h=25.0, sigma=12.5), taps=FIX["taps_s7_h25.0"], device_in=True, device_out=True)

@@ -147,6 +147,40 @@ def test_u8_device_frames_into_device_memory_without_a_wait(amd, ctx):
         buf.close()
 
 
+# ---- more than one chunk -----------------------------------------------------------------------------------------------------------
+CHUNK_KW = dict(weight=5, max_iter=3, eps=1e-3)
+
+
+@pytest.fixture(scope="module")
+def chunk_singles(amd, ctx):
+    """Four float64 frames of 500 x 500 with their one-frame results, computed once: a flat frame (no change in its first sweep:
+    one sweep), a smooth one (rmse 1.4e-3, 8.6e-4: two), a noisy one and the filler between them (rmse above 1e-2 throughout: all
+    three) -- every rmse is far from eps = 1e-3."""
+    M = N = 500
+    rs = np.random.RandomState(5)
+    yy, xx = np.mgrid[0:M, 0:N]
+    smooth = 0.5 + 0.25 * np.sin(xx / 40.0) * np.cos(yy / 55.0)
+    frames = dict(flat=np.full((M, N), 0.5), smooth=smooth, noisy=np.clip(smooth + rs.normal(0.0, 0.1, (M, N)), 0.0, 1.0), filler=rs.rand(M, N))
+    singles = {k: run(amd, ctx, [f], CHUNK_KW) for k, f in frames.items()}
+    assert [int(singles[k][1][0]) for k in ("flat", "smooth", "noisy", "filler")] == [1, 2, 3, 3]
+    return frames, singles
+
+
+@pytest.mark.parametrize("device,per_chunk", [(False, 16), (True, 22)], ids=["host_in_host_out", "device_in_device_out"])
+def test_a_stack_of_two_chunks_with_a_short_last_one(amd, ctx, chunk_singles, device, per_chunk):
+    """float64 frames of 500 x 500 keep 12096256 bytes of workspace each.  Host in, host out: with 2000128 staged bytes either way
+    16 frames fill the 256 MiB of a chunk, so 17 frames are 16 + 1; device in, device out: 22 to a chunk, 23 frames are 22 + 1
+    (tests/test_tvb_plan.py asserts both splits).  The first frame of the first chunk, its last frame and the one frame of the last
+    chunk stop after 1, 2 and 3 sweeps; every frame's result and sweep count are those of its one-frame call, bit for bit."""
+    frames, singles = chunk_singles
+    names = ["flat"] + ["filler"] * (per_chunk - 2) + ["smooth", "noisy"]
+    out, n_iter = run(amd, ctx, [frames[k] for k in names], CHUNK_KW, device_in=device, device_out=device)
+    assert list(n_iter) == [int(singles[k][1][0]) for k in names]
+    assert (n_iter[0], n_iter[per_chunk - 1], n_iter[per_chunk]) == (1, 2, 3)
+    for g, k in enumerate(names):
+        assert np.array_equal(out[g], singles[k][0][0]), (g, k)
+
+
 def test_through_gpet_utils(amd, ctx):
     case = BY_NAME["u8_33x65"]
     img, want = case_input(case), FIX["exp_u8_33x65"]

@@ -69,7 +69,11 @@ def run(amd, ctx, frames, kw, thresholds=None, device_in=False, device_out=False
         else:
             M, N = frames[0].shape
             ptrs = buf.reserve(len(frames), M * N * 8)
-            assert ctx.wavelet_images(raw, out_device_ptrs=ptrs) is None
+            if report:
+                none, rep = ctx.wavelet_images(raw, out_device_ptrs=ptrs, report=True)
+                assert none is None
+            else:
+                assert ctx.wavelet_images(raw, out_device_ptrs=ptrs) is None
             out = np.empty((len(frames), M, N))
             for g, p in enumerate(ptrs):
                 ctx.check(ctx.lib.gpet_dev_copy(ctx.h, out[g].ctypes.data, L._P(p), out[g].nbytes, 1))
@@ -166,6 +170,37 @@ def test_three_frames_in_one_call(amd, ctx, device_in, device_out):
     thr[0] = FIX["thr_f64_37x50_db2"]
     mixed = run(amd, ctx, frames, kw, thresholds=thr, device_in=device_in, device_out=device_out)
     assert np.array_equal(mixed[0], FIX["exp_f64_37x50_db2"]) and np.array_equal(mixed[1], singles[1]) and np.array_equal(mixed[2], singles[2])
+
+
+CHUNK_KW = dict(wavelet="db1", wavelet_levels=1)
+
+
+@pytest.fixture(scope="module")
+def chunk_singles(amd, ctx):
+    """Four float64 frames of 1024 x 1024 with their one-frame results and reports, computed once."""
+    a = np.random.RandomState(3).rand(1024, 1024)
+    frames = dict(a=a, b=a[::-1].copy(), c=np.ascontiguousarray(a[:, ::-1]), filler=np.ascontiguousarray(a.T))
+    singles = {k: run(amd, ctx, [f], CHUNK_KW, report=True) for k, f in frames.items()}
+    assert not np.array_equal(singles["a"][0], singles["b"][0]) and not np.array_equal(singles["a"][0], singles["c"][0])
+    return frames, singles
+
+
+@pytest.mark.parametrize("device,per_chunk", [(False, 10), (True, 32)], ids=["host_in_host_out", "device_in_device_out"])
+def test_a_stack_of_two_chunks_with_a_short_last_one(amd, ctx, chunk_singles, device, per_chunk):
+    """float64 frames of 1024 x 1024 under db1, one level, keep a pyramid of 8388608 bytes each.  Host in, host out: with 8388608
+    staged bytes either way 10 frames fill the 256 MiB of a chunk, so 11 frames are 10 + 1; device in, device out: 32 to a chunk,
+    33 frames are 32 + 1 (tests/test_wavelet_plan.py asserts both splits).  The first frame of the first chunk, its last frame and
+    the one frame of the last chunk differ; every frame's result, noise level, thresholds, means of squares and coefficients --
+    indexed by the frame's number in the whole stack -- are those of its one-frame call, bit for bit."""
+    frames, singles = chunk_singles
+    names = ["a"] + ["filler"] * (per_chunk - 2) + ["b", "c"]
+    out, rep = run(amd, ctx, [frames[k] for k in names], CHUNK_KW, device_in=device, device_out=device, report=True)
+    for g, k in enumerate(names):
+        want, one = singles[k]
+        assert np.array_equal(out[g], want[0]), (g, k)
+        assert rep["sigma"][g] == one["sigma"][0], (g, k)
+        assert np.array_equal(rep["thresholds"][g], one["thresholds"][0]) and np.array_equal(rep["mean_sq"][g], one["mean_sq"][0]), (g, k)
+        assert same(rep["coeffs"][g], one["coeffs"][0]), (g, k)
 
 
 def test_u8_device_frames_into_device_memory(amd, ctx):

@@ -216,6 +216,8 @@ def test_chunk_plan_odd_cases(shim):
     assert [c[0] for c in _stage(shim, 5, 100 << 20, ring=3)["chunks"]] == [0, 1, 2, 0, 1]
     p = _stage(shim, 70, 500 * 500 * 8)  # the stack tests/test_gpu_raw_frames.py reuses the staging slot with
     assert (p["per_chunk"], p["n_chunks"], p["slots"]) == (33, 3, 1) and [c for c in p["chunks"]] == [(0, 0, 33), (0, 33, 33), (0, 66, 4)]
+    p = _stage(shim, 5, 2 * 1024 * 1024 * 8)  # the stack of tests/test_gpu_nlmeans.py: an f64 frame of 1024 x 1024 and its f64 result
+    assert (p["per_chunk"], p["n_chunks"], p["slots"]) == (4, 2, 1) and [c for c in p["chunks"]] == [(0, 0, 4), (0, 4, 1)]
     assert _stage(shim, 0, 1000)["n_chunks"] == 0
 
 

@@ -188,6 +188,11 @@ def test_workspace_bytes_lds_and_chunks(shim):
     # with a staged u8 frame (250112) and a staged f64 result (2000128): 14346496 bytes per frame -> 18 to a chunk, 15 chunks
     shim.shim_chunks(256, 250112 + 2000128, 500, 500, out)
     assert (out[0], out[1]) == (18, 15)
+    # the stacks of tests/test_gpu_tvb.py: f64 frames staged both ways, 16096512 bytes per frame -> 17 = 16 + 1; on the device 23 = 22 + 1
+    shim.shim_chunks(17, 2000128 + 2000128, 500, 500, out)
+    assert (out[0], out[1]) == (16, 2)
+    shim.shim_chunks(23, 0, 500, 500, out)
+    assert (out[0], out[1]) == (22, 2)
     shim.shim_chunks(3, 0, 9, 13, out)
     assert (out[0], out[1]) == (3, 1)
     shim.shim_chunks(200000, 0, 2, 2, out)  # (gridDim.z)

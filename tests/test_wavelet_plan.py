@@ -213,6 +213,13 @@ def test_chunks(shim):
     # with a staged u8 frame (250112) and a staged f64 result (2000128): 4918272 bytes per frame -> 54
     shim.shim_chunks(256, 250112 + 2000128, 333496, out)
     assert (out[0], out[1]) == (54, 5)
+    # the stacks of tests/test_gpu_wavelet.py: f64 frames of 1024 x 1024 under 2 taps, one level: a pyramid of four 512 x 512 bands
+    # = 8388608 bytes; staged both ways 3 x 8388608 per frame -> 11 = 10 + 1; on the device 33 = 32 + 1
+    assert plan(shim, 1024, 1024, 2, 1)[1] == 1048576
+    shim.shim_chunks(11, 8388608 + 8388608, 1048576, out)
+    assert (out[0], out[1]) == (10, 2)
+    shim.shim_chunks(33, 0, 1048576, out)
+    assert (out[0], out[1]) == (32, 2)
     shim.shim_chunks(3, 0, 2080, out)
     assert (out[0], out[1]) == (3, 1)
     shim.shim_chunks(200000, 0, 8, out)  # (gridDim.z)
