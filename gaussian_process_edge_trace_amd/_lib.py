@@ -19,7 +19,7 @@ OK, ERR_BAD_ARG, ERR_HIP, ERR_NOT_PD, ERR_ITER_CAP, ERR_RANK_CAP, ERR_UNSUPPORTE
 # gpet_buf
 (BUF_X_TRAIN, BUF_Y_TRAIN, BUF_CHOL, BUF_ALPHA, BUF_MEAN, BUF_STD, BUF_COV, BUF_FACTOR, BUF_EIGVALS, BUF_NORMALS,
  BUF_SAMPLES, BUF_COSTS, BUF_BEST_IDX, BUF_BEST_COSTS, BUF_SCALARS, BUF_OBS, BUF_KDE, BUF_GRAD_KDE, BUF_GRAD,
- BUF_NOISE_W, BUF_FIN_TRAIN, BUF_FIN_PAR, BUF_FIN_STARTS, BUF_FIN_OUT) = range(24)
+ BUF_NOISE_W, BUF_FIN_TRAIN, BUF_FIN_PAR, BUF_FIN_STARTS, BUF_FIN_OUT, BUF_KDE_TILES) = range(25)
 
 KERNEL_RBF, KERNEL_MATERN = 0, 1
 GRAD_ON_DEVICE = 1  # gpet_batch_create2 / gpet_batch_set_images flag: the gradient image pointers are device pointers
@@ -1432,7 +1432,7 @@ _DT = {BUF_X_TRAIN: np.float64, BUF_Y_TRAIN: np.float64, BUF_CHOL: np.float64, B
        BUF_EIGVALS: np.float64, BUF_NORMALS: np.float64, BUF_SAMPLES: np.float64, BUF_COSTS: np.float64,
        BUF_BEST_IDX: np.int32, BUF_BEST_COSTS: np.float64, BUF_OBS: np.int64, BUF_KDE: np.float32,
        BUF_GRAD_KDE: np.float32, BUF_GRAD: np.float32, BUF_NOISE_W: np.float64, BUF_FIN_TRAIN: np.float64,
-       BUF_FIN_PAR: np.float64, BUF_FIN_STARTS: np.float64, BUF_FIN_OUT: np.float64}
+       BUF_FIN_PAR: np.float64, BUF_FIN_STARTS: np.float64, BUF_FIN_OUT: np.float64, BUF_KDE_TILES: np.int32}
 
 
 class Batch:
@@ -1655,7 +1655,8 @@ class Batch:
                  BUF_SAMPLES: (S, Lg), BUF_COSTS: (S,), BUF_BEST_IDX: (inf["n_keep"],),
                  BUF_BEST_COSTS: (inf["n_keep"],), BUF_OBS: (s.n_obs, 2), BUF_KDE: (self.M, self.N),
                  BUF_GRAD_KDE: (self.M, self.N), BUF_GRAD: (self.M, self.N), BUF_FIN_TRAIN: (3, inf["n_cap"]),
-                 BUF_FIN_PAR: (12,), BUF_FIN_STARTS: (13, 3), BUF_FIN_OUT: (2, Lg)}[which]
+                 BUF_FIN_PAR: (12,), BUF_FIN_STARTS: (13, 3), BUF_FIN_OUT: (2, Lg),
+                 BUF_KDE_TILES: ((self.N + 15) // 16 + 1, 2)}[which]  # (the last row: the two u32 keys of the raw minimum / maximum)
         out = np.zeros(shape, dtype=_DT[which])
         if out.size:
             self.ctx.check(self.lib.gpet_batch_read(self.h, e, which, out.ctypes.data, out.nbytes))

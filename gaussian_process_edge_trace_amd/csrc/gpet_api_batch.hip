@@ -816,6 +816,14 @@ int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
       memcpy(dst, &s, bytes < sizeof s ? bytes : sizeof s);
       return GPET_OK;
     case GPET_BUF_FIN_PAR: src = E.fin_par; avail = 12 * 8; break;
+    case GPET_BUF_KDE_TILES: {
+      const size_t nt = ((size_t)E.N + KDE_TX - 1) / KDE_TX;
+      if (bytes < (nt + 1) * 8) return fail(c, GPET_ERR_BAD_ARG, "KDE_TILES read needs %zu bytes", (nt + 1) * 8);
+      HIPCHK(c, hipMemcpyAsync((char*)dst, E.kde_band, nt * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync((char*)dst + nt * 8, E.mm, 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, gpet_wait(c->stream));
+      return GPET_OK;
+    }
     case GPET_BUF_FIN_STARTS:
       if (!b->lb_starts) return fail(c, GPET_ERR_STATE, "no converged fit has run on this batch yet");
       src = b->lb_starts + (size_t)e * 39;

@@ -41,6 +41,8 @@ struct Carver {  // lays buffers out in one arena (256-byte aligned); with base 
 #define LDS_DYN_MAX (150 * 1024)
 // dynamic LDS available to k_struct_H (the structured path needs at least U + one row of L + beta in it)
 #define STRUCT_H_LDS_MAX LDS_DYN_MAX
+// curves the fused curve KDE stages per pass (k_kde_fused), and the most its register form takes (k_kde_fused_r): the capacity of kde_wt
+constexpr int KDE_NB = 128;
 
 inline int nu_to_code(double nu) {
   if (nu == 0.5) return 0;
@@ -277,6 +279,7 @@ inline BatchBlocks layout_batch_slots(Carver& cv, EdgeDev* edges, int B, const B
     E.best_idx = cv.take<int>((size_t)E.n_keep + 1);
     E.bins = cv.take<double>(gpx);
     E.tmpk = cv.take<double>(gpx);
+    E.kde_wt = gpx >= (size_t)KDE_NB ? E.tmpk : nullptr;  // (the curve KDE's weights between k_kde_prep and k_kde_fused_r: see gpet_dev.h)
     E.kde = cv.take<float>(px);
     E.kde_band = cv.take<int>(2 * ((size_t)E.N / 16 + 2));
     E.colsum = cv.take<double>((size_t)E.N);

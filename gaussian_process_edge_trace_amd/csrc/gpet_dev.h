@@ -88,6 +88,9 @@ struct EdgeDev {
   // pixel-selection workspaces (f1)
   double* bins;          // [(N+2)*(M+2)] linear-binning grid, x-major
   double* tmpk;          // [(N+2)*(M+2)] separable-convolution scratch
+  double* kde_wt;        // [KDE_NB] weights of the kept curves, ((1 / cost) / sum of 1 / cost) / W, written once per edge by kde_prep_body for the
+                         // tiles of k_kde_fused_r.  No space of its own: the first doubles of tmpk, which only the gradient KDE uses (null
+                         // where tmpk is shorter than KDE_NB, and the launcher then takes the staged form)
   float* kde;            // [M*N] normalised curve KDE (stage API); inside gpet_trace_iterate: raw density, band rows only
   int* kde_band;         // [N/16 + 1][2] first / last image row with density, per 16-column tile of the fused KDE
   double* kde_wsum;      // [1] total weight of the gradient KDE's points (sum of colsum in index order; k_kde_wsum)

@@ -25,7 +25,7 @@ constexpr int SC_PAIRS = 15;  // Simpson pairs per tile: 8 lanes x 2 pairs per c
 constexpr int SC_CURVES = 1024, SC_THREADS = 1024;
 constexpr int KDE_TX = 16;
 constexpr int KDE_H = 128;   // image rows per LDS row-chunk
-constexpr int KDE_NB = 128;  // curves staged per pass
+// (KDE_NB = 128 curves staged per pass: gpet_batch_plan.h, which sizes kde_wt by it)
 constexpr int KDE_THREADS = 512;
 constexpr int KDE_PREP_MAXB = 1024;  // kept curves k_kde_prep stages in LDS
 constexpr int PIX_CX = 32;   // columns per workgroup of k_pix_columns
@@ -141,6 +141,20 @@ inline KdeFusedPlan kde_fused_plan(const BatchDims& bd, int B) {
   return {{cdiv(bd.N, KDE_TX), B, 1},
           ((size_t)(KDE_TX + 8) * ((KDE_H + 8) | 1) + (size_t)KDE_NB * (KDE_TX + 8) + KDE_NB) * sizeof(double)};
 }
+// the register form k_kde_fused_r (option kde_variant = 1): every kept curve fits ONE staging pass, so a thread keeps its
+// KDE_NB (KDE_TX + 8) / KDE_THREADS = 6 points in registers from the loads to the binning and LDS holds only the tile and the weights:
+// 27 328 B, four workgroups of eight waves per CU (kde_fused_plan's 51 904 B: three).  Else (more curves, a grid too small to
+// lend kde_wt its KDE_NB doubles, variant 0) the staged form
+struct KdeRegPlan {
+  bool applies;
+  Grid3 grid;  // k_kde_fused_r (KDE_THREADS): as kde_fused_plan's
+  size_t lds;  // the (KDE_TX + 8) x (KDE_H + 8) tile, KDE_NB weights
+};
+inline KdeRegPlan kde_reg_plan(const BatchDims& bd, int B, int kde_variant) {
+  const bool applies = kde_variant != 0 && bd.n_keep <= KDE_NB && (size_t)(bd.M + 2) * (bd.N + 2) >= (size_t)KDE_NB;
+  return {applies, {cdiv(bd.N, KDE_TX), B, 1}, ((size_t)(KDE_TX + 8) * ((KDE_H + 8) | 1) + KDE_NB) * sizeof(double)};
+}
+static_assert(KDE_NB * (KDE_TX + 8) % KDE_THREADS == 0, "k_kde_fused_r: a whole number of points per thread");
 struct PixelPlan {
   Grid3 columns, old, argbest, select;  // k_pix_columns, k_pix_old, k_pix_argbest (256 threads each), k_pix_select (64)
 };

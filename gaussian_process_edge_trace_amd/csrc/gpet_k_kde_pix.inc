@@ -211,6 +211,10 @@ __device__ __forceinline__ void kde_prep_body(const EdgeDev& E, gpet_scalars* sc
   }
   wsum = block_sum(wsum, s_red);
   const double rem = block_sum((double)removed, s_red);
+  // the finished weights once per edge, for the tiles of k_kde_fused_r: k_kde_fused's ((1 / cost) / inv_sum) / W on the same three values
+  // (every thread holds thread 0's W: block_sum adds the waves' sums in one order)
+  if (staged && nk <= KDE_NB && E.kde_wt)
+    for (int b = tid; b < nk; b += (int)wg_threads<NT>()) E.kde_wt[b] = s_ic[b] / wsum;
   if (tid == 0) {
     E.colsum[0] = wsum;     // W
     E.colsum[1] = inv_sum;  // sum of 1/cost over the kept curves
@@ -281,9 +285,11 @@ __global__ void __launch_bounds__(1024) k_score_tail(EdgeDev* edges) {
 // (KDE_TX = 16 columns per tile, KDE_H = 128 rows per chunk, KDE_NB = 128 curves per pass, KDE_THREADS = 512: gpet_iter_plan.h)
 // One workgroup per (16-column tile, edge).  The tile's curve points are staged in LDS once; the
 // rows that can receive weight are the band [ymin-4, ymax+5] of those points, and only that band is
-// processed, in chunks of KDE_H rows through ONE (KDE_TX+8) x (KDE_H+8) f64 LDS tile (39 KB per
-// workgroup with the staging -> 4 workgroups per CU):
-//   linear binning   one (curve, column) point per thread, 64-bit fixed-point LDS atomics (order-independent
+// processed, in chunks of KDE_H rows through ONE (KDE_TX+8) x (KDE_H+8) f64 LDS tile (51 904 B per
+// workgroup with the staging, kde_fused_plan -> 3 workgroups per CU, at 76 registers as well).  This is the STAGED form: the
+// path of more than KDE_NB kept curves, and the cross-check (option kde_variant = 0) of the register form k_kde_fused_r below,
+// which the launcher takes wherever every kept curve fits one staging pass (kde_reg_plan).  The steps of a chunk:
+//   linear binning  one (curve, column) point per thread, 64-bit fixed-point LDS atomics (order-independent
 //                    sums; KDEpy itself convolves by FFT, so no summation order is "the" reference);
 //   vertical 9 taps  in place, register sliding window (halo rows saved before the barrier);
 //   horizontal 9 taps + crop + f32 cast + min/max, straight to HBM.
@@ -293,7 +299,22 @@ __global__ void __launch_bounds__(1024) k_score_tail(EdgeDev* edges) {
 //  of eight, the vertical pass on 63 lanes of every wave -- was built and is bit-identical: 0.85-0.88 against 0.89-0.90 ms
 //  per 1 024 edges on a batch alone, 15.2 against 14.6 ms per step inside the bench; binning per wave as well: 0.90-0.92.
 //  The kernel waits for its binning atomics and the gathers of the staged points, not for its barriers.  Dropped.)
-__global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int raw_band) {
+//
+// REG, the register form (k_kde_fused_r; n_keep <= KDE_NB, so the staging loop runs once): what differs from the staged form is
+// where values wait, never what is computed -- the same loads, products, fixed-point sums and 9-tap sums in the same order.
+//   points    The staging loop and the binning loop walk the same e = tid, tid + KDE_THREADS, ...: a thread bins exactly the
+//             points it loaded, at most KDE_NB (KDE_TX + 8) / KDE_THREADS = 6.  They stay in registers across the band reduction (and
+//             are binned from there again by every further chunk) instead of making the round trip through 24 576 B of LDS.
+//             LDS per workgroup: 27 328 B (kde_reg_plan) + 520 B static -> by LDS five workgroups per CU, by wave slots four.
+//   weights   read from E.kde_wt, where kde_prep_body left them once per edge (three f64 divisions per curve and tile, behind
+//             a dependent load of best_costs, in the staged form); the load goes out beside that of the sample rows.
+//   clearing  the FIRST chunk's tile is cleared while the points' loads are in flight (the band, hence the chunk's height, is
+//             not known yet: the whole tile), and the barrier of the band reduction is its barrier; every further chunk clears
+//             the rows its vertical pass reads.
+//   fixed point -> f64  by the vertical pass's own reads (the same conversion of the same bits): the pass over the tile and its
+//             barrier are gone.  Rows the vertical pass does not write keep fixed-point bits; the horizontal pass reads none of them.
+template <bool REG>
+__device__ __forceinline__ void kde_fused_body(EdgeDev* edges, int raw_band) {
   int edge, tile;  // the column tiles of an edge on one XCD: neighbours share 8 of their 24 staged columns of every curve
   xcd_edge_part((int)gridDim.x, edge, tile);
   const EdgeDev E = edges[edge];
@@ -307,8 +328,9 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
   if (x0 >= N) return;
   const int NC = KDE_TX + 8;
   const int ld = (KDE_H + 8) | 1;
-  double* s_y = s_a + NC * ld;        // [KDE_NB][NC] staged points (-1: none)
-  double* s_wt = s_y + KDE_NB * NC;   // [KDE_NB] staged weights
+  double* s_y = s_a + NC * ld;                              // [KDE_NB][NC] staged points (-1: none); REG: none
+  double* s_wt = REG ? s_a + NC * ld : s_y + KDE_NB * NC;   // [KDE_NB] staged weights
+  constexpr int PT = KDE_NB * (KDE_TX + 8) / KDE_THREADS;   // REG: points per thread
   const int tid = threadIdx.x;
   const bool band = (x0 + KDE_TX + 4 > E.x_st) && (x0 - 4 <= E.x_en);
   // (global_* instead of flat_* accesses: a FLAT instruction counts in the LDS counter as well, so every wait for an LDS
@@ -330,7 +352,13 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
     // fixed-point scale of the binning: a bin holds at most one column's weight, <= 1 / W, so
     // 2^(62 + floor(log2 W)) keeps every sum below 2^62 with an lsb of ~2^-70 (contributions are ~2^-17)
     const int kexp = 62 + ilogb(W > 0.0 ? W : 1.0);
-    const double fscale = ldexp(1.0, kexp), finv = ldexp(1.0, -kexp);
+    // (REG: the same in every lane, and told so to the compiler -- scalar registers, which the 64 vector registers of four
+    //  workgroups per CU have no room to mirror)
+    auto uni = [](double v) {
+      if constexpr (REG) return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+      else return v;
+    };
+    const double fscale = uni(ldexp(1.0, kexp)), finv = uni(ldexp(1.0, -kexp));
     // stage curves [b0, b0+nb) of this tile's columns; returns the rows they touch through (lo, hi)
     auto stage = [&](int b0, int nb, int& lo, int& hi) {
       // (the sample rows of the curves of this pass through LDS first: the loads of the points then depend on nothing
@@ -357,6 +385,13 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
       for (int e = tid; e < nb; e += KDE_THREADS) s_wt[e] = ((1.0 / bcost[b0 + e]) / inv_sum) / W;
     };
     // phase A: band of rows that receive weight
+    double yv[PT];  // REG: this thread's points e = tid + k KDE_THREADS (-1: none), from here to the last chunk's binning
+    if constexpr (REG) {
+      if (tid < E.n_keep) {  // (n_keep <= KDE_NB < KDE_THREADS; two independent loads, one round trip)
+        s_brow[tid] = bidx[tid];
+        s_wt[tid] = as_global(E.kde_wt)[tid];
+      }
+    }
     if (tid == 0) {
       s_band[0] = 0x7FFFFFFF;
       s_band[1] = -1;
@@ -364,10 +399,36 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
     __syncthreads();
     {
       int mylo = 0x7FFFFFFF, myhi = -1;
-      for (int b0 = 0; b0 < E.n_keep; b0 += KDE_NB) {
-        const int nb = (E.n_keep - b0) < KDE_NB ? (E.n_keep - b0) : KDE_NB;
-        if (b0 > 0) __syncthreads();
-        stage(b0, nb, mylo, myhi);
+      if constexpr (REG) {
+        const int npt = E.n_keep * NC;
+        auto load = [&](auto src) {  // (stage's loads, all in flight together)
+#pragma unroll
+          for (int k = 0; k < PT; ++k) {
+            const int e = tid + k * KDE_THREADS;
+            const int bb = e / NC, c = e - bb * NC;
+            const int xc = x0 + c - 4;
+            yv[k] = -1.0;
+            if (e < npt && xc >= E.x_st && xc <= E.x_en) yv[k] = (double)src[(size_t)s_brow[bb] * E.Yp + (xc - E.x_st)];
+          }
+        };
+        if (yf32) load(Yf);
+        else load(Yd);
+        for (int i = tid; i < NC * ld; i += KDE_THREADS) s_a[i] = 0.0;  // (the first chunk's tile, under the loads)
+#pragma unroll
+        for (int k = 0; k < PT; ++k) {
+          if (yv[k] < 0.0 || yv[k] > ymax) yv[k] = -1.0;  // gpet.py:498-500
+          if (yv[k] >= 0.0) {
+            const int iy = (int)floor(yv[k]);
+            mylo = min(mylo, iy);
+            myhi = max(myhi, iy + 1);
+          }
+        }
+      } else {
+        for (int b0 = 0; b0 < E.n_keep; b0 += KDE_NB) {
+          const int nb = (E.n_keep - b0) < KDE_NB ? (E.n_keep - b0) : KDE_NB;
+          if (b0 > 0) __syncthreads();
+          stage(b0, nb, mylo, myhi);
+        }
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
@@ -388,46 +449,76 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
     for (int r0 = y_lo; r0 <= y_hi; r0 += KDE_H) {
       const int nrow = (y_hi + 1 - r0) < KDE_H ? (y_hi + 1 - r0) : KDE_H;
       // LDS row l <-> padded-grid row gy = r0 - 3 + l  (image row y sits at l = y - r0 + 4)
-      for (int i = tid; i < NC * ld; i += KDE_THREADS) s_a[i] = 0.0;
-      __syncthreads();
-      for (int b0 = 0; b0 < E.n_keep; b0 += KDE_NB) {
-        const int nb = (E.n_keep - b0) < KDE_NB ? (E.n_keep - b0) : KDE_NB;
-        if (!single) {
-          int dl = 0, dh = 0;
-          __syncthreads();
-          stage(b0, nb, dl, dh);
+      // REG: the thread index of this chunk, a copy the optimiser cannot see through.  It otherwise computes every point's row, LDS
+      // addresses and fixed-point addends and the passes' addresses ahead of the chunk loop and keeps them beside the points: over
+      // 40 registers, spilled at four workgroups per CU (the points' values get the same treatment below)
+      int tc = tid;
+      if constexpr (REG) asm volatile("" : "+v"(tc));
+      unsigned long long* s_bits = reinterpret_cast<unsigned long long*>(s_a);
+      const int lmax = nrow + 8;
+      // linear binning of one (curve, column) point: 64-bit fixed-point LDS atomics, so the sums do not depend on the
+      // order the points arrive in (deterministic), at the resolution of f64 arithmetic
+      auto bin = [&](int e, double y) {
+        if (y < 0.0) return;
+        const int bb = e / NC, bc = e - bb * NC;
+        const double gy = y + 1.0;
+        const int iy = (int)floor(gy);
+        const int l = iy - (r0 - 3);
+        if (l + 1 < 0 || l >= lmax) return;
+        const double w = s_wt[bb] * fscale;
+        const double fy = gy - (double)iy;
+        unsigned long long* col = s_bits + bc * ld;
+        if (l >= 0) atomicAdd(&col[l], (unsigned long long)__double2ll_rn((1.0 - fy) * w));
+        if (l + 1 < lmax) atomicAdd(&col[l + 1], (unsigned long long)__double2ll_rn(fy * w));
+      };
+      if constexpr (REG) {
+        if (r0 != y_lo) {
+          // rows 0 .. lclr - 1: all that the vertical pass below reads (its last segment reaches lclr - 1).  A quarter of the
+          // workgroup per column, a thread per row: no division by the run-time height
+          const int lclr = min(((nrow + 7) & ~7) + 8, ld);
+          const int l = tc & 127;
+          for (int c = tc >> 7; c < NC; c += KDE_THREADS / 128) {
+            if (l < lclr) s_a[c * ld + l] = 0.0;
+            if (l + 128 < lclr) s_a[c * ld + l + 128] = 0.0;
+          }
           __syncthreads();
         }
-        // linear binning, one (curve, column) point per thread: 64-bit fixed-point LDS atomics, so the sums do
-        // not depend on the order the points arrive in (deterministic), at the resolution of f64 arithmetic
-        unsigned long long* s_bits = reinterpret_cast<unsigned long long*>(s_a);
-        const int lmax = nrow + 8;
-        for (int e = tid; e < nb * NC; e += KDE_THREADS) {
-          const double y = s_y[e];
-          if (y < 0.0) continue;
-          const int bb = e / NC, bc = e - bb * NC;
-          const double gy = y + 1.0;
-          const int iy = (int)floor(gy);
-          const int l = iy - (r0 - 3);
-          if (l + 1 < 0 || l >= lmax) continue;
-          const double w = s_wt[bb] * fscale;
-          const double fy = gy - (double)iy;
-          unsigned long long* col = s_bits + bc * ld;
-          if (l >= 0) atomicAdd(&col[l], (unsigned long long)__double2ll_rn((1.0 - fy) * w));
-          if (l + 1 < lmax) atomicAdd(&col[l + 1], (unsigned long long)__double2ll_rn(fy * w));
+#pragma unroll
+        for (int k = 0; k < PT; ++k) {
+          double y = yv[k];
+          asm volatile("" : "+v"(y));
+          bin(tc + k * KDE_THREADS, y);
         }
+        __syncthreads();
+      } else {
+        for (int i = tid; i < NC * ld; i += KDE_THREADS) s_a[i] = 0.0;
+        __syncthreads();
+        for (int b0 = 0; b0 < E.n_keep; b0 += KDE_NB) {
+          const int nb = (E.n_keep - b0) < KDE_NB ? (E.n_keep - b0) : KDE_NB;
+          if (!single) {
+            int dl = 0, dh = 0;
+            __syncthreads();
+            stage(b0, nb, dl, dh);
+            __syncthreads();
+          }
+          for (int e = tid; e < nb * NC; e += KDE_THREADS) bin(e, s_y[e]);  // (one point per thread)
+        }
+        __syncthreads();
+        for (int i = tid; i < NC * ld; i += KDE_THREADS) s_a[i] = (double)(long long)s_bits[i] * finv;
+        __syncthreads();
       }
-      __syncthreads();
-      for (int i = tid; i < NC * ld; i += KDE_THREADS)
-        s_a[i] = (double)(long long)reinterpret_cast<unsigned long long*>(s_a)[i] * finv;
-      __syncthreads();
+      // what the vertical pass reads: f64 (the staged form converted the tile), REG: fixed point, converted here
+      auto rd = [&](const double* p) {
+        if constexpr (REG) return (double)(long long)*reinterpret_cast<const unsigned long long*>(p) * finv;
+        else return *p;
+      };
       {  // vertical pass in place: filtered value of chunk row q is written to LDS row q + 4.  Thread = (column, segment of
          // EIGHT rows): the nine-row window then rotates through registers with compile-time roles (fully unrolled: one
          // LDS read, nine multiply-adds and one write per row; with run-time segment lengths the window was shifted by
          // sixteen register moves per row and all eight waves ran ~340 instructions where six now run ~110; sixteen-row segments need 88 registers: two workgroups per CU instead of three).  A last
          // segment that reaches beyond the chunk filters rows of zeros into rows nobody reads.
         constexpr int VR = 8;
-        const int seg = tid / NC, c = tid - seg * NC;
+        const int seg = tc / NC, c = tc - seg * NC;
         const int q0 = seg * VR;
         double* col = s_a + c * ld;
         double head[4], tail[4];
@@ -435,8 +526,8 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
         if (active) {
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            head[t] = col[q0 + t];
-            tail[t] = col[q0 + VR + 4 + t];
+            head[t] = rd(&col[q0 + t]);
+            tail[t] = rd(&col[q0 + VR + 4 + t]);
           }
         }
         __syncthreads();
@@ -445,7 +536,7 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
 #pragma unroll
           for (int t = 0; t < 4; ++t) wv[t] = head[t];
 #pragma unroll
-          for (int t = 4; t < VR + 4; ++t) wv[t] = col[q0 + t];  // (rows q0 + 4 .. q0 + VR + 3: this segment's own output rows)
+          for (int t = 4; t < VR + 4; ++t) wv[t] = rd(&col[q0 + t]);  // (rows q0 + 4 .. q0 + VR + 3: this segment's own output rows)
 #pragma unroll
           for (int t = 0; t < 4; ++t) wv[VR + 4 + t] = tail[t];
 #pragma unroll
@@ -460,7 +551,7 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
       if ((N & 3) == 0) {
         // horizontal pass, four adjacent lanes per image row, four output columns each: twelve LDS reads for four outputs (nine
         // per output before), one 16-byte store per lane -- 64 contiguous bytes per row as before
-        const int yl = tid >> 2, xq = tid & 3;
+        const int yl = tc >> 2, xq = tc & 3;
         const int x = x0 + 4 * xq;
         if (yl < nrow && x < N) {
           double in[12];
@@ -482,7 +573,7 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
           *reinterpret_cast<GPET_GLOBAL kde_f4*>(out + (size_t)(r0 + yl) * N + x) = (kde_f4){ov[0], ov[1], ov[2], ov[3]};
         }
       } else {
-        for (int idx = tid; idx < KDE_TX * nrow; idx += KDE_THREADS) {
+        for (int idx = tc; idx < KDE_TX * nrow; idx += KDE_THREADS) {
           const int xl = idx % KDE_TX, yl = idx / KDE_TX;
           const int x = x0 + xl;
           if (x >= N) continue;
@@ -534,6 +625,9 @@ __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int r
     atomicMax(&E.mm[1], kmax);
   }
 }
+__global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int raw_band) { kde_fused_body<false>(edges, raw_band); }
+// (four workgroups of eight waves per CU need at most 64 registers: tests/test_kde_reg_host.py reads the count from the code object)
+__global__ void __launch_bounds__(KDE_THREADS, 8) k_kde_fused_r(EdgeDev* edges, int raw_band) { kde_fused_body<true>(edges, raw_band); }
 
 // normalised curve KDE at a pixel.  raw_band: E.kde holds the raw density of the band rows only; the min-max
 // normalisation of k_kde_normalise ((v - min) / span in float32, gpet_utils.py:81-91) is applied here instead.

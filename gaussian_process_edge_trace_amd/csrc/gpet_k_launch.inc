@@ -591,9 +591,12 @@ hipError_t launch_kde(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& 
   (void)hipGetLastError();  // drop stale errors: report only these launches
   if (mode == 0) {
     // per-iteration path: one prep kernel + one fused bin/convolve kernel + normalise
+    // (the register form where every kept curve fits one staging pass, else -- and as the cross-check, option kde_variant = 0 -- the staged form)
     const KdeFusedPlan kp = kde_fused_plan(bd, B);
+    const KdeRegPlan rp = kde_reg_plan(bd, B, opt(Opt::kde_variant));
     if (parts & 1u) hipLaunchKernelGGL(k_kde_prep, dim3(1, B), dim3(1024), 0, st, d_edges);
-    if (parts & 2u) hipLaunchKernelGGL(k_kde_fused, dim3_of(kp.grid), dim3(KDE_THREADS), kp.lds, st, d_edges, raw_band);
+    if ((parts & 2u) && rp.applies) hipLaunchKernelGGL(k_kde_fused_r, dim3_of(rp.grid), dim3(KDE_THREADS), rp.lds, st, d_edges, raw_band);
+    else if (parts & 2u) hipLaunchKernelGGL(k_kde_fused, dim3_of(kp.grid), dim3(KDE_THREADS), kp.lds, st, d_edges, raw_band);
     if ((parts & 4u) && !raw_band) hipLaunchKernelGGL(k_kde_normalise, dim3(64, B), dim3(256), 0, st, d_edges, mode);
     return hipGetLastError();
   }

@@ -36,7 +36,8 @@ namespace gpet {
   X(solve_mw, 1, 0, 1, "blocked fit: alpha by one workgroup per 64-row block and direction (k_chol_solve_mw); 0: one workgroup per edge") \
   X(diag_in_syrk, 1, 0, 1, "blocked fit: the trailing update's first workgroup factors the next diagonal block; 0: a launch of its own") \
   X(topk_rank, 0, 0, 1, "1: argsort of the costs by rank counting (k_topk) also where the bitonic sort applies") \
-  X(struct_path, 1, 0, 1, "structured loop path (prior eigenbasis of the pixel grid) where it applies; 0: the generic kernels")
+  X(struct_path, 1, 0, 1, "structured loop path (prior eigenbasis of the pixel grid) where it applies; 0: the generic kernels") \
+  X(kde_variant, 1, 0, 1, "fused curve KDE of at most 128 kept curves: 1 = a tile's points stay in registers from the loads to the binning, weights once per edge, four workgroups per CU (k_kde_fused_r); 0 = points and weights staged in LDS by every tile (k_kde_fused: the cross-check, and the form of more curves)")
 
 enum class Opt : int {
 #define GPET_OPT_ENUM(name, def, lo, hi, doc) name,

@@ -97,11 +97,15 @@ typedef enum gpet_buf {
                            *                y_s, m2, s2, 0, 0, 0 */
   GPET_BUF_FIN_STARTS = 22, /* f64 [13][3]  theta0 + the 12 restart points of the last gpet_final_fit_all
                              *                (gpet.py:244-245; sklearn_gpr.py:283-288) */
-  GPET_BUF_FIN_OUT = 23   /* f64 [2][Lg]    converged fit's output block: posterior mean in pixels, then std in standardised
+  GPET_BUF_FIN_OUT = 23,  /* f64 [2][Lg]   converged fit's output block: posterior mean in pixels, then std in standardised
                            *                units (gpet.py:266), as gpet_final_fit_all left them -- what gpet_batch_results and
                            *                gpet_batch_warm_start read.  Writable (tests inject fits no scene produces): exactly
                            *                2 * Lg * 8 bytes; a write changes no state flag, so a record or a warm start after it
                            *                reads the written values where the last converged fit allowed one */
+  GPET_BUF_KDE_TILES = 24 /* i32 [ceil(N/16) + 1][2]  what the fused curve KDE left beside GPET_BUF_KDE: per 16-column tile the
+                           *                first and last image row of its band (written by the loop's form only,
+                           *                gpet_select_pixels_loop / gpet_trace_iterate; (M, -1): no band), then the ordered
+                           *                keys of the raw density's minimum and maximum as two u32.  Read only (tests) */
 } gpet_buf;
 
 /* Per-edge scalar state kept on the device (GPET_BUF_SCALARS). */
