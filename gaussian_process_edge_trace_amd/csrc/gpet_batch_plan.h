@@ -43,6 +43,13 @@ struct Carver {  // lays buffers out in one arena (256-byte aligned); with base 
 #define STRUCT_H_LDS_MAX LDS_DYN_MAX
 // curves the fused curve KDE stages per pass (k_kde_fused), and the most its register form takes (k_kde_fused_r): the capacity of kde_wt
 constexpr int KDE_NB = 128;
+// the eigen-factor stage (rules: gpet_factor_plan.h), as far as the arena is sized by it:
+constexpr int FACTOR_LDS_CAP = 96;     // largest factor capacity of the LDS-resident Jacobi path; above it the any-rank factor
+constexpr int PCH_ONE_WG_MAX = 1024;   // widest edge of that path whose pivoted Cholesky is always one workgroup's (k_pchol)
+constexpr int PCX_COLS = 32;           // columns per workgroup of the multi-workgroup pivoted Cholesky
+// doubles of pcx_cand per workgroup: two halves (current / next step) of one (value, index) pair per wave, four waves (k_pcx_step; the
+// blocked form k_pcb_block keeps one pair per workgroup and half)
+constexpr int PCX_CAND_PER_WG = 2 * 4 * 2;
 
 inline int nu_to_code(double nu) {
   if (nu == 0.5) return 0;
@@ -59,12 +66,12 @@ inline int nu_to_code(double nu) {
 
 inline bool batch_shape_ok(int B, int M, int N) { return B > 0 && M >= 2 && N >= 2; }
 
-// A capacity above 96 on ANY edge selects the whole-GPU Jacobi on the full covariance; that path is chosen per batch.
+// A capacity above FACTOR_LDS_CAP on ANY edge selects the whole-GPU Jacobi on the full covariance; that path is chosen per batch.
 inline bool any_big_edge(const gpet_params* params, int B) {
   for (int e = 0; e < B; ++e) {
     const int Lg = params[e].x_en - params[e].x_st + 1;
-    const int cap = params[e].factor_cap > 0 ? params[e].factor_cap : 96;
-    if ((cap < Lg ? cap : Lg) > 96) return true;
+    const int cap = params[e].factor_cap > 0 ? params[e].factor_cap : FACTOR_LDS_CAP;
+    if ((cap < Lg ? cap : Lg) > FACTOR_LDS_CAP) return true;
   }
   return false;
 }
@@ -97,7 +104,7 @@ inline EdgeCheck resolve_edge(EdgeDev& E, const gpet_params& p, int B, int M, in
   E.n_bins = (int)rint((double)(N - 1 - p.x_st) / (double)p.delta_x) - E.bin_lo + 2;
   E.obs_cap = p.obs_cap > E.n_bins ? p.obs_cap : E.n_bins;
   E.n_cap = E.n_init + E.obs_cap;
-  E.r_cap = p.factor_cap > 0 ? p.factor_cap : 96;  // <= 96: the LDS-resident Jacobi path
+  E.r_cap = p.factor_cap > 0 ? p.factor_cap : FACTOR_LDS_CAP;  // <= 96: the LDS-resident Jacobi path
   if (E.r_cap > Lg) E.r_cap = Lg;
   if (any_big) E.r_cap = Lg;  // (then every edge of the batch keeps all Lg directions)
   E.z_cols = p.z_cols > 0 ? p.z_cols : E.r_cap;
@@ -113,7 +120,7 @@ inline EdgeCheck resolve_edge(EdgeDev& E, const gpet_params& p, int B, int M, in
   // small batches are bound by the chain of Jacobi rounds: their rotations are logged and the eigenvectors formed by a
   // second kernel (k_jacobi_wpass); 40 sweeps x (m - 1) rounds x m / 2 pairs x 16 bytes = 2.9 MB per edge at rank 96
   // (jlog_max_b = 32: the rotation-log form pays while the chain of rounds is the time)
-  E.jlog_cap = (B <= jlog_max_b && E.r_cap <= 96) ? 40 : 0;
+  E.jlog_cap = (B <= jlog_max_b && E.r_cap <= FACTOR_LDS_CAP) ? 40 : 0;
   E.kernel_type = p.kernel_type;
   E.nu_code = p.kernel_type == GPET_KERNEL_MATERN ? nu_to_code(p.nu) : 2;
   E.nu_gen = p.nu;
@@ -261,12 +268,13 @@ inline BatchBlocks layout_batch_slots(Carver& cv, EdgeDev* edges, int B, const B
     E.rho_tab = cv.take<double>((size_t)E.N);
     E.eig = cv.take<EigState>(1);
     // (transposed copy of G: the any-rank factor, and the multi-workgroup pivoted Cholesky -- which launch_factor picks per BATCH
-    //  from the widest edge, pchol_multi_applies, and which then writes Gt of EVERY edge of the batch: the condition is the batch's)
-    E.Gt = cv.take<double>((rc > 96 || bd.Lg > 1024) ? Lg * rc : 1);
-    E.Ap = cv.take<double>(rc > 96 ? 2 * Lg * rc : 1);
+    //  from the widest edge, pchol_plan of gpet_factor_plan.h, and which then writes Gt of EVERY edge of the batch: the condition is the
+    //  batch's, and covers every width at which that plan can choose the multi-workgroup form)
+    E.Gt = cv.take<double>((rc > (size_t)FACTOR_LDS_CAP || bd.Lg > PCH_ONE_WG_MAX) ? Lg * rc : 1);
+    E.Ap = cv.take<double>(rc > (size_t)FACTOR_LDS_CAP ? 2 * Lg * rc : 1);
     E.ap_tag = cv.take<int>(3);
     E.pcx_d = cv.take<double>(Lg);
-    E.pcx_cand = cv.take<double>(16 * ((size_t)E.N / 32 + 2));  // (indexed with the widest edge of the batch)
+    E.pcx_cand = cv.take<double>(PCX_CAND_PER_WG * ((size_t)E.N / PCX_COLS + 2));  // (indexed with the widest edge of the batch)
     E.jlog = cv.take<double>(E.jlog_cap > 0 ? (size_t)E.jlog_cap * 2 * rc * (rc / 2 + 1) : 2);
     E.A = cv.take<double>((size_t)E.a_rows_cap * Lg + 64);  // (+ 64: the sample GEMM loads whole 64-column tiles of the last row)
     E.Z = cv.take<double>((size_t)E.z_ring * S * (size_t)E.z_cols);

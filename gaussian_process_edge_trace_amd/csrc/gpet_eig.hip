@@ -25,17 +25,11 @@
 namespace gpet {
 
 #define WAVE 64
-#define PCX_COLS 32
-#define OJ_B 8
-#define OJ_M 16
-#define OJ_ARGS_MAXB 8     // batches up to this size get their per-edge pointers in the kernel arguments
-#define OJ_STAGE_MAX 1024  // widest edge whose 16-row panel (16 x Lg doubles) is staged in LDS
+// (PCX_COLS, PCB_NB, OJ_B, OJ_M, OJ_ARGS_MAXB, OJ_STAGE_MAX and the panel stride oj_panel_stride: gpet_factor_plan.h)
 // a pair of blocks is left alone when its largest relative coupling is this far (squared) below the stopping tolerance:
 // 1e-4 of it, i.e. 1e-12 at the default 1e-8 -- what one more rotation would make of it is below f64 resolution anyway
 #define OJ_SKIP_REL2 1e-8
 #define OJ_PF 16  // 16-column tiles per wave whose operands are prefetched into registers (4 waves x 16 x 16 = 1024 columns)
-
-static inline int cdiv_h(int a, int b) { return (a + b - 1) / b; }
 
 typedef double v4f64e __attribute__((ext_vector_type(4)));
 
@@ -261,7 +255,6 @@ __global__ void __launch_bounds__(256) k_pcx_step(PcxArgs args, EdgeDev* edges, 
 // under the tolerance is dropped and may come back in a later block), and finishes its columns of the new rows by
 // forward substitution.  Any pivot order gives G^T G = Sigma; NumPy emulation: same Jacobi sweep count as the exact
 // greedy order, no rejected candidates on the Matern frames.
-#define PCB_NB 16
 #define PCB_CH 128
 template <bool ARGS>
 __global__ void __launch_bounds__(256) k_pcb_block(PcxArgs args, EdgeDev* edges, int blk, int nw_max, double accept_ratio) {
@@ -1037,7 +1030,7 @@ __global__ void __launch_bounds__(256) k_oj_round(OjArgs args, EdgeDev* edges, i
   OjSeat seat;  // (the inner sweep's per-lane addresses: once per kernel)
   oj_seat_init(seat, lane);
   const int nch = (Lg + 15) >> 4;  // 16-column chunks = 16-column tiles of the update below
-  const int ldx = ((Lg + 31) & ~31) + 2;
+  const int ldx = oj_panel_stride(Lg, false);
   double v[STAGED ? 16 : 1][4];
   if (STAGED) {
     // -- stage: thread t takes columns t, t + 256, ... of every row: 512 contiguous bytes per wave instruction
@@ -1288,7 +1281,7 @@ __global__ void __launch_bounds__(256) k_oj_persist(OjArgs args, EdgeDev* edges,
   // registers anyway (the 32 loads of a thread); the Gram matrix takes them through LDS one after the other, in the order of the
   // one-pass form (the same bits), and the row update does the half that is still in LDS first, then the other half again.
   const bool two_half = half_stage != 0 && Lg > 512;
-  const int ldx = half_stage ? 514 : ((Lg + 31) & ~31) + 2;
+  const int ldx = oj_panel_stride(Lg, half_stage != 0);
   const int kmax = nch * 16;
   const unsigned int nslots = (unsigned int)(nblk / 2), per_sweep = nslots * (unsigned int)(nblk - 1);
   unsigned int nbar = 0;  // (slots served by this workgroup)
@@ -1608,196 +1601,141 @@ __global__ void __launch_bounds__(256) k_oj_rows(EdgeDev* edges) {
   if (k == 0 && threadIdx.x == 0) E.ap_tag[E.sc->iter & 1] = keep ? E.sc->iter + 1 : 0;
 }
 
-// Enqueues the whole factorisation.  Nothing is read back: a fixed budget of pivot steps and sweeps is launched and
-// the kernels turn into no-ops once the device-side tests (tolerance reached / converged) have fired.
-// the warm start's launches (after the pivoted Cholesky's init kernel, before its blocks): no-ops for an edge without
-// usable previous rows
-static void launch_oj_warm(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
-  const int warm = opt(Opt::oj_warm);
-  if (!warm || bd.Lg > bd.r_cap) return;
-  const int n = bd.Lg, nt = cdiv_h(n, 64);
-  hipLaunchKernelGGL(k_ojw_begin, dim3(cdiv_h(n, 4), B), dim3(256), 0, st, d_edges, warm);
-  hipLaunchKernelGGL(k_ojw_gemm<0>, dim3(nt, nt, B), dim3(256), 0, st, d_edges, warm);
-  hipLaunchKernelGGL(k_ojw_gemm<1>, dim3(nt, nt, B), dim3(256), 0, st, d_edges, warm);
-  for (int k0 = 0; k0 < n; k0 += 64) {
+// ---- launchers: options and device facts in, the plan of gpet_factor_plan.h out, its launches ---------------------------------------
+
+// the per-edge pointers of a small batch as kernel arguments (h_edges: host copy of the edge table); zeros where they are not used
+static PcxArgs pcx_args_of(const EdgeDev* h_edges, int B, bool use_args) {
+  PcxArgs a;
+  memset(&a, 0, sizeof a);
+  for (int e = 0; use_args && e < B; ++e) {
+    const EdgeDev& h = h_edges[e];
+    a.e[e] = {h.G, h.Gt, h.pcx_d, h.pcx_cand, h.cov, h.perm, h.eig, h.sc, h.Lg, h.r_cap, h.factor_injected, 0};
+  }
+  return a;
+}
+static OjArgs oj_args_of(const EdgeDev* h_edges, int B, bool use_args) {
+  OjArgs a;
+  memset(&a, 0, sizeof a);
+  for (int e = 0; use_args && e < B; ++e) a.e[e] = {h_edges[e].G, h_edges[e].eig, h_edges[e].sc, h_edges[e].Lg, h_edges[e].r_cap, h_edges[e].factor_injected, 0};
+  return a;
+}
+
+// CUs of the current device (256, an MI355X's, only where hipDeviceGetAttribute itself fails)
+static int device_cu_count() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
+  (void)hipGetLastError();
+  return n;
+}
+
+// workgroups of k_oj_persist the current device holds at once with `lds` bytes of dynamic LDS (occupancy x CUs): asked when a device
+// meets a new LDS size (a device index beyond the table: every time)
+static int oj_persist_resident(size_t lds, int n_cus) {
+  struct Resident {
+    size_t lds;
+    int wgs;
+  };
+  static Resident known[64] = {};
+  static PerDeviceOnce attr;
+  if (attr.first()) {
+    (void)hipFuncSetAttribute((const void*)k_oj_persist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, OJ_LDS_ATTR);
+    (void)hipFuncSetAttribute((const void*)k_oj_persist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, OJ_LDS_ATTR);
+  }
+  int dev = 0;
+  Resident* slot = (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) ? &known[dev] : nullptr;
+  if (slot && slot->wgs && slot->lds == lds) return slot->wgs;
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_oj_persist<false>, 256, lds) != hipSuccess || occ < 1) occ = 1;
+  (void)hipGetLastError();
+  if (slot) *slot = {lds, occ * n_cus};
+  return occ * n_cus;
+}
+
+// The multi-workgroup pivoted Cholesky of a plan: init, blocks or steps, fin.  px: the per-edge pointers where use_args, else the edge
+// table's are read; between(): launches between the init kernel and the blocks (the any-rank path's warm start)
+template <typename F>
+static void launch_pchol_plan(hipStream_t st, EdgeDev* d_edges, int B, const PcholMultiPlan& p, bool use_args, const PcxArgs& px, F&& between) {
+  const dim3 grid(p.nw, B);
+  if (p.blocked) {
+    hipLaunchKernelGGL(k_pcb_init, grid, dim3(64), 0, st, d_edges, p.nw);
+    between();
+    for (int blk = 0; blk < p.nblocks; ++blk) {
+      if (use_args) hipLaunchKernelGGL((k_pcb_block<true>), grid, dim3(256), 0, st, px, d_edges, blk, p.nw, p.accept);
+      else hipLaunchKernelGGL((k_pcb_block<false>), grid, dim3(256), 0, st, px, d_edges, blk, p.nw, p.accept);
+    }
+    hipLaunchKernelGGL(k_pcb_fin, dim3(B), dim3(64), 0, st, d_edges, p.nw);
+  } else {
+    hipLaunchKernelGGL(k_pcx_init, grid, dim3(256), 0, st, d_edges, p.nw);
+    for (int t = 0; t < p.steps; ++t) {
+      if (use_args) hipLaunchKernelGGL((k_pcx_step<true>), grid, dim3(256), 0, st, px, d_edges, t, p.nw);
+      else hipLaunchKernelGGL((k_pcx_step<false>), grid, dim3(256), 0, st, px, d_edges, t, p.nw);
+    }
+    hipLaunchKernelGGL(k_pcx_fin, dim3(B), dim3(64), 0, st, d_edges, p.steps, p.nw);
+  }
+}
+
+bool pchol_multi_applies(const BatchDims& bd) { return pchol_plan(bd, opt(Opt::pchol_multi), false).form == PcholForm::multi; }
+hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const PcholMultiPlan& p) {
+  (void)hipGetLastError();
+  launch_pchol_plan(st, d_edges, B, p, false, pcx_args_of(nullptr, 0, false), [] {});
+  return hipGetLastError();
+}
+
+// the warm start's launches: no-ops for an edge without usable previous rows
+static void launch_oj_warm(hipStream_t st, EdgeDev* d_edges, int B, const FactorBigPlan& p, int warm) {
+  const dim3 tiles = dim3_of(p.warm_tiles);
+  hipLaunchKernelGGL(k_ojw_begin, dim3_of(p.warm_begin), dim3(256), 0, st, d_edges, warm);
+  hipLaunchKernelGGL(k_ojw_gemm<0>, tiles, dim3(256), 0, st, d_edges, warm);
+  hipLaunchKernelGGL(k_ojw_gemm<1>, tiles, dim3(256), 0, st, d_edges, warm);
+  for (int k0 = 0; k0 < p.warm_n; k0 += 64) {
     hipLaunchKernelGGL(k_ojw_chol_diag, dim3(1, B), dim3(256), 0, st, d_edges, k0, (k0 == 0 && opt(Opt::oj_warm_fail)) ? 1 : 0);
-    const int below = cdiv_h(n - k0 - 64, 64);
+    const int below = ojw_below(p.warm_n, k0);
     if (below > 0) {
       hipLaunchKernelGGL(k_ojw_chol_trsm, dim3(below, B), dim3(256), 0, st, d_edges, k0);
       hipLaunchKernelGGL(k_ojw_chol_syrk, dim3(below, below, B), dim3(256), 0, st, d_edges, k0);
     }
   }
-  hipLaunchKernelGGL(k_ojw_gemm<2>, dim3(nt, nt, B), dim3(256), 0, st, d_edges, warm);
+  hipLaunchKernelGGL(k_ojw_gemm<2>, tiles, dim3(256), 0, st, d_edges, warm);
   hipLaunchKernelGGL(k_ojw_commit, dim3(256, B), dim3(256), 0, st, d_edges);
-}
-
-// The pivoted Cholesky of a WIDE edge of low rank (BASELINE config 3: 2 048 columns, rank <= 96) over the GPU instead of
-// k_pchol's one workgroup (1.2 ms of that factor's 2.2: every pivot streams all previous rows through one CU).  The pivot
-// ORDER matters here: these factors end at the rank CAP, and the blocked candidate selection of the any-rank path, which is
-// free to take pivots out of order when every pivot will be taken anyway, leaves 1e-7 of the largest entry at rank 96 where
-// the greedy order leaves 1e-12 (measured).  Option "pchol_multi": 2 = k_pcb_block with a block ending where the next pivot
-// falls under a tenth of the block's first (the global maximum): the order stays within a constant of the greedy one;
-// 1 = one pivot per launch in the greedy order itself (k_pcx_step); 0 = k_pchol.  The rows' last bits differ from k_pchol's
-// either way, so the prior eigenbasis of the structured loop (whose bits every trace inherits) and edges of up to 1 024
-// columns stay on k_pchol.
-bool pchol_multi_applies(const BatchDims& bd) {
-  const int mode = opt(Opt::pchol_multi);
-  return bd.Lg > 1024 && bd.r_cap <= 96 && mode != 0 && (mode == 1 || cdiv_h(bd.Lg, PCX_COLS) <= 64);
-}
-hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd) {
-  (void)hipGetLastError();
-  const int nw = cdiv_h(bd.Lg, PCX_COLS);
-  const int steps = bd.r_cap < bd.Lg ? bd.r_cap : bd.Lg;
-  PcxArgs px_args;
-  memset(&px_args, 0, sizeof px_args);
-  if (opt(Opt::pchol_multi) == 1) {
-    hipLaunchKernelGGL(k_pcx_init, dim3(nw, B), dim3(256), 0, st, d_edges, nw);
-    for (int t = 0; t < steps; ++t) hipLaunchKernelGGL((k_pcx_step<false>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, t, nw);
-    hipLaunchKernelGGL(k_pcx_fin, dim3(B), dim3(64), 0, st, d_edges, steps, nw);
-  } else {
-    // (every block takes at least its first candidate: `steps` blocks always suffice; one that finds the factorisation
-    //  finished returns at once)
-    hipLaunchKernelGGL(k_pcb_init, dim3(nw, B), dim3(64), 0, st, d_edges, nw);
-    for (int blk = 0; blk < steps; ++blk)
-      hipLaunchKernelGGL((k_pcb_block<false>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, blk, nw, 0.1);
-    hipLaunchKernelGGL(k_pcb_fin, dim3(B), dim3(64), 0, st, d_edges, nw);
-  }
-  return hipGetLastError();
 }
 
 hipError_t launch_factor_big(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, const EdgeDev* h_edges) {
   (void)hipGetLastError();
-  // small batches: the per-edge pointers travel in the kernel arguments (h_edges = host copy of the edge table)
-  OjArgs oj_args;
-  memset(&oj_args, 0, sizeof oj_args);
-  const bool use_args = h_edges != nullptr && B <= OJ_ARGS_MAXB && opt(Opt::oj_args);
-  if (use_args)
-    for (int e = 0; e < B; ++e) {
-      OjEdge& d = oj_args.e[e];
-      d.G = h_edges[e].G;
-      d.st = h_edges[e].eig;
-      d.sc = h_edges[e].sc;
-      d.Lg = h_edges[e].Lg;
-      d.r_cap = h_edges[e].r_cap;
-      d.injected = h_edges[e].factor_injected;
-    }
-  const int nw = cdiv_h(bd.Lg, PCX_COLS);
-  const int steps = bd.r_cap < bd.Lg ? bd.r_cap : bd.Lg;
-  const int nblk = 2 * cdiv_h(steps, 2 * OJ_B);
-  PcxArgs px_args;
-  memset(&px_args, 0, sizeof px_args);
-  if (use_args)
-    for (int e = 0; e < B; ++e) {
-      PcxEdge& d = px_args.e[e];
-      const EdgeDev& h = h_edges[e];
-      d.G = h.G;
-      d.Gt = h.Gt;
-      d.pcx_d = h.pcx_d;
-      d.pcx_cand = h.pcx_cand;
-      d.cov = h.cov;
-      d.perm = h.perm;
-      d.eig = h.eig;
-      d.sc = h.sc;
-      d.Lg = h.Lg;
-      d.r_cap = h.r_cap;
-      d.factor_injected = h.factor_injected;
-    }
-  if (nw <= 64 && !opt(Opt::pcx_one_pivot)) {
-    // blocks of up to PCB_NB pivots; rejected candidates cost extra blocks, so the budget is generous (a block that
-    // finds the factorisation finished returns at once)
-    hipLaunchKernelGGL(k_pcb_init, dim3(nw, B), dim3(64), 0, st, d_edges, nw);
-    launch_oj_warm(st, d_edges, B, bd);
-    const int per_block = nw < PCB_NB ? nw : PCB_NB;  // (one candidate per 32-column workgroup: narrow edges offer fewer)
-    const int nblocks = 2 * cdiv_h(steps, per_block) + 8;
-    for (int blk = 0; blk < nblocks; ++blk) {
-      if (use_args) hipLaunchKernelGGL((k_pcb_block<true>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, blk, nw, 0.0);
-      else hipLaunchKernelGGL((k_pcb_block<false>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, blk, nw, 0.0);
-    }
-    hipLaunchKernelGGL(k_pcb_fin, dim3(B), dim3(64), 0, st, d_edges, nw);
-  } else {
-    hipLaunchKernelGGL(k_pcx_init, dim3(nw, B), dim3(256), 0, st, d_edges, nw);
-    for (int t = 0; t < steps; ++t) {
-      if (use_args) hipLaunchKernelGGL((k_pcx_step<true>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, t, nw);
-      else hipLaunchKernelGGL((k_pcx_step<false>), dim3(nw, B), dim3(256), 0, st, px_args, d_edges, t, nw);
-    }
-    hipLaunchKernelGGL(k_pcx_fin, dim3(B), dim3(64), 0, st, d_edges, steps, nw);
-  }
+  const FactorBigOpts o = {opt(Opt::oj_args), opt(Opt::pcx_one_pivot), opt(Opt::oj_warm), opt(Opt::oj_stage), opt(Opt::oj_half_stage), opt(Opt::oj_persist)};
   const int max_sweeps = opt(Opt::oj_max_sweeps);
-  // LDS staging costs a workgroup a whole CU (131 KB): worth it while a round's workgroups (pairs x edges) fit the
-  // chip's 256 CUs side by side (one edge: 64 pairs; measured 54 vs 61 ms per factor); a bigger batch runs two
-  // register-fed workgroups per CU instead (8 edges: 85 vs 106 ms)
-  const bool staged_lds_ok = bd.Lg <= OJ_STAGE_MAX && opt(Opt::oj_stage);
-  const bool staged = staged_lds_ok && (long long)(nblk / 2) * B <= 256;
-  const size_t stage_lds = (size_t)OJ_M * (((bd.Lg + 31) & ~31) + 2) * sizeof(double);
-  // k_oj_persist with the panel staged one 512-column half at a time (even widths above 512 columns): 66 KB instead of 131 KB,
-  // two workgroups per CU -- a batch of eight 1 024-column edges (config 5's chains) holds all its 512 pair slots at once
-  // (only where the whole panels cannot all be resident -- one workgroup per CU: a single 1 024-column edge, 64 slots, is 3-4 % slower
-  //  with the second read of the first half: 11.6 against 11.2 ms warm; eight edges, 512 slots: 20.9 against 22.6 ms -- the rounds of
-  //  a big batch are bound by what the 64 MB of panels pull from beyond the L2s, not by occupancy: profiles/r06_oj_half_stage.txt)
-  int n_cus = 256;
-  {
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess || n_cus < 1) n_cus = 256;
-    (void)hipGetLastError();
-  }
-  const int half_opt = opt(Opt::oj_half_stage);
-  const int half_stage = (bd.lg_even && bd.Lg > 512 && (half_opt > 0 || (half_opt < 0 && (long long)(nblk / 2) * B > n_cus))) ? 1 : 0;
-  const size_t persist_lds = half_stage ? (size_t)OJ_M * 514 * sizeof(double) : stage_lds;
-  if (staged) {
-    static int attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-      (void)hipFuncSetAttribute((const void*)k_oj_round<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_oj_round<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-      attr_done[dev] = 1;
-    }
-  }
   const double tol2 = pow(10.0, -2.0 * (double)opt(Opt::oj_tol_exp));
-  // staged: the rounds and sweeps in ONE launch (k_oj_persist: pair slots by ticket -- no residency requirement, so the
-  // grid is sized to what the device holds at once and a workgroup serves several slots per round when the batch has more
-  // slots than that; beyond four slots per workgroup and round the round launches' two register-fed workgroups per CU
-  // win); option "oj_persist" = 0: launches
-  static int persist_cap[64] = {};  // workgroups of k_oj_persist the device holds at once (occupancy x CUs), per device ...
-  static size_t persist_cap_lds[64] = {};  // ... for this much dynamic LDS (the occupancy is asked again when the size changes)
-  static bool persist_attr[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (staged_lds_ok && opt(Opt::oj_persist) && dev >= 0 && dev < 64 && (!persist_cap[dev] || persist_cap_lds[dev] != persist_lds)) {
-    if (!persist_attr[dev]) {
-      (void)hipFuncSetAttribute((const void*)k_oj_persist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_oj_persist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-      persist_attr[dev] = true;
+  const int n_cus = device_cu_count();
+  const OjStagePlan s = oj_stage_plan(bd, B, o, n_cus);
+  const int resident = s.lds_ok && o.oj_persist ? oj_persist_resident(s.persist_lds, n_cus) : 0;
+  const FactorBigPlan p = factor_big_plan(bd, B, h_edges != nullptr, o, s, resident);
+  const PcxArgs px = pcx_args_of(h_edges, B, p.use_args);
+  const OjArgs oj = oj_args_of(h_edges, B, p.use_args);
+  launch_pchol_plan(st, d_edges, B, p.pchol, p.use_args, px, [&] {
+    if (p.warm) launch_oj_warm(st, d_edges, B, p, o.oj_warm);
+  });
+  if (p.persist) {
+    const dim3 grid = dim3_of(p.persist_grid);
+    if (p.use_args) hipLaunchKernelGGL((k_oj_persist<true>), grid, dim3(256), s.persist_lds, st, oj, d_edges, s.nblk, max_sweeps, tol2, s.half_stage ? 1 : 0);
+    else hipLaunchKernelGGL((k_oj_persist<false>), grid, dim3(256), s.persist_lds, st, oj, d_edges, s.nblk, max_sweeps, tol2, s.half_stage ? 1 : 0);
+  } else {
+    static PerDeviceOnce attr;
+    if (s.round_staged && attr.first()) {
+      (void)hipFuncSetAttribute((const void*)k_oj_round<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, OJ_LDS_ATTR);
+      (void)hipFuncSetAttribute((const void*)k_oj_round<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, OJ_LDS_ATTR);
     }
-    int occ = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_oj_persist<false>, 256, persist_lds) != hipSuccess || occ < 1) occ = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 64;
-    persist_cap[dev] = occ * cus;
-    persist_cap_lds[dev] = persist_lds;
-    (void)hipGetLastError();
-  }
-  const int cap = (dev >= 0 && dev < 64 && persist_cap[dev] > 0) ? persist_cap[dev] : 64;
-  const long long slots_all = (long long)(nblk / 2) * B;
-  if (staged_lds_ok && opt(Opt::oj_persist) && slots_all <= 4LL * cap) {
-    int wpe = nblk / 2;  // workgroups per edge
-    if (slots_all > cap) wpe = cap / B > 0 ? cap / B : 1;
-    if (use_args) hipLaunchKernelGGL((k_oj_persist<true>), dim3(wpe, B), dim3(256), persist_lds, st, oj_args, d_edges, nblk, max_sweeps, tol2, half_stage);
-    else hipLaunchKernelGGL((k_oj_persist<false>), dim3(wpe, B), dim3(256), persist_lds, st, oj_args, d_edges, nblk, max_sweeps, tol2, half_stage);
-  } else
-  for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-    for (int round = 0; round < nblk - 1; ++round) {
-      if (staged && use_args)
-        hipLaunchKernelGGL((k_oj_round<true, true>), dim3(nblk / 2, B), dim3(256), stage_lds, st, oj_args, d_edges, round, nblk, tol2);
-      else if (staged)
-        hipLaunchKernelGGL((k_oj_round<true, false>), dim3(nblk / 2, B), dim3(256), stage_lds, st, oj_args, d_edges, round, nblk, tol2);
-      else
-        hipLaunchKernelGGL((k_oj_round<false, false>), dim3(nblk / 2, B), dim3(256), 0, st, oj_args, d_edges, round, nblk, tol2);
+    const dim3 grid = dim3_of(p.round_grid);
+    for (int sweep = 0; sweep < max_sweeps; ++sweep) {
+      for (int round = 0; round < s.nblk - 1; ++round) {
+        if (s.round_staged && p.use_args) hipLaunchKernelGGL((k_oj_round<true, true>), grid, dim3(256), s.stage_lds, st, oj, d_edges, round, s.nblk, tol2);
+        else if (s.round_staged) hipLaunchKernelGGL((k_oj_round<true, false>), grid, dim3(256), s.stage_lds, st, oj, d_edges, round, s.nblk, tol2);
+        else hipLaunchKernelGGL((k_oj_round<false, false>), grid, dim3(256), 0, st, oj, d_edges, round, s.nblk, tol2);
+      }
+      hipLaunchKernelGGL(k_oj_check, dim3(B), dim3(64), 0, st, d_edges, tol2);
     }
-    hipLaunchKernelGGL(k_oj_check, dim3(B), dim3(64), 0, st, d_edges, tol2);
   }
-  hipLaunchKernelGGL(k_oj_norms, dim3(cdiv_h(steps, 4), B), dim3(256), 0, st, d_edges);
-  hipLaunchKernelGGL(k_oj_order, dim3(cdiv_h(steps, 256), B), dim3(256), 0, st, d_edges);
-  hipLaunchKernelGGL(k_oj_rows, dim3(steps, B), dim3(256), 0, st, d_edges);
+  hipLaunchKernelGGL(k_oj_norms, dim3_of(p.norms), dim3(256), 0, st, d_edges);
+  hipLaunchKernelGGL(k_oj_order, dim3_of(p.order), dim3(256), 0, st, d_edges);
+  hipLaunchKernelGGL(k_oj_rows, dim3_of(p.rows), dim3(256), 0, st, d_edges);
   return hipGetLastError();
 }
 

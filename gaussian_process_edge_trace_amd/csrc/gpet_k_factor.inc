@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(1024) k_pchol(EdgeDev* edges) {
 // step 1, register-resident variant (Lg <= 512, r_cap <= 96): thread i owns row i of the factor and
 // keeps its <= 96 entries in registers (zero until computed), so a step is 96 FMAs against the
 // pivot row broadcast from LDS -- no global-load chain.  Same arithmetic order as k_pchol.
-#define PCH_R 96
+// (PCH_R = 96: gpet_factor_plan.h)
 __global__ void __launch_bounds__(512) k_pchol_reg(EdgeDev* edges) {
   const EdgeDev E = edges[blockIdx.y];
   gpet_scalars* sc = E.sc;
@@ -385,7 +385,7 @@ __global__ void __launch_bounds__(64 * NT) k_jacobi_prerot(EdgeDev* edges, int w
   const double* Wp = jac_warm_source(E, sc, warm);
   if (!Wp) return;  // (uniform)
   constexpr int mp = 16 * NT, KQ = 4 * NT;
-  constexpr int ld = (mp % 32 == 16) ? mp : mp + 16;  // = 16 mod 32
+  constexpr int ld = prerot_ld(mp);  // = 16 mod 32
   const int r = sc->rank, ldg = E.r_cap;
   if (r > mp) return;  // (never: the launcher sizes NT for the batch's largest rank)
   extern __shared__ double s_pr[];
@@ -448,9 +448,7 @@ __global__ void __launch_bounds__(64 * NT) k_jacobi_prerot(EdgeDev* edges, int w
   }
 }
 
-#define JS_NT 512
-#define JS_LOG_SWEEPS 40  // sweeps a rotation log holds (= the sweep limit of the kernel)
-#define JA_NT_LOG 512     // k_jacobi_ahead, rotation-log form: seven worker waves (two blocks per thread up to rank 82, else three) + the parameter wave
+// (JS_NT, JS_LOG_SWEEPS, JA_NT_LOG and the LDS layout of these kernels -- jac_players, jac_blocks, jac_plane_stride, ...: gpet_factor_plan.h)
 // LOGW (small batches, where the chain of rounds IS the time): the eigenvectors are not accumulated here -- 41 KB of LDS
 // stores a round, 1 200-1 600 of its 2 650 cycles -- but the round's rotations (c, s) go to a log in global memory, and
 // k_jacobi_wpass applies them to the rows of W afterwards, one wave per row in registers, on as many CUs as there are rows.
@@ -466,11 +464,11 @@ __global__ void __launch_bounds__(JS_NT) __attribute__((amdgpu_waves_per_eu(4, 4
   __shared__ int s_pos[96];
   __shared__ double s_theta[96];
   const int r = sc->rank, ldg = E.r_cap;
-  const int m = (r + 1) & ~1;
+  const int m = jac_players(r);
   const int half = m >> 1, m1 = m - 1;
-  const int nblk = half * (half + 1) / 2;
+  const int nblk = jac_blocks(m);
   double* A0 = s_mem;                                                       // [4][nblk]
-  double2* W2 = reinterpret_cast<double2*>(s_mem + 4 * ((nblk + 1) & ~1));  // [hl][m]
+  double2* W2 = reinterpret_cast<double2*>(s_mem + 4 * jac_plane_stride(nblk));  // [hl][m]
   const int tid = threadIdx.x;
   const int hl = half;  // component pairs of W in LDS
   if (nblk > NU * NT) {  // (the launcher picks NU from the batch's capacity)
@@ -766,11 +764,13 @@ __device__ __forceinline__ void ja_run(const EdgeDev& E, gpet_scalars* sc, int s
   //  eigenvector rows in registers: with a scalar loop it needs 106 scalar registers, spills 15 of them into vector lanes and
   //  runs 1.61 instead of 1.47 ms per 1 024 edges)
   const int r = LOGW ? __builtin_amdgcn_readfirstlane(sc->rank) : sc->rank, ldg = E.r_cap;
+  // (m and nreg below are jac_players(r) and jac_reg_rows(RR, m) of gpet_factor_plan.h as text: through either function the compiler
+  //  emits k_jacobi_ahead<2, false, 6>, the bench's kernel, one instruction longer.  Nothing but reading holds the two to the header.)
   const int m = (r + 1) & ~1;
   const int half = m >> 1, m1 = m - 1;
-  const int nblk = half * (half + 1) / 2;
-  const int nbp = (nblk + 1) & ~1;                                             // plane stride
-  const int bst = 4 * nbp + 2;                                                 // copy stride: four planes + the dump slot
+  const int nblk = jac_blocks(m);
+  const int nbp = jac_plane_stride(nblk);                                      // plane stride
+  const int bst = jac_ahead_copy_stride(nbp);                                  // copy stride: four planes + the dump slot
   double* A0 = s_mem;                                                          // [2][4 nbp + 2]
   double2* W2 = reinterpret_cast<double2*>(s_mem + 2 * bst);                   // [hl][m]
   const int tid = threadIdx.x;

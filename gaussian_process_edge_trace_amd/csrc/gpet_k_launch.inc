@@ -340,20 +340,6 @@ hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src,
   return hipGetLastError();
 }
 
-// hipFuncSetAttribute applies to the CURRENT device: remember per device what has been raised, so that one process
-// may hold contexts on several GPUs (the launchers run with the context's device current).
-struct PerDeviceOnce {
-  bool done[64] = {};
-  bool first() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return true;
-    if (done[d]) return false;
-    done[d] = true;
-    return true;
-  }
-};
-
-static dim3 dim3_of(const Grid3& g) { return dim3(g.x, g.y, g.z); }
 // f(std::integral_constant<int, KS>) for the K extent ks a plan chose (one of K_EXTENTS): the template instances of the sample GEMMs and of k_struct_rows
 template <typename F>
 static void for_k_extent(int ks, F&& f) {
@@ -430,91 +416,64 @@ hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const B
   return hipGetLastError();
 }
 
+// ---- eigen-factor stage of the LDS path: the plans of gpet_factor_plan.h decide, these name the template instances and launch ----
+using JacobiKernel = void (*)(EdgeDev*, int, int);
+static int jacobi_kernel_index(const JacobiSmallPlan& p) { return (p.ahead ? 4 : 0) + (p.nu == 3 ? 2 : 0) + (p.log ? 1 : 0); }
+static JacobiKernel jacobi_kernel(int index) {
+  switch (index) {
+    case 0: return k_jacobi_seat<2, false>;
+    case 1: return k_jacobi_seat<2, true>;
+    case 2: return k_jacobi_seat<3, false>;
+    case 3: return k_jacobi_seat<3, true>;
+    case 4: return k_jacobi_ahead<2, false, JA_RR, JS_NT>;
+    case 5: return k_jacobi_ahead<2, true, 0, JA_NT_LOG>;
+    case 6: return k_jacobi_ahead<3, false, 0, JS_NT>;
+    default: return k_jacobi_ahead<3, true, 0, JA_NT_LOG>;
+  }
+}
+using PrerotKernel = void (*)(EdgeDev*, int);
+static PrerotKernel prerot_kernel(int nt) {
+  switch (nt) {
+    case 2: return k_jacobi_prerot<2>;
+    case 3: return k_jacobi_prerot<3>;
+    case 4: return k_jacobi_prerot<4>;
+    case 5: return k_jacobi_prerot<5>;
+    default: return k_jacobi_prerot<6>;  // (no plan names it while its LDS does not fit: jacobi_small_plan)
+  }
+}
+
 static void launch_jacobi_small(hipStream_t st, EdgeDev* d_edges, int B, int rank_max, int scaled_out, bool logw) {
-  const int mm = (rank_max + 1) & ~1;
-  static PerDeviceOnce once;
-  if (once.first()) {
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
-    (void)hipFuncSetAttribute((const void*)k_jacobi_prerot<6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
-#define GPET_JS_ATTR(NU_, LOGW_) \
-  (void)hipFuncSetAttribute((const void*)k_jacobi_seat<NU_, LOGW_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX)
-    GPET_JS_ATTR(2, true); GPET_JS_ATTR(3, true);
-    GPET_JS_ATTR(2, false); GPET_JS_ATTR(3, false);
-#undef GPET_JS_ATTR
-#define GPET_JA_ATTR(NU_, LOGW_, RR_, NT_) \
-  (void)hipFuncSetAttribute((const void*)k_jacobi_ahead<NU_, LOGW_, RR_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX)
-    GPET_JA_ATTR(2, true, 0, JA_NT_LOG); GPET_JA_ATTR(3, true, 0, JA_NT_LOG);
-    GPET_JA_ATTR(3, false, 0, JS_NT); GPET_JA_ATTR(2, false, 6, JS_NT);
-#undef GPET_JA_ATTR
+  const JacobiSmallPlan p = jacobi_small_plan(B, rank_max, scaled_out != 0, logw, opt(Opt::jacobi_variant), opt(Opt::jacobi_warm));
+  static PerDeviceOnce prerot_attr[7], jacobi_attr[8];
+  if (p.prerot_nt) {
+    const PrerotKernel k = prerot_kernel(p.prerot_nt);
+    if (prerot_attr[p.prerot_nt].first()) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+    hipLaunchKernelGGL(k, dim3(1, B), dim3(p.prerot_threads), p.prerot_lds, st, d_edges, p.warm);
   }
-  // warm start (structured loop only: there the matrix of an iteration is a small change of the last one's)
-  const int warm = scaled_out ? opt(Opt::jacobi_warm) : 0;
-  if (warm) {
-    const int nt = (rank_max + 15) >> 4;
-#define GPET_PR_LAUNCH(NT_)                                                                                                \
-  hipLaunchKernelGGL(k_jacobi_prerot<NT_>, dim3(1, B), dim3(64 * NT_),                                                       \
-                     (size_t)2 * (16 * NT_) * ((16 * NT_) % 32 == 16 ? 16 * NT_ : 16 * NT_ + 16) * sizeof(double), st, d_edges, warm)
-    if (nt <= 2) GPET_PR_LAUNCH(2);
-    else if (nt == 3) GPET_PR_LAUNCH(3);
-    else if (nt == 4) GPET_PR_LAUNCH(4);
-    else if (nt == 5) GPET_PR_LAUNCH(5);
-    else GPET_PR_LAUNCH(6);
-#undef GPET_PR_LAUNCH
-  }
-  if (opt(Opt::jacobi_variant) != 0) {
-    // parameters one round ahead, one barrier per round (k_jacobi_ahead): the matrix twice in LDS
-    const size_t nblk = (size_t)(mm / 2) * (mm / 2 + 1) / 2, nbp = (nblk + 1) & ~(size_t)1;
-    const dim3 grid(1, B);
-    if (logw) {
-      const size_t lds = (8 * nbp + 4) * sizeof(double);
-      if (nblk <= 2 * (size_t)(JA_NT_LOG - 64)) hipLaunchKernelGGL((k_jacobi_ahead<2, true, 0, JA_NT_LOG>), grid, dim3(JA_NT_LOG), lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_ahead<3, true, 0, JA_NT_LOG>), grid, dim3(JA_NT_LOG), lds, st, d_edges, scaled_out, warm);
-      hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
-    } else {
-      // two blocks per thread: the last 7 x 6 components of the eigenvectors in the worker waves' registers (RR = 6), the rest
-      // in LDS; three blocks per thread (ranks above 82) have no registers to spare
-      const bool three = nblk > 2 * (size_t)(JS_NT - 64);
-      const int nreg = three ? 0 : ((7 * 6 < mm ? 7 * 6 : mm) & ~1);
-      const size_t lds = (8 * nbp + 4 + (size_t)(mm - nreg) * mm) * sizeof(double);
-      if (three) hipLaunchKernelGGL((k_jacobi_ahead<3, false, 0, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_ahead<2, false, 6, JS_NT>), grid, dim3(JS_NT), lds, st, d_edges, scaled_out, warm);
-    }
-  } else {
-    const size_t nblk = (size_t)(mm / 2) * (mm / 2 + 1) / 2;
-    const size_t lds = (4 * ((nblk + 1) & ~(size_t)1) + (size_t)mm * mm) * sizeof(double);
-    const dim3 grid(1, B), block(JS_NT);
-    if (logw) {
-      // small batch: rotations logged, eigenvectors by a second kernel (one wave per row of W)
-      if (nblk <= 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<2, true>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_seat<3, true>), grid, block, lds, st, d_edges, scaled_out, warm);
-      hipLaunchKernelGGL(k_jacobi_wpass, dim3((rank_max + 3) / 4, B), dim3(256), 0, st, d_edges, scaled_out, warm);
-    } else {
-      if (nblk > 2 * JS_NT) hipLaunchKernelGGL((k_jacobi_seat<3, false>), grid, block, lds, st, d_edges, scaled_out, warm);
-      else hipLaunchKernelGGL((k_jacobi_seat<2, false>), grid, block, lds, st, d_edges, scaled_out, warm);
-    }
-  }
+  const int ki = jacobi_kernel_index(p);
+  const JacobiKernel k = jacobi_kernel(ki);
+  if (jacobi_attr[ki].first()) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX);
+  hipLaunchKernelGGL(k, dim3(1, B), dim3(p.threads), p.lds, st, d_edges, scaled_out, p.warm);
+  // (small batch: rotations logged, eigenvectors by a second kernel, one wave per row of W)
+  if (p.log) hipLaunchKernelGGL(k_jacobi_wpass, dim3_of(p.wpass), dim3(256), 0, st, d_edges, scaled_out, p.warm);
 }
 
 hipError_t launch_factor(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts, const EdgeDev* h_edges,
                          bool single_wg_pchol) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (bd.r_cap > 96) return launch_factor_big(st, d_edges, B, bd, h_edges);  // (any rank: csrc/gpet_eig.hip)
-  if (!(parts & 1u)) {
-  } else if (!single_wg_pchol && pchol_multi_applies(bd)) {
-    const hipError_t e = launch_pchol_multi(st, d_edges, B, bd);
-    if (e != hipSuccess) return e;
-  } else if (bd.Lg <= 512 && bd.r_cap <= PCH_R) {
-    hipLaunchKernelGGL(k_pchol_reg, dim3(1, B), dim3(512), 0, st, d_edges);
-  } else {
-    int pth = bd.Lg >= 1024 ? 1024 : (bd.Lg > 512 ? 1024 : (bd.Lg > 256 ? 512 : 256));
-    hipLaunchKernelGGL(k_pchol, dim3(1, B), dim3(pth), (size_t)(bd.Lg + bd.r_cap) * sizeof(double), st, d_edges);
+  if (bd.r_cap > FACTOR_LDS_CAP) return launch_factor_big(st, d_edges, B, bd, h_edges);  // (any rank: csrc/gpet_eig.hip)
+  const FactorLdsPlan p = factor_lds_plan(bd, B, opt(Opt::pchol_multi), single_wg_pchol);
+  if (parts & 1u) switch (p.pchol.form) {
+    case PcholForm::multi: {
+      const hipError_t e = launch_pchol_multi(st, d_edges, B, p.pchol.multi);
+      if (e != hipSuccess) return e;
+    } break;
+    case PcholForm::reg: hipLaunchKernelGGL(k_pchol_reg, dim3(1, B), dim3(p.pchol.threads), 0, st, d_edges); break;
+    case PcholForm::one_wg: hipLaunchKernelGGL(k_pchol, dim3(1, B), dim3(p.pchol.threads), p.pchol.lds, st, d_edges); break;
   }
-  const int t = cdiv(bd.r_cap, 16);
-  if (parts & 2u) hipLaunchKernelGGL(k_gram, dim3(t, t, B), dim3(256), 0, st, d_edges);
+  if (parts & 2u) hipLaunchKernelGGL(k_gram, dim3_of(p.gram), dim3(256), 0, st, d_edges);
   if (parts & 4u) launch_jacobi_small(st, d_edges, B, bd.r_cap, 0, bd.jlog != 0 && opt(Opt::jacobi_logw) != 0);
-  if (parts & 8u)
-    hipLaunchKernelGGL(k_factor_rows, dim3(bd.r_cap, B), dim3(256), (size_t)bd.r_cap * sizeof(double), st, d_edges);
+  if (parts & 8u) hipLaunchKernelGGL(k_factor_rows, dim3_of(p.rows), dim3(256), p.rows_lds, st, d_edges);
   return hipGetLastError();
 }
 

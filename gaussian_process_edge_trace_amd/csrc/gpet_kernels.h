@@ -4,6 +4,7 @@
 
 #include "gpet_batch_plan.h"  // EdgeDev (gpet_dev.h), BatchDims, STRUCT_H_LDS_MAX
 #include "gpet_iter_plan.h"   // one loop iteration: kernel variant, grid and LDS of every step; the tile constants
+#include "gpet_factor_plan.h"  // eigen-factor stage: kernel variant, grid and LDS of every launch; the layouts its kernels share with it
 #include "gpet_conv_plan.h"   // pixel types, conv geometry, staging plan
 #include "gpet_conv_multi_plan.h"  // slot table of a multi-kernel source: validation, union patch, slots of each frame
 #include "gpet_transpose_plan.h"  // vertical batches: the index map, the tile transpose, the transposed-store convolution
@@ -32,6 +33,20 @@ __device__ inline long long int_f64_to_i64(double r) {
   const unsigned long long mag = ex >= 0 ? mant << ex : mant >> -ex;
   return (u >> 63) ? -(long long)mag : (long long)mag;
 }
+
+// hipFuncSetAttribute applies to the CURRENT device: remember per device what has been raised, so that one process
+// may hold contexts on several GPUs (the launchers run with the context's device current).
+struct PerDeviceOnce {
+  bool done[64] = {};
+  bool first() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return true;
+    if (done[d]) return false;
+    done[d] = true;
+    return true;
+  }
+};
+inline dim3 dim3_of(const Grid3& g) { return dim3(g.x, g.y, g.z); }
 
 hipError_t launch_conv(hipStream_t st, const double* d_img, int M, int N, const double* d_wf, int kh, int kw, int oy,
                        int ox, float* d_tmp, unsigned int* d_minmax);
@@ -92,8 +107,9 @@ hipError_t launch_final_cov(hipStream_t st, EdgeDev* d_edges, int B, const Batch
 hipError_t launch_factor(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts = ~0u,
                          const EdgeDev* h_edges = nullptr, bool single_wg_pchol = false);
 // csrc/gpet_eig.hip: the pivoted Cholesky of a wide edge of rank <= 96 by the multi-workgroup kernels of the any-rank factor
+// (pchol_plan of gpet_factor_plan.h with the option pchol_multi chooses that form; p: that plan's `multi`)
 bool pchol_multi_applies(const BatchDims& bd);
-hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);
+hipError_t launch_pchol_multi(hipStream_t st, EdgeDev* d_edges, int B, const PcholMultiPlan& p);
 hipError_t launch_struct_iteration(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, unsigned parts = ~0u);
 hipError_t launch_struct_basis(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);
 hipError_t launch_normals(hipStream_t st, EdgeDev* d_edges, int B, const unsigned int* d_seeds, int add_iter,

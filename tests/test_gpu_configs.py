@@ -413,6 +413,42 @@ def test_structured_loop_warm_started_eigen_decomposition(amd, ctx):
         assert np.mean(res[1][0]) < np.mean(res[0][0]), (res[0][0], res[1][0])
 
 
+def test_structured_loop_prior_rank_above_80_starts_cold(amd, ctx):
+    """A prior eigenbasis of rank 81 .. 95 would need k_jacobi_prerot<6>, whose 2 * 96 * 112 * 8 = 172 032 bytes of LDS no CU has: the
+    plan (csrc/gpet_factor_plan.h) runs such a batch from the identity, so jacobi_warm = 1 and 0 are the same launches and the same
+    bits.  The length scale is chosen on the host: the greedy pivoted Cholesky of the grid's correlation matrix stops at rank 89 for
+    l = 5 on 160 columns (l = 8: 59, l = 4.5: the capacity, and the batch is not structured)."""
+    from tests import factor_exact as fx
+    L = amd._lib
+    ell = 5.0
+    x = np.arange(160, dtype=np.float64)
+    piv, _, _ = fx.greedy_pivots(orc.corr_matrix("RBF", 2.5, x, x, ell), cap=96)
+    assert 83 <= piv.size <= 93     # (the device's rank may differ by a direction at the tolerance)
+    img, truth = orc.synth_sinusoid_image(160, 2)
+    grad = amd.gpet_utils.comp_grad_img(img, amd.gpet_utils.kernel_builder((11, 5)), ctx=ctx)
+    init = truth[[0, -1], :][:, [1, 0]]
+    kw = dict(kernel_options={'kernel': 'RBF', 'sigma_f': 30, 'length_scale': ell}, noise_y=1, N_samples=64, score_thresh=1,
+              delta_x=5, keep_ratio=0.1, pixel_thresh=4, fix_endpoints=True)
+    seeds = [5, 1002]
+    res = {}
+    for warm in (1, 0):
+        old = L.set_option("jacobi_warm", warm)
+        try:
+            bt = amd.GP_Edge_Tracing_Batch([init] * 2, grad, seeds, **kw, _ctx=ctx)
+            b = bt._batch
+            assert b.info()["structured"] == 1 and 81 <= b.info()["r0"] <= 95, b.info()
+            b.iterate(seeds, 3)
+            assert all(b.scalars(e).status == L.OK for e in range(2))
+            rows = [np.array(b.read(L.BUF_FACTOR, e)) for e in range(2)]
+            b.close()
+            traces = amd.GP_Edge_Tracing_Batch([init] * 2, grad, seeds, **kw, _ctx=ctx)()
+        finally:
+            L.set_option("jacobi_warm", old)
+        res[warm] = (rows, traces)
+    for e in range(2):
+        assert np.array_equal(res[0][0][e], res[1][0][e]) and np.array_equal(res[0][1][e], res[1][1][e]), e
+
+
 def test_any_rank_factor_warm_start(amd, ctx):
     """Option oj_warm (k_ojw_*): from the second iteration on the one-sided Jacobi of a full-rank (Matern) covariance starts
     from rows built out of the previous iteration's factor instead of a pivoted Cholesky factor.  A^T A = Sigma to rounding

@@ -3,8 +3,9 @@ written through GPET_BUF_COV, factored by gpet_gp_factor, GPET_BUF_FACTOR / GPET
 reference of the same matrix (factor_exact.ref_factor, pinned on the host by tests/test_factor_exact.py).  Every residual is
 formed in the extended format.
 
-Paths, selected by the batch's capacity and width (csrc/gpet_k_launch.inc launch_factor), not by the rank that is found:
-* LDS path (capacity <= 96): k_pchol_reg (Lg <= 512), k_pchol (513), launch_pchol_multi (1030, options 1 and 2) -> k_gram ->
+Paths, selected by the batch's capacity and width (the plans of csrc/gpet_factor_plan.h, which tests/test_factor_plan.py holds
+against the shapes used here), not by the rank that is found:
+* LDS path (capacity <= 96): k_pchol_reg (Lg <= 512), k_pchol (513), the multi-workgroup form (1030, options 1 and 2) -> k_gram ->
   k_jacobi_seat<2|3, log|no log> (option jacobi_variant = 0) or k_jacobi_ahead<2|3, log> / <2, no log, RR 6> / <3, no log>
   (1, the default), the log forms followed by k_jacobi_wpass -> k_factor_rows.  Capacities 40 .. 96 on 100 columns stand on
   both sides of every switch: k_jacobi_ahead's two -> three blocks per thread (82 | 84), k_jacobi_seat's (88 | 90), the register
