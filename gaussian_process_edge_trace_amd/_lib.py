@@ -69,7 +69,11 @@ def denoise_spec(denoise):
         raise ValueError("denoise must be a (technique, kwargs) pair")
     if technique == "nl":  # (a stage of its own: RawFrames takes it through nlmeans_spec)
         raise NotImplementedError("denoising technique 'nl' is no gpet_denoise technique: with fast_mode=False it is built as a "
-                                  "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built")
+                                  "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built under "
+                                  "this name: it is the technique 'nl_fast' (nlmeans_fast_spec, Context.nlmeans_fast_images)")
+    if technique == "nl_fast":  # (a stage of its own: RawFrames takes it through nlmeans_fast_spec)
+        raise NotImplementedError("denoising technique 'nl_fast' is no gpet_denoise technique: it is built as a stage of its own "
+                                  "(nlmeans_fast_spec, Context.nlmeans_fast_images)")
     if technique == "wavelet":  # (a stage of its own as well: RawFrames takes it through wavelet_spec)
         raise NotImplementedError("denoising technique 'wavelet' is no gpet_denoise technique: it is built as a stage of its own "
                                   "(wavelet_spec, Context.wavelet_images) and runs when kwargs names the wavelet, e.g. "
@@ -177,7 +181,7 @@ def nlmeans_spec(kwargs, taps=None):
     if kw.get("fast_mode", True):
         raise NotImplementedError("denoising technique 'nl' is built for fast_mode=False only (scikit-image's classic non-local "
                                   "means); fast_mode=True, the library's default, is another algorithm and not built for the "
-                                  "device: pass fast_mode=False")
+                                  "device: pass fast_mode=False (the fast algorithm is the technique 'nl_fast')")
     if kw.get("multichannel", False):
         raise ValueError("denoise: multichannel=True of 'nl' is not supported on the device (frames are 2-D, single-channel)")
     ps, d = int(kw.get("patch_size", 7)), int(kw.get("patch_distance", 11))
@@ -195,6 +199,85 @@ def nlmeans_spec(kwargs, taps=None):
     if taps.shape != (s, s):
         raise ValueError("denoise: the taps of a %d x %d patch are an array of that shape, not %r" % (s, s, taps.shape))
     return NlmeansSpec(ps, d, h, sigma, taps)
+
+
+# fast-mode non-local means (gpet_nlmeans_fast): scikit-image's DEFAULT denoise_nl_means, the technique 'nl_fast'; a stage of its
+# own with the classic stage's flags
+NLF_KEYS = NLM_KEYS
+NLF_STRIP = 64  # rows a wave takes at a time (gpet_nlfast_plan.h: NLF_STRIP)
+NLF_CHUNK_BUDGET = 256 << 20  # bytes a chunk's workspaces and staging stay inside (gpet_nlfast_plan.h: NLF_CHUNK_BUDGET)
+
+
+class GpetNlmeansFast(C.Structure):
+    _fields_ = [("patch_size", C.c_int32), ("patch_distance", C.c_int32), ("h", C.c_double), ("sigma", C.c_double)]
+
+
+class NlmeansFastSpec(object):
+    """What nlmeans_fast_spec returns: ``c`` the gpet_nlmeans_fast of the call, ``s`` the odd patch extent."""
+
+    def __init__(self, patch_size, patch_distance, h, sigma):
+        self.s = patch_size + (1 if patch_size % 2 == 0 else 0)
+        self.c = GpetNlmeansFast(patch_size=patch_size, patch_distance=patch_distance, h=h, sigma=sigma)
+
+    def arg(self):
+        return C.byref(self.c)
+
+
+def nlmeans_fast_spec(kwargs):
+    """The keyword arguments of ``gpet_utils.denoise(image, 'nl_fast', kwargs)`` -> NlmeansFastSpec, decided from the arguments
+    alone (no device).  'nl_fast' is the reference's ``denoise(image, 'nl', dict(kwargs, fast_mode=True))`` = scikit-image's
+    ``denoise_nl_means`` as the library runs it by default: ``patch_size`` (7), ``patch_distance`` (11), ``h`` (0.1), ``sigma``
+    (0.0); ``fast_mode`` only as true and ``multichannel`` only as false.  Any other key raises ValueError naming it, and so does
+    a value the device refuses; ``fast_mode=False`` raises a ValueError that points to 'nl', the classic algorithm."""
+    kw = dict(kwargs or {})
+    for k in kw:
+        if k not in NLF_KEYS:
+            raise ValueError("denoise: keyword %r of 'nl_fast' is not supported on the device (supported: %s)" % (k, ", ".join(NLF_KEYS)))
+    if not kw.get("fast_mode", True):
+        raise ValueError("denoise: fast_mode=False of 'nl_fast': the technique is the library's fast algorithm; the classic one "
+                         "is the technique 'nl' with fast_mode=False")
+    if kw.get("multichannel", False):
+        raise ValueError("denoise: multichannel=True of 'nl_fast' is not supported on the device (frames are 2-D, single-channel)")
+    for k in ("patch_size", "patch_distance"):
+        if k in kw and not (np.ndim(kw[k]) == 0 and int(kw[k]) == kw[k]):
+            raise ValueError("denoise: %s %r of 'nl_fast': a whole number" % (k, kw[k]))
+    for k in ("h", "sigma"):
+        if k in kw and np.ndim(kw[k]) != 0:
+            raise ValueError("denoise: %s %r of 'nl_fast': one number" % (k, kw[k]))
+    ps, d = int(kw.get("patch_size", 7)), int(kw.get("patch_distance", 11))
+    h, sigma = float(kw.get("h", 0.1)), float(kw.get("sigma", 0.0))
+    s = ps + (1 if ps % 2 == 0 else 0)
+    if ps < 2 or s > NLM_PATCH_MAX:
+        raise ValueError("denoise: patch_size %r of 'nl_fast': patches of 3 x 3 to %d x %d pixels are built" % (ps, NLM_PATCH_MAX, NLM_PATCH_MAX))
+    if d < 0 or d > NLM_DIST_MAX:
+        raise ValueError("denoise: patch_distance %r of 'nl_fast': distances of 0 to %d are built" % (d, NLM_DIST_MAX))
+    if not (h > 0 and np.isfinite(h)):
+        raise ValueError("denoise: h %r of 'nl_fast': one finite number above 0" % (h,))
+    if not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError("denoise: sigma %r of 'nl_fast': one finite number, not negative" % (sigma,))
+    return NlmeansFastSpec(ps, d, h, sigma)
+
+
+def nlmeans_fast_plan(M, N, s, d, budget=NLF_CHUNK_BUDGET):
+    """A mirror of gpet_nlfast_plan.h's nlf_plan for M x N frames, odd patch extent ``s`` and distance ``d`` -> dict: ``pad``,
+    ``nr`` x ``nc`` the padded frame, ``n_shifts`` = (2 d + 1)(d + 1), ``rows_per_group`` whole rows of d + 1 shifts whose integral
+    images a frame's workspace holds at a time (0: not one fits ``budget``), ``n_groups``, ``strips`` of NLF_STRIP rows,
+    ``frame_bytes`` of workspace (the padded frame, two accumulators of M N and the group's planes, float64, to 256 bytes) and
+    ``frames_per_chunk`` when nothing is staged."""
+    M, N, s, d = int(M), int(N), int(s), int(d)
+    pad = s // 2 + d + 1
+    nr, nc = M + 2 * pad, N + 2 * pad
+    plane = nr * nc
+
+    def frame_bytes(rows):
+        return ((plane + 2 * M * N + rows * (d + 1) * plane) * 8 + 255) & ~255
+
+    rows = 0
+    while rows < 2 * d + 1 and frame_bytes(rows + 1) <= budget:
+        rows += 1
+    fb = frame_bytes(max(rows, 1))
+    return dict(pad=pad, nr=nr, nc=nc, n_shifts=(2 * d + 1) * (d + 1), rows_per_group=rows, n_groups=-(-(2 * d + 1) // rows) if rows else 0,
+                strips=-(-nr // NLF_STRIP), frame_bytes=fb, frames_per_chunk=max(1, min(budget // fb, 65535)))
 
 
 # wavelet denoising (gpet_wavelet, GPET_WV_*): the second stage of its own in front of the raw-frame path
@@ -393,6 +476,9 @@ PRE_STAGES = {"nl": nlmeans_spec, "wavelet": wavelet_spec}
 # PRE_STAGE_OF)
 PRE_STAGE_OF = dict(PRE_STAGES, tvb=tvb_spec)
 PRE_SPECS = (NlmeansSpec, WaveletSpec, TvbSpec)
+# (these two are pinned as exactly the three by tests/test_tvb_host.py in their turn; RawFrames looks every stage up in the two below)
+PRE_STAGE_BY_NAME = dict(PRE_STAGE_OF, nl_fast=nlmeans_fast_spec)
+PRE_SPEC_TYPES = PRE_SPECS + (NlmeansFastSpec,)
 
 
 class GpetParams(C.Structure):
@@ -739,10 +825,10 @@ class RawFrames(object):
         # ('nl', 'wavelet' and 'tvb' are stages of their own: the frames go through Context.pre_images into device memory first -- see
         # pre_resolved)
         self.pre = None
-        if isinstance(denoise, PRE_SPECS):
+        if isinstance(denoise, PRE_SPEC_TYPES):
             self.pre, denoise = denoise, None
-        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGE_OF:
-            self.pre, denoise = PRE_STAGE_OF[denoise[0]](denoise[1]), None
+        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGE_BY_NAME:
+            self.pre, denoise = PRE_STAGE_BY_NAME[denoise[0]](denoise[1]), None
         self.dn = denoise_spec(denoise)
         self.slots = None
         if slots is not None:
@@ -780,6 +866,11 @@ class RawFrames(object):
     def nlm(self):
         """The non-local means spec of these frames, or None."""
         return self.pre if isinstance(self.pre, NlmeansSpec) else None
+
+    @property
+    def nlf(self):
+        """The fast-mode non-local means spec of these frames, or None."""
+        return self.pre if isinstance(self.pre, NlmeansFastSpec) else None
 
     @property
     def wv(self):
@@ -912,6 +1003,8 @@ SYMBOLS = {
                                       C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_nlmeans_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeans), C.c_uint,
                                       C.POINTER(_P)]),
+    "gpet_nlmeans_fast_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeansFast), C.c_uint,
+                                           C.POINTER(_P)]),
     "gpet_tvb_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetTvb), C.c_uint,
                                   C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_wavelet_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetWavelet), C.c_uint,
@@ -1220,9 +1313,12 @@ class Context:
         return out, n_iter
 
     def pre_images(self, raw, out_device_ptrs=None):
-        """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images, wavelet_images or tvb_images."""
+        """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images, nlmeans_fast_images, wavelet_images or
+        tvb_images."""
         if raw.tvb is not None:
             return self.tvb_images(raw, out_device_ptrs=out_device_ptrs)
+        if raw.nlf is not None:
+            return self.nlmeans_fast_images(raw, out_device_ptrs=out_device_ptrs)
         if raw.wv is not None:
             return self.wavelet_images(raw, out_device_ptrs=out_device_ptrs)
         return self.nlmeans_images(raw, out_device_ptrs=out_device_ptrs)
@@ -1293,6 +1389,18 @@ class Context:
         M, N = raw.shape
         out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
         self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlm.arg(), flags, op))
+        return out
+
+    def nlmeans_fast_images(self, raw, out_device_ptrs=None):
+        """gpet_nlmeans_fast_images: fast-mode non-local means of every frame of ``raw`` (a RawFrames made with
+        ``denoise=('nl_fast', kwargs)`` or a NlmeansFastSpec) in one batched pass -> (T, M, N) float64.  ``out_device_ptrs``: device
+        addresses of float64 (M, N) frames to write instead (GPET_NLM_OUT_ON_DEVICE; returns None) -- with frames on the device
+        too, nothing is waited for."""
+        if raw.nlf is None:
+            raise ValueError("no fast-mode non-local means spec")
+        M, N = raw.shape
+        out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
+        self.check(self.lib.gpet_nlmeans_fast_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlf.arg(), flags, op))
         return out
 
     def normalise_f32(self, img):

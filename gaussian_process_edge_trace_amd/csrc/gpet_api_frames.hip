@@ -1,7 +1,7 @@
 // C ABI, a1 for stacks of raw frames: the one description of a raw-frame source (RawSource, gpet_api_internal.h) with its refusals,
 // conv_frames -- every frame staged and denoised once, its gradient images made on the device --, the entry points on a context
-// (gpet_grad_images*, gpet_denoise_images) and the three stages of their own in front of them (gpet_nlmeans_images,
-// gpet_wavelet_images, gpet_tvb_images).
+// (gpet_grad_images*, gpet_denoise_images) and the four stages of their own in front of them (gpet_nlmeans_images,
+// gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images).
 #include "gpet_api_internal.h"
 
 static_assert(DN_NONE == GPET_DN_NONE && DN_MEDIAN == GPET_DN_MEDIAN && DN_MINIMUM == GPET_DN_MINIMUM && DN_GAUSSIAN == GPET_DN_GAUSSIAN &&
@@ -392,6 +392,36 @@ int gpet_nlmeans_images(gpet_ctx* c, const void* const* raw, int n_img, int pix,
         return launch_nlmeans(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, s, d, (const double*)k.d_extras, var2);
       },
       no_chunk_hook);
+}
+
+// Fast-mode non-local means (gpet_nlfast_plan.h).  No extras.  Frames go chunk by chunk (nlf_chunks), the padded frame, the
+// accumulators and the integral images of a group of shifts through the context's workspace; per chunk one padding launch and
+// per group one integral and one gather launch, enqueued without waiting.
+int gpet_nlmeans_fast_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans_fast* spec,
+                             unsigned int flags, void* const* out) {
+  if (!c || !raw || !spec || !out || n_img <= 0 || M <= 0 || N <= 0)
+    return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_fast_images: bad argument");
+  NlfSpec sp;
+  sp.patch_size = spec->patch_size;
+  sp.patch_distance = spec->patch_distance;
+  sp.h = spec->h;
+  sp.sigma = spec->sigma;
+  if (const char* why = nlf_check(sp, pix, M, N))
+    return fail(c, GPET_ERR_BAD_ARG, "nlmeans_fast: %s (patch_size %d, patch_distance %d, h %g, sigma %g, frames %d x %d)", why, sp.patch_size,
+                sp.patch_distance, sp.h, sp.sigma, M, N);
+  const NlfPlan np = nlf_plan(M, N, nlm_patch(sp.patch_size), sp.patch_distance);
+  if (np.rows_per_group < 1)
+    return fail(c, GPET_ERR_BAD_ARG,
+                "nlmeans_fast: the workspace of a %d x %d frame with the integral images of one row of %d shifts needs %zu bytes, more than %zu",
+                M, N, nlf_row_shifts(np.d), np.frame_bytes, NLF_CHUNK_BUDGET);
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_nlmeans_fast_images: frame or output %d is a null pointer", g);
+  PreStage st;
+  st.out_dev_bit = GPET_NLM_OUT_ON_DEVICE;
+  st.ws_bytes = np.frame_bytes;
+  return pre_stage(
+      c, raw, out, n_img, pix, M, N, flags, st, [&](size_t staged) { return nlf_chunks(n_img, staged, np); },
+      [&](const PreChunk& k) { return launch_nlfast(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, sp, np, k.ws); }, no_chunk_hook);
 }
 
 // Wavelet denoising (gpet_wavelet_plan.h).  Extras: sigma [n_img] | thresholds [n_img * levels * 3] | means of squares [the same].

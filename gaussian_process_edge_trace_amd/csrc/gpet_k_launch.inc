@@ -227,6 +227,28 @@ hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, dou
   });
   return hipGetLastError();
 }
+// ---- a0: fast-mode non-local means (gpet_k_nlfast.inc; geometry: gpet_nlfast_plan.h) ----
+hipError_t launch_nlfast(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                         const NlfSpec& sp, const NlfPlan& p, char* ws) {
+  (void)hipGetLastError();  // drop stale errors: report only these launches
+  if (n < 1 || n > NLF_CHUNK_MAX || nlf_check(sp, pix, M, N) || p.rows_per_group < 1 || p.s != nlm_patch(sp.patch_size) || p.d != sp.patch_distance ||
+      p.nr != M + 2 * p.pad || p.nc != N + 2 * p.pad)
+    return hipErrorInvalidValue;
+  const size_t stride = p.frame_bytes / sizeof(double);
+  const double var2 = 2.0 * sp.sigma * sp.sigma, h2s2 = ((sp.h * sp.h) * p.s) * p.s;
+  for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_nlf_pad<T>), dim3(nlf_pad_blocks(p), 1, n), dim3(NLF_THREADS), 0, st, (const T* const*)d_src, img0, (double*)ws, stride, M, N,
+                       p.pad);
+  });
+  for (int g = 0; g < p.n_groups; ++g) {
+    const int first = nlf_group_first(p, g), cnt = nlf_group_count(p, g);
+    hipLaunchKernelGGL(k_nlf_integral, dim3(cnt, 1, n), dim3(NLF_STRIP), 0, st, (double*)ws, stride, first, p.d, p.nr, p.nc, p.off_i, var2);
+    hipLaunchKernelGGL(k_nlf_gather, dim3(nlf_gather_blocks(M, N), 1, n), dim3(NLF_THREADS), 0, st, (double*)ws, stride, d_dst, img0, M, N, p.off,
+                       p.d, first, cnt, g == p.n_groups - 1 ? 1 : 0, p.off_w, p.off_r, p.off_i, h2s2);
+  }
+  return hipGetLastError();
+}
 // ---- a0: wavelet denoising (gpet_k_wavelet.inc; geometry: gpet_wavelet_plan.h) ----
 template <typename T>
 static void launch_wv_fwd1_t(hipStream_t st, const void* const* d_src, int img0, int n, char* ws, const WvPlan& p, double scale,

@@ -10,6 +10,7 @@
 #include "gpet_transpose_plan.h"  // vertical batches: the index map, the tile transpose, the transposed-store convolution
 #include "gpet_denoise_plan.h"  // denoising spec, workspace layout, chunking
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
+#include "gpet_nlfast_plan.h"   // fast-mode non-local means: spec, shift table, groups, workspace, launch geometry
 #include "gpet_wavelet_plan.h"  // wavelet denoising: spec, levels, pyramid layout, tiles, the threshold's summation order
 #include "gpet_tvb_plan.h"      // split-Bregman TV denoising: spec, skewed workspace, workgroup, sweeps per launch, the order of acc
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
@@ -88,6 +89,11 @@ hipError_t launch_dn_tvc_iter(hipStream_t st, int pix, const void* const* d_src,
 // frames of the DEVICE pointer table d_dst at the same indices; s: the odd patch extent, d_taps: [s * s] on the device
 hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N, int s,
                           int d, const double* d_taps, double var2);
+// a0, fast-mode non-local means (gpet_nlfast_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) ->
+// the f64 frames of the DEVICE pointer table d_dst at the same indices: one padding launch, then per group of shifts one integral
+// and one gather launch.  p: nlf_plan of the frames and the spec; ws: the chunk's n workspaces (p.frame_bytes apart)
+hipError_t launch_nlfast(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                         const NlfSpec& sp, const NlfPlan& p, char* ws);
 // a0, wavelet denoising (gpet_wavelet_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) -> the
 // f64 frames of the DEVICE pointer table d_dst at the same indices, 2 levels + 2 launches (one fewer with injected thresholds).  ws: the
 // chunk's n pyramids; d_sigma [frames], d_thr / d_ms [frames * levels * 3] on the device, indexed by frame like the tables -- with

@@ -20,6 +20,7 @@ namespace gpet {
 #include "gpet_k_conv.inc"
 #include "gpet_k_denoise.inc"
 #include "gpet_k_nlmeans.inc"
+#include "gpet_k_nlfast.inc"
 #include "gpet_k_wavelet.inc"
 #include "gpet_k_tvb.inc"
 #include "gpet_k_fit.inc"

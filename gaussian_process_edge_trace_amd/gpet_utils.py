@@ -2,7 +2,8 @@
 
 ``comp_grad_img`` / ``comp_grad_imgs`` / ``normalise`` run on the GPU through libgpet_hip.so (a1), and so do ``denoise`` /
 ``denoise_imgs`` (a0) for the reference's 'median', 'minimum', 'gaussian', 'tvc', 'nl' (fast_mode=False), 'wavelet' (the
-wavelet named) and 'tvb' (weight given); ``kernel_builder``
+wavelet named) and 'tvb' (weight given), and for 'nl_fast', the reference's 'nl' with the library's default fast_mode=True;
+``kernel_builder``
 is host-side setup (a 11x5 table).  ``construct_test_img`` is this package's own generator of the
 reference's synthetic test image recipe (gpet_utils.py:163-253).  Called like the reference (no ``seed``) it returns the
 reference's own image bit for bit: scikit-image 0.18's ``random_noise(..., seed=1)`` (gpet_utils.py:251) is
@@ -91,8 +92,8 @@ def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False):
     """``denoise`` of every frame of a stack in ONE batched GPU pass (gpet_denoise_images): ``imgs`` is a (T, M, N) array or a
     sequence of (M, N) frames of one dtype, the result a (T, M, N) array whose frame t equals ``denoise(imgs[t], technique,
     kwargs)`` bit for bit.  ``return_n_iter``: also the iterations 'tvc' ran per frame (0 for the filters).  'nl' with
-    ``fast_mode=False``, 'wavelet' with the ``wavelet`` key and 'tvb' with ``weight`` are stages of their own (gpet_nlmeans_images,
-    gpet_wavelet_images, gpet_tvb_images): float64 frames whatever the frames' dtype; for 'tvb' ``return_n_iter`` gives the sweeps
+    ``fast_mode=False``, 'nl_fast', 'wavelet' with the ``wavelet`` key and 'tvb' with ``weight`` are stages of their own
+    (gpet_nlmeans_images, gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images): float64 frames whatever the frames' dtype; for 'tvb' ``return_n_iter`` gives the sweeps
     every frame ran (0 for 'nl' and 'wavelet')."""
     raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs))  # (refuses a bad spec before a device is needed)
     out, n_iter = (ctx or _ctx()).denoise_images(raw)
@@ -113,8 +114,11 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     'nl' is scikit-image's non-local means with ``fast_mode=False`` (``patch_size``, ``patch_distance``, ``h``, ``sigma``): the
     library's classic algorithm bit for bit, in float64 -- integer frames keep their range, a float32 frame gives the library's
     result on ``image.astype(float64)``, and a candidate whose final patch distance exceeds 708 weighs 0.
-    ``fast_mode=True``, the library's default and another algorithm, is not built: 'nl' without ``fast_mode=False`` raises
-    NotImplementedError.
+    ``fast_mode=True``, the library's default and another algorithm, has a name of its own here: 'nl' without ``fast_mode=False``
+    raises NotImplementedError as it always did, and 'nl_fast' (``patch_size``, ``patch_distance``, ``h``, ``sigma``) is the
+    reference's ``denoise(image, 'nl', dict(kwargs, fast_mode=True))`` bit for bit, in float64 with the same two deviations
+    (integer frames keep their range, a float32 frame gives the library's result on ``image.astype(float64)``); the frame's smaller
+    extent must exceed ``patch_size // 2 + patch_distance + 1`` (the padding reflects once; DESIGN.md 9).
     'wavelet' is scikit-image's ``denoise_wavelet`` on PyWavelets (``wavelet``, ``sigma``, ``mode``, ``wavelet_levels``, ``method``,
     ``rescale_sigma``) for the orthogonal wavelets of ``_lib.wavelet_table()``, in float64: integer frames enter as x / 255,
     x / 65535 and come back clipped to [0, 1], a float32 frame gives the library's result on ``image.astype(float64)``, and the
@@ -129,7 +133,7 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     DESIGN.md 9), so the output is the library's bit for bit wherever the sweep counts agree.  It runs only when kwargs gives
     ``weight``, the library's required argument; without it 'tvb' raises NotImplementedError as it always did.  Frames of at least
     2 x 2 pixels whose smaller extent is at most 768."""
-    if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.DN_NOT_BUILT:
+    if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.DN_NOT_BUILT and technique not in _lib.PRE_STAGE_BY_NAME:
         print("Denoising technique not implemented.")
         return None
     if plot or verbose:

@@ -246,7 +246,7 @@ int gpet_grad_images_multi(gpet_ctx* ctx, const void* const* raw, int n_frames, 
  * frames, bit for bit: the classic algorithm (Gaussian-weighted patch distances, the 5.0 cutoff at patch-row starts, the
  * integer-trick exponential), in float64, in the library's order of operations (csrc/gpet_nlmeans_plan.h states it).  A stage of
  * its own, not a gpet_denoise technique: milliseconds per frame, one kernel launch per staging chunk.  fast_mode=True (the
- * library's default, another algorithm) is not built.  The frame is widened to float64 as it is -- u8 / u16 frames keep their
+ * library's default, another algorithm) is gpet_nlmeans_fast_images below.  The frame is widened to float64 as it is -- u8 / u16 frames keep their
  * range, so h and sigma are in the frame's units -- and the result is float64; an f32 frame gives the library's result on the
  * frame widened to f64 (the library would run in f32).  The weight of a candidate whose final patch distance exceeds 708 is
  * +0.0 (there the library's exponential is undefined): parity is claimed where no final distance exceeds 708. */
@@ -268,6 +268,28 @@ typedef struct gpet_nlmeans {
  * frame or output. */
 int gpet_nlmeans_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans* spec,
                         unsigned int flags, void* const* out);
+/* ---- a0: fast-mode non-local means, gpet_utils.denoise(image, 'nl', kwargs) with the library's default fast_mode=True -- */
+/* scikit-image 0.18.3's denoise_nl_means(image, patch_size, patch_distance, h, fast_mode=True, sigma) on 2-D single-channel
+ * frames, bit for bit: per shift an integral image of squared differences whose serial recurrence is followed in its rounding
+ * order, uniform patch weights, the 5.0 cutoff, the integer-trick exponential, and every pixel's sums in the order the library's
+ * scatter reaches it; in float64 (csrc/gpet_nlfast_plan.h states the arithmetic).  A stage of its own like gpet_nlmeans_images,
+ * with the same two deviations: frames are widened to float64 as they are -- u8 / u16 frames keep their range, so h and sigma are
+ * in the frame's units --, an f32 frame gives the library's result on the frame widened to f64, and the result is float64.
+ * The frame is padded by s / 2 + d + 1 pixels, reflected once.  A frame's workspace holds the padded frame, two accumulators
+ * and the integral images of as many whole rows of shifts (d + 1 shifts of one row offset) as fit 256 MiB. */
+typedef struct gpet_nlmeans_fast {
+  int32_t patch_size;     /* an even size means the next odd one s; 3 <= s <= 15; skimage's default 7 */
+  int32_t patch_distance; /* d: shifts up to d pixels in each direction, 0 <= d <= 31; s / 2 + d + 1 <= min(M, N) - 1; default 11 */
+  double h;               /* above 0: cut-off distance in grey levels; skimage's default 0.1 */
+  double sigma;           /* not negative: noise standard deviation, 2 sigma^2 is taken off every squared difference */
+} gpet_nlmeans_fast;
+/* Fast-mode non-local means of n_img frames [M*N] of pixel type pix: out[g] f64 [M*N] receives frame g.  Host frames and host
+ * outputs go through the staging slot in chunks.  flags: GPET_RAW_ON_DEVICE, GPET_NLM_OUT_ON_DEVICE (with both, nothing is waited
+ * for).  GPET_ERR_BAD_ARG, gpet_last_error naming the cause, for a patch_size below 2 or a patch above 15, d below 0 or above 31,
+ * h <= 0, sigma < 0 or non-finite values, a padding s / 2 + d + 1 above min(M, N) - 1, an unknown pix, a null frame or output,
+ * and a frame so large that the integral images of one row of shifts do not fit the workspace bound (the message gives the bytes). */
+int gpet_nlmeans_fast_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_nlmeans_fast* spec,
+                             unsigned int flags, void* const* out);
 /* ---- a0: wavelet denoising, gpet_utils.denoise(image, 'wavelet', kwargs) (gpet_utils.py:137-138) -- */
 /* scikit-image 0.18.3's denoise_wavelet(image, sigma, wavelet, mode, wavelet_levels, method, rescale_sigma) on PyWavelets 1.1.1 for
  * 2-D single-channel frames and an ORTHOGONAL wavelet given by its decomposition low-pass filter: a separable DWT with symmetric
