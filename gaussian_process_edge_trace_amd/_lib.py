@@ -481,6 +481,141 @@ PRE_STAGE_BY_NAME = dict(PRE_STAGE_OF, nl_fast=nlmeans_fast_spec)
 PRE_SPEC_TYPES = PRE_SPECS + (NlmeansFastSpec,)
 
 
+# polar unwrap (gpet_polar, csrc/gpet_polar_plan.h): raw frames resampled to (radius x angle) in front of everything else, so that a
+# closed contour r(theta) is the horizontal edge the tracer follows
+POLAR_OUT_ON_DEVICE = 8  # gpet_polar_images: out[] are device pointers
+POLAR_NTHETA_MIN, POLAR_CELLS_MAX = 4, 1 << 28
+POLAR_KEYS = ("centre", "n_r", "n_theta", "r0", "dr", "theta0", "pad")
+
+
+class GpetPolar(C.Structure):
+    _fields_ = [("cx", C.POINTER(C.c_double)), ("cy", C.POINTER(C.c_double)), ("n_centres", C.c_int32), ("n_r", C.c_int32),
+                ("n_theta", C.c_int32), ("pad", C.c_int32), ("r0", C.c_double), ("dr", C.c_double), ("cos_t", C.POINTER(C.c_double)),
+                ("sin_t", C.POINTER(C.c_double))]
+
+
+def polar_refusal(n_r, n_theta, pad, r0, dr, pix=PIX_F64, M=2, N=2, n_centres=1, n_img=1, cx=(0.0,), cy=(0.0,)):
+    """Why this spec cannot be unwrapped with (polar_check of csrc/gpet_polar_plan.h, same order, same words), or None.  The defaults
+    of the frame's side pass, so the spec alone can be asked about."""
+    if pix not in (PIX_U8, PIX_U16, PIX_F32, PIX_F64):
+        return "polar: unknown pixel type"
+    if M < 2 or N < 2:
+        return "polar: frames must be at least 2 x 2 pixels"
+    if n_r < 1:
+        return "polar: n_r must be at least 1"
+    if n_theta < POLAR_NTHETA_MIN:
+        return "polar: n_theta must be at least 4"
+    if pad < 0 or pad > n_theta:
+        return "polar: pad must lie in [0, n_theta]"
+    if not (r0 >= 0.0 and r0 < np.inf):
+        return "polar: r0 must be finite and at least 0"
+    if not (dr > 0.0 and dr < np.inf):
+        return "polar: dr must be finite and above 0"
+    if n_theta + 1 + 2 * pad > POLAR_CELLS_MAX // n_r:
+        return "polar: the unwrapped frame exceeds 2^28 pixels (n_r * (n_theta + 1 + 2 * pad))"
+    if n_centres != 1 and n_centres != n_img:
+        return "polar: one centre for all frames or one per frame"
+    if cx is None or cy is None:
+        return "polar: the centres are a null pointer"
+    if not (np.all(np.isfinite(np.asarray(cx, dtype=np.float64)[:n_centres]))
+            and np.all(np.isfinite(np.asarray(cy, dtype=np.float64)[:n_centres]))):
+        return "polar: a centre is not finite"
+    return None
+
+
+def polar_tables(n_theta, theta0=0.0):
+    """(cos_t, sin_t): numpy's cos and sin of ``theta0 + 2 pi j / n_theta``, j = 0 .. n_theta - 1, float64 -- the tables the device
+    takes as data."""
+    theta = float(theta0) + (2.0 * np.pi * np.arange(int(n_theta), dtype=np.float64)) / float(int(n_theta))
+    return np.ascontiguousarray(np.cos(theta)), np.ascontiguousarray(np.sin(theta))
+
+
+class PolarSpec(object):
+    """What polar_spec returns: ``centre`` (n_centres, 2) float64 (cx, cy) rows, ``n_r``, ``n_theta``, ``r0``, ``dr``, ``theta0``,
+    ``pad`` (None until the gradient kernel is known: ``resolved``), the tables ``cos_t`` / ``sin_t``; ``shape`` = (n_r, W) and
+    ``width`` = W = n_theta + 1 + 2 pad once pad is resolved."""
+
+    def __init__(self, centre, n_r, n_theta, r0, dr, theta0, pad):
+        self.centre, self.n_r, self.n_theta, self.r0, self.dr, self.theta0, self.pad = centre, n_r, n_theta, r0, dr, theta0, pad
+        self.cos_t, self.sin_t = polar_tables(n_theta, theta0)
+
+    @property
+    def width(self):
+        return self.n_theta + 1 + 2 * self.pad
+
+    @property
+    def shape(self):
+        return (self.n_r, self.width)
+
+    def as_dict(self):
+        return dict(centre=self.centre.copy(), n_r=self.n_r, n_theta=self.n_theta, r0=self.r0, dr=self.dr, theta0=self.theta0, pad=self.pad)
+
+    def resolved(self, default_pad):
+        """This spec with ``pad=None`` replaced by ``default_pad`` (half the width of the widest gradient kernel; 0 without one)."""
+        if self.pad is not None:
+            return self
+        return polar_spec(dict(self.as_dict(), pad=int(default_pad)))
+
+    def with_centre(self, centre):
+        """This spec around other centres (the shape stays)."""
+        return polar_spec(dict(self.as_dict(), centre=centre))
+
+    def refusal(self, pix, shape, n_img):
+        return polar_refusal(self.n_r, self.n_theta, self.pad, self.r0, self.dr, pix, int(shape[0]), int(shape[1]), self.centre.shape[0],
+                             n_img, self.centre[:, 0], self.centre[:, 1])
+
+    def arg(self):
+        """(gpet_polar of the call, what must stay alive while it runs)."""
+        cx, cy = np.ascontiguousarray(self.centre[:, 0]), np.ascontiguousarray(self.centre[:, 1])
+        dp = C.POINTER(C.c_double)
+        c = GpetPolar(cx=cx.ctypes.data_as(dp), cy=cy.ctypes.data_as(dp), n_centres=cx.shape[0], n_r=self.n_r, n_theta=self.n_theta,
+                      pad=self.pad, r0=self.r0, dr=self.dr, cos_t=self.cos_t.ctypes.data_as(dp), sin_t=self.sin_t.ctypes.data_as(dp))
+        return c, (cx, cy, self.cos_t, self.sin_t)
+
+
+def polar_spec(polar):
+    """``polar=dict(centre=(cx, cy) | (T, 2) array, n_r=, n_theta=, r0=0.0, dr=1.0, theta0=0.0, pad=None)`` -> PolarSpec, decided from
+    the arguments alone (no device); a PolarSpec passes through.  ``centre``: x is the column, y the row; one pair for all frames or
+    one per frame.  ``pad=None``: half the width of the widest gradient kernel, 0 where there is none (``PolarSpec.resolved``).  An
+    unknown or missing key and every value the device would refuse (``polar_refusal``) raise ValueError."""
+    if isinstance(polar, PolarSpec):
+        return polar
+    if not isinstance(polar, dict):
+        raise ValueError("polar must be a dict(centre=, n_r=, n_theta=, r0=0.0, dr=1.0, theta0=0.0, pad=None)")
+    for k in polar:
+        if k not in POLAR_KEYS:
+            raise ValueError("polar: unknown key %r (known: %s)" % (k, ", ".join(POLAR_KEYS)))
+    for k in ("centre", "n_r", "n_theta"):
+        if polar.get(k) is None:
+            raise ValueError("polar: %s is required" % k)
+    for k in ("n_r", "n_theta", "pad"):
+        v = polar.get(k)
+        if v is not None and not (np.ndim(v) == 0 and int(v) == v):
+            raise ValueError("polar: %s %r: a whole number" % (k, v))
+    for k in ("r0", "dr", "theta0"):
+        if np.ndim(polar.get(k, 0.0)) != 0:
+            raise ValueError("polar: %s %r: one number" % (k, polar[k]))
+    centre = np.array(polar["centre"], dtype=np.float64)
+    if centre.shape == (2,):
+        centre = centre.reshape(1, 2)
+    if centre.ndim != 2 or centre.shape[1] != 2 or centre.shape[0] < 1:
+        raise ValueError("polar: centre must be (cx, cy) or a (T, 2) array of them")
+    n_r, n_theta, pad = int(polar["n_r"]), int(polar["n_theta"]), polar.get("pad")
+    r0, dr, theta0 = float(polar.get("r0", 0.0)), float(polar.get("dr", 1.0)), float(polar.get("theta0", 0.0))
+    if not np.isfinite(theta0):
+        raise ValueError("polar: theta0 must be finite")
+    why = polar_refusal(n_r, n_theta, 0 if pad is None else int(pad), r0, dr, cx=centre[:, 0], cy=centre[:, 1], n_centres=centre.shape[0],
+                        n_img=centre.shape[0])
+    if why is not None:
+        raise ValueError(why)
+    return PolarSpec(np.ascontiguousarray(centre), n_r, n_theta, r0, dr, theta0, None if pad is None else int(pad))
+
+
+def polar_default_pad(kernels):
+    """Half the width of the widest of ``kernels`` (2-D arrays); 0 for none."""
+    return max([int(k.shape[1]) // 2 for k in kernels] or [0])
+
+
 class GpetParams(C.Structure):
     _fields_ = [("kernel_type", C.c_int32), ("nu", C.c_double), ("sigma_f", C.c_double),
                 ("length_scale", C.c_double), ("noise_y", C.c_double), ("n_samples", C.c_int32),
@@ -817,9 +952,12 @@ class RawFrames(object):
     tvb_spec: the spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
     ``slots=(frame_of, kernel_of)``: a slot table -- ``kernel`` is then a list of kernels (split_kernels) and image g is made of
     frame ``frame_of[g]`` with kernel ``kernel_of[g]`` (the library's *_multi calls); ``len()`` stays the number of frames,
-    ``n_slots`` is the number of images."""
+    ``n_slots`` is the number of images.
+    ``polar``: a polar spec (polar_spec: a dict or a PolarSpec) -- the frames are unwrapped to (radius x angle) before anything else
+    happens to them (pre_resolved); ``shape`` is then the polar shape (n_r, W), ``src_shape`` the frames' own, ``polar`` the resolved
+    spec (``pad=None`` became half the width of the widest kernel)."""
 
-    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None):
+    def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None, polar=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
         # ('nl', 'wavelet' and 'tvb' are stages of their own: the frames go through Context.pre_images into device memory first -- see
@@ -838,7 +976,7 @@ class RawFrames(object):
                 raise ValueError("a slot table has one frame index and one kernel index per image slot")
             kernel = self.kernels[0]
         self.kernel = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
-        if kernel is None and self.dn is None and self.pre is None:
+        if kernel is None and self.dn is None and self.pre is None and polar is None:
             raise ValueError("raw frames need a gradient kernel or a denoising technique")
         if self.kernel is not None and (self.kernel.ndim != 2 or self.kernel.size == 0):
             raise ValueError("the gradient kernel must be a non-empty 2-D array")
@@ -853,6 +991,15 @@ class RawFrames(object):
             self.flags = 0
             self.ptrs = [f.ctypes.data for f in self.frames]
             self.shape = self.frames[0].shape
+        # (a polar spec: the frames are unwrapped first -- see pre_resolved --, and everything behind sees the polar shape)
+        self.src_shape, self.polar = tuple(self.shape), None
+        if polar is not None:
+            kernels = self.kernels if self.slots is not None else ([] if self.kernel is None else [self.kernel])
+            self.polar = polar_spec(polar).resolved(polar_default_pad(kernels))
+            why = self.polar.refusal(self.pix, self.src_shape, len(self))
+            if why is not None:
+                raise ValueError("%s (%d frames of %d x %d, %d centres)" % ((why, len(self)) + self.src_shape + (self.polar.centre.shape[0],)))
+            self.shape = self.polar.shape
         if self.wv is not None:
             self.wv.levels_on(self.shape)  # (refuses levels the frames do not allow before a device is needed)
         if self.tvb is not None and (min(self.shape) < 2 or min(self.shape) > TVB_DIAG_MAX):
@@ -882,10 +1029,24 @@ class RawFrames(object):
         """The split-Bregman spec of these frames, or None."""
         return self.pre if isinstance(self.pre, TvbSpec) else None
 
+    @property
+    def needs_resolve(self):
+        """True when pre_resolved has work to do: a polar spec or a stage of its own."""
+        return self.pre is not None or self.polar is not None
+
     def pre_resolved(self, ctx, buf):
         """These frames as the raw-frame calls take them: without a stage of its own ('nl', 'wavelet', 'tvb'), self; with one, the frames
         denoised into the device memory of ``buf`` (a PreFrames; enqueued on the context's stream) as float64 device frames with
-        the same kernels and slot table and no further denoising."""
+        the same kernels and slot table and no further denoising.  With a polar spec the frames are unwrapped into ``buf`` first
+        (Context.polar_images), and whatever else these frames carry -- a stage of its own, which then writes into ``buf.second()``, an
+        in-pass technique, kernels, slot table -- goes on from the unwrapped float64 frames as if the caller had given those."""
+        if self.polar is not None:
+            ptrs = buf.reserve(len(self), self.shape[0] * self.shape[1] * 8)
+            ctx.polar_images(self, out_device_ptrs=ptrs)
+            kernel = self.kernels if self.slots is not None else self.kernel
+            flat = RawFrames(kernel, device_ptrs=ptrs, dtype=np.float64, shape=self.shape, slots=self.slots,
+                             denoise=self.pre if self.pre is not None else self.dn)
+            return flat.pre_resolved(ctx, buf.second())
         if self.pre is None:
             return self
         M, N = self.shape
@@ -1005,6 +1166,8 @@ SYMBOLS = {
                                       C.POINTER(_P)]),
     "gpet_nlmeans_fast_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetNlmeansFast), C.c_uint,
                                            C.POINTER(_P)]),
+    "gpet_polar_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetPolar), C.c_uint,
+                                    C.POINTER(_P)]),
     "gpet_tvb_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetTvb), C.c_uint,
                                   C.POINTER(_P), C.POINTER(C.c_int32)]),
     "gpet_wavelet_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetWavelet), C.c_uint,
@@ -1190,7 +1353,13 @@ class PreFrames(object):
     object that feeds them to the raw-frame path, grown on demand, reused from frame to frame, freed on close()."""
 
     def __init__(self, ctx):
-        self.ctx, self.ptr, self.bytes = ctx, None, 0
+        self.ctx, self.ptr, self.bytes, self.next = ctx, None, 0, None
+
+    def second(self):
+        """A second buffer that lives and dies with this one: the unwrapped frames stay in this one while a stage of its own writes."""
+        if self.next is None:
+            self.next = PreFrames(self.ctx)
+        return self.next
 
     def reserve(self, n, frame_bytes):
         """Room for n frames of frame_bytes each -> their device addresses."""
@@ -1203,6 +1372,8 @@ class PreFrames(object):
         return [self.ptr.value + g * pitch for g in range(n)]
 
     def close(self):
+        if self.next is not None:
+            self.next.close()
         if self.ptr is not None and getattr(self.ctx, "h", None):
             self.ctx.lib.gpet_dev_free(self.ctx.h, self.ptr)  # (hipFree waits for the device)
         self.ptr, self.bytes = None, 0
@@ -1264,7 +1435,7 @@ class Context:
         """gpet_grad_images: comp_grad_img of every frame of ``raw`` (a RawFrames) in one batched pass -> (T, M, N) float32.
         ``transpose`` (GPET_FRAMES_TRANSPOSED): (T, N, M), every image the transpose of its frame's gradient image, made on the device."""
         M, N = raw.shape
-        if raw.pre is not None:  # ('nl' / 'wavelet' / 'tvb' first, into device memory of this call; the calls below end with a wait)
+        if raw.needs_resolve:  # (the polar unwrap and 'nl' / 'wavelet' / 'tvb' first, into device memory of this call; the calls below end with a wait)
             buf = PreFrames(self)
             try:
                 return self.grad_images(raw.pre_resolved(self, buf), transpose)
@@ -1298,6 +1469,15 @@ class Context:
     def denoise_images(self, raw):
         """gpet_denoise_images: every frame of ``raw`` (a RawFrames with a denoising technique) denoised in one batched pass ->
         ((T, M, N) array of the reference's dtype, iterations per frame: 0 for the filters, 'nl' and 'wavelet'; the sweeps of 'tvb')."""
+        if raw.polar is not None:  # (unwrapped into device memory of this call; every call below ends with a wait)
+            buf = PreFrames(self)
+            try:
+                ptrs = buf.reserve(len(raw), raw.shape[0] * raw.shape[1] * 8)
+                self.polar_images(raw, out_device_ptrs=ptrs)
+                return self.denoise_images(RawFrames(None, device_ptrs=ptrs, dtype=np.float64, shape=raw.shape,
+                                                     denoise=raw.pre if raw.pre is not None else raw.dn))
+            finally:
+                buf.close()
         if raw.tvb is not None:
             return self.tvb_images(raw, return_n_iter=True)
         if raw.pre is not None:
@@ -1314,7 +1494,9 @@ class Context:
 
     def pre_images(self, raw, out_device_ptrs=None):
         """The stage of its own that ``raw`` carries (RawFrames.pre): nlmeans_images, nlmeans_fast_images, wavelet_images or
-        tvb_images."""
+        tvb_images.  Frames that carry a polar spec are unwrapped first (RawFrames.pre_resolved): the stage runs on those."""
+        if raw.polar is not None:
+            raise ValueError("frames with a polar spec are unwrapped first: run the stage on raw.pre_resolved(ctx, buf)")
         if raw.tvb is not None:
             return self.tvb_images(raw, out_device_ptrs=out_device_ptrs)
         if raw.nlf is not None:
@@ -1379,6 +1561,20 @@ class Context:
         self.check(self.lib.gpet_tvb_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.tvb.arg(), flags, op,
                                             n_iter.ctypes.data_as(C.POINTER(C.c_int32)) if return_n_iter else None))
         return (out, n_iter) if return_n_iter else out
+
+    def polar_images(self, raw, out_device_ptrs=None):
+        """gpet_polar_images: every frame of ``raw`` (a RawFrames made with ``polar=``) unwrapped to (radius x angle) in one batched
+        pass -> (T, n_r, W) float64; nothing else ``raw`` carries is applied.  ``out_device_ptrs``: device addresses of float64
+        (n_r, W) frames to write instead (GPET_POLAR_OUT_ON_DEVICE; returns None) -- with frames on the device too, nothing is
+        waited for."""
+        if raw.polar is None:
+            raise ValueError("no polar spec")
+        M, N = raw.src_shape
+        out, op, flags = self._pre_out(raw, out_device_ptrs, POLAR_OUT_ON_DEVICE)
+        c, keep = raw.polar.arg()
+        self.check(self.lib.gpet_polar_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, C.byref(c), flags, op))
+        del keep
+        return out
 
     def nlmeans_images(self, raw, out_device_ptrs=None):
         """gpet_nlmeans_images: non-local means of every frame of ``raw`` (a RawFrames made with ``denoise=('nl', kwargs)`` or a
@@ -1568,7 +1764,7 @@ class Batch:
         self.lib = ctx.lib
         B = len(params)
         self._pre_buf = None  # device frames of a stage of its own in front of the raw-frame path (PreFrames), kept for set_images
-        if raw is not None and raw.pre is not None:
+        if raw is not None and raw.needs_resolve:
             self._pre_buf = PreFrames(ctx)
             raw = raw.pre_resolved(ctx, self._pre_buf)
         if image_of is not None:
@@ -1683,7 +1879,7 @@ class Batch:
             if grads is not None or device_ptrs is not None:
                 raise ValueError("gradient images and raw frames are alternatives")
             assert raw.n_slots == n_img and tuple(raw.shape) == self.frame_shape
-            if raw.pre is not None:  # (refused before the images are swapped: the batch stays on its old frames)
+            if raw.needs_resolve:  # (refused before the images are swapped: the batch stays on its old frames)
                 if self._pre_buf is None:
                     self._pre_buf = PreFrames(self.ctx)
                 raw = raw.pre_resolved(self.ctx, self._pre_buf)

@@ -1,7 +1,7 @@
 // C ABI, a1 for stacks of raw frames: the one description of a raw-frame source (RawSource, gpet_api_internal.h) with its refusals,
 // conv_frames -- every frame staged and denoised once, its gradient images made on the device --, the entry points on a context
 // (gpet_grad_images*, gpet_denoise_images) and the four stages of their own in front of them (gpet_nlmeans_images,
-// gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images).
+// gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images), with the polar unwrap (gpet_polar_images) in front of those.
 #include "gpet_api_internal.h"
 
 static_assert(DN_NONE == GPET_DN_NONE && DN_MEDIAN == GPET_DN_MEDIAN && DN_MINIMUM == GPET_DN_MINIMUM && DN_GAUSSIAN == GPET_DN_GAUSSIAN &&
@@ -290,6 +290,7 @@ struct PreStage {
   const void* init = nullptr;
   size_t init_off = 0, init_bytes = 0;
   size_t ws_bytes = 0;              // what a frame keeps in the context's workspace (pre_ws)
+  size_t out_px = 0;                // pixels of a result where it is not the frame's M N (the polar unwrap); 0: M N
   bool read_back = false;           // the extras come back at the end, in one copy the call waits for ...
   const char* h_extras = nullptr;   // ... into the host copy, which pre_stage leaves here
 };
@@ -314,7 +315,7 @@ static int pre_stage(gpet_ctx* c, const void* const* raw, void* const* out, int 
                      PreStage& st, Chunks&& chunks, Launch&& launch, Hook&& after_chunk) {
   HIPCHK(c, hipSetDevice(c->device));
   const bool in_dev = (flags & GPET_RAW_ON_DEVICE) != 0, out_dev = (flags & st.out_dev_bit) != 0;
-  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = px * sizeof(double);
+  const size_t px = (size_t)M * N, img_bytes = px * (size_t)pix_bytes(pix), out_bytes = (st.out_px ? st.out_px : px) * sizeof(double);
   const size_t st_in = in_dev ? 0 : dn_align(img_bytes), st_out = out_dev ? 0 : dn_align(out_bytes);
   const StagePlan plan = chunks(st_in + st_out);
   int rc = ctx_grow(c, &c->raw_dev, &c->raw_dev_bytes, (size_t)plan.per_chunk * (st_in + st_out));
@@ -422,6 +423,50 @@ int gpet_nlmeans_fast_images(gpet_ctx* c, const void* const* raw, int n_img, int
   return pre_stage(
       c, raw, out, n_img, pix, M, N, flags, st, [&](size_t staged) { return nlf_chunks(n_img, staged, np); },
       [&](const PreChunk& k) { return launch_nlfast(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, sp, np, k.ws); }, no_chunk_hook);
+}
+
+// Polar unwrap (gpet_polar_plan.h).  Extras: cx [n_centres] | cy [n_centres] | cos_t [n_theta] | sin_t [n_theta].  The one stage
+// whose results have another shape than its frames: out[g] is n_r x W.  One launch per chunk of the staging slot, no workspace;
+// frames and outputs both on the device take one launch per 65535 frames and no wait.
+int gpet_polar_images(gpet_ctx* c, const void* const* raw, int n_img, int pix, int M, int N, const gpet_polar* spec, unsigned int flags,
+                      void* const* out) {
+  if (!c || !raw || !spec || !out || n_img <= 0) return fail(c, GPET_ERR_BAD_ARG, "gpet_polar_images: bad argument");
+  PolarSpec sp;
+  sp.r0 = spec->r0;
+  sp.dr = spec->dr;
+  sp.n_r = spec->n_r;
+  sp.n_theta = spec->n_theta;
+  sp.pad = spec->pad;
+  const int nc = spec->n_centres;
+  if (const char* why = polar_check(sp, pix, M, N, nc, n_img, spec->cx, spec->cy))
+    return fail(c, GPET_ERR_BAD_ARG, "%s (n_r %d, n_theta %d, pad %d, r0 %g, dr %g, %d centres, %d frames of %d x %d)", why, sp.n_r, sp.n_theta,
+                sp.pad, sp.r0, sp.dr, nc, n_img, M, N);
+  if (!spec->cos_t || !spec->sin_t) return fail(c, GPET_ERR_BAD_ARG, "polar: the trig tables are a null pointer");
+  for (int g = 0; g < n_img; ++g)
+    if (!raw[g] || !out[g]) return fail(c, GPET_ERR_BAD_ARG, "gpet_polar_images: frame or output %d is a null pointer", g);
+  std::vector<double> ex((size_t)2 * nc + (size_t)2 * sp.n_theta);
+  memcpy(ex.data(), spec->cx, sizeof(double) * (size_t)nc);
+  memcpy(ex.data() + nc, spec->cy, sizeof(double) * (size_t)nc);
+  memcpy(ex.data() + 2 * (size_t)nc, spec->cos_t, sizeof(double) * (size_t)sp.n_theta);
+  memcpy(ex.data() + 2 * (size_t)nc + sp.n_theta, spec->sin_t, sizeof(double) * (size_t)sp.n_theta);
+  PreStage st;
+  st.out_dev_bit = GPET_POLAR_OUT_ON_DEVICE;
+  st.init = ex.data();
+  st.extras_bytes = st.init_bytes = sizeof(double) * ex.size();
+  st.out_px = (size_t)(polar_width(sp.n_theta, sp.pad) * sp.n_r);
+  return pre_stage(
+      c, raw, out, n_img, pix, M, N, flags, st,
+      [&](size_t staged) {
+        if (staged) return stage_plan_z(n_img, staged, STAGE_SLOT_BUDGET);
+        const int per = n_img < POLAR_CHUNK_MAX ? n_img : POLAR_CHUNK_MAX;
+        return StagePlan{per, (n_img + per - 1) / per, 0, 0};
+      },
+      [&](const PreChunk& k) {
+        const double* d_cxy = (const double*)k.d_extras;
+        return launch_polar(c->stream, pix, k.d_src, k.d_dst, k.first, k.cnt, M, N, sp, d_cxy, nc, d_cxy + 2 * (size_t)nc,
+                            d_cxy + 2 * (size_t)nc + sp.n_theta);
+      },
+      no_chunk_hook);
 }
 
 // Wavelet denoising (gpet_wavelet_plan.h).  Extras: sigma [n_img] | thresholds [n_img * levels * 3] | means of squares [the same].

@@ -249,6 +249,21 @@ hipError_t launch_nlfast(hipStream_t st, int pix, const void* const* d_src, doub
   }
   return hipGetLastError();
 }
+// ---- polar unwrap (gpet_k_polar.inc; the rule and the grid: gpet_polar_plan.h) ----
+hipError_t launch_polar(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                        const PolarSpec& sp, const double* d_cxy, int n_centres, const double* d_cos, const double* d_sin) {
+  (void)hipGetLastError();  // drop stale errors: report only this launch
+  if (n < 1 || n > POLAR_CHUNK_MAX || !pix_bytes(pix) || M < 2 || N < 2 || sp.n_r < 1 || sp.n_theta < POLAR_NTHETA_MIN || sp.pad < 0 ||
+      sp.pad > sp.n_theta || polar_width(sp.n_theta, sp.pad) > POLAR_CELLS_MAX / sp.n_r || n_centres < 1 || !d_cxy || !d_cos || !d_sin)
+    return hipErrorInvalidValue;
+  const int W = (int)polar_width(sp.n_theta, sp.pad);
+  for_pix(pix, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_polar<T>), dim3(polar_blocks(sp), 1, n), dim3(POLAR_THREADS), 0, st, (const T* const*)d_src, d_dst, img0, M, N, sp, W, d_cxy,
+                       n_centres, d_cos, d_sin);
+  });
+  return hipGetLastError();
+}
 // ---- a0: wavelet denoising (gpet_k_wavelet.inc; geometry: gpet_wavelet_plan.h) ----
 template <typename T>
 static void launch_wv_fwd1_t(hipStream_t st, const void* const* d_src, int img0, int n, char* ws, const WvPlan& p, double scale,

@@ -13,6 +13,7 @@
 #include "gpet_nlfast_plan.h"   // fast-mode non-local means: spec, shift table, groups, workspace, launch geometry
 #include "gpet_wavelet_plan.h"  // wavelet denoising: spec, levels, pyramid layout, tiles, the threshold's summation order
 #include "gpet_tvb_plan.h"      // split-Bregman TV denoising: spec, skewed workspace, workgroup, sweeps per launch, the order of acc
+#include "gpet_polar_plan.h"    // polar unwrap: spec, column-to-angle map, sample position, bilinear value, launch geometry
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 #include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
@@ -94,6 +95,11 @@ hipError_t launch_nlmeans(hipStream_t st, int pix, const void* const* d_src, dou
 // and one gather launch.  p: nlf_plan of the frames and the spec; ws: the chunk's n workspaces (p.frame_bytes apart)
 hipError_t launch_nlfast(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
                          const NlfSpec& sp, const NlfPlan& p, char* ws);
+// polar unwrap (gpet_polar_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix, M x N) -> the f64
+// frames [n_r x W] of the DEVICE pointer table d_dst at the same indices, one launch.  d_cxy: cx [n_centres] | cy [n_centres] on the
+// device, indexed by frame like the tables (n_centres 1: one centre for all); d_cos / d_sin: [n_theta] on the device
+hipError_t launch_polar(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
+                        const PolarSpec& sp, const double* d_cxy, int n_centres, const double* d_cos, const double* d_sin);
 // a0, wavelet denoising (gpet_wavelet_plan.h): frames img0 .. img0 + n - 1 of the DEVICE pointer table d_src (pixel type pix) -> the
 // f64 frames of the DEVICE pointer table d_dst at the same indices, 2 levels + 2 launches (one fewer with injected thresholds).  ws: the
 // chunk's n pyramids; d_sigma [frames], d_thr / d_ms [frames * levels * 3] on the device, indexed by frame like the tables -- with

@@ -23,6 +23,7 @@ namespace gpet {
 #include "gpet_k_nlfast.inc"
 #include "gpet_k_wavelet.inc"
 #include "gpet_k_tvb.inc"
+#include "gpet_k_polar.inc"
 #include "gpet_k_fit.inc"
 #include "gpet_k_factor.inc"
 #include "gpet_k_rng.inc"

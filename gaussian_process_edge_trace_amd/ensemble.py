@@ -46,7 +46,8 @@ def trace_ensemble(init, grad_img, seeds, tol=2, **ctor_kwargs):
     ``seeds`` (the members' seeds), ``medoid_seed`` and ``result``: the medoid member's own result as ``finish`` returns it (the
     trace, or (trace, credible interval) with ``return_std``) -- None if the device stopped every member.  One dict for one
     init, a list for a list of inits.  ``orientation='vertical'`` (a batch keyword): ``grad_img`` / the raw frame as it lies, ``init``
-    and every trace of the dict in the frame's coordinates, as the batch returns them."""
+    and every trace of the dict in the frame's coordinates, as the batch returns them.  ``polar=dict(...)`` (a batch keyword, with
+    ``raw_imgs``): a closed contour -- ``init`` (``gpet_utils.closed_init``) and every trace of the dict in polar rows and columns."""
     inits, multi = _inits_of(init)
     if not float(tol) >= 0.0:
         raise ValueError("tol must be >= 0 pixels, not %r" % (tol,))

@@ -429,7 +429,7 @@ def _raw_stack(raw_imgs):
 
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
                          raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None, band_rows=None, band_r0=None,
-                         inits=None, transposed=False):
+                         inits=None, transposed=False, polar=None):
     """What a batch's images come as, decided from the arguments alone (no device): a dict with ``kind`` ("grad" or "raw"),
     ``share`` (one image for all edges), ``shape`` (M, N) and the keyword arguments ``batch`` of ``_lib.Batch`` that carry the
     images.  Gradient images and raw frames are alternatives; raw frames need ``grad_kernel``; device pointers need their
@@ -444,7 +444,16 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
     the shape the edges' parameters are resolved for.  ``band_rows=None``: exactly the dict described above.
     ``transposed`` (a vertical batch): the images are (M, N) in the frame's layout -- ``shape`` says so -- and ``trace_shape`` is that
     of the transposed gradient image the batch traces, (N, M); a band is then H of its N rows (frame columns), ``trace_shape``
-    (H, M), and ``inits`` are in the batch's coordinates."""
+    (H, M), and ``inits`` are in the batch's coordinates.
+    ``polar`` (a dict as ``_lib.polar_spec`` takes it, or a PolarSpec; raw frames only, not with ``transposed``): the frames are
+    unwrapped to (radius x angle) first -- ``shape`` is the polar shape (n_r, W), the dict also has ``src_shape``, the frames' own, and
+    ``grad_shape`` of device frames is the frames' own.  ``polar=None``: exactly the dict described above."""
+    if polar is not None:
+        if transposed:
+            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
+                             "the unwrapped frame")
+        if raw_imgs is None and raw_device_ptrs is None:
+            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs with grad_kernel): gradient images are past that stage")
     if transposed:
         src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
                                    denoise, kernel_of=kernel_of, image_of=image_of)
@@ -461,7 +470,7 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
             raise ValueError("band_rows needs images: the full frames (raw_imgs / raw_device_ptrs with grad_kernel) or full-frame "
                              "gradient images (grad_imgs / grad_device_ptrs) the bands are cut from")
         src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
-                                   denoise, kernel_of=kernel_of, image_of=image_of)
+                                   denoise, kernel_of=kernel_of, image_of=image_of, polar=polar)
         src["band"] = resolve_bands(inits, src["shape"][0], band_rows, band_r0)
         src["trace_shape"] = (src["band"][0], src["shape"][1])
         return src
@@ -512,24 +521,25 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
             frame_of, kernel_of_slot, edge_slot = _lib.derive_slots(edge_frames, kernel_of)
             if raw_device_ptrs is not None:
                 raw = _lib.RawFrames(kernels, device_ptrs=frames, dtype=raw_dtype, shape=grad_shape, denoise=denoise,
-                                     slots=(frame_of, kernel_of_slot))
+                                     slots=(frame_of, kernel_of_slot), polar=polar)
             else:
-                raw = _lib.RawFrames(kernels, frames=frames, denoise=denoise, slots=(frame_of, kernel_of_slot))
+                raw = _lib.RawFrames(kernels, frames=frames, denoise=denoise, slots=(frame_of, kernel_of_slot), polar=polar)
             return dict(kind="raw", share=False, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
-                        batch=dict(grads=None, raw=raw), image_of=edge_slot, edge_frames=edge_frames)
+                        batch=dict(grads=None, raw=raw), image_of=edge_slot, edge_frames=edge_frames,
+                        **({} if polar is None else dict(src_shape=raw.src_shape)))
         if raw_device_ptrs is not None:
             if grad_shape is None or raw_dtype is None:
                 raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
             ptrs = _as_list(raw_device_ptrs)
-            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape, denoise=denoise)
+            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape, denoise=denoise, polar=polar)
             share = len(ptrs) == 1
         else:
             frames, share = _raw_stack(raw_imgs)
-            raw = _lib.RawFrames(grad_kernel, frames=frames, denoise=denoise)
+            raw = _lib.RawFrames(grad_kernel, frames=frames, denoise=denoise, polar=polar)
         if not share and len(raw) != n_edges:
             raise ValueError("%d raw frames for %d edges" % (len(raw), n_edges))
         return dict(kind="raw", share=share, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
-                    batch=dict(grads=None, raw=raw))
+                    batch=dict(grads=None, raw=raw), **({} if polar is None else dict(src_shape=raw.src_shape)))
     if grad_device_ptrs is not None:
         if grad_shape is None:
             raise ValueError("grad_device_ptrs need grad_shape = (M, N)")
@@ -694,13 +704,14 @@ class GP_Edge_Tracing_Batch(object):
     """
 
     orientation, _tr, _swap = "horizontal", False, False  # (what the constructor sets for orientation='vertical')
+    polar, _src_shape = None, None  # (what the constructor sets for polar=)
 
     def __init__(self, inits, grad_imgs, seeds, kernel_options=(1, 3, 3), noise_y=1, N_samples=500, score_thresh=1,
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
                  device=0, stream=None, factor_cap=0, z_cols=0, _ctx=None, grad_device_ptrs=None, grad_shape=None,
                  sample_dtype=None, rng=None, raw_imgs=None, grad_kernel=None, raw_device_ptrs=None, raw_dtype=None,
                  denoise=None, image_of=None, history=None, history_cap=64, kernel_of=None, band_rows=None, band_r0=None,
-                 init_follow=None, orientation="horizontal", _batch_coords=False):
+                 init_follow=None, orientation="horizontal", _batch_coords=False, polar=None):
         """``obs``: optional list of per-edge warm-start observation sets (xy), the reference's ``obs`` constructor
         argument (gpet.py:57-61,100,820).  ``grad_device_ptrs`` + ``grad_shape``: the gradient image(s) already live
         on this GPU (e.g. a torch tensor an RCCL broadcast filled): integer device addresses of f32 (M, N) arrays,
@@ -754,10 +765,22 @@ class GP_Edge_Tracing_Batch(object):
         ensemble's ``median``, ``q_lo``, ``q_hi``, ``min``, ``max`` are frame columns indexed by frame row.  Presets of
         ``kernel_options`` see the transposed image: its height is the frame's width, the edge length the row span.  ``band_rows=H``
         is a band of H frame COLUMNS with ``band_r0`` its first column; ``init_follow=dict(window=w, cols=a)`` searches w columns
-        left and right of a point, summing over a rows above and below: x moves, y never does."""
+        left and right of a point, summing over a rows above and below: x moves, y never does.
+        ``polar=dict(centre=(cx, cy) | (n_frames, 2) array, n_r=, n_theta=, r0=0.0, dr=1.0, theta0=0.0, pad=None)`` (raw frames only):
+        closed contours -- every frame is resampled on the device to (radius x angle) around its centre (``gpet_utils.unwrap_polar_imgs``;
+        the rule: csrc/gpet_polar_plan.h) before anything else happens to it, and the batch is, bit for bit, the batch on
+        ``unwrap_polar_imgs(frames, **polar)`` given as float64 frames.  ``inits``, ``obs``, traces, intervals, bands, ``history()`` and
+        ``ensemble()`` are in polar rows (radius ``r0 + row dr``) and columns (angle index ``(column - pad) mod n_theta``);
+        ``gpet_utils.closed_init(row, batch.polar)`` gives the two init points that close the contour, ``gpet_utils.polar_trace_xy`` maps
+        a result back to the frame.  ``pad=None``: half the width of the widest kernel.  ``polar`` (attribute) is the resolved spec;
+        ``grad_shape`` of ``raw_device_ptrs`` stays the frames' own shape.  ``set_frame`` keeps the spec; ``set_frame(...,
+        polar=dict(centre=...))`` replaces the centres.  Refused with gradient images and with ``orientation='vertical'``."""
         self.orientation = orientation
         self._tr = resolve_orientation(orientation)       # the library holds the transposed gradient images
         self._swap = self._tr and not _batch_coords       # ... and this object swaps the coordinates of what it takes and returns
+        if polar is not None and self._tr:  # (before the init points are looked at as those of a vertical edge)
+            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
+                             "the unwrapped frame")
         if self._swap:
             inits = vertical_inits(inits)
             obs = None if obs is None else [swap_xy(np.asarray(o).reshape(-1, 2)) for o in obs]
@@ -779,8 +802,10 @@ class GP_Edge_Tracing_Batch(object):
             raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
         src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
                                    raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of, band_rows=band_rows,
-                                   band_r0=band_r0, inits=None if band_rows is None else list(inits), transposed=self._tr)
+                                   band_r0=band_r0, inits=None if band_rows is None else list(inits), transposed=self._tr, polar=polar)
         self._denoise = denoise
+        self.polar = None if polar is None else src["batch"]["raw"].polar  # (resolved: pad known)
+        self._src_shape = src.get("src_shape")
         self.band_rows, self.band_r0 = (None, None) if band_rows is None else (src["band"][0], src["band"][1])
         # (a slot table: the kernels, the kernel and the frame of every edge are remembered for set_frame; the batch's own image
         #  map is then the edge-to-slot map)
@@ -885,7 +910,7 @@ class GP_Edge_Tracing_Batch(object):
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
                   raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None, warm_from=None,
-                  group_of=None, tol=2, band=None, init=None, init_follow=None):
+                  group_of=None, tol=2, band=None, init=None, init_follow=None, polar=None):
         """The next frame of an image sequence for the same edges (gpet.py:57-61: the previous trace warm-starts the
         next through ``obs``): new gradient image(s) -- host arrays, or device addresses with ``grad_device_ptrs`` --
         new warm-start observations and, optionally, new seeds.  Geometry, kernel and every other parameter stay, so
@@ -923,7 +948,11 @@ class GP_Edge_Tracing_Batch(object):
         ``'keep'``.  Bands are placed against the points as they are BEFORE this call; the search then stays inside the band.
         Whatever is refused raises ValueError before anything is touched.
         A vertical batch takes its frames and gradient images in the frame's layout, ``obs`` and ``init`` as (x, y) of the frame, and
-        ``band`` as first frame columns."""
+        ``band`` as first frame columns.
+        A polar batch unwraps the new frames by the constructor's spec; ``polar=dict(centre=...)`` replaces the centres from this frame
+        on (the whole dict may be given again: whatever would change the polar shape -- ``n_r``, ``n_theta``, ``pad`` -- or the radii
+        and angles behind the rows and columns -- ``r0``, ``dr``, ``theta0`` -- is refused with ValueError)."""
+        new_polar = self._frame_polar(polar, raw_imgs is not None or raw_device_ptrs is not None)
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
         if warm_from is not None:
@@ -970,20 +999,22 @@ class GP_Edge_Tracing_Batch(object):
             multi = self._kernel_of is not None
             n_img = self._n_frames if multi else b.n_img  # (frames expected)
             fshape = b.frame_shape  # (the frames as they lie: (frame_M, N), on a vertical batch (N, frame_M))
+            given_shape = fshape if self.polar is None else self._src_shape  # (device frames of a polar batch: the frames' own shape)
             if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
                 raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
             have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
             if not (n_img == 1 and np.ndim(have) == 2) and len(have) != n_img:
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % ((len(have), self._images_text()) + fshape))
-            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, fshape, raw_imgs, raw_device_ptrs,
+            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, given_shape, raw_imgs, raw_device_ptrs,
                                        self._raw_dtype if raw_dtype is None else raw_dtype, kern,
                                        None if denoise is False else (self._denoise if denoise is None else denoise),
-                                       kernel_of=self._kernel_of, image_of=self._edge_frames)
+                                       kernel_of=self._kernel_of, image_of=self._edge_frames, polar=new_polar)
             # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
             if len(src["batch"]["raw"]) != n_img or src["shape"] != fshape:
                 raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"
                                  % ((len(src["batch"]["raw"]), self._images_text()) + fshape))
             swap(raw=src["batch"]["raw"], next_frame=next_frame)
+            self.polar = new_polar
         elif grad_device_ptrs is not None:
             ptrs = _as_list(grad_device_ptrs)
             if len(ptrs) != self._batch.n_img:
@@ -1022,6 +1053,26 @@ class GP_Edge_Tracing_Batch(object):
             self.seeds = [int(v) for v in seeds]
         if warm_every is None:
             self._set_obs()
+
+    def _frame_polar(self, polar, have_raw):
+        """The spec ``set_frame`` unwraps the new frames with: the batch's own, or the one ``polar`` asks for when it keeps the shape and
+        the meaning of rows and columns.  ValueError for everything else, before anything is touched."""
+        if polar is None:
+            return self.polar
+        if self.polar is None:
+            raise ValueError("polar: this batch was not built on polar frames (give polar= to the constructor)")
+        if not have_raw:
+            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs): gradient images are past that stage")
+        if isinstance(polar, dict):
+            polar = dict(self.polar.as_dict(), **{k: v for k, v in polar.items() if not (k == "pad" and v is None)})
+        new = _lib.polar_spec(polar).resolved(self.polar.pad)
+        old = self.polar
+        if (new.n_r, new.n_theta, new.pad) != (old.n_r, old.n_theta, old.pad):
+            raise ValueError("polar: set_frame cannot change the shape of the polar frames: n_r, n_theta, pad are %d, %d, %d, not %d, %d, %d"
+                             % (old.n_r, old.n_theta, old.pad, new.n_r, new.n_theta, new.pad))
+        if (new.r0, new.dr, new.theta0) != (old.r0, old.dr, old.theta0):
+            raise ValueError("polar: set_frame replaces the centres only: r0, dr, theta0 are %r, %r, %r" % (old.r0, old.dr, old.theta0))
+        return new
 
     def warm_start_from(self, src_of, warm_every):
         """The explicit form of the device's warm start (gpet_batch_warm_start_from), where ``set_frame`` would make it -- after the

@@ -64,7 +64,7 @@ def comp_grad_img(img, kernel, norm=True, astyp=np.float32, ctx=None):
     return out.astype(astyp)
 
 
-def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None, transpose=False):
+def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None, transpose=False, polar=None):
     """``comp_grad_img`` of every frame of a stack in ONE batched GPU pass (gpet_grad_images): ``imgs`` is a (T, M, N) array
     or a sequence of (M, N) frames, the result a (T, M, N) float32 array whose frame t equals ``comp_grad_img(imgs[t],
     kernel)`` bit for bit.  uint8, uint16, float32 and float64 frames go to the device as they are (integer pixels mean their
@@ -77,25 +77,33 @@ def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None, transpose=False):
     (gpet_grad_images_multi).
     ``transpose=True``: the stage a vertical batch (``orientation='vertical'``) runs -- denoising and the kernel applied to the frames
     as they lie, every image stored transposed on the device: (T, N, M), or (T, n_kern, N, M), equal to the result without it with
-    the last two axes swapped, bit for bit."""
+    the last two axes swapped, bit for bit.
+    ``polar=dict(centre=, n_r=, n_theta=, ...)`` (``unwrap_polar_imgs``' arguments; ``pad=None``: half the widest kernel's width): the
+    frames are unwrapped to (radius x angle) on the device first -- the result equals the same call on
+    ``unwrap_polar_imgs(imgs, **polar)`` bit for bit, (T, n_r, W) or (T, n_kern, n_r, W).  Not with ``transpose``."""
+    if polar is not None and transpose:
+        raise ValueError("polar and transpose are alternatives: a closed contour is traced as a horizontal edge of the unwrapped frame")
     kernels, multi = _lib.split_kernels(kernel)
     if not multi:
-        raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise)  # (refuses a bad spec before a device is needed)
+        raw = _lib.RawFrames(kernel, frames=imgs, denoise=denoise, polar=polar)  # (refuses a bad spec before a device is needed)
         return (ctx or _ctx()).grad_images(raw, transpose)
     T, K = len(imgs), len(kernels)
-    raw = _lib.RawFrames(kernels, frames=imgs, denoise=denoise, slots=([t for t in range(T) for _ in range(K)], list(range(K)) * T))
+    raw = _lib.RawFrames(kernels, frames=imgs, denoise=denoise, slots=([t for t in range(T) for _ in range(K)], list(range(K)) * T),
+                         polar=polar)
     out = (ctx or _ctx()).grad_images(raw, transpose)
     return out.reshape((T, K) + out.shape[1:])
 
 
-def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False):
+def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False, polar=None):
     """``denoise`` of every frame of a stack in ONE batched GPU pass (gpet_denoise_images): ``imgs`` is a (T, M, N) array or a
     sequence of (M, N) frames of one dtype, the result a (T, M, N) array whose frame t equals ``denoise(imgs[t], technique,
     kwargs)`` bit for bit.  ``return_n_iter``: also the iterations 'tvc' ran per frame (0 for the filters).  'nl' with
     ``fast_mode=False``, 'nl_fast', 'wavelet' with the ``wavelet`` key and 'tvb' with ``weight`` are stages of their own
     (gpet_nlmeans_images, gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images): float64 frames whatever the frames' dtype; for 'tvb' ``return_n_iter`` gives the sweeps
-    every frame ran (0 for 'nl' and 'wavelet')."""
-    raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs))  # (refuses a bad spec before a device is needed)
+    every frame ran (0 for 'nl' and 'wavelet').
+    ``polar=dict(...)``: the frames are unwrapped to (radius x angle) first (``pad`` defaults to 0: there is no kernel) -- the result
+    equals ``denoise_imgs(unwrap_polar_imgs(imgs, **polar), technique, kwargs)`` bit for bit."""
+    raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs), polar=polar)  # (refuses a bad spec before a device is needed)
     out, n_iter = (ctx or _ctx()).denoise_images(raw)
     return (out, n_iter) if return_n_iter else out
 
@@ -204,3 +212,58 @@ def trace_dicecoef(edge_pred, edge_true, jaccard=False):
     tb = (rows >= edge_true[:, 0].astype(int)[None, :]).astype(float)
     jacc = np.sum(pb * tb) / np.sum(np.clip(pb + tb, 0, 1))
     return np.round(jacc, 4) if jaccard else np.round(2 * jacc / (jacc + 1), 4)
+
+
+# ---- closed contours: the polar unwrap (csrc/gpet_polar_plan.h) -----------------------------------------------------
+def unwrap_polar_imgs(frames, centre, n_r, n_theta, r0=0.0, dr=1.0, theta0=0.0, pad=0, ctx=None):
+    """Every frame of a stack resampled to (radius x angle) around ``centre`` in ONE batched GPU pass (gpet_polar_images):
+    ``frames`` is a (T, M, N) array or a sequence of (M, N) frames (uint8, uint16, float32 and float64 go to the device as they are),
+    ``centre`` = (cx, cy) -- x the column, y the row -- or a (T, 2) array with one centre per frame; the result is (T, n_r, W)
+    float64 with W = n_theta + 1 + 2 pad.  Row i is the radius ``r0 + i dr``; column c the angle ``theta0 + 2 pi a / n_theta`` with
+    a = (c - pad) mod n_theta, clockwise on the screen: columns ``pad`` and ``pad + n_theta`` are the same ray (the seam), and the
+    ``pad`` columns either side repeat the far end, so a filter sees periodic data there.  Bilinear, a ray that leaves the frame
+    repeats the border pixel; integer frames keep their range.  A closed, roughly star-shaped contour around the centre is a
+    horizontal edge of the result: trace it between ``closed_init(row, polar)``."""
+    raw = _lib.RawFrames(None, frames=frames, polar=dict(centre=centre, n_r=n_r, n_theta=n_theta, r0=r0, dr=dr, theta0=theta0, pad=pad))
+    return (ctx or _ctx()).polar_images(raw)
+
+
+def closed_init(row, polar):
+    """The two init points that close a contour traced on polar frames: ``[[pad, row], [pad + n_theta, row]]`` -- the same ray at
+    both ends of the traced columns, pinned to one radius row.  ``polar``: the dict (``pad`` given) or a resolved ``_lib.PolarSpec``."""
+    sp = _lib.polar_spec(polar)
+    if sp.pad is None:
+        raise ValueError("closed_init needs pad: give it in the dict, or pass the resolved spec (the tracing object's .polar)")
+    return np.array([[sp.pad, int(row)], [sp.pad + sp.n_theta, int(row)]], dtype=np.int64)
+
+
+def polar_to_xy(rows, cols, polar, frame=0, shape=None):
+    """Frame coordinates (x, y), float64, of the polar pixels (rows, cols) by the rule's own arithmetic (csrc/gpet_polar_plan.h):
+    rho = r0 + row dr; x = cx + rho cos_t[a]; y = cy + rho sin_t[a]; a = (col - pad) mod n_theta.  Host numpy.  ``rows`` may be
+    fractional (an interval curve).  ``frame``: whose centre, where there is one per frame.  ``shape`` = (M, N) of the frames: the
+    positions are clamped into the frame as the unwrap clamps them; without it they are the ray's own, which is the same wherever
+    the ray stays inside the frame."""
+    sp = _lib.polar_spec(polar)
+    if sp.pad is None:
+        raise ValueError("polar_to_xy needs pad: give it in the dict, or pass the resolved spec (the tracing object's .polar)")
+    rows, cols = np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.int64)
+    a = np.mod(cols - sp.pad, sp.n_theta)
+    cx, cy = sp.centre[0 if sp.centre.shape[0] == 1 else int(frame)]
+    rho = sp.r0 + rows * sp.dr
+    x, y = cx + rho * sp.cos_t[a], cy + rho * sp.sin_t[a]
+    if shape is not None:
+        x, y = np.minimum(np.maximum(x, 0.0), shape[1] - 1.0), np.minimum(np.maximum(y, 0.0), shape[0] - 1.0)
+    return x, y
+
+
+def polar_trace_xy(result, polar, frame=0):
+    """What a tracer returned on polar frames, in frame coordinates: a trace -- an (n, 2) array of (row, column) -- becomes an (n, 2)
+    float64 array of (x, y); with ``return_std`` the result is ``(trace, (lower, upper))`` and the two interval curves, radii rows
+    indexed like the trace, are mapped along the trace's rays: ``(xy, (xy_lower, xy_upper))``."""
+    if isinstance(result, tuple):
+        trace, (lower, upper) = result
+        cols = np.asarray(trace)[:, 1]
+        return (polar_trace_xy(trace, polar, frame), tuple(np.stack(polar_to_xy(np.asarray(c).reshape(-1), cols, polar, frame), axis=1)
+                                                           for c in (lower, upper)))
+    trace = np.asarray(result)
+    return np.stack(polar_to_xy(trace[:, 0], trace[:, 1], polar, frame), axis=1)

@@ -109,13 +109,18 @@ class SequenceTracer(object):
     ``orientation='vertical'``: the edges run down the frames (``GP_Edge_Tracing_Batch``) -- the sequence is, bit for bit, the
     horizontal one on the transposed gradient images with the coordinates of ``init`` swapped, and every result, ensemble dict and
     ``inits[t]`` comes back in the frame's coordinates.  The frames -- raw or gradient images -- are given as they lie; the transposes
-    are made on the device.  ``warm_start_obs`` is applied to the traces of the transposed images."""
+    are made on the device.  ``warm_start_obs`` is applied to the traces of the transposed images.
+
+    ``polar=dict(centre=(cx, cy) | (T, 2) array, n_r=, n_theta=, ...)`` with ``grad_kernel``: closed contours (``GP_Edge_Tracing_Batch``)
+    -- every frame is unwrapped to (radius x angle) on the device, around its own centre where ``centre`` has one per frame, and the
+    sequence is, bit for bit, the one on ``unwrap_polar_imgs(frames, **polar)``; ``init`` (``closed_init(row, polar)``), results and
+    everything else are in polar rows and columns.  ``polar`` (attribute) is the resolved spec.  Not with ``orientation='vertical'``."""
 
     _UNSET = object()
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
                  denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, init_follow=None,
-                 orientation="horizontal", **kw):
+                 orientation="horizontal", polar=None, **kw):
         if ensemble_seeds is not None:
             if seed is not SequenceTracer._UNSET or seeds is not None:
                 raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
@@ -135,6 +140,9 @@ class SequenceTracer(object):
         self.T = len(frames)
         self.orientation = orientation
         self._tr = resolve_orientation(orientation)
+        if polar is not None and self._tr:
+            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
+                             "the unwrapped frame")
         self._inits, self.multi = _inits_of(init)
         if not self._inits:
             raise ValueError("no init")
@@ -177,6 +185,16 @@ class SequenceTracer(object):
                                                            "keep_ratio", "pixel_thresh", "return_std", "fix_endpoints")}
         self.band_rows = None if band_rows is None else int(band_rows)
         shape = np.asarray(frames[0]).shape
+        # (closed contours: every step's batch unwraps its frames by this spec, around the centres of the step's frames; inits, traces
+        #  and everything else are in polar rows and columns)
+        self.polar = None
+        if polar is not None:
+            if grad_kernel is None:
+                raise ValueError("polar needs raw frames, i.e. grad_kernel")
+            self.polar = _lib.polar_spec(polar).resolved(_lib.polar_default_pad(split_kernels(grad_kernel)[0]))
+            if self.polar.centre.shape[0] not in (1, self.T):
+                raise ValueError("polar: %d centres for %d frames: one for all frames or one per frame" % (self.polar.centre.shape[0], self.T))
+            shape = self.polar.shape
         if self._tr:
             shape = (shape[1], shape[0])
         self._frame_M = int(shape[0])
@@ -224,6 +242,12 @@ class SequenceTracer(object):
         if t.size == 0:
             t = rows
         return _lib.band_place(self._frame_M, self.band_rows, int(t.min()), int(t.max()), i_lo, i_hi)
+
+    def _polar_of(self, active):
+        """The polar spec of a step's batch: the sequence's own, around the centres of the step's frames where there is one per frame."""
+        if self.polar is None or self.polar.centre.shape[0] == 1:
+            return self.polar
+        return self.polar.with_centre(self.polar.centre[[f for _, f in active]])
 
     def _frames_of_step(self, s):
         return [lo + s for lo, hi in self.chains if lo + s < hi]
@@ -330,6 +354,8 @@ class SequenceTracer(object):
                     images.update(band_rows=self.band_rows, band_r0=r0s)
                 if self.init_follow is not None:  # (remembered by the batch: its set_frame then follows by default)
                     images["init_follow"] = self.init_follow
+                if self.polar is not None:
+                    images["polar"] = self._polar_of(active)
                 self._tracer = GP_Edge_Tracing_Batch(tab["inits"], seeds=seeds, obs=obs, device=self.device, _ctx=self._ctx,
                                                      image_of=tab["image_of"], orientation=self.orientation, _batch_coords=self._tr,
                                                      **images, **self.kw)
@@ -339,6 +365,8 @@ class SequenceTracer(object):
                 warm = dict(warm_every=self.warm_every)
                 if ens:  # (the ensemble of the step before is reduced and kept on the device, then warm-starts every member)
                     warm.update(warm_from=self.warm_from, group_of=tab["group_of"], tol=self.ensemble_tol)
+                if self.polar is not None:
+                    warm["polar"] = self._polar_of(active)
                 if self.grad_kernel is None:
                     self._tracer.set_frame(imgs, None, seeds, **warm)
                 else:

@@ -363,6 +363,41 @@ typedef struct gpet_tvb {
  * of LDS), an unknown pix, a null spec, frame or output. */
 int gpet_tvb_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_tvb* spec, unsigned int flags,
                     void* const* out, int32_t* n_iter_out);
+/* ---- polar unwrap: closed contours as horizontal edges (no reference function: csrc/gpet_polar_plan.h defines the rule) -- */
+/* A frame resampled to (radius x angle) around a centre: a boundary that closes on itself, r(theta), becomes the edge y(x) the
+ * tracer follows.  The result of one frame is ONE f64 frame of n_r rows and W = n_theta + 1 + 2 pad columns:
+ *   column c     holds angle index a(c) = (c - pad) mod n_theta (non-negative): columns pad and pad + n_theta are the same ray --
+ *                the seam --, the pad columns either side repeat the far end, so filters see periodic data there
+ *   position     rho = r0 + i dr;  x = cx + rho cos_t[a];  y = cy + rho sin_t[a]  (x the column, y the row; one multiply and one
+ *                add each in f64, not contracted; positive angles run clockwise on the screen)
+ *   clamp        x into [0, N - 1], y into [0, M - 1]: a ray that leaves the frame repeats the border pixel
+ *   taps         x0 = min(floor(x), N - 2), fx = x - x0; y0, fy likewise
+ *   value        top = (1 - fx) p[y0, x0] + fx p[y0, x0 + 1]; bot the same on row y0 + 1; out = (1 - fy) top + fy bot, in this order;
+ *                u8 / u16 / f32 pixels widened exactly to f64 first (integer frames keep their range)
+ * cos_t / sin_t are cos and sin of theta0 + 2 pi j / n_theta, computed by the CALLER and taken as data: the device evaluates no
+ * trigonometric function.  (Added without a change of GPET_ABI_VERSION: the surface only grew.) */
+typedef struct gpet_polar {
+  const double* cx;    /* centres, columns: n_centres values (host) */
+  const double* cy;    /* centres, rows */
+  int32_t n_centres;   /* 1: one centre for all frames; else n_img, one per frame */
+  int32_t n_r;         /* rows of the result, at least 1 */
+  int32_t n_theta;     /* distinct angles, at least 4 */
+  int32_t pad;         /* periodic columns added on each side, 0 .. n_theta */
+  double r0;           /* radius of row 0, finite, at least 0 */
+  double dr;           /* radius step per row, finite, above 0 */
+  const double* cos_t; /* [n_theta] (host) */
+  const double* sin_t; /* [n_theta] (host) */
+} gpet_polar;
+/* out[] are DEVICE pointers (f64 [n_r * W] each) on the context's device */
+#define GPET_POLAR_OUT_ON_DEVICE 8u
+/* The polar unwrap of n_img frames [M*N] of pixel type pix: out[g] f64 [n_r * W] receives frame g.  Host frames and host outputs
+ * go through the staging slot in chunks, one launch per chunk.  flags: GPET_RAW_ON_DEVICE, GPET_POLAR_OUT_ON_DEVICE (with both,
+ * nothing is waited for).  GPET_ERR_BAD_ARG, gpet_last_error carrying polar_check's words, and nothing launched, for an unknown
+ * pix, a frame below 2 x 2, n_r < 1, n_theta < 4, pad outside [0, n_theta], r0 < 0, dr <= 0 or non-finite values, n_r * W above
+ * 2^28 (a result's bytes stay within 2^31), n_centres neither 1 nor n_img, a non-finite centre, and null centres, tables, frames
+ * or outputs. */
+int gpet_polar_images(gpet_ctx* ctx, const void* const* raw, int n_img, int pix, int M, int N, const gpet_polar* spec,
+                      unsigned int flags, void* const* out);
 /* gpet_utils.normalise(img, (0,1)) for an f32 image (gpet.py:97): out f32 [count] (host). */
 int gpet_normalise_f32(gpet_ctx* ctx, const float* img, size_t count, float* out);
 
