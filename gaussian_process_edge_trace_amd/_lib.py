@@ -19,7 +19,8 @@ OK, ERR_BAD_ARG, ERR_HIP, ERR_NOT_PD, ERR_ITER_CAP, ERR_RANK_CAP, ERR_UNSUPPORTE
 # gpet_buf
 (BUF_X_TRAIN, BUF_Y_TRAIN, BUF_CHOL, BUF_ALPHA, BUF_MEAN, BUF_STD, BUF_COV, BUF_FACTOR, BUF_EIGVALS, BUF_NORMALS,
  BUF_SAMPLES, BUF_COSTS, BUF_BEST_IDX, BUF_BEST_COSTS, BUF_SCALARS, BUF_OBS, BUF_KDE, BUF_GRAD_KDE, BUF_GRAD,
- BUF_NOISE_W, BUF_FIN_TRAIN, BUF_FIN_PAR, BUF_FIN_STARTS, BUF_FIN_OUT, BUF_KDE_TILES) = range(25)
+ BUF_NOISE_W, BUF_FIN_TRAIN, BUF_FIN_PAR, BUF_FIN_STARTS, BUF_FIN_OUT, BUF_KDE_TILES, BUF_STRUCT_Q0, BUF_STRUCT_LAM0,
+ BUF_STRUCT_H) = range(28)
 
 KERNEL_RBF, KERNEL_MATERN = 0, 1
 GRAD_ON_DEVICE = 1  # gpet_batch_create2 / gpet_batch_set_images flag: the gradient image pointers are device pointers
@@ -1736,7 +1737,8 @@ _DT = {BUF_X_TRAIN: np.float64, BUF_Y_TRAIN: np.float64, BUF_CHOL: np.float64, B
        BUF_EIGVALS: np.float64, BUF_NORMALS: np.float64, BUF_SAMPLES: np.float64, BUF_COSTS: np.float64,
        BUF_BEST_IDX: np.int32, BUF_BEST_COSTS: np.float64, BUF_OBS: np.int64, BUF_KDE: np.float32,
        BUF_GRAD_KDE: np.float32, BUF_GRAD: np.float32, BUF_NOISE_W: np.float64, BUF_FIN_TRAIN: np.float64,
-       BUF_FIN_PAR: np.float64, BUF_FIN_STARTS: np.float64, BUF_FIN_OUT: np.float64, BUF_KDE_TILES: np.int32}
+       BUF_FIN_PAR: np.float64, BUF_FIN_STARTS: np.float64, BUF_FIN_OUT: np.float64, BUF_KDE_TILES: np.int32,
+       BUF_STRUCT_Q0: np.float64, BUF_STRUCT_LAM0: np.float64, BUF_STRUCT_H: np.float64}
 
 
 class Batch:
@@ -1960,8 +1962,11 @@ class Batch:
                  BUF_BEST_COSTS: (inf["n_keep"],), BUF_OBS: (s.n_obs, 2), BUF_KDE: (self.M, self.N),
                  BUF_GRAD_KDE: (self.M, self.N), BUF_GRAD: (self.M, self.N), BUF_FIN_TRAIN: (3, inf["n_cap"]),
                  BUF_FIN_PAR: (12,), BUF_FIN_STARTS: (13, 3), BUF_FIN_OUT: (2, Lg),
-                 BUF_KDE_TILES: ((self.N + 15) // 16 + 1, 2)}[which]  # (the last row: the two u32 keys of the raw minimum / maximum)
+                 BUF_KDE_TILES: ((self.N + 15) // 16 + 1, 2),  # (the last row: the two u32 keys of the raw minimum / maximum)
+                 BUF_STRUCT_Q0: (inf["r0"], Lg), BUF_STRUCT_LAM0: (inf["r0"],), BUF_STRUCT_H: (inf["r0"], inf["r0"])}[which]
         out = np.zeros(shape, dtype=_DT[which])
+        if which in (BUF_STRUCT_Q0, BUF_STRUCT_LAM0, BUF_STRUCT_H) and not inf["structured"]:
+            out = np.zeros(1, dtype=np.float64)  # (the library refuses these on a batch that is not structured: let it say so)
         if out.size:
             self.ctx.check(self.lib.gpet_batch_read(self.h, e, which, out.ctypes.data, out.nbytes))
         return out

@@ -824,6 +824,17 @@ int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
       HIPCHK(c, gpet_wait(c->stream));
       return GPET_OK;
     }
+    case GPET_BUF_STRUCT_Q0: case GPET_BUF_STRUCT_LAM0: case GPET_BUF_STRUCT_H: {
+      if (!b->structured) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_read: buffer %d exists on a structured batch only", which);
+      const size_t r0 = (size_t)E.r0;
+      if (which == GPET_BUF_STRUCT_Q0) { src = E.Q0; avail = r0 * Lg * 8; break; }
+      if (which == GPET_BUF_STRUCT_LAM0) { src = E.lam0; avail = r0 * 8; break; }
+      // H: compact [r0][r0] out of E.C, whose rows have the stride r_cap
+      if (bytes < r0 * r0 * 8) return fail(c, GPET_ERR_BAD_ARG, "STRUCT_H read needs %zu bytes", r0 * r0 * 8);
+      HIPCHK(c, hipMemcpy2DAsync(dst, r0 * 8, E.C, (size_t)E.r_cap * 8, r0 * 8, r0, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, gpet_wait(c->stream));
+      return GPET_OK;
+    }
     case GPET_BUF_FIN_STARTS:
       if (!b->lb_starts) return fail(c, GPET_ERR_STATE, "no converged fit has run on this batch yet");
       src = b->lb_starts + (size_t)e * 39;

@@ -138,6 +138,11 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
   if (!b || !ms_per_rep || reps < 1) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   HIPCHK(c, hipSetDevice(c->device));
+  // 120-123 on a batch that has left the structured path (gpet_batch_set_obs with an off-grid observation clears b->structured;
+  // the edges keep structured = 1 and their basis): k_struct_H / k_structB_build would gather Q0[a * Lg + (x - x_st)] with the
+  // off-grid x outside the basis.  Refused before any launch
+  if (stage >= 120 && stage <= 123 && !b->structured)
+    return fail(c, GPET_ERR_BAD_ARG, "gpet_profile_stage: stage %d needs a structured batch (gpet_batch_info: structured)", stage);
   // 170: the in-place normaliser of the raw-frame path (k_normalise_f32_batch) over the batch's image slots, with the neutral pair
   // (min 0, max 1) in every slot of d_minmax -- (x - 0) / 1 leaves every bit of the images as it is
   float** d_slots = nullptr;

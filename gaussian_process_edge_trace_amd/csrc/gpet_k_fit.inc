@@ -581,9 +581,10 @@ __global__ void __launch_bounds__(256) k_chol_diag(EdgeDev* edges, int k0, int w
   chol_diag_body(E, sc, k0, with_inv);
 }
 
-// row blocks below the diagonal block by SUBSTITUTION (one row per lane of the first wave): the blocked objective of
-// the converged fits keeps it -- the optimiser visits nearly singular matrices (noise 1e-10 of the amplitude) where a
-// product with the explicit inverse of a diagonal block costs digits (2e-8 instead of 1e-9 relative on f = 1.2e8)
+// row blocks below the diagonal block by SUBSTITUTION (one row per lane of the first wave), for the loop's blocked fit and the
+// blocked objective of the converged fits alike.  A product with the explicit inverse of the diagonal block on the matrix cores
+// (k_chol_trsm, removed) costs digits where the block is nearly singular: the optimiser visits noise levels of 1e-10 of the
+// amplitude (2e-8 instead of 1e-9 relative on f = 1.2e8), and the loop's n == Lg sets have only the jitter on K's diagonal
 __global__ void __launch_bounds__(256) k_chol_trsm_sub(EdgeDev* edges, int k0) {
   const EdgeDev E = edges[blockIdx.y];
   const gpet_scalars* sc = E.sc;
@@ -602,59 +603,36 @@ __global__ void __launch_bounds__(256) k_chol_trsm_sub(EdgeDev* edges, int k0) {
     sA[i][j] = (i < rows) ? E.K[(size_t)(i0 + i) * ld + k0 + j] : 0.0;
   }
   __syncthreads();
-  if (tid < rows) {
-    for (int j = 0; j < nb; ++j) {
-      double acc = sA[tid][j];
-      for (int t = 0; t < j; ++t) acc -= sA[tid][t] * sL[j][t];
-      sA[tid][j] = acc / sL[j][j];
+  // in sub-blocks of 16 columns (as k_struct_H's substitution): (a) every thread takes (row, column of the sub-block) entries and
+  // subtracts the columns BEFORE the sub-block -- independent inner products, all four waves busy; (b) one lane per row finishes
+  // the sub-block's 16 columns.  An entry's terms are subtracted in ascending order either way: the bits of the one-lane-per-row
+  // loop over all 64 columns (2 016 dependent steps instead of 480)
+  for (int j0 = 0; j0 < nb; j0 += 16) {
+    if (j0 > 0) {
+      for (int o = tid; o < rows * 16; o += bs) {
+        const int i = o >> 4, j = j0 + (o & 15);
+        double acc = sA[i][j];
+        for (int t = 0; t < j0; ++t) acc -= sA[i][t] * sL[j][t];
+        sA[i][j] = acc;
+      }
+      __syncthreads();
     }
+    if (tid < rows) {
+      for (int j = j0; j < j0 + 16; ++j) {
+        double acc = sA[tid][j];
+        for (int t = j0; t < j; ++t) acc -= sA[tid][t] * sL[j][t];
+        sA[tid][j] = acc / sL[j][j];
+      }
+    }
+    __syncthreads();
   }
-  __syncthreads();
   for (int e = tid; e < rows * CB; e += bs) {
     const int i = e >> 6, j = e & 63;
     E.K[(size_t)(i0 + i) * ld + k0 + j] = sA[i][j];
   }
 }
 
-// row blocks below the diagonal block: X L_kk^T = A_ik, i.e. X = A_ik (L_kk^-1)^T on v_mfma_f64_16x16x4_f64
-// (A lane l <- A[16 w + (l & 15)][kk + (l >> 4)], B lane l <- Linv[16 t + (l & 15)][kk + (l >> 4)])
 typedef double v4f64c __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(256) k_chol_trsm(EdgeDev* edges, int k0) {
-  const EdgeDev E = edges[blockIdx.y];
-  const gpet_scalars* sc = E.sc;
-  if ((sc->done && !sc->force) || sc->status != GPET_OK) return;
-  const int n = sc->n, ld = E.n_cap;
-  const int i0 = k0 + CB * ((int)blockIdx.x + 1);
-  if (i0 >= n) return;
-  const int rows = (n - i0) < CB ? (n - i0) : CB;
-  __shared__ double sL[CB][CB + 1];
-  __shared__ double sA[CB][CB + 1];
-  const int tid = threadIdx.x, bs = blockDim.x;
-  const double* inv = E.chol_inv + (size_t)(k0 / CB) * CB * CB;
-  for (int e = tid; e < CB * CB; e += bs) {
-    const int i = e >> 6, j = e & 63;
-    sL[i][j] = inv[e];
-    sA[i][j] = (i < rows) ? E.K[(size_t)(i0 + i) * ld + k0 + j] : 0.0;
-  }
-  __syncthreads();
-  const int lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
-  v4f64c acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = (v4f64c){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int kk = 0; kk < CB; kk += 4) {
-    const double a = sA[16 * w + li][kk + lq];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sL[16 * t + li][kk + lq], acc[t], 0, 0, 0);
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int i = 16 * w + lq + 4 * g, j = 16 * t + li;
-      if (i < rows) E.K[(size_t)(i0 + i) * ld + k0 + j] = acc[t][g];
-    }
-}
 
 // trailing update A_ij -= X_i X_j^T for the 64x64 tiles (bj <= bi) behind panel k0, v_mfma_f64_16x16x4_f64
 // next_diag: the workgroup of the first tile then factors it (the diagonal block of the next panel, with its inverse)
@@ -954,7 +932,10 @@ static void launch_fit_blocked(hipStream_t st, EdgeDev* d_edges, int B, const Ba
     if (k0 == 0 || !diag_in_syrk) hipLaunchKernelGGL(k_chol_diag, dim3(1, B), dim3(256), 0, st, d_edges, k0, 1);
     const int below = cdiv(bd.n_cap - k0 - CB, CB);
     if (below > 0) {
-      hipLaunchKernelGGL(k_chol_trsm, dim3(below, B), dim3(256), 0, st, d_edges, k0);
+      // (by substitution: on n == Lg sets, where K is the jitter away from singular and a 64-column diagonal block has a
+      //  condition number of 1e7, the product with the block's explicit inverse left |L L^T - K| at 1.41 times the
+      //  factorisation's backward error bound -- tests/test_gpu_struct_injected.py, full130)
+      hipLaunchKernelGGL(k_chol_trsm_sub, dim3(below, B), dim3(256), 0, st, d_edges, k0);
       hipLaunchKernelGGL(k_chol_syrk, dim3(below, below, B), dim3(256), 0, st, d_edges, k0, diag_in_syrk);
     }
   }

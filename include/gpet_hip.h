@@ -102,10 +102,19 @@ typedef enum gpet_buf {
                            *                gpet_batch_warm_start read.  Writable (tests inject fits no scene produces): exactly
                            *                2 * Lg * 8 bytes; a write changes no state flag, so a record or a warm start after it
                            *                reads the written values where the last converged fit allowed one */
-  GPET_BUF_KDE_TILES = 24 /* i32 [ceil(N/16) + 1][2]  what the fused curve KDE left beside GPET_BUF_KDE: per 16-column tile the
+  GPET_BUF_KDE_TILES = 24, /* i32 [ceil(N/16) + 1][2]  what the fused curve KDE left beside GPET_BUF_KDE: per 16-column tile the
                            *                first and last image row of its band (written by the loop's form only,
                            *                gpet_select_pixels_loop / gpet_trace_iterate; (M, -1): no band), then the ordered
                            *                keys of the raw density's minimum and maximum as two u32.  Read only (tests) */
+  /* What the structured loop path (prior eigenbasis of the pixel grid) keeps.  Read only (tests); gpet_batch_read refuses them
+   * with GPET_ERR_BAD_ARG on a batch that is not structured (gpet_batch_info: structured == 0, at creation or after an
+   * off-grid observation).  r0 is gpet_batch_info's. */
+  GPET_BUF_STRUCT_Q0 = 25,   /* f64 [r0][Lg]  unit eigenvectors of the grid's unit-amplitude correlation matrix, fixed at creation */
+  GPET_BUF_STRUCT_LAM0 = 26, /* f64 [r0]      their eigenvalues */
+  GPET_BUF_STRUCT_H = 27     /* f64 [r0][r0]  H = amp * diag(lam0) - U^T U of the current observation set, compact (on the device its
+                              *                rows have the factor capacity's stride).  Valid after stage 121 of gpet_profile_stage
+                              *                and before stage 122 only: the eigen-decomposition's warm start rotates it in place,
+                              *                so after stage 122 or a loop iteration its contents are unspecified */
 } gpet_buf;
 
 /* Per-edge scalar state kept on the device (GPET_BUF_SCALARS). */

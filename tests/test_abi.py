@@ -52,6 +52,31 @@ def test_struct_layouts_match_the_header(tmp_path):
                    S.n.offset, S.done.offset]
 
 
+def test_buffer_ids_match_the_header(tmp_path):
+    """Every GPET_BUF_* of the header against the ctypes side's BUF_*: the same names, the same values, none missing on either
+    side; the ids up to GPET_BUF_KDE_TILES = 24 stay where they were, the structured path's three views follow them, and
+    INTEGRATION.md names the three with the window in which H is valid."""
+    import subprocess
+    from gaussian_process_edge_trace_amd import _lib
+    text = open(os.path.join(ROOT, "include", "gpet_hip.h")).read()
+    names = re.findall(r"^\s*(GPET_BUF_[A-Z0-9_]+)\s*=", text, flags=re.M)
+    prog = tmp_path / "bufs.c"
+    prog.write_text('#include <stdio.h>\n#include "gpet_hip.h"\nint main(void){' +
+                    "".join('printf("%s %%d\\n", (int)%s);' % (n, n) for n in names) + "return 0;}\n")
+    exe = tmp_path / "bufs"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
+    got = dict((k, int(v)) for k, v in (ln.split() for ln in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()))
+    mine = {"GPET_" + k: v for k, v in vars(_lib).items() if k.startswith("BUF_")}
+    assert got == mine
+    assert sorted(got.values()) == list(range(28))
+    assert (got["GPET_BUF_KDE_TILES"], got["GPET_BUF_STRUCT_Q0"], got["GPET_BUF_STRUCT_LAM0"], got["GPET_BUF_STRUCT_H"]) == (24, 25, 26, 27)
+    assert all(v in _lib._DT for k, v in mine.items() if k != "GPET_BUF_SCALARS")
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for n in ("GPET_BUF_STRUCT_Q0", "GPET_BUF_STRUCT_LAM0", "GPET_BUF_STRUCT_H"):
+        assert "`%s`" % n in doc, n
+    assert "after stage 121" in doc and "before stage 122" in doc
+
+
 def test_no_gpu_fails_loudly_without_fallback():
     """Without a HIP device the product refuses to run (no CPU path)."""
     import torch

@@ -9,7 +9,7 @@ n_init + obs_cap, never by the count n (tests/test_iter_plan.py holds the table'
 
   n_cap <= 128 (64, 127, 128)        fit: k_fit<true, .>, K in LDS, 4 x 4 register tiles, the solves by one wave
                                      predict: k_predict<true, .>, a wave's 64 columns of V in LDS
-  129 .. 286 (129, 200, 285, 286)    fit: blocked in HBM by CB = 64 -- k_fit_head, k_fit_kbuild, per panel k_chol_diag / k_chol_trsm /
+  129 .. 286 (129, 200, 285, 286)    fit: blocked in HBM by CB = 64 -- k_fit_head, k_fit_kbuild, per panel k_chol_diag / k_chol_trsm_sub /
                                      k_chol_syrk (which factors the next diagonal block), k_chol_solve_mw<.> or k_chol_solve -- in
                                      the loop; k_fit<false, true>, left-looking in HBM, for the converged fit
                                      predict: still k_predict<true, .> ((64 n_cap + 3 n_cap) * 8 <= 150 KB of LDS up to 286)
