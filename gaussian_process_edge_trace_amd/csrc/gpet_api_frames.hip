@@ -147,11 +147,10 @@ int conv_frames(gpet_ctx* c, const RawSource& s, float* const* dst, unsigned int
   // (tr: the transposed-store forms -- the image at dst[g] is then N x M; the element-wise normaliser below does not care)
   auto convolve = [&](int p, const void* const* from, int first, int cnt) {
     if (multi)
-      return (tr ? launch_conv_multi_tr : launch_conv_multi)(c->stream, p, from, first, cnt, M, N, d_wf, cu,
-                                                             (const ConvKernDesc*)(c->raw_tab + o_kd), (const int32_t*)(c->raw_tab + o_so),
-                                                             (const int32_t*)(c->raw_tab + o_sl), (const int32_t*)(c->raw_tab + o_ko), d_dst,
-                                                             d_mm);
-    return (tr ? launch_conv_batch_tr : launch_conv_batch)(c->stream, p, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
+      return launch_conv_multi(c->stream, p, tr, from, first, cnt, M, N, d_wf, cu, (const ConvKernDesc*)(c->raw_tab + o_kd),
+                               (const int32_t*)(c->raw_tab + o_so), (const int32_t*)(c->raw_tab + o_sl),
+                               (const int32_t*)(c->raw_tab + o_ko), d_dst, d_mm);
+    return launch_conv_batch(c->stream, p, tr, from, first, cnt, M, N, d_wf, kh, kw, d_dst, d_mm);
   };
   if (on_dev && !dn_on) {
     HIPCHK(c, convolve(pix, d_src, 0, n_fr));

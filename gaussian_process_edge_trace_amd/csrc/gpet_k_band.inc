@@ -80,15 +80,7 @@ __global__ void k_band_minmax(const float* const* __restrict__ G_of, const long 
     kmin = min(kmin, k);
     kmax = max(kmax, k);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&minmax[2 * (size_t)e], kmin);
-    atomicMax(&minmax[2 * (size_t)e + 1], kmax);
-  }
+  wave_minmax_commit(kmin, kmax, threadIdx.x, &minmax[2 * (size_t)e], &minmax[2 * (size_t)e + 1]);
 }
 
 // Part 2: k_normalise_f32 of the same band into the edge's own image slot (EdgeDev::grad, H x N in the arena) -- the re-normalisation an
@@ -101,10 +93,8 @@ __global__ void k_band_normalise(const EdgeDev* __restrict__ edges, const float*
   const float mn = f32_from_key(minmax[2 * (size_t)e]);
   const float mx = f32_from_key(minmax[2 * (size_t)e + 1]);
   const float span = mx - mn;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-    const float a = in[i] - mn;
-    out[i] = a / span;
-  }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = f32_min_span(in[i], mn, span);
 }
 
 hipError_t launch_band_place(hipStream_t st, const EdgeDev* d_edges, int B, const int32_t* d_src, const int32_t* d_group_of, const char* d_kept,

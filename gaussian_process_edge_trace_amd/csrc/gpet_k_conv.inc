@@ -11,60 +11,181 @@ __device__ __forceinline__ float f32_from_key(unsigned int k) {
   unsigned int u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
   return __uint_as_float(u);
 }
-
-// (a workgroup of 64 x 4 threads owns 64 columns x 16 rows of the output; its (16 + kh - 1) x (64 + kw - 1) patch of the
-//  edge-replicated image goes through LDS once -- every thread fetching its kh kw taps from global memory took 1.5 ms per
-//  2048 x 2048 image; the products and their order are unchanged)
-#define CONV_RY 16
-__global__ void k_conv_relu(const double* __restrict__ img, int M, int N, const double* __restrict__ wf,
-                            int kh, int kw, int oy, int ox, float* __restrict__ out, unsigned int* minmax) {
-#pragma clang fp contract(off)
-  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch [CONV_RY + kh - 1][64 + kw - 1]
-  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
-  for (int i = tid; i < kh * kw; i += nthr) s_w[i] = wf[i];
-  const int pw = 64 + kw - 1, ph = CONV_RY + kh - 1;
-  double* s_p = s_w + kh * kw;
-  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * CONV_RY;
-  for (int e = tid; e < pw * ph; e += nthr) {
-    const int py = e / pw, px = e - py * pw;
-    int ry = y0 + py - oy, rx = x0 + px - ox;
-    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
-    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
-    s_p[e] = img[(size_t)ry * N + rx];
-  }
-  __syncthreads();
-  const int x = x0 + threadIdx.x;
-  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
-  for (int yl = threadIdx.y; yl < CONV_RY; yl += blockDim.y) {
-    const int y = y0 + yl;
-    if (x < N && y < M) {
-      double acc = 0.0;
-      for (int a = 0; a < kh; ++a) {
-        const double* row = s_p + (yl + a) * pw + threadIdx.x;
-        for (int b = 0; b < kw; ++b) {
-          const double w = s_w[a * kw + b];
-          if (w == 0.0) continue;
-          acc = acc + row[b] * w;
-        }
-      }
-      if (acc < 0.0) acc = 0.0;
-      const float v = (float)acc;
-      out[(size_t)y * N + x] = v;
-      const unsigned int key = f32_order_key(v);
-      kmin = min(kmin, key);
-      kmax = max(kmax, key);
-    }
-  }
-  // workgroup min/max -> one atomic pair per wave
+// a thread's order-key (min, max) -> the wave's, then one atomic pair per wave (lane_id: any index whose low six bits are the lane)
+__device__ __forceinline__ void wave_minmax_commit(unsigned int kmin, unsigned int kmax, unsigned int lane_id, unsigned int* pmin,
+                                                   unsigned int* pmax) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
     kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
   }
-  if ((tid & 63) == 0) {
-    atomicMin(&minmax[0], kmin);
-    atomicMax(&minmax[1], kmax);
+  if ((lane_id & 63) == 0) {
+    atomicMin(pmin, kmin);
+    atomicMax(pmax, kmax);
   }
+}
+// gpet_utils.py:84-89 in float32:  a = x - min;  a /= max(a);  (x1, +0 are no-ops) -- two operations, each rounded
+__device__ __forceinline__ float f32_min_span(float v, float mn, float span) {
+  const float a = v - mn;
+  return a / span;
+}
+
+// ---------------------------------------------------------------------------------------
+// The convolution has five entry points -- one f64 image (k_conv_relu), a stack of frames of pixel type T (k_conv_relu_batch), several
+// kernels on shared frames (k_conv_relu_multi; the table: gpet_conv_multi_plan.h), and the two transposed-store forms of vertical
+// batches (k_conv_tr_batch, k_conv_tr_multi; geometry: gpet_transpose_plan.h) -- and ONE body: conv_load, a barrier, conv_slot.  Per
+// pixel the products, their order, the skipped zero taps, the clamp, the cast and the order key are therefore the same in all five, and
+// so are an image's bits and its (min, max) pair, whichever form computed it.
+//
+// A workgroup of 64 x 4 threads owns a tile of one image's output.  Its edge-replicated patch goes through LDS once -- every thread
+// fetching its kh kw taps from global memory took 1.5 ms per 2048 x 2048 image -- as f64, whatever T is (exact for u8, u16, f32), which
+// keeps the LDS reads of the tap loop 8 bytes wide.  The patch load reads the image along its rows: consecutive lanes read consecutive
+// pixels of a patch row (one or two cache lines of u8, nine of f64), and each image is read once.
+//
+// What differs between the row-major and the turned tile is the layout policy L:
+//   ConvRows   64 columns x 16 rows; threadIdx.x is the column, threadIdx.y walks the rows; the patch lies row-major at pitch pw; pixel
+//              (y, x) is stored at y * N + x.
+//   ConvTurned 16 frame columns x 64 frame rows; threadIdx.x is the ROW, threadIdx.y walks the columns; pixel (y, x) is stored at
+//              x * M + y of the N x M image, so the 64 lanes of a wave write 64 consecutive floats.  The patch lies in LDS TRANSPOSED,
+//              pw columns of ph pixels at an odd pitch, so that the lanes of a tap read (one patch row apart) are consecutive doubles
+//              as they are under ConvRows; the few writes of the patch load are the strided ones, and the odd pitch spreads them over
+//              the banks.
+// ---------------------------------------------------------------------------------------
+#define CONV_RY 16
+struct ConvRows {
+  static constexpr int TILE_X = 64, TILE_Y = CONV_RY, SPAN = CONV_RY;  // SPAN: what threadIdx.y walks
+  static __device__ __forceinline__ int x0() { return blockIdx.x * 64; }
+  static __device__ __forceinline__ int y0() { return blockIdx.y * CONV_RY; }
+  static __device__ __forceinline__ int yl(int j) { return j; }
+  static __device__ __forceinline__ int xl(int) { return threadIdx.x; }
+  static __device__ __forceinline__ int pitch(int, int pw) { return pw; }
+  static __device__ __forceinline__ int cell(int py, int px, int pitch) { return py * pitch + px; }
+  static __device__ __forceinline__ int tap_step(int) { return 1; }  // doubles from tap b to tap b + 1
+  static __device__ __forceinline__ size_t out_offset(int y, int x, int, int N) { return (size_t)y * N + x; }
+};
+struct ConvTurned {
+  static constexpr int TILE_X = CONV_T_TILE_X, TILE_Y = CONV_T_TILE_Y, SPAN = CONV_T_TILE_X;
+  static __device__ __forceinline__ int x0() { return conv_t_col(blockIdx.x, 0); }
+  static __device__ __forceinline__ int y0() { return conv_t_row(blockIdx.y, 0); }
+  static __device__ __forceinline__ int yl(int) { return threadIdx.x; }
+  static __device__ __forceinline__ int xl(int j) { return j; }
+  static __device__ __forceinline__ int pitch(int ph, int) { return conv_t_pitch(ph); }
+  static __device__ __forceinline__ int cell(int py, int px, int pitch) { return px * pitch + py; }
+  static __device__ __forceinline__ int tap_step(int pitch) { return pitch; }
+  static __device__ __forceinline__ size_t out_offset(int y, int x, int M, int) { return tr_offset(y, x, M); }
+};
+
+// The n_taps taps at wf into s_w, and behind them the ph x pw patch of img whose cell (0, 0) is pixel (y0 - top, x0 - left), clamped
+// to the image, as f64 in L's layout.  Returns the patch; the caller's barrier follows.
+template <typename L, typename T>
+__device__ __forceinline__ const double* conv_load(double* s_w, const double* __restrict__ wf, int n_taps, const T* __restrict__ img, int M,
+                                                   int N, int top, int left, int ph, int pw) {
+  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
+  for (int i = tid; i < n_taps; i += nthr) s_w[i] = wf[i];
+  double* s_p = s_w + n_taps;
+  const int x0 = L::x0(), y0 = L::y0(), pitch = L::pitch(ph, pw);
+  for (int e = tid; e < pw * ph; e += nthr) {
+    const int py = e / pw, px = e - py * pw;
+    int ry = y0 + py - top, rx = x0 + px - left;
+    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
+    s_p[L::cell(py, px, pitch)] = (double)img[(size_t)ry * N + rx];
+  }
+  return s_p;
+}
+
+// One kernel's image of the workgroup's tile out of the patch: taps w [kh][kw], tap (0, 0) at (dy, dx) of the output pixel's patch
+// cell; clamp, f32 cast, store, and the tile's order-key (min, max) into mm[0], mm[1] with one atomic pair per wave.
+template <typename L>
+__device__ __forceinline__ void conv_slot(const double* s_p, int pitch, const double* w, int kh, int kw, int dy, int dx, int M, int N,
+                                          float* __restrict__ out, unsigned int* mm) {
+#pragma clang fp contract(off)
+  const int x0 = L::x0(), y0 = L::y0(), step = L::tap_step(pitch);
+  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
+  for (int j = threadIdx.y; j < L::SPAN; j += blockDim.y) {
+    const int yl = L::yl(j), xl = L::xl(j), y = y0 + yl, x = x0 + xl;
+    if (x < N && y < M) {
+      double acc = 0.0;
+      for (int a = 0; a < kh; ++a) {
+        const double* row = s_p + L::cell(yl + a + dy, xl + dx, pitch);
+        for (int b = 0; b < kw; ++b) {
+          const double wt = w[a * kw + b];
+          if (wt == 0.0) continue;
+          acc = acc + row[b * step] * wt;
+        }
+      }
+      if (acc < 0.0) acc = 0.0;
+      const float v = (float)acc;
+      out[L::out_offset(y, x, M, N)] = v;
+      const unsigned int key = f32_order_key(v);
+      kmin = min(kmin, key);
+      kmax = max(kmax, key);
+    }
+  }
+  wave_minmax_commit(kmin, kmax, threadIdx.x + threadIdx.y * blockDim.x, mm, mm + 1);
+}
+
+// one kernel on one image: the image's patch, then its one slot with the whole tap array
+template <typename L, typename T>
+__device__ __forceinline__ void conv_single(const T* __restrict__ img, int M, int N, const double* __restrict__ wf, int kh, int kw, int oy,
+                                            int ox, float* __restrict__ out, unsigned int* mm) {
+  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch
+  const int ph = L::TILE_Y + kh - 1, pw = L::TILE_X + kw - 1;
+  const double* s_p = conv_load<L>(s_w, wf, kh * kw, img, M, N, oy, ox, ph, pw);
+  __syncthreads();
+  conv_slot<L>(s_p, L::pitch(ph, pw), s_w, kh, kw, 0, 0, M, N, out, mm);
+}
+// blockIdx.z is a FRAME: the union patch of all kernels and their flipped taps, loaded once, then every slot of the frame out of it --
+// slot g's kernel k reads patch row yl + a + kd[k].dy, column xl + b + kd[k].dx for its tap (a, b), the pixel the single-kernel form
+// reads for it.  (min, max) per slot.
+template <typename L, typename T>
+__device__ __forceinline__ void conv_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf,
+                                           int n_taps, const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
+                                           const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
+                                           const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
+  extern __shared__ double s_w[];  // [n_taps] taps of all kernels, then the union patch
+  const int f = frame0 + blockIdx.z;
+  const double* s_p = conv_load<L>(s_w, wf, n_taps, src[f], M, N, top, left, ph, pw);
+  __syncthreads();
+  for (int si = slot_off[f]; si < slot_off[f + 1]; ++si) {
+    const int g = slot_list[si];
+    const ConvKernDesc K = kd[kernel_of[g]];
+    conv_slot<L>(s_p, L::pitch(ph, pw), s_w + K.w0, K.kh, K.kw, K.dy, K.dx, M, N, dst[g], minmax + 2 * (size_t)g);
+  }
+}
+
+__global__ void k_conv_relu(const double* __restrict__ img, int M, int N, const double* __restrict__ wf,
+                            int kh, int kw, int oy, int ox, float* __restrict__ out, unsigned int* minmax) {
+  conv_single<ConvRows>(img, M, N, wf, kh, kw, oy, ox, out, minmax);
+}
+// image img0 + blockIdx.z of a stack (gpet_grad_images, gpet_batch_create_raw, gpet_batch_set_raw_images), into the image's own
+// (min, max) slot
+template <typename T>
+__global__ void k_conv_relu_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
+                                  int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
+  const int g = img0 + blockIdx.z;
+  conv_single<ConvRows>(src[g], M, N, wf, kh, kw, oy, ox, dst[g], minmax + 2 * (size_t)g);
+}
+template <typename T>
+__global__ void k_conv_tr_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
+                                    int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
+  const int g = img0 + blockIdx.z;
+  conv_single<ConvTurned>(src[g], M, N, wf, kh, kw, oy, ox, dst[g], minmax + 2 * (size_t)g);
+}
+// (gpet_grad_images_multi, gpet_batch_create_raw_multi, gpet_batch_set_raw_images_multi)
+template <typename T>
+__global__ void k_conv_relu_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
+                                  const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
+                                  const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
+                                  const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
+  conv_multi<ConvRows>(src, frame0, M, N, wf, n_taps, kd, top, left, ph, pw, slot_off, slot_list, kernel_of, dst, minmax);
+}
+template <typename T>
+__global__ void k_conv_tr_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
+                                    const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
+                                    const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
+                                    const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
+  conv_multi<ConvTurned>(src, frame0, M, N, wf, n_taps, kd, top, left, ph, pw, slot_off, slot_list, kernel_of, dst, minmax);
 }
 
 __global__ void k_minmax_f32(const float* __restrict__ in, size_t count, unsigned int* minmax) {
@@ -74,90 +195,16 @@ __global__ void k_minmax_f32(const float* __restrict__ in, size_t count, unsigne
     kmin = min(kmin, k);
     kmax = max(kmax, k);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&minmax[0], kmin);
-    atomicMax(&minmax[1], kmax);
-  }
+  wave_minmax_commit(kmin, kmax, threadIdx.x, &minmax[0], &minmax[1]);
 }
 
-// gpet_utils.py:84-89 in float32:  a = x - min;  a /= max(a);  (x1, +0 are no-ops)
 __global__ void k_normalise_f32(const float* __restrict__ in, size_t count, const unsigned int* minmax,
                                 float* __restrict__ out) {
   const float mn = f32_from_key(minmax[0]);
   const float mx = f32_from_key(minmax[1]);
   const float span = mx - mn;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-    const float a = in[i] - mn;
-    out[i] = a / span;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// a1, batched: raw frames -> gradient images of a whole batch (gpet_grad_images, gpet_batch_create_raw,
-//     gpet_batch_set_raw_images).  k_conv_relu for image img0 + blockIdx.z of a stack: pixels of type T become f64 on their
-//     way into the LDS patch (exact for u8, u16, f32), then the same taps in the same order, the same clamp, cast and
-//     order-key min/max -- into the image's own (min, max) slot.  The patch load is k_conv_relu's: consecutive lanes read
-//     consecutive pixels of a patch row (64 + kw - 1 of them: one or two cache lines of u8, nine of f64), each image is read
-//     once, and the f64 patch keeps the LDS reads of the tap loop 8 bytes wide whatever T is.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ void k_conv_relu_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
-                                  int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
-#pragma clang fp contract(off)
-  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch [CONV_RY + kh - 1][64 + kw - 1]
-  const int g = img0 + blockIdx.z;
-  const T* __restrict__ img = src[g];
-  float* __restrict__ out = dst[g];
-  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
-  for (int i = tid; i < kh * kw; i += nthr) s_w[i] = wf[i];
-  const int pw = 64 + kw - 1, ph = CONV_RY + kh - 1;
-  double* s_p = s_w + kh * kw;
-  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * CONV_RY;
-  for (int e = tid; e < pw * ph; e += nthr) {
-    const int py = e / pw, px = e - py * pw;
-    int ry = y0 + py - oy, rx = x0 + px - ox;
-    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
-    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
-    s_p[e] = (double)img[(size_t)ry * N + rx];
-  }
-  __syncthreads();
-  const int x = x0 + threadIdx.x;
-  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
-  for (int yl = threadIdx.y; yl < CONV_RY; yl += blockDim.y) {
-    const int y = y0 + yl;
-    if (x < N && y < M) {
-      double acc = 0.0;
-      for (int a = 0; a < kh; ++a) {
-        const double* row = s_p + (yl + a) * pw + threadIdx.x;
-        for (int b = 0; b < kw; ++b) {
-          const double w = s_w[a * kw + b];
-          if (w == 0.0) continue;
-          acc = acc + row[b] * w;
-        }
-      }
-      if (acc < 0.0) acc = 0.0;
-      const float v = (float)acc;
-      out[(size_t)y * N + x] = v;
-      const unsigned int key = f32_order_key(v);
-      kmin = min(kmin, key);
-      kmax = max(kmax, key);
-    }
-  }
-  // workgroup min/max -> one atomic pair per wave, into the image's slot
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((tid & 63) == 0) {
-    atomicMin(&minmax[2 * (size_t)g], kmin);
-    atomicMax(&minmax[2 * (size_t)g + 1], kmax);
-  }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = f32_min_span(in[i], mn, span);
 }
 
 // k_normalise_f32 in place for image img0 + blockIdx.y of a stack, with that image's (min, max) slot
@@ -167,205 +214,8 @@ __global__ void k_normalise_f32_batch(float* const* __restrict__ imgs, int img0,
   const float mn = f32_from_key(minmax[2 * (size_t)g]);
   const float mx = f32_from_key(minmax[2 * (size_t)g + 1]);
   const float span = mx - mn;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-    const float a = p[i] - mn;
-    p[i] = a / span;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// a1, batched, several kernels on shared frames (gpet_grad_images_multi, gpet_batch_create_raw_multi,
-//     gpet_batch_set_raw_images_multi; the table: gpet_conv_multi_plan.h).  blockIdx.z is a FRAME: its workgroup loads the union
-//     patch of all kernels once -- k_conv_relu_batch's load, with the union's halo -- and the flipped taps of all kernels, then
-//     evaluates every slot of the frame out of that patch: slot g's kernel k reads patch row yl + a + kd[k].dy, column
-//     tx + b + kd[k].dx for its tap (a, b), which is the pixel k_conv_relu_batch reads for it.  Per output the products, their
-//     order, the skipped zero taps, the clamp and the cast are k_conv_relu_batch's, so a slot's image has its bits.  One
-//     order-key (min, max) atomic pair per wave and slot.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ void k_conv_relu_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
-                                  const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
-                                  const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
-                                  const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
-#pragma clang fp contract(off)
-  extern __shared__ double s_w[];  // [n_taps] taps of all kernels, then the union patch [ph][pw]
-  const int f = frame0 + blockIdx.z;
-  const T* __restrict__ img = src[f];
-  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
-  for (int i = tid; i < n_taps; i += nthr) s_w[i] = wf[i];
-  double* s_p = s_w + n_taps;
-  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * CONV_RY;
-  for (int e = tid; e < pw * ph; e += nthr) {
-    const int py = e / pw, px = e - py * pw;
-    int ry = y0 + py - top, rx = x0 + px - left;
-    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
-    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
-    s_p[e] = (double)img[(size_t)ry * N + rx];
-  }
-  __syncthreads();
-  const int x = x0 + threadIdx.x;
-  for (int si = slot_off[f]; si < slot_off[f + 1]; ++si) {
-    const int g = slot_list[si];
-    const ConvKernDesc K = kd[kernel_of[g]];
-    const double* __restrict__ w_k = s_w + K.w0;
-    float* __restrict__ out = dst[g];
-    unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (int yl = threadIdx.y; yl < CONV_RY; yl += blockDim.y) {
-      const int y = y0 + yl;
-      if (x < N && y < M) {
-        double acc = 0.0;
-        for (int a = 0; a < K.kh; ++a) {
-          const double* row = s_p + (yl + a + K.dy) * pw + threadIdx.x + K.dx;
-          for (int b = 0; b < K.kw; ++b) {
-            const double w = w_k[a * K.kw + b];
-            if (w == 0.0) continue;
-            acc = acc + row[b] * w;
-          }
-        }
-        if (acc < 0.0) acc = 0.0;
-        const float v = (float)acc;
-        out[(size_t)y * N + x] = v;
-        const unsigned int key = f32_order_key(v);
-        kmin = min(kmin, key);
-        kmax = max(kmax, key);
-      }
-    }
-    // wave min/max -> one atomic pair per wave, into the slot's pair
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-      kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-    }
-    if ((tid & 63) == 0) {
-      atomicMin(&minmax[2 * (size_t)g], kmin);
-      atomicMax(&minmax[2 * (size_t)g + 1], kmax);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// a1, batched, transposed store (GPET_FRAMES_TRANSPOSED; geometry: gpet_transpose_plan.h).  k_conv_relu_batch with the tile turned:
-//     a workgroup of 64 x 4 threads owns 16 frame columns x 64 frame rows, threadIdx.x is the ROW within the tile, and pixel (y, x)
-//     is stored at x * M + y of the N x M image -- the 64 lanes of a wave write 64 consecutive floats.  The patch lies in LDS
-//     TRANSPOSED, [16 + kw - 1] columns of 64 + kh - 1 pixels at an odd pitch, so the lanes of a tap read (one patch row apart) are
-//     consecutive doubles, as they are in k_conv_relu_batch; the few writes of the patch load are the strided ones.
-//     Per pixel the products, their order, the skipped zero taps, the clamp, the cast and the order key are k_conv_relu_batch's:
-//     the image is that kernel's, transposed, bit for bit, and the (min, max) slot holds the same pair.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ void k_conv_tr_batch(const T* const* __restrict__ src, int img0, int M, int N, const double* __restrict__ wf,
-                                    int kh, int kw, int oy, int ox, float* const* __restrict__ dst, unsigned int* minmax) {
-#pragma clang fp contract(off)
-  extern __shared__ double s_w[];  // [kh * kw] taps, then the patch, column-major: [CONV_T_TILE_X + kw - 1][pitch]
-  const int g = img0 + blockIdx.z;
-  const T* __restrict__ img = src[g];
-  float* __restrict__ out = dst[g];
-  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
-  for (int i = tid; i < kh * kw; i += nthr) s_w[i] = wf[i];
-  const int pw = CONV_T_TILE_X + kw - 1, ph = CONV_T_TILE_Y + kh - 1, pitch = conv_t_pitch(ph);
-  double* s_p = s_w + kh * kw;
-  const int x0 = conv_t_col(blockIdx.x, 0), y0 = conv_t_row(blockIdx.y, 0);
-  for (int e = tid; e < pw * ph; e += nthr) {
-    const int py = e / pw, px = e - py * pw;
-    int ry = y0 + py - oy, rx = x0 + px - ox;
-    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
-    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
-    s_p[px * pitch + py] = (double)img[(size_t)ry * N + rx];
-  }
-  __syncthreads();
-  const int yl = threadIdx.x, y = y0 + yl;
-  unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
-  for (int xl = threadIdx.y; xl < CONV_T_TILE_X; xl += blockDim.y) {
-    const int x = x0 + xl;
-    if (x < N && y < M) {
-      double acc = 0.0;
-      for (int a = 0; a < kh; ++a) {
-        const double* row = s_p + xl * pitch + yl + a;  // (patch row yl + a of column xl; the next column is `pitch` further)
-        for (int b = 0; b < kw; ++b) {
-          const double w = s_w[a * kw + b];
-          if (w == 0.0) continue;
-          acc = acc + row[b * pitch] * w;
-        }
-      }
-      if (acc < 0.0) acc = 0.0;
-      const float v = (float)acc;
-      out[tr_offset(y, x, M)] = v;
-      const unsigned int key = f32_order_key(v);
-      kmin = min(kmin, key);
-      kmax = max(kmax, key);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((tid & 63) == 0) {
-    atomicMin(&minmax[2 * (size_t)g], kmin);
-    atomicMax(&minmax[2 * (size_t)g + 1], kmax);
-  }
-}
-
-// k_conv_relu_multi with the tile turned the same way: the union patch column-major at the odd pitch, every slot of the frame out of it
-template <typename T>
-__global__ void k_conv_tr_multi(const T* const* __restrict__ src, int frame0, int M, int N, const double* __restrict__ wf, int n_taps,
-                                    const ConvKernDesc* __restrict__ kd, int top, int left, int ph, int pw,
-                                    const int32_t* __restrict__ slot_off, const int32_t* __restrict__ slot_list,
-                                    const int32_t* __restrict__ kernel_of, float* const* __restrict__ dst, unsigned int* minmax) {
-#pragma clang fp contract(off)
-  extern __shared__ double s_w[];  // [n_taps] taps of all kernels, then the union patch, column-major: [pw][pitch]
-  const int f = frame0 + blockIdx.z;
-  const T* __restrict__ img = src[f];
-  const int tid = threadIdx.x + threadIdx.y * blockDim.x, nthr = blockDim.x * blockDim.y;
-  for (int i = tid; i < n_taps; i += nthr) s_w[i] = wf[i];
-  double* s_p = s_w + n_taps;
-  const int pitch = conv_t_pitch(ph);
-  const int x0 = conv_t_col(blockIdx.x, 0), y0 = conv_t_row(blockIdx.y, 0);
-  for (int e = tid; e < pw * ph; e += nthr) {
-    const int py = e / pw, px = e - py * pw;
-    int ry = y0 + py - top, rx = x0 + px - left;
-    ry = ry < 0 ? 0 : (ry > M - 1 ? M - 1 : ry);
-    rx = rx < 0 ? 0 : (rx > N - 1 ? N - 1 : rx);
-    s_p[px * pitch + py] = (double)img[(size_t)ry * N + rx];
-  }
-  __syncthreads();
-  const int yl = threadIdx.x, y = y0 + yl;
-  for (int si = slot_off[f]; si < slot_off[f + 1]; ++si) {
-    const int g = slot_list[si];
-    const ConvKernDesc K = kd[kernel_of[g]];
-    const double* __restrict__ w_k = s_w + K.w0;
-    float* __restrict__ out = dst[g];
-    unsigned int kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (int xl = threadIdx.y; xl < CONV_T_TILE_X; xl += blockDim.y) {
-      const int x = x0 + xl;
-      if (x < N && y < M) {
-        double acc = 0.0;
-        for (int a = 0; a < K.kh; ++a) {
-          const double* row = s_p + (xl + K.dx) * pitch + yl + a + K.dy;
-          for (int b = 0; b < K.kw; ++b) {
-            const double w = w_k[a * K.kw + b];
-            if (w == 0.0) continue;
-            acc = acc + row[b * pitch] * w;
-          }
-        }
-        if (acc < 0.0) acc = 0.0;
-        const float v = (float)acc;
-        out[tr_offset(y, x, M)] = v;
-        const unsigned int key = f32_order_key(v);
-        kmin = min(kmin, key);
-        kmax = max(kmax, key);
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-      kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-    }
-    if ((tid & 63) == 0) {
-      atomicMin(&minmax[2 * (size_t)g], kmin);
-      atomicMax(&minmax[2 * (size_t)g + 1], kmax);
-    }
-  }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = f32_min_span(p[i], mn, span);
 }
 
 // A finished M x N f32 image into the N x M one (gradient images a caller hands a vertical batch): a TR_TILE x TR_TILE tile through
@@ -390,12 +240,8 @@ __global__ void k_transpose_f32(const float* __restrict__ in, int M, int N, cons
     const int x = x0 + cc, y = y0 + threadIdx.x;
     if (y < M && x < N) {
       float v = s_t[threadIdx.x * TR_PITCH + cc];
-      if (NORM) {
-        const float a = v - mn;
-        v = a / span;
-      }
+      if (NORM) v = f32_min_span(v, mn, span);
       out[tr_offset(y, x, M)] = v;
     }
   }
 }
-

@@ -136,15 +136,7 @@ __global__ void __launch_bounds__(256) k_kde_conv_x(EdgeDev* edges, int mode) {
       kmax = max(kmax, key);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(&E.mm[0], kmin);
-    atomicMax(&E.mm[1], kmax);
-  }
+  wave_minmax_commit(kmin, kmax, threadIdx.x, &E.mm[0], &E.mm[1]);
 }
 
 __global__ void __launch_bounds__(256) k_kde_normalise(EdgeDev* edges, int mode) {
@@ -156,7 +148,7 @@ __global__ void __launch_bounds__(256) k_kde_normalise(EdgeDev* edges, int mode)
   float* a = (mode == 0) ? E.kde : (float*)E.grad_kde;
   const size_t px = (size_t)E.M * E.N;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < px; i += (size_t)gridDim.x * blockDim.x)
-    a[i] = (a[i] - mn) / span;
+    a[i] = f32_min_span(a[i], mn, span);
 }
 
 // ---- fused curve KDE (per-iteration path) ----------------------------------------------
@@ -615,15 +607,7 @@ __device__ __forceinline__ void kde_fused_body(EdgeDev* edges, int raw_band) {
     kmin = min(kmin, kz);
     kmax = max(kmax, kz);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    kmin = min(kmin, (unsigned int)__shfl_xor((int)kmin, o, WAVE));
-    kmax = max(kmax, (unsigned int)__shfl_xor((int)kmax, o, WAVE));
-  }
-  if ((tid & 63) == 0) {
-    atomicMin(&E.mm[0], kmin);
-    atomicMax(&E.mm[1], kmax);
-  }
+  wave_minmax_commit(kmin, kmax, tid, &E.mm[0], &E.mm[1]);
 }
 __global__ void __launch_bounds__(KDE_THREADS) k_kde_fused(EdgeDev* edges, int raw_band) { kde_fused_body<false>(edges, raw_band); }
 // (four workgroups of eight waves per CU need at most 64 registers: tests/test_kde_reg_host.py reads the count from the code object)

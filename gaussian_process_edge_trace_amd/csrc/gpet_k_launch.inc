@@ -7,10 +7,9 @@
 hipError_t launch_conv(hipStream_t st, const double* d_img, int M, int N, const double* d_wf, int kh, int kw, int oy,
                        int ox, float* d_tmp, unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  dim3 bs(64, 4), gs(cdiv(N, 64), cdiv(M, CONV_RY));
-  const size_t lds = ((size_t)kh * kw + (size_t)(CONV_RY + kh - 1) * (64 + kw - 1)) * sizeof(double);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;  // (a kernel of hundreds of taps per side: not the reference's use)
-  hipLaunchKernelGGL(k_conv_relu, gs, bs, lds, st, d_img, M, N, d_wf, kh, kw, oy, ox, d_tmp, d_minmax);
+  const ConvGrid cg = conv_grid(M, N);
+  if (conv_lds_bytes(kh, kw) > CONV_LDS_MAX) return hipErrorInvalidValue;  // (a kernel of hundreds of taps per side: not the reference's use)
+  hipLaunchKernelGGL(k_conv_relu, dim3(cg.gx, cg.gy), dim3(64, 4), conv_lds_bytes(kh, kw), st, d_img, M, N, d_wf, kh, kw, oy, ox, d_tmp, d_minmax);
   return hipGetLastError();
 }
 hipError_t launch_minmax(hipStream_t st, const float* d_in, size_t count, unsigned int* d_minmax) {
@@ -57,47 +56,45 @@ static hipError_t for_grid_z(int n, F&& f) {
 }
 
 // raw frames of a stack -> unnormalised f32 gradient images: images img0 .. img0 + n - 1 of the device pointer tables d_src /
-// d_dst in ONE launch (geometry: gpet_conv_plan.h); d_minmax holds a (min, max) slot per image of the stack
-static_assert(CONV_RY == CONV_TILE_Y && CONV_TILE_X == 64, "k_conv_relu_batch tiles as gpet_conv_plan.h says");
-template <typename T>
-static hipError_t launch_conv_batch_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
-                                      int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
-  const ConvGrid cg = conv_grid(M, N);
-  hipLaunchKernelGGL(k_conv_relu_batch<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_lds_bytes(kh, kw), st, (const T* const*)d_src, img0,
-                     M, N, d_wf, kh, kw, conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
-  return hipGetLastError();
-}
-hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+// d_dst in ONE launch; d_minmax holds a (min, max) slot per image of the stack.  tr: the transposed-store form of a vertical batch --
+// an N x M image G.T at every d_dst[g].  Geometry: gpet_conv_plan.h, turned: gpet_transpose_plan.h.
+static_assert(CONV_RY == CONV_TILE_Y && CONV_TILE_X == 64, "ConvRows tiles as gpet_conv_plan.h says");
+hipError_t launch_conv_batch(hipStream_t st, int pix, bool tr, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
                              int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (!conv_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  if (!(tr ? conv_t_fits_lds(kh, kw) : conv_fits_lds(kh, kw)) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  const ConvGrid cg = tr ? conv_t_grid(M, N) : conv_grid(M, N);
+  if (tr && cg.gy > 65535) return hipErrorInvalidValue;  // (a frame of more than 4 M rows)
+  const size_t lds = tr ? conv_t_lds_bytes(kh, kw) : conv_lds_bytes(kh, kw);
   return for_pix(pix, [&](auto t) {
     using T = typename decltype(t)::type;
-    return for_grid_z(n, [&](int i, int m) { return launch_conv_batch_t<T>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); });
+    const auto kern = tr ? k_conv_tr_batch<T> : k_conv_relu_batch<T>;
+    return for_grid_z(n, [&](int i, int m) {
+      hipLaunchKernelGGL(kern, dim3(cg.gx, cg.gy, m), dim3(64, 4), lds, st, (const T* const*)d_src, img0 + i, M, N, d_wf, kh, kw,
+                         conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
+      return hipGetLastError();
+    });
   });
 }
 // frames frame0 .. frame0 + n - 1 of d_src -> the unnormalised f32 gradient images of all their slots in ONE launch: the device
 // tables of gpet_conv_multi_plan.h (taps of all kernels, kernel descriptors, slots of each frame, kernel of each slot), d_dst and
-// d_minmax per SLOT
-template <typename T>
-static hipError_t launch_conv_multi_t(hipStream_t st, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
-                                      const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
-                                      const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
-  const ConvGrid cg = conv_grid(M, N);
-  hipLaunchKernelGGL(k_conv_relu_multi<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_union_lds_bytes(u), st, (const T* const*)d_src, frame0,
-                     M, N, d_wf, (int)u.taps, d_kd, u.top, u.left, conv_union_rows(u), conv_union_cols(u), d_slot_off, d_slot_list,
-                     d_kernel_of, d_dst, d_minmax);
-  return hipGetLastError();
-}
-hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+// d_minmax per SLOT; tr as above
+hipError_t launch_conv_multi(hipStream_t st, int pix, bool tr, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
                              const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
                              const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
   (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (u.taps == 0 || conv_union_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  const size_t lds = tr ? conv_union_t_lds_bytes(u) : conv_union_lds_bytes(u);
+  if (u.taps == 0 || lds > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
+  const ConvGrid cg = tr ? conv_t_grid(M, N) : conv_grid(M, N);
+  if (tr && cg.gy > 65535) return hipErrorInvalidValue;
+  const int ph = tr ? conv_union_t_rows(u) : conv_union_rows(u), pw = tr ? conv_union_t_cols(u) : conv_union_cols(u);
   return for_pix(pix, [&](auto t) {
     using T = typename decltype(t)::type;
+    const auto kern = tr ? k_conv_tr_multi<T> : k_conv_relu_multi<T>;
     return for_grid_z(n, [&](int i, int m) {
-      return launch_conv_multi_t<T>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax);
+      hipLaunchKernelGGL(kern, dim3(cg.gx, cg.gy, m), dim3(64, 4), lds, st, (const T* const*)d_src, frame0 + i, M, N, d_wf, (int)u.taps,
+                         d_kd, u.top, u.left, ph, pw, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax);
+      return hipGetLastError();
     });
   });
 }
@@ -112,49 +109,6 @@ hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, s
   return hipGetLastError();
 }
 
-// ---- vertical batches: the transposed-store forms (gpet_k_conv.inc; geometry: gpet_transpose_plan.h) ----
-// launch_conv_batch for an N x M image G.T at every d_dst[g]: the same launches with the turned tile
-template <typename T>
-static hipError_t launch_conv_batch_tr_t(hipStream_t st, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
-                                         int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
-  const ConvGrid cg = conv_t_grid(M, N);
-  hipLaunchKernelGGL(k_conv_tr_batch<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_t_lds_bytes(kh, kw), st, (const T* const*)d_src, img0,
-                     M, N, d_wf, kh, kw, conv_origin(kh), conv_origin(kw), d_dst, d_minmax);
-  return hipGetLastError();
-}
-hipError_t launch_conv_batch_tr(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
-                                int kh, int kw, float* const* d_dst, unsigned int* d_minmax) {
-  (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (!conv_t_fits_lds(kh, kw) || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
-  if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;  // (a frame of more than 4 M rows)
-  return for_pix(pix, [&](auto t) {
-    using T = typename decltype(t)::type;
-    return for_grid_z(n, [&](int i, int m) { return launch_conv_batch_tr_t<T>(st, d_src, img0 + i, m, M, N, d_wf, kh, kw, d_dst, d_minmax); });
-  });
-}
-template <typename T>
-static hipError_t launch_conv_multi_tr_t(hipStream_t st, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
-                                         const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
-                                         const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
-  const ConvGrid cg = conv_t_grid(M, N);
-  hipLaunchKernelGGL(k_conv_tr_multi<T>, dim3(cg.gx, cg.gy, n), dim3(64, 4), conv_union_t_lds_bytes(u), st, (const T* const*)d_src,
-                     frame0, M, N, d_wf, (int)u.taps, d_kd, u.top, u.left, conv_union_t_rows(u), conv_union_t_cols(u), d_slot_off,
-                     d_slot_list, d_kernel_of, d_dst, d_minmax);
-  return hipGetLastError();
-}
-hipError_t launch_conv_multi_tr(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
-                                const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
-                                const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax) {
-  (void)hipGetLastError();  // drop stale errors: report only these launches
-  if (u.taps == 0 || conv_union_t_lds_bytes(u) > CONV_LDS_MAX || n < 1 || pix_bytes(pix) == 0) return hipErrorInvalidValue;
-  if (conv_t_grid(M, N).gy > 65535) return hipErrorInvalidValue;
-  return for_pix(pix, [&](auto t) {
-    using T = typename decltype(t)::type;
-    return for_grid_z(n, [&](int i, int m) {
-      return launch_conv_multi_tr_t<T>(st, d_src, frame0 + i, m, M, N, d_wf, u, d_kd, d_slot_off, d_slot_list, d_kernel_of, d_dst, d_minmax);
-    });
-  });
-}
 // an M x N f32 image -> the N x M one at d_out (d_out != d_in); d_minmax != nullptr: launch_normalise's arithmetic on the way
 hipError_t launch_transpose(hipStream_t st, const float* d_in, int M, int N, const unsigned int* d_minmax, float* d_out) {
   (void)hipGetLastError();  // drop stale errors: report only these launches

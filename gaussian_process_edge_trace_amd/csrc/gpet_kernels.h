@@ -56,22 +56,16 @@ hipError_t launch_minmax(hipStream_t st, const float* d_in, size_t count, unsign
 hipError_t launch_normalise(hipStream_t st, const float* d_in, size_t count, const unsigned int* d_minmax,
                             float* d_out);
 // a1 for a stack of raw frames (pix: PIX_* of gpet_conv_plan.h): images img0 .. img0 + n - 1 of the DEVICE pointer tables, one
-// launch each; every image of the stack has its own (min, max) slot in d_minmax
-hipError_t launch_conv_batch(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
+// launch each; every image of the stack has its own (min, max) slot in d_minmax.  tr: a vertical batch (gpet_transpose_plan.h) -- the
+// image at d_dst[g] is the N x M transpose of the M x N gradient image, per pixel the same bits and the same (min, max) slot
+hipError_t launch_conv_batch(hipStream_t st, int pix, bool tr, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
                              int kh, int kw, float* const* d_dst, unsigned int* d_minmax);
 // the same for a slot table (gpet_conv_multi_plan.h): frames frame0 .. frame0 + n - 1 of d_src, every slot of each of them, one
 // launch; d_dst and d_minmax are per slot
-hipError_t launch_conv_multi(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
+hipError_t launch_conv_multi(hipStream_t st, int pix, bool tr, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
                              const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
                              const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax);
 hipError_t launch_normalise_batch(hipStream_t st, float* const* d_imgs, int n, size_t count, const unsigned int* d_minmax);
-// vertical batches (gpet_transpose_plan.h): launch_conv_batch / launch_conv_multi whose image at d_dst[g] is the N x M transpose of
-// the M x N gradient image, per pixel the same bits and the same (min, max) slots
-hipError_t launch_conv_batch_tr(hipStream_t st, int pix, const void* const* d_src, int img0, int n, int M, int N, const double* d_wf,
-                                int kh, int kw, float* const* d_dst, unsigned int* d_minmax);
-hipError_t launch_conv_multi_tr(hipStream_t st, int pix, const void* const* d_src, int frame0, int n, int M, int N, const double* d_wf,
-                                const ConvUnion& u, const ConvKernDesc* d_kd, const int32_t* d_slot_off, const int32_t* d_slot_list,
-                                const int32_t* d_kernel_of, float* const* d_dst, unsigned int* d_minmax);
 // an M x N f32 image on the device -> the N x M one at d_out, out of place; d_minmax != nullptr: every element through
 // launch_normalise's arithmetic with that (min, max) pair on its way
 hipError_t launch_transpose(hipStream_t st, const float* d_in, int M, int N, const unsigned int* d_minmax, float* d_out);
