@@ -1912,10 +1912,13 @@ class Batch:
         return cache[key]
 
     def info(self, e=0):
-        v = (C.c_int32 * 14)()
-        self.ctx.check(self.lib.gpet_batch_info(self.h, e, v, 14))
+        v = (C.c_int32 * 18)()
+        self.ctx.check(self.lib.gpet_batch_info(self.h, e, v, 18))
+        # (the last four are the batch's normals store: iterations held per edge -- 0 before the first trace and where there is
+        #  none --, its size, the (edge, iteration) streams the loop has generated so far for iterations the edge went on to run, and
+        #  the streams its store launches drew, exactly)
         keys = ["Lg", "S", "n_keep", "n_cap", "factor_cap", "z_cols", "factor_rows_cap", "n_bins", "obs_cap",
-                "algo_thresh", "structured", "r0", "z_ring", "arena_mib"]
+                "algo_thresh", "structured", "r0", "z_ring", "arena_mib", "zstore_iters", "zstore_mib", "normals_generated", "normals_drawn"]
         return dict(zip(keys, list(v)))
 
     def scalars(self, e=0) -> GpetScalars:

@@ -391,6 +391,11 @@ static int batch_create_from(gpet_ctx* c, int B, int M, int N, const ImageSource
   lay(meas);
   b->arena_bytes = meas.off + 256;
   hipError_t he = hipMalloc(&b->arena, b->arena_bytes);
+  if (he != hipSuccess) {  // (the store a destroyed batch left for the next one is in nobody's use: its room first)
+    (void)hipGetLastError();
+    zstore_pool_drain();
+    he = hipMalloc(&b->arena, b->arena_bytes);
+  }
   if (he != hipSuccess) {
     b->arena = nullptr;
     return fail(c, GPET_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", b->arena_bytes, hipGetErrorString(he));
@@ -564,6 +569,10 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->d_fin_n) (void)hipFree(b->d_fin_n);
   if (b->d_results) (void)hipFree(b->d_results);
   if (b->d_hist) (void)hipFree(b->d_hist);
+  zstore_release(b);
+  if (b->zst.d_edges) (void)hipFree(b->zst.d_edges);
+  if (b->zst.d_seeds) (void)hipFree(b->zst.d_seeds);
+  if (b->zst.d_running) (void)hipFree(b->zst.d_running);
   ensemble_free(b);
   if (b->band.G) (void)hipFree(b->band.G);
   if (b->band.tab) (void)hipFree(b->band.tab);
@@ -602,9 +611,15 @@ int gpet_batch_image_count(const gpet_batch* b) { return b ? batch_source_count(
 int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count) {
   if (!b || e < 0 || e >= b->B || !out) return GPET_ERR_BAD_ARG;
   const EdgeDev& E = b->h_edges[e];
-  const int32_t v[14] = {E.Lg, E.S, E.n_keep, E.n_cap, E.r_cap, E.z_cols, E.a_rows_cap, E.n_bins, E.obs_cap, E.algo_thresh,
-                         b->structured ? 1 : 0, E.r0, E.z_ring, (int32_t)(b->arena_bytes >> 20)};
-  for (int i = 0; i < count && i < 14; ++i) out[i] = v[i];
+  // (the last three: the normals store -- iterations held per edge (0: none, the batch runs on its ring alone), its size, and the
+  //  (edge, iteration) streams the loop has generated so far for iterations the edge ran, then the streams its store launches drew,
+  //  exactly; both saturating)
+  const long long gen = b->zst.generated < 0x7fffffffll ? b->zst.generated : 0x7fffffffll;
+  const long long drw = b->zst.drawn < 0x7fffffffll ? b->zst.drawn : 0x7fffffffll;
+  const int32_t v[18] = {E.Lg, E.S, E.n_keep, E.n_cap, E.r_cap, E.z_cols, E.a_rows_cap, E.n_bins, E.obs_cap, E.algo_thresh,
+                         b->structured ? 1 : 0, E.r0, E.z_ring, (int32_t)(b->arena_bytes >> 20),
+                         b->zst.iters, (int32_t)(b->zst.bytes >> 20), (int32_t)gen, (int32_t)drw};
+  for (int i = 0; i < count && i < 18; ++i) out[i] = v[i];
   return GPET_OK;
 }
 
@@ -790,7 +805,7 @@ int gpet_batch_read(gpet_batch* b, int e, int which, void* dst, size_t bytes) {
     case GPET_BUF_COV: src = E.cov; avail = Lg * Lg * 8; break;
     case GPET_BUF_FACTOR: src = E.A; avail = (size_t)s.rank * Lg * 8; break;
     case GPET_BUF_EIGVALS: src = E.theta; avail = (size_t)s.rank * 8; break;
-    case GPET_BUF_NORMALS: src = E.Z + (size_t)(s.iter % E.z_ring) * E.S * E.z_cols; avail = (size_t)E.S * E.z_cols * 8; break;
+    case GPET_BUF_NORMALS: src = z_slot(E, s.iter); avail = (size_t)E.S * E.z_cols * 8; break;
     case GPET_BUF_SAMPLES: {
       // rows of Yp elements on the device (f32 after gpet_batch_set_sample_dtype); the interface is a dense [S][Lg] f64 matrix
       const size_t cnt = (size_t)E.S * Lg, pitch = (size_t)E.Yp, esz = E.y_f32 ? 4 : 8;
@@ -926,7 +941,8 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
       gpet_scalars s;
       int rc = read_scalars(b, e, &s);
       if (rc) return rc;
-      dst = E.Z + (size_t)(s.iter % E.z_ring) * E.S * E.z_cols;
+      dst = z_slot(E, s.iter);
+      if (s.iter < b->zst.iters) b->zst.tags[(size_t)e * b->zst.iters + s.iter] = 0;  // (injected: not what any seed draws)
       cap = (size_t)E.S * E.z_cols * 8;
       b->have_normals = true;
       break;
@@ -995,6 +1011,7 @@ int gpet_batch_set_rng(gpet_batch* b, int mode) {
   HIPCHK(c, gpet_wait(c->stream));
   if (b->side) HIPCHK(c, gpet_wait(b->side));
   b->rng_mode = mode;
+  zstore_clear_tags(b->zst);  // (the store's slots hold the other mode's numbers)
   b->have_normals = false;
   return GPET_OK;
 }

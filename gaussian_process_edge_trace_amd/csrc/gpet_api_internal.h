@@ -20,6 +20,8 @@
 //                        per normals mode, the kernel chain of an iteration, the end of a group); the dispatch of the normal
 //                        generators (normals_auto, launch_normals_seq)
 //   gpet_loop_plan.h     the loop's scheduling decisions as plain data (no HIP): options -> LoopPlan, the chunked head, group sizes
+//   gpet_zstore_plan.h   the normals store's decisions as plain data (no HIP): its size from the free memory and two options, the tag of
+//                        a slot, which edges of a group miss
 //   gpet_api_comm.hip    multi-GPU helpers on RCCL (8e): communicator, broadcast of the gradient image, gather of the traces
 //                        and of the result records
 //   gpet_api_results.hip the finished result record of every edge (k_finish_results): gpet_result_bytes, gpet_batch_results
@@ -88,6 +90,42 @@ struct BandState {
   bool moved = false;                // gpet_batch_init_follow has rewritten (i_lo, i_hi) and the inits on the device since h_tab was current
 };
 
+// The normals store of a batch: one allocation OUTSIDE the arena (edge e owns iters slots of slot_bytes from e * iters * slot_bytes;
+// EdgeDev::Zs / zs_iters), the tags on the HOST -- the host decides what is generated -- and the tables of the launches that
+// generate for some edges only.  iters == 0: no store (never asked for, refused by the budget, or the allocation failed): the
+// batch then runs on its ring alone, as every batch did before the store existed.
+struct ZGenLaunch {      // a generator launch of the loop whose effect the host does not know yet (Loop::end_group settles it)
+  int from, n;           // iterations [from, from + n)
+  bool store;            // into store slots: their tags are set once it is certain the edge generated
+  std::vector<int> idx;  // the batch's edges it ran for (empty: all of them)
+};
+struct ZStore {
+  bool decided = false;
+  double* mem = nullptr;
+  int iters = 0;
+  size_t slot_bytes = 0, bytes = 0, alloc_bytes = 0;  // alloc_bytes >= bytes: a block taken over from a destroyed batch may be larger
+  std::vector<uint64_t> tags;          // [B][iters]; 0: empty
+  long long generated = 0;             // (edge, iteration) streams the loop generated for iterations the edge went on to run (gpet_batch_info)
+  long long drawn = 0;                 // (edge, iteration) streams the loop's STORE launches generated, exactly: they always generate
+  std::vector<ZGenLaunch> pending;
+  // compacted edge / seed tables of the launches that generate for the edges with a miss: segments of one device block, taken in
+  // order and reused when the same edges miss again; the host copies stay untouched while a copy may still read them
+  EdgeDev* d_edges = nullptr;
+  unsigned int* d_seeds = nullptr;
+  std::vector<EdgeDev> h_edges;
+  std::vector<unsigned int> h_seeds;
+  size_t cap = 0, used = 0;
+  std::vector<int> last_idx;           // the edges of the segment taken last, at last_off (emptied by every gpet_trace_iterate)
+  size_t last_off = 0;
+  hipStream_t last_stream = nullptr;
+  gpet_scalars* d_running = nullptr;   // a record that says "running" (done = 0, status OK): what the entries of those tables read
+};
+// gpet_api_loop.hip: the store of a batch being destroyed goes to the process's pool or back to the device; the pool emptied
+void zstore_release(gpet_batch* b);
+void zstore_pool_drain();
+// empties every tag (what the slots would hold has changed, or may have been overwritten: gpet_batch_set_rng, the stage generators)
+static inline void zstore_clear_tags(ZStore& z) { std::fill(z.tags.begin(), z.tags.end(), (uint64_t)0); }
+
 struct gpet_batch {
   gpet_ctx* ctx = nullptr;
   int B = 0;
@@ -99,9 +137,11 @@ struct gpet_batch {
   unsigned int* d_seeds_act = nullptr;
   std::vector<EdgeDev> h_edges_act;
   std::vector<unsigned int> h_seeds_act;
+  std::vector<int> h_idx_act;          // their indices in the batch
   char* arena = nullptr;
   size_t arena_bytes = 0;
   unsigned int* d_seeds = nullptr;
+  std::vector<unsigned int> h_seeds_dev;  // what d_seeds was last written from (the stage generators' tags)
   gpet_scalars* d_scalars = nullptr;   // [B] contiguous: one copy reads every edge's state
   double* d_fin_out = nullptr;         // [B][2][Lg_max] contiguous results of the converged fits
   double* d_fin_par = nullptr;         // [B][12] contiguous hyper-parameters / transforms of the converged fits
@@ -195,6 +235,7 @@ struct gpet_batch {
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;
   gpet_history_plan hist{};
+  ZStore zst;      // the normals store (gpet_zstore_plan.h), decided and allocated by the batch's first gpet_trace_iterate
   BandState band;  // tracking bands (gpet_batch_create_banded)
   // a vertical batch (GPET_FRAMES_TRANSPOSED at creation): the caller's frames and gradient images are bd.N rows of (band.H ? band.M :
   // bd.M) pixels, and load_images writes their transposes -- everything behind it works on the batch's own (M, N) as ever

@@ -1,5 +1,6 @@
 // C ABI, part 3: the per-stage entry points (a2-a7, f1) and gpet_profile_stage.
 #include "gpet_api_internal.h"
+#include "gpet_zstore_plan.h"
 
 extern "C" {
 
@@ -41,8 +42,20 @@ int gpet_gp_normals(gpet_batch* b, const uint32_t* seeds) {
     int rcn = normals_auto(b, c->stream, b->d_edges, b->B, b->d_seeds, 0, -1, 1, 0);
     if (rcn) return rcn;
   }
+  b->h_seeds_dev.assign(seeds, seeds + b->B);
   HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
   HIPCHK(c, gpet_wait(c->stream));
+  if (b->zst.iters > 0) {
+    // the slot z_slot names at every edge's own iteration now holds the stream of the seed the caller named, every column of it:
+    // its tag says so (the loop finds it where seed + iteration + 1 is that seed).  An edge in an error state was skipped
+    const int rcs = fetch_all_scalars(b);
+    if (rcs) return rcs;
+    for (int e = 0; e < b->B; ++e) {
+      const gpet_scalars& s = b->h_scalars[e];
+      if (s.status == GPET_OK && s.iter >= 0 && s.iter < b->zst.iters)
+        b->zst.tags[(size_t)e * b->zst.iters + s.iter] = zstore_tag(seeds[e], b->rng_mode, b->bd.z_cols);
+    }
+  }
   b->have_normals = true;
   return GPET_OK;
 }
@@ -165,6 +178,7 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
       if (p) (void)hipFree(p);
     }
   } slot_guard{d_slots};
+  bool normals_profiled = false;
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));
   for (int r = 0; r < reps; ++r) {
     switch (stage) {
@@ -182,6 +196,7 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
       case 2:
         if (b->rng_mode == 1) HIPCHK(c, launch_normals_philox(c->stream, b->d_edges, b->B, b->bd, b->d_seeds, 1, -1, b->bd.z_ring, loop_z_store(b)));
         else HIPCHK(c, launch_normals_seq(b, c->stream, b->d_edges, b->B, b->d_seeds, 1, -1, b->bd.z_ring, loop_z_store(b)));
+        normals_profiled = true;  // (always generates, into the slots z_slot names: their tags are settled below)
         break;
       case 3: HIPCHK(c, launch_sample(c->stream, b->d_edges, b->B, b->bd, b->structured ? b->bd.r0_max : 0)); break;
       case 4: HIPCHK(c, launch_score(c->stream, b->d_edges, b->B, b->bd)); break;
@@ -207,7 +222,21 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
   float ms = 0.f;
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   *ms_per_rep = ms / (float)reps;
-  return check_device_status(b);
+  const int rc_status = check_device_status(b);  // (reads every edge's state)
+  if (normals_profiled && b->zst.iters > 0) {
+    // Stage 2 drew, for every running edge, the z_ring iterations from its own on by the loop's seed rule from the seeds on the
+    // device: the store slots among them hold exactly what the loop would draw there, so they get the loop's tags.  Without a host
+    // copy of those seeds, or after an error, the slots it may have written lose theirs.
+    const int zsel = loop_z_store(b), zs = zsel > 0 && zsel < b->bd.z_cols ? zsel : b->bd.z_cols;
+    const bool known = rc_status == GPET_OK && (int)b->h_seeds_dev.size() == b->B;
+    for (int e = 0; e < b->B; ++e) {
+      const gpet_scalars& s = b->h_scalars[e];
+      if (known && (s.done || s.status != GPET_OK)) continue;  // (skipped by the generators: untouched)
+      for (int q = std::max(0, s.iter); q < s.iter + b->bd.z_ring && q < b->zst.iters; ++q)
+        b->zst.tags[(size_t)e * b->zst.iters + q] = known ? zstore_loop_tag(b->h_seeds_dev[e], q, b->rng_mode, zs) : 0;
+    }
+  }
+  return rc_status;
 }
 
 int gpet_select_pixels_only(gpet_batch* b) {

@@ -108,6 +108,23 @@ struct EdgeDev {
   double* fin_par;       // [12]
   double* fin_out;       // [2 * Lg_max] mean (pixels) then std, in the batch's contiguous output block
   char* hist;            // this edge's region of the iteration history (gpet_history_plan.h), outside the arena; nullptr: history off
+  double* Zs;            // [zs_iters][S*z_cols] this edge's part of the batch's normals store (gpet_zstore_plan.h), outside the arena:
+  int zs_iters;          // slot of iteration k < zs_iters = k; 0 (and Zs == nullptr): no store, every iteration takes the ring
 };
+
+#if defined(__HIPCC__)
+#define GPET_DEV_HD __host__ __device__
+#else
+#define GPET_DEV_HD
+#endif
+// Where the normals of iteration `iter` of an edge live: its store slot, or the ring's.  The ONE place that knows: the generators
+// write through it, the sample GEMMs and the buffer API read through it.
+// (z_slot_of: the same rule on copies of the fields, for k_mt_normals4, which declares them wave-uniform one by one)
+GPET_DEV_HD inline double* z_slot_of(double* Z, int z_ring, double* Zs, int zs_iters, size_t slot, int iter) {
+  return iter < zs_iters ? Zs + (size_t)iter * slot : Z + (size_t)(iter % z_ring) * slot;
+}
+GPET_DEV_HD inline double* z_slot(const EdgeDev& E, int iter) {
+  return z_slot_of(E.Z, E.z_ring, E.Zs, E.zs_iters, (size_t)E.S * (size_t)E.z_cols, iter);
+}
 
 }  // namespace gpet

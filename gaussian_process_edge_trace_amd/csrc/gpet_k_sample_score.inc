@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(256) k_sample_gemm_mfma(EdgeDev* edges) {
   const int s0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
   if (s0 >= S || j0 >= Lg) return;
   const int rows = sc->rank;
-  const double* __restrict__ Zs = E.Z + (size_t)(sc->iter % E.z_ring) * ((size_t)S * zc);
+  const double* __restrict__ Zs = z_slot(E, sc->iter);
   __shared__ double sz[64][33];  // [s][k]
   __shared__ double sa[32][65];  // [k][j]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -109,7 +109,7 @@ __device__ __forceinline__ void sample_gemm_body(const EdgeDev& E, const gpet_sc
   const int jhi = (jlo + tpc * 64 < Lg) ? (jlo + tpc * 64) : Lg;
   if (jlo >= Lg) return;
   const int rows = sc->rank;
-  const GPET_GLOBAL double* __restrict__ Zs = as_global(E.Z) + (size_t)(sc->iter % E.z_ring) * ((size_t)S * zc);
+  const GPET_GLOBAL double* __restrict__ Zs = as_global(z_slot(E, sc->iter));
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, lq = lane >> 4;
   const int srow = s0 + 16 * w + li;

@@ -37,7 +37,9 @@ namespace gpet {
   X(diag_in_syrk, 1, 0, 1, "blocked fit: the trailing update's first workgroup factors the next diagonal block; 0: a launch of its own") \
   X(topk_rank, 0, 0, 1, "1: argsort of the costs by rank counting (k_topk) also where the bitonic sort applies") \
   X(struct_path, 1, 0, 1, "structured loop path (prior eigenbasis of the pixel grid) where it applies; 0: the generic kernels") \
-  X(kde_variant, 1, 0, 1, "fused curve KDE of at most 128 kept curves: 1 = a tile's points stay in registers from the loads to the binning, weights once per edge, four workgroups per CU (k_kde_fused_r); 0 = points and weights staged in LDS by every tile (k_kde_fused: the cross-check, and the form of more curves)")
+  X(kde_variant, 1, 0, 1, "fused curve KDE of at most 128 kept curves: 1 = a tile's points stay in registers from the loads to the binning, weights once per edge, four workgroups per CU (k_kde_fused_r); 0 = points and weights staged in LDS by every tile (k_kde_fused: the cross-check, and the form of more curves)") \
+  X(normals_store, -1, -1, 1, "normals store of a batch (read at its first trace): the normals of an edge's first iterations are kept, tagged with what drew them, and drawn again only where a tag does not match -- a trace repeated with the same seeds launches no generator; -1 = at least 8 iterations fit the budget (a quarter of the free device memory, outside the device's last eighth), 0 = never, 1 = whatever the budget allows") \
+  X(normals_store_iters, -1, -1, 32, "iterations per edge the normals store holds: -1 = 12, 0 = a budget of zero (no store), n = n iterations or as many as the budget holds")
 
 enum class Opt : int {
 #define GPET_OPT_ENUM(name, def, lo, hi, doc) name,

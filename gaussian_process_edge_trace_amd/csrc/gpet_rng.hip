@@ -189,8 +189,7 @@ __global__ void __launch_bounds__(64) k_mt_normals4(EdgeDev* edges, const unsign
       const bool skip = (s_done && !s_force) || s_status != GPET_OK;
       if (!skip) {
         const int iter_idx = (iter_abs >= 0 ? iter_abs : r4_uni(sc->iter)) + ahead;
-        const int ring = r4_uni(E.z_ring);
-        Zb[s] = (double*)r4_uni_ptr(E.Z) + (size_t)(iter_idx % ring) * ((size_t)S * zc);
+        Zb[s] = z_slot_of((double*)r4_uni_ptr(E.Z), r4_uni(E.z_ring), (double*)r4_uni_ptr(E.Zs), r4_uni(E.zs_iters), (size_t)S * zc, iter_idx);
         if (my_s == s) live = true;
         unsigned int p = (unsigned int)r4_uni((int)seeds[e_idx]) + (add_iter ? (unsigned int)(iter_idx + 1) : 0u);  // gpet.py:839
 #pragma unroll

@@ -465,7 +465,11 @@ int gpet_batch_size(const gpet_batch* b);
 int gpet_batch_image_count(const gpet_batch* b);
 /* out[0..count): Lg, S, n_keep, n_cap, factor_cap, z_cols, factor_rows_cap, n_bins, obs_cap, algo_thresh,
  * structured (1: the loop uses the prior-eigenbasis path), r0 (rank of the grid's correlation matrix), z_ring (slots
- * of pre-generated normals per edge), arena size of the batch in MiB */
+ * of pre-generated normals per edge), arena size of the batch in MiB, then the batch's normals store (options normals_store,
+ * normals_store_iters; decided by the first gpet_trace_iterate): zstore_iters (iterations held per edge; 0: no store),
+ * its size in MiB, normals_generated (the (edge, iteration) streams the loop has generated so far for iterations the edge
+ * went on to run), normals_drawn (the streams the loop's launches into the store generated, exactly: they generate whatever
+ * the edge's `done` flag says, look-ahead included); both saturating */
 int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count);
 
 /* Back to the state right after gpet_batch_create: no observations, initial score threshold,
