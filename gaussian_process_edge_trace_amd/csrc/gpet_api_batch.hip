@@ -663,11 +663,7 @@ int check_device_status(gpet_batch* b) {
 int warm_start_finish(gpet_batch* b, int32_t* n_obs_out) {
   const int rc_h = history_clear(b, -1);
   if (rc_h) return rc_h;
-  b->have_results = false;
-  b->have_last_fit = false;
-  b->ens_kept = false;  // (a kept ensemble belongs to the trace these fits ended)
-  b->iters_issued = 0;
-  b->norm_issued = 0;
+  state_apply(b->st, StateEvent::observations_set);
   const int rc = fetch_all_scalars(b);  // (the one copy and the one wait: the counts are in the scalars)
   if (rc) return rc;
   b->h_nobs_prev.assign((size_t)b->B, 0);
@@ -716,9 +712,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
   gpet_ctx* c = b->ctx;
   EdgeDev& E = b->h_edges[e];
   if (n_obs > E.obs_cap) return fail(c, GPET_ERR_BAD_ARG, "n_obs=%d exceeds obs_cap=%d", n_obs, E.obs_cap);
-  b->have_results = false;
-  b->have_last_fit = false;  // (the trace that follows is not the one the fits in d_fin_out belong to)
-  b->ens_kept = false;
+  state_apply(b->st, StateEvent::set_obs_entry);  // (the trace that follows is not the one the fits in d_fin_out belong to)
   // the pixel kernels index the density images with the observations (gpet.py:568: kde_arr[pre_fobs[:,0], pre_fobs[:,1]]
   // raises IndexError in the reference for pixels outside the image)
   for (int i = 0; i < n_obs; ++i)
@@ -739,12 +733,11 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
     int rc3 = clear_factor_rows(b, e);
     if (rc3) return rc3;
   }
-  b->iters_issued = 0;   // (all edges of a batch are restarted together)
+  state_apply(b->st, StateEvent::observations_set);  // (all edges of a batch are restarted together)
   int rc4 = history_clear(b, e);  // (the history is the trace's that ends here)
   if (rc4) return rc4;
   if ((int)b->h_nobs_prev.size() != b->B) b->h_nobs_prev.assign(b->B, 0);
   b->h_nobs_prev[e] = n_obs;  // (a batch of up to 64 edges sizes the loop's groups by the growth of its observation sets from here: next_group)
-  b->norm_issued = 0;
   if (b->structured)
     for (int i = 0; i < n_obs; ++i)
       if (obs_xy[2 * i] < E.x_st || obs_xy[2 * i] > E.x_en) {  // off-grid training point: generic path from now on
@@ -761,7 +754,7 @@ int gpet_batch_set_obs(gpet_batch* b, int e, const int64_t* obs_xy, int n_obs) {
 // GPET_OK when gpet_batch_warm_start can run, else its refusal -- for a caller that swaps the images first and must not find out after
 int gpet_batch_warm_start_ready(gpet_batch* b) {
   if (!b) return GPET_ERR_BAD_ARG;
-  if (!b->have_last_fit)
+  if (state_missing(b->st, StateEvent::read_last_fit))
     return fail(b->ctx, GPET_ERR_BAD_ARG, "gpet_batch_warm_start: no converged fits of a last trace on the device (run a trace to its "
                                           "gpet_final_fit_all first; gpet_batch_set_obs or a warm start since then have used them up)");
   return GPET_OK;
@@ -934,7 +927,7 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
       HIPCHK(c, hipMemcpyAsync(E.sc, &s, sizeof s, hipMemcpyHostToDevice, c->stream));
       E.factor_injected = 1;
       HIPCHK(c, hipMemcpyAsync(b->d_edges + e, &E, sizeof E, hipMemcpyHostToDevice, c->stream));
-      b->have_factor = true;
+      state_apply(b->st, StateEvent::write_factor);
       break;
     }
     case GPET_BUF_NORMALS: {
@@ -944,11 +937,11 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
       dst = z_slot(E, s.iter);
       if (s.iter < b->zst.iters) b->zst.tags[(size_t)e * b->zst.iters + s.iter] = 0;  // (injected: not what any seed draws)
       cap = (size_t)E.S * E.z_cols * 8;
-      b->have_normals = true;
+      state_apply(b->st, StateEvent::write_normals);
       break;
     }
     case GPET_BUF_SAMPLES: {
-      b->have_samples = true;
+      state_apply(b->st, StateEvent::write_samples);
       // (dense [S][Lg] f64 in, rows of Yp elements on the device; rounded to f32 here, as the GEMM does when it stores)
       const size_t cnt = (size_t)E.S * Lg, pitch = (size_t)E.Yp, esz = E.y_f32 ? 4 : 8, nel = bytes / 8;
       if (bytes > cnt * 8) return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_write: %zu bytes exceed capacity %zu", bytes, cnt * 8);
@@ -965,7 +958,7 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
       return GPET_OK;
     }
     case GPET_BUF_FIN_OUT: {
-      // (dense [2][Lg] in; no state flag changes: have_results / have_last_fit stay as the last converged fit left them)
+      // (dense [2][Lg] in; no state event: the batch goes on holding what the last converged fit left it holding)
       if (bytes != 2 * Lg * 8) return fail(c, GPET_ERR_BAD_ARG, "FIN_OUT write: expected %zu bytes", 2 * Lg * 8);
       HIPCHK(c, hipMemcpyAsync(E.fin_out, src, Lg * 8, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipMemcpyAsync(E.fin_out + b->bd.Lg, (const char*)src + Lg * 8, Lg * 8, hipMemcpyHostToDevice, c->stream));
@@ -975,11 +968,11 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
     case GPET_BUF_GRAD_KDE: dst = (void*)E.grad_kde; cap = px * 4; break;
     case GPET_BUF_KDE: dst = E.kde; cap = px * 4; break;
     case GPET_BUF_COSTS: dst = E.costs; cap = (size_t)E.S * 8; break;
-    case GPET_BUF_BEST_IDX: dst = E.best_idx; cap = (size_t)E.n_keep * 4; b->have_scores = true; break;
+    case GPET_BUF_BEST_IDX: dst = E.best_idx; cap = (size_t)E.n_keep * 4; state_apply(b->st, StateEvent::write_best_idx); break;
     case GPET_BUF_BEST_COSTS: dst = E.best_costs; cap = (size_t)E.n_keep * 8; break;
     case GPET_BUF_MEAN: dst = E.mean; cap = Lg * 8; break;
-    case GPET_BUF_COV: dst = E.cov; cap = Lg * Lg * 8; b->have_fit = true; break;
-    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); b->have_results = b->have_last_fit = false; break;
+    case GPET_BUF_COV: dst = E.cov; cap = Lg * Lg * 8; state_apply(b->st, StateEvent::write_cov); break;
+    case GPET_BUF_SCALARS: dst = E.sc; cap = sizeof(gpet_scalars); state_apply(b->st, StateEvent::write_scalars); break;
     default:
       return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_write: buffer %d is not writable", which);
   }
@@ -1012,7 +1005,7 @@ int gpet_batch_set_rng(gpet_batch* b, int mode) {
   if (b->side) HIPCHK(c, gpet_wait(b->side));
   b->rng_mode = mode;
   zstore_clear_tags(b->zst);  // (the store's slots hold the other mode's numbers)
-  b->have_normals = false;
+  state_apply(b->st, StateEvent::set_rng);
   return GPET_OK;
 }
 
@@ -1029,7 +1022,7 @@ int gpet_batch_set_sample_dtype(gpet_batch* b, int f32) {
   b->bd.y_arith = GPET_SAMPLE_ARITH_F64;  // (no batch holds f64 storage with f32 arithmetic)
   HIPCHK(c, hipMemcpyAsync(b->d_edges, b->h_edges.data(), sizeof(EdgeDev) * (size_t)b->B, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, gpet_wait(c->stream));
-  b->have_samples = false;
+  state_apply(b->st, StateEvent::set_sample_type);
   return GPET_OK;
 }
 
@@ -1045,7 +1038,7 @@ int gpet_batch_set_sample_arith(gpet_batch* b, int arith) {
   HIPCHK(c, gpet_wait(c->stream));
   if (b->side) HIPCHK(c, gpet_wait(b->side));
   b->bd.y_arith = arith;
-  b->have_samples = false;
+  state_apply(b->st, StateEvent::set_sample_type);
   return GPET_OK;
 }
 
@@ -1060,12 +1053,11 @@ int gpet_batch_clear_injected_factor(gpet_batch* b, int e) {
   return GPET_OK;
 }
 
-static int batch_reset(gpet_batch* b, bool next_frame) {
+// ev: what restarts the batch (StateEvent::reset, StateEvent::images_swapped)
+static int batch_reset(gpet_batch* b, bool next_frame, StateEvent ev) {
   gpet_ctx* c = b->ctx;
-  b->have_results = false;
+  state_apply(b->st, ev);
   b->h_nobs_prev.assign(b->B, 0);
-  b->iters_issued = 0;
-  b->norm_issued = 0;
   HIPCHK(c, hipSetDevice(c->device));
   if (b->bd.r_cap > 96) {  // (any-rank batches keep the last factor rows in a ring)
     if (next_frame && opt(Opt::oj_warm)) {  // where every edge's last rows are, before the iteration counters go
@@ -1092,8 +1084,7 @@ static int batch_reset(gpet_batch* b, bool next_frame) {
 int gpet_batch_reset(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
-  b->ens_kept = false;  // (gpet_batch_set_images goes through batch_reset itself and leaves a kept ensemble alone)
-  return batch_reset(b, false);
+  return batch_reset(b, false, StateEvent::reset);
 }
 
 // The orientation of a batch is decided at its creation: a vertical batch takes its frames in frame layout without the bit being
@@ -1116,8 +1107,7 @@ static int batch_set_images_from(gpet_batch* b, const ImageSource& src) {
   // gradient KDE of every distinct image (gpet.py:127), then the state of a fresh constructor
   rc = image_kde(b);
   if (rc) return rc;
-  b->have_fit = b->have_factor = b->have_normals = b->have_samples = b->have_scores = false;
-  return batch_reset(b, (flags & GPET_IMAGES_NEXT_FRAME) != 0);
+  return batch_reset(b, (flags & GPET_IMAGES_NEXT_FRAME) != 0, StateEvent::images_swapped);
 }
 
 // raw frames: the orientation, then everything check_raw_source refuses, before the batch is touched

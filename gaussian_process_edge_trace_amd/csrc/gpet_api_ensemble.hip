@@ -20,7 +20,7 @@ struct EnsembleScratch {
   char* stage = nullptr;
   size_t stage_bytes = 0;
   // the kept ensemble (gpet_batch_ensemble_keep; layout: gpet_warm_plan.h): the buffer of gpet_batch_ensemble for len_cap = the widest
-  // edge with the group table behind it, valid while gpet_batch::ens_kept; the host's copy of the table (kept alive for its copy)
+  // edge with the group table behind it, valid while the batch's state says so (ST_ENS_KEPT); the host's copy of the table (kept alive for its copy)
   char* kept = nullptr;
   size_t kept_bytes = 0;
   int kept_G = 0;
@@ -46,9 +46,14 @@ void ensemble_free(gpet_batch* b) {
 
 // the state gpet_batch_results asks for, with its status
 static int check_fit(gpet_batch* b, const char* who) {
-  if (!b->have_results)
+  if (state_missing(b->st, StateEvent::read_results))
     return fail(b->ctx, GPET_ERR_BAD_ARG, "%s: no converged fit of the current trace (run gpet_final_fit_all first)", who);
   return GPET_OK;
+}
+
+// a kept ensemble can be read: the state says it is valid, and the allocation it would be in exists
+static bool ensemble_is_kept(const gpet_batch* b) {
+  return !state_missing(b->st, StateEvent::read_kept_ensemble) && b->ens && b->ens->kept;
 }
 
 static int scratch(gpet_batch* b, EnsembleScratch** out) {
@@ -224,7 +229,7 @@ int gpet_batch_ensemble_keep(gpet_batch* b, int n_groups, const int32_t* group_o
   if (!b || !group_of) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
   const int B = b->B;
-  b->ens_kept = false;
+  state_apply(b->st, StateEvent::ensemble_keep_begin);
   int rc = check_fit(b, "gpet_batch_ensemble_keep");
   if (rc) return rc;
   int widest = 0;
@@ -252,7 +257,7 @@ int gpet_batch_ensemble_keep(gpet_batch* b, int n_groups, const int32_t* group_o
                            hipMemcpyHostToDevice, c->stream));
   s->kept_G = n_groups;
   s->kept_len_cap = widest;
-  b->ens_kept = true;
+  state_apply(b->st, StateEvent::ensemble_keep_end);
   return GPET_OK;
 }
 
@@ -262,7 +267,7 @@ int gpet_batch_ensemble_kept(gpet_batch* b, int64_t len_cap, void* dst, int dst_
   gpet_ctx* c = b->ctx;
   const int B = b->B;
   EnsembleScratch* const s = b->ens;
-  if (!b->ens_kept || !s || !s->kept)
+  if (!ensemble_is_kept(b))
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_ensemble_kept: no ensemble is kept (gpet_batch_ensemble_keep makes one; a warm start, "
                                      "gpet_batch_set_obs, gpet_batch_reset or another gpet_final_fit_all drop it)");
   const int G = s->kept_G;
@@ -302,7 +307,7 @@ static int warm_start_sourced(gpet_batch* b, int from, const int32_t* src_of, in
   if (ready) return ready;
   char msg[384];
   if (!src_of) {
-    const int rc = warm_groups_check(from, b->ens_kept && b->ens && b->ens->kept, msg, sizeof msg);
+    const int rc = warm_groups_check(from, ensemble_is_kept(b), msg, sizeof msg);
     if (rc) return fail(c, rc, "%s", msg);
   } else {
     std::vector<int32_t> x_st((size_t)B), x_en((size_t)B);
@@ -358,7 +363,7 @@ int gpet_batch_band_place(gpet_batch* b, const int32_t* src_of, int from) {
   const bool groups = !src_of && from >= 0;
   char msg[384];
   if (groups) {
-    const int rc = warm_groups_check(from, b->ens_kept && b->ens && b->ens->kept, msg, sizeof msg);
+    const int rc = warm_groups_check(from, ensemble_is_kept(b), msg, sizeof msg);
     if (rc) return fail(c, rc, "%s", msg);
   } else if (src_of) {
     std::vector<int32_t> x_st((size_t)B), x_en((size_t)B);

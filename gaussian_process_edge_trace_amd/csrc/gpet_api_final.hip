@@ -104,8 +104,8 @@ int gpet_final_predict_all(gpet_batch* b, const double* par, double* mean_out, d
   HIPCHK(c, hipSetDevice(c->device));
   for (int e = 0; e < b->B; ++e)
     if (b->h_edges[e].fin_n < 1) return fail(c, GPET_ERR_STATE, "gpet_final_predict_all before the training sets are set");
-  b->have_results = false;  // (a caller's own parameters: not the optimum gpet_batch_results reports)
-  b->have_last_fit = false;  // (nor a trace's converged fit)
+  // (a caller's own parameters: not the optimum gpet_batch_results reports, nor a trace's converged fit)
+  state_apply(b->st, StateEvent::final_predict_begin);
   // (slots 9..11 of every edge stay: the lattice of its training set)
   HIPCHK(c, hipMemcpy2DAsync(b->d_fin_par, 12 * sizeof(double), par, 12 * sizeof(double), 9 * sizeof(double), b->B,
                              hipMemcpyHostToDevice, c->stream));
@@ -118,7 +118,7 @@ int gpet_final_predict_all(gpet_batch* b, const double* par, double* mean_out, d
     memcpy(mean_out + (size_t)e * stride, host.data() + (size_t)e * 2 * b->bd.Lg, sizeof(double) * Lg);
     memcpy(std_out + (size_t)e * stride, host.data() + (size_t)e * 2 * b->bd.Lg + b->bd.Lg, sizeof(double) * Lg);
   }
-  b->have_fit = false;  // the loop's L/alpha were overwritten by the converged fit
+  state_apply(b->st, StateEvent::final_predict_end);  // the loop's L/alpha were overwritten by the converged fit
   return check_device_status(b);
 }
 
@@ -356,9 +356,7 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
   GPET_BATCH_SCOPE(b);
   if (!b || !seeds || !mean_out || !std_out || stride < b->bd.Lg) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  b->have_results = false;
-  b->have_last_fit = false;
-  b->ens_kept = false;  // (a kept ensemble is the last converged fits')
+  state_apply(b->st, StateEvent::final_fit_begin);  // (a kept ensemble is the last converged fits')
   HIPCHK(c, hipSetDevice(c->device));
   int rc = fetch_all_scalars(b);  // (synchronises the loop's stream: the observation sets are final)
   if (rc) return rc;
@@ -399,9 +397,9 @@ int gpet_final_fit_all(gpet_batch* b, const uint32_t* seeds, double* mean_out, d
     if (theta_out) memcpy(theta_out + (size_t)e * 4, th.data() + (size_t)e * 4, sizeof(double) * 4);
   }
   if (rounds_out) *rounds_out = rounds;
-  b->have_fit = false;  // the loop's L/alpha were overwritten by the converged fit
-  b->have_results = true;  // (fin_out + lb_theta_out: what gpet_batch_results packs)
-  b->have_last_fit = true;  // (fin_out: what gpet_batch_warm_start reads, past the reset of the next frame)
+  // the loop's L/alpha were overwritten by the converged fit; fin_out + lb_theta_out: what gpet_batch_results packs; fin_out: what
+  // gpet_batch_warm_start reads, past the reset of the next frame
+  state_apply(b->st, StateEvent::final_fit_end);
   if (b->band.H)  // (and the bands these fits are expressed in: what placement and the warm start across bands add to their rows)
     HIPCHK(c, hipMemcpyAsync(b->band.fit, b->band.r0, sizeof(long long) * (size_t)b->B, hipMemcpyDeviceToDevice, c->stream));
   return check_device_status(b);
@@ -414,7 +412,7 @@ int gpet_final_optimize(gpet_batch* b, int n_starts, const double* starts, const
   gpet_ctx* c = b->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   const int B = b->B, P = n_starts * B;
-  b->have_results = false;  // (lb_theta_out is about to hold another optimum)
+  state_apply(b->st, StateEvent::final_optimize);  // (lb_theta_out is about to hold another optimum)
   LbCfg cfg;
   cfg.nstart = n_starts;
   for (int k = 0; k < 3; ++k) {

@@ -17,14 +17,11 @@ int band_refresh_host(gpet_batch* b) {
 
 // legal only while no iteration has run since creation, gpet_batch_reset or an image swap
 static int init_state_check(gpet_batch* b, const char* who) {
-  if (b->iters_issued != 0)
+  if (state_missing(b->st, StateEvent::init_moved))
     return fail(b->ctx, GPET_ERR_STATE, "%s: %d iterations have run since the batch was created, reset or given new images; the init points "
-                                         "can move only before the first one", who, b->iters_issued);
+                                         "can move only before the first one", who, b->st.iters_issued);
   return GPET_OK;
 }
-
-// whatever was derived from the old init rows by the per-stage entry points is not the next stage's input any more
-static void init_forget_stages(gpet_batch* b) { b->have_fit = b->have_factor = b->have_samples = b->have_scores = false; }
 
 extern "C" {
 
@@ -55,7 +52,7 @@ int gpet_batch_init_follow(gpet_batch* b, int window, int cols, int64_t* init_ou
   } else {
     HIPCHK(c, launch_init_follow(c->stream, b->d_edges, b->B, window, cols, b->n_init_max, nullptr, nullptr, nullptr));
   }
-  init_forget_stages(b);
+  state_apply(b->st, StateEvent::init_moved);
   return init_out ? gpet_batch_init_xy(b, init_out) : GPET_OK;
 }
 
@@ -112,7 +109,7 @@ int gpet_batch_set_init(gpet_batch* b, const int64_t* const* init_xy) {
     HIPCHK(c, hipMemcpyAsync(bs.lohi, &bs.h_tab[t.off_lohi], sizeof(long long) * (t.count - t.off_lohi), hipMemcpyHostToDevice, c->stream));
     bs.moved = false;  // (every row of both tables has just been written from the host copy)
   }
-  init_forget_stages(b);
+  state_apply(b->st, StateEvent::init_moved);
   HIPCHK(c, gpet_wait(c->stream));
   return GPET_OK;
 }

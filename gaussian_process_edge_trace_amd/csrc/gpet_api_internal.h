@@ -14,6 +14,8 @@
 //                        reads / writes
 //   gpet_batch_plan.h    what batch creation decides, as plain data (no HIP): edge parameters -> EdgeDev fields and BatchDims, the
 //                        arena's layout (layout_batch: the one place where buffer sizes live; Carver), structured-path planning
+//   gpet_state_plan.h    what a batch knows about the validity of what it holds, as plain data (no HIP): the facts, the events, the
+//                        one table of what every call needs, makes and drops
 //   gpet_api_stages.hip  the per-stage entry points (a2-a7, f1) and gpet_profile_stage
 //   gpet_api_final.hip   the converged fit (f2): objective, device L-BFGS-B, posterior at the optimum
 //   gpet_api_loop.hip    the device-resident loop (a8): gpet_trace_iterate, a short driver over its pieces (compaction, one function
@@ -50,6 +52,7 @@
 
 #include "gpet_kernels.h"
 #include "gpet_options.h"
+#include "gpet_state_plan.h"
 
 using namespace gpet;
 
@@ -153,7 +156,6 @@ struct gpet_batch {
   std::vector<gpet_scalars> h_scalars;
   std::vector<int> h_nobs_prev;        // observations per edge at the last group boundary of the loop: batches up to 64 edges size
                                        // the next group by their growth (next_group, gpet_loop_plan.h)
-  int iters_issued = 0;                // iterations enqueued since the last reset (== sc->iter of active edges)
   int rng_mode = 0;                    // 0: MT19937 + polar method = numpy's RandomState stream; 1: Philox4x32-10 + Box-Muller (opt-in)
   hipStream_t side = nullptr;          // RNG stream: normals of upcoming iterations run ahead of the loop
   double* d_fin_stage = nullptr;       // staging of the converged fits' training sets (x | y | w blocks)
@@ -164,7 +166,6 @@ struct gpet_batch {
   hipEvent_t ev_norm[16] = {};
   hipEvent_t ev_gemm[16] = {};         // sample GEMM of iteration k done: ring slot k % ring may be refilled
   hipEvent_t ev_pix[16] = {};          // pixel selection of iteration k done: the `done` flags of iteration k + 1 are final
-  int norm_issued = 0;                 // iterations whose normals have been enqueued on `side`
   hipEvent_t ev_main = nullptr;
   unsigned int* d_minmax = nullptr;    // [2 B]: (min, max) of every gradient image being uploaded
   std::vector<unsigned int> h_mm0;     // their reset values (kept alive for the asynchronous copy)
@@ -213,24 +214,14 @@ struct gpet_batch {
   // largest lattice lag of every edge's converged-fit training set as the HOST knows it (fin_par[9..10] on the device):
   // -1 = no lattice (caller-supplied x off any grid) -> the vector objective kernels; see fin_lattice()
   std::vector<int> fin_lag;
-  bool have_fit = false, have_factor = false, have_normals = false, have_samples = false, have_scores = false;
-  // gpet_final_fit_all has run on the current trace: d_fin_out / lb_theta_out hold what gpet_batch_results packs (cleared by
-  // everything that starts another trace or overwrites the converged fit)
-  bool have_results = false;
-  // the converged fits of the LAST trace are in d_fin_out: what gpet_batch_warm_start derives the next frame's observations from.
-  // Unlike have_results it survives gpet_batch_reset / gpet_batch_set_images (they do not touch d_fin_out); cleared by whatever
-  // starts the trace after (gpet_batch_set_obs, gpet_batch_warm_start, gpet_trace_iterate, gpet_select_pixels[_only], a write of
-  // the scalars) or overwrites the fit
-  bool have_last_fit = false;
+  // what of all this is valid now, and the iterations enqueued since the last restart: changed by state_apply alone, asked through
+  // state_missing alone (gpet_state_plan.h has the table of what every call needs, makes and drops)
+  BatchState st;
   char* d_results = nullptr;           // device staging of gpet_batch_results into host memory (grown on demand)
   size_t results_bytes = 0;
   // seed ensembles (gpet_api_ensemble.hip): the scratch of gpet_batch_final_costs / gpet_batch_ensemble, allocations of their own made
   // on first use (nullptr: never called -- the batch then holds and enqueues nothing for them)
   struct EnsembleScratch* ens = nullptr;
-  // gpet_batch_ensemble_keep has left the ensemble of the last converged fits in the scratch (with its group table): what
-  // gpet_batch_warm_start_groups takes its sources from.  Survives gpet_batch_set_images; cleared by every warm start, gpet_batch_set_obs,
-  // gpet_batch_reset and the next gpet_final_fit_all
-  bool ens_kept = false;
   // iteration history (gpet_batch_set_history): storage of its own, B regions of hist.edge_bytes (gpet_history_plan.h); hist.level == 0
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;

@@ -297,7 +297,7 @@ struct Loop {
       if (rc) return rc;
     }
     for (int q = from; q < from + n; ++q) HIPCHK(c, hipEventRecord(b->ev_norm[q % 16], st));
-    b->norm_issued = from + n;
+    b->st.norm_issued = from + n;
     return GPET_OK;
   }
   // What the group's generator launches did, now that the host has the edges' state and every stream has been waited for.  Store
@@ -323,13 +323,13 @@ struct Loop {
   }
   int normals_inline_iteration(int cur) { return normals(c->stream, cur, 1); }
   int normals_inline_group(int cur) {  // at the group's first iteration (and again where a group is longer than the ring)
-    return b->norm_issued > cur ? GPET_OK : normals(c->stream, cur, std::min(horizon - cur, ring - 1));
+    return b->st.norm_issued > cur ? GPET_OK : normals(c->stream, cur, std::min(horizon - cur, ring - 1));
   }
   // The streams of the next n <= look iterations in ONE launch (blockIdx.x = iteration), side by side, whenever at most refill_at are
   // left.  Their ring slots were last read by the sample GEMMs of iterations <= cur - 1 (outstanding + n <= ring).
   int normals_side_deep(int cur) {
-    if (b->norm_issued - cur > plan.refill_at) return GPET_OK;
-    const int j = b->norm_issued, n = std::min(ring - (j - cur), plan.look);
+    if (b->st.norm_issued - cur > plan.refill_at) return GPET_OK;
+    const int j = b->st.norm_issued, n = std::min(ring - (j - cur), plan.look);
     if (cur - 1 >= first) HIPCHK(c, hipStreamWaitEvent(b->side, b->ev_gemm[(cur - 1) % 16], 0));
     // the head of a trace: chunked, one launch per iteration on the side stream, while the sequential launch of the iterations
     // after them runs beside them on the (idle until the converged fits) fit stream
@@ -346,8 +346,8 @@ struct Loop {
   }
   // one launch per iteration, `look` iterations ahead of the loop, never past the horizon of the iterations enqueued together
   int normals_side_shallow(int cur) {
-    while (b->norm_issued <= cur + plan.look && b->norm_issued < horizon) {
-      const int j = b->norm_issued;
+    while (b->st.norm_issued <= cur + plan.look && b->st.norm_issued < horizon) {
+      const int j = b->st.norm_issued;
       if (plan.look == 0) {
         if (j - 1 >= first) HIPCHK(c, hipStreamWaitEvent(b->side, b->ev_pix[(j - 1) % 16], 0));
       } else if (j - ring >= first) {
@@ -383,14 +383,14 @@ struct Loop {
     HIPCHK(c, launch_pixels(c->stream, edges_l, B_l, b->bd, 1));
     HIPCHK(c, hipEventRecord(b->ev_pix[cur % 16], c->stream));
     // opt-in history: the record of this iteration for the edges that completed it (their counter is now iters_issued + 1)
-    if (b->d_hist) HIPCHK(c, launch_history(c->stream, edges_l, B_l, b->hist, b->iters_issued + 1));
-    b->iters_issued += 1;
+    if (b->d_hist) HIPCHK(c, launch_history(c->stream, edges_l, B_l, b->hist, b->st.iters_issued + 1));
+    state_apply(b->st, StateEvent::iteration_enqueued);
     return GPET_OK;
   }
 
   // waits for the group (n_it iterations, of `group` planned), reads the edges' state and sizes the next group (*next = 0: stop)
   int end_group(int group, int n_it, int* active, int* next) {
-    b->have_fit = b->have_factor = b->have_normals = b->have_samples = b->have_scores = true;
+    state_apply(b->st, StateEvent::group_end);
     HIPCHK(c, gpet_wait(b->side));  // (its launches read the compacted tables too)
     if (fit_used) HIPCHK(c, gpet_wait(b->fit));
     fit_used = false;
@@ -417,8 +417,7 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   GPET_BATCH_SCOPE(b);
   if (!b || !base_seeds || !n_active || max_iters < 0) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  b->have_results = false;
-  b->have_last_fit = false;  // (another trace is under way: d_fin_out belongs to the one before until its own converged fit)
+  state_apply(b->st, StateEvent::trace_entry);  // (another trace is under way: d_fin_out belongs to the one before until its own converged fit)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(b->d_seeds, base_seeds, sizeof(uint32_t) * b->B, hipMemcpyHostToDevice, c->stream));
   b->h_seeds_dev.assign(base_seeds, base_seeds + b->B);
@@ -441,9 +440,9 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
     const int n_it = std::min(group, remaining);
     int rc = *n_active < b->B ? l.compact_active() : GPET_OK;
     if (rc) return rc;
-    l.first = b->iters_issued;
+    l.first = b->st.iters_issued;
     l.horizon = l.first + n_it;
-    if (b->norm_issued < l.first) b->norm_issued = l.first;
+    if (b->st.norm_issued < l.first) b->st.norm_issued = l.first;
     HIPCHK(c, hipEventRecord(b->ev_main, c->stream));  // the seeds and the edge table are on the device
     HIPCHK(c, hipStreamWaitEvent(b->side, b->ev_main, 0));
     for (int cur = l.first; cur < l.horizon && !rc; ++cur) {

@@ -63,7 +63,7 @@ size_t result_record_bytes(int64_t len_cap) {
 
 static int check_results(gpet_batch* b, int64_t len_cap) {
   gpet_ctx* c = b->ctx;
-  if (!b->have_results)
+  if (state_missing(b->st, StateEvent::read_results))
     return fail(c, GPET_ERR_BAD_ARG, "gpet_batch_results: no converged fit of the current trace (run gpet_final_fit_all first)");
   int widest = 0;
   for (const EdgeDev& E : b->h_edges) widest = std::max(widest, E.Lg);

@@ -2,33 +2,58 @@
 #include "gpet_api_internal.h"
 #include "gpet_zstore_plan.h"
 
+// ---- stages ---------------------------------------------------------------------------
+// What the per-stage entry points share once nothing refuses: the stage's launches with every edge made to run it (launch_set_force
+// around them), then the event; status: the edges' device status is read back and reported
+template <class Launches>
+static int forced_stage(gpet_batch* b, StateEvent ev, bool status, Launches launches) {
+  gpet_ctx* c = b->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
+  const int rc = launches();
+  if (rc) return rc;
+  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
+  state_apply(b->st, ev);
+  return status ? check_device_status(b) : GPET_OK;
+}
+
+// The one body of the three pixel-selection entry points, behind their refusals.  kde: the curve KDE first (else the selection
+// runs on the density GPET_BUF_KDE holds); raw_band: the form the device loop runs after its scorer (enqueue_iteration) -- the
+// density stays raw and band-limited in GPET_BUF_KDE, rows outside a tile's band keep what they held, the pixel kernels normalise
+// on the fly
+static int select_pixels(gpet_batch* b, StateEvent begin, bool kde, int raw_band) {
+  gpet_ctx* c = b->ctx;
+  state_apply(b->st, begin);  // (a new observation set: another trace)
+  // (k_pix_select advances every active edge's iteration counter)
+  return forced_stage(b, StateEvent::iteration_enqueued, true, [&]() -> int {
+    if (kde) HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0, ~0u, raw_band));
+    else HIPCHK(c, launch_pixels_reset(c->stream, b->d_edges, b->B, b->bd));
+    HIPCHK(c, launch_pixels(c->stream, b->d_edges, b->B, b->bd, raw_band));
+    return GPET_OK;
+  });
+}
+
 extern "C" {
 
-
-// ---- stages ---------------------------------------------------------------------------
 int gpet_gp_fit_predict(gpet_batch* b, int want_cov) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_fit_predict(c->stream, b->d_edges, b->B, b->bd, want_cov));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->have_fit = true;
-  return check_device_status(b);
+  return forced_stage(b, StateEvent::stage_fit, true, [&]() -> int {
+    HIPCHK(c, launch_fit_predict(c->stream, b->d_edges, b->B, b->bd, want_cov));
+    return GPET_OK;
+  });
 }
 
 int gpet_gp_factor(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_fit) return fail(c, GPET_ERR_STATE, "gpet_gp_factor before gpet_gp_fit_predict");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_factor(c->stream, b->d_edges, b->B, b->bd, ~0u, b->h_edges.data()));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->have_factor = true;
-  return check_device_status(b);
+  if (state_missing(b->st, StateEvent::stage_factor)) return fail(c, GPET_ERR_STATE, "gpet_gp_factor before gpet_gp_fit_predict");
+  return forced_stage(b, StateEvent::stage_factor, true, [&]() -> int {
+    HIPCHK(c, launch_factor(c->stream, b->d_edges, b->B, b->bd, ~0u, b->h_edges.data()));
+    return GPET_OK;
+  });
 }
 
 int gpet_gp_normals(gpet_batch* b, const uint32_t* seeds) {
@@ -56,7 +81,7 @@ int gpet_gp_normals(gpet_batch* b, const uint32_t* seeds) {
         b->zst.tags[(size_t)e * b->zst.iters + s.iter] = zstore_tag(seeds[e], b->rng_mode, b->bd.z_cols);
     }
   }
-  b->have_normals = true;
+  state_apply(b->st, StateEvent::stage_normals);
   return GPET_OK;
 }
 
@@ -64,39 +89,34 @@ int gpet_gp_sample(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_fit || !b->have_factor || !b->have_normals)
+  if (state_missing(b->st, StateEvent::stage_sample))
     return fail(c, GPET_ERR_STATE, "gpet_gp_sample needs fit, factor and normals first");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_sample(c->stream, b->d_edges, b->B, b->bd));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->have_samples = true;
-  return GPET_OK;
+  return forced_stage(b, StateEvent::stage_sample, false, [&]() -> int {
+    HIPCHK(c, launch_sample(c->stream, b->d_edges, b->B, b->bd));
+    return GPET_OK;
+  });
 }
 
 int gpet_score_curves(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_samples) return fail(c, GPET_ERR_STATE, "gpet_score_curves before samples exist");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_score(c->stream, b->d_edges, b->B, b->bd));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->have_scores = true;
-  return GPET_OK;
+  if (state_missing(b->st, StateEvent::stage_score)) return fail(c, GPET_ERR_STATE, "gpet_score_curves before samples exist");
+  return forced_stage(b, StateEvent::stage_score, false, [&]() -> int {
+    HIPCHK(c, launch_score(c->stream, b->d_edges, b->B, b->bd));
+    return GPET_OK;
+  });
 }
 
 int gpet_curve_kde(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_scores) return fail(c, GPET_ERR_STATE, "gpet_curve_kde before gpet_score_curves");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  return check_device_status(b);
+  if (state_missing(b->st, StateEvent::stage_kde)) return fail(c, GPET_ERR_STATE, "gpet_curve_kde before gpet_score_curves");
+  return forced_stage(b, StateEvent::stage_kde, true, [&]() -> int {
+    HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0));
+    return GPET_OK;
+  });
 }
 
 int gpet_final_cov(gpet_batch* b) {
@@ -108,7 +128,7 @@ int gpet_final_cov(gpet_batch* b) {
     if (b->h_edges[e].fin_n < 1) return fail(c, GPET_ERR_STATE, "gpet_final_cov before gpet_final_predict_all");
   HIPCHK(c, launch_final_cov(c->stream, b->d_edges, b->B, b->bd));
   HIPCHK(c, gpet_wait(c->stream));
-  b->have_fit = true;  // (mean in the caller's hands, covariance in GPET_BUF_COV: gpet_gp_factor may follow)
+  state_apply(b->st, StateEvent::final_cov);  // (mean in the caller's hands, covariance in GPET_BUF_COV: gpet_gp_factor may follow)
   return GPET_OK;
 }
 
@@ -116,34 +136,23 @@ int gpet_select_pixels(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_scores) return fail(c, GPET_ERR_STATE, "gpet_select_pixels before gpet_score_curves");
-  b->have_results = false;  // (a new observation set: another trace)
-  b->have_last_fit = false;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0));
-  HIPCHK(c, launch_pixels(c->stream, b->d_edges, b->B, b->bd));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->iters_issued += 1;  // k_pix_select advanced every active edge's iteration counter
-  return check_device_status(b);
+  if (state_missing(b->st, StateEvent::select_pixels)) return fail(c, GPET_ERR_STATE, "gpet_select_pixels before gpet_score_curves");
+  return select_pixels(b, StateEvent::select_pixels, true, 0);
 }
 
-// gpet_select_pixels in the form the device loop runs after its scorer (enqueue_iteration): the density stays raw and
-// band-limited in GPET_BUF_KDE, rows outside a tile's band keep what they held, the pixel kernels normalise on the fly
+// gpet_select_pixels in the form the device loop runs after its scorer
 int gpet_select_pixels_loop(gpet_batch* b) {
   GPET_BATCH_SCOPE(b);
   if (!b) return GPET_ERR_BAD_ARG;
   gpet_ctx* c = b->ctx;
-  if (!b->have_scores) return fail(c, GPET_ERR_STATE, "gpet_select_pixels_loop before gpet_score_curves");
-  b->have_results = false;  // (a new observation set: another trace)
-  b->have_last_fit = false;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_kde(c->stream, b->d_edges, b->B, b->bd, 0, ~0u, 1));
-  HIPCHK(c, launch_pixels(c->stream, b->d_edges, b->B, b->bd, 1));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->iters_issued += 1;  // k_pix_select advanced every active edge's iteration counter
-  return check_device_status(b);
+  if (state_missing(b->st, StateEvent::select_pixels)) return fail(c, GPET_ERR_STATE, "gpet_select_pixels_loop before gpet_score_curves");
+  return select_pixels(b, StateEvent::select_pixels, true, 1);
+}
+
+int gpet_select_pixels_only(gpet_batch* b) {
+  GPET_BATCH_SCOPE(b);
+  if (!b) return GPET_ERR_BAD_ARG;
+  return select_pixels(b, StateEvent::select_pixels_only, false, 0);
 }
 
 int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
@@ -237,21 +246,6 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
     }
   }
   return rc_status;
-}
-
-int gpet_select_pixels_only(gpet_batch* b) {
-  GPET_BATCH_SCOPE(b);
-  if (!b) return GPET_ERR_BAD_ARG;
-  gpet_ctx* c = b->ctx;
-  b->have_results = false;  // (a new observation set: another trace)
-  b->have_last_fit = false;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 1));
-  HIPCHK(c, launch_pixels_reset(c->stream, b->d_edges, b->B, b->bd));
-  HIPCHK(c, launch_pixels(c->stream, b->d_edges, b->B, b->bd));
-  HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
-  b->iters_issued += 1;
-  return check_device_status(b);
 }
 
 }  // extern "C"
