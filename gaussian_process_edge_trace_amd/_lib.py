@@ -1136,6 +1136,102 @@ def init_follow_refusal(window, cols):
     return None
 
 
+# label maps (csrc/gpet_label_plan.h; include/gpet_hip.h "label maps"): traces rasterised into uint8 masks on the device
+LABELS_EXTEND, LABELS_TRANSPOSED, LABELS_OUT_ON_DEVICE = 1, 2, 4
+LABEL_EDGES_MAX, LABEL_VERTS_MIN, LABEL_VERTS_MAX = 32, 4, 4096
+LABEL_NO_ROW = -(1 << 63)  # GPET_LABEL_NO_ROW: a row that does not count
+LABEL_CELLS_MAX = 1 << 31
+
+
+def _label_refusal_maps(null_arg, M, N, map_of, n_maps, noun):
+    """label_check_maps of csrc/gpet_label_plan.h, same order, same words: (reason or None, L)."""
+    if null_arg or map_of is None:
+        return "label maps: a null pointer", 0
+    if M < 2 or N < 2:
+        return "label maps: frames must be at least 2 x 2 pixels", 0
+    if M > LABEL_CELLS_MAX // N:
+        return "label maps: a map exceeds 2^31 pixels (M * N)", 0
+    if n_maps < 1:
+        return "label maps: n_maps must be at least 1", 0
+    for e, f in enumerate(map_of):
+        if f < -1 or f >= n_maps:
+            return "label maps: map_of[%d] = %d lies outside [-1, n_maps = %d)" % (e, f, n_maps), 0
+    L = 0
+    for f in range(n_maps):
+        cnt = sum(1 for v in map_of if v == f)
+        if cnt == 0:
+            return "label maps: map %d has no %s" % (f, noun), 0
+        if cnt > LABEL_EDGES_MAX:
+            return "label maps: map %d has more than 32 %ss (%d)" % (f, noun, cnt), 0
+        L = max(L, cnt)
+    return None, L
+
+
+def label_refusal(M, N, x_st, length, map_of, n_maps, rows=(), out=()):
+    """Why row maps cannot be made of these edges (label_check of csrc/gpet_label_plan.h, same order, same words), or None.  ``rows`` /
+    ``out`` None: the null pointer's case."""
+    why, _ = _label_refusal_maps(rows is None or out is None or x_st is None or length is None, M, N, map_of, n_maps, "edge")
+    if why is not None:
+        return why
+    for e, (x0, n) in enumerate(zip(x_st, length)):
+        if n < 1 or x0 < 0 or x0 + n > N:
+            return "label maps: the grid of edge %d lies outside [0, N) (x_st = %d, len = %d, N = %d)" % (e, x0, n, N)
+    return None
+
+
+def label_refusal_xy(Ms, Ns, n_vert, map_of, n_maps, xy=(), out=()):
+    """The same for maps of closed outlines (label_check_xy)."""
+    why, _ = _label_refusal_maps(xy is None or out is None or n_vert is None, Ms, Ns, map_of, n_maps, "contour")
+    if why is not None:
+        return why
+    for e, n in enumerate(n_vert):
+        if n < LABEL_VERTS_MIN or n > LABEL_VERTS_MAX:
+            return "label maps: contour %d has %d vertices, outside [4, 4096]" % (e, n)
+    return None
+
+
+def label_closed_refusal(e, x_st, x_en, pad, n_theta):
+    """Why edge e of a polar batch is no closed contour (label_check_closed), or None."""
+    if x_st == pad and x_en == pad + n_theta:
+        return None
+    return ("label maps: edge %d does not span the closed contour (x_st = %d, x_en = %d; pad = %d, pad + n_theta = %d)"
+            % (e, x_st, x_en, pad, pad + n_theta))
+
+
+def label_thick_count(n_maps, L, N):
+    """gpet_label_thick_count: the int32 elements of ``thick`` for n_maps maps of at most L edges and N columns."""
+    n = C.c_int64()
+    if load().gpet_label_thick_count(int(n_maps), int(L), int(N), C.byref(n)) != OK:
+        raise ValueError("label maps: thick of %d maps, %d edges, %d columns is out of range" % (n_maps, L, N))
+    return n.value
+
+
+def label_map_table(map_of, n_edges):
+    """``map_of`` as the int32 table the library takes and the number of maps it names; None: every edge on map 0."""
+    if map_of is None:
+        return np.zeros(int(n_edges), dtype=np.int32), 1
+    m = np.ascontiguousarray(np.asarray(map_of).reshape(-1), dtype=np.int32)
+    if m.shape[0] != n_edges:
+        raise ValueError("map_of has %d entries for %d edges" % (m.shape[0], n_edges))
+    return m, int(m.max()) + 1 if m.size and m.max() >= 0 else 1
+
+
+def _label_out(n_maps, shape, out_device_ptrs, thick_count, thick_device_ptr):
+    """(maps or None, pointer array, thick or None, thick pointer, flag) of a label-map call."""
+    if out_device_ptrs is not None:
+        ptrs = [int(p) for p in out_device_ptrs]
+        if len(ptrs) != n_maps:
+            raise ValueError("%d output pointers for %d maps" % (len(ptrs), n_maps))
+        if thick_count and thick_device_ptr is None:
+            raise ValueError("maps on the device need thick_device_ptr for the thickness too")
+        return None, (_P * n_maps)(*ptrs), None, (C.cast(_P(int(thick_device_ptr)), C.POINTER(C.c_int32)) if thick_count else None), LABELS_OUT_ON_DEVICE
+    maps = np.empty((n_maps,) + tuple(shape), dtype=np.uint8)
+    step = int(shape[0]) * int(shape[1])
+    op = (_P * n_maps)(*[maps.ctypes.data + f * step for f in range(n_maps)])
+    thick = np.empty(thick_count, dtype=np.int32) if thick_count else None
+    return maps, op, thick, (thick.ctypes.data_as(C.POINTER(C.c_int32)) if thick_count else None), 0
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -1275,6 +1371,14 @@ SYMBOLS = {
     "gpet_batch_init_follow": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "gpet_batch_set_init": (C.c_int, [_P, C.POINTER(_P)]),
     "gpet_batch_init_xy": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "gpet_label_maps": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int32), C.c_int, C.c_uint, C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "gpet_label_maps_xy": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                     C.c_int, C.c_uint, C.POINTER(_P)]),
+    "gpet_batch_label_maps": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_uint, C.POINTER(_P), C.POINTER(C.c_int32)]),
+    "gpet_batch_label_maps_xy": (C.c_int, [_P, C.POINTER(GpetPolar), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_uint,
+                                           C.POINTER(_P)]),
+    "gpet_label_thick_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1599,6 +1703,52 @@ class Context:
         out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
         self.check(self.lib.gpet_nlmeans_fast_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlf.arg(), flags, op))
         return out
+
+    def label_maps(self, shape, x_st, rows, map_of=None, extend=False, transposed=False, thickness=False, out_device_ptrs=None,
+                   thick_device_ptr=None):
+        """gpet_label_maps: Rule 1 of include/gpet_hip.h "label maps" on injected rows -- ``shape`` = (M, N), ``x_st[e]`` the first
+        column of edge e and ``rows[e]`` its int64 rows (``LABEL_NO_ROW``: the row does not count), ``map_of[e]`` its map or -1.  Returns
+        (n_maps, M, N) uint8 -- (n_maps, N, M) with ``transposed`` -- and, with ``thickness``, also (n_maps, L + 1, N) int32.
+        ``out_device_ptrs`` (one device address per map; ``thick_device_ptr`` for the thickness): written there instead, enqueued on
+        the context's stream, nothing waited for, None returned."""
+        M, N = int(shape[0]), int(shape[1])
+        rows = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int64) for r in rows]
+        n = len(rows)
+        m, n_maps = label_map_table(map_of, n)
+        xs = np.ascontiguousarray(np.asarray(x_st).reshape(-1), dtype=np.int32)
+        ln = np.array([r.shape[0] for r in rows], dtype=np.int32)
+        why = label_refusal(M, N, xs.tolist(), ln.tolist(), m.tolist(), n_maps) if xs.shape[0] == n else "x_st has %d entries for %d edges" % (xs.shape[0], n)
+        if why is not None:
+            raise ValueError(why)
+        L = int(np.bincount(m[m >= 0], minlength=1).max())
+        maps, op, thick, tp, flag = _label_out(n_maps, (N, M) if transposed else (M, N), out_device_ptrs,
+                                               label_thick_count(n_maps, L, N) if thickness else 0, thick_device_ptr)
+        flat = np.concatenate(rows) if n else np.zeros(0, dtype=np.int64)
+        ip = C.POINTER(C.c_int32)
+        flags = flag | (LABELS_EXTEND if extend else 0) | (LABELS_TRANSPOSED if transposed else 0)
+        self.check(self.lib.gpet_label_maps(self.h, M, N, n, xs.ctypes.data_as(ip), ln.ctypes.data_as(ip), flat.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            m.ctypes.data_as(ip), n_maps, flags, op, tp))
+        if maps is None:
+            return None
+        return (maps, thick.reshape(n_maps, L + 1, N)) if thickness else maps
+
+    def label_maps_xy(self, shape, outlines, map_of=None, out_device_ptrs=None):
+        """gpet_label_maps_xy: Rule 2 on injected vertices -- ``outlines[e]`` an (n, 2) float64 array of (x, y), 4 <= n <= 4096, in the
+        coordinates of the (Ms, Ns) = ``shape`` frame.  Returns (n_maps, Ms, Ns) uint8: how many outlines of its map a pixel is inside."""
+        Ms, Ns = int(shape[0]), int(shape[1])
+        outs = [np.ascontiguousarray(np.asarray(o, dtype=np.float64).reshape(-1, 2)) for o in outlines]
+        n = len(outs)
+        m, n_maps = label_map_table(map_of, n)
+        nv = np.array([o.shape[0] for o in outs], dtype=np.int32)
+        why = label_refusal_xy(Ms, Ns, nv.tolist(), m.tolist(), n_maps)
+        if why is not None:
+            raise ValueError(why)
+        maps, op, _, _, flag = _label_out(n_maps, (Ms, Ns), out_device_ptrs, 0, None)
+        flat = np.ascontiguousarray(np.concatenate(outs, axis=0))
+        ip = C.POINTER(C.c_int32)
+        self.check(self.lib.gpet_label_maps_xy(self.h, Ms, Ns, n, nv.ctypes.data_as(ip), flat.ctypes.data_as(C.POINTER(C.c_double)),
+                                               m.ctypes.data_as(ip), n_maps, flag, op))
+        return maps
 
     def normalise_f32(self, img):
         a = np.ascontiguousarray(img, dtype=np.float32)
@@ -2059,6 +2209,39 @@ class Batch:
         raw = np.empty(max(1, self.B * result_bytes(L)), dtype=np.uint8)
         self.ctx.check(self.lib.gpet_batch_results(self.h, L, raw.ctypes.data, 0))
         return decode_results(raw, self.B, L)
+
+    def label_maps(self, map_of=None, extend=False, transposed=False, thickness=False, out_device_ptrs=None, thick_device_ptr=None):
+        """gpet_batch_label_maps: Rule 1 of include/gpet_hip.h "label maps" from the converged fits where they lie -- valid when
+        ``results`` is.  ``map_of`` one map index per edge, -1 for none (None: all edges on map 0).  Returns (n_maps, M, N) uint8 in the
+        batch's full-frame shape -- ``(frame_M, N)``; with ``transposed`` (N, frame_M) -- and with ``thickness`` also (n_maps, L + 1, N)
+        int32.  ``out_device_ptrs`` / ``thick_device_ptr``: written there instead, enqueued only, None returned."""
+        m, n_maps = label_map_table(map_of, self.B)
+        why, L = _label_refusal_maps(False, self.frame_M, self.N, m.tolist(), n_maps, "edge")
+        if why is not None:
+            raise ValueError(why)
+        M, N = self.frame_M, self.N
+        maps, op, thick, tp, flag = _label_out(n_maps, (N, M) if transposed else (M, N), out_device_ptrs,
+                                               label_thick_count(n_maps, L, N) if thickness else 0, thick_device_ptr)
+        flags = flag | (LABELS_EXTEND if extend else 0) | (LABELS_TRANSPOSED if transposed else 0)
+        self.ctx.check(self.lib.gpet_batch_label_maps(self.h, m.ctypes.data_as(C.POINTER(C.c_int32)), n_maps, flags, op, tp))
+        if maps is None:
+            return None
+        return (maps, thick.reshape(n_maps, L + 1, N)) if thickness else maps
+
+    def label_maps_xy(self, polar, shape, map_of=None, out_device_ptrs=None):
+        """gpet_batch_label_maps_xy: Rule 2 from the converged fits of a batch on polar frames -- ``polar`` the resolved PolarSpec the
+        frames were unwrapped with (one centre, or one per map), ``shape`` = (Ms, Ns) of the source frames.  Returns (n_maps, Ms, Ns)
+        uint8."""
+        Ms, Ns = int(shape[0]), int(shape[1])
+        m, n_maps = label_map_table(map_of, self.B)
+        why, _ = _label_refusal_maps(polar is None, Ms, Ns, m.tolist(), n_maps, "edge")
+        if why is not None:
+            raise ValueError(why)
+        maps, op, _, _, flag = _label_out(n_maps, (Ms, Ns), out_device_ptrs, 0, None)
+        c, keep = polar.arg()
+        self.ctx.check(self.lib.gpet_batch_label_maps_xy(self.h, C.byref(c), Ms, Ns, m.ctypes.data_as(C.POINTER(C.c_int32)), n_maps, flag, op))
+        del keep
+        return maps
 
     def final_costs(self):
         """The scorer's cost of every edge's converged mean curve on its own gradient image, (B,) f64 (gpet_batch_final_costs:

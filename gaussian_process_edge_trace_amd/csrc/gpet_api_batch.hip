@@ -574,6 +574,7 @@ void gpet_batch_destroy(gpet_batch* b) {
   if (b->zst.d_seeds) (void)hipFree(b->zst.d_seeds);
   if (b->zst.d_running) (void)hipFree(b->zst.d_running);
   ensemble_free(b);
+  label_free(b->lab);
   if (b->band.G) (void)hipFree(b->band.G);
   if (b->band.tab) (void)hipFree(b->band.tab);
   if (b->band.d_G_of) (void)hipFree(b->band.d_G_of);

@@ -156,6 +156,7 @@ void gpet_ctx_destroy(gpet_ctx* c) {
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->scratch) (void)hipFree(c->scratch);
+  label_free(c->lab);
   if (c->raw_dev) (void)hipFree(c->raw_dev);
   if (c->raw_tab) (void)hipFree(c->raw_tab);
   if (c->pre_ws) (void)hipFree(c->pre_ws);

@@ -33,6 +33,8 @@
 //   gpet_api_ensemble.hip seed ensembles: gpet_batch_final_costs, gpet_ensemble_bytes, gpet_batch_ensemble
 //   gpet_ensemble_plan.h the layout of an ensemble's buffer, the validation of its arguments, member tables and tile width (no HIP)
 //                        and, for sequences, gpet_batch_ensemble_keep / _kept, gpet_batch_warm_start_groups / _from
+//   gpet_api_label.hip   label maps: gpet_label_maps[_xy], gpet_batch_label_maps[_xy], gpet_label_thick_count
+//   gpet_label_plan.h    the two rasterisation rules, their refusals, the fill kernels' launch shapes (no HIP)
 //   gpet_api_init.hip    endpoint tracking: gpet_batch_init_follow, gpet_batch_set_init, gpet_batch_init_xy
 //   gpet_init_plan.h     the rule that moves an init point, its refusals (no HIP)
 //   gpet_warm_plan.h     the source of every edge's warm start (medoid, best cost, consensus, another edge, none), the refusals, the
@@ -74,6 +76,7 @@ struct gpet_ctx {
   // replaced, so a stage finds no other stage's work in it; grown on demand
   char* pre_ws = nullptr;
   size_t pre_ws_bytes = 0;
+  struct LabelScratch* lab = nullptr;  // label maps on injected rows / vertices (gpet_api_label.hip): made on first use
   std::string err;
 };
 
@@ -222,6 +225,9 @@ struct gpet_batch {
   // seed ensembles (gpet_api_ensemble.hip): the scratch of gpet_batch_final_costs / gpet_batch_ensemble, allocations of their own made
   // on first use (nullptr: never called -- the batch then holds and enqueues nothing for them)
   struct EnsembleScratch* ens = nullptr;
+  // label maps (gpet_api_label.hip): the scratch of gpet_batch_label_maps[_xy], an allocation of its own made on first use (nullptr: never
+  // called -- the batch then holds and enqueues nothing for them)
+  struct LabelScratch* lab = nullptr;
   // iteration history (gpet_batch_set_history): storage of its own, B regions of hist.edge_bytes (gpet_history_plan.h); hist.level == 0
   // and d_hist == nullptr: off -- the loop then enqueues nothing for it
   char* d_hist = nullptr;
@@ -361,6 +367,9 @@ int history_clear(gpet_batch* b, int e);
 // ---- gpet_api_ensemble.hip ------------------------------------------------------------------------------------------------
 // frees the scratch of the ensemble entry points (gpet_batch_destroy)
 void ensemble_free(gpet_batch* b);
+// ---- gpet_api_label.hip ---------------------------------------------------------------------------------------------------
+// frees the scratch of the label-map entry points and clears the pointer (gpet_ctx_destroy, gpet_batch_destroy)
+void label_free(struct LabelScratch*& s);
 // ---- gpet_api_init.hip ----------------------------------------------------------------------------------------------------
 // the host copy of a banded batch's (i_lo, i_hi) and full-frame init tables made current again after gpet_batch_init_follow (one wait;
 // nothing to do when they are)

@@ -18,6 +18,7 @@
 #include "gpet_ensemble_plan.h"  // seed ensembles: layout of the returned buffer, validation, member tables, tile width
 #include "gpet_band_plan.h"  // tracking bands: refusals, the placement rule, the sizes of what a banded batch owns in addition
 #include "gpet_init_plan.h"  // endpoint tracking: the rule that moves the init points, its refusals
+#include "gpet_label_plan.h"  // label maps: the two rules, their refusals, the fill kernels' launch shapes
 #include "gpet_warm_plan.h"  // warm start from a group's medoid / best cost / consensus or from another edge: source per edge, refusals
 
 namespace gpet {
@@ -190,6 +191,28 @@ hipError_t launch_final_costs(hipStream_t st, const EdgeDev* d_edges, int B, con
 hipError_t launch_ensemble(hipStream_t st, const EdgeDev* d_edges, int B, int G, const EnsembleGroup* d_groups, const int32_t* d_members,
                            const int32_t* d_member_group, const int32_t* d_wg_group, const int32_t* d_wg_tile, int n_wg, size_t lds,
                            double tol, long long len_cap, const EnsembleLayout& L, const double* d_cost, int* d_off_acc, char* d_dst);
+// label maps (gpet_k_label.inc; the rules: gpet_label_plan.h).  A contributing edge as the kernels read it, in map order: its grid, its
+// map (the centre of Rule 2), and where its rows come from -- edge >= 0: the converged fit of that edge of the batch; edge < 0: the int64
+// rows the caller gave, row_off into them
+struct LabelEdge {
+  int32_t x_st, len, edge, map;
+  long long row_off;
+};
+// T [n_used][N] int32: d_rows for the stand-alone form (d_edges unused), d_edges / d_r0_fit (nullptr: no bands) for the batch form
+hipError_t launch_label_thresholds(hipStream_t st, const LabelEdge* d_le, int n_used, const long long* d_rows, const EdgeDev* d_edges,
+                                   const long long* d_r0_fit, int M, int N, bool extend, int* d_T);
+// map f of n_maps (edges map_off[f] .. map_off[f + 1] of T; L the most on one map) to d_out0 + d_out_off[f]: M x N bytes, or N x M transposed
+hipError_t launch_label_fill(hipStream_t st, const int* d_T, const int32_t* d_map_off, int n_maps, int L, unsigned char* d_out0,
+                             const long long* d_out_off, int M, int N, bool transposed);
+hipError_t launch_label_thick(hipStream_t st, const int* d_T, const int32_t* d_map_off, int n_maps, int M, int N, int L, int* d_thick);
+// d_xy [n_used][n_theta][2] from the converged fits; d_cxy: cx [n_centres] | cy [n_centres]
+hipError_t launch_label_vertices(hipStream_t st, const LabelEdge* d_le, int n_used, const EdgeDev* d_edges, const long long* d_r0_fit,
+                                 const double* d_cxy, int n_centres, const double* d_cos, const double* d_sin, double r0, double dr, int n_theta,
+                                 double* d_xy);
+// contour u: d_n_vert[u] vertices from pair d_vert_off[u] of d_xy on; n_vert_max: the most of any
+hipError_t launch_label_fill_xy(hipStream_t st, const double* d_xy, const long long* d_vert_off, const int32_t* d_n_vert,
+                                const int32_t* d_map_off, int n_maps, int n_vert_max, unsigned char* d_out0, const long long* d_out_off, int Ms,
+                                int Ns);
 hipError_t launch_score_kde_fused_tail(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);
 
 // converged fit on the device (gpet_lbfgsb.hip): training sets + start points, L-BFGS-B state machines, best restart

@@ -37,5 +37,6 @@ namespace gpet {
 #include "gpet_k_ensemble.inc"
 #include "gpet_k_band.inc"
 #include "gpet_k_init.inc"
+#include "gpet_k_label.inc"
 
 }  // namespace gpet

@@ -1176,6 +1176,46 @@ class GP_Edge_Tracing_Batch(object):
             rec = swap_record(rec, ("trace",))
         return results_from_records(rec, self.return_std)
 
+    def default_map_of(self):
+        """The map every edge goes on when ``label_maps`` is not told: the raw frame (or image) the edge reads."""
+        if self._edge_frames is not None:
+            return list(self._edge_frames)
+        b = self._batch
+        if b.image_of is not None:
+            return list(b.image_of)
+        return [0] * self.B if b.share_image else list(range(self.B))
+
+    def label_maps(self, map_of=None, extend=False, thickness=False, space=None, out_device_ptrs=None, thick_device_ptr=None):
+        """The regions the traced edges bound, as uint8 label maps made on the device from the converged fits where they lie
+        (gpet_batch_label_maps / gpet_batch_label_maps_xy; the rules: include/gpet_hip.h "label maps") -- equal to
+        ``gpet_utils.label_maps`` of the traces this object returned.  Valid when ``results`` is, raises what it raises; the trace,
+        the fits and a kept ensemble are not touched.
+        ``map_of``: one map index per edge, -1 for "on no map"; default: the frame (image) the edge reads -- ``image_of``, e with one
+        image per edge, 0 with a shared image.  With seed ensembles choose the members yourself, e.g. -1 everywhere but the medoids
+        of ``ensemble()``.  An edge the device stopped with an error contributes nothing.
+        Returns (n_maps, M, N) uint8 in the frame's shape and orientation -- ``label[f, r, c]`` = edges of map f at or above pixel
+        (r, c); a vertical batch: at or left of it; a banded batch: full-frame rows -- and with ``thickness`` also (n_maps, L + 1, N')
+        int32, rows (a vertical batch: columns) of label l per column (per row).  ``extend``: columns outside an edge's grid take its
+        first / last row instead of not counting.
+        ``space`` (a polar batch): ``'polar'`` (default) -- the maps above in polar rows and columns; ``'frame'`` -- (n_maps, Ms, Ns)
+        maps on the source frames' shape: the pixels inside the closed outline of every edge of the map (even-odd rule on the
+        vertices ``polar_trace_xy`` gives, the seam's second column left out), with the batch's own spec, the centre of map f the
+        f-th.  ``space='frame'`` on a batch without ``polar`` raises ValueError.
+        ``out_device_ptrs`` (one device address per map; ``thick_device_ptr`` for the thickness): the maps are written there, the
+        work is enqueued on the batch's stream, nothing is waited for and None is returned."""
+        if space not in (None, "polar", "frame"):
+            raise ValueError("space must be None, 'polar' or 'frame', not %r" % (space,))
+        if space == "frame" and self.polar is None:
+            raise ValueError("space='frame' maps closed contours back to their frames: the batch was not built on polar frames (polar=)")
+        if map_of is None:
+            map_of = self.default_map_of()
+        if space == "frame":
+            if extend or thickness:
+                raise ValueError("extend and thickness belong to the row maps (space='polar')")
+            return self._batch.label_maps_xy(self.polar, self._src_shape, map_of, out_device_ptrs=out_device_ptrs)
+        return self._batch.label_maps(map_of, extend=extend, transposed=self._tr, thickness=thickness, out_device_ptrs=out_device_ptrs,
+                                      thick_device_ptr=thick_device_ptr)
+
     def final_costs(self):
         """(B,) f64: the scorer's cost of every edge's converged mean curve on its own gradient image -- the reference's
         ``cost_funct(optim_mean_curve)`` (gpet.py:888-890), the algorithm's own figure of merit for a finished trace -- computed on

@@ -267,3 +267,44 @@ def polar_trace_xy(result, polar, frame=0):
                                                            for c in (lower, upper)))
     trace = np.asarray(result)
     return np.stack(polar_to_xy(trace[:, 0], trace[:, 1], polar, frame), axis=1)
+
+
+# ---- label maps: traces rasterised into masks on the device (csrc/gpet_label_plan.h) -----------------------------------
+def _trace_list(traces):
+    if isinstance(traces, np.ndarray) and traces.ndim == 2:
+        return [traces]
+    return [np.asarray(t) for t in traces]
+
+
+def label_maps(traces, shape, map_of=None, extend=False, thickness=False, transpose=False, ctx=None):
+    """The regions between traced edges as uint8 label maps, made on the GPU (gpet_label_maps; Rule 1 of include/gpet_hip.h "label
+    maps").  ``traces``: one (Lg, 2) yx trace as every tracer returns it, or a list of them -- consecutive columns, the rows integers;
+    ``shape`` = (M, N) of the frame; ``map_of[e]`` the map edge e goes on, -1 for none (None: all edges on one map).  Returns
+    (n_maps, M, N) uint8 with ``label[f, r, c]`` = the number of edges of map f whose row at column c is <= r: for one edge the
+    reference's ``pred_bin`` (gpet_utils.py:303-307, "at or below the trace"), for E stacked edges the layer index 0 .. E; edges may
+    cross.  Rows outside the frame are clamped, ``_lib.LABEL_NO_ROW`` does not count.  A column outside an edge's grid is not counted
+    for it -- with ``extend`` the edge's first / last row is used there.  ``thickness``: also (n_maps, L + 1, N) int32, the number of
+    rows of label l in every column (its sum over the columns is the layer's area), L the most edges on one map.
+    ``transpose``: the traces are those of vertical edges -- (row, column) of the frame, one entry per consecutive row -- and
+    ``label[f, r, c]`` counts the edges whose column at row r is <= c; the thickness is then per frame row."""
+    tr = _trace_list(traces)
+    M, N = int(shape[0]), int(shape[1])
+    a, b = (1, 0) if transpose else (0, 1)  # (the traced coordinate, the grid coordinate)
+    for e, t in enumerate(tr):
+        if t.ndim != 2 or t.shape[1] != 2 or t.shape[0] < 1:
+            raise ValueError("trace %d has shape %s, not (Lg, 2)" % (e, t.shape))
+        if not np.array_equal(t[:, b], t[0, b] + np.arange(t.shape[0])):
+            raise ValueError("trace %d does not run over consecutive %s" % (e, "rows" if transpose else "columns"))
+    out = (ctx or _ctx()).label_maps((N, M) if transpose else (M, N), [int(t[0, b]) for t in tr], [t[:, a] for t in tr], map_of, extend=extend,
+                                     transposed=transpose, thickness=thickness)
+    return out
+
+
+def outline_label_maps(outlines_xy, shape, map_of=None, ctx=None):
+    """The inside of closed outlines as uint8 label maps, made on the GPU (gpet_label_maps_xy; Rule 2 of include/gpet_hip.h "label
+    maps").  ``outlines_xy``: one (n, 2) float64 array of (x, y) vertices in frame coordinates, 4 <= n <= 4096, or a list of them --
+    for instance ``polar_trace_xy(result, polar)[:-1]`` (the seam's second column repeats the first vertex); ``shape`` = (Ms, Ns).
+    Returns (n_maps, Ms, Ns) uint8: how many outlines of its map the pixel (x = column, y = row) lies inside by the even-odd rule --
+    two nested outlines give lumen 2, wall 1, outside 0.  An outline with a vertex that is not finite contributes nothing."""
+    outs = _trace_list(outlines_xy)
+    return (ctx or _ctx()).label_maps_xy(shape, outs, map_of)

@@ -67,6 +67,24 @@ def _inits_of(init):
     return [a], False
 
 
+def resolve_labels(labels):
+    """``labels`` as ``SequenceTracer`` accepts it, decided without a device: None / False (off), True, or a dict with any of
+    ``extend``, ``thickness``, ``space`` -> None or dict(extend=, thickness=, space=).  ValueError for anything else."""
+    if labels is None or labels is False:
+        return None
+    out = dict(extend=False, thickness=False, space=None)
+    if labels is True:
+        return out
+    if not isinstance(labels, dict) or not set(labels) <= set(out):
+        raise ValueError("labels must be True or dict(extend=, thickness=, space=), not %r" % (labels,))
+    out.update(labels)
+    if out["space"] not in (None, "polar", "frame"):
+        raise ValueError("labels: space must be None, 'polar' or 'frame', not %r" % (out["space"],))
+    if out["space"] == "frame" and (out["extend"] or out["thickness"]):
+        raise ValueError("labels: extend and thickness belong to the row maps (space='polar')")
+    return out
+
+
 class SequenceTracer(object):
     """Traces ``init`` through ``frames`` (T gradient images of one shape) in ``n_chains`` chains on one GPU.
 
@@ -114,13 +132,25 @@ class SequenceTracer(object):
     ``polar=dict(centre=(cx, cy) | (T, 2) array, n_r=, n_theta=, ...)`` with ``grad_kernel``: closed contours (``GP_Edge_Tracing_Batch``)
     -- every frame is unwrapped to (radius x angle) on the device, around its own centre where ``centre`` has one per frame, and the
     sequence is, bit for bit, the one on ``unwrap_polar_imgs(frames, **polar)``; ``init`` (``closed_init(row, polar)``), results and
-    everything else are in polar rows and columns.  ``polar`` (attribute) is the resolved spec.  Not with ``orientation='vertical'``."""
+    everything else are in polar rows and columns.  ``polar`` (attribute) is the resolved spec.  Not with ``orientation='vertical'``.
+
+    ``labels=True`` or ``dict(extend=, thickness=, space=)``: after every step's trace the label map of every frame -- all E edges of
+    the frame on one map, ``GP_Edge_Tracing_Batch.label_maps`` -- is made on the device from that step's fits, before the next
+    ``set_frame``: ``labels[t]`` is frame t's (M, N) uint8 map (``space='frame'`` with ``polar``: on the source frame's shape),
+    ``thickness[t]`` its (E + 1, N) int32 profiles when asked for.  Not with ``ensemble_seeds`` (ValueError): the ensemble of a step
+    is known only after the swap, when the fits' results are no longer valid -- labels from an ensemble's consensus are out of scope."""
 
     _UNSET = object()
 
     def __init__(self, frames, init, n_chains=1, warm_every=None, seed=_UNSET, seeds=None, *, device=0, _ctx=None, grad_kernel=None,
                  denoise=None, kernel_of=None, ensemble_seeds=None, ensemble_tol=2, warm_from='medoid', band_rows=None, init_follow=None,
-                 orientation="horizontal", polar=None, **kw):
+                 orientation="horizontal", polar=None, labels=None, **kw):
+        self._labels = resolve_labels(labels)
+        if self._labels is not None and ensemble_seeds is not None:
+            raise ValueError("labels and ensemble_seeds are alternatives: a step's ensemble is known only after the swap to the next "
+                             "frame, when the fits the maps are made from are no longer valid")
+        if self._labels is not None and self._labels["space"] == "frame" and polar is None:
+            raise ValueError("labels: space='frame' maps closed contours back to their frames: it needs polar")
         if ensemble_seeds is not None:
             if seed is not SequenceTracer._UNSET or seeds is not None:
                 raise ValueError("ensemble_seeds are the seeds of every frame's members: seed / seeds are not accepted with them")
@@ -153,6 +183,8 @@ class SequenceTracer(object):
         resolve_init_follow(init_follow)  # (refused here, before a frame is looked at)
         self.init_follow = init_follow
         self.inits = [None] * self.T  # the init points every frame was traced with
+        self.labels = [None] * self.T     # labels=: the label map of every frame
+        self.thickness = [None] * self.T  # labels=dict(thickness=True): its thickness profiles
         self._cur = {}  # (chain, edge of the frame) -> the init points the chain's last frame left, in the order of `init`
         self.kw = dict(kw)
         self.kw.pop("obs", None)
@@ -225,6 +257,18 @@ class SequenceTracer(object):
             if self._tr:
                 got = swap_xy(got)
             self.inits[f] = got if self.multi else got[0]
+
+    def _file_labels(self, active):
+        """The label maps of the step just traced, one per frame (map = the chain's frame), filed per frame."""
+        E, K = self.E, self.K
+        opts = self._labels
+        got = self._tracer.label_maps([ci for ci in range(len(active)) for _ in range(E * K)], extend=opts["extend"],
+                                      thickness=opts["thickness"], space=opts["space"])
+        maps, thick = got if opts["thickness"] else (got, None)
+        for ci, (_, f) in enumerate(active):
+            self.labels[f] = maps[ci]
+            if thick is not None:
+                self.thickness[f] = thick[ci]
 
     def _result_out(self, res):
         """A result of the step's batch as it is handed back: on a vertical sequence with the trace in the frame's coordinates."""
@@ -376,6 +420,8 @@ class SequenceTracer(object):
                     pending = None
             self._file_inits(active)
             out = self._tracer(max_iter)
+            if self._labels is not None:  # (from this step's fits, before the next set_frame invalidates them)
+                self._file_labels(active)
             pending = (active, out, list(self._tracer.timings["iters"]), tab["group_of"])
             if not ens:
                 self._close_step(pending, None, results, prev)

@@ -924,6 +924,66 @@ int gpet_batch_init_follow(gpet_batch* b, int window, int cols, int64_t* init_ou
 int gpet_batch_set_init(gpet_batch* b, const int64_t* const* init_xy);
 int gpet_batch_init_xy(gpet_batch* b, int64_t* out);
 
+/* ---- label maps: traces rasterised into uint8 masks on the device (the rules: csrc/gpet_label_plan.h) ----------
+ * Rule 1, row maps.  A map is M x N uint8.  Contributing edge e has a grid [x_st, x_en] of len = x_en - x_st + 1 columns, int64 rows
+ * t_e[k], k = 0 .. len - 1, and a map index map_of[e] in [-1, n_maps); -1: the edge is in no map.  The edges of a map need not be
+ * adjacent.  The threshold of edge e at frame column c, in this order:
+ *   1. x_st <= c <= x_en: k = c - x_st;
+ *   2. else with GPET_LABELS_EXTEND: k = 0 left of the grid, k = len - 1 right of it;
+ *   3. else the edge does not count at c: T = M;
+ *   4. a row equal to GPET_LABEL_NO_ROW does not count: T = M;
+ *   5. else T_e[c] = min(max(t_e[k], 0), M).
+ *   label[f][r][c] = #{e : map_of[e] = f, r >= T_e[c]}: for one edge the mask "at or below the trace", for stacked edges the layer index,
+ *       and edges that cross need no ordering.
+ *   thick[f][l][c] = #{r in [0, M) : label[f][r][c] = l}, int32 [n_maps][L + 1][N], L the largest number of edges on one map: the
+ *       thickness profile of layer l; its sum over c is the layer's area.
+ * At most GPET_LABEL_EDGES_MAX edges on a map.  GPET_LABELS_TRANSPOSED writes every map as N x M with out[c][r] = label[r][c] (the
+ * frame's own orientation for a vertical batch); thick is the same either way.
+ * Rule 2, frame maps of closed outlines.  A map is Ms x Ns uint8 in the coordinates of the raw frame.  Contour e has n vertices
+ * (X_j, Y_j), f64, 4 <= n <= GPET_LABEL_VERTS_MAX.  For the pixel (px, py), integers taken as doubles, and every j with (xi, yi) = V_j,
+ * (xj, yj) = V_((j + 1) mod n):
+ *   1. if (yi > py) != (yj > py): a = (px - xi) * (yj - yi), b = (xj - xi) * (py - yi), every product rounded once, no division;
+ *   2. the pixel toggles when yj > yi ? a < b : a > b.
+ * The pixel is inside when the toggles are odd in number; label_xy[f][py][px] is the number of contours of map f it is inside (two
+ * nested outlines: lumen 2, wall 1, outside 0).  A contour with a vertex that is not finite contributes nothing.
+ *   gpet_label_maps(ctx, M, N, n_edges, x_st, len, rows, map_of, n_maps, flags, out, thick)   Rule 1 on the caller's rows: rows holds
+ *       len[0] + len[1] + ... int64, edge after edge (host).  out: n_maps pointers to M * N bytes; thick (may be NULL):
+ *       gpet_label_thick_count elements.
+ *   gpet_label_maps_xy(ctx, Ms, Ns, n_contours, n_vert, xy, map_of, n_maps, flags, out)   Rule 2 on the caller's vertices: xy holds
+ *       (x, y) pairs, contour after contour (host).
+ *   gpet_batch_label_maps(batch, map_of, n_maps, flags, out, thick)   Rule 1 from the batch's converged fits where they lie:
+ *       t_e[k] = (int64) rint(mean[k]) as gpet_batch_results rounds it, plus the first row of the band the fit was made in on a banded
+ *       batch; a mean that is not finite is GPET_LABEL_NO_ROW, and an edge whose status is not GPET_OK contributes nothing.  The maps
+ *       have the batch's full-frame shape (M x N as the batch traces it; a banded batch: full-frame rows).
+ *   gpet_batch_label_maps_xy(batch, polar, Ms, Ns, map_of, n_maps, flags, out)   Rule 2 from the converged fits of a batch on polar
+ *       frames: polar is the spec the frames were unwrapped with, n_centres 1 or n_maps, the centre of map f is centre f.  Every
+ *       contributing edge has x_st = pad and x_en = pad + n_theta (else GPET_ERR_BAD_ARG naming the edge).  Vertex j = 0 .. n_theta - 1
+ *       comes from grid index j: rho = r0 + (double)t dr, X = cx + rho cos_t[j], Y = cy + rho sin_t[j], not clamped; the seam's second
+ *       column is no vertex, the polygon closes from n_theta - 1 to 0.
+ *   gpet_label_thick_count(n_maps, L, N, count)   the int32 elements of thick.
+ * flags: GPET_LABELS_EXTEND, GPET_LABELS_TRANSPOSED (Rule 1), GPET_LABELS_OUT_ON_DEVICE: out[] and thick are DEVICE pointers, the work
+ * is enqueued on the context's stream and nothing waits; otherwise the call is complete on return.
+ * The batch forms are valid exactly when gpet_batch_results is (GPET_ERR_BAD_ARG with a message otherwise); they leave the loop's
+ * state, the fits and a kept ensemble untouched, and their scratch is an allocation of its own, made on first use: a batch that never
+ * asks for a map holds and enqueues nothing for it.  Refused with GPET_ERR_BAD_ARG, gpet_last_error carrying label_check's words, and
+ * nothing launched: a null pointer, n_maps < 1, a map_of entry outside [-1, n_maps), a map with no edge or with more than 32, a grid
+ * outside [0, N), M * N above 2^31, a vertex count outside [4, 4096], a frame below 2 x 2.  (Added without a change of
+ * GPET_ABI_VERSION: the surface only grew.) */
+#define GPET_LABELS_EXTEND 1u
+#define GPET_LABELS_TRANSPOSED 2u
+#define GPET_LABELS_OUT_ON_DEVICE 4u
+#define GPET_LABEL_EDGES_MAX 32
+#define GPET_LABEL_VERTS_MAX 4096
+#define GPET_LABEL_NO_ROW INT64_MIN
+int gpet_label_maps(gpet_ctx* ctx, int M, int N, int n_edges, const int32_t* x_st, const int32_t* len, const int64_t* rows,
+                    const int32_t* map_of, int n_maps, unsigned int flags, void* const* out, int32_t* thick);
+int gpet_label_maps_xy(gpet_ctx* ctx, int Ms, int Ns, int n_contours, const int32_t* n_vert, const double* xy, const int32_t* map_of,
+                       int n_maps, unsigned int flags, void* const* out);
+int gpet_batch_label_maps(gpet_batch* b, const int32_t* map_of, int n_maps, unsigned int flags, void* const* out, int32_t* thick);
+int gpet_batch_label_maps_xy(gpet_batch* b, const gpet_polar* polar, int Ms, int Ns, const int32_t* map_of, int n_maps,
+                             unsigned int flags, void* const* out);
+int gpet_label_thick_count(int n_maps, int L, int N, int64_t* count);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
