@@ -36,7 +36,6 @@ PIX_OF_DTYPE = {np.dtype(np.uint8): PIX_U8, np.dtype(np.uint16): PIX_U16, np.dty
 # denoising techniques / boundary modes of gpet_denoise (GPET_DN_*, GPET_DN_MODE_*)
 DN_NONE, DN_MEDIAN, DN_MINIMUM, DN_GAUSSIAN, DN_TVC = range(5)
 DN_OF_TECHNIQUE = {"median": DN_MEDIAN, "minimum": DN_MINIMUM, "gaussian": DN_GAUSSIAN, "tvc": DN_TVC}
-DN_NOT_BUILT = ("nl", "wavelet", "tvb")  # techniques of the reference's denoise() that are not stencils the device runs
 DN_MODE_OF_NAME = {"reflect": 0, "nearest": 1}
 DN_WINDOW_MAX = 81
 
@@ -61,30 +60,15 @@ def denoise_spec(denoise):
     kwargs carry scipy's / scikit-image's own names: ``size`` and ``mode`` for 'median' / 'minimum'; ``sigma``, ``truncate``,
     ``order`` (0 only) and ``mode`` for 'gaussian'; ``weight``, ``eps`` and ``n_iter_max`` for 'tvc'.  ValueError names a key
     the device does not take (footprint, origin, cval, multichannel, ...) or a value it refuses; NotImplementedError names a
-    technique of the reference that is not built ('nl', 'wavelet', 'tvb').  A GpetDenoise passes through; None stays None."""
+    technique that is a stage of its own and no gpet_denoise technique (PRE_STAGES).  A GpetDenoise passes through; None stays None."""
     if denoise is None or isinstance(denoise, GpetDenoise):
         return denoise
     try:
         technique, kwargs = denoise
     except (TypeError, ValueError):
         raise ValueError("denoise must be a (technique, kwargs) pair")
-    if technique == "nl":  # (a stage of its own: RawFrames takes it through nlmeans_spec)
-        raise NotImplementedError("denoising technique 'nl' is no gpet_denoise technique: with fast_mode=False it is built as a "
-                                  "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built under "
-                                  "this name: it is the technique 'nl_fast' (nlmeans_fast_spec, Context.nlmeans_fast_images)")
-    if technique == "nl_fast":  # (a stage of its own: RawFrames takes it through nlmeans_fast_spec)
-        raise NotImplementedError("denoising technique 'nl_fast' is no gpet_denoise technique: it is built as a stage of its own "
-                                  "(nlmeans_fast_spec, Context.nlmeans_fast_images)")
-    if technique == "wavelet":  # (a stage of its own as well: RawFrames takes it through wavelet_spec)
-        raise NotImplementedError("denoising technique 'wavelet' is no gpet_denoise technique: it is built as a stage of its own "
-                                  "(wavelet_spec, Context.wavelet_images) and runs when kwargs names the wavelet, e.g. "
-                                  "dict(wavelet='db1')")
-    if technique == "tvb":  # (the third such stage: RawFrames takes it through tvb_spec)
-        raise NotImplementedError("denoising technique 'tvb' is no gpet_denoise technique: it is built as a stage of its own "
-                                  "(tvb_spec, Context.tvb_images) and runs when kwargs gives weight, e.g. dict(weight=5)")
-    if technique in DN_NOT_BUILT:
-        raise NotImplementedError("denoising technique %r is not built for the device (built: %s)"
-                                  % (technique, ", ".join(sorted(DN_OF_TECHNIQUE))))
+    if technique in PRE_STAGES:  # (a stage of its own: RawFrames takes it through the stage's from_kwargs)
+        raise NotImplementedError(PRE_STAGES[technique].not_a_filter)
     if technique not in DN_OF_TECHNIQUE:
         raise ValueError("unknown denoising technique %r" % (technique,))
     kw = dict(kwargs or {})
@@ -131,6 +115,24 @@ def denoised_dtype(dn, pix):
     return [dt for dt, code in PIX_OF_DTYPE.items() if code == pix][0]
 
 
+class PreSpec(object):
+    """What the specs of the stages of their own share (PRE_STAGES below).  Every such class says: ``technique`` its name in
+    gpet_utils.denoise, ``symbol`` the library call, ``out_on_device`` that call's flag for device outputs, ``not_a_filter`` what
+    denoise_spec answers for the technique, ``from_kwargs`` (kwargs -> spec; the module function of the stage) -- and may replace
+    the three defaults here.  ``c`` is the C struct of the call."""
+    reports_n_iter = False  # the call ends with an int32 n_iter[] (or null) behind out[]
+
+    def check_frames(self, shape):
+        """Refuses (M, N) frames the stage does not take, before a device is needed (ValueError); by default none."""
+
+    def arg(self):
+        return C.byref(self.c)
+
+    def call_arg(self, T, shape):
+        """-> (the spec argument of a call on T frames of ``shape``, what must stay alive while it runs)."""
+        return C.byref(self.c), None
+
+
 # non-local means (gpet_nlmeans, GPET_NLM_*): a stage of its own in front of the raw-frame path, not a gpet_denoise technique
 NLM_OUT_ON_DEVICE = 8  # gpet_nlmeans_images: out[] are device pointers
 NLM_PATCH_MAX, NLM_DIST_MAX = 15, 31
@@ -155,17 +157,18 @@ def nlmeans_taps(patch_size, h):
     return w
 
 
-class NlmeansSpec(object):
+class NlmeansSpec(PreSpec):
     """What nlmeans_spec returns: ``c`` the gpet_nlmeans of the call, ``taps`` the (s, s) float64 array it points to (kept alive
     here), ``s`` the odd patch extent."""
+    technique, symbol, out_on_device = "nl", "gpet_nlmeans_images", NLM_OUT_ON_DEVICE
+    not_a_filter = ("denoising technique 'nl' is no gpet_denoise technique: with fast_mode=False it is built as a "
+                    "stage of its own (nlmeans_spec, Context.nlmeans_images); fast_mode=True is not built under "
+                    "this name: it is the technique 'nl_fast' (nlmeans_fast_spec, Context.nlmeans_fast_images)")
 
     def __init__(self, patch_size, patch_distance, h, sigma, taps):
         self.s = patch_size + (1 if patch_size % 2 == 0 else 0)
         self.taps = np.ascontiguousarray(taps, dtype=np.float64)
         self.c = GpetNlmeans(patch_size=patch_size, patch_distance=patch_distance, h=h, sigma=sigma, taps=self.taps.ctypes.data)
-
-    def arg(self):
-        return C.byref(self.c)
 
 
 def nlmeans_spec(kwargs, taps=None):
@@ -203,8 +206,7 @@ def nlmeans_spec(kwargs, taps=None):
 
 
 # fast-mode non-local means (gpet_nlmeans_fast): scikit-image's DEFAULT denoise_nl_means, the technique 'nl_fast'; a stage of its
-# own with the classic stage's flags
-NLF_KEYS = NLM_KEYS
+# own with the classic stage's flags and keys
 NLF_STRIP = 64  # rows a wave takes at a time (gpet_nlfast_plan.h: NLF_STRIP)
 NLF_CHUNK_BUDGET = 256 << 20  # bytes a chunk's workspaces and staging stay inside (gpet_nlfast_plan.h: NLF_CHUNK_BUDGET)
 
@@ -213,15 +215,15 @@ class GpetNlmeansFast(C.Structure):
     _fields_ = [("patch_size", C.c_int32), ("patch_distance", C.c_int32), ("h", C.c_double), ("sigma", C.c_double)]
 
 
-class NlmeansFastSpec(object):
+class NlmeansFastSpec(PreSpec):
     """What nlmeans_fast_spec returns: ``c`` the gpet_nlmeans_fast of the call, ``s`` the odd patch extent."""
+    technique, symbol, out_on_device = "nl_fast", "gpet_nlmeans_fast_images", NLM_OUT_ON_DEVICE
+    not_a_filter = ("denoising technique 'nl_fast' is no gpet_denoise technique: it is built as a stage of its own "
+                    "(nlmeans_fast_spec, Context.nlmeans_fast_images)")
 
     def __init__(self, patch_size, patch_distance, h, sigma):
         self.s = patch_size + (1 if patch_size % 2 == 0 else 0)
         self.c = GpetNlmeansFast(patch_size=patch_size, patch_distance=patch_distance, h=h, sigma=sigma)
-
-    def arg(self):
-        return C.byref(self.c)
 
 
 def nlmeans_fast_spec(kwargs):
@@ -232,8 +234,8 @@ def nlmeans_fast_spec(kwargs):
     a value the device refuses; ``fast_mode=False`` raises a ValueError that points to 'nl', the classic algorithm."""
     kw = dict(kwargs or {})
     for k in kw:
-        if k not in NLF_KEYS:
-            raise ValueError("denoise: keyword %r of 'nl_fast' is not supported on the device (supported: %s)" % (k, ", ".join(NLF_KEYS)))
+        if k not in NLM_KEYS:
+            raise ValueError("denoise: keyword %r of 'nl_fast' is not supported on the device (supported: %s)" % (k, ", ".join(NLM_KEYS)))
     if not kw.get("fast_mode", True):
         raise ValueError("denoise: fast_mode=False of 'nl_fast': the technique is the library's fast algorithm; the classic one "
                          "is the technique 'nl' with fast_mode=False")
@@ -322,9 +324,13 @@ def wavelet_out_len(n, n_taps):
     return (n + n_taps - 1) // 2
 
 
-class WaveletSpec(object):
+class WaveletSpec(PreSpec):
     """What wavelet_spec returns: ``c`` the gpet_wavelet of the call without what depends on the frames (VisuShrink's constant,
     the injected thresholds: for_frames fills them in), ``name`` the wavelet, ``thresholds`` the injected table or None."""
+    technique, symbol, out_on_device = "wavelet", "gpet_wavelet_images", WV_OUT_ON_DEVICE
+    not_a_filter = ("denoising technique 'wavelet' is no gpet_denoise technique: it is built as a stage of its own "
+                    "(wavelet_spec, Context.wavelet_images) and runs when kwargs names the wavelet, e.g. "
+                    "dict(wavelet='db1')")
 
     def __init__(self, name, dec_lo, levels, mode, method, sigma, rescale_sigma, thresholds=None, ppf=WV_PPF75):
         self.name, self.dec_lo = name, [float(v) for v in dec_lo]
@@ -373,6 +379,9 @@ class WaveletSpec(object):
             keep = np.ascontiguousarray(t)
             c.thresholds, c.n_thresholds = keep.ctypes.data, keep.size
         return c, keep
+
+    check_frames = levels_on  # (refuses levels the frames do not allow)
+    call_arg = for_frames
 
 
 def wavelet_spec(kwargs, thresholds=None):
@@ -435,14 +444,20 @@ class GpetTvb(C.Structure):
     _fields_ = [("weight", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int32), ("isotropic", C.c_int32)]
 
 
-class TvbSpec(object):
+class TvbSpec(PreSpec):
     """What tvb_spec returns: ``c`` the gpet_tvb of the call."""
+    technique, symbol, out_on_device = "tvb", "gpet_tvb_images", TVB_OUT_ON_DEVICE
+    not_a_filter = ("denoising technique 'tvb' is no gpet_denoise technique: it is built as a stage of its own "
+                    "(tvb_spec, Context.tvb_images) and runs when kwargs gives weight, e.g. dict(weight=5)")
+    reports_n_iter = True
 
     def __init__(self, weight, eps, max_iter, isotropic):
         self.c = GpetTvb(weight=weight, eps=eps, max_iter=max_iter, isotropic=int(bool(isotropic)))
 
-    def arg(self):
-        return C.byref(self.c)
+    def check_frames(self, shape):
+        if min(shape) < 2 or min(shape) > TVB_DIAG_MAX:
+            raise ValueError("denoise: 'tvb' takes frames of at least 2 x 2 pixels whose smaller extent is at most %d, not %d x %d"
+                             % (TVB_DIAG_MAX, shape[0], shape[1]))
 
 
 def tvb_spec(kwargs):
@@ -470,16 +485,12 @@ def tvb_spec(kwargs):
     return TvbSpec(float(weight), float(eps), int(max_iter), bool(kw.get("isotropic", True)))
 
 
-# the stages of their own in front of the raw-frame path: technique -> (kwargs -> spec).  RawFrames.pre holds the spec,
-# RawFrames.pre_resolved runs it (Context.pre_images) into a PreFrames and hands float64 device frames on
-PRE_STAGES = {"nl": nlmeans_spec, "wavelet": wavelet_spec}
-# (PRE_STAGES is pinned as exactly these two by tests/test_wavelet_host.py; every stage of its own, 'tvb' included, is looked up in
-# PRE_STAGE_OF)
-PRE_STAGE_OF = dict(PRE_STAGES, tvb=tvb_spec)
-PRE_SPECS = (NlmeansSpec, WaveletSpec, TvbSpec)
-# (these two are pinned as exactly the three by tests/test_tvb_host.py in their turn; RawFrames looks every stage up in the two below)
-PRE_STAGE_BY_NAME = dict(PRE_STAGE_OF, nl_fast=nlmeans_fast_spec)
-PRE_SPEC_TYPES = PRE_SPECS + (NlmeansFastSpec,)
+# the stages of their own in front of the raw-frame path: technique -> spec class (see PreSpec).  RawFrames.pre holds the spec,
+# RawFrames.pre_resolved runs it (Context.pre_images) into a PreFrames and hands float64 device frames on.  A new stage is one
+# spec class, its from_kwargs and one entry here
+NlmeansSpec.from_kwargs, NlmeansFastSpec.from_kwargs = staticmethod(nlmeans_spec), staticmethod(nlmeans_fast_spec)
+WaveletSpec.from_kwargs, TvbSpec.from_kwargs = staticmethod(wavelet_spec), staticmethod(tvb_spec)
+PRE_STAGES = {cls.technique: cls for cls in (NlmeansSpec, NlmeansFastSpec, WaveletSpec, TvbSpec)}
 
 
 # polar unwrap (gpet_polar, csrc/gpet_polar_plan.h): raw frames resampled to (radius x angle) in front of everything else, so that a
@@ -534,7 +545,9 @@ def polar_tables(n_theta, theta0=0.0):
 class PolarSpec(object):
     """What polar_spec returns: ``centre`` (n_centres, 2) float64 (cx, cy) rows, ``n_r``, ``n_theta``, ``r0``, ``dr``, ``theta0``,
     ``pad`` (None until the gradient kernel is known: ``resolved``), the tables ``cos_t`` / ``sin_t``; ``shape`` = (n_r, W) and
-    ``width`` = W = n_theta + 1 + 2 pad once pad is resolved."""
+    ``width`` = W = n_theta + 1 + 2 pad once pad is resolved.  No denoising technique, but its call has the shape of theirs:
+    ``symbol``, ``out_on_device`` and ``call_arg`` as PreSpec describes them."""
+    symbol, out_on_device, reports_n_iter = "gpet_polar_images", POLAR_OUT_ON_DEVICE, False
 
     def __init__(self, centre, n_r, n_theta, r0, dr, theta0, pad):
         self.centre, self.n_r, self.n_theta, self.r0, self.dr, self.theta0, self.pad = centre, n_r, n_theta, r0, dr, theta0, pad
@@ -565,8 +578,8 @@ class PolarSpec(object):
         return polar_refusal(self.n_r, self.n_theta, self.pad, self.r0, self.dr, pix, int(shape[0]), int(shape[1]), self.centre.shape[0],
                              n_img, self.centre[:, 0], self.centre[:, 1])
 
-    def arg(self):
-        """(gpet_polar of the call, what must stay alive while it runs)."""
+    def call_arg(self, T=None, shape=None):
+        """(gpet_polar of the call, what must stay alive while it runs) -- whatever the frames: the signature is PreSpec's."""
         cx, cy = np.ascontiguousarray(self.centre[:, 0]), np.ascontiguousarray(self.centre[:, 1])
         dp = C.POINTER(C.c_double)
         c = GpetPolar(cx=cx.ctypes.data_as(dp), cy=cy.ctypes.data_as(dp), n_centres=cx.shape[0], n_r=self.n_r, n_theta=self.n_theta,
@@ -949,8 +962,8 @@ class RawFrames(object):
     Host frames (``frames``: see native_frames) or, with ``device_ptrs`` (integer device addresses of (M, N) arrays of
     ``dtype`` on the context's device, e.g. ``tensor.data_ptr()``) and ``shape``, nothing on the host at all.
     ``denoise``: optionally how the frames are denoised on the device before the kernel is applied, a ``(technique, kwargs)``
-    pair of gpet_utils.denoise (see denoise_spec); 'nl', 'wavelet' and 'tvb' are stages of their own (nlmeans_spec, wavelet_spec,
-    tvb_spec: the spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
+    pair of gpet_utils.denoise (see denoise_spec); 'nl', 'nl_fast', 'wavelet' and 'tvb' are stages of their own (PRE_STAGES: the
+    spec is ``pre``, and pre_resolved runs it first).  ``kernel=None``: frames to denoise only (Context.denoise_images).
     ``slots=(frame_of, kernel_of)``: a slot table -- ``kernel`` is then a list of kernels (split_kernels) and image g is made of
     frame ``frame_of[g]`` with kernel ``kernel_of[g]`` (the library's *_multi calls); ``len()`` stays the number of frames,
     ``n_slots`` is the number of images.
@@ -961,13 +974,13 @@ class RawFrames(object):
     def __init__(self, kernel, frames=None, device_ptrs=None, dtype=None, shape=None, denoise=None, slots=None, polar=None):
         if (frames is None) == (device_ptrs is None):
             raise ValueError("raw frames come either from the host or as device pointers")
-        # ('nl', 'wavelet' and 'tvb' are stages of their own: the frames go through Context.pre_images into device memory first -- see
-        # pre_resolved)
+        # (the techniques of PRE_STAGES are stages of their own: the frames go through Context.pre_images into device memory first --
+        # see pre_resolved)
         self.pre = None
-        if isinstance(denoise, PRE_SPEC_TYPES):
+        if isinstance(denoise, tuple(PRE_STAGES.values())):
             self.pre, denoise = denoise, None
-        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGE_BY_NAME:
-            self.pre, denoise = PRE_STAGE_BY_NAME[denoise[0]](denoise[1]), None
+        elif isinstance(denoise, (tuple, list)) and len(denoise) == 2 and isinstance(denoise[0], str) and denoise[0] in PRE_STAGES:
+            self.pre, denoise = PRE_STAGES[denoise[0]].from_kwargs(denoise[1]), None
         self.dn = denoise_spec(denoise)
         self.slots = None
         if slots is not None:
@@ -1001,11 +1014,8 @@ class RawFrames(object):
             if why is not None:
                 raise ValueError("%s (%d frames of %d x %d, %d centres)" % ((why, len(self)) + self.src_shape + (self.polar.centre.shape[0],)))
             self.shape = self.polar.shape
-        if self.wv is not None:
-            self.wv.levels_on(self.shape)  # (refuses levels the frames do not allow before a device is needed)
-        if self.tvb is not None and (min(self.shape) < 2 or min(self.shape) > TVB_DIAG_MAX):
-            raise ValueError("denoise: 'tvb' takes frames of at least 2 x 2 pixels whose smaller extent is at most %d, not %d x %d"
-                             % (TVB_DIAG_MAX, self.shape[0], self.shape[1]))
+        if self.pre is not None:
+            self.pre.check_frames(self.shape)  # (refuses frames the stage does not take before a device is needed)
 
     def __len__(self):
         return len(self.ptrs)
@@ -1036,7 +1046,7 @@ class RawFrames(object):
         return self.pre is not None or self.polar is not None
 
     def pre_resolved(self, ctx, buf):
-        """These frames as the raw-frame calls take them: without a stage of its own ('nl', 'wavelet', 'tvb'), self; with one, the frames
+        """These frames as the raw-frame calls take them: without a stage of its own (PRE_STAGES), self; with one, the frames
         denoised into the device memory of ``buf`` (a PreFrames; enqueued on the context's stream) as float64 device frames with
         the same kernels and slot table and no further denoising.  With a polar spec the frames are unwrapped into ``buf`` first
         (Context.polar_images), and whatever else these frames carry -- a stage of its own, which then writes into ``buf.second()``, an
@@ -1055,8 +1065,6 @@ class RawFrames(object):
         ctx.pre_images(self, out_device_ptrs=ptrs)
         kernel = self.kernels if self.slots is not None else self.kernel
         return RawFrames(kernel, device_ptrs=ptrs, dtype=np.float64, shape=(M, N), slots=self.slots)
-
-    nlm_resolved = pre_resolved
 
     def pointer_array(self):
         return (_P * len(self.ptrs))(*self.ptrs)
@@ -1490,9 +1498,6 @@ class PreFrames(object):
             pass
 
 
-NlmFrames = PreFrames  # (the name it had while non-local means was the only such stage)
-
-
 class Context:
     """gpet_ctx: one device + one HIP stream."""
 
@@ -1583,10 +1588,9 @@ class Context:
                                                      denoise=raw.pre if raw.pre is not None else raw.dn))
             finally:
                 buf.close()
-        if raw.tvb is not None:
-            return self.tvb_images(raw, return_n_iter=True)
-        if raw.pre is not None:
-            return self.pre_images(raw), np.zeros(len(raw), dtype=np.int32)
+        if raw.pre is not None:  # (a stage of its own: its sweeps where it counts them, zeros where not)
+            n_iter = np.zeros(len(raw), dtype=np.int32)
+            return self._run_stage(raw, raw.pre, raw.shape, None, n_iter), n_iter
         if raw.dn is None:
             raise ValueError("no denoising technique")
         M, N = raw.shape
@@ -1602,13 +1606,24 @@ class Context:
         tvb_images.  Frames that carry a polar spec are unwrapped first (RawFrames.pre_resolved): the stage runs on those."""
         if raw.polar is not None:
             raise ValueError("frames with a polar spec are unwrapped first: run the stage on raw.pre_resolved(ctx, buf)")
-        if raw.tvb is not None:
-            return self.tvb_images(raw, out_device_ptrs=out_device_ptrs)
-        if raw.nlf is not None:
-            return self.nlmeans_fast_images(raw, out_device_ptrs=out_device_ptrs)
-        if raw.wv is not None:
-            return self.wavelet_images(raw, out_device_ptrs=out_device_ptrs)
-        return self.nlmeans_images(raw, out_device_ptrs=out_device_ptrs)
+        if raw.pre is None:
+            raise ValueError("no stage of its own")
+        return self._run_stage(raw, raw.pre, raw.shape, out_device_ptrs)
+
+    def _run_stage(self, raw, spec, shape, out_device_ptrs, n_iter=None, fill=None):
+        """One batched call of a stage of its own, or of the polar unwrap, on the frames of ``raw``: ``spec`` names the call (``symbol``,
+        ``out_on_device``, ``call_arg``: see PreSpec), ``shape`` is the frames' as the call takes them.  ``n_iter``: (T,) int32 the
+        call fills where the stage counts sweeps (``reports_n_iter``) and leaves alone where not.  ``fill``: called with the spec
+        argument before the call.  -> what _pre_out made: the (T, M, N) float64 result, or None with ``out_device_ptrs``."""
+        T, (M, N) = len(raw), shape
+        out, op, flags = self._pre_out(raw, out_device_ptrs, spec.out_on_device)
+        arg, keep = spec.call_arg(T, (M, N))
+        if fill is not None:
+            fill(arg)
+        tail = (None if n_iter is None else n_iter.ctypes.data_as(C.POINTER(C.c_int32)),) if spec.reports_n_iter else ()
+        self.check(getattr(self.lib, spec.symbol)(self.h, raw.pointer_array(), T, raw.pix, M, N, arg, flags, op, *tail))
+        del keep
+        return out
 
     @staticmethod
     def _pre_out(raw, out_device_ptrs, on_device):
@@ -1631,21 +1646,17 @@ class Context:
         frame a list of dict(aa, ad, da, dd) per level (aa of every level but the coarsest holds the reconstruction)."""
         if raw.wv is None:
             raise ValueError("no wavelet spec")
-        M, N = raw.shape
+        if not report:
+            return self._run_stage(raw, raw.wv, raw.shape, out_device_ptrs)
         T = len(raw)
-        c, keep = raw.wv.for_frames(T, (M, N))
-        rep = None
-        if report:
-            levels, fd = raw.wv.pyramid((M, N))
-            L = len(levels)
-            rep = dict(sigma=np.empty(T), thresholds=np.empty((T, L, 3)), mean_sq=np.full((T, L, 3), np.nan), pyramid=np.empty((T, fd)))
+        levels, fd = raw.wv.pyramid(raw.shape)
+        L = len(levels)
+        rep = dict(sigma=np.empty(T), thresholds=np.empty((T, L, 3)), mean_sq=np.full((T, L, 3), np.nan), pyramid=np.empty((T, fd)))
+
+        def fill(c):
             c.sigma_out, c.thresholds_out = rep["sigma"].ctypes.data, rep["thresholds"].ctypes.data
             c.mean_sq_out, c.coeffs_out = rep["mean_sq"].ctypes.data, rep["pyramid"].ctypes.data
-        out, op, flags = self._pre_out(raw, out_device_ptrs, WV_OUT_ON_DEVICE)
-        self.check(self.lib.gpet_wavelet_images(self.h, raw.pointer_array(), T, raw.pix, M, N, C.byref(c), flags, op))
-        del keep
-        if not report:
-            return out
+        out = self._run_stage(raw, raw.wv, raw.shape, out_device_ptrs, fill=fill)
         pyr = rep.pop("pyramid")
         rep["coeffs"] = [[{k: pyr[g, off + b * mo * no: off + (b + 1) * mo * no].reshape(mo, no).copy()
                            for b, k in enumerate(("aa", "ad", "da", "dd"))} for mo, no, off in levels] for g in range(T)]
@@ -1660,11 +1671,8 @@ class Context:
         without ``return_n_iter``, nothing is waited for.  ``return_n_iter``: also the sweeps every frame ran, (T,) int32."""
         if raw.tvb is None:
             raise ValueError("no split-Bregman spec")
-        M, N = raw.shape
-        out, op, flags = self._pre_out(raw, out_device_ptrs, TVB_OUT_ON_DEVICE)
         n_iter = np.zeros(len(raw), dtype=np.int32) if return_n_iter else None
-        self.check(self.lib.gpet_tvb_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.tvb.arg(), flags, op,
-                                            n_iter.ctypes.data_as(C.POINTER(C.c_int32)) if return_n_iter else None))
+        out = self._run_stage(raw, raw.tvb, raw.shape, out_device_ptrs, n_iter)
         return (out, n_iter) if return_n_iter else out
 
     def polar_images(self, raw, out_device_ptrs=None):
@@ -1674,12 +1682,7 @@ class Context:
         waited for."""
         if raw.polar is None:
             raise ValueError("no polar spec")
-        M, N = raw.src_shape
-        out, op, flags = self._pre_out(raw, out_device_ptrs, POLAR_OUT_ON_DEVICE)
-        c, keep = raw.polar.arg()
-        self.check(self.lib.gpet_polar_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, C.byref(c), flags, op))
-        del keep
-        return out
+        return self._run_stage(raw, raw.polar, raw.src_shape, out_device_ptrs)
 
     def nlmeans_images(self, raw, out_device_ptrs=None):
         """gpet_nlmeans_images: non-local means of every frame of ``raw`` (a RawFrames made with ``denoise=('nl', kwargs)`` or a
@@ -1687,10 +1690,7 @@ class Context:
         write instead (GPET_NLM_OUT_ON_DEVICE; returns None) -- with frames on the device too, nothing is waited for."""
         if raw.nlm is None:
             raise ValueError("no non-local means spec")
-        M, N = raw.shape
-        out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
-        self.check(self.lib.gpet_nlmeans_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlm.arg(), flags, op))
-        return out
+        return self._run_stage(raw, raw.nlm, raw.shape, out_device_ptrs)
 
     def nlmeans_fast_images(self, raw, out_device_ptrs=None):
         """gpet_nlmeans_fast_images: fast-mode non-local means of every frame of ``raw`` (a RawFrames made with
@@ -1699,10 +1699,7 @@ class Context:
         too, nothing is waited for."""
         if raw.nlf is None:
             raise ValueError("no fast-mode non-local means spec")
-        M, N = raw.shape
-        out, op, flags = self._pre_out(raw, out_device_ptrs, NLM_OUT_ON_DEVICE)
-        self.check(self.lib.gpet_nlmeans_fast_images(self.h, raw.pointer_array(), len(raw), raw.pix, M, N, raw.nlf.arg(), flags, op))
-        return out
+        return self._run_stage(raw, raw.nlf, raw.shape, out_device_ptrs)
 
     def label_maps(self, shape, x_st, rows, map_of=None, extend=False, transposed=False, thickness=False, out_device_ptrs=None,
                    thick_device_ptr=None):
@@ -2238,7 +2235,7 @@ class Batch:
         if why is not None:
             raise ValueError(why)
         maps, op, _, _, flag = _label_out(n_maps, (Ms, Ns), out_device_ptrs, 0, None)
-        c, keep = polar.arg()
+        c, keep = polar.call_arg()
         self.ctx.check(self.lib.gpet_batch_label_maps_xy(self.h, C.byref(c), Ms, Ns, m.ctypes.data_as(C.POINTER(C.c_int32)), n_maps, flag, op))
         del keep
         return maps

@@ -141,7 +141,7 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     DESIGN.md 9), so the output is the library's bit for bit wherever the sweep counts agree.  It runs only when kwargs gives
     ``weight``, the library's required argument; without it 'tvb' raises NotImplementedError as it always did.  Frames of at least
     2 x 2 pixels whose smaller extent is at most 768."""
-    if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.DN_NOT_BUILT and technique not in _lib.PRE_STAGE_BY_NAME:
+    if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.PRE_STAGES:
         print("Denoising technique not implemented.")
         return None
     if plot or verbose:

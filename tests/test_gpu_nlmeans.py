@@ -38,7 +38,7 @@ def run(amd, ctx, frames, kw, taps=None, device_in=False, device_out=False):
     L = amd._lib
     spec = kw if isinstance(kw, L.NlmeansSpec) else L.nlmeans_spec(dict(kw, fast_mode=False), taps=taps)
     dev = DeviceFrames(ctx, frames) if device_in else None
-    buf = L.NlmFrames(ctx) if device_out else None
+    buf = L.PreFrames(ctx) if device_out else None
     try:
         if device_in:
             raw = L.RawFrames(None, device_ptrs=dev.ptrs, dtype=frames[0].dtype, shape=frames[0].shape, denoise=spec)

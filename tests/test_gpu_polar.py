@@ -126,6 +126,39 @@ def test_a_stage_of_its_own_runs_on_the_unwrapped_frames(amd, ctx, comp):
     assert np.array_equal(got, U.denoise_imgs(flat(0), "gaussian", dict(sigma=1.0), ctx=ctx))
 
 
+STAGES = {"nl": ("nlmeans_images", dict(patch_size=3, patch_distance=2, h=25.0, fast_mode=False)),
+          "nl_fast": ("nlmeans_fast_images", dict(patch_size=3, patch_distance=1, h=25.0)),
+          "wavelet": ("wavelet_images", dict(wavelet="db1")),
+          "tvb": ("tvb_images", dict(weight=5, max_iter=7))}
+
+
+@pytest.mark.parametrize("technique", list(STAGES))
+def test_every_stage_of_its_own_is_reached_through_the_registry(amd, ctx, comp, technique):
+    """The two routes to a stage that no other test takes for all four: the registry's (denoise_images and the raw-frame path, the
+    polar unwrap first) against the stage's own public method on the unwrapped frames.  Both sides run the same kernels: equality
+    says the dispatch reaches the right call with the right arguments, not that the stage is right (its fixture tests say that).
+    6 x 7 frames: the smallest all four stages take ('nl_fast' needs more than 1 + 1 + 1 rows)."""
+    U, L = amd.gpet_utils, amd._lib
+    frames, pol, flat = comp
+    method, kw = STAGES[technique]
+    small = dict(pol, n_r=6, n_theta=4, pad=1)
+    unwrapped = U.unwrap_polar_imgs(frames, ctx=ctx, **small)
+    assert unwrapped.shape == (3, 6, 7)
+    got, n_iter = U.denoise_imgs(frames, technique, kw, ctx=ctx, polar=small, return_n_iter=True)
+    raw = L.RawFrames(None, frames=unwrapped, denoise=(technique, kw))
+    if technique == "tvb":
+        want, sweeps = ctx.tvb_images(raw, return_n_iter=True)
+        assert sweeps.dtype == np.int32 and sweeps.shape == (3,) and sweeps.any()  # (max_iter is 7)
+    else:
+        want, sweeps = getattr(ctx, method)(raw), np.zeros(3, dtype=np.int32)
+    assert want.dtype == np.float64 and want.shape == (3, 6, 7) and np.isfinite(want).all() and not np.array_equal(want, unwrapped)
+    assert got.dtype == np.float64 and np.array_equal(got, want)
+    assert n_iter.dtype == np.int32 and np.array_equal(n_iter, sweeps)
+    K = U.kernel_builder((5, 3))
+    grad = U.comp_grad_imgs(unwrapped, K, ctx=ctx, denoise=(technique, kw))
+    assert np.isfinite(grad).all() and np.array_equal(U.comp_grad_imgs(frames, K, ctx=ctx, denoise=(technique, kw), polar=small), grad)
+
+
 # ---- 3. the batch --------------------------------------------------------------------------------------------------------------------
 KW = dict(kernel_options={"kernel": "RBF", "sigma_f": 10, "length_scale": 8}, noise_y=1, N_samples=128, score_thresh=1, delta_x=5,
           keep_ratio=0.1, pixel_thresh=3, fix_endpoints=True)

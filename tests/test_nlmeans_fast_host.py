@@ -18,7 +18,7 @@ def test_spec_carries_skimages_defaults_and_the_odd_patch():
     assert (sp.c.patch_size, sp.c.patch_distance, sp.c.h, sp.c.sigma, sp.s) == (4, 2, 0.3, 0.05, 5)  # an even size is the next odd one
     assert _lib.nlmeans_fast_spec(dict(patch_size=2)).s == 3 and _lib.nlmeans_fast_spec(dict(patch_size=15, patch_distance=31)).s == 15
     assert _lib.nlmeans_fast_spec(dict(patch_distance=0)).c.patch_distance == 0
-    assert _lib.NLF_KEYS == ("patch_size", "patch_distance", "h", "sigma", "fast_mode", "multichannel")
+    assert _lib.NLM_KEYS == ("patch_size", "patch_distance", "h", "sigma", "fast_mode", "multichannel")
 
 
 @pytest.mark.parametrize("key", ["preserve_range", "size", "mode", "weight", "channel_axis", "sigma_x", "taps"])
@@ -66,10 +66,6 @@ def test_both_technique_names_resolve_as_described():
         _lib.denoise_spec(("nl_fast", {}))
     assert isinstance(_lib.RawFrames(K, frames=[FRAME], denoise=("nl", dict(fast_mode=False))).pre, _lib.NlmeansSpec)
     assert isinstance(_lib.RawFrames(K, frames=[FRAME], denoise=("nl_fast", {})).pre, _lib.NlmeansFastSpec)
-    # the tables earlier stages pinned stay; the new technique is looked up in the tables that hold every stage
-    assert _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb") and "nl_fast" not in _lib.PRE_STAGE_OF and _lib.NlmeansFastSpec not in _lib.PRE_SPECS
-    assert _lib.PRE_STAGE_BY_NAME == dict(_lib.PRE_STAGE_OF, nl_fast=_lib.nlmeans_fast_spec)
-    assert _lib.PRE_SPEC_TYPES == _lib.PRE_SPECS + (_lib.NlmeansFastSpec,)
     assert gpet_utils.denoise(FRAME, "bilateral", {}) is None  # (an unknown technique: the reference's message, None)
 
 

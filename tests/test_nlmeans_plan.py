@@ -58,7 +58,7 @@ def test_struct_and_flag_agree_between_header_and_python():
     # int32 x 2 | double x 2 | pointer
     assert C.sizeof(_lib.GpetNlmeans) == 32 and _lib.GpetNlmeans.h.offset == 8 and _lib.GpetNlmeans.taps.offset == 24
     # the technique tables of gpet_denoise stay as they were
-    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4) and _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb")
+    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4)
 
 
 # ---- the header through a host-compiled shim -------------------------------------------------------------------------------------

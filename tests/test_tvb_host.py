@@ -25,7 +25,6 @@ def test_without_weight_the_technique_stays_not_built(kw):
                  lambda: gpet.resolve_image_source(1, raw_imgs=FRAME, grad_kernel=K, denoise=("tvb", kw))):
         with pytest.raises(NotImplementedError, match="'tvb'.*weight"):
             call()
-    assert _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb")
 
 
 def test_denoise_spec_points_to_the_stage():
@@ -72,8 +71,5 @@ def test_raw_frames_and_resolve_image_source_carry_the_spec_through_the_pre_stag
     src = gpet.resolve_image_source(2, raw_device_ptrs=[4096, 8192], raw_dtype=np.float32, grad_shape=(40, 60), grad_kernel=K,
                                     denoise=("tvb", dict(weight=5)))
     assert src["on_device"] and src["batch"]["raw"].tvb is not None
-    # the seam's tables: every stage of its own by name, and the spec types
-    assert _lib.PRE_STAGE_OF == dict(nl=_lib.nlmeans_spec, wavelet=_lib.wavelet_spec, tvb=_lib.tvb_spec)
-    assert _lib.PRE_SPECS == (_lib.NlmeansSpec, _lib.WaveletSpec, _lib.TvbSpec)
     # frames to denoise only need no kernel
     assert _lib.RawFrames(None, frames=[FRAME], denoise=("tvb", dict(weight=5))).kernel is None

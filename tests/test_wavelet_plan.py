@@ -69,7 +69,7 @@ def test_struct_and_flags_agree_between_header_and_python():
     W = _lib.GpetWavelet
     assert C.sizeof(W) == 216 and W.dec_lo.offset == 16 and W.sigma.offset == 144 and W.ppf.offset == 160 and W.thresholds.offset == 176
     # the technique tables of gpet_denoise stay as they were
-    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4) and _lib.DN_NOT_BUILT == ("nl", "wavelet", "tvb")
+    assert _lib.DN_OF_TECHNIQUE == dict(median=1, minimum=2, gaussian=3, tvc=4)
 
 
 def test_struct_layout_is_what_a_c_compiler_makes_of_the_header(tmp_path):

@@ -53,7 +53,7 @@ def main(args):
     init = np.array([[0, size // 2], [size - 1, size // 2]])
     bt = pkg.GP_Edge_Tracing_Batch([init] * n, None, list(range(1, n + 1)), raw_imgs=list(frames["u8"]), grad_kernel=k, _ctx=ctx, **KW)
     dev = {t: DeviceFrames(ctx, frames[t]) for t in ("u8", "f64")}
-    buf = L.NlmFrames(ctx)
+    buf = L.PreFrames(ctx)
     out_ptrs = buf.reserve(n, size * size * 8)
     variants = {"P_u8": lambda: bt.set_frame(raw_imgs=list(frames["u8"]), next_frame=False)}
     for p, by_type in params.items():
