@@ -1,10 +1,11 @@
 """Covariances of known spectrum for the eigen-factor stage (GPET_BUF_COV -> GPET_BUF_FACTOR, GPET_BUF_EIGVALS), an
 extended-precision reference of their factor, and the bounds a float64 factor has to meet: tests/test_factor_exact.py pins the
-reference on the host, tests/test_gpu_factor_injected.py the kernels (csrc/gpet_k_factor.inc, csrc/gpet_eig.hip) against it.
+reference on the host, tests/test_gpu_factor_injected.py the kernels (csrc/gpet_k_factor.inc, csrc/gpet_eig.hip) against it,
+tests/test_gpu_factor_warm_injected.py the any-rank path's warm start ("Warm start" below).
 Nothing here comes from the oracle or from the kernels.
 
 Inputs.  Sigma = B^T B with B (r x Lg) a matrix of small integers times powers of two, so that every entry of Sigma is a sum of
-at most 136 integers below 10 on a grid of 2^-32: exact in float64 in any order of summation (``sigma_of`` forms it in the
+at most 136 integers below 10 on a grid of 2^-32 (the warm start's cases: at most 193 on a grid of 2^-18): exact in float64 in any order of summation (``sigma_of`` forms it in the
 extended format and asserts that nothing is lost).  The exact rank is r.
 * ``graded``: B = diag(2^-e_k) C, C random integers in [-3, 3], e_k integers over ``octaves`` <= 16 (``graded_exponents``; rank-deficient cases with a lead row, see there): a spectrum
   that spans about 4^octaves with no structure the kernels could exploit.
@@ -45,6 +46,30 @@ the difference of the norms, of the reference's; rows where that exceeds sqrt(s_
 are compared as clusters: sum over the group of A_k^T A_k, by the gap to the nearest eigenvalue outside the group.
 ``isolated_fraction`` (from the reference alone) must be at least 0.9 for every case that has no exact degeneracy: the octaves are
 chosen so that it is (``test_isolated_rows_are_not_skipped``).
+
+Warm start (any-rank path, k_ojw_* of csrc/gpet_eig.hip).  From the second factor of a trace on, the Jacobi starts from rows built
+out of the previous factor's rows A_0: with s_k = |A_0k|^2, T = A_0 Sigma, M' = T A_0^T, L' = chol(M'), X = (diag(1 / s) L')^T A_0.
+* Inputs (``WARM``: widths 97, 128, 129, 130, 161, 193).  "w<Lg>-0": Sigma_0 = B_0^T B_0, B_0 = graded(Lg, Lg, octaves) of full rank.
+  "w<Lg>-1": Sigma_1 = (D B_0)^T (D B_0), D = ``warm_scales``: ones, and 2^-1 / 2^-3 alternately on 5 or 40 rows -- Sigma_0 less a
+  positive-semidefinite matrix of that rank, what an iteration's new observations do to a posterior covariance; exact in float64.
+  Octaves 3 .. 6, chosen per width so that r u s_0 / s_min <= 1e-6 for both matrices (1.2e-8 .. 7.6e-7; a square C of integers
+  is ill conditioned before any grading, and D^2 adds up to 64): check_edge's ``relev`` (1e-6 relative) has to FOLLOW from a
+  backward error of r u sqrt(Sigma_ii Sigma_jj) (see _octaves_big).
+  "w<Lg>-def" (129: rank 100, 161: rank 120) and "w<Lg>-def1" (rank 128 and 159): rank-deficient matrices on the same columns,
+  safe for the rank test; after Sigma_0 their M' is exactly singular from column r on.
+* ``warm_start`` restates the kernels in float64 (``blocked_cholesky``: 64-column panels -- diagonal block, rows below, trailing
+  update --, pivots tested for > 0 as the device does); ``projector`` and ``projected`` form P = A_0^T diag(1 / s) A_0 and P Sigma P
+  in the extended format.  X^T X = P Sigma P exactly in exact arithmetic, and a Jacobi preserves X^T X: the warm path factors
+  P Sigma P.  Of bound_ij = 124 r u sqrt(Sigma_ii Sigma_jj) the start of the Jacobi has the 2 r u of the first line above
+  (``warm_bound``); from A_0 = the reference rows of Sigma_0 rounded to float64 (|P - I|_2 = 1.3e-16 .. 1.4e-16) the restatement
+  is at 0.058, 0.036, 0.037, 0.050, 0.036, 0.028 of it at 97, 128, 129, 130, 161, 193 columns.
+* Teeth (tests/test_factor_exact.py).  Leaving the terms beyond the last whole chunk of 32 out of T makes M' lose positivity at
+  97, 129, 130, 161 and 193 columns (first at columns 39, 52, 48, 79, 89: no warm rows at all, which the GPU test reads off the
+  sweeps); leaving a last panel of fewer than 64 columns unfactored puts X^T X at 8e10, 5e5 and 3e11 times the share at 97, 129
+  and 161.  At 128 columns neither corruption changes a bit.
+* Sigma_def after Sigma_0: the restatement's first pivot that is not positive is at column 102 of 129 and 120 of 161 -- in the
+  panel that starts at column 64, after G and Gt were overwritten.  Sigma_def1: its one (129) or two (161) pivots of rounding
+  size come out positive in the restatement; on the device that is a matter of its own rounding.
 """
 import functools
 import math
@@ -202,6 +227,34 @@ _case("bhad128-r105", "degenerate", functools.partial(hadamard, 128, 130, [0, 1,
 CAP_ERR = 40
 _case("g100-r41-over", "graded", lambda: np.vstack([graded(40, 100, 4, 8), graded(1, 100, 0, 9) * 2.0 ** -10]))
 
+# warm start of the any-rank path (see "Warm start" in the module docstring): width -> (octaves of B_0, rows D scales down)
+WARM = {97: (6, 5), 128: (3, 40), 129: (5, 5), 130: (4, 40), 161: (3, 40), 193: (4, 5)}
+WARM_WIDTHS = (97, 128, 129, 161, 193)
+WARM_DEF = {129: 100, 161: 120}  # width -> exact rank of Sigma_def: M' loses positivity in the panel at column 64
+WARM_DEF1 = {129: 128, 161: 159}  # ... of Sigma_def1: one or two pivots of rounding size, which the float64 restatement ACCEPTS
+
+
+def warm_scales(Lg):
+    """The diagonal of D: ones, and 2^-1 / 2^-3 alternately on WARM[Lg][1] rows drawn without replacement."""
+    rng = np.random.default_rng(7919 * Lg + 11)
+    d = np.ones(Lg)
+    rows = np.sort(rng.choice(Lg, size=WARM[Lg][1], replace=False))
+    d[rows[0::2]], d[rows[1::2]] = 0.5, 0.125
+    return d
+
+
+def warm_start_rows(Lg):
+    return graded(Lg, Lg, WARM[Lg][0], 10)
+
+
+for _Lg in WARM:
+    _case("w%d-0" % _Lg, "graded", functools.partial(warm_start_rows, _Lg))
+    _case("w%d-1" % _Lg, "graded", lambda _Lg=_Lg: warm_scales(_Lg)[:, None] * warm_start_rows(_Lg))
+for _Lg, _r in WARM_DEF.items():
+    _case("w%d-def" % _Lg, "graded", functools.partial(graded, _r, _Lg, _octaves_big(_r), 11))
+for _Lg, _r in WARM_DEF1.items():
+    _case("w%d-def1" % _Lg, "graded", functools.partial(graded, _r, _Lg, _octaves_big(_r), 11))
+
 CASES = tuple(_TABLE)
 
 
@@ -276,14 +329,101 @@ def ref_factor(B, tol=1e-17, max_sweeps=60, use_decimal=None):
 
 
 @functools.lru_cache(maxsize=None)
-def case(name):
-    """(B, Sigma, F, s) of a case of the table; computed once, not to be changed."""
+def sigma(name):
+    """(B, Sigma) of a case of the table, without its reference factor; computed once, not to be changed."""
     B = _TABLE[name][1]()
     S = sigma_of(B)
-    F, s, _ = ref_factor(B)
     for a in (B, S):
         a.setflags(write=False)
+    return B, S
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(B, Sigma, F, s) of a case of the table; computed once, not to be changed."""
+    B, S = sigma(name)
+    F, s, _ = ref_factor(B)
     return B, S, F, s
+
+
+# ---- the warm start, restated ----------------------------------------------------------------------------------------------------
+
+WARM_PANEL = 64  # columns of a panel of the blocked Cholesky
+WARM_CHUNK = 32  # terms of a product that go through LDS together
+
+
+def blocked_cholesky(M, skip_partial_panel=False):
+    """Lower Cholesky factor of M (its lower triangle is read) in float64 by panels of WARM_PANEL columns -- diagonal block, the
+    rows below it, the trailing update --, the order of the device's k_ojw_chol_*: (L, k) with k the first column whose pivot is
+    not positive (L is then unfinished), or None.  skip_partial_panel: a corruption for the tests -- a last panel of fewer than
+    WARM_PANEL columns is left as the trailing updates made it."""
+    n = M.shape[0]
+    K = np.tril(M).astype(np.float64)
+    for k0 in range(0, n, WARM_PANEL):
+        nb = min(WARM_PANEL, n - k0)
+        if skip_partial_panel and nb < WARM_PANEL:
+            break
+        D = K[k0:k0 + nb, k0:k0 + nb]
+        for c in range(nb):
+            piv = D[c, c]
+            if not piv > 0.0:
+                return K, k0 + c
+            f = D[c + 1:, c] / piv
+            D[c + 1:, c + 1:] -= np.tril(np.outer(f, D[c + 1:, c]))
+        d = np.sqrt(np.diag(D).copy())
+        D[:] = np.tril(D / d[None, :])
+        np.fill_diagonal(D, d)
+        if k0 + nb < n:
+            Lkk = D
+            X = K[k0 + nb:, k0:k0 + nb]
+            for c in range(nb):  # X Lkk^T = A by columns
+                X[:, c] /= Lkk[c, c]
+                X[:, c + 1:] -= np.outer(X[:, c], Lkk[c + 1:, c])
+            K[k0 + nb:, k0 + nb:] -= np.tril(X @ X.T)
+    return K, None
+
+
+def warm_start(A0, S, drop_partial_chunk=False, skip_partial_panel=False):
+    """The warm start of the any-rank factor in float64 from the previous rows A0 (Lg x Lg): 1 / s_k from the rows' float64
+    squared norms, T = A0 Sigma, M' = T A0^T (lower), L' = chol(M'), X = (diag(1 / s) L')^T A0.  Returns (X, k): k the first
+    column of M' whose pivot is not positive (X is then None: the device falls back to the pivoted Cholesky), else None.
+    drop_partial_chunk: a corruption for the tests -- the terms of T beyond the last whole chunk of WARM_CHUNK are left out."""
+    n = A0.shape[0]
+    assert A0.shape == S.shape == (n, n)
+    s = (A0 * A0).sum(axis=1)
+    inv = np.where(s > 0.0, 1.0 / np.where(s > 0.0, s, 1.0), 0.0)
+    kk = (n // WARM_CHUNK) * WARM_CHUNK if drop_partial_chunk else n
+    T = A0[:, :kk] @ S[:kk, :]
+    M = T @ A0.T
+    L, bad = blocked_cholesky(M, skip_partial_panel)
+    if bad is not None:
+        return None, bad
+    return (inv[:, None] * L).T @ A0, None
+
+
+def projector(A):
+    """P = A^T diag(1 / |A_k|^2) A of the float64 rows A, in the extended format: the identity where the rows are orthogonal and
+    span everything."""
+    Ax = ext(A)
+    nrm2 = (Ax * Ax).sum(axis=1)
+    return (Ax / nrm2[:, None]).T @ Ax
+
+
+def projected(P, S):
+    """P Sigma P in the extended format."""
+    return P @ ext(S) @ P
+
+
+def projector_defect(P):
+    """|P - I|_2 (the difference formed in the extended format)."""
+    n = P.shape[0]
+    return float(np.linalg.norm(f64(P - ext(np.eye(n))), 2))
+
+
+def warm_bound(S, r):
+    """The share of bound_matrix that belongs to the start of the Jacobi: 2 r u sqrt(Sigma_ii Sigma_jj)."""
+    d = np.diag(S)
+    return 2 * r * U * np.sqrt(np.outer(d, d))
 
 
 # ---- the rank test, restated ---------------------------------------------------------------------------------------------------------

@@ -1,6 +1,11 @@
 """The reference and the case table of tests/factor_exact.py, on the host: the extended-precision one-sided Jacobi against mpmath
 at 40 digits and against LAPACK, the table's conditions -- exact representability, safety for the device's rank test, isolated
-rows -- and the Hadamard cases' eigenvectors in integer arithmetic.  No GPU, no kernel code."""
+rows --, the Hadamard cases' eigenvectors in integer arithmetic, and the float64 restatement of the any-rank path's warm start
+(factor_exact.warm_start) against P Sigma P in the extended format, with the two corruptions that only ragged widths catch.
+No GPU, no kernel code."""
+import functools
+import math
+
 import numpy as np
 import pytest
 
@@ -81,7 +86,7 @@ def test_reference_matches_lapack_and_reconstructs(name):
 def test_case_is_exact_and_safe_for_the_rank_test(name):
     B, S, F, s = fx.case(name)  # (sigma_of has asserted that Sigma is exact)
     r, Lg = B.shape
-    assert r <= 136 and (fx.kind_of(name) == "small" or np.abs(np.log2(np.abs(B[B != 0]))).max() <= 16 + 4)
+    assert r <= 193 and (fx.kind_of(name) == "small" or np.abs(np.log2(np.abs(B[B != 0]))).max() <= 16 + 4)
     if fx.kind_of(name) == "graded":  # integers in [-3, 3] times one power of two per row
         for row in B:
             assert any(np.all(row * 2.0 ** e == np.round(row * 2.0 ** e)) and np.abs(row * 2.0 ** e).max() <= 3 for e in range(17))
@@ -145,3 +150,106 @@ def test_clusters_and_gaps():
     np.testing.assert_allclose(fx.gaps(s, False), [4.0, 0.0, 0.0, 1e-9, 1e-9, 0.25], atol=1e-15)
     assert fx.gaps(s, True)[-1] == 0.75 - 1e-9
     assert fx.C_REC * 96 * fx.U <= 1e-9 / 100 and fx.C_REC * 136 * fx.U <= 2e-12
+
+
+# ---- the warm start of the any-rank path, restated (factor_exact.warm_start) --------------------------------------------------------
+
+WARM_RAGGED = (97, 129, 161)
+
+
+@functools.lru_cache(maxsize=None)
+def _warm_host(Lg):
+    """(A_0, P Sigma_1 P, |P - I|_2): A_0 the reference rows of Sigma_0 rounded to float64, P their projector."""
+    A0 = fx.f64(fx.case("w%d-0" % Lg)[2])
+    P = fx.projector(A0)
+    return A0, fx.projected(P, fx.sigma("w%d-1" % Lg)[1]), fx.projector_defect(P)
+
+
+def _warm_fraction(Lg, **corruption):
+    """max |X^T X - P Sigma_1 P|_ij / (2 r u sqrt(Sigma_ii Sigma_jj)) of the restatement; inf where its Cholesky meets a pivot
+    that is not positive -- the device then starts cold, which the GPU tests' sweep counts notice."""
+    A0, PSP, _ = _warm_host(Lg)
+    S1 = fx.sigma("w%d-1" % Lg)[1]
+    X, bad = fx.warm_start(A0, S1, **corruption)
+    if X is None:
+        return math.inf
+    Xx = fx.ext(X)
+    return float((fx.f64(abs(Xx.T @ Xx - PSP)) / fx.warm_bound(S1, Lg)).max())
+
+
+@pytest.mark.parametrize("Lg", sorted(fx.WARM))
+def test_warm_step_is_a_downdate_of_known_rank(Lg):
+    """Sigma_0 - Sigma_1 = B_0^T (I - D^2) B_0: positive semidefinite of rank = the rows D scales (B_0 has full rank), D's
+    entries 1, 2^-1 and 2^-3; and both matrices are conditioned so that an eigenvalue's 1e-6 follows from a backward error of
+    r u sqrt(Sigma_ii Sigma_jj) (factor_exact._octaves_big)."""
+    B0, S0 = fx.sigma("w%d-0" % Lg)
+    B1, S1 = fx.sigma("w%d-1" % Lg)
+    d = fx.warm_scales(Lg)
+    assert B0.shape == (Lg, Lg) and np.array_equal(B1, d[:, None] * B0) and set(d) == {1.0, 0.5, 0.125}
+    assert int((d != 1).sum()) == fx.WARM[Lg][1] and np.linalg.matrix_rank(B0) == Lg
+    E = np.sqrt(1 - d * d)[:, None] * B0
+    np.testing.assert_allclose(E.T @ E, S0 - S1, rtol=0, atol=8 * Lg * fx.U * np.abs(S0).max())
+    for name in ("w%d-0" % Lg, "w%d-1" % Lg):
+        s = fx.f64(fx.case(name)[3])
+        assert Lg * fx.U * s[0] / s[-1] <= 1e-6, (name, s[0] / s[-1])
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129, 161])
+def test_blocked_cholesky_is_a_cholesky(n):
+    """Higham, Thm 10.3: |L L^T - M|_ij <= (n + 1) u sqrt(M_ii M_jj); and the first pivot that is not positive is reported."""
+    rng = np.random.default_rng(n)
+    G = rng.integers(-3, 4, size=(n + 5, n)).astype(np.float64)
+    M = G.T @ G
+    L, bad = fx.blocked_cholesky(M)
+    assert bad is None and np.array_equal(L, np.tril(L))
+    d = np.sqrt(np.diag(M))
+    assert np.all(np.abs(fx.f64(fx.ext(L) @ fx.ext(L).T - fx.ext(M))) <= (n + 1) * fx.U * np.outer(d, d))
+    if n >= 65:
+        M2 = M.copy()
+        M2[n - 1, n - 1] = -1.0
+        assert fx.blocked_cholesky(M2)[1] == n - 1
+
+
+@pytest.mark.parametrize("Lg", sorted(fx.WARM))
+def test_warm_restatement_meets_the_start_share_of_the_bound(Lg):
+    """The condition the GPU test puts to the kernels, 124 r u sqrt(Sigma_ii Sigma_jj) against P Sigma_1 P, leaves 2 r u of it
+    to the start of the Jacobi: the float64 restatement stays within that (0.03 .. 0.06 of it, printed)."""
+    A0, PSP, defect = _warm_host(Lg)
+    assert defect <= 8 * fx.U, defect  # (rows orthogonal to 1e-17, rounded to float64)
+    frac = _warm_fraction(Lg)
+    print("warm restatement %d columns: %.3g of 2 r u sqrt(Sigma_ii Sigma_jj), |P - I|_2 = %.2e" % (Lg, frac, defect))
+    assert frac <= 1.0, (Lg, frac)
+
+
+@pytest.mark.parametrize("Lg", WARM_RAGGED)
+def test_warm_condition_catches_a_dropped_partial_chunk_and_an_empty_partial_panel(Lg):
+    assert not _warm_fraction(Lg, drop_partial_chunk=True) <= 1.0
+    assert not _warm_fraction(Lg, skip_partial_panel=True) <= 1.0
+
+
+def test_warm_corruptions_pass_unnoticed_at_the_aligned_width():
+    """128 columns have no partial chunk of 32 and no partial panel of 64: why aligned widths prove nothing about either."""
+    want = _warm_fraction(128)
+    assert _warm_fraction(128, drop_partial_chunk=True) == want <= 1.0
+    assert _warm_fraction(128, skip_partial_panel=True) == want
+
+
+@pytest.mark.parametrize("Lg", sorted(fx.WARM_DEF))
+def test_rank_deficient_step_loses_positivity_in_a_later_panel(Lg):
+    """M' = A_0 Sigma_def A_0^T has exact rank r >= 64: its Schur complement after r pivots is rounding, and the restatement
+    meets a pivot that is not positive in the panel that starts at column 64 -- after G and Gt have been overwritten."""
+    r = fx.WARM_DEF[Lg]
+    assert fx.sigma("w%d-def" % Lg)[0].shape == (r, Lg) and 64 <= r < 128
+    X, bad = fx.warm_start(_warm_host(Lg)[0], fx.sigma("w%d-def" % Lg)[1])
+    assert X is None and r <= bad < 128, bad
+
+
+@pytest.mark.parametrize("Lg", sorted(fx.WARM_DEF1))
+def test_nearly_full_rank_step_has_its_rounding_pivots_accepted(Lg):
+    """Rank Lg - 1 and Lg - 2: the last one or two pivots of M' are rounding, and in the restatement they come out positive --
+    the warm start is then accepted with rank Lg and the next one divides by squared norms of rounding size.  (The sign of a
+    pivot of rounding size is the device's own; the GPU test's contract covers both outcomes.)"""
+    r = fx.WARM_DEF1[Lg]
+    assert fx.sigma("w%d-def1" % Lg)[0].shape == (r, Lg) and Lg - 2 <= r < Lg
+    X, bad = fx.warm_start(_warm_host(Lg)[0], fx.sigma("w%d-def1" % Lg)[1])
+    assert bad is None and np.all(np.isfinite(X))

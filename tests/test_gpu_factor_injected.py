@@ -122,8 +122,10 @@ def _frac(dev, bound):
     return float((dev[~zero] / bound[~zero]).max(initial=0.0))
 
 
-def check_edge(L, b, e, name, path, what):
-    """All of the module docstring's conditions on edge e against the case ``name``; returns {check: fraction of its bound}."""
+def check_edge(L, b, e, name, path, what, rec_target=None):
+    """All of the module docstring's conditions on edge e against the case ``name``; returns {check: fraction of its bound}.
+    rec_target: the matrix (extended format) that ``rec`` compares A^T A with where the algorithm does not target Sigma itself
+    (tests/test_gpu_factor_warm_injected.py: the warm start's P Sigma P); every bound stays Sigma's."""
     B, S, F, s = fx.case(name)
     r, Lg = B.shape
     sc = b.scalars(e)
@@ -134,7 +136,7 @@ def check_edge(L, b, e, name, path, what):
     sf = fx.f64(s)
     bound, bf = fx.bound_matrix(S, r), fx.bound_fro(S, r)
     Ax = fx.ext(A)
-    out = {"rec": _frac(abs(Ax.T @ Ax - fx.ext(S)), bound)}
+    out = {"rec": _frac(abs(Ax.T @ Ax - (fx.ext(S) if rec_target is None else rec_target)), bound)}
     nrm2 = (Ax * Ax).sum(axis=1)
     out["weyl"] = _frac(abs(fx.ext(ev) - s), np.full(r, bf))
     out["evnorm"] = _frac(abs(fx.ext(ev) - nrm2), (Lg + 2) * U * ev)
