@@ -29,6 +29,7 @@ RAW_ON_DEVICE = 4  # gpet_grad_images / gpet_batch_create_raw / gpet_batch_set_r
 FRAMES_TRANSPOSED = 16  # the raw-frame calls and every batch creation with flags: a vertical batch -- frames in frame layout, images and batch shape (N, M)
 # pixel types of raw frames (GPET_PIX_*): the dtypes that go to the device as they are
 PIX_U8, PIX_U16, PIX_F32, PIX_F64 = range(4)
+PIX_BYTES = (1, 2, 4, 8)
 PIX_OF_DTYPE = {np.dtype(np.uint8): PIX_U8, np.dtype(np.uint16): PIX_U16, np.dtype(np.float32): PIX_F32,
                 np.dtype(np.float64): PIX_F64}
 
@@ -926,6 +927,22 @@ def native_frames(imgs):
     return frames, PIX_OF_DTYPE[dt]
 
 
+class metrics_frames(object):
+    """One side of the pairs ``Context.metrics_images`` scores: host frames (``frames``: a (T, M, N) array or a sequence of (M, N)
+    arrays of ONE dtype among uint8, uint16, float32, float64 -- any other dtype is converted to float64, as native_frames does) or,
+    with ``device_ptrs``, ``dtype`` and ``shape``, frames that lie on the context's device."""
+
+    def __init__(self, frames=None, device_ptrs=None, dtype=None, shape=None):
+        if (frames is None) == (device_ptrs is None):
+            raise ValueError("frames come either from the host or as device pointers")
+        if device_ptrs is not None:
+            self.frames, self.pix, self.flags = None, pix_code(dtype), RAW_ON_DEVICE
+            self.ptrs, self.shape = [int(p) for p in device_ptrs], (int(shape[0]), int(shape[1]))
+        else:
+            self.frames, self.pix = native_frames(frames)
+            self.flags, self.ptrs, self.shape = 0, [f.ctypes.data for f in self.frames], tuple(self.frames[0].shape)
+
+
 def split_kernels(kernel):
     """(list of float64 2-D kernels, multi): a list or tuple of 2-D kernels, or a 3-D array, is several kernels; a 2-D array or a
     nested list of numbers is ONE kernel (multi False), as it always was."""
@@ -1240,6 +1257,71 @@ def _label_out(n_maps, shape, out_device_ptrs, thick_count, thick_device_ptr):
     return maps, op, thick, (thick.ctypes.data_as(C.POINTER(C.c_int32)) if thick_count else None), 0
 
 
+# denoise quality metrics (gpet_metrics, GPET_METRICS_*; csrc/gpet_metrics_plan.h)
+METRICS_B_ON_DEVICE, METRICS_MAPS_ON_DEVICE = 32, 64  # gpet_metrics_images: raw_b[] / ssim_maps[] are device pointers
+METRICS_PX_MAX = 1 << 26
+METRICS_CHUNK_BUDGET = 512 << 20
+METRICS_KEYS = ("K1", "K2", "use_sample_covariance")
+METRICS_RANGE_WORDS = ("im_true has intensity values outside the range expected for its data type.  Please manually specify the "
+                       "data_range")
+
+
+class GpetMetrics(C.Structure):
+    _fields_ = [("win_size", C.c_int32), ("use_sample_covariance", C.c_int32), ("K1", C.c_double), ("K2", C.c_double),
+                ("data_range", C.c_double)]
+
+
+def metrics_frame_bytes(px, staged_a, staged_b):
+    """Bytes of one pair's workspace (gpet_metrics_plan.h: metrics_frame_bytes): six float64 planes and the staged host frames."""
+    al = lambda b: (int(b) + 255) & ~255
+    return al(6 * px * 8) + al(staged_a) + al(staged_b)
+
+
+def metrics_refusal(n_img, pix_a, pix_b, M, N, win_size=7, K1=0.01, K2=0.03, data_range=0.0, staged_a=0, staged_b=0):
+    """The words gpet_metrics_images refuses these arguments with (gpet_metrics_plan.h: metrics_check, in its order), or None."""
+    if n_img < 1:
+        return "metrics: no frame"
+    if pix_a not in range(4) or pix_b not in range(4):
+        return "metrics: unknown pixel type"
+    if M < 1 or N < 1:
+        return "metrics: empty frame"
+    if win_size > M or win_size > N:
+        return "win_size exceeds image extent.  If the input is a multichannel (color) image, set multichannel=True."
+    if win_size % 2 != 1:
+        return "Window size must be odd."
+    if win_size < 3:
+        return "metrics: win_size must be at least 3"
+    if not K1 >= 0:
+        return "K1 must be positive"
+    if not K2 >= 0:
+        return "K2 must be positive"
+    if not (data_range >= 0 and data_range < float("inf")):
+        return "metrics: data_range must be a finite number above 0 (0: the library's rule)"
+    if M * N > METRICS_PX_MAX:
+        return "metrics: a frame exceeds 2^26 pixels (M * N)"
+    fb = metrics_frame_bytes(M * N, staged_a, staged_b)
+    if fb > METRICS_CHUNK_BUDGET:
+        return ("metrics: the workspace of one frame (%d bytes: six float64 planes of %d x %d and its staging) exceeds the chunk budget of "
+                "%d bytes" % (fb, M, N, METRICS_CHUNK_BUDGET))
+    return None
+
+
+def metrics_spec(win_size=7, data_range=None, **ssim_kwargs):
+    """The keyword arguments of scikit-image's ``structural_similarity`` that the device builds -> GpetMetrics.  ``gaussian_weights``,
+    ``gradient`` and ``multichannel`` set True, and any other key, raise ValueError naming the key."""
+    for k in ("gaussian_weights", "gradient", "multichannel"):
+        if ssim_kwargs.pop(k, False):
+            raise ValueError("metrics: %s=True is not supported on the device (uniform window, no gradient, 2-D single-channel frames)" % k)
+    for k in ssim_kwargs:
+        if k not in METRICS_KEYS:
+            raise ValueError("metrics: keyword %r is not supported on the device (supported: %s)" % (k, ", ".join(METRICS_KEYS)))
+    w = 7 if win_size is None else win_size
+    if int(w) != w:
+        raise ValueError("metrics: win_size %r: a whole number" % (win_size,))
+    return GpetMetrics(int(w), 1 if ssim_kwargs.get("use_sample_covariance", True) else 0, float(ssim_kwargs.get("K1", 0.01)),
+                       float(ssim_kwargs.get("K2", 0.03)), 0.0 if data_range is None else float(data_range))
+
+
 class GpetError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libgpet_hip status {code}: {msg}")
@@ -1387,6 +1469,8 @@ SYMBOLS = {
     "gpet_batch_label_maps_xy": (C.c_int, [_P, C.POINTER(GpetPolar), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_uint,
                                            C.POINTER(_P)]),
     "gpet_label_thick_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "gpet_metrics_images": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GpetMetrics),
+                                      C.c_uint, C.POINTER(C.c_double), C.POINTER(_P)]),
 }
 COMM_ID_BYTES = 128
 SAMPLE_ARITH_F64, SAMPLE_ARITH_F32 = 0, 1  # gpet_batch_set_sample_arith
@@ -1746,6 +1830,65 @@ class Context:
         self.check(self.lib.gpet_label_maps_xy(self.h, Ms, Ns, n, nv.ctypes.data_as(ip), flat.ctypes.data_as(C.POINTER(C.c_double)),
                                                m.ctypes.data_as(ip), n_maps, flag, op))
         return maps
+
+    def metrics_images(self, raw_a, raw_b, spec=None, full=False, maps_device_ptrs=None):
+        """gpet_metrics_images: the four figures of the reference's ``denoise(verbose=True)`` for every pair of two stacks -- ``raw_a``
+        the frames as given, ``raw_b`` the denoised frames, each a RawFrames-like object (``ptrs``, ``pix``, ``flags``, ``shape``; see
+        ``metrics_frames``) on the host or on the device, of any two pixel types.  ``spec``: a GpetMetrics (``metrics_spec``).  Returns
+        a (T, 4) float64 array -- psnr, ssim, nrmse, entropy -- and, with ``full``, the (T, M, N) float64 SSIM maps;
+        ``maps_device_ptrs``: the maps are written to these device addresses instead (None returned for them).  A refusal in the
+        words of scikit-image (the window, a float frame outside [-1, 1] without ``data_range``) raises ValueError, as the library does."""
+        T, (M, N) = len(raw_a.ptrs), raw_a.shape
+        if len(raw_b.ptrs) != T or tuple(raw_b.shape) != (M, N):
+            raise ValueError("Input images must have the same dimensions.")
+        spec = spec if spec is not None else metrics_spec()
+        why = metrics_refusal(T, raw_a.pix, raw_b.pix, M, N, spec.win_size, spec.K1, spec.K2, spec.data_range,
+                              0 if raw_a.flags & RAW_ON_DEVICE else M * N * PIX_BYTES[raw_a.pix],
+                              0 if raw_b.flags & RAW_ON_DEVICE else M * N * PIX_BYTES[raw_b.pix])
+        if why is not None:
+            raise ValueError(why)
+        out = np.empty((T, 4), dtype=np.float64)
+        flags = (RAW_ON_DEVICE if raw_a.flags & RAW_ON_DEVICE else 0) | (METRICS_B_ON_DEVICE if raw_b.flags & RAW_ON_DEVICE else 0)
+        maps, mp = None, None
+        if maps_device_ptrs is not None:
+            if len(maps_device_ptrs) != T:
+                raise ValueError("%d maps for %d frames" % (len(maps_device_ptrs), T))
+            mp, flags = (_P * T)(*[int(p) for p in maps_device_ptrs]), flags | METRICS_MAPS_ON_DEVICE
+        elif full:
+            maps = np.empty((T, M, N), dtype=np.float64)
+            mp = (_P * T)(*[maps[g].ctypes.data for g in range(T)])
+        rc = self.lib.gpet_metrics_images(self.h, (_P * T)(*raw_a.ptrs), raw_a.pix, (_P * T)(*raw_b.ptrs), raw_b.pix, T, M, N, C.byref(spec),
+                                          flags, out.ctypes.data_as(C.POINTER(C.c_double)), mp)
+        if rc == ERR_BAD_ARG:
+            msg = (self.lib.gpet_last_error(self.h) or b"").decode()
+            if msg.startswith(METRICS_RANGE_WORDS):
+                raise ValueError(msg)
+        self.check(rc)
+        return (out, maps) if full or maps_device_ptrs is not None else out
+
+    def denoise_images_scored(self, raw, spec=None):
+        """``denoise_images`` of host frames and ``metrics_images`` of (the frames, the result) -> (result, iterations, (T, 4)
+        figures).  A stage of its own writes into device memory of this call (``out_device_ptrs``), the frames are scored there and
+        copied home afterwards; an in-pass technique's result comes home first and goes up again."""
+        if raw.polar is not None or raw.frames is None:
+            raise ValueError("scoring takes host frames without a polar spec")
+        a = metrics_frames(frames=raw.frames)
+        if raw.pre is None:
+            out, n_iter = self.denoise_images(raw)
+            return out, n_iter, self.metrics_images(a, metrics_frames(frames=out), spec)
+        T, (M, N) = len(raw), raw.shape
+        buf = PreFrames(self)
+        try:
+            ptrs = buf.reserve(T, M * N * 8)
+            n_iter = np.zeros(T, dtype=np.int32)
+            self._run_stage(raw, raw.pre, raw.shape, ptrs, n_iter)
+            fig = self.metrics_images(a, metrics_frames(device_ptrs=ptrs, dtype=np.float64, shape=(M, N)), spec)
+            out = np.empty((T, M, N), dtype=np.float64)
+            for g in range(T):
+                self.check(self.lib.gpet_dev_copy(self.h, out[g].ctypes.data, ptrs[g], M * N * 8, 1))
+            return out, n_iter, fig
+        finally:
+            buf.close()
 
     def normalise_f32(self, img):
         a = np.ascontiguousarray(img, dtype=np.float32)

@@ -35,6 +35,8 @@
 //                        and, for sequences, gpet_batch_ensemble_keep / _kept, gpet_batch_warm_start_groups / _from
 //   gpet_api_label.hip   label maps: gpet_label_maps[_xy], gpet_batch_label_maps[_xy], gpet_label_thick_count
 //   gpet_label_plan.h    the two rasterisation rules, their refusals, the fill kernels' launch shapes (no HIP)
+//   gpet_api_metrics.hip denoise quality metrics: gpet_metrics_images
+//   gpet_metrics_plan.h  the four figures' arithmetic, the one summation order, the method of the counts, refusals, launch shapes (no HIP)
 //   gpet_api_init.hip    endpoint tracking: gpet_batch_init_follow, gpet_batch_set_init, gpet_batch_init_xy
 //   gpet_init_plan.h     the rule that moves an init point, its refusals (no HIP)
 //   gpet_warm_plan.h     the source of every edge's warm start (medoid, best cost, consensus, another edge, none), the refusals, the

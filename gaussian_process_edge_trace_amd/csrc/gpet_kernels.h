@@ -12,6 +12,7 @@
 #include "gpet_nlmeans_plan.h"  // non-local means: spec, LDS patch, grid, the exponential
 #include "gpet_nlfast_plan.h"   // fast-mode non-local means: spec, shift table, groups, workspace, launch geometry
 #include "gpet_wavelet_plan.h"  // wavelet denoising: spec, levels, pyramid layout, tiles, the threshold's summation order
+#include "gpet_metrics_plan.h"  // denoise quality metrics: working type, running-sum filter, S, keys, the one summation order
 #include "gpet_tvb_plan.h"      // split-Bregman TV denoising: spec, skewed workspace, workgroup, sweeps per launch, the order of acc
 #include "gpet_polar_plan.h"    // polar unwrap: spec, column-to-angle map, sample position, bilinear value, launch geometry
 #include "gpet_history_plan.h"  // iteration history: record layout, workgroups per edge
@@ -106,6 +107,13 @@ hipError_t launch_wavelet(hipStream_t st, int pix, const void* const* d_src, dou
 // epilogue.  ws: the chunk's n workspaces (tvb_frame_bytes apart); d_state [frames] on the device, zero before the first launch
 hipError_t launch_tvb(hipStream_t st, int pix, const void* const* d_src, double* const* d_dst, int img0, int n, int M, int N,
                       const TvbSpec& sp, char* ws, TvbState* d_state);
+// denoise quality metrics (gpet_metrics_plan.h): pairs img0 .. img0 + n - 1 of the DEVICE table d_tab (a, b per pair) -> the sums of
+// d_acc and the S map in every pair's workspace (ws, `stride` bytes apart); launch_metrics_entropy, afterwards, sorts b's keys over the
+// intermediate planes (S stays) and adds the entropy terms
+hipError_t launch_metrics(hipStream_t st, const void* const* d_tab, MetricsAcc* d_acc, int img0, int n, int pix_a, int pix_b, int M, int N,
+                          const MetricsSpec& sp, double R_ssim, char* ws, size_t stride);
+hipError_t launch_metrics_entropy(hipStream_t st, const void* const* d_tab, MetricsAcc* d_acc, int img0, int n, int pix_b, int M, int N, char* ws,
+                                  size_t stride);
 hipError_t launch_fit_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd, int want_cov,
                               unsigned parts = ~0u);
 hipError_t launch_final_predict(hipStream_t st, EdgeDev* d_edges, int B, const BatchDims& bd);

@@ -38,5 +38,6 @@ namespace gpet {
 #include "gpet_k_band.inc"
 #include "gpet_k_init.inc"
 #include "gpet_k_label.inc"
+#include "gpet_k_metrics.inc"
 
 }  // namespace gpet

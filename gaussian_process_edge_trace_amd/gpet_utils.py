@@ -94,7 +94,7 @@ def comp_grad_imgs(imgs, kernel, ctx=None, denoise=None, transpose=False, polar=
     return out.reshape((T, K) + out.shape[1:])
 
 
-def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False, polar=None):
+def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False, polar=None, return_metrics=False):
     """``denoise`` of every frame of a stack in ONE batched GPU pass (gpet_denoise_images): ``imgs`` is a (T, M, N) array or a
     sequence of (M, N) frames of one dtype, the result a (T, M, N) array whose frame t equals ``denoise(imgs[t], technique,
     kwargs)`` bit for bit.  ``return_n_iter``: also the iterations 'tvc' ran per frame (0 for the filters).  'nl' with
@@ -102,10 +102,54 @@ def denoise_imgs(imgs, technique, kwargs, ctx=None, return_n_iter=False, polar=N
     (gpet_nlmeans_images, gpet_nlmeans_fast_images, gpet_wavelet_images, gpet_tvb_images): float64 frames whatever the frames' dtype; for 'tvb' ``return_n_iter`` gives the sweeps
     every frame ran (0 for 'nl' and 'wavelet').
     ``polar=dict(...)``: the frames are unwrapped to (radius x angle) first (``pad`` defaults to 0: there is no kernel) -- the result
-    equals ``denoise_imgs(unwrap_polar_imgs(imgs, **polar), technique, kwargs)`` bit for bit."""
+    equals ``denoise_imgs(unwrap_polar_imgs(imgs, **polar), technique, kwargs)`` bit for bit.
+    ``return_metrics``: also ``denoise_metrics(imgs, result)`` -- the dict comes last in the returned tuple, and equals that call bit
+    for bit.  A stage of its own leaves its float64 frames on the device (``out_device_ptrs``), where they are scored before they come
+    home; the in-pass techniques (median, minimum, gaussian, tvc) hand their result to the host through gpet_denoise_images, and it
+    goes up again to be scored.  Not with ``polar`` (the frames as given and the result differ in shape)."""
     raw = _lib.RawFrames(None, frames=imgs, denoise=(technique, kwargs), polar=polar)  # (refuses a bad spec before a device is needed)
-    out, n_iter = (ctx or _ctx()).denoise_images(raw)
-    return (out, n_iter) if return_n_iter else out
+    if not return_metrics:
+        out, n_iter = (ctx or _ctx()).denoise_images(raw)
+        return (out, n_iter) if return_n_iter else out
+    if polar is not None:
+        raise ValueError("return_metrics scores the result against the frames as given: not with polar, which changes their shape")
+    _refuse_nan(raw.frames)
+    out, n_iter, fig = (ctx or _ctx()).denoise_images_scored(raw, _lib.metrics_spec())
+    m = _metrics_dict(fig)
+    return (out, n_iter, m) if return_n_iter else (out, m)
+
+
+def _refuse_nan(frames):
+    for t, f in enumerate(frames):
+        if f.dtype.kind == "f" and np.isnan(f).any():
+            raise ValueError("frame %d holds a NaN: the metrics of such a frame are not defined" % t)
+
+
+def _metrics_dict(fig, maps=None):
+    m = dict(psnr=fig[:, 0].copy(), ssim=fig[:, 1].copy(), nrmse=fig[:, 2].copy(), entropy=fig[:, 3].copy())
+    if maps is not None:
+        m["ssim_map"] = maps
+    return m
+
+
+def denoise_metrics(imgs, denoised, win_size=7, data_range=None, full=False, ctx=None, **ssim_kwargs):
+    """The four figures the reference's ``denoise(..., verbose=True)`` prints (gpet_utils.py:151-156), for every frame of a stack, on
+    the GPU (gpet_metrics_images): ``imgs`` the frames as given, ``denoised`` the denoised frames -- (T, M, N) arrays or sequences of
+    (M, N) frames; the two stacks may differ in dtype.  Returns a dict of (T,) float64 arrays: ``psnr``
+    (peak_signal_noise_ratio), ``ssim`` (structural_similarity, the library's default call: uniform window), ``nrmse``
+    (normalized_root_mse, normalization='min-max') and ``entropy`` (shannon_entropy of the denoised frame), as scikit-image 0.18.3
+    computes them; with ``full`` also ``ssim_map``, (T, M, N), the library's S map bit for bit.  The figures differ from the library's
+    only by the order of three sums (DESIGN.md 9 has the bounds).  ``win_size`` (odd, 3 .. the smaller extent), ``data_range`` (of
+    PSNR and SSIM; None: the library's rule from ``imgs``' dtype), ``K1``, ``K2``, ``use_sample_covariance`` as in the library;
+    ``gaussian_weights``, ``gradient``, ``multichannel`` set True raise ValueError.  A mixed pair is scored as the library scores it:
+    a uint8 frame against a float64 result in [0, 1] is compared with data_range 255 -- pass ``data_range`` (and frames of one scale)
+    for figures that mean something.  Frames that hold a NaN are refused."""
+    spec = _lib.metrics_spec(win_size, data_range, **ssim_kwargs)
+    a, b = _lib.metrics_frames(frames=imgs), _lib.metrics_frames(frames=denoised)
+    _refuse_nan(a.frames)
+    _refuse_nan(b.frames)
+    res = (ctx or _ctx()).metrics_images(a, b, spec, full=full)
+    return _metrics_dict(*res) if full else _metrics_dict(res)
 
 
 def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
@@ -117,8 +161,9 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     place for some arguments -- visible in float64 results only), 'tvc' bit for bit with one deviation: a float32 image is
     iterated in float64 (the result is the reference's on ``image.astype(float64)``).  Images of any other dtype are converted
     to float64 first.  Any other keyword raises ValueError naming it; an
-    unknown technique prints the reference's message and returns None, as the reference does.  ``plot`` and ``verbose`` are
-    accepted and ignored.
+    unknown technique prints the reference's message and returns None, as the reference does.  ``plot`` is accepted and ignored
+    with a warning; ``verbose`` prints the reference's four lines -- Peak-SNR, Structural Similarity, Mean Square Error (the min-max
+    NRMSE), Shannon Entropy, rounded to 2, 2, 5 and 3 places -- from ``denoise_imgs(..., return_metrics=True)``.
     'nl' is scikit-image's non-local means with ``fast_mode=False`` (``patch_size``, ``patch_distance``, ``h``, ``sigma``): the
     library's classic algorithm bit for bit, in float64 -- integer frames keep their range, a float32 frame gives the library's
     result on ``image.astype(float64)``, and a candidate whose final patch distance exceeds 708 weighs 0.
@@ -144,10 +189,16 @@ def denoise(image, technique, kwargs, plot=False, verbose=False, ctx=None):
     if technique not in _lib.DN_OF_TECHNIQUE and technique not in _lib.PRE_STAGES:
         print("Denoising technique not implemented.")
         return None
-    if plot or verbose:
+    if plot:
         import warnings
-        warnings.warn("plot and verbose are accepted for API compatibility but ignored by the GPU denoiser")
-    return denoise_imgs([np.asarray(image)], technique, kwargs, ctx=ctx)[0]
+        warnings.warn("plot is accepted for API compatibility but ignored by the GPU denoiser")
+    if not verbose:
+        return denoise_imgs([np.asarray(image)], technique, kwargs, ctx=ctx)[0]
+    out, m = denoise_imgs([np.asarray(image)], technique, kwargs, ctx=ctx, return_metrics=True)
+    psnr, ss = round(float(m["psnr"][0]), 2), round(float(m["ssim"][0]), 2)
+    nmse, entropy = round(float(m["nrmse"][0]), 5), round(float(m["entropy"][0]), 3)
+    print(f'Peak-SNR: {psnr}.\nStructural Similarity: {ss}.\nMean Square Error: {nmse}.\nShannon Entropy: {entropy}.\n')
+    return out[0]
 
 
 def construct_test_img(size, amplitude, curvature, noise_level, ltype, intensity, gaps=False, seed=None):

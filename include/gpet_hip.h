@@ -984,6 +984,39 @@ int gpet_batch_label_maps_xy(gpet_batch* b, const gpet_polar* polar, int Ms, int
                              unsigned int flags, void* const* out);
 int gpet_label_thick_count(int n_maps, int L, int N, int64_t* count);
 
+/* ---- denoise quality metrics: what the reference's denoise(verbose=True) prints (gpet_utils.py:151-156) ------------------------------ */
+/* The four figures of scikit-image 0.18.3 for n_img pairs (a = the frame as given, b = the denoised frame, M x N each, pixel types pix_a
+ * and pix_b, which may differ): peak_signal_noise_ratio(a, b), structural_similarity(a, b) in its default form (uniform window),
+ * normalized_root_mse(a, b, normalization='min-max') and shannon_entropy(b).  csrc/gpet_metrics_plan.h states the arithmetic:
+ *   PSNR, NRMSE  a - b and its square round in the library's working type (f32 unless a or b is f64), the squares are summed in f64;
+ *                data_range 0: the library's rule from a's type (255, 65535; floats 1 when min(a) >= 0, else 2 -- a float frame
+ *                outside [-1, 1] is refused in the library's words); min(a), max(a) and their difference in the working type.
+ *   SSIM         both frames widened to f64; the planes x, y, x x, y y, x y through scipy.ndimage.uniform_filter's running sums (axis 0,
+ *                then axis 1, reflect), S in the library's order of operations, no fused multiply-add: the S map is the library's bit
+ *                for bit.  data_range 0: 255, 65535, floats 2.  The mean runs over the map cropped by (win_size - 1) / 2.
+ *   entropy      the counts of b's distinct values (-0.0 and 0.0 are one) are exact: b's order-preserving keys are sorted in workspace.
+ * The deviations are three summation orders -- the squared differences, S over the crop, the entropy terms -- which the plan header
+ * defines (metrics_sum); DESIGN.md section 9 gives the bounds that follow.  Frames that hold a NaN have no defined figures.
+ * out (host, f64 [n_img][4]): psnr, ssim, nrmse, entropy of every pair.  ssim_maps (NULL, or [n_img] pointers to f64 [M*N]): the S map
+ * of every pair.  flags: GPET_RAW_ON_DEVICE (raw_a[] are device pointers), GPET_METRICS_B_ON_DEVICE (raw_b[] are),
+ * GPET_METRICS_MAPS_ON_DEVICE (ssim_maps[] are).  The pairs go through workspace the context owns, grown on demand, in chunks of at most
+ * 512 MB: six f64 planes per pair and the staged copies of host frames.  The call waits for the stream: it reads the sums back and
+ * finishes the figures on the host.  GPET_ERR_BAD_ARG, gpet_last_error carrying metrics_check's words (the library's own where it has
+ * some), and nothing launched: a null pointer, no frame, an unknown pixel type, win_size above an extent ("win_size exceeds image
+ * extent. ..."), even ("Window size must be odd.") or below 3, a negative K1 or K2, a data_range that is negative or not finite, a
+ * frame above 2^26 pixels or whose workspace exceeds the chunk budget, unknown flag bits.  (Added without a change of
+ * GPET_ABI_VERSION: the surface only grew.) */
+typedef struct gpet_metrics {
+  int32_t win_size;               /* odd, 3 .. min(M, N); the library's default 7 */
+  int32_t use_sample_covariance;  /* not 0: covariances normalised by NP / (NP - 1) (the library's default) */
+  double K1, K2;                  /* the library's defaults 0.01, 0.03 */
+  double data_range;              /* above 0: R of PSNR and SSIM; 0: the library's rule from a's pixel type */
+} gpet_metrics;
+#define GPET_METRICS_B_ON_DEVICE 32u
+#define GPET_METRICS_MAPS_ON_DEVICE 64u
+int gpet_metrics_images(gpet_ctx* ctx, const void* const* raw_a, int pix_a, const void* const* raw_b, int pix_b, int n_img, int M, int N,
+                        const gpet_metrics* spec, unsigned int flags, double* out, double* const* ssim_maps);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Enqueue one stage `reps` times between two hipEvents on the context's stream and return the
  * mean milliseconds per repetition.  stage: 0 fit+predict+cov, 1 factor, 2 normals, 3 sample
