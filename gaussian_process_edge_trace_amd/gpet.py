@@ -427,6 +427,24 @@ def _raw_stack(raw_imgs):
     raise ValueError("raw_imgs must be an (M, N) frame, a (B, M, N) stack or a list of (M, N) frames")
 
 
+_BAND_R0_ALONE = "band_r0 places the bands of band_rows: it needs band_rows"
+
+
+def refuse_polar_vertical(polar, transposed):
+    """The one refusal of ``polar`` on a vertical batch or sequence (``transposed``: what ``resolve_orientation`` returned)."""
+    if polar is not None and transposed:
+        raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
+                         "the unwrapped frame")
+
+
+def check_kernel_of(kernel_of, n_kernels):
+    """``kernel_of`` as a list of ints, every one an index into ``n_kernels`` gradient kernels; ValueError otherwise."""
+    kernel_of = [int(v) for v in np.asarray(kernel_of).reshape(-1)]
+    if any(k < 0 or k >= n_kernels for k in kernel_of):
+        raise ValueError("kernel_of holds an index outside grad_kernel's %d kernels" % n_kernels)
+    return kernel_of
+
+
 def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None,
                          raw_dtype=None, grad_kernel=None, denoise=None, kernel_of=None, image_of=None, band_rows=None, band_r0=None,
                          inits=None, transposed=False, polar=None):
@@ -448,36 +466,19 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
     ``polar`` (a dict as ``_lib.polar_spec`` takes it, or a PolarSpec; raw frames only, not with ``transposed``): the frames are
     unwrapped to (radius x angle) first -- ``shape`` is the polar shape (n_r, W), the dict also has ``src_shape``, the frames' own, and
     ``grad_shape`` of device frames is the frames' own.  ``polar=None``: exactly the dict described above."""
-    if polar is not None:
-        if transposed:
-            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
-                             "the unwrapped frame")
-        if raw_imgs is None and raw_device_ptrs is None:
-            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs with grad_kernel): gradient images are past that stage")
-    if transposed:
-        src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
-                                   denoise, kernel_of=kernel_of, image_of=image_of)
-        M, N = src["shape"]
-        src["trace_shape"] = (N, M)
-        if band_rows is not None:
-            src["band"] = resolve_bands(inits, N, band_rows, band_r0)
-            src["trace_shape"] = (src["band"][0], M)
-        elif band_r0 is not None:
-            raise ValueError("band_r0 places the bands of band_rows: it needs band_rows")
-        return src
-    if band_rows is not None:
-        if all(a is None for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs)):
-            raise ValueError("band_rows needs images: the full frames (raw_imgs / raw_device_ptrs with grad_kernel) or full-frame "
-                             "gradient images (grad_imgs / grad_device_ptrs) the bands are cut from")
-        src = resolve_image_source(n_edges, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
-                                   denoise, kernel_of=kernel_of, image_of=image_of, polar=polar)
-        src["band"] = resolve_bands(inits, src["shape"][0], band_rows, band_r0)
-        src["trace_shape"] = (src["band"][0], src["shape"][1])
-        return src
-    if band_r0 is not None:
-        raise ValueError("band_r0 places the bands of band_rows: it needs band_rows")
     have_grad = grad_imgs is not None or grad_device_ptrs is not None
     have_raw = raw_imgs is not None or raw_device_ptrs is not None
+    if polar is not None:
+        refuse_polar_vertical(polar, transposed)
+        if not have_raw:
+            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs with grad_kernel): gradient images are past that stage")
+    # (a horizontal batch hears what is wrong with the band keywords themselves before its images are looked at; a vertical one has
+    #  always heard of its images first -- the order of two simultaneous refusals is kept)
+    if band_rows is not None and not transposed and not have_grad and not have_raw:
+        raise ValueError("band_rows needs images: the full frames (raw_imgs / raw_device_ptrs with grad_kernel) or full-frame "
+                         "gradient images (grad_imgs / grad_device_ptrs) the bands are cut from")
+    if band_rows is None and band_r0 is not None and not transposed:
+        raise ValueError(_BAND_R0_ALONE)
     if denoise is not None and not have_raw:
         raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs with grad_kernel): gradient images are past that stage")
     if have_grad and have_raw:
@@ -498,20 +499,22 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
         if multi and kernel_of is None:
             raise ValueError("a list of %d kernels in grad_kernel needs kernel_of, the kernel index of every edge" % len(kernels))
         if kernel_of is not None:
-            kernel_of = [int(v) for v in np.asarray(kernel_of).reshape(-1)]
-            if any(k < 0 or k >= len(kernels) for k in kernel_of):
-                raise ValueError("kernel_of holds an index outside grad_kernel's %d kernels" % len(kernels))
+            kernel_of = check_kernel_of(kernel_of, len(kernels))
             if set(kernel_of) != set(range(len(kernels))):
                 raise ValueError("kernel_of never uses kernel %d of grad_kernel" % min(set(range(len(kernels))) - set(kernel_of)))
             if image_of is not None and len(image_of) != len(kernel_of):
                 raise ValueError("kernel_of has %d entries, image_of %d" % (len(kernel_of), len(image_of)))
-            if raw_device_ptrs is not None:
-                if grad_shape is None or raw_dtype is None:
-                    raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
-                frames = _as_list(raw_device_ptrs)
-                share = len(frames) == 1
-            else:
-                frames, share = _raw_stack(raw_imgs)
+        if raw_device_ptrs is not None:
+            if grad_shape is None or raw_dtype is None:
+                raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
+            frames = _as_list(raw_device_ptrs)
+            share, where = len(frames) == 1, dict(device_ptrs=frames, dtype=raw_dtype, shape=grad_shape)
+        else:
+            frames, share = _raw_stack(raw_imgs)
+            where = dict(frames=frames)
+        # (a slot table: the distinct (frame, kernel) pairs are the images, and the batch's image map is the edge-to-slot map)
+        slots, table = None, {}
+        if kernel_of is not None:
             B = len(kernel_of)
             if image_of is None and not share and len(frames) != B:
                 raise ValueError("kernel_of has %d entries for %d raw frames, one per edge" % (B, len(frames)))
@@ -519,40 +522,37 @@ def resolve_image_source(n_edges, grad_imgs=None, grad_device_ptrs=None, grad_sh
             if image_of is not None and len(frames) != n_edges:
                 raise ValueError("%d raw frames for %d frames of the image map" % (len(frames), n_edges))
             frame_of, kernel_of_slot, edge_slot = _lib.derive_slots(edge_frames, kernel_of)
-            if raw_device_ptrs is not None:
-                raw = _lib.RawFrames(kernels, device_ptrs=frames, dtype=raw_dtype, shape=grad_shape, denoise=denoise,
-                                     slots=(frame_of, kernel_of_slot), polar=polar)
-            else:
-                raw = _lib.RawFrames(kernels, frames=frames, denoise=denoise, slots=(frame_of, kernel_of_slot), polar=polar)
-            return dict(kind="raw", share=False, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
-                        batch=dict(grads=None, raw=raw), image_of=edge_slot, edge_frames=edge_frames,
-                        **({} if polar is None else dict(src_shape=raw.src_shape)))
-        if raw_device_ptrs is not None:
-            if grad_shape is None or raw_dtype is None:
-                raise ValueError("raw_device_ptrs need grad_shape = (M, N) and raw_dtype")
-            ptrs = _as_list(raw_device_ptrs)
-            raw = _lib.RawFrames(grad_kernel, device_ptrs=ptrs, dtype=raw_dtype, shape=grad_shape, denoise=denoise, polar=polar)
-            share = len(ptrs) == 1
-        else:
-            frames, share = _raw_stack(raw_imgs)
-            raw = _lib.RawFrames(grad_kernel, frames=frames, denoise=denoise, polar=polar)
-        if not share and len(raw) != n_edges:
+            slots, share, table = (frame_of, kernel_of_slot), False, dict(image_of=edge_slot, edge_frames=edge_frames)
+        raw = _lib.RawFrames(kernels if slots is not None else kernels[0], denoise=denoise, slots=slots, polar=polar, **where)
+        if slots is None and not share and len(raw) != n_edges:
             raise ValueError("%d raw frames for %d edges" % (len(raw), n_edges))
-        return dict(kind="raw", share=share, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
-                    batch=dict(grads=None, raw=raw), **({} if polar is None else dict(src_shape=raw.src_shape)))
-    if grad_device_ptrs is not None:
+        src = dict(kind="raw", share=share, shape=tuple(raw.shape), pix=raw.pix, on_device=raw.frames is None,
+                   batch=dict(grads=None, raw=raw), **table)
+        if polar is not None:
+            src["src_shape"] = raw.src_shape
+    elif grad_device_ptrs is not None:
         if grad_shape is None:
             raise ValueError("grad_device_ptrs need grad_shape = (M, N)")
         ptrs = _as_list(grad_device_ptrs)
         share = len(ptrs) == 1
         assert share or len(ptrs) == n_edges
-        return dict(kind="grad", share=share, shape=tuple(grad_shape), on_device=True,
-                    batch=dict(grads=None, device_ptrs=ptrs, shape=grad_shape))
-    share = not isinstance(grad_imgs, (list, tuple))
-    imgs = [grad_imgs] if share else list(grad_imgs)
-    assert share or len(imgs) == n_edges
-    g32 = [np.ascontiguousarray(g, dtype=np.float32) for g in imgs]
-    return dict(kind="grad", share=share, shape=tuple(g32[0].shape), on_device=False, batch=dict(grads=g32))
+        src = dict(kind="grad", share=share, shape=tuple(grad_shape), on_device=True, batch=dict(grads=None, device_ptrs=ptrs, shape=grad_shape))
+    else:
+        share = not isinstance(grad_imgs, (list, tuple))
+        imgs = [grad_imgs] if share else list(grad_imgs)
+        assert share or len(imgs) == n_edges
+        g32 = [np.ascontiguousarray(g, dtype=np.float32) for g in imgs]
+        src = dict(kind="grad", share=share, shape=tuple(g32[0].shape), on_device=False, batch=dict(grads=g32))
+    # (the image the batch traces: the transposed gradient image of a vertical batch, and of that the H rows of a band)
+    M, N = src["shape"][::-1] if transposed else src["shape"]
+    if transposed:
+        src["trace_shape"] = (M, N)
+    if band_rows is not None:
+        src["band"] = resolve_bands(inits, M, band_rows, band_r0)
+        src["trace_shape"] = (src["band"][0], N)
+    elif band_r0 is not None:
+        raise ValueError(_BAND_R0_ALONE)
+    return src
 
 
 def init_row_span(init):
@@ -691,6 +691,127 @@ def _shift_rows(d, keys, r0, col=None):
     return out
 
 
+class BatchImages(object):
+    """What images a batch takes and what its next frames must look like: the one place that knows, and it needs no device.  Built
+    once from the image arguments of ``GP_Edge_Tracing_Batch`` (``inits`` in the batch's coordinates, ``transposed`` what
+    ``resolve_orientation`` returned); ``resolve_image_source`` decides, here and in ``next_frame``.
+    ``batch_kwargs``: the keyword arguments of ``_lib.Batch`` that carry the images (``grads``, ``share_image`` and the library's own
+    ``image_of`` -- the edge-to-slot map where there is a slot table -- included); ``trace_shape``: the shape the edges' parameters are
+    resolved for; ``band``: (H, r0 list or None), or None without bands; ``polar`` / ``src_shape``: the resolved polar spec (pad
+    known) and the frames' own shape, or None; ``edge_frames``: the frame of every edge of a slot table, else None.
+    ``n_img`` images of ``frame_shape`` (as they lie in the caller's memory; the polar shape of a polar batch) are what the library
+    holds, derived the way it derives them -- one shared image: 1; an image map: its count; a slot table: its slots; else one per edge
+    -- and ``n_frames`` raw frames are what makes them: as many, but behind a slot table the frames the constructor got."""
+
+    def __init__(self, inits, grad_imgs=None, grad_device_ptrs=None, grad_shape=None, raw_imgs=None, raw_device_ptrs=None, raw_dtype=None,
+                 grad_kernel=None, denoise=None, image_of=None, kernel_of=None, band_rows=None, band_r0=None, polar=None, transposed=False):
+        B = n_given = len(inits)
+        if image_of is not None:
+            image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
+            if len(image_of) != B:
+                raise ValueError("image_of has %d entries for %d edges" % (len(image_of), B))
+            n_given = max(image_of) + 1
+            given = [a for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs) if a is not None]
+            if len(given) == 1 and not (isinstance(given[0], (list, tuple)) or np.ndim(given[0]) == 3):
+                raise ValueError("with image_of the images are a list (or stack) of n_img = %d" % n_given)
+            if len(given) == 1 and len(given[0]) != n_given:
+                raise ValueError("%d images for an image map of n_img = %d" % (len(given[0]), n_given))
+            if grad_imgs is not None:
+                grad_imgs = list(grad_imgs)
+        if kernel_of is not None and len(np.asarray(kernel_of).reshape(-1)) != B:
+            raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
+        src = resolve_image_source(n_given, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
+                                   denoise, kernel_of=kernel_of, image_of=image_of, band_rows=band_rows, band_r0=band_r0,
+                                   inits=None if band_rows is None else list(inits), transposed=transposed, polar=polar)
+        raw = src["batch"].get("raw")
+        self.transposed = transposed
+        self.trace_shape, self.frame_shape = src.get("trace_shape", src["shape"]), src["shape"]
+        self.band, self.src_shape, self.edge_frames = src.get("band"), src.get("src_shape"), src.get("edge_frames")
+        self.polar = None if polar is None else raw.polar  # (resolved: pad known)
+        self.mapped = image_of is not None
+        self.share = src["share"] and not self.mapped  # (a map of one image is the shared layout, decided by the library)
+        # (what next_frame falls back on; with a slot table the kernels as the table counts them and the kernel of every edge)
+        self._dtype, self._denoise, self._kernel_of = raw_dtype, denoise, None
+        self.n_img = self.n_frames = 1 if self.share else n_given
+        if self.edge_frames is not None:
+            self._kernel, self._kernel_of = raw.kernels, check_kernel_of(kernel_of, len(raw.kernels))
+            image_of, self.n_img, self.n_frames = src["image_of"], raw.n_slots, len(raw)
+        else:
+            self._kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
+        self.batch_kwargs = dict(src["batch"], share_image=self.share, image_of=image_of, transposed=transposed)
+        if self.band is not None:
+            self.batch_kwargs["band"] = self.band
+
+    def images_text(self):
+        if self._kernel_of is not None:
+            return "%d raw frames behind the %d image slots of the batch's slot table" % (self.n_frames, self.n_img)
+        if self.mapped:
+            return "%d images, the batch's image map has n_img = %d" % (self.n_img, self.n_img)
+        return "one shared image" if self.share else "one image per edge, %d" % self.n_img
+
+    def misfit(self, what, n, shape=True):
+        """The one refusal of images that do not fit the batch: ``n`` of ``what`` ('frames' / 'images') were given."""
+        return ValueError("the new %s do not fit the batch: %d given (%s%s)"
+                          % (what, n, self.images_text(), ", %d x %d" % self.frame_shape if shape else ""))
+
+    def frame_polar(self, polar, have_raw):
+        """The spec ``set_frame`` unwraps the new frames with: the batch's own, or the one ``polar`` asks for when it keeps the shape and
+        the meaning of rows and columns.  ValueError for everything else."""
+        if polar is None:
+            return self.polar
+        if self.polar is None:
+            raise ValueError("polar: this batch was not built on polar frames (give polar= to the constructor)")
+        if not have_raw:
+            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs): gradient images are past that stage")
+        if isinstance(polar, dict):
+            polar = dict(self.polar.as_dict(), **{k: v for k, v in polar.items() if not (k == "pad" and v is None)})
+        new = _lib.polar_spec(polar).resolved(self.polar.pad)
+        old = self.polar
+        if (new.n_r, new.n_theta, new.pad) != (old.n_r, old.n_theta, old.pad):
+            raise ValueError("polar: set_frame cannot change the shape of the polar frames: n_r, n_theta, pad are %d, %d, %d, not %d, %d, %d"
+                             % (old.n_r, old.n_theta, old.pad, new.n_r, new.n_theta, new.pad))
+        if (new.r0, new.dr, new.theta0) != (old.r0, old.dr, old.theta0):
+            raise ValueError("polar: set_frame replaces the centres only: r0, dr, theta0 are %r, %r, %r" % (old.r0, old.dr, old.theta0))
+        return new
+
+    def next_frame(self, grad_imgs=None, grad_device_ptrs=None, raw_imgs=None, raw_device_ptrs=None, raw_dtype=None, grad_kernel=None,
+                   denoise=None, polar=None):
+        """(the keyword arguments of ``Batch.set_images`` that carry the next frame's images, the polar spec to adopt with them), from
+        the image arguments of ``set_frame``; kernel(s), slot table, dtype and ``denoise`` are the constructor's where the call does
+        not give them.  ValueError for images that do not fit the batch and whatever else ``set_frame`` refuses about them.  Pure:
+        nothing on this object changes (``set_frame`` adopts the spec once the images are swapped)."""
+        have_raw = raw_imgs is not None or raw_device_ptrs is not None
+        new_polar = self.frame_polar(polar, have_raw)
+        if denoise not in (None, False) and not have_raw:
+            raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
+        if have_raw:
+            if raw_imgs is not None and self.batch_kwargs["image_of"] is not None and np.ndim(raw_imgs) == 2:
+                raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
+            have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
+            if not (self.n_frames == 1 and np.ndim(have) == 2) and len(have) != self.n_frames:
+                raise self.misfit("frames", len(have))
+            src = resolve_image_source(self.n_frames, grad_imgs, grad_device_ptrs,
+                                       self.frame_shape if self.polar is None else self.src_shape,  # (device frames: their own shape)
+                                       raw_imgs, raw_device_ptrs, self._dtype if raw_dtype is None else raw_dtype,
+                                       self._kernel if grad_kernel is None else grad_kernel,
+                                       None if denoise is False else (self._denoise if denoise is None else denoise),
+                                       kernel_of=self._kernel_of, image_of=self.edge_frames, polar=new_polar)
+            raw = src["batch"]["raw"]
+            # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
+            if len(raw) != self.n_frames or src["shape"] != self.frame_shape:
+                raise self.misfit("frames", len(raw))
+            return dict(raw=raw), new_polar
+        if grad_device_ptrs is not None:
+            ptrs = _as_list(grad_device_ptrs)
+            if len(ptrs) != self.n_img:
+                raise self.misfit("images", len(ptrs), shape=False)
+            return dict(device_ptrs=ptrs), new_polar
+        imgs = list(grad_imgs) if isinstance(grad_imgs, (list, tuple)) else [grad_imgs]
+        if len(imgs) != self.n_img or any(np.shape(g) != self.frame_shape for g in imgs):
+            raise self.misfit("images", len(imgs))
+        return dict(grads=[np.ascontiguousarray(g, dtype=np.float32) for g in imgs]), new_polar  # (no copy of f32 input)
+
+
 class GP_Edge_Tracing_Batch(object):
     """B independent edges traced together on one GPU (BASELINE config 4's per-GPU share).
 
@@ -702,9 +823,6 @@ class GP_Edge_Tracing_Batch(object):
     or a list with one image per edge; ``seeds``: per-edge RNG seed (gpet.py:33,839).
     Remaining keyword arguments are the reference constructor's (gpet.py:22-35), common to all edges.
     """
-
-    orientation, _tr, _swap = "horizontal", False, False  # (what the constructor sets for orientation='vertical')
-    polar, _src_shape = None, None  # (what the constructor sets for polar=)
 
     def __init__(self, inits, grad_imgs, seeds, kernel_options=(1, 3, 3), noise_y=1, N_samples=500, score_thresh=1,
                  delta_x=20, keep_ratio=0.1, pixel_thresh=5, return_std=False, fix_endpoints=True, *, obs=None,
@@ -776,50 +894,18 @@ class GP_Edge_Tracing_Batch(object):
         ``grad_shape`` of ``raw_device_ptrs`` stays the frames' own shape.  ``set_frame`` keeps the spec; ``set_frame(...,
         polar=dict(centre=...))`` replaces the centres.  Refused with gradient images and with ``orientation='vertical'``."""
         self.orientation = orientation
-        self._tr = resolve_orientation(orientation)       # the library holds the transposed gradient images
-        self._swap = self._tr and not _batch_coords       # ... and this object swaps the coordinates of what it takes and returns
-        if polar is not None and self._tr:  # (before the init points are looked at as those of a vertical edge)
-            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
-                             "the unwrapped frame")
+        tr = resolve_orientation(orientation)       # the library holds the transposed gradient images
+        self._swap = tr and not _batch_coords       # ... and this object swaps the coordinates of what it takes and returns
+        refuse_polar_vertical(polar, tr)  # (before the init points are looked at as those of a vertical edge)
         if self._swap:
             inits = vertical_inits(inits)
             obs = None if obs is None else [swap_xy(np.asarray(o).reshape(-1, 2)) for o in obs]
         B = len(inits)
         self._init_follow = resolve_init_follow(init_follow)
-        if image_of is not None:
-            image_of = [int(v) for v in np.asarray(image_of).reshape(-1)]
-            if len(image_of) != B:
-                raise ValueError("image_of has %d entries for %d edges" % (len(image_of), B))
-            n_img = max(image_of) + 1
-            given = [a for a in (grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs) if a is not None]
-            if len(given) == 1 and not (isinstance(given[0], (list, tuple)) or np.ndim(given[0]) == 3):
-                raise ValueError("with image_of the images are a list (or stack) of n_img = %d" % n_img)
-            if len(given) == 1 and len(given[0]) != n_img:
-                raise ValueError("%d images for an image map of n_img = %d" % (len(given[0]), n_img))
-            if grad_imgs is not None:
-                grad_imgs = list(grad_imgs)
-        if kernel_of is not None and len(np.asarray(kernel_of).reshape(-1)) != B:
-            raise ValueError("kernel_of has %d entries for %d edges" % (len(np.asarray(kernel_of).reshape(-1)), B))
-        src = resolve_image_source(B if image_of is None else n_img, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs,
-                                   raw_dtype, grad_kernel, denoise, kernel_of=kernel_of, image_of=image_of, band_rows=band_rows,
-                                   band_r0=band_r0, inits=None if band_rows is None else list(inits), transposed=self._tr, polar=polar)
-        self._denoise = denoise
-        self.polar = None if polar is None else src["batch"]["raw"].polar  # (resolved: pad known)
-        self._src_shape = src.get("src_shape")
-        self.band_rows, self.band_r0 = (None, None) if band_rows is None else (src["band"][0], src["band"][1])
-        # (a slot table: the kernels, the kernel and the frame of every edge are remembered for set_frame; the batch's own image
-        #  map is then the edge-to-slot map)
-        self._kernel_of, self._edge_frames, self._n_frames = None, None, None
-        if "image_of" in src:
-            self._kernel_of = [int(v) for v in np.asarray(kernel_of).reshape(-1)]
-            self._edge_frames, self._n_frames = src["edge_frames"], len(src["batch"]["raw"])
-            self._grad_kernel = src["batch"]["raw"].kernels
-            image_of = src["image_of"]
-        else:
-            self._grad_kernel = None if grad_kernel is None else np.array(grad_kernel, dtype=np.float64)
-        self._raw_dtype = raw_dtype
-        share = src["share"] and image_of is None  # (a map of one image is the shared layout, decided by the library)
-        shapes = [src.get("trace_shape", src["shape"])] * B  # (banded: the parameters are those of the (H, N) crop)
+        im = self._images = BatchImages(inits, grad_imgs, grad_device_ptrs, grad_shape, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel,
+                                        denoise, image_of, kernel_of, band_rows, band_r0, polar, transposed=tr)
+        self.band_rows, self.band_r0 = (None, None) if im.band is None else im.band
+        shapes = [im.trace_shape] * B  # (banded: the parameters are those of the (H, N) crop)
         assert len(seeds) == B
         obs = [np.array([])] * B if obs is None else list(obs)
         inits = list(inits)  # (an ndarray of shape (B, n, 2) makes a fresh view per access: materialise the items once)
@@ -848,11 +934,10 @@ class GP_Edge_Tracing_Batch(object):
             self._ps.append(pe)
             abi.append(hit[1])
         self._ctx = _ctx if _ctx is not None else _lib.Context(device, stream)
-        kw = dict(src["batch"])
-        if band_rows is not None:
-            kw["band"] = (self.band_rows, self.band_r0)
-        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], share_image=share, image_of=image_of,
-                                 transposed=self._tr, **kw)
+        kw = dict(im.batch_kwargs)
+        self._batch = _lib.Batch(self._ctx, kw.pop("grads"), abi, [p["init"] for p in self._ps], **kw)
+        # (from here on what fits the batch is decided by `im` alone: once, that it counts the images as the library does)
+        assert (im.n_img, tuple(im.frame_shape)) == (self._batch.n_img, tuple(self._batch.frame_shape))
         if band_rows is not None:  # (the table as the library placed or took it; observations are kept in band rows from here on)
             self.band_r0 = self._batch.band_r0()
             self._init_span = [init_row_span(p["init"]) for p in self._ps]
@@ -900,13 +985,15 @@ class GP_Edge_Tracing_Batch(object):
         self._batch.reset()
         self._set_obs()
 
-    def _images_text(self):
-        b = self._batch
-        if self._kernel_of is not None:
-            return "%d raw frames behind the %d image slots of the batch's slot table" % (self._n_frames, b.n_img)
-        if b.image_of is not None:
-            return "%d images, the batch's image map has n_img = %d" % (b.n_img, b.n_img)
-        return "one shared image" if b.share_image else "one image per edge, %d" % b.n_img
+    @property
+    def polar(self):
+        """The resolved polar spec the frames are unwrapped by (``set_frame`` may replace its centres), None without ``polar=``."""
+        return self._images.polar
+
+    def _keep_obs(self, obs):
+        """The warm-start observation sets as ``reset()`` sets them again (the device's own are read back once for this)."""
+        for p, o in zip(self._ps, obs):
+            p["obs"] = np.asarray(o).reshape(-1, 2).astype(np.int64)
 
     def set_frame(self, grad_imgs=None, obs=None, seeds=None, grad_device_ptrs=None, next_frame=True, raw_imgs=None,
                   raw_device_ptrs=None, raw_dtype=None, grad_kernel=None, denoise=None, warm_every=None, warm_from=None,
@@ -922,7 +1009,8 @@ class GP_Edge_Tracing_Batch(object):
         ``denoise`` default to the constructor's (``denoise=None``); ``denoise=False`` takes these frames as they are, without
         denoising, whatever the constructor was given.
         A batch with an image map takes ``n_img`` images.  A call whose images do not fit the batch raises ValueError, a
-        ``warm_every`` without a last trace raises GpetError, and both leave the batch as it was.
+        ``warm_every`` without a last trace raises GpetError, and both leave the batch as it was; a call that is wrong in both ways
+        raises the ValueError.
         ``warm_every=k`` instead of ``obs``: the warm start is made on the device (gpet_batch_warm_start) -- every edge's
         observations from its own last converged fit by the rule of ``sequence.warm_start_obs(trace, x_st, x_en, k, algo_thresh,
         M)`` -- with no trip of the traces through the host; the sets are read back once, so that ``reset()`` restores the same
@@ -946,13 +1034,17 @@ class GP_Edge_Tracing_Batch(object):
         rows, with the x and counts the batch has (on a banded batch only together with an explicit ``band=[r0_e]`` that holds them
         as well as the current points).  Default: ``'follow'`` when the constructor or this call has ``init_follow``, else
         ``'keep'``.  Bands are placed against the points as they are BEFORE this call; the search then stays inside the band.
-        Whatever is refused raises ValueError before anything is touched.
+        Whatever is refused without a device -- images that do not fit, ``denoise`` without raw frames and the ensemble keywords
+        included -- raises ValueError before anything is touched: every such check comes before the first device call, so neither the
+        kept ensemble nor ``last_ensemble`` has changed when it does.
         A vertical batch takes its frames and gradient images in the frame's layout, ``obs`` and ``init`` as (x, y) of the frame, and
         ``band`` as first frame columns.
         A polar batch unwraps the new frames by the constructor's spec; ``polar=dict(centre=...)`` replaces the centres from this frame
         on (the whole dict may be given again: whatever would change the polar shape -- ``n_r``, ``n_theta``, ``pad`` -- or the radii
         and angles behind the rows and columns -- ``r0``, ``dr``, ``theta0`` -- is refused with ValueError)."""
-        new_polar = self._frame_polar(polar, raw_imgs is not None or raw_device_ptrs is not None)
+        # 1. every check that needs no device, in the order they are reported
+        if polar is not None:  # (a spec that is refused is refused first, as ever; next_frame takes the checked one as it is)
+            polar = self._images.frame_polar(polar, raw_imgs is not None or raw_device_ptrs is not None)
         if warm_every is not None and obs is not None:
             raise ValueError("obs and warm_every are alternatives: the device derives the observations itself")
         if warm_from is not None:
@@ -977,6 +1069,9 @@ class GP_Edge_Tracing_Batch(object):
                     raise ValueError("band of edge %d: %s (M = %d, band_rows = %d, r0 = %d, init rows %d .. %d)"
                                      % ((e, why, self._batch.frame_M, self.band_rows, r0) + self._init_span[e]))
         imode, ipoints = resolve_frame_init(init, init_follow, self._init_follow, self._inits, self._batch.frame_M, self.band_rows, mode)
+        images, new_polar = self._images.next_frame(grad_imgs, grad_device_ptrs, raw_imgs, raw_device_ptrs, raw_dtype, grad_kernel, denoise,
+                                                    polar)
+        # 2. the device calls
         if warm_every is not None or mode == "follow":
             self._batch.warm_start_ready()  # (refused before the images are swapped: the batch stays on its old frames)
         if warm_from is not None:
@@ -984,48 +1079,13 @@ class GP_Edge_Tracing_Batch(object):
             self._batch.ensemble_keep(groups, tol)
             keys = ("trace", "median", "q_lo", "q_hi", "min", "max", "agree", "members", "off", "cost", "medoid", "best_cost")
             self.last_ensemble = self._ensemble_rows([{k: d[k] for k in keys} for d in self._batch.ensemble_kept()[0]], groups)
-
-        def swap(**kw):  # (placement sits between the kept ensemble and the swap; the swap reads the placed table on the device)
-            if mode == "follow":
-                self._batch.band_place(frm=warm_from)
-            elif mode is not None:
-                self._batch.band_set(mode)
-            self._batch.set_images(**kw)
-        if denoise not in (None, False) and raw_imgs is None and raw_device_ptrs is None:
-            raise ValueError("denoise needs raw frames (raw_imgs / raw_device_ptrs)")
-        if raw_imgs is not None or raw_device_ptrs is not None:
-            kern = self._grad_kernel if grad_kernel is None else grad_kernel
-            b = self._batch
-            multi = self._kernel_of is not None
-            n_img = self._n_frames if multi else b.n_img  # (frames expected)
-            fshape = b.frame_shape  # (the frames as they lie: (frame_M, N), on a vertical batch (N, frame_M))
-            given_shape = fshape if self.polar is None else self._src_shape  # (device frames of a polar batch: the frames' own shape)
-            if raw_imgs is not None and b.image_of is not None and np.ndim(raw_imgs) == 2:
-                raw_imgs = [raw_imgs]  # (a 2-D array is ONE frame)
-            have = raw_imgs if raw_imgs is not None else _as_list(raw_device_ptrs)
-            if not (n_img == 1 and np.ndim(have) == 2) and len(have) != n_img:
-                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)" % ((len(have), self._images_text()) + fshape))
-            src = resolve_image_source(n_img, grad_imgs, grad_device_ptrs, given_shape, raw_imgs, raw_device_ptrs,
-                                       self._raw_dtype if raw_dtype is None else raw_dtype, kern,
-                                       None if denoise is False else (self._denoise if denoise is None else denoise),
-                                       kernel_of=self._kernel_of, image_of=self._edge_frames, polar=new_polar)
-            # (whether ONE image is shared was decided at construction: a batch of one edge has one image either way)
-            if len(src["batch"]["raw"]) != n_img or src["shape"] != fshape:
-                raise ValueError("the new frames do not fit the batch: %d given (%s, %d x %d)"
-                                 % ((len(src["batch"]["raw"]), self._images_text()) + fshape))
-            swap(raw=src["batch"]["raw"], next_frame=next_frame)
-            self.polar = new_polar
-        elif grad_device_ptrs is not None:
-            ptrs = _as_list(grad_device_ptrs)
-            if len(ptrs) != self._batch.n_img:
-                raise ValueError("the new images do not fit the batch: %d given (%s)" % (len(ptrs), self._images_text()))
-            swap(device_ptrs=ptrs, next_frame=next_frame)
-        else:
-            imgs = list(grad_imgs) if isinstance(grad_imgs, (list, tuple)) else [grad_imgs]
-            if len(imgs) != self._batch.n_img or any(np.shape(g) != self._batch.frame_shape for g in imgs):
-                raise ValueError("the new images do not fit the batch: %d given (%s, %d x %d)"
-                                 % ((len(imgs), self._images_text()) + self._batch.frame_shape))
-            swap(grads=[np.ascontiguousarray(g, dtype=np.float32) for g in imgs], next_frame=next_frame)  # (no copy of f32 input)
+        # (placement sits between the kept ensemble and the swap; the swap reads the placed table on the device)
+        if mode == "follow":
+            self._batch.band_place(frm=warm_from)
+        elif mode is not None:
+            self._batch.band_set(mode)
+        self._batch.set_images(next_frame=next_frame, **images)
+        self._images.polar = new_polar
         # (the init points move between the swap and the warm start, which keeps columns strictly inside the end points only)
         if imode == "follow":
             self._take_inits(self._batch.init_follow(*ipoints))
@@ -1034,9 +1094,9 @@ class GP_Edge_Tracing_Batch(object):
             self._take_inits(ipoints)
         if warm_from is not None:
             self._batch.warm_start_groups(warm_from, warm_every)
-            obs = self._batch.read_obs_all()  # (what reset() sets again)
         elif warm_every is not None:
             self._batch.warm_start(warm_every)
+        if warm_every is not None:
             obs = self._batch.read_obs_all()  # (what reset() sets again)
         else:
             obs = [np.array([])] * self.B if obs is None else list(obs)
@@ -1045,42 +1105,20 @@ class GP_Edge_Tracing_Batch(object):
             if warm_every is None:  # (a caller's observations are in full-frame rows; the device's own are band rows already)
                 obs = [np.asarray(o).reshape(-1, 2).astype(np.int64) - np.array([0, int(r0)], dtype=np.int64)
                        for o, r0 in zip(obs, self.band_r0)]
-        for e, p in enumerate(self._ps):
-            p["obs"] = np.asarray(obs[e]).reshape(-1, 2).astype(np.int64)
-            if seeds is not None:
-                p["seed"] = int(seeds[e])
+        self._keep_obs(obs)
         if seeds is not None:
             self.seeds = [int(v) for v in seeds]
+            for p, s in zip(self._ps, self.seeds):
+                p["seed"] = s
         if warm_every is None:
             self._set_obs()
-
-    def _frame_polar(self, polar, have_raw):
-        """The spec ``set_frame`` unwraps the new frames with: the batch's own, or the one ``polar`` asks for when it keeps the shape and
-        the meaning of rows and columns.  ValueError for everything else, before anything is touched."""
-        if polar is None:
-            return self.polar
-        if self.polar is None:
-            raise ValueError("polar: this batch was not built on polar frames (give polar= to the constructor)")
-        if not have_raw:
-            raise ValueError("polar needs raw frames (raw_imgs / raw_device_ptrs): gradient images are past that stage")
-        if isinstance(polar, dict):
-            polar = dict(self.polar.as_dict(), **{k: v for k, v in polar.items() if not (k == "pad" and v is None)})
-        new = _lib.polar_spec(polar).resolved(self.polar.pad)
-        old = self.polar
-        if (new.n_r, new.n_theta, new.pad) != (old.n_r, old.n_theta, old.pad):
-            raise ValueError("polar: set_frame cannot change the shape of the polar frames: n_r, n_theta, pad are %d, %d, %d, not %d, %d, %d"
-                             % (old.n_r, old.n_theta, old.pad, new.n_r, new.n_theta, new.pad))
-        if (new.r0, new.dr, new.theta0) != (old.r0, old.dr, old.theta0):
-            raise ValueError("polar: set_frame replaces the centres only: r0, dr, theta0 are %r, %r, %r" % (old.r0, old.dr, old.theta0))
-        return new
 
     def warm_start_from(self, src_of, warm_every):
         """The explicit form of the device's warm start (gpet_batch_warm_start_from), where ``set_frame`` would make it -- after the
         images were swapped: edge e's observations from the last converged fit of edge ``src_of[e]`` (on the same columns), -1 for
         none.  The sets are read back once, so that ``reset()`` restores them.  Returns their sizes."""
         cnt = self._batch.warm_start_from(src_of, warm_every)
-        for p, o in zip(self._ps, self._batch.read_obs_all()):
-            p["obs"] = np.asarray(o).reshape(-1, 2).astype(np.int64)
+        self._keep_obs(self._batch.read_obs_all())
         return cnt
 
     def run_loop(self, max_iter=1000, chunk=64):
@@ -1178,12 +1216,12 @@ class GP_Edge_Tracing_Batch(object):
 
     def default_map_of(self):
         """The map every edge goes on when ``label_maps`` is not told: the raw frame (or image) the edge reads."""
-        if self._edge_frames is not None:
-            return list(self._edge_frames)
-        b = self._batch
-        if b.image_of is not None:
-            return list(b.image_of)
-        return [0] * self.B if b.share_image else list(range(self.B))
+        im = self._images
+        if im.edge_frames is not None:
+            return list(im.edge_frames)
+        if im.mapped:
+            return list(im.batch_kwargs["image_of"])
+        return [0] * self.B if im.share else list(range(self.B))
 
     def label_maps(self, map_of=None, extend=False, thickness=False, space=None, out_device_ptrs=None, thick_device_ptr=None):
         """The regions the traced edges bound, as uint8 label maps made on the device from the converged fits where they lie
@@ -1212,9 +1250,9 @@ class GP_Edge_Tracing_Batch(object):
         if space == "frame":
             if extend or thickness:
                 raise ValueError("extend and thickness belong to the row maps (space='polar')")
-            return self._batch.label_maps_xy(self.polar, self._src_shape, map_of, out_device_ptrs=out_device_ptrs)
-        return self._batch.label_maps(map_of, extend=extend, transposed=self._tr, thickness=thickness, out_device_ptrs=out_device_ptrs,
-                                      thick_device_ptr=thick_device_ptr)
+            return self._batch.label_maps_xy(self.polar, self._images.src_shape, map_of, out_device_ptrs=out_device_ptrs)
+        return self._batch.label_maps(map_of, extend=extend, transposed=self._images.transposed, thickness=thickness,
+                                      out_device_ptrs=out_device_ptrs, thick_device_ptr=thick_device_ptr)
 
     def final_costs(self):
         """(B,) f64: the scorer's cost of every edge's converged mean curve on its own gradient image -- the reference's

@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import split_kernels
-from .gpet import GP_Edge_Tracing_Batch, resolve_init_follow, resolve_orientation, resolve_params, swap_record, swap_xy, vertical_inits
+from .gpet import (GP_Edge_Tracing_Batch, check_kernel_of, refuse_polar_vertical, resolve_init_follow, resolve_orientation, resolve_params,
+                   swap_record, swap_xy, vertical_inits)
 
 
 def chain_slices(n_frames, n_chains):
@@ -170,9 +171,7 @@ class SequenceTracer(object):
         self.T = len(frames)
         self.orientation = orientation
         self._tr = resolve_orientation(orientation)
-        if polar is not None and self._tr:
-            raise ValueError("polar and orientation='vertical' are alternatives: a closed contour is traced as a horizontal edge of "
-                             "the unwrapped frame")
+        refuse_polar_vertical(polar, self._tr)
         self._inits, self.multi = _inits_of(init)
         if not self._inits:
             raise ValueError("no init")
@@ -205,8 +204,7 @@ class SequenceTracer(object):
                 kernel_of = [int(v) for v in kernel_of]
                 if len(kernel_of) != self.E:
                     raise ValueError("kernel_of has %d entries for %d inits" % (len(kernel_of), self.E))
-                if any(k < 0 or k >= len(kernels) for k in kernel_of):
-                    raise ValueError("kernel_of holds an index outside grad_kernel's %d kernels" % len(kernels))
+                check_kernel_of(kernel_of, len(kernels))
                 used = sorted(set(kernel_of))  # (kernels no init uses are dropped: the library refuses a kernel no slot reads)
                 self.grad_kernel = [kernels[k] for k in used]
                 self.kernel_of = [used.index(k) for k in kernel_of]

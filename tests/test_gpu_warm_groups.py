@@ -157,6 +157,23 @@ def test_group_warm_start_equals_the_definition_through_set_obs(amd, ctx, world,
     twin._batch.close()
 
 
+def test_refused_images_touch_neither_the_ensemble_nor_the_batch(amd, ctx, world):
+    """Two gradient images for the batch of one shared image: refused before the ensemble is kept, so ``last_ensemble`` stays and the
+    next accepted call leaves what it leaves on a twin that never saw the refused one."""
+    dev, twin = injected(amd, ctx, world), injected(amd, ctx, world)
+    dev.last_ensemble = before = ["the ensemble of the frame before"]
+    with pytest.raises(ValueError) as err:
+        dev.set_frame([world["nxt"], world["nxt"]], warm_every=5, warm_from="medoid", group_of=GROUPS, tol=TOL)
+    assert str(err.value) == "the new images do not fit the batch: 2 given (one shared image, 72 x 72)"
+    assert dev.last_ensemble is before
+    for b in (dev, twin):
+        b.set_frame(world["nxt"], warm_every=5, warm_from="medoid", group_of=GROUPS, tol=TOL)
+    assert len(dev.last_ensemble) == 8
+    assert_same_state_and_trace(dev, twin, "after a refused call")
+    dev._batch.close()
+    twin._batch.close()
+
+
 # ---- identity, the kept ensemble's life, refusals --------------------------------------------------------------------------------
 SMALL = [0, 1, 2, 71, 72]  # three 70-point edges and two 40-point edges of the scene, traced as they are
 
@@ -339,7 +356,7 @@ def test_refusals_leave_the_batch_on_its_old_frames(amd, ctx, world, small_first
     assert_traces_old_frames(fresh, small_first)
     # and a call that is not refused: last_ensemble is what ensemble() returned for the frame left
     want = fresh.ensemble(g, TOL)
-    assert fresh.last_ensemble is not None
+    assert fresh.last_ensemble is None  # (no refused call, the one for its images included, has kept an ensemble)
     fresh.set_frame(nxt, None, [3, 4, 5, 6, 7], warm_every=5, warm_from="best_cost", group_of=g, tol=TOL)
     assert len(fresh.last_ensemble) == 2
     for dg, dw in zip(fresh.last_ensemble, want):
