@@ -936,7 +936,7 @@ int gpet_batch_write(gpet_batch* b, int e, int which, const void* src, size_t by
       int rc = read_scalars(b, e, &s);
       if (rc) return rc;
       dst = z_slot(E, s.iter);
-      if (s.iter < b->zst.iters) b->zst.tags[(size_t)e * b->zst.iters + s.iter] = 0;  // (injected: not what any seed draws)
+      if (uint64_t* t = zstore_tag_at(b->zst, e, s.iter)) *t = 0;  // (injected: not what any seed draws; store or ring slot)
       cap = (size_t)E.S * E.z_cols * 8;
       state_apply(b->st, StateEvent::write_normals);
       break;
@@ -1005,7 +1005,7 @@ int gpet_batch_set_rng(gpet_batch* b, int mode) {
   HIPCHK(c, gpet_wait(c->stream));
   if (b->side) HIPCHK(c, gpet_wait(b->side));
   b->rng_mode = mode;
-  zstore_clear_tags(b->zst);  // (the store's slots hold the other mode's numbers)
+  zstore_clear_tags(b->zst);  // (the store's and the ring's slots hold the other mode's numbers)
   state_apply(b->st, StateEvent::set_rng);
   return GPET_OK;
 }

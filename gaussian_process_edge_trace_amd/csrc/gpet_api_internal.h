@@ -106,6 +106,8 @@ struct ZGenLaunch {      // a generator launch of the loop whose effect the host
   int from, n;           // iterations [from, from + n)
   bool store;            // into store slots: their tags are set once it is certain the edge generated
   std::vector<int> idx;  // the batch's edges it ran for (empty: all of them)
+  bool keep = false;     // into ring slots, with ring tags kept: the slots get their tags when the launch is settled (zring_settle)
+  bool certain = false;  // ... and every stream of it was generated, whatever the edge's state afterwards
 };
 struct ZStore {
   bool decided = false;
@@ -113,6 +115,10 @@ struct ZStore {
   int iters = 0;
   size_t slot_bytes = 0, bytes = 0, alloc_bytes = 0;  // alloc_bytes >= bytes: a block taken over from a destroyed batch may be larger
   std::vector<uint64_t> tags;          // [B][iters]; 0: empty
+  // ring tags (gpet_zstore_plan.h): what the ring slot of iteration k >= iters, k % ring, holds.  No device memory: made by the
+  // batch's first gpet_trace_iterate with or without a store; ring == 0: none yet, or the edges' rings differ in length
+  std::vector<uint64_t> rtags;         // [B][ring]; 0: empty
+  int ring = 0;
   long long generated = 0;             // (edge, iteration) streams the loop generated for iterations the edge went on to run (gpet_batch_info)
   long long drawn = 0;                 // (edge, iteration) streams the loop's STORE launches generated, exactly: they always generate
   std::vector<ZGenLaunch> pending;
@@ -132,7 +138,16 @@ struct ZStore {
 void zstore_release(gpet_batch* b);
 void zstore_pool_drain();
 // empties every tag (what the slots would hold has changed, or may have been overwritten: gpet_batch_set_rng, the stage generators)
-static inline void zstore_clear_tags(ZStore& z) { std::fill(z.tags.begin(), z.tags.end(), (uint64_t)0); }
+static inline void zstore_clear_tags(ZStore& z) {
+  std::fill(z.tags.begin(), z.tags.end(), (uint64_t)0);
+  std::fill(z.rtags.begin(), z.rtags.end(), (uint64_t)0);
+}
+// the tag of the slot z_slot names for iteration `iter` of edge e, in the store or in the ring (nullptr: that slot has no tag)
+static inline uint64_t* zstore_tag_at(ZStore& z, int e, int iter) {
+  if (iter < 0) return nullptr;
+  if (iter < z.iters) return &z.tags[(size_t)e * z.iters + iter];
+  return z.ring > 0 ? &z.rtags[(size_t)e * z.ring + iter % z.ring] : nullptr;
+}
 
 struct gpet_batch {
   gpet_ctx* ctx = nullptr;

@@ -171,6 +171,8 @@ struct Loop {
   int B_l;
   int first = 0, horizon = 0;  // the group's iterations: first <= cur < horizon
   bool fit_used = false;       // the head of a small batch's normals put a launch on the fit stream (this group)
+  bool ring_keep = false;      // ring tags are kept by this call (zring_keep: an inline mode, normals_ring_keep != 0, one ring length)
+  bool table_running = false;  // the current table holds only edges the host has seen running (from the call's second group on)
   std::vector<unsigned char> miss_buf;  // per entry of the current table: it belongs to the store launch at hand
   std::vector<int> miss_lo, miss_hi;    // per entry of the current table: the store iterations it misses (zstore_misses)
 
@@ -208,11 +210,40 @@ struct Loop {
   // them), iterations [from, from + n).  The launch is noted and end_group settles it: a launch into the RING skips an edge whose
   // `done` flag is set when it runs, which the host does not know here; a launch into the store always generates (miss_table),
   // but its slots are tagged only once the group has come back without a device error.
+  // A launch into the ring empties the tags of the slots it may overwrite HERE, whatever the mode (a side-stream launch, or one
+  // under normals_ring_keep = 0, must not leave a stale tag behind for a later trace of the batch that keeps them); keep: its
+  // slots get their tags when it is settled, `certain`: for every stream, else for the iterations the edge went on to run.
   int generate(hipStream_t st, EdgeDev* tab, const unsigned int* seeds, const int* idx, int count, int from, int n, bool allow_chunked,
-               bool store) {
+               bool store, bool keep = false, bool certain = false) {
+    ZStore& z = b->zst;
+    if (!store && z.ring > 0) zring_clear(z.rtags.data(), z.ring, idx, count, from, n);
     int rc = normals_auto(b, st, tab, count, seeds, 1, from, n, loop_z_store(b), allow_chunked);
     if (rc) return rc;
-    b->zst.pending.push_back(ZGenLaunch{from, n, store, idx ? std::vector<int>(idx, idx + count) : std::vector<int>()});
+    z.pending.push_back(ZGenLaunch{from, n, store, idx ? std::vector<int>(idx, idx + count) : std::vector<int>(), keep, certain});
+    return GPET_OK;
+  }
+  // One launch on st per distinct range [miss_lo[i], miss_hi[i]] of the current table's entries (a cold trace, a new seed, an
+  // injected slot: one), each through a table of its own that always generates (miss_table); `left` = entries with a miss.
+  int generate_misses(hipStream_t st, int left, bool allow_chunked, bool store) {
+    for (int i0 = 0; i0 < B_l && left > 0; ++i0) {
+      const int lo = miss_lo[i0], hi = miss_hi[i0];
+      if (lo > hi) continue;
+      int count = 0;
+      for (int i = 0; i < B_l; ++i) {
+        miss_buf[i] = i >= i0 && miss_lo[i] == lo && miss_hi[i] == hi;
+        if (miss_buf[i]) {
+          count += 1;
+          miss_hi[i] = miss_lo[i] - 1;  // (taken)
+        }
+      }
+      left -= count;
+      EdgeDev* tab = nullptr;
+      unsigned int* sd = nullptr;
+      const int* idx = nullptr;
+      int rc = miss_table(st, miss_buf.data(), count, &tab, &sd, &idx);
+      if (!rc) rc = generate(st, tab, sd, idx, count, lo, hi - lo + 1, allow_chunked, store, !store, !store);
+      if (rc) return rc;
+    }
     return GPET_OK;
   }
   // A device table of the current table's entries with miss[i] set, for a launch on st into the store (ZStore: segments of one
@@ -261,39 +292,34 @@ struct Loop {
     return GPET_OK;
   }
   // The normals of iterations [from, from + n) on st, and their events.  The leading iterations that live in the store are
-  // generated only for the edges whose tags miss (no edge: no launch -- a trace repeated with the same seeds); the rest take the
-  // ring, one launch for the current table, as ever.
+  // generated only for the edges whose tags miss (no edge: no launch -- a trace repeated with the same seeds).  The rest take the
+  // ring.  Where ring tags are kept (the inline modes: st is the loop's own stream) the same holds for them; a table that misses
+  // the whole range throughout -- a cold trace -- gets its one launch for the current table as ever.  Elsewhere: that launch, always.
   int normals(hipStream_t st, int from, int n, bool allow_chunked = true) {
     ZStore& z = b->zst;
     const int n_st = zstore_span(from, n, z.iters);
+    miss_buf.resize((size_t)B_l);
+    miss_lo.resize((size_t)B_l);
+    miss_hi.resize((size_t)B_l);
     if (n_st > 0) {
-      miss_buf.resize((size_t)B_l);
-      miss_lo.resize((size_t)B_l);
-      miss_hi.resize((size_t)B_l);
-      int left = zstore_misses(z.tags.data(), z.iters, idx_l(), base_seeds, B_l, from, n_st, b->rng_mode, zs_l(), miss_lo.data(), miss_hi.data());
-      // one launch per distinct range of missing iterations (a cold trace, a new seed, an injected slot: one)
-      for (int i0 = 0; i0 < B_l && left > 0; ++i0) {
-        const int lo = miss_lo[i0], hi = miss_hi[i0];
-        if (lo > hi) continue;
-        int count = 0;
-        for (int i = 0; i < B_l; ++i) {
-          miss_buf[i] = i >= i0 && miss_lo[i] == lo && miss_hi[i] == hi;
-          if (miss_buf[i]) {
-            count += 1;
-            miss_hi[i] = miss_lo[i] - 1;  // (taken)
-          }
-        }
-        left -= count;
-        EdgeDev* tab = nullptr;
-        unsigned int* sd = nullptr;
-        const int* idx = nullptr;
-        int rc = miss_table(st, miss_buf.data(), count, &tab, &sd, &idx);
-        if (!rc) rc = generate(st, tab, sd, idx, count, lo, hi - lo + 1, allow_chunked, true);
-        if (rc) return rc;
-      }
+      const int left = zstore_misses(z.tags.data(), z.iters, idx_l(), base_seeds, B_l, from, n_st, b->rng_mode, zs_l(), miss_lo.data(), miss_hi.data());
+      int rc = generate_misses(st, left, allow_chunked, true);
+      if (rc) return rc;
     }
     if (n > n_st) {
-      int rc = generate(st, edges_l, seeds_l, idx_l(), B_l, from + n_st, n - n_st, allow_chunked, false);
+      const int rf = from + n_st, rn = n - n_st;
+      const bool keep = ring_keep && st == c->stream && rn <= z.ring;
+      int left = B_l;
+      bool whole = true;  // every entry misses all of [rf, rf + rn)
+      if (keep) {
+        left = zring_misses(z.rtags.data(), z.ring, idx_l(), base_seeds, B_l, rf, rn, b->rng_mode, zs_l(), miss_lo.data(), miss_hi.data());
+        for (int i = 0; i < B_l && whole; ++i) whole = miss_lo[i] == rf && miss_hi[i] == rf + rn - 1;
+      }
+      int rc = GPET_OK;
+      // (the launch lies before the kernels of iteration `from` on the loop's stream: at a group's first iteration, with a table of
+      //  edges the host has just seen running, no entry can have finished when it runs -- every stream is generated)
+      if (whole) rc = generate(st, edges_l, seeds_l, idx_l(), B_l, rf, rn, allow_chunked, false, keep, keep && table_running && from == first);
+      else rc = generate_misses(st, left, allow_chunked, false);
       if (rc) return rc;
     }
     for (int q = from; q < from + n; ++q) HIPCHK(c, hipEventRecord(b->ev_norm[q % 16], st));
@@ -317,6 +343,7 @@ struct Loop {
         if (g.store) z.drawn += g.n;  // (a store launch generates every stream it was enqueued for)
         if (g.store)
           for (int q = g.from; q < g.from + g.n && q < z.iters; ++q) z.tags[(size_t)e * z.iters + q] = zstore_loop_tag(base_seeds[e], q, mode, zs);
+        if (g.keep) zring_settle(z.rtags.data(), z.ring, e, base_seeds[e], g.from, g.n, s.done, s.iter, g.certain, mode, zs);
       }
     }
     z.pending.clear();
@@ -397,6 +424,7 @@ struct Loop {
     int rc = read_active(b, active);
     if (rc) return rc;
     settle_generated();
+    table_running = true;  // (the next group's table: all B edges if all are running, else the compacted one)
     EdgeProgress prog[64];  // (next_group looks at the edges of a batch of up to 64 only)
     const int count = b->B <= 64 && *active > 0 ? b->B : 0;
     if (count && (int)b->h_nobs_prev.size() != b->B) b->h_nobs_prev.assign(b->B, 0);
@@ -433,7 +461,15 @@ int gpet_trace_iterate(gpet_batch* b, const uint32_t* base_seeds, int max_iters,
   b->zst.pending.clear();  // (of a call that ended in an error: its slots stay untagged)
   b->zst.last_idx.clear();
   b->zst.used = 0;         // (every launch of the call before has completed: end_group waited for the three streams)
+  if (b->zst.rtags.empty()) {  // ring tags, once per batch: host memory only (edges whose rings differ in length: none)
+    bool one = b->bd.z_ring > 0 && b->bd.z_ring <= kZRingMax;
+    for (const EdgeDev& E : b->h_edges) one = one && E.z_ring == b->bd.z_ring;
+    b->zst.ring = one ? b->bd.z_ring : 0;
+    b->zst.rtags.assign((size_t)b->B * (size_t)(one ? b->bd.z_ring : 1), 0);
+  }
   Loop l{b, c, base_seeds, b->bd.z_ring, plan, b->d_edges, b->d_seeds, b->B};
+  l.ring_keep = zring_keep(opt(Opt::normals_ring_keep), plan.mode == NormalsMode::inline_per_iteration || plan.mode == NormalsMode::inline_per_group,
+                           b->zst.ring);
   // Groups of iterations (next_group): after every group the host reads the `done` flags, stops if no edge is left and otherwise
   // enqueues the next group for the edges still running.
   for (int remaining = max_iters, group = 8; remaining > 0 && group > 0;) {

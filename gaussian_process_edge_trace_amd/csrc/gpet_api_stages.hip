@@ -70,15 +70,16 @@ int gpet_gp_normals(gpet_batch* b, const uint32_t* seeds) {
   b->h_seeds_dev.assign(seeds, seeds + b->B);
   HIPCHK(c, launch_set_force(c->stream, b->d_edges, b->B, 0));
   HIPCHK(c, gpet_wait(c->stream));
-  if (b->zst.iters > 0) {
-    // the slot z_slot names at every edge's own iteration now holds the stream of the seed the caller named, every column of it:
-    // its tag says so (the loop finds it where seed + iteration + 1 is that seed).  An edge in an error state was skipped
+  if (b->zst.iters > 0 || b->zst.ring > 0) {
+    // the slot z_slot names at every edge's own iteration -- of the store or of the ring -- now holds the stream of the seed the
+    // caller named, every column of it: its tag says so (the loop finds it where seed + iteration + 1 is that seed).  An edge in
+    // an error state was skipped
     const int rcs = fetch_all_scalars(b);
     if (rcs) return rcs;
     for (int e = 0; e < b->B; ++e) {
       const gpet_scalars& s = b->h_scalars[e];
-      if (s.status == GPET_OK && s.iter >= 0 && s.iter < b->zst.iters)
-        b->zst.tags[(size_t)e * b->zst.iters + s.iter] = zstore_tag(seeds[e], b->rng_mode, b->bd.z_cols);
+      if (s.status != GPET_OK) continue;
+      if (uint64_t* t = zstore_tag_at(b->zst, e, s.iter)) *t = zstore_tag(seeds[e], b->rng_mode, b->bd.z_cols);
     }
   }
   state_apply(b->st, StateEvent::stage_normals);
@@ -232,17 +233,18 @@ int gpet_profile_stage(gpet_batch* b, int stage, int reps, float* ms_per_rep) {
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   *ms_per_rep = ms / (float)reps;
   const int rc_status = check_device_status(b);  // (reads every edge's state)
-  if (normals_profiled && b->zst.iters > 0) {
+  if (normals_profiled && (b->zst.iters > 0 || b->zst.ring > 0)) {
     // Stage 2 drew, for every running edge, the z_ring iterations from its own on by the loop's seed rule from the seeds on the
-    // device: the store slots among them hold exactly what the loop would draw there, so they get the loop's tags.  Without a host
-    // copy of those seeds, or after an error, the slots it may have written lose theirs.
+    // device: the store slots among them, and the ring slots of the others (z_ring iterations: z_ring distinct slots at most), hold
+    // exactly what the loop would draw there, so they get the loop's tags.  Without a host copy of those seeds, or after an error,
+    // the slots it may have written lose theirs.
     const int zsel = loop_z_store(b), zs = zsel > 0 && zsel < b->bd.z_cols ? zsel : b->bd.z_cols;
     const bool known = rc_status == GPET_OK && (int)b->h_seeds_dev.size() == b->B;
     for (int e = 0; e < b->B; ++e) {
       const gpet_scalars& s = b->h_scalars[e];
       if (known && (s.done || s.status != GPET_OK)) continue;  // (skipped by the generators: untouched)
-      for (int q = std::max(0, s.iter); q < s.iter + b->bd.z_ring && q < b->zst.iters; ++q)
-        b->zst.tags[(size_t)e * b->zst.iters + q] = known ? zstore_loop_tag(b->h_seeds_dev[e], q, b->rng_mode, zs) : 0;
+      for (int q = std::max(0, s.iter); q < s.iter + b->bd.z_ring; ++q)
+        if (uint64_t* t = zstore_tag_at(b->zst, e, q)) *t = known ? zstore_loop_tag(b->h_seeds_dev[e], q, b->rng_mode, zs) : 0;
     }
   }
   return rc_status;

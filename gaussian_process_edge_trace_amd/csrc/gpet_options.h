@@ -39,7 +39,8 @@ namespace gpet {
   X(struct_path, 1, 0, 1, "structured loop path (prior eigenbasis of the pixel grid) where it applies; 0: the generic kernels") \
   X(kde_variant, 1, 0, 1, "fused curve KDE of at most 128 kept curves: 1 = a tile's points stay in registers from the loads to the binning, weights once per edge, four workgroups per CU (k_kde_fused_r); 0 = points and weights staged in LDS by every tile (k_kde_fused: the cross-check, and the form of more curves)") \
   X(normals_store, -1, -1, 1, "normals store of a batch (read at its first trace): the normals of an edge's first iterations are kept, tagged with what drew them, and drawn again only where a tag does not match -- a trace repeated with the same seeds launches no generator; -1 = at least 8 iterations fit the budget (a quarter of the free device memory, outside the device's last eighth), 0 = never, 1 = whatever the budget allows") \
-  X(normals_store_iters, -1, -1, 32, "iterations per edge the normals store holds: -1 = 12, 0 = a budget of zero (no store), n = n iterations or as many as the budget holds")
+  X(normals_store_iters, -1, -1, 32, "iterations per edge the normals store holds: -1 = 12, 0 = a budget of zero (no store), n = n iterations or as many as the budget holds") \
+  X(normals_ring_keep, -1, -1, 1, "ring tags: the slots of the normals ring are tagged like the store's, so a trace repeated with the same seeds draws a ring iteration again only where its slot was overwritten since; -1 = on where the generator runs on the loop's stream (rng_inline 1 or 2), 0 = never (every trace draws its ring iterations), 1 = as -1 (reserved)")
 
 enum class Opt : int {
 #define GPET_OPT_ENUM(name, def, lo, hi, doc) name,

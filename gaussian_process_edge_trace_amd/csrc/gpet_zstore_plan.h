@@ -7,7 +7,8 @@
 // walks the same MT19937 streams again to store the same columns.  The store keeps the normals of an edge's first `store_iters`
 // iterations in slots of their own (one slot = one ring slot = 8 S z_cols bytes) with a TAG per (edge, iteration) that names what
 // produced the slot's contents; the loop generates only where a tag does not match, and the sample GEMM reads the slot (z_slot,
-// gpet_dev.h).  Iterations from store_iters on use the ring as ever.
+// gpet_dev.h).  Iterations from store_iters on take the ring, whose slots are tagged too (ring tags, below): where the generator
+// runs on the loop's own stream, a ring iteration is drawn again only if its slot has been overwritten since -- no memory added.
 #pragma once
 #include <stdint.h>
 
@@ -90,6 +91,61 @@ inline int zstore_misses(const uint64_t* tags, int store_iters, const int* edge_
     edges += lo[i] <= hi[i] ? 1 : 0;
   }
   return edges;
+}
+
+// ---- ring tags ----------------------------------------------------------------------------------------------------------------
+// The ring's slots carry tags of the same kind, [.][ring] per ORIGINAL edge: iteration k >= store_iters lies in slot k % ring, and
+// the tag of a slot names the iteration it holds (two iterations that share a slot have different effective seeds).  A tag is
+// CLEARED when a launch that may overwrite its slot is enqueued and SET once the launch is known to have generated (zring_settle),
+// so a tag never promises what the slot does not hold.  Launch ranges have n <= ring: no range meets a slot twice.
+constexpr int kZRingMax = 16;  // the longest ring a batch has (gpet_batch_plan.h: 2, 9 or 16 slots)
+
+inline int zring_slot(int iter, int ring) { return iter % ring; }
+
+// zstore_misses for the ring iterations [from, from + n) (from >= store_iters, n <= ring) of a launch table: [lo[i], hi[i]] = from
+// the first to the last iteration whose slot does not hold what edge i would draw there.  Returns the number of edges with a miss.
+inline int zring_misses(const uint64_t* rtags, int ring, const int* edge_idx, const uint32_t* base_seeds, int n_edges, int from, int n,
+                        int rng_mode, int zs, int* lo, int* hi) {
+  int edges = 0;
+  for (int i = 0; i < n_edges; ++i) {
+    const int e = edge_idx ? edge_idx[i] : i;
+    lo[i] = from + n;
+    hi[i] = from - 1;
+    for (int q = from; q < from + n; ++q)
+      if (rtags[(long long)e * ring + zring_slot(q, ring)] != zstore_loop_tag(base_seeds[e], q, rng_mode, zs)) {
+        if (q < lo[i]) lo[i] = q;
+        hi[i] = q;
+      }
+    edges += lo[i] <= hi[i] ? 1 : 0;
+  }
+  return edges;
+}
+
+// A launch for the ring iterations [from, from + n) of these edges has been enqueued: whatever their slots held is no longer promised
+// (n >= ring: every slot of the edge).
+inline void zring_clear(uint64_t* rtags, int ring, const int* edge_idx, int n_edges, int from, int n) {
+  const int m = n < ring ? n : ring;
+  for (int i = 0; i < n_edges; ++i) {
+    const int e = edge_idx ? edge_idx[i] : i;
+    for (int q = from; q < from + m; ++q) rtags[(long long)e * ring + zring_slot(q, ring)] = 0;
+  }
+}
+
+// The launch for the ring iterations [from, from + n) of edge e has come back without a device error; the edge's state is (done,
+// iter).  `certain`: every stream was generated -- a table whose entries never read `done`, or a launch enqueued before the first
+// iteration of a group whose table held running edges only.  Otherwise the generators skipped the edge once it had finished: only
+// the iterations it went on to run (those below its counter) are known to be there.
+inline void zring_settle(uint64_t* rtags, int ring, int e, uint32_t base_seed, int from, int n, int done, int iter, int certain,
+                         int rng_mode, int zs) {
+  int end = from + n;
+  if (!certain && done && iter < end) end = iter;
+  for (int q = from; q < end; ++q) rtags[(long long)e * ring + zring_slot(q, ring)] = zstore_loop_tag(base_seed, q, rng_mode, zs);
+}
+
+// option normals_ring_keep (-1 automatic, 0 never, 1 reserved = automatic): ring tags are kept where the generator's launches go
+// onto the loop's own stream (inline: rng_inline 1 or 2); the side-stream modes regenerate their ring iterations on every trace
+inline bool zring_keep(int normals_ring_keep, bool inline_mode, int ring) {
+  return normals_ring_keep != 0 && inline_mode && ring > 0 && ring <= kZRingMax;
 }
 
 }  // namespace gpet

@@ -468,7 +468,9 @@ int gpet_batch_image_count(const gpet_batch* b);
  * of pre-generated normals per edge), arena size of the batch in MiB, then the batch's normals store (options normals_store,
  * normals_store_iters; decided by the first gpet_trace_iterate): zstore_iters (iterations held per edge; 0: no store),
  * its size in MiB, normals_generated (the (edge, iteration) streams the loop has generated so far for iterations the edge
- * went on to run), normals_drawn (the streams the loop's launches into the store generated, exactly: they generate whatever
+ * went on to run; a trace repeated with the same seeds does not move it for the iterations the store holds, nor -- where the
+ * generator runs on the loop's own stream, option normals_ring_keep -- for ring iterations whose slots nothing has overwritten
+ * since), normals_drawn (the streams the loop's launches into the store generated, exactly: they generate whatever
  * the edge's `done` flag says, look-ahead included); both saturating */
 int gpet_batch_info(const gpet_batch* b, int e, int32_t* out, int count);
 
